@@ -7,7 +7,12 @@ One "step" = one pass of the hot path over one batch of synthetic input, per GPU
   2. R independent receding-horizon SCP solves (GuSTO on the Diamond TPWL ROM, r = 30, N = 50) started
      from the projected states, all inside ONE persistent kernel launch (sgusto_plan_solve_dev).
 `value` = SCP iterations (LOCP solves) per second summed over rollouts and ranks; inputs are resident in
-HBM before the timed region.  Rank 0 at N = 1 also times the CPU port (oracle/) on a bounded sample.
+HBM before the timed region.
+
+A plain run sets up, warms up, times --steps steps and prints the result line (`roofline` from the projection
+launches of those steps).  --full adds everything else: the secondary metrics, the layout A/B, the CPU port
+(oracle/) on a bounded sample with the parity sample (rank 0 at N = 1), the detail files.  --dump-outputs DIR
+writes what the last timed step computed (rank 0) as DIR/<name>.npy.
 """
 import argparse
 import ctypes as C
@@ -1073,6 +1078,29 @@ def emit(out, write_files=True):
     sys.stdout.flush()
 
 
+def _sample_rows(n, row_bytes, budget, seed):
+    """All n rows if they fit the byte budget, else a fixed seeded sample of them in ascending order."""
+    cap = max(1, budget // row_bytes)
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=cap, replace=False))
+
+
+def dump_outputs(path, proj, xopt, uopt, zopt, iters, status):
+    """--dump-outputs: what a caller of the timed path receives from its last step, float64, as <path>/<name>.npy -- the reduced
+    states of the projection (B x r) and, per rollout, the solution xopt / uopt / zopt, the SCP iteration count and the status.
+    Where the rows outgrow their budget (< 48 MB in all) a fixed seeded sample is written, with its row indices beside it."""
+    os.makedirs(path, exist_ok=True)
+    R_ = xopt.shape[0]
+    pi = _sample_rows(proj.shape[0], proj[0].nbytes, 24 << 20, seed=1)
+    ri = _sample_rows(R_, xopt[0].nbytes + uopt[0].nbytes + zopt[0].nbytes, 16 << 20, seed=2)
+    si = _sample_rows(R_, 16, 4 << 20, seed=3)
+    arrays = {'proj_reduced_states': proj[pi], 'proj_rows': pi, 'xopt': xopt[ri], 'uopt': uopt[ri], 'zopt': zopt[ri], 'solution_rollouts': ri,
+              'scp_iterations': iters[si], 'status': status[si], 'status_rollouts': si}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def stub_main(args, rank, world):
     """SRH_BENCH_STUB_DEVICE=1: the multi-rank skeleton of this file WITHOUT a GPU -- gloo instead of RCCL, a seeded stand-in
     for the solve -- so that the launcher, the 127.0.0.1 rendezvous, the barrier-bracketed timing with its max over ranks,
@@ -1122,7 +1150,10 @@ def stub_main(args, rank, world):
         dist.destroy_process_group()
 
 
-def main():
+def parse_args(argv=None):
+    """The command line and what it decides: a plain run measures the headline only -- no CPU baselines, no secondary metrics,
+    and the GuSTO constructor's own solve at the cap of the timed calls (`first_solve_cap`) instead of the reference-default 500
+    SCP iterations, whose throughput only `--full` reports (`secondary.scp_uncapped_500`)."""
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=3)
@@ -1132,11 +1163,26 @@ def main():
     ap.add_argument('--proj-launches', type=int, default=4, help='projection launches per step')
     ap.add_argument('--max-gusto-iters', type=int, default=5,
                     help='GuSTO iteration cap per solve (the reference default is 500; its real-time drivers use 0-5)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the secondary metrics (iLQR C3, Gramian C4)')
+    ap.add_argument('--full', action='store_true',
+                    help='also the secondary metrics, the layout A/B, the CPU baselines with the parity sample and the detail files '
+                         '(off: the headline figure only)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines and the parity sample')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full: skip the secondary metrics (iLQR C3, Gramian C4, ...)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (rank 0; seeded sample of the rollouts) as DIR/<name>.npy')
     ap.add_argument('--dry-launch', action='store_true',
                     help='with --gpus N > 1 and no WORLD_SIZE: print the per-rank environments / command lines and exit (no GPU call)')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be >= 1')
+    if not args.full:
+        args.no_cpu_baseline = args.no_secondary = True
+    args.first_solve_cap = None if args.full else args.max_gusto_iters
+    return args
+
+
+def main():
+    args = parse_args()
 
     # `python bench.py --gpus N` on its own (no torch.distributed.run around it): this process is only a launcher.  It
     # starts N fresh rank processes of this file BEFORE anything touches a GPU (no torch.cuda.*, no _lib.lib()), waits,
@@ -1202,15 +1248,18 @@ def main():
     t_ctor = time.perf_counter()
     gusto = GuSTO(gm, N, dt, w['Qz'], w['R'], x0, u_init, x_init, z=z, U=Polyhedron(w['UA'], w['Ub']),
                   X=Polyhedron(w['XA'], w['Xb']), x_char=xc, f_char=fc, convg_thresh=1e-3, batch=R_, max_trace=0,
-                  max_gusto_iters=args.max_gusto_iters)
+                  max_gusto_iters=args.max_gusto_iters, first_solve_cap=args.first_solve_cap)
     t_ctor = time.perf_counter() - t_ctor
-    # the constructor solves with the reference's default cap of 500 SCP iterations (gusto.py:142-147): its throughput is
-    # reported next to the capped (real-time iteration) headline; host buffers + plan creation inside this wall time
-    uncapped = {'what': 'GuSTO constructor: plan creation + one solve of the %d rollouts at the reference-default cap of 500 SCP '
-                        'iterations (trust-region-active QPs included), host buffers' % R_,
-                'seconds': t_ctor, 'scp_iterations': int(gusto.iters.sum()), 'max_iterations_of_a_rollout': int(gusto.iters.max()),
-                'scp_iterations_per_s': float(gusto.iters.sum()) / t_ctor, 'not_converged': int((gusto.status != 0).sum())}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    # with --full the constructor solves with the reference's default cap of 500 SCP iterations (gusto.py:142-147): its throughput
+    # is reported next to the capped (real-time iteration) headline; host buffers + plan creation inside this wall time.  A plain
+    # run caps that solve like the timed ones (solves are independent: the timed launches compute the same either way).
+    uncapped = None
+    if args.full:
+        uncapped = {'what': 'GuSTO constructor: plan creation + one solve of the %d rollouts at the reference-default cap of 500 SCP '
+                            'iterations (trust-region-active QPs included), host buffers' % R_,
+                    'seconds': t_ctor, 'scp_iterations': int(gusto.iters.sum()), 'max_iterations_of_a_rollout': int(gusto.iters.max()),
+                    'scp_iterations_per_s': float(gusto.iters.sum()) / t_ctor, 'not_converged': int((gusto.status != 0).sum())}
+    if uncapped is not None and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:      # the same uncapped solve on the host, all usable cores, bounded sample (the first 64 rollouts)
             from oracle import cpu_twin
             ncpu, nb = usable_cpus(), min(64, R_)
@@ -1274,8 +1323,12 @@ def main():
     status = o['status'].to_array((R_,), dtype=np.int32)
     kinfo = gusto.kernel_info          # the instantiation the timed launches ran + rollouts handed to the fused kernel in the last one
     n_par = min(R_, 512)         # the rollouts the CPU side may solve as well: GPU trajectories kept for `parity_sample`
-    gx = o['xopt'].to_array((R_, N + 1, n))[:n_par].copy()
-    gu = o['uopt'].to_array((R_, N, m))[:n_par].copy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dXr.to_array((B, r)), o['xopt'].to_array((R_, N + 1, n)), o['uopt'].to_array((R_, N, m)),
+                     o['zopt'].to_array((R_, N + 1, nz)), iters, status)
+    if not args.no_cpu_baseline:
+        gx = o['xopt'].to_array((R_, N + 1, n))[:n_par].copy()
+        gu = o['uopt'].to_array((R_, N, m))[:n_par].copy()
     it_per_step = int(iters.sum())
     total_iters = it_per_step * args.steps
     per_rank_ms = [elapsed / args.steps * 1e3]
@@ -1391,7 +1444,7 @@ def main():
                      'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic,
                      'avg_launch_ms': avg_ms, 'algorithmic_bytes_per_launch': alg_bytes, 'traffic_source': traffic_source},
     }
-    if sec is not None and isinstance(sec, dict):
+    if sec is not None and isinstance(sec, dict) and uncapped is not None:
         sec['scp_uncapped_500'] = uncapped
     if world == 1 and not args.no_cpu_baseline:
       try:
@@ -1428,7 +1481,7 @@ def main():
         out['cpu_baseline'] = {'error': repr(exc)}
     if sec is not None:
         out['secondary'] = sec
-    emit(out)
+    emit(out, write_files=args.full)
     if dist is not None:
         dist.destroy_process_group()
 

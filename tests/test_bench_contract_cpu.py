@@ -180,3 +180,53 @@ def test_compact_line_without_a_cpu_leg_and_with_failed_legs():
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype',
               'data', 'config', 'roofline', 'cpu_baseline'):
         assert k in d, k
+
+
+def test_plain_run_is_lean_and_full_is_an_option():
+    """What the command line decides (bench.parse_args): a plain run skips the CPU baselines and the secondary metrics and caps the
+    GuSTO constructor's own solve like the timed ones; --full restores all of it (the uncapped 500-iteration constructor solve
+    included) and --no-cpu-baseline / --no-secondary still narrow it.  --steps must be >= 1."""
+    import subprocess
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    plain = bench.parse_args(['--gpus', '1', '--steps', '7', '--warmup', '2'])
+    assert (plain.full, plain.no_cpu_baseline, plain.no_secondary) == (False, True, True)
+    assert plain.steps == 7 and plain.warmup == 2 and plain.dump_outputs is None
+    assert plain.first_solve_cap == plain.max_gusto_iters == 5
+    assert bench.parse_args(['--max-gusto-iters', '3']).first_solve_cap == 3
+    full = bench.parse_args(['--full'])
+    assert (full.no_cpu_baseline, full.no_secondary, full.first_solve_cap) == (False, False, None)
+    narrowed = bench.parse_args(['--full', '--no-cpu-baseline', '--no-secondary'])
+    assert (narrowed.no_cpu_baseline, narrowed.no_secondary, narrowed.first_solve_cap) == (True, True, None)
+    assert bench.parse_args(['--dump-outputs', 'd']).dump_outputs == 'd'
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], capture_output=True, text=True, timeout=120)
+    assert out.returncode != 0 and '--steps' in out.stderr
+
+
+def test_dump_outputs_writes_float_files_within_budget(tmp_path):
+    """--dump-outputs at the bench's shapes (65536 x 30 projection, 4096 rollouts of N = 50, n_x = 60, n_u = 4, 6 outputs): float64
+    .npy files, under 64 MB in all, the same seeded sample of rows on every call."""
+    import sys
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(0)
+    B, r, R, N, n, m, nz = 65536, 30, 4096, 50, 60, 4, 6
+    args = (rng.standard_normal((B, r)), rng.standard_normal((R, N + 1, n)), rng.standard_normal((R, N, m)),
+            rng.standard_normal((R, N + 1, nz)), rng.integers(0, 6, R).astype(np.int32), rng.integers(0, 3, R).astype(np.int32))
+    bench.dump_outputs(str(tmp_path / 'a'), *args)
+    bench.dump_outputs(str(tmp_path / 'b'), *args)
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == sorted(os.listdir(tmp_path / 'b')) and {'proj_reduced_states.npy', 'xopt.npy', 'uopt.npy', 'scp_iterations.npy'} <= set(files)
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) < 64 << 20
+    for f in files:
+        a, b = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b), f
+    ri = np.load(tmp_path / 'a' / 'solution_rollouts.npy').astype(int)
+    si = np.load(tmp_path / 'a' / 'status_rollouts.npy').astype(int)
+    pi = np.load(tmp_path / 'a' / 'proj_rows.npy').astype(int)
+    assert 0 < len(ri) < R and np.all(np.diff(ri) > 0) and np.array_equal(si, np.arange(R)) and np.array_equal(pi, np.arange(B))
+    for name, full, idx in (('xopt', args[1], ri), ('uopt', args[2], ri), ('zopt', args[3], ri), ('proj_reduced_states', args[0], pi),
+                            ('scp_iterations', args[4], si), ('status', args[5], si)):
+        assert np.array_equal(np.load(tmp_path / 'a' / (name + '.npy')), full[idx]), name

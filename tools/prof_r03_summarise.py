@@ -1,7 +1,7 @@
-"""Summaries of the rocprofv3 passes of tools/prof_r03.sh (gpurun_out/r03_*) -> small tracked JSON / CSV files under profiles/."""
+"""Summaries of the rocprofv3 passes of tools/prof_r03.sh ($PROF_OUT/r03_*, default prof_out/) -> small tracked JSON / CSV files under profiles/."""
 import csv, glob, json, os, shutil, statistics
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G, P = os.path.join(R, 'gpurun_out'), os.path.join(R, 'profiles')
+G, P = os.environ.get('PROF_OUT', os.path.join(R, 'prof_out')), os.path.join(R, 'profiles')
 
 
 def rows(pattern):
@@ -22,7 +22,7 @@ if tr:
     proj = [r for r in tr if r['Kernel_Name'].startswith('void (anonymous namespace)::proj_kernel<2, 0, true, true, false>')]
     big = [dur_ms(r) for r in proj if int(r.get('Grid_Size', r.get('Grid_Size_X', 0))) == 131072]
     alg = 8 * (65536 * 4884 + 4884 * 30 + 4884 + 65536 * 30)
-    out = {'source': 'rocprofv3 --kernel-trace of `python3 bench.py --no-cpu-baseline --steps 3 --warmup 1` (tools/prof_r03.sh); the launches of '
+    out = {'source': 'rocprofv3 --kernel-trace of `python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1` (tools/prof_r03.sh); the launches of '
                      'proj_kernel<2,0,true,true,false> with grid 131072 = the B = 65536 x n_f = 4884 x r = 30 projections of the bench step and of pod_shapes',
            'algorithmic_bytes_per_launch': alg, 'launches': len(big), 'ms': [round(x, 6) for x in big],
            'ms_mean': statistics.mean(big) if big else None, 'ms_median': statistics.median(big) if big else None,
@@ -71,7 +71,7 @@ if m:
         if 'SQ_VALU_MFMA_BUSY_CYCLES' in cnt and cnt.get('GRBM_GUI_ACTIVE', 0) > 0:
             res.setdefault(k, []).append({'dispatch': did, 'SQ_VALU_MFMA_BUSY_CYCLES': cnt['SQ_VALU_MFMA_BUSY_CYCLES'], 'GRBM_GUI_ACTIVE': cnt['GRBM_GUI_ACTIVE'],
                                           'mfma_busy_fraction': cnt['SQ_VALU_MFMA_BUSY_CYCLES'] / ((cnt['GRBM_GUI_ACTIVE'] / 8) * 256 * 4)})
-    json.dump({'source': 'rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace -- python3 bench.py --no-cpu-baseline --no-secondary --steps 1 --warmup 0',
+    json.dump({'source': 'rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace -- python3 bench.py --full --no-cpu-baseline --no-secondary --steps 1 --warmup 0',
                'formula': 'SQ_VALU_MFMA_BUSY_CYCLES / ((GRBM_GUI_ACTIVE / 8) * 256 CUs * 4 SIMDs)', 'kernels': res},
               open(os.path.join(P, 'r03_mfma_util.json'), 'w'), indent=1)
 for name in ('r03_bench_under_rocprof.log',):

@@ -1,9 +1,9 @@
-"""Summaries of the rocprofv3 passes of tools/prof_round.sh <tag> (gpurun_out/<tag>_*) -> small tracked JSON / CSV files under profiles/.
+"""Summaries of the rocprofv3 passes of tools/prof_round.sh <tag> ($PROF_OUT/<tag>_*, default prof_out/) -> small tracked JSON / CSV files under profiles/.
 Usage: python3 tools/prof_summarise.py r04   (prof_r03_summarise.py is this script frozen at the round-3 tag)."""
 import csv, glob, json, os, shutil, statistics, sys
 TAG = sys.argv[1] if len(sys.argv) > 1 else 'r04'
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G, P = os.path.join(R, 'gpurun_out'), os.path.join(R, 'profiles')
+G, P = os.environ.get('PROF_OUT', os.path.join(R, 'prof_out')), os.path.join(R, 'profiles')
 
 
 def rows(pattern):
@@ -24,7 +24,7 @@ if tr:
     proj = [r for r in tr if r['Kernel_Name'].startswith('void (anonymous namespace)::proj_kernel<2, 0, true, true, false>')]
     big = [dur_ms(r) for r in proj if int(r.get('Grid_Size', r.get('Grid_Size_X', 0))) == 131072]
     alg = 8 * (65536 * 4884 + 4884 * 30 + 4884 + 65536 * 30)
-    out = {'source': 'rocprofv3 --kernel-trace of `python3 bench.py --no-cpu-baseline --steps 3 --warmup 1` (tools/prof_round.sh); the launches of '
+    out = {'source': 'rocprofv3 --kernel-trace of `python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1` (tools/prof_round.sh); the launches of '
                      'proj_kernel<2,0,true,true,false> with grid 131072 = the B = 65536 x n_f = 4884 x r = 30 projections of the bench step and of pod_shapes',
            'algorithmic_bytes_per_launch': alg, 'launches': len(big), 'ms': [round(x, 6) for x in big],
            'ms_mean': statistics.mean(big) if big else None, 'ms_median': statistics.median(big) if big else None,
@@ -55,7 +55,7 @@ if tr:
         rows_out.append({'kernel': name, 'grid_threads': grid, 'workgroup': wgs, 'workgroups': grid // wgs if wgs else None, 'launches': len(v),
                          'ms_mean': statistics.mean(v), 'ms_median': statistics.median(v), 'ms_min': min(v), 'ms_max': max(v),
                          'ms_last_32': [round(x, 6) for x in v[-32:]]})
-    json.dump({'source': 'rocprofv3 --kernel-trace of `python3 bench.py --no-cpu-baseline --steps 3 --warmup 1` (tools/prof_round.sh): every launch of the POD kernels '
+    json.dump({'source': 'rocprofv3 --kernel-trace of `python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1` (tools/prof_round.sh): every launch of the POD kernels '
                          '(projection r = 30 / 36, both state forms; U^T M U = proj_kernel<..., true> + utmu_reduce_kernel; lift), grouped by instantiation and grid',
                'template_arguments': 'proj_kernel<NTF full 16-column tiles, NQ 4-column tiles, HAS_REF, VEC2, UTMU>; lift_kernel<KS, MT>',
                'algorithmic_bytes': {'project B=65536 r=30': 8 * (65536 * 4884 + 4884 * 30 + 4884 + 65536 * 30), 'project B=65536 r=36': 8 * (65536 * 4884 + 4884 * 36 + 4884 + 65536 * 36),
@@ -127,7 +127,7 @@ if m:
         if 'SQ_VALU_MFMA_BUSY_CYCLES' in cnt and cnt.get('GRBM_GUI_ACTIVE', 0) > 0:
             res.setdefault(k, []).append({'dispatch': did, 'SQ_VALU_MFMA_BUSY_CYCLES': cnt['SQ_VALU_MFMA_BUSY_CYCLES'], 'GRBM_GUI_ACTIVE': cnt['GRBM_GUI_ACTIVE'],
                                           'mfma_busy_fraction': cnt['SQ_VALU_MFMA_BUSY_CYCLES'] / ((cnt['GRBM_GUI_ACTIVE'] / 8) * 256 * 4)})
-    json.dump({'source': 'rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace -- python3 bench.py --no-cpu-baseline --no-secondary --steps 1 --warmup 0',
+    json.dump({'source': 'rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace -- python3 bench.py --full --no-cpu-baseline --no-secondary --steps 1 --warmup 0',
                'formula': 'SQ_VALU_MFMA_BUSY_CYCLES / ((GRBM_GUI_ACTIVE / 8) * 256 CUs * 4 SIMDs)', 'kernels': res},
               open(os.path.join(P, TAG + '_mfma_util.json'), 'w'), indent=1)
 for name in (TAG + '_bench_under_rocprof.log',):
@@ -167,7 +167,7 @@ if mix:
         der['icache_miss_rate'] = c.get('SQC_ICACHE_MISSES', 0) / c['SQC_ICACHE_REQ']
     if c.get('SQ_INSTS_MFMA'):
         der['mfma_flop_per_launch'] = c['SQ_INSTS_MFMA'] * 2048.0
-    json.dump({'source': 'rocprofv3 --pmc (separate passes, tools/prof_round.sh) over `python3 bench.py --no-cpu-baseline --no-secondary --steps 1 --warmup 0`; '
+    json.dump({'source': 'rocprofv3 --pmc (separate passes, tools/prof_round.sh) over `python3 bench.py --full --no-cpu-baseline --no-secondary --steps 1 --warmup 0`; '
                          'the timed 4096-rollout launch of the lean GuSTO kernel (largest dispatch of that kernel); SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_* count quad-cycles',
                'kernel': kernel, 'counters': counters, 'derived': der}, open(os.path.join(P, TAG + '_lean_instruction_mix.json'), 'w'), indent=1)
 print('summaries written')

@@ -5,9 +5,9 @@
 TAG=${1:?usage: bash tools/run_round.sh <tag, e.g. r05>}; export TAG
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/$TAG; mkdir -p $O
-timeout 2400 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; echo "pytest rc $?"; tail -3 $O/pytest_gpu.log
-timeout 900 python bench.py > $O/bench.log 2> $O/bench.err; echo "bench rc $?"
-bash tools/prof_round.sh $TAG > $O/prof_round.log 2>&1; echo "prof rc $?"; tail -2 $O/prof_round.log
+timeout -k 10 2400 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; rc=$?; echo "pytest rc $rc"; tail -3 $O/pytest_gpu.log; [ $rc -eq 0 ] || exit $rc
+timeout -k 10 900 python bench.py --full > $O/bench.log 2> $O/bench.err; rc=$?; echo "bench rc $rc"; [ $rc -eq 0 ] || exit $rc
+bash tools/prof_round.sh $TAG > $O/prof_round.log 2>&1; rc=$?; echo "prof rc $rc"; tail -2 $O/prof_round.log; [ $rc -eq 0 ] || exit $rc
 timeout 600 python tools/probes/lean_phase_clocks.py $O/lean_phase_clocks.json > $O/phase.log 2>&1
 python tools/probes/summarise_phase_clocks.py ${PHASE_RAW:-profiles/${TAG}a_lean_phase_clocks_raw.json} $O/lean_phase_clocks.json $O/${TAG}_lean_phase_clocks.json
 timeout 300 python tools/determinism_probe.py c2 > $O/determinism.log 2>&1; tail -3 $O/determinism.log
