@@ -378,6 +378,13 @@ int slocp_plan_solve_dev(slocp_plan_t *plan, const double *Ad_dev, const double 
                          const double *x0_dev, const double *xk_dev, const double *delta_dev, const double *omega_dev,
                          const double *z_dev, const double *zf_dev, const double *ud_dev, double *x_dev, double *u_dev,
                          double *s_dev, double *J_dev, int32_t *status_dev, int32_t *iters_dev, void *stream);
+/* The same with new_horizon = 0 for a horizon that has not changed since the previous call with the SAME Ad_dev / Bd_dev: the
+ * transposed copies of that call are reused (slocp_plan_solve_dev transposes the whole batch x N horizon on every call). */
+int slocp_plan_solve_dev_resident(slocp_plan_t *plan, int new_horizon, const double *Ad_dev, const double *Bd_dev,
+                                  const double *dd_dev, const double *x0_dev, const double *xk_dev, const double *delta_dev,
+                                  const double *omega_dev, const double *z_dev, const double *zf_dev, const double *ud_dev,
+                                  double *x_dev, double *u_dev, double *s_dev, double *J_dev, int32_t *status_dev,
+                                  int32_t *iters_dev, void *stream);
 
 /* Which kernels a plan launches -- for tests and bench records (parity is claimed per instantiation; what ran is otherwise
  * visible only in a rocprof trace).  family: 1 = the lean condensed kernel first (csrc/lean.hip) with the fused kernel
@@ -492,6 +499,55 @@ int sgusto_plan_solve_end(sgusto_plan_t *plan, double *xopt, double *uopt, doubl
  * to the last device-to-host copy on the plan's stream (HIP events) -- the solver's own time, what the reference reports
  * as its solve time (scp/ros.py:116-124), independent of when the caller came back for the result; -1 before the first. */
 int sgusto_plan_last_async_ms(sgusto_plan_t *plan, double *ms);
+
+/* =====================================================================================================
+ * Koopman baseline. reference: sofacontrol/baselines/koopman/koopman_utils.py, koopman/koopman.py, baselines/ros.py:139-235
+ * zeta = [y_t, y_{t-1} .. y_{t-d}, u_{t-1} .. u_{t-d}] of scaled samples (KoopmanData.get_zeta, koopman_utils.py:30-47;
+ * scale_down = (v - offset) / factor, 104-107), nzeta = n_y (d + 1) + m d; psi = the monomials of zeta of degree 1 .. degree
+ * in the order of get_lifting_function (koopman_utils.py:156-175: sympy grlex over the REVERSED variables), then the constant
+ * (dmd = 0) or no constant (dmd = 1); the lift writes W psi when W (n_w x n_psi) is given and is not the identity, else psi.
+ * Limits: nzeta <= 64, degree <= 4, n_psi <= 1024 (beyond them skoop_create fails with SRH_EINVAL).
+ * ===================================================================================================== */
+typedef struct skoop skoop_t;
+int skoop_num_observables(int nzeta, int degree, int dmd);                 /* n_psi (0 on bad arguments) */
+int skoop_exponents(int nzeta, int degree, int dmd, int32_t *exps);        /* (n_psi x nzeta), the constant row last unless dmd */
+/* KoopmanModel + KoopmanScaling: y_offset / y_factor (n_y), u_offset / u_factor (m); W (n_w x n_psi) or NULL; batch = the
+ * problems of the online ring (skoop_push) and of an MPC plan on this handle. */
+int skoop_create(skoop_t **out, int n_y, int m, int delays, int degree, int dmd, const double *y_offset, const double *y_factor,
+                 const double *u_offset, const double *u_factor, const double *W, int n_w, int64_t batch);
+int skoop_destroy(skoop_t *h);
+int skoop_info(skoop_t *h, int *nzeta, int *n_psi, int *n_out, int *has_w);   /* n_out = columns the lift writes */
+/* lift_data for rows of zeta (rows x nzeta) -> (rows x n_out) */
+int skoop_lift(skoop_t *h, const double *zeta, int64_t rows, double *out);
+int skoop_lift_dev(skoop_t *h, const double *zeta_dev, int64_t rows, double *out_dev, void *stream);
+/* add_zeta_offline (koopman_utils.py:75-83) + lift over a raw record y (T x n_y), u (T x m) (unscaled): row i - d for
+ * i = d .. T-1, so (T - d) x n_out rows; nothing when T < d + 1. */
+int skoop_embed_lift(skoop_t *h, const double *y, const double *u, int64_t T, double *out);
+int skoop_embed_lift_dev(skoop_t *h, const double *y_dev, const double *u_dev, int64_t T, double *out_dev, void *stream);
+/* Online ring (KoopmanData.add_measurement, 16-28): the last d + 1 scaled samples of every problem of the batch.  skoop_push
+ * takes y (batch x n_y), u (batch x m) through the handle's pinned block and is asynchronous on the handle's stream;
+ * skoop_ring_lift_dev writes the lift of the current zeta of every problem to out_dev (batch x n_out) on that stream. */
+int skoop_push(skoop_t *h, const double *y, const double *u);
+int skoop_reset(skoop_t *h);
+int skoop_state_dev(skoop_t *h, const double **ring_dev, int *slots, int *head, int64_t *count, void **stream);
+int skoop_ring_lift_dev(skoop_t *h, double *out_dev);
+/* Resident Koopman MPC (MPCSolverNode.mpc_callback, baselines/ros.py:202-235): an slocp plan of `batch` problems with
+ * A (n_x x n_x), B (n_x x n_u) tiled over the horizon once in HBM (d_d = 0) and prob->tr_active = 0, n_x = n_out.
+ * skoop_mpc_step: [push y, u_prev (both NULL: none)] -> lift the ring into the plan's x0 -> slocp_plan_solve_dev -> one copy
+ * of (x0, x, u, J, status) back, one synchronisation.  z (batch x (N+1) x n_z), zf (batch x n_z), u_des (batch x N x n_u):
+ * NULL keeps the last given (none given: no target).  x0 (batch x n_x) may be NULL. */
+typedef struct skoop_mpc skoop_mpc_t;
+int skoop_mpc_create(skoop_mpc_t **out, skoop_t *h, const slocp_problem *prob, const double *A, const double *B);
+int skoop_mpc_destroy(skoop_mpc_t *plan);
+int skoop_mpc_step(skoop_mpc_t *plan, const double *y, const double *u_prev, const double *z, const double *zf,
+                   const double *u_des, double *x0, double *x, double *u, double *J, int32_t *status);
+/* Step records for probes and tests.  skoop_mpc_set_timing(plan, 1) brackets the parts of every following step with HIP events on
+ * the handle's stream; skoop_mpc_stats then gives the steps taken, the blocking host waits the last step made (event or stream
+ * synchronisations, counted where they are made) and ms[4] of the last step: [step start .. QP launch] (push, targets, lift),
+ * [QP] (slocp_plan_solve_dev_resident: its transposes when the horizon is new, then the QP kernels), [results copied back],
+ * [whole step on the device]; -1 while timing is off. */
+int skoop_mpc_set_timing(skoop_mpc_t *plan, int on);
+int skoop_mpc_stats(skoop_mpc_t *plan, int64_t *steps, int64_t *waits_last_step, double *ms);
 
 #ifdef __cplusplus
 }

@@ -81,6 +81,7 @@ struct slocp_plan {
     int lean_args[6] = {0, 0, 0, 0, 0, 0};
     size_t lean_lds = 0;
     srh::DevBuf handed;
+    const double *dev_horizon_A = nullptr, *dev_horizon_B = nullptr;   // horizon of the last _dev call (transposed in dAT / dBT)
     srh::DevBuf dA, dAT, dB, dBT, dD, dx0, dxk, ddel, dom, dz, dzf, dud, ox, ou, os, oJ, ost, oit, work, dbg;
 };
 
@@ -227,6 +228,7 @@ int slocp_plan_solve(slocp_plan_t *pl, const double *Ad, const double *Bd, const
         return SRH_OK;
     };
     int rc;
+    if (new_horizon) pl->dev_horizon_A = pl->dev_horizon_B = nullptr;     // dAT / dBT now hold this horizon
     if (new_horizon && ((rc = up(pl->dA, Ad, D * B * N * n * n)) || (rc = up(pl->dB, Bd, D * B * N * n * m)) || (rc = up(pl->dD, dd, D * B * N * n)))) return rc;
     if ((rc = up(pl->dx0, x0, D * B * n)) || (rc = up(pl->ddel, delta, D * B)) || (rc = up(pl->dom, omega, D * B))) return rc;
     if (xk && (rc = up(pl->dxk, xk, D * B * (N + 1) * n))) return rc;
@@ -253,10 +255,21 @@ int slocp_plan_solve_dev(slocp_plan_t *pl, const double *Ad_dev, const double *B
                          const double *xk_dev, const double *delta_dev, const double *omega_dev, const double *z_dev, const double *zf_dev,
                          const double *ud_dev, double *x_dev, double *u_dev, double *s_dev, double *J_dev, int32_t *status_dev,
                          int32_t *iters_dev, void *stream) {
+    return slocp_plan_solve_dev_resident(pl, 1, Ad_dev, Bd_dev, dd_dev, x0_dev, xk_dev, delta_dev, omega_dev, z_dev, zf_dev, ud_dev, x_dev,
+                                         u_dev, s_dev, J_dev, status_dev, iters_dev, stream);
+}
+
+int slocp_plan_solve_dev_resident(slocp_plan_t *pl, int new_horizon, const double *Ad_dev, const double *Bd_dev, const double *dd_dev,
+                                  const double *x0_dev, const double *xk_dev, const double *delta_dev, const double *omega_dev,
+                                  const double *z_dev, const double *zf_dev, const double *ud_dev, double *x_dev, double *u_dev,
+                                  double *s_dev, double *J_dev, int32_t *status_dev, int32_t *iters_dev, void *stream) {
     SRH_REQUIRE(pl && Ad_dev && Bd_dev && dd_dev && x0_dev && delta_dev && omega_dev && x_dev && u_dev && J_dev && status_dev,
                 "slocp_plan_solve_dev: null argument");
     SRH_REQUIRE(!pl->C.dims.tr || xk_dev, "slocp_plan_solve_dev: xk is required when the trust region is active");
-    return slocp_plan_launch(pl, Ad_dev, Bd_dev, dd_dev, true, x0_dev, xk_dev ? xk_dev : pl->dxk.as<double>(), delta_dev, omega_dev, z_dev,
+    // the transposed horizon of the previous call is reused only for the same (unchanged) device arrays
+    const bool fresh = new_horizon || !pl->dev_horizon_A || pl->dev_horizon_A != Ad_dev || pl->dev_horizon_B != Bd_dev;
+    pl->dev_horizon_A = Ad_dev; pl->dev_horizon_B = Bd_dev;
+    return slocp_plan_launch(pl, Ad_dev, Bd_dev, dd_dev, fresh, x0_dev, xk_dev ? xk_dev : pl->dxk.as<double>(), delta_dev, omega_dev, z_dev,
                              zf_dev, ud_dev, x_dev, u_dev, s_dev ? s_dev : pl->os.as<double>(), J_dev, status_dev,
                              iters_dev ? iters_dev : pl->oit.as<int32_t>(), (hipStream_t)stream);
 }
