@@ -314,23 +314,9 @@ struct sgusto_plan {
 };
 
 namespace {
-// layout of the pinned staging block of a plan (byte offsets)
-struct PinLayout {
-    size_t x0, u_init, x_init, z, zf, ud, xopt, uopt, zopt, iters, status, trace, total;
-};
 PinLayout pin_layout(const sgusto_plan *pl) {
     const QPDims &d = pl->C.dims;
-    const size_t N = d.N, n = d.n, m = d.m, nz = d.nz, B = pl->batch, D = sizeof(double);
-    PinLayout L{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 63) & ~(size_t)63; return at; };
-    L.x0 = take(D * B * n); L.u_init = take(D * B * N * m); L.x_init = take(D * B * (N + 1) * n);
-    L.z = take(D * B * (N + 1) * nz); L.zf = take(D * B * nz); L.ud = take(D * B * N * m);
-    L.xopt = take(D * B * (N + 1) * n); L.uopt = take(D * B * N * m); L.zopt = take(D * B * (N + 1) * nz);
-    L.iters = take(sizeof(int32_t) * B); L.status = take(sizeof(int32_t) * B);
-    L.trace = take(D * B * (size_t)std::max(1, pl->par.max_trace) * 4);
-    L.total = o;
-    return L;
+    return pin_layout(d.N, d.n, d.m, d.nz, pl->batch, pl->par.max_trace, true);
 }
 }  // namespace
 
@@ -361,11 +347,10 @@ int sgusto_plan_create(sgusto_plan_t **out, stpwl_t *h, const slocp_problem *pro
     int rc = build_consts(&p2, pl->C, batch > 256);
     if (rc) { delete pl; return rc; }
     QPDims &d = pl->C.dims;
-    pl->par = GustoPar{par->delta0, par->omega0, par->rho, par->beta_fail, par->gamma_fail, par->epsilon,
-                       par->omega_max, par->convg_thresh, dt, par->max_gusto_iters, max_trace, 0,
-                       (getenv("SRH_LEAN_POISON_WARM") != nullptr ? 1 : 0) | (getenv("SRH_GUSTO_TRACE_QIT") != nullptr ? 2 : 0) | (getenv("SRH_LEAN_SERIAL_WAVE") != nullptr ? 4 : 0) |
-                       (getenv("SRH_LEAN_FORCE_HANDOVER") != nullptr ? (atoi(getenv("SRH_LEAN_FORCE_HANDOVER")) + 1) << 4 : 0),
-                       getenv("SRH_GUSTO_WARM_FULL") != nullptr ? 1 : 0};
+    pl->par = gusto_par(par, dt, max_trace);
+    pl->par.poison_warm |= (getenv("SRH_LEAN_POISON_WARM") != nullptr ? 1 : 0) | (getenv("SRH_LEAN_SERIAL_WAVE") != nullptr ? 4 : 0) |
+                           (getenv("SRH_LEAN_FORCE_HANDOVER") != nullptr ? (atoi(getenv("SRH_LEAN_FORCE_HANDOVER")) + 1) << 4 : 0);
+    pl->par.warm_full = getenv("SRH_GUSTO_WARM_FULL") != nullptr ? 1 : 0;
     const size_t N = d.N, n = d.n, m = d.m, nz = d.nz;
     size_t doubles = gusto_work(d).end;
     doubles = (doubles + 3) & ~(size_t)3;
@@ -446,20 +431,21 @@ int sgusto_plan_variant(const sgusto_plan_t *pl, int *split, int *n_u_fixed, int
 
 // phase 0: everything (lean launch + the fused kernel behind it for what the lean kernel hands over -- or the fused kernel alone);
 // phase 1: the lean launch alone, without the hand-over counter (the caller looks at the status words itself: zero-copy solves);
-// phase 2: the fused kernel in resume mode alone (after phase 1 found handed-over rollouts)
+// phase 2: the fused kernel in resume mode alone (after phase 1 found handed-over rollouts).
+// host_args: x0, z, zf, u_des sit in pinned host memory (zero-copy solves): the kernels work on copies in the work blocks
 static int solve_dev_impl(sgusto_plan_t *pl, const double *x0, const double *u_init, const double *x_init,
                           const double *z, const double *zf, const double *u_des, double *xopt, double *uopt,
-                          double *zopt, int32_t *iters, int32_t *status, double *trace, void *stream, int phase);
+                          double *zopt, int32_t *iters, int32_t *status, double *trace, void *stream, int phase, bool host_args);
 
 int sgusto_plan_solve_dev(sgusto_plan_t *pl, const double *x0, const double *u_init, const double *x_init,
                           const double *z, const double *zf, const double *u_des, double *xopt, double *uopt,
                           double *zopt, int32_t *iters, int32_t *status, double *trace, void *stream) {
-    return solve_dev_impl(pl, x0, u_init, x_init, z, zf, u_des, xopt, uopt, zopt, iters, status, trace, stream, 0);
+    return solve_dev_impl(pl, x0, u_init, x_init, z, zf, u_des, xopt, uopt, zopt, iters, status, trace, stream, 0, false);
 }
 
 static int solve_dev_impl(sgusto_plan_t *pl, const double *x0, const double *u_init, const double *x_init,
                           const double *z, const double *zf, const double *u_des, double *xopt, double *uopt,
-                          double *zopt, int32_t *iters, int32_t *status, double *trace, void *stream, int phase) {
+                          double *zopt, int32_t *iters, int32_t *status, double *trace, void *stream, int phase, bool host_args) {
     SRH_REQUIRE(pl && x0 && u_init && x_init && xopt && uopt && zopt && iters && status,
                 "sgusto_plan_solve_dev: null argument");
     if (phase == 0) pl->host_handed = -1;
@@ -468,7 +454,7 @@ static int solve_dev_impl(sgusto_plan_t *pl, const double *x0, const double *u_i
                 "sgusto_plan_solve_dev: an asynchronous request is in flight on this plan (call sgusto_plan_solve_end first)");
     GustoBatch b{x0, u_init, x_init, z, zf, u_des, pl->fs.as<double>(), xopt, uopt, zopt, iters, status, trace,
                  pl->work.as<double>(), pl->work_stride, nullptr, pl->last_iters.as<int32_t>(), 0, pl->handed.as<int32_t>(), pl->Jopt.as<double>(),
-                 phase != 0 ? 1 : 0};        // phases 1 / 2 = the zero-copy host path: pinned host arguments
+                 host_args ? 1 : 0};
     if (pl->have_last && pl->batch > 256 && pl->use_lpt) {      // more rollouts than CUs: order matters
         lpt_order_kernel<<<1, 1024, 0, (hipStream_t)stream>>>(pl->last_iters.as<int32_t>(), pl->batch, pl->order.as<int32_t>());
         b.order = pl->order.as<int32_t>();
@@ -561,19 +547,11 @@ int sgusto_plan_solve(sgusto_plan_t *pl, const double *x0, const double *u_init,
         }
         char *dp = nullptr;
         SRH_CHECK_HIP(hipHostGetDevicePointer((void **)&dp, pl->pin, 0));
-        const size_t D = sizeof(double);
-        memcpy(pl->pin + PL.x0, x0, D * B * n);
-        memcpy(pl->pin + PL.u_init, u_init, D * B * N * m);
-        memcpy(pl->pin + PL.x_init, x_init, D * B * (N + 1) * n);
-        if (z) memcpy(pl->pin + PL.z, z, D * B * (N + 1) * nz);
-        if (zf) memcpy(pl->pin + PL.zf, zf, D * B * nz);
-        if (u_des) memcpy(pl->pin + PL.ud, u_des, D * B * N * m);
-        auto dv = [&](size_t off) { return reinterpret_cast<double *>(dp + off); };
-        int32_t *st_host = reinterpret_cast<int32_t *>(pl->pin + PL.status);
+        const PinArgs P = pin_stage(PL, pl->pin, dp, x0, u_init, x_init, z, zf, u_des, trace != nullptr);
+        const int32_t *st_host = reinterpret_cast<const int32_t *>(pl->pin + PL.status);
         auto launch = [&](int phase) {
-            return solve_dev_impl(pl, dv(PL.x0), dv(PL.u_init), dv(PL.x_init), z ? dv(PL.z) : nullptr, zf ? dv(PL.zf) : nullptr,
-                                  u_des ? dv(PL.ud) : nullptr, dv(PL.xopt), dv(PL.uopt), dv(PL.zopt), reinterpret_cast<int32_t *>(dp + PL.iters),
-                                  reinterpret_cast<int32_t *>(dp + PL.status), trace ? dv(PL.trace) : nullptr, nullptr, phase);
+            return solve_dev_impl(pl, P.x0, P.u_init, P.x_init, P.z, P.zf, P.ud, P.xopt, P.uopt, P.zopt, P.iters, P.status, P.trace, nullptr,
+                                  phase, true);
         };
         int rc = launch(pl->lean ? 1 : 0);
         if (rc) return rc;
@@ -591,12 +569,7 @@ int sgusto_plan_solve(sgusto_plan_t *pl, const double *x0, const double *u_init,
             }
         }
         const auto t_sync = clk::now();
-        memcpy(xopt, pl->pin + PL.xopt, D * B * (N + 1) * n);
-        memcpy(uopt, pl->pin + PL.uopt, D * B * N * m);
-        memcpy(zopt, pl->pin + PL.zopt, D * B * (N + 1) * nz);
-        if (iters) memcpy(iters, pl->pin + PL.iters, sizeof(int32_t) * B);
-        if (status) memcpy(status, pl->pin + PL.status, sizeof(int32_t) * B);
-        if (trace) memcpy(trace, pl->pin + PL.trace, D * B * pl->par.max_trace * 4);
+        pin_copy_out(PL, pl->pin, xopt, uopt, zopt, iters, status, trace);
         if (trace_ms >= 0.0) {
             const auto ms = [](clk::time_point a, clk::time_point b2) { return std::chrono::duration<double, std::milli>(b2 - a).count(); };
             const auto t_out = clk::now();
@@ -722,15 +695,7 @@ int sgusto_plan_solve_end(sgusto_plan_t *pl, double *xopt, double *uopt, double 
     SRH_CHECK_HIP(hipEventSynchronize(pl->adone));
     pl->pending = false;
     { float ms = -1.0f; if (hipEventElapsedTime(&ms, pl->abegin, pl->adone) == hipSuccess) pl->last_ms = ms; else pl->last_ms = -1.0; }
-    const QPDims &d = pl->C.dims;
-    const size_t N = d.N, n = d.n, m = d.m, nz = d.nz, B = pl->batch, D = sizeof(double);
-    const PinLayout L = pin_layout(pl);
-    memcpy(xopt, pl->pin + L.xopt, D * B * (N + 1) * n);
-    memcpy(uopt, pl->pin + L.uopt, D * B * N * m);
-    memcpy(zopt, pl->pin + L.zopt, D * B * (N + 1) * nz);
-    if (iters) memcpy(iters, pl->pin + L.iters, sizeof(int32_t) * B);
-    if (status) memcpy(status, pl->pin + L.status, sizeof(int32_t) * B);
-    if (trace && pl->want_trace) memcpy(trace, pl->pin + L.trace, D * B * (size_t)pl->par.max_trace * 4);
+    pin_copy_out(pin_layout(pl), pl->pin, xopt, uopt, zopt, iters, status, pl->want_trace ? trace : nullptr);
     return SRH_OK;
 }
 

@@ -683,18 +683,9 @@ struct sgusto_ssm_plan {
 };
 
 namespace {
-struct SsmPin { size_t x0, u_init, x_init, z, ud, xopt, uopt, zopt, iters, status, trace, total; };
-SsmPin ssm_pin_layout(const sgusto_ssm_plan *pl) {
+PinLayout pin_layout(const sgusto_ssm_plan *pl) {
     const QPDims &d = pl->C.dims;
-    const size_t N = d.N, n = pl->n, m = d.m, nz = d.nz, B = pl->batch, D = sizeof(double);
-    SsmPin L;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o += (bytes + 63) & ~(size_t)63; return at; };
-    L.x0 = take(D * B * n); L.u_init = take(D * B * N * m); L.x_init = take(D * B * (N + 1) * n); L.z = take(D * B * (N + 1) * nz);
-    L.ud = take(D * B * N * m); L.xopt = take(D * B * (N + 1) * n); L.uopt = take(D * B * N * m); L.zopt = take(D * B * (N + 1) * nz);
-    L.iters = take(sizeof(int32_t) * B); L.status = take(sizeof(int32_t) * B); L.trace = take(D * B * (size_t)std::max(1, pl->max_trace) * 4);
-    L.total = o;
-    return L;
+    return pin_layout(d.N, pl->n, d.m, d.nz, pl->batch, pl->max_trace, false);
 }
 
 int ssm_gusto_launch(sgusto_ssm_plan *pl, const SsmGustoBatch &b, hipStream_t st) {
@@ -746,8 +737,7 @@ int sgusto_ssm_plan_create(sgusto_ssm_plan_t **out, sssm_t *model, const slocp_p
         const bool inst = (d.m == 4 && (gx == 1 || gx == 2)) || (d.m == 8 && gx == 1);
         pl->lean_gx = (shape && inst && !getenv("SRH_GUSTO_SSM_NO_LEAN")) ? gx : 0;
     }
-    pl->par = GustoPar{par->delta0, par->omega0, par->rho, par->beta_fail, par->gamma_fail, par->epsilon,
-                       par->omega_max, par->convg_thresh, dt, par->max_gusto_iters, max_trace, 0, getenv("SRH_GUSTO_TRACE_QIT") != nullptr ? 2 : 0, 0};
+    pl->par = gusto_par(par, dt, max_trace);
     const size_t n = model->n, nz = d.nz;
     size_t doubles = (ssm_gusto_work(d, (int)n).end + 3) & ~(size_t)3;
     d.qc_off = (long long)doubles;
@@ -790,7 +780,7 @@ int sgusto_ssm_plan_create(sgusto_ssm_plan_t **out, sssm_t *model, const slocp_p
         return rc;
     if (nX > 0 && ((rc = pl->XA.upload(XA, sizeof(double) * nX * n)) || (rc = pl->Xb.upload(Xb, sizeof(double) * nX)))) return rc;
     SRH_CHECK_HIP(hipMemset(pl->work.p, 0, sizeof(double) * pl->work_stride * batch));
-    const SsmPin PL = ssm_pin_layout(pl.get());
+    const PinLayout PL = pin_layout(pl.get());
     SRH_CHECK_HIP(hipHostMalloc((void **)&pl->pin, PL.total, hipHostMallocDefault));
     pl->pin_bytes = PL.total;
     *out = pl.release();
@@ -804,6 +794,14 @@ int sgusto_ssm_plan_destroy(sgusto_ssm_plan_t *pl) { delete pl; return SRH_OK; }
 int sgusto_ssm_plan_set_warm_across(sgusto_ssm_plan_t *pl, int on) {
     SRH_REQUIRE(pl, "sgusto_ssm_plan_set_warm_across: null plan");
     pl->par.warm_across = (on && (pl->lean_gx > 0 || pl->dense_u)) ? 1 : 0;
+    return SRH_OK;
+}
+
+/* Whether the plan honours sgusto_ssm_plan_set_warm_across: *active = 1 when it was requested and the plan's shape runs the lean one-wave
+ * interior point or the dense one-wave QP (the flag sgusto_ssm_plan_set_warm_across kept). */
+int sgusto_ssm_plan_warm_across_active(const sgusto_ssm_plan_t *pl, int *active) {
+    SRH_REQUIRE(pl && active, "sgusto_ssm_plan_warm_across_active: null argument");
+    *active = pl->par.warm_across;
     return SRH_OK;
 }
 
@@ -835,36 +833,23 @@ int sgusto_ssm_plan_solve_dev(sgusto_ssm_plan_t *pl, const double *x0, const dou
 int sgusto_ssm_plan_solve(sgusto_ssm_plan_t *pl, const double *x0, const double *u_init, const double *x_init, const double *z,
                           const double *u_des, double *xopt, double *uopt, double *zopt, int32_t *iters, int32_t *status, double *trace) {
     SRH_REQUIRE(pl && x0 && u_init && x_init && xopt && uopt && zopt, "sgusto_ssm_plan_solve: null argument");
-    const QPDims &d = pl->C.dims;
-    const size_t N = d.N, n = pl->n, m = d.m, nz = d.nz, B = pl->batch, D = sizeof(double);
-    const SsmPin PL = ssm_pin_layout(pl);
+    const PinLayout PL = pin_layout(pl);
     char *dp = nullptr;
     SRH_CHECK_HIP(hipHostGetDevicePointer((void **)&dp, pl->pin, 0));
-    memcpy(pl->pin + PL.x0, x0, D * B * n);
-    memcpy(pl->pin + PL.u_init, u_init, D * B * N * m);
-    memcpy(pl->pin + PL.x_init, x_init, D * B * (N + 1) * n);
-    if (z) memcpy(pl->pin + PL.z, z, D * B * (N + 1) * nz);
-    if (u_des) memcpy(pl->pin + PL.ud, u_des, D * B * N * m);
-    auto dv = [&](size_t off) { return reinterpret_cast<double *>(dp + off); };
     const bool want_trace = trace != nullptr && pl->max_trace > 0;
-    SsmGustoBatch b{dv(PL.x0), dv(PL.u_init), dv(PL.x_init), z ? dv(PL.z) : nullptr, u_des ? dv(PL.ud) : nullptr, pl->fs.as<double>(),
-                    pl->Hm.as<double>(), pl->nXv ? pl->XA.as<double>() : nullptr, pl->nXv ? pl->Xb.as<double>() : nullptr, pl->nXv,
-                    dv(PL.xopt), dv(PL.uopt), dv(PL.zopt), reinterpret_cast<int32_t *>(dp + PL.iters), reinterpret_cast<int32_t *>(dp + PL.status),
-                    want_trace ? dv(PL.trace) : nullptr, pl->work.as<double>(), pl->work_stride, pl->n, pl->mode, pl->Jopt.as<double>(), 1};
+    const PinArgs P = pin_stage(PL, pl->pin, dp, x0, u_init, x_init, z, nullptr, u_des, want_trace);
+    SsmGustoBatch b{P.x0, P.u_init, P.x_init, P.z, P.ud, pl->fs.as<double>(), pl->Hm.as<double>(), pl->nXv ? pl->XA.as<double>() : nullptr,
+                    pl->nXv ? pl->Xb.as<double>() : nullptr, pl->nXv, P.xopt, P.uopt, P.zopt, P.iters, P.status, P.trace, pl->work.as<double>(),
+                    pl->work_stride, pl->n, pl->mode, pl->Jopt.as<double>(), 1};
     GustoPar keep = pl->par;
     if (!want_trace) pl->par.max_trace = 0;
-    if (want_trace) for (size_t i = 0; i < B * (size_t)pl->max_trace * 4; ++i) reinterpret_cast<double *>(pl->pin + PL.trace)[i] = NAN;
+    if (want_trace) for (size_t i = 0; i < (size_t)pl->batch * pl->max_trace * 4; ++i) reinterpret_cast<double *>(pl->pin + PL.trace)[i] = NAN;
     const int rc = ssm_gusto_launch(pl, b, nullptr);
     pl->par = keep;
     if (rc) return rc;
     SRH_CHECK_HIP(hipStreamSynchronize(nullptr));
     pl->solved = true;
-    memcpy(xopt, pl->pin + PL.xopt, D * B * (N + 1) * n);
-    memcpy(uopt, pl->pin + PL.uopt, D * B * N * m);
-    memcpy(zopt, pl->pin + PL.zopt, D * B * (N + 1) * nz);
-    if (iters) memcpy(iters, pl->pin + PL.iters, sizeof(int32_t) * B);
-    if (status) memcpy(status, pl->pin + PL.status, sizeof(int32_t) * B);
-    if (want_trace) memcpy(trace, pl->pin + PL.trace, D * B * (size_t)pl->max_trace * 4);
+    pin_copy_out(PL, pl->pin, xopt, uopt, zopt, iters, status, want_trace ? trace : nullptr);
     return SRH_OK;
 }
 

@@ -18,6 +18,13 @@ struct GustoPar {
                                         // every omega x 5 -- so the default stays the cold start
 };
 
+// GustoPar of a plan from the API's parameters, with the one debug knob both GuSTO plans read (SRH_GUSTO_TRACE_QIT); the TPWL
+// plan ORs in its own test knobs
+inline GustoPar gusto_par(const sgusto_params *p, double dt, int max_trace) {
+    return GustoPar{p->delta0, p->omega0, p->rho, p->beta_fail, p->gamma_fail, p->epsilon, p->omega_max, p->convg_thresh, dt,
+                    p->max_gusto_iters, max_trace, 0, getenv("SRH_GUSTO_TRACE_QIT") != nullptr ? 2 : 0, 0};
+}
+
 struct GustoBatch {
     const double *x0, *u_init, *x_init, *z, *zf, *ud;
     const double *fs;                   // 1/|f_char| (n)
@@ -68,6 +75,61 @@ __host__ __device__ inline GustoWork gusto_work(const QPDims &d) {
     g.udc = g.zfc + d.nz;
     g.end = g.udc + N * m;
     return g;
+}
+
+// The pinned, device-visible block of a GuSTO plan's zero-copy solves, [inputs | outputs]: byte offsets (64-byte aligned) and the
+// extents they were made for.  has_zf = false (the SSM plan): no terminal target.
+struct PinLayout {
+    size_t x0, u_init, x_init, z, zf, ud, xopt, uopt, zopt, iters, status, trace, total;
+    size_t N, n, m, nz, B;
+    int max_trace;
+};
+inline PinLayout pin_layout(size_t N, size_t n, size_t m, size_t nz, size_t B, int max_trace, bool has_zf) {
+    const size_t D = sizeof(double);
+    PinLayout L{};
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 63) & ~(size_t)63; return at; };
+    L.x0 = take(D * B * n); L.u_init = take(D * B * N * m); L.x_init = take(D * B * (N + 1) * n);
+    L.z = take(D * B * (N + 1) * nz); L.zf = take(has_zf ? D * B * nz : 0); L.ud = take(D * B * N * m);
+    L.xopt = take(D * B * (N + 1) * n); L.uopt = take(D * B * N * m); L.zopt = take(D * B * (N + 1) * nz);
+    L.iters = take(sizeof(int32_t) * B); L.status = take(sizeof(int32_t) * B);
+    L.trace = take(D * B * (size_t)std::max(1, max_trace) * 4);
+    L.total = o;
+    L.N = N; L.n = n; L.m = m; L.nz = nz; L.B = B; L.max_trace = max_trace;
+    return L;
+}
+
+// device addresses of the staged arguments and of the results (null where the caller passed none)
+struct PinArgs {
+    const double *x0, *u_init, *x_init, *z, *zf, *ud;
+    double *xopt, *uopt, *zopt, *trace;
+    int32_t *iters, *status;
+};
+// the caller's arguments -> the pinned block `pin`, whose device address is dp
+inline PinArgs pin_stage(const PinLayout &L, char *pin, char *dp, const double *x0, const double *u_init, const double *x_init,
+                         const double *z, const double *zf, const double *ud, bool trace) {
+    const size_t D = sizeof(double), N = L.N, n = L.n, m = L.m, nz = L.nz, B = L.B;
+    memcpy(pin + L.x0, x0, D * B * n);
+    memcpy(pin + L.u_init, u_init, D * B * N * m);
+    memcpy(pin + L.x_init, x_init, D * B * (N + 1) * n);
+    if (z) memcpy(pin + L.z, z, D * B * (N + 1) * nz);
+    if (zf) memcpy(pin + L.zf, zf, D * B * nz);
+    if (ud) memcpy(pin + L.ud, ud, D * B * N * m);
+    auto dv = [&](size_t off) { return reinterpret_cast<double *>(dp + off); };
+    return PinArgs{dv(L.x0), dv(L.u_init), dv(L.x_init), z ? dv(L.z) : nullptr, zf ? dv(L.zf) : nullptr, ud ? dv(L.ud) : nullptr,
+                   dv(L.xopt), dv(L.uopt), dv(L.zopt), trace ? dv(L.trace) : nullptr,
+                   reinterpret_cast<int32_t *>(dp + L.iters), reinterpret_cast<int32_t *>(dp + L.status)};
+}
+// the results out of the pinned block (iters, status, trace: null = not wanted)
+inline void pin_copy_out(const PinLayout &L, const char *pin, double *xopt, double *uopt, double *zopt, int32_t *iters, int32_t *status,
+                         double *trace) {
+    const size_t D = sizeof(double), N = L.N, n = L.n, m = L.m, nz = L.nz, B = L.B;
+    memcpy(xopt, pin + L.xopt, D * B * (N + 1) * n);
+    memcpy(uopt, pin + L.uopt, D * B * N * m);
+    memcpy(zopt, pin + L.zopt, D * B * (N + 1) * nz);
+    if (iters) memcpy(iters, pin + L.iters, sizeof(int32_t) * B);
+    if (status) memcpy(status, pin + L.status, sizeof(int32_t) * B);
+    if (trace) memcpy(trace, pin + L.trace, D * B * (size_t)L.max_trace * 4);
 }
 
 }  // namespace

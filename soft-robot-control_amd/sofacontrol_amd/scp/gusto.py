@@ -159,13 +159,13 @@ class GuSTO:
 
     @property
     def solver_state_kept(self):
-        """True when keep_solver_state was requested AND the plan's kernels honour it (sgusto_plan_warm_across_active)."""
+        """True when keep_solver_state was requested AND the plan's kernels honour it (sgusto_plan_warm_across_active,
+        sgusto_ssm_plan_warm_across_active)."""
         if not self.keep_solver_state or not self._fused:
             return False
-        if self._ssm:
-            return True
+        name = 'sgusto_ssm_plan_warm_across_active' if self._ssm else 'sgusto_plan_warm_across_active'
         a = C.c_int(0)
-        _lib.check(_lib.lib().sgusto_plan_warm_across_active(self._plan, C.byref(a)), 'sgusto_plan_warm_across_active')
+        _lib.check(getattr(_lib.lib(), name)(self._plan, C.byref(a)), name)
         return bool(a.value)
 
     @property
@@ -265,18 +265,23 @@ class GuSTO:
         return H_d, c_d
 
     # ---- solve
+    def _batch_args(self, x0, u_init, x_init, z, zf, u):
+        """The six arguments of a batched solve as contiguous float64 arrays of the plan's shapes (z, zf, u: None stays None; zf also
+        without a terminal cost)."""
+        B, N, n, m, nz = self.batch, self.N, self.n_x, self.n_u, self.n_z
+        f = _lib.f64
+        return (f(np.asarray(x0).reshape(B, n)), f(np.asarray(u_init).reshape(B, N, m)), f(np.asarray(x_init).reshape(B, N + 1, n)),
+                None if z is None else f(np.asarray(z).reshape(B, N + 1, nz)),
+                None if (zf is None or self.Qzf is None) else f(np.asarray(zf).reshape(B, nz)),
+                None if u is None else f(np.asarray(u).reshape(B, N, m)))
+
     def solve_batch(self, x0, u_init, x_init, z=None, zf=None, u=None):
         """`batch` independent rollouts in one launch: x0 (B,n_x), u_init (B,N,n_u), x_init (B,N+1,n_x),
         z (B,N+1,n_z) ..."""
         if not self._fused:
             raise RuntimeError('solve_batch needs a TPWLGuSTO or SSMGuSTO model (a resident device plan)')
         B, N, n, m, nz = self.batch, self.N, self.n_x, self.n_u, self.n_z
-        f = _lib.f64
-        x0 = f(np.asarray(x0).reshape(B, n)); u_init = f(np.asarray(u_init).reshape(B, N, m))
-        x_init = f(np.asarray(x_init).reshape(B, N + 1, n))
-        z = None if z is None else f(np.asarray(z).reshape(B, N + 1, nz))
-        zf = None if (zf is None or self.Qzf is None) else f(np.asarray(zf).reshape(B, nz))
-        u = None if u is None else f(np.asarray(u).reshape(B, N, m))
+        x0, u_init, x_init, z, zf, u = self._batch_args(x0, u_init, x_init, z, zf, u)
         xo = np.empty((B, N + 1, n)); uo = np.empty((B, N, m)); zo = np.empty((B, N + 1, nz))
         iters = np.empty(B, dtype=np.int32); status = np.empty(B, dtype=np.int32)
         trace = np.full((B, self.max_trace, 4), np.nan) if self.max_trace > 0 else None
@@ -307,13 +312,7 @@ class GuSTO:
         `solve_end()` waits and installs the result like `solve` does.  (scp/ros.py:183-223 `send_request(wait=False)`.)"""
         if not self._fused or self._ssm:
             raise RuntimeError('asynchronous solves need the fused TPWL plan')
-        B, N, n, m, nz = self.batch, self.N, self.n_x, self.n_u, self.n_z
-        f = _lib.f64
-        x0 = f(np.asarray(x0).reshape(B, n)); u_init = f(np.asarray(u_init).reshape(B, N, m))
-        x_init = f(np.asarray(x_init).reshape(B, N + 1, n))
-        z = None if z is None else f(np.asarray(z).reshape(B, N + 1, nz))
-        zf = None if (zf is None or self.Qzf is None) else f(np.asarray(zf).reshape(B, nz))
-        u = None if u is None else f(np.asarray(u).reshape(B, N, m))
+        x0, u_init, x_init, z, zf, u = self._batch_args(x0, u_init, x_init, z, zf, u)
         _lib.check(_lib.lib().sgusto_plan_set_max_iters(self._plan, C.c_int(int(self.max_gusto_iters))), 'set_max_iters')
         self._t_begin = time.time()
         _lib.check(_lib.lib().sgusto_plan_solve_begin(self._plan, _lib.dptr(x0), _lib.dptr(u_init), _lib.dptr(x_init),

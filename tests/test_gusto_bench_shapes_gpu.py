@@ -374,6 +374,36 @@ def test_handed_over_zero_copy_solve_is_not_slower_than_the_copying_form(monkeyp
     assert ms['zero_copy'] <= 1.3 * ms['copying'], ms
 
 
+def test_fused_only_zero_copy_solve_equals_the_copying_form(monkeypatch):
+    """A plan without the lean kernel (SRH_GUSTO_NO_LEAN=1) solves small batches zero-copy too: the fused kernel works on copies of x0 / z /
+    zf / u_des in its work block (GustoBatch::host_args, set by the zero-copy path for every launch).  Two C2 rollouts at the reference's
+    default cap of 500 SCP iterations, traces on: the zero-copy and the copying form (SRH_GUSTO_NO_ZEROCOPY=1) return the same solve, bit
+    for bit."""
+    import workloads as wl
+    from sofacontrol_amd.scp.gusto import GuSTO
+    from sofacontrol_amd.utils import Polyhedron
+    w = wl.diamond_c2()
+    gm, xc, fc, x0, u_init, x_init, z = problem(w, 2, 2, 1354)
+    monkeypatch.setenv('SRH_GUSTO_NO_LEAN', '1')
+    g = GuSTO(gm, w['N'], w['dt'], w['Qz'], w['R'], x0, u_init, x_init, z=z, U=Polyhedron(w['UA'], w['Ub']), X=Polyhedron(w['XA'], w['Xb']),
+              x_char=xc, f_char=fc, convg_thresh=1e-3, batch=2, max_trace=64, max_gusto_iters=500)
+    monkeypatch.delenv('SRH_GUSTO_NO_LEAN', raising=False)
+    assert g.kernel_info['family'] == 'fused'
+    out = {}
+    for tag in ('zero_copy', 'copying'):
+        if tag == 'copying':
+            monkeypatch.setenv('SRH_GUSTO_NO_ZEROCOPY', '1')
+        g.solve_batch(x0, u_init, x_init, z=z)
+        out[tag] = (g.iters.copy(), g.status.copy(), g.xopt.copy(), g.uopt.copy(), g.zopt.copy(), g.trace.copy())
+    monkeypatch.delenv('SRH_GUSTO_NO_ZEROCOPY', raising=False)
+    iters = out['zero_copy'][0]
+    assert (iters > 1).all()
+    for a, b in zip(out['zero_copy'][:5], out['copying'][:5]):
+        np.testing.assert_array_equal(a, b)
+    for r in range(2):                              # (the rows past a rollout's iterations are not written by its solve)
+        np.testing.assert_array_equal(out['zero_copy'][5][r, :iters[r]], out['copying'][5][r, :iters[r]])
+
+
 @pytest.mark.parametrize('delta0', [1.0, 4.0])
 def test_binding_trust_region_qps_follow_the_oracle(delta0, monkeypatch):
     """QPs whose trust region BINDS, chosen rather than waited for: with delta0 = 1 or 4 (instead of the reference's 1e4, gusto.py:142-147)

@@ -134,17 +134,17 @@ def test_gusto_ssm_nonlinear_observer(with_X, path, monkeypatch):
     close(got[:, :3], np.asarray(tr)[:, :3], 1e-6)
 
 
-@pytest.mark.parametrize('qp', ['dense', 'fused'])
+@pytest.mark.parametrize('qp', ['dense', 'qp_solve'])
 def test_gusto_ssm_three_cost_outputs_follow_the_oracle(qp, monkeypatch):
     """The cost of the reference's SSM hardware driver weighs THREE outputs (examples/hardware/diamond_SSM.py:322-326): no p_o = 2 output
     space for the lean one-wave interior point.  `dense`: the QP in the space of the inputs on one wave (csrc/locp_dense_u.h: N n_u <= 16);
-    `fused`: qp::solve (SRH_GUSTO_SSM_NO_DENSE=1).  n_x = 6, n_u = 4, N = 3, U box, up to 4 SCP iterations: iteration counts, (J, delta,
-    omega) trace and trajectories of oracle.gusto.solve_generic; with the solver state kept between solves the second solve of the same
-    problem returns the same plan."""
+    `qp_solve`: qp::solve (SRH_GUSTO_SSM_NO_DENSE=1).  n_x = 6, n_u = 4, N = 3, U box, up to 4 SCP iterations: iteration counts, (J,
+    delta, omega) trace and trajectories of oracle.gusto.solve_generic; keep_solver_state is honoured on the one-wave route only
+    (GuSTO.solver_state_kept), and either way the second solve of the same problem returns the same plan."""
     from sofacontrol_amd.scp.models.ssm import SSMGuSTO
     from sofacontrol_amd.scp.gusto import GuSTO
     from sofacontrol_amd.utils import HyperRectangle
-    if qp == 'fused':
+    if qp == 'qp_solve':
         monkeypatch.setenv('SRH_GUSTO_SSM_NO_DENSE', '1')
     n, m, N, dt = 6, 4, 3, 0.02
     model = ossm.synthetic(n, m, 3, 2, seed=96)
@@ -159,7 +159,9 @@ def test_gusto_ssm_three_cost_outputs_follow_the_oracle(qp, monkeypatch):
     z = np.tile(ossm.observe(model, x0) + np.array([0.02, -0.01, 0.015, 0, 0, 0]), (N + 1, 1))
     U = HyperRectangle([3.0] * m, [-1.0] * m)
     g = GuSTO(gm, N, dt, Qz, R, x0, u_init, x_init, z=z, U=U, verbose=0, max_gusto_iters=4, convg_thresh=1e-5, keep_solver_state=True)
-    assert g._ssm and g.solver_state_kept
+    assert g._ssm
+    # only the one-wave routes keep the solver state: `qp_solve` has neither the dense one-wave QP nor (three outputs) the lean one
+    assert g.solver_state_kept == (qp == 'dense')
     xo, uo, _, tr = ogusto.solve_generic(lambda x, u: ossm.jacobians(model, x, u, dt, 'be'),
                                          lambda x, u: (lambda A, B, d: (A @ x + B @ u + d, A, B))(*ossm.continuous_jacobians(model, x, u)),
                                          np.zeros((n, n)), N, dt, Qz, R, x0, u_init, x_init, z=z, U=(U.A, U.b),
