@@ -92,6 +92,13 @@ __host__ __device__ inline size_t lds_doubles(const QPDims &d, int nthreads, int
 }
 // doubles of the half-size layout's homes in the L2 block behind the packed G: [pad (YPAD) | yf (16 KT) | goff (N ints)]
 __host__ __device__ inline size_t half_l2_off(const QPDims &d) { return (size_t)goff(d.N, d.m, d.N * d.po) + 48; }
+// first stage whose packed rows, with those of every later stage, fit the K-tile area (what a staged Gram fill reads from LDS)
+__host__ __device__ inline int gram_stage_j0(const QPDims &d) {
+    const int NP = d.N * d.po, cap = d.KT * (d.KT + 1) / 2 * TSZ;
+    int j = 0;
+    while (goff(d.N, d.m, NP) - goff(j, d.m, NP) > cap) ++j;
+    return j;
+}
 __device__ inline void lds_carve(Lds &L, lptr base, const QPDims &d, int nthreads, gptr work_base = nullptr) {
     const Sizes s = sizes(d, nthreads, d.lean_j0);
     const bool half = d.lean_half != 0;
@@ -629,8 +636,16 @@ __device__ __forceinline__ void gT_times(const QPDims &d, const GP &g, Lds &L, c
 #ifdef SRH_PROFILE
 __device__ long long g_prof_waves[16];         // per-wave clocks of the Gram fill (products, epilogue), cumulative over the launch's workgroup 0
 #endif
-template <int MSEL, class GP>
-__device__ __forceinline__ void gram(const QPDims &d, const QPConst &c, const GP &g, Lds &L) {
+// STAGE (the half-size layout, where every packed row has its home in the L2 block): the K-tile area L.B is dead when a Gram fill
+// starts -- the factor of the iteration before has been used, every tile is rewritten here -- so the rows of the stages >= g.j0 are
+// copied into it once (g.gt == L.B, from gsrc) and the tiles read them from LDS instead of once per tile row and column they meet
+// from L2.  The tiles walk the stages in the same ascending order: same bits.  An epilogue must not write a tile into L.B while
+// another wave still reads staged rows there: the accumulators of ALL tiles of a wave stay in registers (GRAM_SLOTS tasks of at most
+// 4, 3, 1 tiles: 8 accumulators), one barrier, then the epilogues.  Register arrays want compile-time indices, so the tasks are not
+// pulled here: c.gram_sched is the static table [wave][slot] of scp_host.h:lean_gram_slots.
+constexpr int GRAM_SLOTS = 3;          // per wave of a staged Gram fill: {I, J0, nJ, 0} with nJ <= 4, 3, 1 (nJ = 0: slot not used)
+template <int MSEL, bool STAGE, class GP>
+__device__ __forceinline__ void gram_t(const QPDims &d, const QPConst &c, const GP &g, Lds &L, cgptr gsrc = nullptr) {
     static_assert(MSEL == 4 || MSEL == 8, "lean Gram: n_u = 4 or 8");
     constexpr int M = MSEL, SPS = M / 4;                       // k-steps per stage
     const int N = d.N, KT = d.KT, NP = g.NP;
@@ -653,18 +668,20 @@ __device__ __forceinline__ void gram(const QPDims &d, const QPConst &c, const GP
     if (tid < GRAM_TASKS * 4) tl[4 + tid] = c.gram_sched[tid];
     if (tid == 0) tl[0] = 0;
     for (int e = tid; e < N * M; e += nt) { const double s = L.Ldi[e]; w2[e] = s * s; }
+    if constexpr (STAGE) {                                     // (packed offsets of a stage are multiples of 4: 16-byte pieces)
+        const int nq = (goff(N, M, NP) - goff0) >> 1;
+        const double2 *s2 = (const double2 *)(gsrc + goff0);
+        double2 *d2 = (double2 *)(lptr)g.gt;
+#pragma unroll 4
+        for (int e = tid; e < nq; e += nt) d2[e] = s2[e];
+    }
     __syncthreads();
     GR_LAP(0);
-    while (true) {
-        int tnext = 0;
-        if (lane == 0) tnext = __hip_atomic_fetch_add(tl, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        tnext = __builtin_amdgcn_readfirstlane(tnext);
-        if (tnext >= GRAM_TASKS) break;
-        const int I = __builtin_amdgcn_readfirstlane(tl[4 + 4 * tnext]), J0 = __builtin_amdgcn_readfirstlane(tl[5 + 4 * tnext]),
-                  nJ = __builtin_amdgcn_readfirstlane(tl[6 + 4 * tnext]);
-        GR_LAP(1);
-        if (nJ == 0) break;
-        wg::qp_d4 acc[4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
+    constexpr int NACC = STAGE ? 8 : 4;
+    wg::qp_d4 acc[NACC];
+    // ---- the products of one task: tiles (I, J0 .. J0 + nJ - 1) into acc[BASE ..], nJ <= CAP
+    auto products = [&](int I, int J0, int nJ, auto BASE, auto CAP) {
+        constexpr int base = decltype(BASE)::value, cap = decltype(CAP)::value;
         const int jend = min(N, 8 * (I + 1));                  // stages with 2 j < 16 (I + 1)
         const int jfull = min(jend, 8 * I + 1);                // stages with 2 j <= 16 I: every lane of the row is live
         const int ia = 16 * I + l16;
@@ -707,7 +724,7 @@ __device__ __forceinline__ void gram(const QPDims &d, const QPConst &c, const GP
                 for (int u = 0; u < KS; ++u)
 #pragma unroll
                     for (int t = 0; t < nj; ++t)
-                        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u][t], acc[t], 0, 0, 0);
+                        acc[base + t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u][t], acc[base + t], 0, 0, 0);
             };
             int j0 = jb;
             for (; j0 + UN <= je; j0 += UN) trip(j0, std::integral_constant<int, UN>{});
@@ -721,15 +738,17 @@ __device__ __forceinline__ void gram(const QPDims &d, const QPConst &c, const GP
             if (jfull > g.j0) run(g.gt - goff0, g.j0, jfull, std::false_type{}, NJ);
             if (jend > max(jfull, g.j0)) run(g.gt - goff0, max(jfull, g.j0), jend, std::true_type{}, NJ);
         };
-        if (nJ == 4) task_body(std::integral_constant<int, 4>{});
-        else if (nJ == 3) task_body(std::integral_constant<int, 3>{});
-        else if (nJ == 2) task_body(std::integral_constant<int, 2>{});
-        else task_body(std::integral_constant<int, 1>{});
-        GR_LAP(2);
-        // ---- Ls on both sides, + I, raw tile to the store; the diagonal feeds the Jacobi scaling
-        // (the factors of the rows are the same for every tile of the task; the row r ^ 1 of an output stage sits in the neighbouring
-        // row of 16 lanes: wg::xor16, two v_permlane16_swap instead of a ds_bpermute round trip; the scale factors of the Jacobi
-        // scaling only where the tile is a diagonal one -- round 5: 13 k of the 40 k clocks of a Gram fill were this epilogue)
+        if constexpr (cap >= 4) { if (nJ == 4) { task_body(std::integral_constant<int, 4>{}); return; } }
+        if constexpr (cap >= 3) { if (nJ == 3) { task_body(std::integral_constant<int, 3>{}); return; } }
+        if constexpr (cap >= 2) { if (nJ == 2) { task_body(std::integral_constant<int, 2>{}); return; } }
+        task_body(std::integral_constant<int, 1>{});
+    };
+    // ---- Ls on both sides, + I, raw tile to the store; the diagonal feeds the Jacobi scaling
+    // (the factors of the rows are the same for every tile of the task; the row r ^ 1 of an output stage sits in the neighbouring
+    // row of 16 lanes: wg::xor16, two v_permlane16_swap instead of a ds_bpermute round trip; the scale factors of the Jacobi
+    // scaling only where the tile is a diagonal one -- round 5: 13 k of the 40 k clocks of a Gram fill were this epilogue)
+    auto epilogue = [&](int I, int J0, int nJ, auto BASE, auto CAP) {
+        constexpr int base = decltype(BASE)::value, cap = decltype(CAP)::value;
         double la0[4], la2[4], la3[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -739,7 +758,7 @@ __device__ __forceinline__ void gram(const QPDims &d, const QPConst &c, const GP
         }
         const bool ar0 = (kk & 1) == 0;                                  // row of the output stage: 16 I + 4 q are even
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
+        for (int t = 0; t < cap; ++t) {
             if (t >= nJ) continue;
             const int J = J0 + t;
             const int gjc = 16 * J + l16, kb = min(gjc >> 1, N - 1), bc = gjc & 1;
@@ -749,7 +768,7 @@ __device__ __forceinline__ void gram(const QPDims &d, const QPConst &c, const GP
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int r = kk + 4 * q, gi = 16 * I + r;
-                double v = (gi < NP && gjc < NP) ? acc[t][q] : 0.0;      // padding rows / columns: exactly the identity
+                double v = (gi < NP && gjc < NP) ? acc[base + t][q] : 0.0;  // padding rows / columns: exactly the identity
                 const double vp = wg::dpp_mov<0xB1>(v);                 // the other column of the output stage
                 v = fma(vp, cb_oth, v * cb_own);                        // (Ky Ls)
                 const double vr = wg::xor16(v);                         // the other row of the output stage (kk ^ 1)
@@ -763,6 +782,49 @@ __device__ __forceinline__ void gram(const QPDims &d, const QPConst &c, const GP
                 T[r * TS + l16] = v;
             }
         }
+    };
+    constexpr std::integral_constant<int, 0> B0{};
+    constexpr std::integral_constant<int, 4> C4{};
+    if constexpr (!STAGE) {
+        while (true) {
+            int tnext = 0;
+            if (lane == 0) tnext = __hip_atomic_fetch_add(tl, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            tnext = __builtin_amdgcn_readfirstlane(tnext);
+            if (tnext >= GRAM_TASKS) break;
+            const int I = __builtin_amdgcn_readfirstlane(tl[4 + 4 * tnext]), J0 = __builtin_amdgcn_readfirstlane(tl[5 + 4 * tnext]),
+                      nJ = __builtin_amdgcn_readfirstlane(tl[6 + 4 * tnext]);
+            GR_LAP(1);
+            if (nJ == 0) break;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) acc[t] = {0.0, 0.0, 0.0, 0.0};
+            products(I, J0, nJ, B0, C4);
+            GR_LAP(2);
+            epilogue(I, J0, nJ, B0, C4);
+            GR_LAP(3);
+        }
+    } else {
+        constexpr std::integral_constant<int, 4> B1{};
+        constexpr std::integral_constant<int, 7> B2{};
+        constexpr std::integral_constant<int, 3> C3{};
+        constexpr std::integral_constant<int, 1> C1{};
+        int sI[GRAM_SLOTS], sJ[GRAM_SLOTS], sn[GRAM_SLOTS];
+#pragma unroll
+        for (int s = 0; s < GRAM_SLOTS; ++s) {
+            const int e = 4 + 4 * (GRAM_SLOTS * wave + s);
+            sI[s] = __builtin_amdgcn_readfirstlane(tl[e]); sJ[s] = __builtin_amdgcn_readfirstlane(tl[e + 1]); sn[s] = __builtin_amdgcn_readfirstlane(tl[e + 2]);
+        }
+        GR_LAP(1);
+#pragma unroll
+        for (int t = 0; t < NACC; ++t) acc[t] = {0.0, 0.0, 0.0, 0.0};
+        if (sn[0] > 0) products(sI[0], sJ[0], sn[0], B0, C4);
+        if (sn[1] > 0) products(sI[1], sJ[1], sn[1], B1, C3);
+        if (sn[2] > 0) products(sI[2], sJ[2], sn[2], B2, C1);
+        GR_LAP(2);
+        __syncthreads();                                       // every wave has read its last staged row: L.B takes the tiles
+        GR_LAP(4);
+        if (sn[0] > 0) epilogue(sI[0], sJ[0], sn[0], B0, C4);
+        if (sn[1] > 0) epilogue(sI[1], sJ[1], sn[1], B1, C3);
+        if (sn[2] > 0) epilogue(sI[2], sJ[2], sn[2], B2, C1);
         GR_LAP(3);
     }
     __syncthreads();
@@ -786,6 +848,8 @@ __device__ __forceinline__ void gram(const QPDims &d, const QPConst &c, const GP
 #endif
 #undef GR_LAP
 }
+template <int MSEL, class GP>
+__device__ __forceinline__ void gram(const QPDims &d, const QPConst &c, const GP &g, Lds &L) { gram_t<MSEL, false>(d, c, g, L); }
 
 // ------------------------------------------------------------------ tile Cholesky on one wave set, without set-wide barriers
 // qpc::tile_cholesky synchronises the whole workgroup twice per tile row; its critical path is wave 0 (a 16 x 16 factorisation
@@ -1714,7 +1778,8 @@ __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, co
 //   * a thread owns BOTH an input (its two box rows) and a state-row slot (ipm_box gives them to different threads: N m + N GX <= 512);
 //     the per-stage sums of the state rows are the same DPP sums over GX adjacent lanes;
 //   * the free response yf and the region sequence of the condensation come from the problem's L2 block (Lds::yfg / goffg), every packed
-//     row of G from there as well (lean_j0 = N), the inverses of the diagonal tiles sit in the tiles' own places (rinv_tile);
+//     row of G from there as well (lean_j0 = N; the Gram fill stages the rows that fit the K-tile area there first: gram_t<.., STAGE>), the
+//     inverses of the diagonal tiles sit in the tiles' own places (rinv_tile);
 //   * the condensation runs in two column passes (condense_half), rollouts take two row passes (rollout<.., WG = 4>).
 // Sums over rows are taken in another order than ipm_box's (reduce2 over 4 waves, two roles per thread): rounding-level differences.
 template <int MSEL, int NSEL, int GX, int NST = 0, int J0SEL = 0>
@@ -1735,7 +1800,19 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
     gptr gh = work_base + dfull.qc_off;
     const int N = d.N, m = d.m, nm = N * m, ldG = 16 * d.KT, NP = 2 * N, nz = d.nz;
     GPackT<NST, J0SEL> g{(cgptr)gh, (clptr)(L.Gt), d.lean_j0, m, NP};
+    // the Gram fill's own pack: the stages >= gram_stage_j0 staged in the K-tile area (gram_t)
+    const GPack gg{(cgptr)gh, (clptr)(L.B), gram_stage_j0(d), m, NP};
     Prof pf;
+#ifdef SRH_PROFILE
+    for (int i = 0; i < 24; ++i) pf.t[i] = 0;
+    long long tq_last = clock64();
+    auto qlap = [&](int slot) { const long long now = clock64(); prof[slot] += now - tq_last; tq_last = now; };
+    if (tid < 15) L.Qu[tid] = 0.0;                             // (the laps of gram_t; [15] is the serial wave's)
+    int ngram = 0;
+#define Q4_LAP(x) qlap(x)
+#else
+#define Q4_LAP(x) ((void)0)
+#endif
     constexpr double WARM_FLOOR = 1e-2;
     if (warm) { for (int e = tid; e < nm; e += nt) L.u[e] = w.u[e]; }
     else { for (int e = tid; e < nm; e += nt) { w.u[e] = 0.0; L.u[e] = 0.0; } }
@@ -1758,6 +1835,7 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
     }
     if (!reuse) {
         rollout<MSEL, NSEL, false, 4>(d, dyn, q.x0, (cgptr) nullptr, w.x, L);
+        Q4_LAP(0);
         condense_half<MSEL, NSEL>(d, c, dyn, w.x, gh, L);
         for (int k = tid; k < N; k += nt) L.goffg[k] = L.idxl[k];
         if (tid == 0) L.flag[2] = 1;
@@ -1773,6 +1851,7 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
         for (int e = tid; e < ldG; e += nt) { L.y[e] = L.yfg[e]; L.dy[e] = 0.0; }
     }
     __syncthreads();
+    Q4_LAP(2);
     // ---- this thread's rows: the two box rows of input `tid`, and one state-row slot
     const bool isu = tid < nm;
     const bool isx = tid < N * GX;
@@ -1839,6 +1918,7 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
     }
     while (true) {
         tid = SRH_TID;
+        Q4_LAP(7);
         // ---------------- rows -> weights, gradient shifts, and their per-stage sums, all in place
         double musum = 0.0, rpm = 0.0;
         double Du[2] = {0.0, 0.0}, rhu[2] = {0.0, 0.0}, Dx = 0.0, rhx = 0.0;
@@ -1918,11 +1998,16 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
             rp = rpm;
         }
         __syncthreads();
+        Q4_LAP(1);
         // ---------------- Newton system
         double rd = 0.0;
         bool ok = true;
         if (mode != CORR) {
-            gram<MSEL>(d, c, g, L);
+            gram_t<MSEL, true>(d, c, gg, L, (cgptr)gh);
+            Q4_LAP(4);
+#ifdef SRH_PROFILE
+            ++ngram;
+#endif
             // the factorisation (waves 0-1: a chain of one-wave 16 x 16 factorisations) beside the half of the Newton solve that
             // does not need the factor (waves 2-3), see Waves
             const clptr gyd = mode == PRED ? (clptr)L.yg : (clptr) nullptr;
@@ -1936,10 +2021,12 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
             if (tid < 5) L.flag[3 + tid] = 0;
             if (gyd) rd = L.Qu[0];
             if (ok) unit_tiles(d, L);
+            Q4_LAP(5);
             if (ok) newton_back<MSEL>(d, g, L, pf);
         } else {
             newton_solve<MSEL>(d, g, L, (clptr) nullptr, &rd, pf, ya_const);
         }
+        Q4_LAP(6);
         // ---------------- use the direction
         if (mode == INIT) {
             if (!ok) { status = 2; break; }
@@ -2026,6 +2113,20 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
         if (xrow) w.lam[lsx] = lxr;
     }
     __syncthreads();
+#ifdef SRH_PROFILE
+    for (int i = 0; i < 8; ++i) prof[8 + i] += pf.t[8 + i];
+    prof[24] += it; prof[25] += 1; prof[26] += warm ? 1 : 0;
+    if (tid == 0 && blockIdx.x == 0) {
+        printf("lean gram laps (this QP, wave 0, %d fills): 1/D+staging+barrier %.0f descriptors %.0f products %.0f epilogue %.0f barrier %.0f scaling+barrier %.0f\n",
+               ngram, L.Qu[4], L.Qu[5], L.Qu[6], L.Qu[7], L.Qu[13], L.Qu[14]);
+        printf("lean gram per wave (cumulative) products:");
+        for (int i = 0; i < 4; ++i) printf(" %lld", g_prof_waves[i]);
+        printf("  epilogue:");
+        for (int i = 0; i < 4; ++i) printf(" %lld", g_prof_waves[8 + i]);
+        printf("\n");
+    }
+#endif
+#undef Q4_LAP
     if (iters_out) *iters_out = it;
     return status;
 }

@@ -125,6 +125,50 @@ static bool lean_gram_schedule(int N, int m, int KT, int nw, std::vector<int> &o
     return have;
 }
 
+// Gram tile tasks of the half-size layout's STAGED fill (ql::gram_t<.., STAGE = true>): a wave keeps the accumulators of all its tiles
+// in registers until every wave is through with the staged rows, so its tasks are a static table of GRAM_SLOTS slots that hold at most
+// 4, 3 and 1 tiles.  The tile rows are cut into chunks of 4 and a remainder; a chunk of 4 goes to a slot 0, one of 2 or 3 to a slot 1,
+// a single tile to a slot 2.  The products and the epilogues are two phases with a barrier between them, so of all such assignments
+// (at most (nw!)^3, nw <= 4) the one with the smallest  max over waves (MFMAs) + 22 max over waves (tiles)  is kept (the units of
+// lean_gram_schedule: an epilogue costs about 22 MFMAs; the operands come from LDS here).
+// Output: [wave][slot] x {I, J0, nJ, 0}, nJ = 0 for an empty slot; false if a slot class has more chunks than there are waves.
+static bool lean_gram_slots(int N, int m, int KT, int nw, std::vector<int> &out) {
+    struct Task { int I, J0, nJ; double cost; };
+    if (KT < 1 || nw < 1 || nw > 4) return false;
+    std::vector<Task> cls[ql::GRAM_SLOTS];
+    for (int I = 0; I < KT; ++I)
+        for (int J = I; J < KT; J += 4) {
+            const int nJ = std::min(4, KT - J);
+            const double ks = std::min(N, 8 * (I + 1)) * (m / 4);
+            cls[nJ == 4 ? 0 : (nJ >= 2 ? 1 : 2)].push_back({I, J, nJ, nJ * ks});
+        }
+    for (const auto &c : cls) if ((int)c.size() > nw) return false;
+    std::vector<int> p0(nw), p1(nw), p2(nw), b0, b1, b2;
+    for (int w = 0; w < nw; ++w) p0[w] = p1[w] = p2[w] = w;
+    double best = -1.0;
+    auto add = [&](std::vector<double> &load, std::vector<double> &tiles, const std::vector<Task> &c, const std::vector<int> &p) {
+        for (size_t i = 0; i < c.size(); ++i) { load[p[i]] += c[i].cost; tiles[p[i]] += c[i].nJ; }
+    };
+    do {
+        do {
+            do {
+                std::vector<double> load(nw, 0.0), tiles(nw, 0.0);
+                add(load, tiles, cls[0], p0); add(load, tiles, cls[1], p1); add(load, tiles, cls[2], p2);
+                const double mx = *std::max_element(load.begin(), load.end()) + 22.0 * *std::max_element(tiles.begin(), tiles.end());
+                if (best < 0.0 || mx < best - 1e-9) { best = mx; b0 = p0; b1 = p1; b2 = p2; }
+            } while (std::next_permutation(p2.begin(), p2.end()));
+        } while (std::next_permutation(p1.begin(), p1.end()));
+    } while (std::next_permutation(p0.begin(), p0.end()));
+    out.assign((size_t)ql::GRAM_TASKS * 4, 0);
+    const std::vector<int> *bp[ql::GRAM_SLOTS] = {&b0, &b1, &b2};
+    for (int q = 0; q < ql::GRAM_SLOTS; ++q)
+        for (size_t i = 0; i < cls[q].size(); ++i) {
+            int *o = &out[((size_t)(*bp[q])[i] * ql::GRAM_SLOTS + q) * 4];
+            o[0] = cls[q][i].I; o[1] = cls[q][i].J0; o[2] = cls[q][i].nJ; o[3] = 0;
+        }
+    return true;
+}
+
 // want_half: the caller's batch is larger than the chip has CUs -- lay the problem out for the half-size lean workgroup where it fits (two
 // rollouts per CU: throughput; a single rollout is faster on the full-size workgroup).  SRH_LEAN_HALF=1 / 0 in the environment overrides.
 int build_consts(const slocp_problem *pr, QPConstHost &C, bool want_half = false) {
@@ -407,7 +451,7 @@ int build_consts(const slocp_problem *pr, QPConstHost &C, bool want_half = false
             // (the SCP loop of the lean GuSTO kernel stages both trajectories in the K-tile area between two QPs: csrc/lean.hip)
             const int lthreads = half ? 256 : NTHREADS;
             const bool stage_fits = j0 >= 0 && ql::sizes(d, lthreads, j0).regX >= (size_t)2 * (N + 1) * n + (size_t)2 * N * m + (size_t)pr->nX * n;
-            if (j0 >= 0 && (j0 < N || half) && stage_fits && (half || ql::condense_fits(d, NTHREADS / 64)) && lean_gram_schedule(N, m, d.KT, lthreads / 64, sched)) {
+            if (j0 >= 0 && (j0 < N || half) && stage_fits && (half || ql::condense_fits(d, NTHREADS / 64)) && (half ? lean_gram_slots(N, m, d.KT, lthreads / 64, sched) : lean_gram_schedule(N, m, d.KT, lthreads / 64, sched))) {
                 d.lean = 1;
                 d.lean_j0 = j0;
 

@@ -6,7 +6,9 @@ child process, parses the last launch's lines and writes one JSON file:
     python tools/probes/lean_phase_clocks.py [out.json]
 Clocks are s_memtime ticks of the profile build (100 MHz-independent shader clock, ~2.4 GHz under this load); the profile build
 is slower than the product build (extra barriers at the gusto-level laps), so the ms figures next to them come from the PRODUCT
-library timed in the same run (SRH_LIB_PATH unset in that child)."""
+library timed in the same run (SRH_LIB_PATH unset in that child).
+A fourth case, c2_N50_half, is C2 once more on the half-size workgroup (SRH_LEAN_HALF=1, instantiation <4, 60, 4, 50, 50, 4>), whose Gram
+fill is lapped per wave as well (`lean gram laps` / `lean gram per wave`)."""
 import json
 import os
 import re
@@ -15,7 +17,9 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-CASES = (('closed_loop_N5', 5, 0.05, 1, 5), ('hardware_closed_loop_N3', 3, 0.1, 0, 5), ('c2_N50', 50, 0.05, 1, 5))
+CASES = (('closed_loop_N5', 5, 0.05, 1, 5, {}), ('hardware_closed_loop_N3', 3, 0.1, 0, 5, {}), ('c2_N50', 50, 0.05, 1, 5, {}),
+         ('c2_N50_half', 50, 0.05, 1, 5, {'SRH_LEAN_HALF': '1'}))
+# SRH_PHASE_CASES=c2_N50_half,... restricts the run to the named cases
 
 
 def child(N, dt, with_X, cap):
@@ -58,6 +62,37 @@ def child(N, dt, with_X, cap):
 
 
 LINE = re.compile(r'^lean (gusto clocks|qp laps|newton laps|step laps|qp tail|split)')
+GRAM = re.compile(r'^lean gram laps \(this QP, wave 0(?:, (\d+) fills)?\): (.*)$')
+WAVES = re.compile(r'^lean gram per wave \(cumulative\) products:((?: \d+)+)  epilogue:((?: \d+)+)')
+
+
+def parse_gram(text):
+    """Gram-fill laps of the last launch: the per-QP wave-0 laps summed over its QPs, the per-wave product / epilogue clocks as the
+    increase of the cumulative counters over that launch (they are never reset)."""
+    lines = text.splitlines()
+    starts = [i for i, ln in enumerate(lines) if ln.startswith('lean gusto clocks')]
+    waves = [(i, WAVES.match(ln)) for i, ln in enumerate(lines) if WAVES.match(ln)]
+    if not starts or not waves:
+        return None
+    # a launch prints its QPs' gram lines first and its gusto clocks last
+    lo = starts[-2] if len(starts) > 1 else -1
+    hi = starts[-1]
+    laps, fills = {}, 0
+    for ln in lines[lo + 1:hi]:
+        m = GRAM.match(ln)
+        if m:
+            fills += int(m.group(1) or 0)
+            for k, v in re.findall(r'([A-Za-z/+0-9 ]+?) (\d+)(?= |$)', m.group(2)):
+                laps[k.strip()] = laps.get(k.strip(), 0) + int(v)
+    cum = lambda m: ([int(x) for x in m.group(1).split()], [int(x) for x in m.group(2).split()])
+    before = [w for w in waves if w[0] <= lo]
+    last = [w for w in waves if lo < w[0] < hi]
+    if not last:
+        return None
+    p1, e1 = cum(last[-1][1])
+    p0, e0 = cum(before[-1][1]) if before else ([0] * len(p1), [0] * len(e1))
+    return {'gram_fills': fills, 'wave0_laps': laps, 'products_per_wave': [a - b for a, b in zip(p1, p0)],
+            'epilogue_per_wave': [a - b for a, b in zip(e1, e0)]}
 
 
 def parse(text):
@@ -90,9 +125,13 @@ if __name__ == '__main__':
     out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, 'gpurun_out', 'lean_phase_clocks.json')
     prof_lib = os.environ.get('SRH_PROF_LIB', os.path.join(ROOT, 'gpurun_variants', 'libsofacontrol_hip_prof.so'))
     res = {'what': __doc__.split('\n')[0], 'profile_library': os.path.basename(prof_lib), 'cases': {}}
-    for key, N, dt, with_X, cap in CASES:
-        entry = {'N': N, 'dt': dt, 'X_rows': 4 if with_X else 0, 'max_gusto_iters': cap}
-        for flavour, env in (('product', {k: v for k, v in os.environ.items() if k != 'SRH_LIB_PATH'}), ('profile', dict(os.environ, SRH_LIB_PATH=prof_lib))):
+    only = [c for c in os.environ.get('SRH_PHASE_CASES', '').split(',') if c]
+    for key, N, dt, with_X, cap, extra in CASES:
+        if only and key not in only:
+            continue
+        entry = {'N': N, 'dt': dt, 'X_rows': 4 if with_X else 0, 'max_gusto_iters': cap, 'env': extra}
+        for flavour, env in (('product', dict({k: v for k, v in os.environ.items() if k != 'SRH_LIB_PATH'}, **extra)),
+                             ('profile', dict(os.environ, SRH_LIB_PATH=prof_lib, **extra))):
             p = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', str(N), str(dt), str(with_X), str(cap)], env=env,
                                capture_output=True, text=True, timeout=600)
             txt = p.stdout
@@ -100,6 +139,7 @@ if __name__ == '__main__':
             entry[flavour] = json.loads(m.group(1)) if m else {'error': (p.stderr or txt)[-400:]}
             if flavour == 'profile':
                 entry['clocks_last_solve'] = parse(txt.split('=== timed solves')[-1])
+                entry['gram_last_solve'] = parse_gram(txt.split('=== timed solves')[-1])
                 with open(out_path.replace('.json', '_%s.log' % key), 'w') as f:
                     f.write(txt[-20000:])
         res['cases'][key] = entry
