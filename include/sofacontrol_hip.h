@@ -479,6 +479,10 @@ int sgusto_plan_variant(const sgusto_plan_t *plan, int *split, int *n_u_fixed, i
 int sgusto_plan_costs(sgusto_plan_t *plan, double *J);
 /* srh_kernel_info of a GuSTO plan (see slocp_plan_info). */
 int sgusto_plan_info(sgusto_plan_t *plan, srh_kernel_info *info);
+/* QPs of the plan's LAST solve that the lean kernel condensed by the single-region recursion (every stage of the horizon in
+ * one TPWL region: the condensed matrix is block-Toeplitz and is built from one chain of N products); 0 for a plan without
+ * the lean kernel, before the first solve, and for a plan created under SRH_LEAN_NO_TOEPLITZ=1.  Waits for the solve. */
+int sgusto_plan_single_region_qps(sgusto_plan_t *plan, int32_t *count);
 int sgusto_plan_solve(sgusto_plan_t *plan, const double *x0, const double *u_init, const double *x_init,
                       const double *z, const double *zf, const double *u_des, double *xopt, double *uopt,
                       double *zopt, int32_t *iters, int32_t *status, double *trace);

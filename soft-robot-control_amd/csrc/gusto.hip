@@ -286,7 +286,7 @@ struct sgusto_plan {
     QPConstHost C;
     GustoPar par{};
     int64_t batch = 0;
-    srh::DevBuf fs, work, x0, u_init, x_init, z, zf, ud, xopt, uopt, zopt, iters, status, trace, order, last_iters, handed, Jopt;
+    srh::DevBuf fs, work, x0, u_init, x_init, z, zf, ud, xopt, uopt, zopt, iters, status, trace, order, last_iters, handed, single, Jopt;
     bool have_last = false;             // a previous solve left its iteration counts
     size_t work_stride = 0;
     size_t lds = 0, lean_lds = 0;
@@ -365,14 +365,15 @@ int sgusto_plan_create(sgusto_plan_t **out, stpwl_t *h, const slocp_problem *pro
         (rc = pl->xopt.alloc(sizeof(double) * batch * (N + 1) * n)) || (rc = pl->uopt.alloc(sizeof(double) * batch * N * m)) ||
         (rc = pl->zopt.alloc(sizeof(double) * batch * (N + 1) * nz)) || (rc = pl->iters.alloc(sizeof(int32_t) * batch)) ||
         (rc = pl->status.alloc(sizeof(int32_t) * batch)) || (rc = pl->order.alloc(sizeof(int32_t) * batch)) ||
-        (rc = pl->last_iters.alloc(sizeof(int32_t) * batch)) || (rc = pl->handed.alloc(sizeof(int32_t))) || (rc = pl->Jopt.alloc(sizeof(double) * batch)) ||
+        (rc = pl->last_iters.alloc(sizeof(int32_t) * batch)) || (rc = pl->handed.alloc(sizeof(int32_t))) || (rc = pl->single.alloc(sizeof(int32_t))) || (rc = pl->Jopt.alloc(sizeof(double) * batch)) ||
         (rc = pl->trace.alloc(sizeof(double) * batch * (size_t)std::max(1, max_trace) * 4)) ||
         (rc = set_lds_limit(gusto_entry(d), pl->lds))) {
         delete pl;
         return rc;
     }
     // the resume / warm-start records of the work blocks start as "nothing there"
-    if (hipMemset(pl->work.p, 0, sizeof(double) * pl->work_stride * batch) != hipSuccess || hipMemset(pl->handed.p, 0, sizeof(int32_t)) != hipSuccess) {
+    if (hipMemset(pl->work.p, 0, sizeof(double) * pl->work_stride * batch) != hipSuccess || hipMemset(pl->handed.p, 0, sizeof(int32_t)) != hipSuccess ||
+        hipMemset(pl->single.p, 0, sizeof(int32_t)) != hipSuccess) {
         delete pl;
         SRH_REQUIRE(false, "sgusto_plan_create: hipMemset of the hand-over counter failed");
     }
@@ -468,7 +469,11 @@ static int solve_dev_impl(sgusto_plan_t *pl, const double *x0, const double *u_i
         if (phase != 2) {
             if (phase == 0) SRH_CHECK_HIP(hipMemsetAsync(pl->handed.p, 0, sizeof(int32_t), (hipStream_t)stream));
             else b.handed_over = nullptr;
-            int rc = lean_launch_gusto(pl->lean_variant, pl->C.dims, pl->C.view(), pl->model->view(), par, b, (unsigned)pl->batch, pl->lean_lds,
+            // (the QPs of this launch that condense by the single-region recursion: sgusto_plan_single_region_qps)
+            SRH_CHECK_HIP(hipMemsetAsync(pl->single.p, 0, sizeof(int32_t), (hipStream_t)stream));
+            QPConst cv = pl->C.view();
+            cv.single_qps = (giptr)pl->single.as<int32_t>();
+            int rc = lean_launch_gusto(pl->lean_variant, pl->C.dims, cv, pl->model->view(), par, b, (unsigned)pl->batch, pl->lean_lds,
                                        (hipStream_t)stream);
             if (rc) return rc;
         }
@@ -518,6 +523,17 @@ int sgusto_plan_info(sgusto_plan_t *pl, srh_kernel_info *info) {
         if (pl->host_handed >= 0) info->handed_over = pl->host_handed;
         else SRH_CHECK_HIP(hipMemcpy(&info->handed_over, pl->handed.p, sizeof(int32_t), hipMemcpyDeviceToHost));
         if (!pl->lean) info->handed_over = 0;
+    }
+    return SRH_OK;
+}
+
+int sgusto_plan_single_region_qps(sgusto_plan_t *pl, int32_t *count) {
+    SRH_REQUIRE(pl && count, "sgusto_plan_single_region_qps: null argument");
+    SRH_REQUIRE(!pl->pending, "sgusto_plan_single_region_qps: an asynchronous request is in flight on this plan (call sgusto_plan_solve_end first)");
+    *count = 0;
+    if (pl->solved && pl->lean) {
+        SRH_CHECK_HIP(hipDeviceSynchronize());          // (as sgusto_plan_info: the last solve may sit on a caller's stream)
+        SRH_CHECK_HIP(hipMemcpy(count, pl->single.p, sizeof(int32_t), hipMemcpyDeviceToHost));
     }
     return SRH_OK;
 }

@@ -42,6 +42,8 @@ struct QPDims {
     int ls_pd;          // 1 (p_o = 2): the constant output blocks S*_k are positive definite, so every S_k = S*_k + T^T D_x T has an
                         // invertible Cholesky factor Ls_k -- the lean Newton solve then gets dy from the solved system itself
                         // (ql::newton_back) instead of a second product with G
+    int lean_toeplitz;  // 1: a QP whose horizon lies in one TPWL region condenses by the restricted recursion (ql::condense_single);
+                        // 0 (SRH_LEAN_NO_TOEPLITZ=1 when the constants are built): always the general recursion
 };
 
 namespace qp {
@@ -73,6 +75,7 @@ struct QPConst {                       // shared by the whole batch (HBM/L2 resi
     cgptr Tx, Txf;                     // (nX x po), (nXf x po): X.A = Tx C_o, Xf.A = Txf C_o
     cgptr Cz2, Czf2;                   // (po x nz): C_o H^T 2 Qz, C_o H^T 2 Qzf
     cgiptr gram_sched;                 // lean kernels: tile tasks of the Gram product, ql::GRAM_TASKS x {I, J0, nJ, 0}, longest first (pulled by the waves)
+    giptr single_qps;                  // lean kernels: counts the QPs condensed by the single-region recursion (plan-owned), or null
 };
 
 struct QPDyn {                         // stage dynamics: matrix k at base + idx[k]*size (idx null: k)

@@ -41,6 +41,7 @@ struct Lds : qpc::Lds {
     // block behind the packed G (read once per QP), Rinv == B marks "inverse of a diagonal tile in the tile's own place" (rinv_tile)
     gptr yfg;
     giptr goffg;
+    gptr gtoep;        // half-size layout: the Toeplitz generators g_b[0 .. NP) (b < m) of a single-region condensation, behind goffg in the L2 block
     int ypad;          // zeros behind ya / yd / yg (gT_times): 48, or 24 when a pass has 32 rows (256 threads)
     int ldTc;          // row pitch of Theta^T while condensing: 16 KT + 1, or the widest column pass + 1
 };
@@ -90,8 +91,11 @@ __host__ __device__ inline size_t lds_doubles(const QPDims &d, int nthreads, int
     const Sizes s = sizes(d, nthreads, j0);
     return s.regX + s.gt + s.ldi + s.ls + 2 * s.nm4 + s.nyv * s.ldG + 3 * s.ypad + s.ua + s.tx + s.nvv * s.ld + 16 + 16 + 4 + s.nidx * s.idx;
 }
-// doubles of the half-size layout's homes in the L2 block behind the packed G: [pad (YPAD) | yf (16 KT) | goff (N ints)]
+// doubles of the half-size layout's homes in the L2 block behind the packed G: [pad (YPAD) | yf (16 KT) | goff (N ints) | g (m NP)]
 __host__ __device__ inline size_t half_l2_off(const QPDims &d) { return (size_t)goff(d.N, d.m, d.N * d.po) + 48; }
+__host__ __device__ inline size_t half_l2_doubles(const QPDims &d) {
+    return half_l2_off(d) + 16 * (size_t)d.KT + (((size_t)(d.N / 2 + 2) + 3) & ~(size_t)3) + (size_t)d.m * d.N * d.po;
+}
 // first stage whose packed rows, with those of every later stage, fit the K-tile area (what a staged Gram fill reads from LDS)
 __host__ __device__ inline int gram_stage_j0(const QPDims &d) {
     const int NP = d.N * d.po, cap = d.KT * (d.KT + 1) / 2 * TSZ;
@@ -128,11 +132,12 @@ __device__ inline void lds_carve(Lds &L, lptr base, const QPDims &d, int nthread
     L.goff = half ? (liptr) nullptr : (liptr)take(s.idx);
     L.ypad = (int)s.ypad;
     L.ldTc = (int)s.ldTc;
-    L.yfg = nullptr; L.goffg = nullptr;
+    L.yfg = nullptr; L.goffg = nullptr; L.gtoep = nullptr;
     if (half && work_base != nullptr) {
         gptr hb = work_base + d.qc_off + half_l2_off(d);
         L.yfg = hb;
         L.goffg = (giptr)(hb + s.ldG);
+        L.gtoep = hb + s.ldG + s.idx;
     }
 }
 
@@ -144,6 +149,7 @@ struct GPackT {
     cgptr gh;          // rows of the stages j < j0
     clptr gt;          // rows of the stages j >= j0, offset so that gt[goff(j) + ...] addresses stage j
     int j0, m, NP;
+    cgptr gto;         // the Toeplitz generators g_b[0 .. NP) when the L2-resident rows are their expansion (row (j, b) = g_b[0 .. NP - 2 j)), else null
     static constexpr int NF = NF_, J0F = J0F_;
 };
 using GPack = GPackT<0, 0>;
@@ -441,6 +447,110 @@ __device__ __forceinline__ void condense_half(const QPDims &d, const QPConst &c,
     }
 }
 
+// The condensation of a horizon that lies in ONE region (idx[0] = ... = idx[N-1]: A_j = A, B_j = B).  The block of Theta_j that belongs
+// to output stage k is then C_o A^(k-j-1) -- it depends on k - j only -- and G is block-Toeplitz: packed row (j, b) is the first
+// NP - 2 j entries of one vector g_b, g_b[2 t + a] = (C_o A^t B)[a, b].  The general recursion recomputes, at every stage and for every
+// older output stage, numbers an earlier stage has produced for the newest one.  Here the recursion runs for the two columns of
+// output stage N alone: one 16-column tile of Theta^T (the columns sit at the lanes they have in tile KT - 1), one MFMA item per
+// wave and stage, the panel loaded once and its operand kept in registers, Theta^T double buffered (one barrier per stage); the
+// packed rows are then copies of g.  Every number goes through the k-steps, operands and order the general recursion gives the
+// column of output stage N, and an output column of an MFMA product does not depend on its neighbours: the packed G has the same
+// bits.  yf, the pad behind G and the stores (L2 head / LDS by lean_j0; the half-size layout: all in L2) as condense() leaves them.
+constexpr int TOEP_PITCH = 17;         // row pitch of the one-tile Theta^T
+__host__ __device__ inline bool toeplitz_fits(const QPDims &d, int nwaves, int ldTc) {
+    return d.po == 2 && d.NPa / 16 <= nwaves && 2 * d.NK * TOEP_PITCH + d.m * d.N * d.po <= d.NK * ldTc;
+}
+template <int MSEL, int NSEL>
+__device__ __forceinline__ void condense_single(const QPDims &d, const QPConst &c, const QPDyn &dyn, cgptr x, gptr gh, Lds &L) {
+    const int N = d.N, n = d.n, m = d.m, po = d.po, ld = d.ld, ldG = 16 * d.KT;
+    const int nk = d.NK, NPa = d.NPa, NP = N * po, j0 = d.lean_j0;
+    const int tid = SRH_TID, nt = blockDim.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, nw = nt >> 6;
+    const int l16 = lane & 15, kk = lane >> 4;
+    constexpr int TP = TOEP_PITCH;
+    const bool half = d.lean_half != 0;
+    for (int e = tid; e < ldG; e += nt) {
+        double v = 0.0;
+        if (e < NP) {
+            const int k = e / po + 1, a = e - (k - 1) * po;
+            for (int j = 0; j < n; ++j) v = fma(c.Co[(size_t)a * n + j], x[(size_t)k * n + j], v);
+        }
+        if (half) L.yfg[e] = v; else L.yf[e] = v;
+    }
+    lptr gl = L.B + 2 * nk * TP;                       // g_b[0 .. NP) for b < m, behind the two Theta^T buffers
+    for (int e = tid; e < 2 * nk * TP; e += nt) L.B[e] = 0.0;
+    for (int e = tid; e < nk * ld; e += nt) L.panel[e] = 0.0;
+    const int goff0 = goff(j0, m, NP);
+    for (int e = tid; e < YPAD; e += nt) gh[goff0 + e] = 0.0;
+    __syncthreads();
+    QPLds P{};
+    P.AB = L.panel; P.idxl = L.idxl; P.psel = -1;
+    const int MT = NPa >> 4;
+    const int KS = (n + 3) >> 2;
+    const int lc0 = (NP - po) & 15;                    // lane of column (N, 0) in its tile
+    (void)qp::panel_load(d, dyn, P, N - 1);
+    for (int e = tid; e < po * n; e += nt) { const int a = e / n, r = e - a * n; L.B[r * TP + lc0 + a] = c.Co[(size_t)a * n + r]; }
+    __syncthreads();
+    constexpr int KSMAX = NSEL > 0 ? (NSEL + 3) / 4 : 32;
+    const bool item = wave < MT;                       // row tile `wave` of [A | B]^T
+    double aop[KSMAX];
+#pragma unroll
+    for (int s = 0; s < KSMAX; ++s) aop[s] = (item && s < KS) ? L.panel[(4 * s + kk) * ld + 16 * wave + l16] : 0.0;
+    const int ca = l16 - lc0;
+    const bool born = ca >= 0 && ca < po;
+    lptr cur = L.B, nxt = L.B + nk * TP;
+    for (int j = N - 1; j >= 0; --j) {
+        if (item) {
+            wg::qp_d4 acc = {0.0, 0.0, 0.0, 0.0};
+            double bop[KSMAX];
+#pragma unroll
+            for (int s = 0; s < KSMAX; ++s) bop[s] = s < KS ? cur[(4 * s + kk) * TP + l16] : 0.0;
+#pragma unroll
+            for (int s = 0; s < KSMAX; ++s)
+                if (s < KS) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[s], bop[s], acc, 0, 0, 0);
+            if (born) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int row = 16 * wave + kk + 4 * q;
+                    if (row < n) nxt[row * TP + l16] = acc[q];
+                    else if (row < n + m) gl[(row - n) * NP + po * (N - 1 - j) + ca] = acc[q];
+                }
+            }
+        }
+        __syncthreads();
+        lptr t = cur; cur = nxt; nxt = t;
+    }
+    if (half) for (int e = tid; e < m * NP; e += nt) L.gtoep[e] = gl[e];       // (the Gram fills of this G read g instead of the packed rows)
+    // expansion: row (j, b) <- g_b[0 .. NP - 2 j), a wave per row
+    for (int r = wave; r < N * m; r += nw) {
+        const int j = r / m, b = r - j * m, len = NP - po * j, at = goff(j, m, NP) + b * len;
+        for (int e = lane; e < len; e += 64) {
+            const double v = gl[b * NP + e];
+            if (j < j0) gh[at + e] = v; else L.Gt[at - goff0 + e] = v;
+        }
+    }
+    __syncthreads();
+}
+
+// Whether this QP's horizon lies in one region (all N entries of the region sequence in L.idxl equal) and the plan allows the
+// single-region condensation (QPDims::lean_toeplitz; explicit per-stage matrices -- no region index -- never qualify).  Uniform over
+// the workgroup; counts the QP in the plan's counter (QPConst::single_qps).  Called between two barriers of the caller's preamble;
+// L.red is free there.
+__device__ __forceinline__ bool single_region(const QPDims &d, const QPConst &c, const QPDyn &dyn, Lds &L) {
+    if (dyn.idx == nullptr || !d.lean_toeplitz || !toeplitz_fits(d, (int)blockDim.x >> 6, L.ldTc)) return false;
+    const int tid = SRH_TID, nt = blockDim.x;
+    liptr f = (liptr)L.red;
+    int uni = 1;
+    const int first = L.idxl[0];
+    for (int k = tid; k < d.N; k += nt) uni = uni && (L.idxl[k] == first);
+    if (tid == 0) f[0] = 1;
+    __syncthreads();
+    if (!uni) f[0] = 0;
+    __syncthreads();
+    const bool single = __builtin_amdgcn_readfirstlane(f[0]) != 0;
+    if (single && tid == 0 && c.single_qps) __hip_atomic_fetch_add(c.single_qps, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return single;
+}
+
 // ------------------------------------------------------------------ products with G
 // Row (j, b) of the packed G^T starts at goff(j) + b (NP - 2 j); with R(j, b) = that start - 2 j, element i sits at R + i and
 //     R(j + 1, b) = R(j, b) + m (NP - 2 j) - 2 b - 2
@@ -471,13 +581,14 @@ __device__ __forceinline__ void g_times_fixed(const GP &g, Lds &L, clptr uv, lpt
     for (int b = grp; b < M; b += GR) {                               // wave-uniform
         clptr pu = uv + b;
         // stages [JB, JE) from `pg` (pointing at element (0, b, column) of its store minus SHIFT), MASK: triangular part
-        auto block = [&](auto pg, auto JB_, auto JE_, auto SHIFT_, auto MASK) {
+        auto block = [&](auto pg, auto JB_, auto JE_, auto SHIFT_, auto MASK, auto TOEP) {
             constexpr int JB = decltype(JB_)::value, JE = decltype(JE_)::value, SHIFT = decltype(SHIFT_)::value;
-            constexpr bool masked = decltype(MASK)::value;
+            constexpr bool masked = decltype(MASK)::value, toep = decltype(TOEP)::value;
             double gv[JE - JB], uu[JE - JB];
 #pragma unroll
             for (int j = JB; j < JE; ++j) {
-                gv[j - JB] = pg[(M * (j * NP - j * (j - 1)) - 2 * j - SHIFT) - 2 * j * b];
+                if constexpr (toep) gv[j - JB] = pg[-2 * j];            // g_b[column - 2 j]
+                else gv[j - JB] = pg[(M * (j * NP - j * (j - 1)) - 2 * j - SHIFT) - 2 * j * b];
                 uu[j - JB] = pu[j * M];
             }
 #pragma unroll
@@ -486,18 +597,22 @@ __device__ __forceinline__ void g_times_fixed(const GP &g, Lds &L, clptr uv, lpt
                 else acc[j & 3] = fma(gv[j - JB], uu[j - JB], acc[j & 3]);
             }
         };
-        auto span = [&](auto pg, auto LO_, auto HI_, auto SHIFT_) {   // compile-time range [LO, HI) in blocks of BLK
+        auto span = [&](auto pg, auto LO_, auto HI_, auto SHIFT_, auto TOEP) {   // compile-time range [LO, HI) in blocks of BLK
             constexpr int LO = decltype(LO_)::value, HI = decltype(HI_)::value;
             srh_static_for<0, (HI - LO + BLK - 1) / BLK>([&](auto K_) {
                 constexpr int JB = LO + decltype(K_)::value * BLK, JE = JB + BLK < HI ? JB + BLK : HI;
                 if (JB <= jany) {                                     // uniform
-                    if (JE - 1 <= jall) block(pg, std::integral_constant<int, JB>{}, std::integral_constant<int, JE>{}, SHIFT_, std::false_type{});
-                    else block(pg, std::integral_constant<int, JB>{}, std::integral_constant<int, JE>{}, SHIFT_, std::true_type{});
+                    if (JE - 1 <= jall) block(pg, std::integral_constant<int, JB>{}, std::integral_constant<int, JE>{}, SHIFT_, std::false_type{}, TOEP);
+                    else block(pg, std::integral_constant<int, JB>{}, std::integral_constant<int, JE>{}, SHIFT_, std::true_type{}, TOEP);
                 }
             });
         };
-        if constexpr (J0F > 0) span(g.gh + (b * NP + cc), std::integral_constant<int, 0>{}, std::integral_constant<int, (J0F < NF ? J0F : NF)>{}, std::integral_constant<int, 0>{});
-        if constexpr (J0F < NF) span(g.gt + (b * NP + cc), std::integral_constant<int, J0F>{}, std::integral_constant<int, NF>{}, std::integral_constant<int, goff0>{});
+        if constexpr (J0F > 0) {
+            constexpr std::integral_constant<int, (J0F < NF ? J0F : NF)> HEAD{};
+            if (g.gto != nullptr) span(g.gto + (b * NP + cc), std::integral_constant<int, 0>{}, HEAD, std::integral_constant<int, 0>{}, std::true_type{});
+            else span(g.gh + (b * NP + cc), std::integral_constant<int, 0>{}, HEAD, std::integral_constant<int, 0>{}, std::false_type{});
+        }
+        if constexpr (J0F < NF) span(g.gt + (b * NP + cc), std::integral_constant<int, J0F>{}, std::integral_constant<int, NF>{}, std::integral_constant<int, goff0>{}, std::false_type{});
     }
     lptr part = L.part;
     part[grp * CW + col] = (acc[0] + acc[1]) + (acc[2] + acc[3]);
@@ -583,12 +698,12 @@ __device__ __forceinline__ void gT_times(const QPDims &d, const GP &g, Lds &L, c
     const int NP = g.NP, nm = d.N * M, tid = W.tid, nt = W.nt;
     const int g8 = tid & 7, rpp = nt / 8;
     const int goff0 = goff(g.j0, M, NP);
-    auto rows = [&](auto src, int rb, int re, auto TWO) {           // rows [rb, re) from `src` (indexed by the global offset)
+    auto rows = [&](auto src, int rb, int re, auto TWO, bool toep = false) {   // rows [rb, re) from `src` (indexed by the global offset; toep: by b NP + i - 2 j)
         constexpr bool two = decltype(TWO)::value;
         for (int r0 = rb; r0 < re; r0 += rpp) {
             const int r = r0 + (tid >> 3), rc = r < re ? r : re - 1;
             const int j = rc / M, b = rc - j * M, len = NP - 2 * j;
-            const int at = goff(j, M, NP) + b * len + g8;
+            const int at = (toep ? b * NP : goff(j, M, NP) + b * len) + g8;
             clptr p1 = y1 + 2 * j + g8, p2 = (two ? y2 : y1) + 2 * j + g8;
             const int nq = (NP - 2 * (r0 / M) + 7) >> 3;             // trips of the longest row of this pass (uniform)
             double a1 = 0.0, a2 = 0.0, c1 = 0.0, c2 = 0.0;         // two chains per output
@@ -612,11 +727,13 @@ __device__ __forceinline__ void gT_times(const QPDims &d, const GP &g, Lds &L, c
         }
     };
     const int rh = min(nm, g.j0 * M);
+    const bool toep = g.gto != nullptr;                             // (uniform) the L2-resident rows read from their generators
+    cgptr head = toep ? g.gto : g.gh;
     if (y2) {
-        if (rh > 0) rows(g.gh, 0, rh, std::true_type{});
+        if (rh > 0) rows(head, 0, rh, std::true_type{}, toep);
         if (nm > rh) rows(g.gt - goff0, rh, nm, std::true_type{});
     } else {
-        if (rh > 0) rows(g.gh, 0, rh, std::false_type{});
+        if (rh > 0) rows(head, 0, rh, std::false_type{}, toep);
         if (nm > rh) rows(g.gt - goff0, rh, nm, std::false_type{});
     }
     W.sync();
@@ -643,9 +760,16 @@ __device__ long long g_prof_waves[16];         // per-wave clocks of the Gram fi
 // another wave still reads staged rows there: the accumulators of ALL tiles of a wave stay in registers (GRAM_SLOTS tasks of at most
 // 4, 3, 1 tiles: 8 accumulators), one barrier, then the epilogues.  Register arrays want compile-time indices, so the tasks are not
 // pulled here: c.gram_sched is the static table [wave][slot] of scp_host.h:lean_gram_slots.
+// STAGE with gtoep != null (wave-uniform; the packed G is the expansion of the Toeplitz generators g_b, ql::condense_single): operand
+// element (j, b, i) of the packed rows is g_b[i - 2 j].  The four vectors are staged instead of the rows -- each behind TOEP_FRONT zeros,
+// for the lanes of a triangular stage that sit before its first column (masked as in the packed form; the index must only be
+// addressable) and in front of zeros up to the pitch (the padding columns i >= NP of the last tile) -- and EVERY stage reads LDS: no
+// L2 head, ~3 loads per thread instead of 59.  Same stages in the same order into the same accumulators: same bits.
 constexpr int GRAM_SLOTS = 3;          // per wave of a staged Gram fill: {I, J0, nJ, 0} with nJ <= 4, 3, 1 (nJ = 0: slot not used)
+constexpr int TOEP_FRONT = 16;
+__host__ __device__ inline int toep_pitch(int KT) { return TOEP_FRONT + 16 * KT + 16; }
 template <int MSEL, bool STAGE, class GP>
-__device__ __forceinline__ void gram_t(const QPDims &d, const QPConst &c, const GP &g, Lds &L, cgptr gsrc = nullptr) {
+__device__ __forceinline__ void gram_t(const QPDims &d, const QPConst &c, const GP &g, Lds &L, cgptr gsrc = nullptr, cgptr gtoep = nullptr) {
     static_assert(MSEL == 4 || MSEL == 8, "lean Gram: n_u = 4 or 8");
     constexpr int M = MSEL, SPS = M / 4;                       // k-steps per stage
     const int N = d.N, KT = d.KT, NP = g.NP;
@@ -668,20 +792,29 @@ __device__ __forceinline__ void gram_t(const QPDims &d, const QPConst &c, const 
     if (tid < GRAM_TASKS * 4) tl[4 + tid] = c.gram_sched[tid];
     if (tid == 0) tl[0] = 0;
     for (int e = tid; e < N * M; e += nt) { const double s = L.Ldi[e]; w2[e] = s * s; }
+    const int TGP = toep_pitch(KT);
     if constexpr (STAGE) {                                     // (packed offsets of a stage are multiples of 4: 16-byte pieces)
-        const int nq = (goff(N, M, NP) - goff0) >> 1;
-        const double2 *s2 = (const double2 *)(gsrc + goff0);
-        double2 *d2 = (double2 *)(lptr)g.gt;
+        if (gtoep != nullptr) {
+            for (int e = tid; e < M * TGP; e += nt) {
+                const int b = e / TGP, col = e - b * TGP - TOEP_FRONT;
+                L.B[e] = (col >= 0 && col < NP) ? gtoep[b * NP + col] : 0.0;
+            }
+        } else {
+            const int nq = (goff(N, M, NP) - goff0) >> 1;
+            const double2 *s2 = (const double2 *)(gsrc + goff0);
+            double2 *d2 = (double2 *)(lptr)g.gt;
 #pragma unroll 4
-        for (int e = tid; e < nq; e += nt) d2[e] = s2[e];
+            for (int e = tid; e < nq; e += nt) d2[e] = s2[e];
+        }
     }
     __syncthreads();
     GR_LAP(0);
     constexpr int NACC = STAGE ? 8 : 4;
     wg::qp_d4 acc[NACC];
     // ---- the products of one task: tiles (I, J0 .. J0 + nJ - 1) into acc[BASE ..], nJ <= CAP
-    auto products = [&](int I, int J0, int nJ, auto BASE, auto CAP) {
+    auto products = [&](int I, int J0, int nJ, auto BASE, auto CAP, auto TOEP) {
         constexpr int base = decltype(BASE)::value, cap = decltype(CAP)::value;
+        constexpr bool toep = decltype(TOEP)::value;          // operands from the staged Toeplitz generators
         const int jend = min(N, 8 * (I + 1));                  // stages with 2 j < 16 (I + 1)
         const int jfull = min(jend, 8 * I + 1);                // stages with 2 j <= 16 I: every lane of the row is live
         const int ia = 16 * I + l16;
@@ -695,6 +828,7 @@ __device__ __forceinline__ void gram_t(const QPDims &d, const QPConst &c, const 
             constexpr int nj = decltype(NJ)::value;
             int R = goff(jb, M, NP) + kk * (NP - 2 * jb) - 2 * jb + ia;           // R(jb, b = kk) + column of the A operand
             int dl = M * (NP - 2 * jb) - 2 * kk - 2;
+            if constexpr (toep) { R = kk * TGP + TOEP_FRONT + ia - 2 * jb; dl = -2; }      // g_b[i - 2 j], b = kk
 #ifndef SRH_GRAM_KS
 #define SRH_GRAM_KS 4
 #endif
@@ -708,7 +842,7 @@ __device__ __forceinline__ void gram_t(const QPDims &d, const QPConst &c, const 
 #pragma unroll
                     for (int sub = 0; sub < SPS; ++sub) {
                         const int u = us * SPS + sub;
-                        const int base = R + 4 * sub * (NP - 2 * j);
+                        const int base = R + 4 * sub * (toep ? TGP : NP - 2 * j);
                         av[u] = src[base] * w2[j * M + 4 * sub + kk];
 #pragma unroll
                         for (int t = 0; t < nj; ++t) bv[u][t] = src[base + dJ + 16 * t];
@@ -718,7 +852,8 @@ __device__ __forceinline__ void gram_t(const QPDims &d, const QPConst &c, const 
                             if (diag0) bv[u][0] = va ? bv[u][0] : 0.0;
                         }
                     }
-                    R += dl; dl -= 2 * M;
+                    R += dl;
+                    if constexpr (!toep) dl -= 2 * M;
                 }
 #pragma unroll
                 for (int u = 0; u < KS; ++u)
@@ -732,6 +867,11 @@ __device__ __forceinline__ void gram_t(const QPDims &d, const QPConst &c, const 
         };
         // four ranges: {L2 head, LDS} x {full, triangular}
         auto task_body = [&](auto NJ) {
+            if constexpr (toep) {                                  // two ranges: full, triangular
+                if (jfull > 0) run((clptr)L.B, 0, jfull, std::false_type{}, NJ);
+                if (jend > jfull) run((clptr)L.B, jfull, jend, std::true_type{}, NJ);
+                return;
+            }
             const int hf = min(jfull, g.j0), he = min(jend, g.j0);
             if (hf > 0) run(g.gh, 0, hf, std::false_type{}, NJ);
             if (he > hf) run(g.gh, hf, he, std::true_type{}, NJ);
@@ -797,7 +937,7 @@ __device__ __forceinline__ void gram_t(const QPDims &d, const QPConst &c, const 
             if (nJ == 0) break;
 #pragma unroll
             for (int t = 0; t < 4; ++t) acc[t] = {0.0, 0.0, 0.0, 0.0};
-            products(I, J0, nJ, B0, C4);
+            products(I, J0, nJ, B0, C4, std::false_type{});
             GR_LAP(2);
             epilogue(I, J0, nJ, B0, C4);
             GR_LAP(3);
@@ -816,9 +956,15 @@ __device__ __forceinline__ void gram_t(const QPDims &d, const QPConst &c, const 
         GR_LAP(1);
 #pragma unroll
         for (int t = 0; t < NACC; ++t) acc[t] = {0.0, 0.0, 0.0, 0.0};
-        if (sn[0] > 0) products(sI[0], sJ[0], sn[0], B0, C4);
-        if (sn[1] > 0) products(sI[1], sJ[1], sn[1], B1, C3);
-        if (sn[2] > 0) products(sI[2], sJ[2], sn[2], B2, C1);
+        if (gtoep != nullptr) {
+            if (sn[0] > 0) products(sI[0], sJ[0], sn[0], B0, C4, std::true_type{});
+            if (sn[1] > 0) products(sI[1], sJ[1], sn[1], B1, C3, std::true_type{});
+            if (sn[2] > 0) products(sI[2], sJ[2], sn[2], B2, C1, std::true_type{});
+        } else {
+            if (sn[0] > 0) products(sI[0], sJ[0], sn[0], B0, C4, std::false_type{});
+            if (sn[1] > 0) products(sI[1], sJ[1], sn[1], B1, C3, std::false_type{});
+            if (sn[2] > 0) products(sI[2], sJ[2], sn[2], B2, C1, std::false_type{});
+        }
         GR_LAP(2);
         __syncthreads();                                       // every wave has read its last staged row: L.B takes the tiles
         GR_LAP(4);
@@ -1474,9 +1620,11 @@ __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, co
         if (tid == 0) L.flag[3] = 0;                           // tile_cholesky_set's early-tile counter from here on
     }
     if (!reuse) {
+        const bool single = single_region(d, c, dyn, L);
         rollout<MSEL, NSEL>(d, dyn, q.x0, (cgptr) nullptr, w.x, L);
         QB_LAP(0);
-        condense<MSEL, NSEL>(d, c, dyn, w.x, gh, L);
+        if (single) condense_single<MSEL, NSEL>(d, c, dyn, w.x, gh, L);
+        else condense<MSEL, NSEL>(d, c, dyn, w.x, gh, L);
         for (int k = tid; k < N; k += nt) L.goff[k] = L.idxl[k];
         if (tid == 0) L.flag[2] = 1;
     }
@@ -1808,7 +1956,8 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
     long long tq_last = clock64();
     auto qlap = [&](int slot) { const long long now = clock64(); prof[slot] += now - tq_last; tq_last = now; };
     if (tid < 15) L.Qu[tid] = 0.0;                             // (the laps of gram_t; [15] is the serial wave's)
-    int ngram = 0;
+    int ngram = 0, cond_mode = 0;                              // condensation of this QP: 0 kept from the QP before, 1 general, 2 single-region
+    long long cond_clk = 0;
 #define Q4_LAP(x) qlap(x)
 #else
 #define Q4_LAP(x) ((void)0)
@@ -1834,13 +1983,20 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
         if (tid == 0) L.flag[3] = 0;                           // tile_cholesky_set's early-tile counter from here on
     }
     if (!reuse) {
+        const bool single = single_region(d, c, dyn, L);
         rollout<MSEL, NSEL, false, 4>(d, dyn, q.x0, (cgptr) nullptr, w.x, L);
         Q4_LAP(0);
-        condense_half<MSEL, NSEL>(d, c, dyn, w.x, gh, L);
+        if (single) condense_single<MSEL, NSEL>(d, c, dyn, w.x, gh, L);
+        else condense_half<MSEL, NSEL>(d, c, dyn, w.x, gh, L);
+#ifdef SRH_PROFILE
+        cond_mode = single ? 2 : 1; cond_clk = clock64() - tq_last;
+#endif
         for (int k = tid; k < N; k += nt) L.goffg[k] = L.idxl[k];
-        if (tid == 0) L.flag[2] = 1;
+        if (tid == 0) L.flag[2] = single ? 2 : 1;              // 2: the packed G is the expansion of L.gtoep (kept over the QPs that reuse it)
         __syncthreads();
     }
+    const bool toep = __builtin_amdgcn_readfirstlane(L.flag[2]) == 2;
+    g.gto = toep ? (cgptr)L.gtoep : (cgptr) nullptr;           // the products read the generators (3.2 KB) instead of the packed rows (82 KB)                         // (uniform: written before a barrier, by this QP or the one that condensed)
     if (warm) {                                               // y = y_free + G u
         __syncthreads();
         g_times<MSEL>(d, g, L, L.u, L.dy);
@@ -2003,7 +2159,7 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
         double rd = 0.0;
         bool ok = true;
         if (mode != CORR) {
-            gram_t<MSEL, true>(d, c, gg, L, (cgptr)gh);
+            gram_t<MSEL, true>(d, c, gg, L, (cgptr)gh, toep ? (cgptr)L.gtoep : (cgptr) nullptr);
             Q4_LAP(4);
 #ifdef SRH_PROFILE
             ++ngram;
@@ -2117,6 +2273,7 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
     for (int i = 0; i < 8; ++i) prof[8 + i] += pf.t[8 + i];
     prof[24] += it; prof[25] += 1; prof[26] += warm ? 1 : 0;
     if (tid == 0 && blockIdx.x == 0) {
+        printf("lean condense (this QP): mode %d clocks %lld interior-point iterations %d status %d\n", cond_mode, cond_clk, it, status);
         printf("lean gram laps (this QP, wave 0, %d fills): 1/D+staging+barrier %.0f descriptors %.0f products %.0f epilogue %.0f barrier %.0f scaling+barrier %.0f\n",
                ngram, L.Qu[4], L.Qu[5], L.Qu[6], L.Qu[7], L.Qu[13], L.Qu[14]);
         printf("lean gram per wave (cumulative) products:");

@@ -444,7 +444,7 @@ int build_consts(const slocp_problem *pr, QPConstHost &C, bool want_half = false
                 half = ql::lds_doubles(dh, 256, N) * sizeof(double) <= (size_t)80 * 1024 && wide * MTh <= 4 * ql::CONDENSE_SLOTS &&
                        N * m <= 256 && N * GXh <= 256 && RXh <= 8 && (N * m) % GXh == 0 &&
                        sh.regX >= (size_t)2 * (N + 1) * n + (size_t)2 * N * m + (size_t)pr->nX * n &&
-                       ql::half_l2_off(dh) + 16 * (size_t)dh.KT + (size_t)(N / 2 + 2) <= qc_work_doubles(dh);
+                       ql::half_l2_doubles(dh) <= qc_work_doubles(dh);
                 if (half) { d.lean_half = 1; j0 = N; }
             }
             std::vector<int> sched;
@@ -454,6 +454,9 @@ int build_consts(const slocp_problem *pr, QPConstHost &C, bool want_half = false
             if (j0 >= 0 && (j0 < N || half) && stage_fits && (half || ql::condense_fits(d, NTHREADS / 64)) && (half ? lean_gram_slots(N, m, d.KT, lthreads / 64, sched) : lean_gram_schedule(N, m, d.KT, lthreads / 64, sched))) {
                 d.lean = 1;
                 d.lean_j0 = j0;
+                // A/B and test knob, read when the constants are built: SRH_LEAN_NO_TOEPLITZ=1 keeps the general condensation for
+                // single-region horizons too (ql::condense_single)
+                d.lean_toeplitz = getenv("SRH_LEAN_NO_TOEPLITZ") == nullptr ? 1 : 0;
 
                 // rows next to their sums (ql::ipm_box): the reference's HyperRectangle layout of the input rows (rows 2 b,
                 // 2 b + 1 act on input b alone, utils.py:390-414), at most 8 state rows per stage, everything in 512 threads

@@ -192,14 +192,20 @@ class GuSTO:
     def kernel_info(self):
         """What the last solve of this plan launched (sgusto_plan_info): the kernel family, the template arguments of
         the instantiation -- the name a rocprof trace shows, e.g. 'lean<4, 60, 4, 50, 7, 4>' for BASELINE C2 -- and how
-        many rollouts the lean kernel handed to the fused one.  The host-loop models report their LOCP plan's kernels."""
+        many rollouts the lean kernel handed to the fused one.  The host-loop models report their LOCP plan's kernels.
+        'single_region_qps' (resident TPWL plan): QPs of the last solve whose horizon lay in one TPWL region and were
+        condensed by the single-region recursion (sgusto_plan_single_region_qps)."""
         if self._ssm:
             return {'family': 'ssm', 'kernel': 'gusto_ssm_kernel', 'lean': None, 'fused': None, 'handed_over': 0}
         if not self._fused:
             return self.locp.kernel_info
         info = _lib.SrhKernelInfo()
         _lib.check(_lib.lib().sgusto_plan_info(self._plan, C.byref(info)), 'sgusto_plan_info')
-        return info.as_dict()
+        out = info.as_dict()
+        nsingle = C.c_int32(0)
+        _lib.check(_lib.lib().sgusto_plan_single_region_qps(self._plan, C.byref(nsingle)), 'sgusto_plan_single_region_qps')
+        out['single_region_qps'] = int(nsingle.value)
+        return out
 
     # ---- helper tests with the reference's names (host arrays; used by the generic loop / by users)
     def is_converged(self, x, u):

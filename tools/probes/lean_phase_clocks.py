@@ -8,7 +8,8 @@ Clocks are s_memtime ticks of the profile build (100 MHz-independent shader cloc
 is slower than the product build (extra barriers at the gusto-level laps), so the ms figures next to them come from the PRODUCT
 library timed in the same run (SRH_LIB_PATH unset in that child).
 A fourth case, c2_N50_half, is C2 once more on the half-size workgroup (SRH_LEAN_HALF=1, instantiation <4, 60, 4, 50, 50, 4>), whose Gram
-fill is lapped per wave as well (`lean gram laps` / `lean gram per wave`)."""
+fill is lapped per wave as well (`lean gram laps` / `lean gram per wave`), and whose condensation is reported per QP with its kind
+(`lean condense (this QP)`: kept from the QP before / general two-pass recursion / single-region recursion + expansion)."""
 import json
 import os
 import re
@@ -95,6 +96,21 @@ def parse_gram(text):
             'epilogue_per_wave': [a - b for a, b in zip(e1, e0)]}
 
 
+COND = re.compile(r'^lean condense \(this QP\): mode (\d) clocks (\d+) interior-point iterations (\d+) status (-?\d+)')
+
+
+def parse_condense(text):
+    """The condensation of every QP of the last launch, in order: kind, clocks of the profile build, interior-point iterations of the QP."""
+    lines = text.splitlines()
+    starts = [i for i, ln in enumerate(lines) if ln.startswith('lean gusto clocks')]
+    if not starts:
+        return None
+    lo = starts[-2] if len(starts) > 1 else -1
+    kinds = ('kept', 'general', 'single_region')
+    return [{'condensation': kinds[int(m.group(1))], 'clocks': int(m.group(2)), 'ipm_iterations': int(m.group(3)), 'status': int(m.group(4))}
+            for m in (COND.match(ln) for ln in lines[lo + 1:starts[-1]]) if m]
+
+
 def parse(text):
     """the LAST launch's lines (the last solve of the child: rollout 7)"""
     blocks, cur = [], None
@@ -140,6 +156,7 @@ if __name__ == '__main__':
             if flavour == 'profile':
                 entry['clocks_last_solve'] = parse(txt.split('=== timed solves')[-1])
                 entry['gram_last_solve'] = parse_gram(txt.split('=== timed solves')[-1])
+                entry['condense_last_solve'] = parse_condense(txt.split('=== timed solves')[-1])
                 with open(out_path.replace('.json', '_%s.log' % key), 'w') as f:
                     f.write(txt[-20000:])
         res['cases'][key] = entry
