@@ -293,9 +293,15 @@ int sric_dare_fixed_point(const double *A, const double *B, int64_t batch, int n
  * max_iter steps do not converge. */
 int sric_dare(const double *A, const double *B, int64_t batch, int n_x, int n_u, const double *Q, const double *R,
               double tol, int max_iter, double *L, double *P, int32_t *iters);
+/* The same solver for a wide input block, 1 <= n_u <= 64 (sric_dare keeps its n_u <= 16): the Luenberger gain of the ROMPC
+ * observer is dare(A_d^T, C^T, Q, R) (baselines/rompc/observer.py:27), whose "input" dimension is the measurement dimension.
+ * Same arguments, doubling steps, stopping rule, shapes and SRH_ENUMERIC cases; R and R + B^T P B are factored by the whole
+ * workgroup.  n_x as far as sric_dare goes (above 62 or so the five n x n slots move from LDS to the HBM workspace). */
+int sric_dare_wide(const double *A, const double *B, int64_t batch, int n_x, int n_u, const double *Q, const double *R,
+                   double tol, int max_iter, double *L, double *P, int32_t *iters);
 
 /* =====================================================================================================
- * iLQR.                           reference: sofacontrol/lqr/ilqr.py, sofacontrol/lqr/config.py
+ * iLQR.                          reference: sofacontrol/lqr/ilqr.py, sofacontrol/lqr/config.py
  * ===================================================================================================== */
 typedef struct silqr_params {
     int    max_iter;          /* config.py:3   50  */
@@ -555,6 +561,49 @@ int skoop_mpc_step(skoop_mpc_t *plan, const double *y, const double *u_prev, con
  * [whole step on the device]; -1 while timing is off. */
 int skoop_mpc_set_timing(skoop_mpc_t *plan, int on);
 int skoop_mpc_stats(skoop_mpc_t *plan, int64_t *steps, int64_t *waits_last_step, double *ms);
+
+/* =====================================================================================================
+ * ROMPC baseline. reference: sofacontrol/baselines/rompc/rompc.py:57-89, rompc/observer.py:30-46, rompc_utils.py:52-53
+ * `batch` independent loops on one linear reduced model (problem-major arrays everywhere).  One control step is
+ *   u     = u_given                                   (start-up, rompc.py:69-70; or observer.update(u, y) on its own)
+ *   u     = ubar + K (x_hat - xbar)                   (rompc.py:79)
+ *   x_hat <- A x_hat + B u + d + L ((y - y_ref) - C x_hat)                          (observer.py:37-40)
+ *   z     = H x_hat + z_ref, or C x_hat + y_ref when H is NULL (then n_z = n_y)     (observer.py:42-46)
+ * FOLDED FORM: the device holds F = A_d - L C, formed on the host at srompc_create / srompc_set_gains, and evaluates
+ * x_hat <- [F | B | L] [x_hat ; u ; y - y_ref] + d.  f64 throughout; a workgroup owns 16 problems, stages the constants in
+ * LDS once and forms the products on v_mfma_f64_16x16x4_f64 (a problem gives the same bits alone and inside any batch).
+ * Limits: n_x, n_u, n_y, n_z <= 128 each, and [F B L], K, the output map and the tile must fit 160 KB of LDS -- n_x = 80,
+ * n_u = 16, n_y = 64, n_z = 16 fits (152 KB); the same without H (z = C x + y_ref, 64 rows) does not.  What does not fit is
+ * refused by srompc_create with SRH_EINVAL.  K NULL: zeros.  Every call ends with the handle's stream drained.
+ * ===================================================================================================== */
+typedef struct srompc srompc_t;
+int srompc_create(srompc_t **out, int64_t batch, int n_x, int n_u, int n_y, int n_z, const double *A_d, const double *B_d,
+                  const double *d_d, const double *C, const double *y_ref, const double *H, const double *z_ref, const double *K,
+                  const double *L);
+int srompc_destroy(srompc_t *h);
+int srompc_set_gains(srompc_t *h, const double *K, const double *L);      /* K (n_u x n_x), L (n_x x n_y); NULL keeps */
+int srompc_set_state(srompc_t *h, const double *x);                       /* batch x n_x */
+int srompc_get_state(srompc_t *h, double *x, double *z);                  /* either may be NULL */
+/* observer.initialize (observer.py:30-35): x_hat = V^T (x_full - x_ref) by srom_project_dev straight into the estimate;
+ * x_full (batch x 2 n_f), the basis must give 2 r = n_x.  x_out, z_out optional. */
+int srompc_initialize(srompc_t *h, srom_t *rom, const double *x_full, double *x_out, double *z_out);
+/* One control step: [x_full != NULL: initialize first] -> u (u_given, or the feedback on ubar (batch x n_u), xbar (batch x n_x))
+ * -> observer update with y (batch x n_y, the full-order measurement) -> z.  One launch sequence on the handle's stream, one
+ * copy back of (u, x_hat, z) and ONE blocking wait; inputs and results go through the handle's pinned blocks (no allocation,
+ * except the full-state block at the first x_full call).  Outputs are optional. */
+int srompc_step(srompc_t *h, srom_t *rom, const double *x_full, const double *u_given, const double *ubar, const double *xbar,
+                const double *y, double *u_out, double *x_out, double *z_out);
+/* T steps of the same recursion over a record in one launch: Y (T x batch x n_y), and U_given (T x batch x n_u) or
+ * Ubar (T x batch x n_u) / Xbar (T x batch x n_x).  The time loop runs inside the kernel, the estimate tile stays in LDS,
+ * Y[t] is streamed.  U_out / X_out / Z_out (T x batch x .) optional; the estimate ends at X_out[T - 1]. */
+int srompc_replay(srompc_t *h, int T, const double *Y, const double *U_given, const double *Ubar, const double *Xbar,
+                  double *U_out, double *X_out, double *Z_out);
+/* steps taken, and the blocking host waits of the last initialize / step / replay call */
+int srompc_stats(srompc_t *h, int64_t *steps, int64_t *waits_last_step);
+/* For probes: srompc_set_timing(h, 1) brackets every following initialize / step / replay / get_state with HIP events on the
+ * handle's stream; srompc_last_device_ms gives the last call's device-side duration, first enqueue to last copy (-1: none). */
+int srompc_set_timing(srompc_t *h, int on);
+int srompc_last_device_ms(srompc_t *h, double *ms);
 
 #ifdef __cplusplus
 }

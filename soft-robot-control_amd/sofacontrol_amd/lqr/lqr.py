@@ -42,6 +42,21 @@ def dare(Ad, Bd, Q, R):
     return L[0], P[0]
 
 
+def dare_wide(Ad, Bd, Q, R):
+    """`dare` for an input block of up to 64 columns (`sric_dare_wide`, csrc/dare_wide.hip): what the ROMPC observer asks
+    for, dare(A_d.T, C.T, Q, R) with one "input" per measurement (baselines/rompc/observer.py:27).  Same doubling steps,
+    tolerance and sign (u = +K x); a stack of (A_d, B_d) pairs returns stacked (K, P)."""
+    Ad, Bd = np.asarray(Ad), np.asarray(Bd)
+    A = _lib.f64(Ad.reshape(-1, Ad.shape[-2], Ad.shape[-1]))
+    B = _lib.f64(Bd.reshape(-1, Bd.shape[-2], Bd.shape[-1]))
+    batch, n, m = B.shape
+    K = np.empty((batch, m, n)); P = np.empty((batch, n, n)); it = np.empty(batch, dtype=np.int32)
+    _lib.check(_lib.lib().sric_dare_wide(_lib.dptr(A), _lib.dptr(B), C.c_int64(batch), C.c_int(n), C.c_int(m),
+                                         _lib.dptr(_lib.f64(Q)), _lib.dptr(_lib.f64(R)), C.c_double(1e-14), C.c_int(100),
+                                         _lib.dptr(K), _lib.dptr(P), _lib.iptr(it)), 'sric_dare_wide')
+    return (K, P) if Bd.ndim == 3 else (K[0], P[0])
+
+
 def dare_batch(Ad, Bd, Q, R, tol=1e-14):
     """Gains for a stack of (A_d, B_d) pairs in one launch (the per-point gains of the scp controller,
     tpwl/controllers.py:238-246)."""
