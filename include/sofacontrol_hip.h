@@ -420,6 +420,13 @@ typedef struct sgusto_params {
     int    max_gusto_iters;
 } sgusto_params;
 void sgusto_default_params(sgusto_params *p);
+/* GuSTO's step rule (csrc/scp_types.h: what the kernels do with delta, omega and the previous accepted step after every QP) replayed on
+ * the HOST over a script of T QP answers, each (md = max_k |x_scale (x_k - xbar_k)|_inf, J, rho_k, viol = largest state-constraint
+ * violation, dsum = sum_k |x_scale (x_k - xbar_k)|_2); N, n_x as the convergence measure divides by them.  Needs no GPU; for tests of
+ * the rule.  steps (T x 4): per iteration delta and omega of its QP, 1.0 if the step was accepted, J of the last accepted step after it;
+ * iters = answers consumed (the rule may stop before T), status (0, 2 or 3 as sgusto_solve), converged. */
+int sgusto_rule_replay(const sgusto_params *par, int N, int n_x, int T, const double *script, double *steps, int32_t *iters,
+                       int32_t *status, int32_t *converged);
 
 /* GuSTO.solve (gusto.py:283-487) on a pre-discretised nn-TPWL model, `batch` independent rollouts:
  *   x0 (batch x n_x), u_init (batch x N x n_u), x_init (batch x (N+1) x n_x), z (batch x (N+1) x n_z)

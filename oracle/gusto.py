@@ -12,17 +12,66 @@ DEFAULTS = dict(delta0=1e4, omega0=1.0, rho=0.1, beta_fail=0.5, gamma_fail=5.0, 
                 omega_max=1e10, max_gusto_iters=500, convg_thresh=0.1)  # gusto.py:12-22
 
 
+def max_step(x, xk, xs):
+    """max_k |x_scale (x_k - xbar_k)|_inf: what the trust region bounds."""
+    return np.max(np.linalg.norm(xs * (x - xk), np.inf, axis=1))
+
+
 def is_in_trust_region(x, xk, xs, delta, eps):
     """gusto.py:174-183."""
-    md = np.max(np.linalg.norm(xs * (x - xk), np.inf, axis=1))
+    md = max_step(x, xk, xs)
     return (md, False) if md - delta > eps else (0.0, True)
+
+
+def mean_step(dsum, N, n):
+    """The convergence measure from dsum = sum_k |x_scale (x_k - xbar_k)|_2 (gusto.py:159)."""
+    return (1. / N) * (1. / n) * dsum
 
 
 def is_converged(x, xk, xs, N, thresh):
     """gusto.py:150-161."""
-    n = x.shape[1]
-    dsol = (1. / N) * (1. / n) * np.sum(np.linalg.norm(xs * (x - xk), axis=1))
+    dsol = mean_step(np.sum(np.linalg.norm(xs * (x - xk), axis=1)), N, x.shape[1])
     return dsol, dsol <= thresh
+
+
+def start(par):
+    """State of the step rule in front of the first QP (gusto.py:320-331)."""
+    return dict(delta=par['delta0'], omega=par['omega0'], J_prev=np.inf, d_prev=np.inf, o_prev=np.inf, converged=False)
+
+
+def running(par, st, itr):
+    """gusto.py:333 (is_valid_iteration: gusto.py:163-172)."""
+    return itr <= par['max_gusto_iters'] and not st['converged'] and st['omega'] <= par['omega_max']
+
+
+def judge(par, st, itr, md, J, rho_k, viol, dsol):
+    """One transition of the step rule after QP number `itr` (gusto.py:371-428): what becomes of delta, omega, the previous accepted
+    (J, delta, omega) and `converged` in `st`.  md = max_step of the QP's minimiser, J its objective; rho_k, viol, dsol: callables for the
+    model-accuracy ratio, the largest state-constraint violation and the convergence measure, evaluated only where the rule gets to them.
+    Returns (new_solution, tr_ok, rho_k)."""
+    if md - st['delta'] > par['epsilon']:
+        st['omega'] = par['gamma_fail'] * st['omega']
+        return False, False, -1.0
+    rho = rho_k()
+    if rho > par['rho'] and itr != 1:
+        st['delta'] = par['beta_fail'] * st['delta']
+        return False, True, rho
+    if st['d_prev'] == st['delta'] and st['o_prev'] == st['omega'] and st['J_prev'] <= J:
+        st['delta'] = par['beta_fail'] * st['delta']
+    st['d_prev'], st['J_prev'], st['o_prev'] = st['delta'], J, st['omega']
+    X_ok = not (viol() > par['epsilon'])
+    if not X_ok:
+        st['omega'] = par['gamma_fail'] * st['omega']
+    st['converged'] = bool(dsol() <= par['convg_thresh']) and X_ok
+    return True, True, rho
+
+
+def exit_status(par, st, itr):
+    """How a loop that ran out of QPs to try ended (gusto.py:475-483; the kernels' status word): 2 = omega > omega_max, 3 = max
+    iterations, else 0."""
+    if st['omega'] > par['omega_max']:
+        return 2
+    return 3 if itr - 1 > par['max_gusto_iters'] else 0
 
 
 def state_violation(X, x):
@@ -97,14 +146,12 @@ def _loop(get_traj, model, H, N, dt, Qz, R, x0, u_init, x_init, z, u_des, Qzf, z
     xk, uk = x_init.copy(), u_init.copy()
     A_k, B_k, d_k = get_traj(xk, uk)
     H_k, c_k = get_obs(xk)
-    delta, omega = par['delta0'], par['omega0']
-    new_solution = True
-    J_prev = d_prev = o_prev = np.inf
-    converged = False
+    st = start(par)
     itr = 0
     trace = []
     warm_state, ipm_iters = None, []
-    while itr <= par['max_gusto_iters'] and not converged and omega <= par['omega_max']:
+    while running(par, st, itr):
+        delta, omega = st['delta'], st['omega']
         if stage_qp:
             # the stage-structured interior point (numpy statement of the kernel's algorithm) on the same QP data;
             # seconds instead of minutes at the BASELINE shapes.  Checked against solve_exact in tests/test_locp_oracle.py
@@ -139,30 +186,13 @@ def _loop(get_traj, model, H, N, dt, Qz, R, x0, u_init, x_init, z, u_des, Qzf, z
                 w = qp_solver(qp)
                 J = olocp.objective(qp, w)
             x_next, u_next, _ = olocp.split(qp, w)
-        new_solution = False
-        rho_k = -1.0
-        e_tr, tr_ok = is_in_trust_region(x_next, xk, xs, delta, par['epsilon'])
-        d_cur, o_cur = delta, omega
-        if tr_ok:
-            rho_k = compute_accuracy(model, x_next, u_next, xk, uk, J, dt, fs)
-            if rho_k > par['rho'] and itr != 1:
-                delta = par['beta_fail'] * delta
-            else:
-                if d_prev == delta and o_prev == omega and J_prev <= J:
-                    delta = par['beta_fail'] * delta
-                d_prev, J_prev, o_prev = delta, J, omega
-                viol = state_violation(X, x_next)
-                X_ok = not (viol > par['epsilon'])
-                if not X_ok:
-                    omega = par['gamma_fail'] * omega
-                _, converged = is_converged(x_next, xk, xs, N, par['convg_thresh'])
-                if not X_ok:
-                    converged = False
-                new_solution = True
-        else:
-            omega = par['gamma_fail'] * omega
+        new_solution, tr_ok, rho_k = judge(
+            par, st, itr, max_step(x_next, xk, xs), J,
+            rho_k=lambda: compute_accuracy(model, x_next, u_next, xk, uk, J, dt, fs),
+            viol=lambda: state_violation(X, x_next),
+            dsol=lambda: is_converged(x_next, xk, xs, N, par['convg_thresh'])[0])
         itr += 1
-        trace.append((J, d_cur, o_cur, rho_k, new_solution, tr_ok))
+        trace.append((J, delta, omega, rho_k, new_solution, tr_ok))
         if new_solution:
             xk, uk = x_next.copy(), u_next.copy()
             if par['max_gusto_iters'] >= 1:

@@ -61,32 +61,20 @@ __global__ __launch_bounds__(NTHREADS) void gusto_kernel(QPDims d, QPConst c, Tp
     cgptr udp = (cgptr)(b.ud ? b.ud + p * (size_t)N * m : nullptr);
     if (b.host_args) {
         // zero-copy solve: the arguments sit in pinned host memory -- work on copies in the work block (mode 2: the lean kernel made them)
-        gptr x0c = base + gw.x0c, zc = base + gw.zc, zfc = base + gw.zfc, udc = base + gw.udc;
-        if (b.mode != 2) {
-            for (int e = tid; e < n; e += nt) x0c[e] = x0[e];
-            if (zp) for (int e = tid; e < (N + 1) * nz; e += nt) zc[e] = zp[e];
-            if (zfp) for (int e = tid; e < nz; e += nt) zfc[e] = zfp[e];
-            if (udp) for (int e = tid; e < N * m; e += nt) udc[e] = udp[e];
-        }
-        x0 = (cgptr)x0c;
-        if (zp) zp = (cgptr)zc;
-        if (zfp) zfp = (cgptr)zfc;
-        if (udp) udp = (cgptr)udc;
+        gusto_stage_args(x0, zp, zfp, udp, base + gw.x0c, base + gw.zc, base + gw.zfc, base + gw.udc, N, n, m, nz, b.mode != 2, tid, nt);
     }
-    double delta = par.delta0, omega = par.omega0;
-    double J_prev = INFINITY, d_prev = INFINITY, o_prev = INFINITY;
-    bool converged = false;
-    int itr = 0, status = 0;
+    GustoState s = gusto_start(par);
+    int status = 0;
     bool tr_hot = false;                               // expect the trust region to bind in the next QP (see qp::solve, full_first)
     bool warm_relaxed = false;                         // the previous QP ended in the relaxed Riccati pass (qp::solve, warm)
     bool warm_full = false;                            // the previous QP ended in the full pass (trust-region rows): qp::solve, warm_full
     if (b.mode == 2) {
         // only the rollouts a lean launch (lean.hip) could not finish: xk, uk, idx are where it left them
-        if (rec[0] != 1.0) return;
-        delta = rec[1]; omega = rec[2]; J_prev = rec[3]; d_prev = rec[4]; o_prev = rec[5]; itr = (int)rec[6];
-        tr_hot = rec[7] == 100.0;                      // the lean kernel found this QP's relaxed minimiser outside the trust region
+        int lean_st;
+        if (!gusto_rec_load(rec, s, &lean_st)) return;
+        tr_hot = lean_st == 100;                       // the lean kernel found this QP's relaxed minimiser outside the trust region
         __syncthreads();
-        if (tid == 0) rec[0] = 0.0;
+        if (tid == 0) rec[REC_PENDING] = 0.0;
     } else {
         for (int e = tid; e < (N + 1) * n; e += nt) xk[e] = b.x_init[p * (size_t)(N + 1) * n + e];
         for (int e = tid; e < N * m; e += nt) uk[e] = b.u_init[p * (size_t)N * m + e];
@@ -96,9 +84,9 @@ __global__ __launch_bounds__(NTHREADS) void gusto_kernel(QPDims d, QPConst c, Tp
     GU_LAP(0);
 
     QPDyn dyn{T.Ad, T.AdT, T.Bd, T.BdT, T.dd, (cgiptr)idx};
-    while (itr <= par.max_iters && !converged && omega <= par.omega_max) {
+    while (gusto_running(par, s)) {
         tid = SRH_TID; lane = tid & 63;
-        QPData q{x0, xk, zp, zfp, udp, delta, omega, (gptr)nullptr};
+        QPData q{x0, xk, zp, zfp, udp, s.delta, s.omega, (gptr)nullptr};
         double J;
         int qit;
         GU_LAP(1);
@@ -113,11 +101,11 @@ __global__ __launch_bounds__(NTHREADS) void gusto_kernel(QPDims d, QPConst c, Tp
         double md = 0.0;
         for (int e = tid; e < (N + 1) * n; e += nt) md = fmax(md, fabs(c.xs[e % n] * (w.x[e] - xk[e])));
         md = wg::reduce(md, 1, L.red);
-        const bool tr_ok = !(md - delta > par.epsilon);
-        const bool on_boundary = md >= delta * (1.0 - 1e-9);      // this QP's minimiser used the whole trust region
+        const bool tr_ok = gusto_inside(par, s, md);
+        const bool on_boundary = gusto_on_boundary(s, md);        // this QP's minimiser used the whole trust region
         bool new_solution = false;
         double rho_k = -1.0;
-        const double d_cur = delta, o_cur = omega;
+        const double d_cur = s.delta, o_cur = s.omega;
         if (tr_ok) {
             // model accuracy (gusto.py:203-223) with continuous nearest-point dynamics
             GU_LAP(3);
@@ -187,12 +175,8 @@ __global__ __launch_bounds__(NTHREADS) void gusto_kernel(QPDims d, QPConst c, Tp
             double err = 0.0, app = 0.0;      // sequential sums in stage order, as the reference loop
             for (int i = 0; i < N; ++i) { err += accb[2 * i]; app += accb[2 * i + 1]; }
             rho_k = err / (J + app);
-            if (rho_k > par.rho && itr != 1) {
-                delta = par.beta_fail * delta;
-            } else {
-                if (d_prev == delta && o_prev == omega && J_prev <= J) delta = par.beta_fail * delta;
-                d_prev = delta; J_prev = J; o_prev = omega;
-                // state-constraint violation (gusto.py:185-201): all k = 0..N
+            // state-constraint violation (gusto.py:185-201): all k = 0..N
+            auto viol_max = [&]() {
                 double viol = 0.0;
                 if (d.nX > 0) {
                     for (int k = tid; k <= N; k += nt) {
@@ -207,9 +191,10 @@ __global__ __launch_bounds__(NTHREADS) void gusto_kernel(QPDims d, QPConst c, Tp
                     }
                     viol = wg::reduce(viol, 1, L.red);
                 }
-                const bool X_ok = !(viol > par.epsilon);
-                if (!X_ok) omega = par.gamma_fail * omega;
-                // convergence (gusto.py:150-161)
+                return viol;
+            };
+            // convergence (gusto.py:150-161)
+            auto step_sum = [&]() {
                 double ds = 0.0;
                 for (int k = wave; k <= N; k += nw) {
                     double v2 = 0.0;
@@ -220,23 +205,19 @@ __global__ __launch_bounds__(NTHREADS) void gusto_kernel(QPDims d, QPConst c, Tp
                     v2 = wg::wave_sum(v2);
                     if (lane == 0) ds += sqrt(v2);
                 }
-                ds = wg::reduce(ds, 0, L.red);
-                const double dsol = (1.0 / N) * ((1.0 / n) * ds);
-                converged = (dsol <= par.convg_thresh) && X_ok;
-                new_solution = true;
-            }
+                return wg::reduce(ds, 0, L.red);
+            };
+            new_solution = gusto_judge(par, s, J, rho_k, N, n, viol_max, step_sum);
         } else {
-            omega = par.gamma_fail * omega;
+            gusto_outside(par, s);
         }
-        if (b.trace && itr < par.max_trace && tid == 0) {
-            double *tr = b.trace + (p * par.max_trace + itr) * 4;
-            tr[0] = J; tr[1] = d_cur; tr[2] = o_cur; tr[3] = rho_k;
+        gusto_trace_row(par, b.trace, p, s.itr, tid, J, d_cur, o_cur, rho_k, [&](double *tr) {
             if (par.poison_warm & 2) tr[3] = (double)(qit + 1000 * (qpass + 1));     // debug (SRH_GUSTO_TRACE_QIT=1): interior-point iterations + 1000 (pass + 1)
-        }
+        });
         // the next QP keeps this linearisation point when the step was rejected (smaller delta or larger omega, same relaxed
         // minimiser): if this one already ended on the boundary of its trust region the next one is certain to bind
         tr_hot = on_boundary && !new_solution;
-        ++itr;
+        ++s.itr;
         GU_LAP(6);
         if (new_solution) {
             __syncthreads();
@@ -252,22 +233,11 @@ __global__ __launch_bounds__(NTHREADS) void gusto_kernel(QPDims d, QPConst c, Tp
 #ifdef SRH_PROFILE
     if (tid == 0 && blockIdx.x == 0)
         printf("gusto clocks (%d iterations): init+nearest %lld loop-top %lld qp %lld tr-test %lld nearest(new) %lld accuracy %lld tests %lld accept+nearest %lld\n",
-               itr, gup[0], gup[1], gup[2], gup[3], gup[4], gup[5], gup[6], gup[7]);
+               s.itr, gup[0], gup[1], gup[2], gup[3], gup[4], gup[5], gup[6], gup[7]);
 #endif
-    if (status == 0) {
-        if (omega > par.omega_max) status = 2;
-        else if (itr - 1 > par.max_iters) status = 3;
-    }
-    __syncthreads();
-    for (int e = tid; e < (N + 1) * n; e += nt) b.xopt[p * (size_t)(N + 1) * n + e] = xk[e];
-    for (int e = tid; e < N * m; e += nt) b.uopt[p * (size_t)N * m + e] = uk[e];
-    for (int e = tid; e < (N + 1) * nz; e += nt) {
-        const int k = e / nz, a = e - k * nz;
-        double v = 0.0;
-        for (int j = 0; j < n; ++j) v = fma(c.H[a * n + j], xk[(size_t)k * n + j], v);
-        b.zopt[p * (size_t)(N + 1) * nz + e] = v;
-    }
-    if (tid == 0) { b.iters[p] = itr; b.status[p] = status; if (b.last_iters) b.last_iters[p] = itr; if (b.Jopt) b.Jopt[p] = J_prev; }
+    status = gusto_final_status(par, s, status);
+    gusto_write_out(b.xopt, b.uopt, b.zopt, p, N, n, m, nz, c.H, xk, uk, tid, nt);
+    if (tid == 0) { b.iters[p] = s.itr; b.status[p] = status; if (b.last_iters) b.last_iters[p] = s.itr; if (b.Jopt) b.Jopt[p] = s.J_prev; }
 }
 
 
@@ -326,6 +296,24 @@ void sgusto_default_params(sgusto_params *p) {
     if (!p) return;
     p->delta0 = 1e4; p->omega0 = 1.0; p->rho = 0.1; p->beta_fail = 0.5; p->gamma_fail = 5.0;
     p->epsilon = 0.01; p->omega_max = 1e10; p->convg_thresh = 0.1; p->max_gusto_iters = 500;
+}
+
+int sgusto_rule_replay(const sgusto_params *p, int N, int n, int T, const double *script, double *steps, int32_t *iters, int32_t *status,
+                       int32_t *converged) {
+    SRH_REQUIRE(p && script && steps && iters && status && converged && N > 0 && n > 0 && T >= 0, "sgusto_rule_replay: bad argument");
+    const GustoPar par = gusto_par(p, 0.0, 0);
+    GustoState s = gusto_start(par);
+    for (; s.itr < T && gusto_running(par, s); ++s.itr) {
+        const double *q = script + 5 * (size_t)s.itr;          // the QP's answer: md, J, rho_k, viol, dsum
+        double *o = steps + 4 * (size_t)s.itr;
+        o[0] = s.delta; o[1] = s.omega;
+        bool new_solution = false;
+        if (gusto_inside(par, s, q[0])) new_solution = gusto_judge(par, s, q[1], q[2], N, n, [&] { return q[3]; }, [&] { return q[4]; });
+        else gusto_outside(par, s);
+        o[2] = new_solution ? 1.0 : 0.0; o[3] = s.J_prev;
+    }
+    *iters = s.itr; *status = gusto_final_status(par, s, 0); *converged = s.converged ? 1 : 0;
+    return SRH_OK;
 }
 
 

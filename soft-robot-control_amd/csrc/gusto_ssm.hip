@@ -264,13 +264,8 @@ __global__ __launch_bounds__(SSM_THREADS) void gusto_ssm_kernel(QPDims d, QPCons
     cgptr zp = (cgptr)(b.z ? b.z + p * (size_t)(N + 1) * nz : nullptr);
     cgptr udp = (cgptr)(b.ud ? b.ud + p * (size_t)N * m : nullptr);
     if (b.host_args) {
-        gptr x0c = base + gw.x0c, zc = base + gw.zc, udc = base + gw.udc;
-        for (int e = tid; e < n; e += nt) x0c[e] = x0[e];
-        if (zp) for (int e = tid; e < (N + 1) * nz; e += nt) zc[e] = zp[e];
-        if (udp) for (int e = tid; e < N * m; e += nt) udc[e] = udp[e];
-        x0 = (cgptr)x0c;
-        if (zp) zp = (cgptr)zc;
-        if (udp) udp = (cgptr)udc;
+        cgptr no_zf = nullptr;                             // (no terminal target in this QP)
+        gusto_stage_args(x0, zp, no_zf, udp, base + gw.x0c, base + gw.zc, (gptr)nullptr, base + gw.udc, N, n, m, nz, true, tid, nt);
     }
     for (int e = tid; e < (N + 1) * n; e += nt) xk[e] = b.x_init[p * (size_t)(N + 1) * n + e];
     for (int e = tid; e < N * m; e += nt) uk[e] = b.u_init[p * (size_t)N * m + e];
@@ -430,16 +425,15 @@ __global__ __launch_bounds__(SSM_THREADS) void gusto_ssm_kernel(QPDims d, QPCons
     gptr rec = base + gw.rec;
     // have_warm: the work block holds the minimiser and multipliers of a converged lean QP -- of this solve, or (warm_across: the reference's
     // warm_start=True keeps its solver state between solves, locp.py:181) of the rollout's previous solve
-    bool have_warm = (GXL > 0 || dense_u) && par.warm_across != 0 && rec[0] == 1.0;
+    bool have_warm = (GXL > 0 || dense_u) && par.warm_across != 0 && rec[SSM_REC_WARM] == 1.0;
     gptr lamd = base + gw.lamd;
     double qdbg[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};              // phase clocks of the last dense one-wave QP (SRH_GUSTO_TRACE_QIT=1: trace row 1)
-    double delta = par.delta0, omega = par.omega0;
-    double J_prev = INFINITY, d_prev = INFINITY, o_prev = INFINITY;
-    bool converged = false, tr_hot = false;
-    int itr = 0, status = 0;
-    while (itr <= par.max_iters && !converged && omega <= par.omega_max) {
+    GustoState s = gusto_start(par);
+    bool tr_hot = false;
+    int status = 0;
+    while (gusto_running(par, s)) {
         tid = SRH_TID;
-        QPData q{(cgptr)x0a, (cgptr)xka, zp, (cgptr)nullptr, udp, delta, omega, (gptr)nullptr};
+        QPData q{(cgptr)x0a, (cgptr)xka, zp, (cgptr)nullptr, udp, s.delta, s.omega, (gptr)nullptr};
         double J;
         int qit, qpass = -1;
         __syncthreads();
@@ -486,11 +480,11 @@ __global__ __launch_bounds__(SSM_THREADS) void gusto_ssm_kernel(QPDims d, QPCons
             md = fmax(md, fabs(c.xs[j] * (w.x[(size_t)k * na + j] - xk[e])));
         }
         md = wg::reduce(md, 1, red);
-        const bool tr_ok = !(md - delta > par.epsilon);
-        const bool on_boundary = md >= delta * (1.0 - 1e-9);
+        const bool tr_ok = gusto_inside(par, s, md);
+        const bool on_boundary = gusto_on_boundary(s, md);
         bool new_solution = false;
         double rho_k = -1.0;
-        const double d_cur = delta, o_cur = omega;
+        const double d_cur = s.delta, o_cur = s.omega;
         if (tr_ok) {
             // model accuracy (gusto.py:203-223): f = A x + B u + d with the CONTINUOUS Jacobians at each point (models/ssm.py:35-54)
             if (tab && task_stride > 0) {
@@ -587,12 +581,8 @@ __global__ __launch_bounds__(SSM_THREADS) void gusto_ssm_kernel(QPDims d, QPCons
             double err = 0.0, app = 0.0;
             for (int i = 0; i < N; ++i) { err += accb[2 * i]; app += accb[2 * i + 1]; }
             rho_k = err / (J + app);
-            if (rho_k > par.rho && itr != 1) {
-                delta = par.beta_fail * delta;
-            } else {
-                if (d_prev == delta && o_prev == omega && J_prev <= J) delta = par.beta_fail * delta;
-                d_prev = delta; J_prev = J; o_prev = omega;
-                // state-constraint violation (gusto.py:185-201): X applied to the states, all k = 0..N
+            // state-constraint violation (gusto.py:185-201): X applied to the states, all k = 0..N
+            auto viol_max = [&]() {
                 double viol = 0.0;
                 if (b.nXv > 0) {
                     for (int k = tid; k <= N; k += nt) {
@@ -607,9 +597,10 @@ __global__ __launch_bounds__(SSM_THREADS) void gusto_ssm_kernel(QPDims d, QPCons
                     }
                     viol = wg::reduce(viol, 1, red);
                 }
-                const bool X_ok = !(viol > par.epsilon);
-                if (!X_ok) omega = par.gamma_fail * omega;
-                // convergence (gusto.py:150-161)
+                return viol;
+            };
+            // convergence (gusto.py:150-161)
+            auto step_sum = [&]() {
                 double ds = 0.0;
                 for (int k = tid; k <= N; k += nt) {
                     double v2 = 0.0;
@@ -619,25 +610,21 @@ __global__ __launch_bounds__(SSM_THREADS) void gusto_ssm_kernel(QPDims d, QPCons
                     }
                     ds += sqrt(v2);
                 }
-                ds = wg::reduce(ds, 0, red);
-                const double dsol = (1.0 / N) * ((1.0 / n) * ds);
-                converged = (dsol <= par.convg_thresh) && X_ok;
-                new_solution = true;
-            }
+                return wg::reduce(ds, 0, red);
+            };
+            new_solution = gusto_judge(par, s, J, rho_k, N, n, viol_max, step_sum);
         } else {
-            omega = par.gamma_fail * omega;
+            gusto_outside(par, s);
         }
-        if (b.trace && itr < par.max_trace && tid == 0) {
-            double *tr = b.trace + (p * par.max_trace + itr) * 4;
-            tr[0] = J; tr[1] = d_cur; tr[2] = o_cur; tr[3] = rho_k;
+        gusto_trace_row(par, b.trace, p, s.itr, tid, J, d_cur, o_cur, rho_k, [&](double *tr) {
             if (par.poison_warm & 2) {                     // debug (SRH_GUSTO_TRACE_QIT=1): shader clocks of the phases + interior-point iterations
                 lap_tests += clock64() - lap0;
                 tr[0] = (double)lap_lin; tr[1] = (double)lap_qp; tr[2] = (double)lap_tests; tr[3] = (double)(qit + 1000 * (qpass + 1));
                 if (par.max_trace >= 4) for (int i = 0; i < 10; ++i) tr[4 + i] = qdbg[i];     // rows 1..3 of the trace (a one-iteration solve leaves them free)
             }
-        }
+        });
         tr_hot = on_boundary && !new_solution;
-        ++itr;
+        ++s.itr;
         if (new_solution) {
             __syncthreads();
             for (int e = tid; e < (N + 1) * n; e += nt) { const int k = e / n, j = e - k * n; xk[e] = w.x[(size_t)k * na + j]; }
@@ -646,20 +633,9 @@ __global__ __launch_bounds__(SSM_THREADS) void gusto_ssm_kernel(QPDims d, QPCons
             if (par.max_iters >= 1) linearise_all();          // gusto.py:458-473
         }
     }
-    if (status == 0) {
-        if (omega > par.omega_max) status = 2;
-        else if (itr - 1 > par.max_iters) status = 3;
-    }
-    __syncthreads();
-    for (int e = tid; e < (N + 1) * n; e += nt) b.xopt[p * (size_t)(N + 1) * n + e] = xk[e];
-    for (int e = tid; e < N * m; e += nt) b.uopt[p * (size_t)N * m + e] = uk[e];
-    for (int e = tid; e < (N + 1) * nz; e += nt) {
-        const int k = e / nz, a = e - k * nz;
-        double v = 0.0;
-        for (int j = 0; j < n; ++j) v = fma(b.Hm[a * n + j], xk[(size_t)k * n + j], v);
-        b.zopt[p * (size_t)(N + 1) * nz + e] = v;
-    }
-    if (tid == 0) { rec[0] = have_warm ? 1.0 : 0.0; b.iters[p] = itr; b.status[p] = status; if (b.Jopt) b.Jopt[p] = J_prev; }
+    status = gusto_final_status(par, s, status);
+    gusto_write_out(b.xopt, b.uopt, b.zopt, p, N, n, m, nz, b.Hm, xk, uk, tid, nt);
+    if (tid == 0) { rec[SSM_REC_WARM] = have_warm ? 1.0 : 0.0; b.iters[p] = s.itr; b.status[p] = status; if (b.Jopt) b.Jopt[p] = s.J_prev; }
 }
 
 }  // namespace

@@ -68,15 +68,7 @@ __global__ __launch_bounds__(lean_threads(NST, J0SEL), 2) void gusto_lean_kernel
     if (NST < 0 || b.host_args) {
         // zero-copy solves (gusto.hip) pass pinned HOST pointers: x0, the targets and the desired inputs would be read across PCIe by every
         // QP and interior-point iteration -- keep copies in the work block (the fused kernel finds them there when it resumes a rollout)
-        gptr x0c = base + gw.x0c, zc = base + gw.zc, zfc = base + gw.zfc, udc = base + gw.udc;
-        for (int e = tid; e < n; e += nt) x0c[e] = x0[e];
-        if (zp) for (int e = tid; e < (N + 1) * nz; e += nt) zc[e] = zp[e];
-        if (zfp) for (int e = tid; e < nz; e += nt) zfc[e] = zfp[e];
-        if (udp) for (int e = tid; e < N * m; e += nt) udc[e] = udp[e];
-        x0 = (cgptr)x0c;
-        if (zp) zp = (cgptr)zc;
-        if (zfp) zfp = (cgptr)zfc;
-        if (udp) udp = (cgptr)udc;
+        gusto_stage_args(x0, zp, zfp, udp, base + gw.x0c, base + gw.zc, base + gw.zfc, base + gw.udc, N, n, m, nz, true, tid, nt);
     }
     for (int e = tid; e < (N + 1) * n; e += nt) xk[e] = b.x_init[p * (size_t)(N + 1) * n + e];
     for (int e = tid; e < N * m; e += nt) uk[e] = b.u_init[p * (size_t)N * m + e];
@@ -85,14 +77,13 @@ __global__ __launch_bounds__(lean_threads(NST, J0SEL), 2) void gusto_lean_kernel
     GU_LAP(0);
 
     QPDyn dyn{T.Ad, T.AdT, T.Bd, T.BdT, T.dd, (cgiptr)idx};
-    double delta = par.delta0, omega = par.omega0;
-    double J_prev = INFINITY, d_prev = INFINITY, o_prev = INFINITY;
+    GustoState s = gusto_start(par);
     // have_warm: w.u / w.lam of the work block hold a converged QP -- of this solve, or (warm_across) of the rollout's previous solve
-    bool converged = false, handed_over = false, have_warm = GXSEL > 0 && par.warm_across != 0 && rec[8] == 1.0;
-    int itr = 0, status = 0;
-    while (itr <= par.max_iters && !converged && omega <= par.omega_max) {
+    bool handed_over = false, have_warm = GXSEL > 0 && par.warm_across != 0 && rec[REC_WARM] == 1.0;
+    int status = 0;
+    while (gusto_running(par, s)) {
         tid = SRH_TID; lane = tid & 63;
-        QPData q{x0, xk, zp, zfp, udp, delta, omega, (gptr)nullptr};
+        QPData q{x0, xk, zp, zfp, udp, s.delta, s.omega, (gptr)nullptr};
         double J;
         int qit;
         GU_LAP(1);
@@ -107,14 +98,12 @@ __global__ __launch_bounds__(lean_threads(NST, J0SEL), 2) void gusto_lean_kernel
         // test knob (SRH_LEAN_FORCE_HANDOVER=k at plan creation): hand SCP iteration k to the fused kernel as if its relaxed minimiser
         // had left the trust region -- the full QP the fused kernel then solves has the same minimiser, so the solve must come out the
         // same through the hand-over record, the resume launch and the host paths around them
-        if (st == 0 && (par.poison_warm >> 4) - 1 == itr) st = 100;
+        if (st == 0 && (par.poison_warm >> 4) - 1 == s.itr) st = 100;
         have_warm = st == 0;
         GU_LAP(2);
         if (st != 0) {                               // the fused kernel takes this rollout from here
             if (tid == 0) {
-                rec[0] = 1.0; rec[1] = delta; rec[2] = omega; rec[3] = J_prev; rec[4] = d_prev; rec[5] = o_prev; rec[6] = (double)itr;
-                rec[7] = (double)st;                  // 100: relaxed minimiser outside the trust region (the fused kernel skips its own relaxed attempts)
-                rec[8] = 0.0;                         // (the fused kernel carves the block differently: nothing to start the next solve from)
+                gusto_rec_save(rec, s, st);          // st = 100: relaxed minimiser outside the trust region (the fused kernel skips its own relaxed attempts)
                 if (b.handed_over) atomicAdd(b.handed_over, 1);
             }
             handed_over = true;
@@ -136,10 +125,10 @@ __global__ __launch_bounds__(lean_threads(NST, J0SEL), 2) void gusto_lean_kernel
         double md = 0.0;
         for (int e = tid; e < (N + 1) * n; e += nt) md = fmax(md, fabs(c.xs[e % n] * (Xn[e] - Xo[e])));
         md = wg::reduce(md, 1, L.red);
-        const bool tr_ok = !(md - delta > par.epsilon);
+        const bool tr_ok = gusto_inside(par, s, md);
         bool new_solution = false;
         double rho_k = -1.0;
-        const double d_cur = delta, o_cur = omega;
+        const double d_cur = s.delta, o_cur = s.omega;
         if (tr_ok) {
             // model accuracy (gusto.py:203-223) with continuous nearest-point dynamics
             GU_LAP(3);
@@ -213,12 +202,8 @@ __global__ __launch_bounds__(lean_threads(NST, J0SEL), 2) void gusto_lean_kernel
             double err = 0.0, app = 0.0;      // sequential sums in stage order, as the reference loop
             for (int i = 0; i < N; ++i) { err += accb[2 * i]; app += accb[2 * i + 1]; }
             rho_k = err / (J + app);
-            if (rho_k > par.rho && itr != 1) {
-                delta = par.beta_fail * delta;
-            } else {
-                if (d_prev == delta && o_prev == omega && J_prev <= J) delta = par.beta_fail * delta;
-                d_prev = delta; J_prev = J; o_prev = omega;
-                // state-constraint violation (gusto.py:185-201): all k = 0..N
+            // state-constraint violation (gusto.py:185-201): all k = 0..N
+            auto viol_max = [&]() {
                 double viol = 0.0;
                 if (d.nX > 0 && d.nX <= nz) {
                     // one thread per (stage, row) for the n_x products of a row (one thread per stage walked n_X n_x = 240 of them),
@@ -257,9 +242,10 @@ __global__ __launch_bounds__(lean_threads(NST, J0SEL), 2) void gusto_lean_kernel
                     }
                     viol = wg::reduce(viol, 1, L.red);
                 }
-                const bool X_ok = !(viol > par.epsilon);
-                if (!X_ok) omega = par.gamma_fail * omega;
-                // convergence (gusto.py:150-161)
+                return viol;
+            };
+            // convergence (gusto.py:150-161)
+            auto step_sum = [&]() {
                 double ds = 0.0;
                 for (int k = wave; k <= N; k += nw) {
                     double v2 = 0.0;
@@ -270,19 +256,14 @@ __global__ __launch_bounds__(lean_threads(NST, J0SEL), 2) void gusto_lean_kernel
                     v2 = wg::wave_sum(v2);
                     if (lane == 0) ds += sqrt(v2);
                 }
-                ds = wg::reduce(ds, 0, L.red);
-                const double dsol = (1.0 / N) * ((1.0 / n) * ds);
-                converged = (dsol <= par.convg_thresh) && X_ok;
-                new_solution = true;
-            }
+                return wg::reduce(ds, 0, L.red);
+            };
+            new_solution = gusto_judge(par, s, J, rho_k, N, n, viol_max, step_sum);
         } else {
-            omega = par.gamma_fail * omega;
+            gusto_outside(par, s);
         }
-        if (b.trace && itr < par.max_trace && tid == 0) {
-            double *tr = b.trace + (p * par.max_trace + itr) * 4;
-            tr[0] = J; tr[1] = d_cur; tr[2] = o_cur; tr[3] = rho_k;
-        }
-        ++itr;
+        gusto_trace_row(par, b.trace, p, s.itr, tid, J, d_cur, o_cur, rho_k, [](double *) {});
+        ++s.itr;
         GU_LAP(6);
         if (new_solution) {
             __syncthreads();
@@ -298,7 +279,7 @@ __global__ __launch_bounds__(lean_threads(NST, J0SEL), 2) void gusto_lean_kernel
 #ifdef SRH_PROFILE
     if (tid == 0 && blockIdx.x == 0) {
         printf("lean gusto clocks (%d iterations): init+nearest %lld loop-top %lld qp %lld tr-test %lld nearest(new) %lld accuracy %lld tests %lld accept+nearest %lld\n",
-               itr, gup[0], gup[1], gup[2], gup[3], gup[4], gup[5], gup[6], gup[7]);
+               s.itr, gup[0], gup[1], gup[2], gup[3], gup[4], gup[5], gup[6], gup[7]);
         printf("lean qp laps: setup+rollout %lld rows %lld condense %lld stage-factors %lld gram %lld cholesky %lld grad+newton %lld steps %lld\n",
                prof[0], prof[1], prof[2], prof[3], prof[4], prof[5], prof[6], prof[7]);
         printf("lean newton laps: gradients %lld gT(1) %lld rhs+dinv %lld g(1) %lld k_solve %lld gT(2) %lld du %lld g(2) %lld\n",
@@ -311,23 +292,12 @@ __global__ __launch_bounds__(lean_threads(NST, J0SEL), 2) void gusto_lean_kernel
     }
 #endif
     if (handed_over) {
-        if (tid == 0) { b.iters[p] = itr; b.status[p] = LEAN_PENDING; }
+        if (tid == 0) { b.iters[p] = s.itr; b.status[p] = LEAN_PENDING; }
         return;
     }
-    if (status == 0) {
-        if (omega > par.omega_max) status = 2;
-        else if (itr - 1 > par.max_iters) status = 3;
-    }
-    __syncthreads();
-    for (int e = tid; e < (N + 1) * n; e += nt) b.xopt[p * (size_t)(N + 1) * n + e] = xk[e];
-    for (int e = tid; e < N * m; e += nt) b.uopt[p * (size_t)N * m + e] = uk[e];
-    for (int e = tid; e < (N + 1) * nz; e += nt) {
-        const int k = e / nz, a = e - k * nz;
-        double v = 0.0;
-        for (int j = 0; j < n; ++j) v = fma(c.H[a * n + j], xk[(size_t)k * n + j], v);
-        b.zopt[p * (size_t)(N + 1) * nz + e] = v;
-    }
-    if (tid == 0) { rec[0] = 0.0; rec[8] = have_warm ? 1.0 : 0.0; b.iters[p] = itr; b.status[p] = status; if (b.last_iters) b.last_iters[p] = itr; if (b.Jopt) b.Jopt[p] = J_prev; }
+    status = gusto_final_status(par, s, status);
+    gusto_write_out(b.xopt, b.uopt, b.zopt, p, N, n, m, nz, c.H, xk, uk, tid, nt);
+    if (tid == 0) { rec[REC_PENDING] = 0.0; rec[REC_WARM] = have_warm ? 1.0 : 0.0; b.iters[p] = s.itr; b.status[p] = status; if (b.last_iters) b.last_iters[p] = s.itr; if (b.Jopt) b.Jopt[p] = s.J_prev; }
 }
 
 template <int MSEL, int NSEL, int GXSEL, int NST, int J0SEL, int NXR>

@@ -1,5 +1,7 @@
-// Kernel argument blocks shared by the fused kernels (scp.hip, gusto.hip) and the lean condensed kernels (lean.hip), and
-// the launch entry points of the latter (lean.hip is its own translation unit: the variants compile in parallel).
+// What the SCP kernels (scp.hip, gusto.hip, lean.hip, gusto_ssm.hip) share: kernel argument blocks, the layouts of a rollout's work block and
+// of a plan's pinned block, GuSTO's step rule -- the (J, delta, omega) state machine of every GuSTO kernel and of the host replay
+// (sgusto_rule_replay), stated ONCE here; how a kernel walks its data to the numbers the rule judges is tuning and stays in the kernel --
+// with the TPWL kernels' hand-over record, and the launch entry points of lean.hip (its own translation unit: the variants compile in parallel).
 #pragma once
 #include "scp_host.h"
 
@@ -56,8 +58,105 @@ struct LocpBatch {
 namespace {
 
 constexpr int LEAN_PENDING = -77;       // status of a QP / rollout the lean kernel hands to the fused kernel
-constexpr int GUSTO_REC = 10;           // doubles of the resume record behind the SCP loop's index arrays ([8]: 1.0 = the work block holds a
-                                        // converged QP of the previous solve: GustoPar::warm_across)
+constexpr int GUSTO_REC = 10;           // doubles of the TPWL kernels' resume record behind the SCP loop's index arrays; its slots:
+enum GustoRecSlot {
+    REC_PENDING = 0,                    // 1.0: the lean kernel handed this rollout over, the slots below hold its SCP state
+    REC_DELTA, REC_OMEGA, REC_J_PREV, REC_D_PREV, REC_O_PREV, REC_ITR,
+    REC_QP_STATUS,                      // status of the QP the lean kernel stopped at (100.0: relaxed minimiser outside the trust region)
+    REC_WARM                            // 1.0: the work block holds a converged lean QP of the previous solve (GustoPar::warm_across)
+};
+constexpr int SSM_REC_WARM = 0;         // the SSM kernel's own record (gusto_ssm.hip: SsmGustoWork::rec) has this one slot, meaning as REC_WARM
+
+// ---- GuSTO's step rule (sofacontrol/scp/gusto.py:371-428; reads like GuSTO._judge of sofacontrol_amd/scp/gusto.py).  Plain scalars, no
+// LDS, no barriers of its own.  A kernel's loop: gusto_start; while (gusto_running) { QP; md = max_k |x_scale (x_k - xbar_k)|_inf;
+// gusto_inside ? gusto_judge : gusto_outside; trace row; ++itr; move the linearisation point if accepted }; gusto_final_status.
+#define SRH_RULE __host__ __device__ __forceinline__
+// radius and penalty of the next QP; (J, delta, omega) of the last accepted step; QPs solved so far
+struct GustoState { double delta, omega, J_prev, d_prev, o_prev; int itr; bool converged; };
+SRH_RULE GustoState gusto_start(const GustoPar &par) { return GustoState{par.delta0, par.omega0, INFINITY, INFINITY, INFINITY, 0, false}; }
+SRH_RULE bool gusto_running(const GustoPar &par, const GustoState &s) { return s.itr <= par.max_iters && !s.converged && s.omega <= par.omega_max; }
+SRH_RULE bool gusto_inside(const GustoPar &par, const GustoState &s, double md) { return !(md - s.delta > par.epsilon); }      // gusto.py:174-183
+// the minimiser used the whole trust region: if the step is rejected the next QP (same linearisation point) is certain to bind (tr_hot)
+SRH_RULE bool gusto_on_boundary(const GustoState &s, double md) { return md >= s.delta * (1.0 - 1e-9); }
+SRH_RULE void gusto_outside(const GustoPar &par, GustoState &s) { s.omega = par.gamma_fail * s.omega; }       // harder penalty, same QP data
+// A step inside the trust region: accepted (true) or not.  viol() = the largest state-constraint violation (gusto.py:185-201), dsum() =
+// sum_k |x_scale (x_k - xbar_k)|_2 (gusto.py:150-161): callables, evaluated on the accept path only and in this order -- the kernels'
+// contain workgroup reductions, which every thread reaches because the rule is uniform over the workgroup.
+template <class Viol, class Dsum>
+SRH_RULE bool gusto_judge(const GustoPar &par, GustoState &s, double J, double rho_k, int N, int n, Viol &&viol, Dsum &&dsum) {
+    bool new_solution = false;
+    if (rho_k > par.rho && s.itr != 1) {
+        s.delta = par.beta_fail * s.delta;               // model too inaccurate over this step: shrink, same QP data
+    } else {
+        if (s.d_prev == s.delta && s.o_prev == s.omega && s.J_prev <= J) s.delta = par.beta_fail * s.delta;
+        s.d_prev = s.delta; s.J_prev = J; s.o_prev = s.omega;
+        const bool X_ok = !(viol() > par.epsilon);
+        if (!X_ok) s.omega = par.gamma_fail * s.omega;
+        const double dsol = (1.0 / N) * ((1.0 / n) * dsum());
+        s.converged = (dsol <= par.convg_thresh) && X_ok;
+        new_solution = true;
+    }
+    return new_solution;
+}
+// status of a solve whose loop ended: a QP failure (1) stands, else 2 = omega > omega_max, 3 = max iterations
+SRH_RULE int gusto_final_status(const GustoPar &par, const GustoState &s, int status) {
+    if (status == 0) {
+        if (s.omega > par.omega_max) status = 2;
+        else if (s.itr - 1 > par.max_iters) status = 3;
+    }
+    return status;
+}
+// The lean kernel hands a rollout it cannot finish to the fused kernel (mode 2) through the resume record: the state in front of the QP it
+// stopped at.  (The fused kernel carves the work block differently: nothing there to start the next solve from, REC_WARM = 0.)
+__device__ __forceinline__ void gusto_rec_save(gptr rec, const GustoState &s, int qp_status) {
+    rec[REC_PENDING] = 1.0; rec[REC_DELTA] = s.delta; rec[REC_OMEGA] = s.omega; rec[REC_J_PREV] = s.J_prev; rec[REC_D_PREV] = s.d_prev;
+    rec[REC_O_PREV] = s.o_prev; rec[REC_ITR] = (double)s.itr; rec[REC_QP_STATUS] = (double)qp_status; rec[REC_WARM] = 0.0;
+}
+// false: nothing pending.  (The caller clears REC_PENDING once every thread has read the record.)
+__device__ __forceinline__ bool gusto_rec_load(gptr rec, GustoState &s, int *qp_status) {
+    if (rec[REC_PENDING] != 1.0) return false;
+    s = GustoState{rec[REC_DELTA], rec[REC_OMEGA], rec[REC_J_PREV], rec[REC_D_PREV], rec[REC_O_PREV], (int)rec[REC_ITR], false}; *qp_status = (int)rec[REC_QP_STATUS];
+    return true;
+}
+// The arguments of a zero-copy solve (GustoBatch::host_args) sit in pinned HOST memory, where every QP / interior-point iteration would read
+// them: the kernel works on copies in the work block (x0, z, zf, ud -> x0c, zc, zfc, udc; a null argument stays null).  copy = false: an
+// earlier launch made the copies.
+__device__ __forceinline__ void gusto_stage_args(cgptr &x0, cgptr &zp, cgptr &zfp, cgptr &udp, gptr x0c, gptr zc, gptr zfc, gptr udc, int N, int n,
+                                                 int m, int nz, bool copy, int tid, int nt) {
+    if (copy) {
+        for (int e = tid; e < n; e += nt) x0c[e] = x0[e];
+        if (zp) for (int e = tid; e < (N + 1) * nz; e += nt) zc[e] = zp[e];
+        if (zfp) for (int e = tid; e < nz; e += nt) zfc[e] = zfp[e];
+        if (udp) for (int e = tid; e < N * m; e += nt) udc[e] = udp[e];
+    }
+    x0 = (cgptr)x0c;
+    if (zp) zp = (cgptr)zc;
+    if (zfp) zfp = (cgptr)zfc;
+    if (udp) udp = (cgptr)udc;
+}
+// Row `itr` of rollout p's trace (J, delta and omega of the QP, rho_k) by thread 0; debug(row): a kernel's own debug overwrite
+template <class Debug>
+__device__ __forceinline__ void gusto_trace_row(const GustoPar &par, double *trace, size_t p, int itr, int tid, double J, double d_cur, double o_cur,
+                                                double rho_k, Debug &&debug) {
+    if (trace && itr < par.max_trace && tid == 0) {
+        double *tr = trace + (p * par.max_trace + itr) * 4;
+        tr[0] = J; tr[1] = d_cur; tr[2] = o_cur; tr[3] = rho_k;
+        debug(tr);
+    }
+}
+// xopt, uopt and zopt = H xopt (gusto.py:486) of rollout p from its accepted iterate; by all threads
+template <class HPtr>
+__device__ __forceinline__ void gusto_write_out(double *xopt, double *uopt, double *zopt, size_t p, int N, int n, int m, int nz, HPtr H, gptr xk, gptr uk, int tid, int nt) {
+    __syncthreads();
+    for (int e = tid; e < (N + 1) * n; e += nt) xopt[p * (size_t)(N + 1) * n + e] = xk[e];
+    for (int e = tid; e < N * m; e += nt) uopt[p * (size_t)N * m + e] = uk[e];
+    for (int e = tid; e < (N + 1) * nz; e += nt) {
+        const int k = e / nz, a = e - k * nz;
+        double v = 0.0;
+        for (int j = 0; j < n; ++j) v = fma(H[a * n + j], xk[(size_t)k * n + j], v);
+        zopt[p * (size_t)(N + 1) * nz + e] = v;
+    }
+}
 
 // offsets (doubles) of the SCP loop's own arrays inside a rollout's work block
 struct GustoWork { size_t xk, uk, acc, idx, rec, x0c, zc, zfc, udc, end; };

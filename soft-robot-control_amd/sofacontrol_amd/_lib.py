@@ -150,3 +150,16 @@ class DeviceBuffer:
 
 def sync():
     check(lib().srh_sync(), 'srh_sync')
+
+
+def gusto_rule_replay(params, N, n_x, script):
+    """sgusto_rule_replay: GuSTO's step rule as the kernels run it (csrc/scp_types.h), replayed on the host -- no GPU needed.
+    params: dict with SGustoParams' field names; script (T x 5): the QP answers (md, J, rho_k, viol, dsum).  Returns
+    (steps (iters x 4): delta, omega of the QP, accepted, J_prev after the step; iters, status, converged)."""
+    par = SGustoParams(**params)
+    script = np.ascontiguousarray(script, dtype=np.float64).reshape(-1, 5)
+    steps = np.zeros((script.shape[0], 4))
+    iters, status, converged = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    check(lib().sgusto_rule_replay(C.byref(par), C.c_int(N), C.c_int(n_x), C.c_int(script.shape[0]), dptr(script), dptr(steps),
+                                   C.byref(iters), C.byref(status), C.byref(converged)), 'sgusto_rule_replay')
+    return steps[:iters.value], iters.value, status.value, bool(converged.value)
