@@ -428,6 +428,27 @@ void sgusto_default_params(sgusto_params *p);
 int sgusto_rule_replay(const sgusto_params *par, int N, int n_x, int T, const double *script, double *steps, int32_t *iters,
                        int32_t *status, int32_t *converged);
 
+/* The interior point's rule on one inequality row (csrc/ipm_rule.h: the functions all seven QP kernels call) evaluated on the HOST, one
+ * phase per call, over n rows.  rows (n x 8): g, t, lambda, rg, rc, dt, dlambda, a.d of each row (a phase reads what it needs); par (8)
+ * and the results out (n x 8, columns as listed) and scal (8) per phase:
+ *   INIT       par: unit weight                          out: D, rho, lambda
+ *   COLD       par: min g, max g                         out: t, lambda                 scal: the shifts sh_t, sh_l
+ *   WARM       par: poison (0 / 1); lambda = previous    out: t, lambda
+ *   PRED       par: dreg                                 out: rg, D, rho, running sum lambda t, running max |rg|
+ *   CORR       par: dreg, sigma, mu                      out: rc, rho
+ *   DIRECTION  par: dreg, pred (0 / 1)                   out: dlambda, dt, the step bound of t, of lambda, running bound (from 1e300)
+ *   AFFINE     par: amax, mu, row count                  out: the row's term at the affine step, running sum
+ *                                                        scal: a_aff, a (the step taken from this amax), mu_aff, sigma
+ *   ADVANCE    par: a                                    out: t, lambda
+ *   SCALES     par: max |target gradient|, max |U.b|, omega, delta, reg (n = 0)         scal: scale_d, scale_p, dreg
+ *   VERDICT    rows: ok (0 / 1), mu, rd, rp, iteration, row count; par: scale_d, scale_p, tol, max_iter, near_opt before the first row
+ *              out: the predictor's verdict (a status, or -1 = go on; near_opt carries from row to row), near_opt after it, the
+ *              verdict of a starting / corrector system with this ok, the verdict on this row count
+ * scal[7] = the warm-start floor in every phase.  Needs no GPU; for tests of the rule. */
+enum { SQP_IPM_INIT = 0, SQP_IPM_COLD, SQP_IPM_WARM, SQP_IPM_PRED, SQP_IPM_CORR, SQP_IPM_DIRECTION, SQP_IPM_AFFINE, SQP_IPM_ADVANCE,
+       SQP_IPM_SCALES, SQP_IPM_VERDICT };
+int sqp_ipm_rule_replay(int phase, int n, const double *rows, const double *par, double *out, double *scal);
+
 /* GuSTO.solve (gusto.py:283-487) on a pre-discretised nn-TPWL model, `batch` independent rollouts:
  *   x0 (batch x n_x), u_init (batch x N x n_u), x_init (batch x (N+1) x n_x), z (batch x (N+1) x n_z)
  *   or NULL, zf, u_des as slocp_solve; x_char / f_char (n_x,) or NULL (ones); dt = horizon step.

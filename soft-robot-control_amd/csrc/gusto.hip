@@ -316,6 +316,49 @@ int sgusto_rule_replay(const sgusto_params *p, int N, int n, int T, const double
     return SRH_OK;
 }
 
+int sqp_ipm_rule_replay(int phase, int n, const double *rows, const double *par, double *out, double *scal) {
+    SRH_REQUIRE(rows && par && out && scal && n >= 0, "sqp_ipm_rule_replay: bad argument");
+    double musum = 0.0, rpm = 0.0, amax = 1e300, ma = 0.0;
+    bool near_opt = par[4] != 0.0;                                 // SQP_IPM_VERDICT
+    for (int i = 0; i < n; ++i) {
+        const double *r = rows + 8 * (size_t)i;
+        double *o = out + 8 * (size_t)i;
+        const double g = r[0], t = r[1], lam = r[2], rg = r[3], rc = r[4], dt = r[5], dl = r[6], ad = r[7];
+        switch (phase) {
+        case SQP_IPM_INIT: ipm::init_row(g, par[0], o[0], o[1], o[2]); break;
+        case SQP_IPM_COLD: ipm::start_cold(g, ipm::start_shift(par[0], par[1]), o[0], o[1]); break;
+        case SQP_IPM_WARM: ipm::start_warm(g, [&] { return lam; }, par[0] != 0.0, o[0], o[1]); break;
+        case SQP_IPM_PRED: ipm::pred_row(g, t, lam, par[0], o[0], o[1], o[2], musum, rpm); o[3] = musum; o[4] = rpm; break;
+        case SQP_IPM_CORR: ipm::corr_row(t, lam, rg, dt, dl, par[1], par[2], par[0], o[0], o[1]); break;
+        case SQP_IPM_DIRECTION: {
+            ipm::direction(par[1] != 0.0, t, lam, rg, rc, ad, par[0], o[0], o[1]);
+            o[2] = o[3] = 1e300;                                   // the slack's bound and the multiplier's, each on its own
+            ipm::step_bound(t, lam, o[1], 0.0, o[2]);
+            ipm::step_bound(t, lam, 0.0, o[0], o[3]);
+            ipm::step_bound(t, lam, o[1], o[0], amax); o[4] = amax;
+        } break;
+        case SQP_IPM_AFFINE: o[0] = ipm::affine_term(t, lam, dt, dl, ipm::step_affine(par[0])); ma += o[0]; o[1] = ma; break;
+        case SQP_IPM_ADVANCE: o[0] = t; o[1] = lam; ipm::advance(par[0], dt, dl, o[0], o[1]); break;
+        case SQP_IPM_VERDICT:
+            o[0] = (double)ipm::verdict(r[0] != 0.0, r[1], r[2], r[3], par[0], par[1], par[2], (int)r[4], (int)par[3], near_opt);
+            o[1] = near_opt ? 1.0 : 0.0;
+            o[2] = (double)ipm::verdict_system(r[0] != 0.0); o[3] = (double)ipm::verdict_no_rows((int)r[5]);
+            break;
+        default: SRH_REQUIRE(false, "sqp_ipm_rule_replay: unknown phase");
+        }
+    }
+    if (phase == SQP_IPM_COLD) { const ipm::Shift sh = ipm::start_shift(par[0], par[1]); scal[0] = sh.t; scal[1] = sh.l; }
+    if (phase == SQP_IPM_AFFINE) {                                 // par: amax, mu, the QP's row count
+        scal[0] = ipm::step_affine(par[0]); scal[1] = ipm::step_length(par[0]);
+        scal[2] = ma / par[2]; scal[3] = ipm::centring(scal[2], par[1]);
+    }
+    if (phase == SQP_IPM_SCALES) {                                 // par: max |target gradient|, max |U.b|, omega, delta, reg
+        scal[0] = par[0]; scal[1] = par[1];
+        ipm::scales(par[2], par[3], par[4], scal[0], scal[1], scal[2]);
+    }
+    scal[7] = ipm::WARM_FLOOR;
+    return SRH_OK;
+}
 
 int sgusto_plan_create(sgusto_plan_t **out, stpwl_t *h, const slocp_problem *prob, const sgusto_params *par,
                        double dt, int64_t batch, const double *x_char, const double *f_char, int max_trace) {

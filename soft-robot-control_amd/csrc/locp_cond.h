@@ -857,12 +857,8 @@ __device__ __forceinline__ int solve(const QPDims &dfull, const QPConst &c, cons
                                      lptr smem, QPLds &Lq, int *iters_out, QPWork &wout) {
     int tid = SRH_TID;                                       // re-read at the top of every interior-point iteration (dev_la.h: SRH_TID)
     const int nt = blockDim.x;
-    QPDims d = dfull;                               // the QP without its trust-region rows
-    d.tr = 0;
-    d.nrx = d.nX;
-    d.RX = d.nrx + d.nXf;
-    d.NR = d.N * d.RX + d.N * d.nU;
-    d.ng = d.N * d.nrx + d.nXf + d.N * d.nU;
+    QPDims d = dfull;
+    drop_trust_region_rows(d);
     QPWork w;
     qp_carve(w, work_base, d);
     wout = w;
@@ -933,22 +929,16 @@ __device__ __forceinline__ int solve(const QPDims &dfull, const QPConst &c, cons
         for (int qi = 0; qi < QR; ++qi) {
             if (!rv[qi]) continue;
             const int e = tid + nt * qi;
+            double D, rho;                                  // of this row, to L2 for the stage sums
             if (mode == INIT) {
-                const double g = row_val(qi, L.y, L.u) - rh[qi];
-                w.D[e] = 1.0; w.rho[e] = g; rlam[qi] = 0.0;
+                ipm::init_row(row_val(qi, L.y, L.u) - rh[qi], 1.0, D, rho, rlam[qi]);
+                w.D[e] = D; w.rho[e] = rho;
             } else if (mode == PRED) {
-                const double g = row_val(qi, L.y, L.u) - rh[qi];
-                const double t = rt[qi], lam = rlam[qi], rg = g + t;
-                rrg[qi] = rg;
-                const double D = lam / (t + dreg * lam);
-                w.D[e] = D; w.rho[e] = D * (rg + dreg * lam); w.lam[e] = lam;
-                musum += lam * t;
-                rpm = fmax(rpm, fabs(rg));
+                ipm::pred_row(row_val(qi, L.y, L.u) - rh[qi], rt[qi], rlam[qi], dreg, rrg[qi], D, rho, musum, rpm);
+                w.D[e] = D; w.rho[e] = rho; w.lam[e] = rlam[qi];
             } else {
-                const double t = rt[qi], lam = rlam[qi];
-                const double rc = lam * t + rdt[qi] * rdl[qi] - sig * mu;
-                rrc[qi] = rc;
-                w.rho[e] = lam + (lam * rrg[qi] - rc) / (t + dreg * lam);
+                ipm::corr_row(rt[qi], rlam[qi], rrg[qi], rdt[qi], rdl[qi], sig, mu, dreg, rrc[qi], rho);
+                w.rho[e] = rho;
             }
         }
         if (mode == PRED) {
@@ -981,11 +971,11 @@ __device__ __forceinline__ int solve(const QPDims &dfull, const QPConst &c, cons
         QC_LAP(6);
         // ---------------- use the direction
         if (mode == INIT) {
-            if (!ok) { status = 2; break; }
+            if (ipm::stops(ipm::verdict_system(ok), status)) break;
             for (int e = tid; e < nm; e += nt) L.u[e] += L.du[e];
             for (int e = tid; e < ldG; e += nt) L.y[e] += L.dy[e];
             __syncthreads();
-            if (d.ng == 0) { status = 0; break; }
+            if (ipm::stops(ipm::verdict_no_rows(d.ng), status)) break;
             double zmin = INFINITY, zmax = -INFINITY;
 #pragma unroll
             for (int qi = 0; qi < QR; ++qi) {
@@ -996,18 +986,10 @@ __device__ __forceinline__ int solve(const QPDims &dfull, const QPConst &c, cons
             }
             zmin = wg::reduce(zmin, 2, L.red);
             zmax = wg::reduce(zmax, 1, L.red);
-            const double sh_t = zmax >= 0.0 ? 1.0 + zmax : 0.0, sh_l = zmin <= 0.0 ? 1.0 - zmin : 0.0;
+            const ipm::Shift sh = ipm::start_shift(zmin, zmax);
 #pragma unroll
-            for (int qi = 0; qi < QR; ++qi) { rt[qi] = -rrg[qi] + sh_t; rlam[qi] = rrg[qi] + sh_l; }
-            for (int e = tid; e < d.n; e += nt) {
-                double g = 0.0;
-                if (q.z) for (int a = 0; a < d.nz; ++a) g = fma(c.HtQz2[e * d.nz + a], -q.z[d.nz + a], g);
-                sd = fmax(sd, fabs(g));
-            }
-            for (int e = tid; e < d.nU; e += nt) sp = fmax(sp, fabs(c.Ub[e]));
-            sd = fmax(wg::reduce(sd, 1, L.red), q.omega);
-            sp = fmax(wg::reduce(sp, 1, L.red), fabs(q.delta));
-            dreg = d.reg / sd;
+            for (int qi = 0; qi < QR; ++qi) ipm::start_cold(rrg[qi], sh, rt[qi], rlam[qi]);
+            qp::residual_scales(d, c, q, tid, nt, sd, sp, dreg, [&](double &a, double &b) { a = wg::reduce(a, 1, L.red); b = wg::reduce(b, 1, L.red); });
             mode = PRED;
             continue;
         }
@@ -1017,43 +999,34 @@ __device__ __forceinline__ int solve(const QPDims &dfull, const QPConst &c, cons
 #pragma unroll
             for (int qi = 0; qi < QR; ++qi) {
                 if (!rv[qi]) continue;
-                const double t = rt[qi], lam = rlam[qi], rga = rrg[qi] + row_val(qi, L.dy, L.du);
-                const double dl = ((mode == PRED ? -lam * t : -rrc[qi]) + lam * rga) / (t + dreg * lam);
-                const double dtv = -rga + dreg * dl;
-                rdl[qi] = dl; rdt[qi] = dtv;
-                if (dtv < 0.0) amax = fmin(amax, -t / dtv);
-                if (dl < 0.0) amax = fmin(amax, -lam / dl);
+                ipm::direction(mode == PRED, rt[qi], rlam[qi], rrg[qi], rrc[qi], row_val(qi, L.dy, L.du), dreg, rdl[qi], rdt[qi]);
+                ipm::step_bound(rt[qi], rlam[qi], rdt[qi], rdl[qi], amax);
             }
         }
         amax = wg::reduce(amax, 2, L.red);
         if (mode == PRED) {
-            if (!ok) { status = near_opt ? 0 : 2; break; }
-            if (!(mu == mu)) { status = near_opt ? 0 : 5; break; }
-            if (!(rd == rd)) { status = near_opt ? 0 : 6; break; }
+            if (ipm::stops(ipm::verdict_failed(ok, mu, rd, near_opt), status)) break;
             if (q.dbg && tid == 0) { gptr g = q.dbg + 8 * it; g[0] = mu; g[1] = rd; g[2] = rp; g[3] = sd; g[4] = sp; }
-            const double ltol = fmax(d.tol, 1e-9);
-            if (rd <= ltol * sd && rp <= ltol * sp && mu <= d.tol) { status = 0; break; }
-            near_opt = (rd <= 1e-8 * sd && rp <= 1e-8 * sp && mu <= 1e-8);
-            if (it >= d.max_iter) { status = 1; break; }
-            const double a_aff = fmin(1.0, amax);
+            if (ipm::stops(ipm::verdict_converged(mu, rd, rp, sd, sp, d.tol, it, d.max_iter, near_opt), status)) break;
+            const double a_aff = ipm::step_affine(amax);
             double ma = 0.0;
 #pragma unroll
             for (int qi = 0; qi < QR; ++qi)
-                if (rv[qi]) ma += (rlam[qi] + a_aff * rdl[qi]) * (rt[qi] + a_aff * rdt[qi]);
+                if (rv[qi]) ma += ipm::affine_term(rt[qi], rlam[qi], rdt[qi], rdl[qi], a_aff);
             const double mu_aff = wg::reduce(ma, 0, L.red) / d.ng;
-            sig = mu > 0.0 ? (mu_aff / mu) * (mu_aff / mu) * (mu_aff / mu) : 0.0;
+            sig = ipm::centring(mu_aff, mu);
             if (q.dbg && tid == 0) { gptr g = q.dbg + 8 * it; g[5] = a_aff; g[6] = sig; }
             mode = CORR;
             continue;
         }
         // mode == CORR: step
-        if (!ok) { status = 2; break; }
-        const double a = fmin(1.0, 0.99 * amax);
+        if (ipm::stops(ipm::verdict_system(ok), status)) break;
+        const double a = ipm::step_length(amax);
         if (q.dbg && tid == 0) { gptr g = q.dbg + 8 * it; g[7] = a; }
         for (int e = tid; e < nm; e += nt) L.u[e] += a * L.du[e];
         for (int e = tid; e < ldG; e += nt) L.y[e] += a * L.dy[e];
 #pragma unroll
-        for (int qi = 0; qi < QR; ++qi) { rt[qi] += a * rdt[qi]; rlam[qi] += a * rdl[qi]; }
+        for (int qi = 0; qi < QR; ++qi) ipm::advance(a, rdt[qi], rdl[qi], rt[qi], rlam[qi]);
         __syncthreads();
         ++it;
         mode = PRED;

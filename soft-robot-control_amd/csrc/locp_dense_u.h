@@ -247,7 +247,6 @@ __device__ __forceinline__ int solve(const QPDims &d, const QPConst &c, const QP
         };
         QDU_LAP(1);
         // ---- the interior point (ql::ipm_box's iteration)
-        constexpr double WARM_FLOOR = 1e-2;
         const double ng = (double)nr;
         if (lane < 16) ul[lane] = (warm && lane < nu) ? w.u[lane] : 0.0;
         fence();
@@ -256,19 +255,9 @@ __device__ __forceinline__ int solve(const QPDims &d, const QPConst &c, const QP
         int mode = INIT;
         double mu = 0.0, rp = 0.0, sig = 0.0, sd = 1.0, sp = 1.0, dreg = 0.0;
         bool near_opt = false;
-        auto scales = [&]() {
-            for (int e = lane; e < n; e += 64) {
-                double gq = 0.0;
-                if (q.z) for (int a = 0; a < nz; ++a) gq = fma(c.HtQz2[e * nz + a], -q.z[nz + a], gq);
-                sd = fmax(sd, fabs(gq));
-            }
-            for (int e = lane; e < d.nU; e += 64) sp = fmax(sp, fabs(c.Ub[e]));
-            sd = fmax(wg::wave_max(sd), q.omega);
-            sp = fmax(wg::wave_max(sp), fabs(q.delta));
-            dreg = d.reg / sd;
-        };
+        auto scales = [&]() { qp::residual_scales(d, c, q, lane, 64, sd, sp, dreg, [](double &a, double &b) { a = wg::wave_max(a); b = wg::wave_max(b); }); };
         if (warm && nr > 0) {
-            if (isrow) { tr_ = fmax(-(row_dot(ul) - hr), WARM_FLOOR); lr = fmax(lam[lane], WARM_FLOOR); }
+            if (isrow) ipm::start_warm(row_dot(ul) - hr, [&] { return lam[lane]; }, false, tr_, lr);
             scales();
             mode = PRED;
         }
@@ -277,17 +266,9 @@ __device__ __forceinline__ int solve(const QPDims &d, const QPConst &c, const QP
             double Dw = 0.0, rho = 0.0, musum = 0.0, rpm = 0.0;
             if (isrow) {
                 const double gq = mode != CORR ? row_dot(ul) - hr : 0.0;          // (the corrector's rows use the predictor's residuals)
-                if (mode == INIT) { Dw = 1.0; rho = gq; lr = 0.0; }
-                else if (mode == PRED) {
-                    rg = gq + tr_;
-                    Dw = lr / (tr_ + dreg * lr);
-                    rho = Dw * (rg + dreg * lr);
-                    musum = lr * tr_;
-                    rpm = fabs(rg);
-                } else {
-                    rc = lr * tr_ + dtr * dlr - sig * mu;
-                    rho = lr + (lr * rg - rc) / (tr_ + dreg * lr);
-                }
+                if (mode == INIT) ipm::init_row(gq, 1.0, Dw, rho, lr);
+                else if (mode == PRED) ipm::pred_row(gq, tr_, lr, dreg, rg, Dw, rho, musum, rpm);
+                else ipm::corr_row(tr_, lr, rg, dtr, dlr, sig, mu, dreg, rc, rho);
             }
             if (mode != CORR) sdl[lane] = sqrt(Dw);
             rhol[lane] = rho;
@@ -312,49 +293,38 @@ __device__ __forceinline__ int solve(const QPDims &d, const QPConst &c, const QP
             if (ok) msolve();
             QDU_LAP(4);
             if (mode == INIT) {
-                if (!ok) { status = 2; break; }
+                if (ipm::stops(ipm::verdict_system(ok), status)) break;
                 if (lane < 16) ul[lane] += dul[lane];
                 fence();
-                if (nr == 0) { status = 0; break; }
+                if (ipm::stops(ipm::verdict_no_rows(nr), status)) break;
                 double zmin = INFINITY, zmax = -INFINITY, gq = 0.0;
                 if (isrow) { gq = row_dot(ul) - hr; zmin = gq; zmax = gq; }
                 zmin = wg::wave_min(zmin); zmax = wg::wave_max(zmax);
-                const double sh_t = zmax >= 0.0 ? 1.0 + zmax : 0.0, sh_l = zmin <= 0.0 ? 1.0 - zmin : 0.0;
-                tr_ = -gq + sh_t; lr = gq + sh_l;
+                ipm::start_cold(gq, ipm::start_shift(zmin, zmax), tr_, lr);
                 scales();
                 mode = PRED;
                 continue;
             }
             double amax = 1e300;
             if (ok && isrow) {
-                const double rga = rg + row_dot(dul);
-                const double dl = ((mode == PRED ? -lr * tr_ : -rc) + lr * rga) / (tr_ + dreg * lr);
-                const double dtv = -rga + dreg * dl;
-                dlr = dl; dtr = dtv;
-                if (dtv < 0.0) amax = fmin(amax, -tr_ / dtv);
-                if (dl < 0.0) amax = fmin(amax, -lr / dl);
+                ipm::direction(mode == PRED, tr_, lr, rg, rc, row_dot(dul), dreg, dlr, dtr);
+                ipm::step_bound(tr_, lr, dtr, dlr, amax);
             }
             amax = wg::wave_min(amax);
             QDU_LAP(9);
             if (mode == PRED) {
-                if (!ok) { status = near_opt ? 0 : 2; break; }
-                if (!(mu == mu)) { status = near_opt ? 0 : 5; break; }
-                if (!(rd == rd)) { status = near_opt ? 0 : 6; break; }
-                const double ltol = fmax(d.tol, 1e-9);
-                if (rd <= ltol * sd && rp <= ltol * sp && mu <= d.tol) { status = 0; break; }
-                near_opt = (rd <= 1e-8 * sd && rp <= 1e-8 * sp && mu <= 1e-8);
-                if (it >= d.max_iter) { status = 1; break; }
-                const double a_aff = fmin(1.0, amax);
-                const double ma = isrow ? (lr + a_aff * dlr) * (tr_ + a_aff * dtr) : 0.0;
+                if (ipm::stops(ipm::verdict(ok, mu, rd, rp, sd, sp, d.tol, it, d.max_iter, near_opt), status)) break;
+                const double a_aff = ipm::step_affine(amax);
+                const double ma = isrow ? ipm::affine_term(tr_, lr, dtr, dlr, a_aff) : 0.0;
                 const double mu_aff = wg::wave_sum(ma) / ng;
-                sig = mu > 0.0 ? (mu_aff / mu) * (mu_aff / mu) * (mu_aff / mu) : 0.0;
+                sig = ipm::centring(mu_aff, mu);
                 mode = CORR;
                 continue;
             }
-            if (!ok) { status = 2; break; }
-            const double a = fmin(1.0, 0.99 * amax);
+            if (ipm::stops(ipm::verdict_system(ok), status)) break;
+            const double a = ipm::step_length(amax);
             if (lane < 16) ul[lane] += a * dul[lane];
-            if (isrow) { tr_ += a * dtr; lr += a * dlr; }
+            if (isrow) ipm::advance(a, dtr, dlr, tr_, lr);
             fence();
             ++it;
             mode = PRED;

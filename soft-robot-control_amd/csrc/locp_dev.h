@@ -9,6 +9,7 @@
 // owns s_k, the 2n+1 trust-region rows, the X rows and (k = N) the Xf rows.
 #pragma once
 #include "dev_la.h"
+#include "ipm_rule.h"
 #include <type_traits>
 
 struct QPDims {
@@ -45,6 +46,15 @@ struct QPDims {
     int lean_toeplitz;  // 1: a QP whose horizon lies in one TPWL region condenses by the restricted recursion (ql::condense_single);
                         // 0 (SRH_LEAN_NO_TOEPLITZ=1 when the constants are built): always the general recursion
 };
+
+// The QP without its trust-region rows (the prescreen of qp::solve, the condensed and the lean interior points): the row counts that follow
+inline __host__ __device__ void drop_trust_region_rows(QPDims &d) {
+    d.tr = 0;
+    d.nrx = d.nX;
+    d.RX = d.nrx + d.nXf;
+    d.NR = d.N * d.RX + d.N * d.nU;
+    d.ng = d.N * d.nrx + d.nXf + d.N * d.nU;
+}
 
 namespace qp {
 // Kernel instantiations for a fixed n_u (MSEL) and n_x (NSEL): overwrite the runtime copies with the constants (and
@@ -1051,11 +1061,26 @@ __device__ __forceinline__ bool riccati_solve(const QPDims &d, const QPConst &c,
 __device__ __forceinline__ double max_step(const QPDims &d, const QPWork &w, QPLds &L) {
     double a = 1e300;
     for_rows(d, [&](int row, bool, int, int) {
-        const double dt = w.dt[row], dl = w.dlam[row];
-        if (dt < 0.0) a = fmin(a, -w.t[row] / dt);
-        if (dl < 0.0) a = fmin(a, -w.lam[row] / dl);
+        ipm::step_bound(w.t[row], w.lam[row], w.dt[row], w.dlam[row], a);
     });
     return wg::reduce(a, 2, L.red);
+}
+
+// Residual scales of the stopping test (as oracle/riccati_ipm.py: the dual one from the target's gradient and omega, the primal one from
+// the input bounds and delta) and the dual regularisation, once per QP.  Every interior point walks the two maxima with its own stride;
+// max2(sd, sp) is its reduction of both over the threads that solve the QP (it may hold barriers: every one of them calls).
+template <class Max2>
+__device__ __forceinline__ void residual_scales(const QPDims &d, const QPConst &c, const QPData &q, int first, int stride, double &sd, double &sp,
+                                                double &dreg, Max2 &&max2) {
+    const int nz = d.nz;
+    for (int e = first; e < d.n; e += stride) {
+        double g = 0.0;
+        if (q.z) for (int a = 0; a < nz; ++a) g = fma(c.HtQz2[e * nz + a], -q.z[nz + a], g);
+        sd = fmax(sd, fabs(g));
+    }
+    for (int e = first; e < d.nU; e += stride) sp = fmax(sp, fabs(c.Ub[e]));
+    max2(sd, sp);
+    ipm::scales(q.omega, q.delta, d.reg, sd, sp, dreg);
 }
 
 }  // namespace qp
@@ -1082,7 +1107,6 @@ __device__ __forceinline__ int solve(const QPDims &dfull, const QPConst &c, cons
     // w.lam of that layout still hold its minimiser and multipliers -- the relaxed pass of this QP starts from them
     // (t = max(-g(u), floor), lam = max(lam, floor), no starting system); a warm attempt that fails is repeated cold.
     // pass_out: -1 condensed path, 0 relaxed Riccati pass, 1 full QP -- what produced the result.
-    constexpr double WARM_FLOOR = 1e-2;
     int tid = SRH_TID;                                       // re-read at the top of every interior-point iteration (dev_la.h: SRH_TID)
     const int nt = blockDim.x;
     int status = 1, it = 0;
@@ -1144,13 +1168,7 @@ __device__ __forceinline__ int solve(const QPDims &dfull, const QPConst &c, cons
         // (dropping satisfied constraints cannot change an optimum; the slack cost omega*s >= 0 is minimal
         // at 0) -- identical result, 10x fewer rows.  Otherwise pass 1 solves the full QP.
         QPDims d = dfull;
-        if (npass == 2 && pass == 0) {
-            d.tr = 0;
-            d.nrx = d.nX;
-            d.RX = d.nrx + d.nXf;
-            d.NR = d.N * d.RX + d.N * d.nU;
-            d.ng = d.N * d.nrx + d.nXf + d.N * d.nU;
-        }
+        if (npass == 2 && pass == 0) drop_trust_region_rows(d);
         QPWork w;
         qp_carve(w, work_base, d);
         wout = w;
@@ -1176,25 +1194,16 @@ __device__ __forceinline__ int solve(const QPDims &dfull, const QPConst &c, cons
         int mode = INIT;
         double mu = 0.0, rp = 0.0, sig = 0.0, sd = 1.0, sp = 1.0, dreg = 0.0;
         bool near_opt = false;
-        // scales for the stopping test (as oracle/riccati_ipm.py)
         auto scales = [&]() {
-            for (int e = tid; e < n; e += nt) {
-                double g = 0.0;
-                if (q.z) for (int a = 0; a < d.nz; ++a) g = fma(c.HtQz2[e * d.nz + a], -q.z[d.nz + a], g);
-                sd = fmax(sd, fabs(g));
-            }
-            for (int e = tid; e < d.nU; e += nt) sp = fmax(sp, fabs(c.Ub[e]));
-            sd = fmax(wg::reduce(sd, 1, L.red), q.omega);
-            sp = fmax(wg::reduce(sp, 1, L.red), fabs(q.delta));
-            dreg = d.reg / sd;
+            residual_scales(d, c, q, tid, nt, sd, sp, dreg, [&](double &a, double &b) { a = wg::reduce(a, 1, L.red); b = wg::reduce(b, 1, L.red); });
         };
         if (warm_now && d.ng > 0) {
             rows_apply(d, c, w.x, w.s, w.u, w.rg);
             __syncthreads();
             for_rows(d, [&](int row, bool isU, int k, int r) {
-                const double g = w.rg[row] - row_h(d, c, q, isU, k, r);
-                w.t[row] = fmax(-g, WARM_FLOOR);
-                w.lam[row] = fmax(w.lam[row], WARM_FLOOR);
+                double t, lam;
+                ipm::start_warm(w.rg[row] - row_h(d, c, q, isU, k, r), [&] { return w.lam[row]; }, false, t, lam);
+                w.t[row] = t; w.lam[row] = lam;
             });
             __syncthreads();
             scales();
@@ -1209,30 +1218,24 @@ __device__ __forceinline__ int solve(const QPDims &dfull, const QPConst &c, cons
             }
             if (mode == INIT) {
                 for_rows(d, [&](int row, bool isU, int k, int r) {
-                    const double g = w.rg[row] - row_h(d, c, q, isU, k, r);
-                    w.D[row] = d.ng ? 1.0 : 0.0; w.rho[row] = g; w.lam[row] = 0.0;
+                    double D, rho, lam;
+                    ipm::init_row(w.rg[row] - row_h(d, c, q, isU, k, r), d.ng ? 1.0 : 0.0, D, rho, lam);
+                    w.D[row] = D; w.rho[row] = rho; w.lam[row] = lam;
                 });
             } else if (mode == PRED) {
                 double musum = 0.0, rpm = 0.0;
                 for_rows(d, [&](int row, bool isU, int k, int r) {
-                    const double g = w.rg[row] - row_h(d, c, q, isU, k, r);
-                    const double t = w.t[row], lam = w.lam[row];
-                    const double rg = g + t;
-                    w.rg[row] = rg;
-                    const double D = lam / (t + dreg * lam);     // regularised weight (see oracle/riccati_ipm.py)
-                    w.D[row] = D;
-                    w.rho[row] = D * (rg + dreg * lam);
-                    musum += lam * t;
-                    rpm = fmax(rpm, fabs(rg));
+                    double rg, D, rho;
+                    ipm::pred_row(w.rg[row] - row_h(d, c, q, isU, k, r), w.t[row], w.lam[row], dreg, rg, D, rho, musum, rpm);
+                    w.rg[row] = rg; w.D[row] = D; w.rho[row] = rho;
                 });
                 mu = wg::reduce(musum, 0, L.red) / d.ng;
                 rp = wg::reduce(rpm, 1, L.red);
             } else {
                 for_rows(d, [&](int row, bool, int, int) {
-                    const double t = w.t[row], lam = w.lam[row];
-                    const double rc = lam * t + w.dt[row] * w.dlam[row] - sig * mu;
-                    w.rc[row] = rc;
-                    w.rho[row] = lam + (lam * w.rg[row] - rc) / (t + dreg * lam);
+                    double rc, rho;
+                    ipm::corr_row(w.t[row], w.lam[row], w.rg[row], w.dt[row], w.dlam[row], sig, mu, dreg, rc, rho);
+                    w.rc[row] = rc; w.rho[row] = rho;
                 });
             }
             __syncthreads();
@@ -1245,12 +1248,12 @@ __device__ __forceinline__ int solve(const QPDims &dfull, const QPConst &c, cons
             if (mode == CORR) SRH_LAP(4); else SRH_LAP(3);
             // ---------------- use the direction
             if (mode == INIT) {
-                if (!ok) { status = 2; break; }
+                if (ipm::stops(ipm::verdict_system(ok), status)) break;
                 for (int e = tid; e < (N + 1) * n; e += nt) w.x[e] += w.dx[e];
                 for (int e = tid; e < N * m; e += nt) w.u[e] += w.du[e];
                 for (int e = tid; e <= N; e += nt) w.s[e] = (e == 0) ? s0 : w.s[e] + w.ds[e];
                 __syncthreads();
-                if (d.ng == 0) { status = 0; break; }      // no inequality rows: the Newton point is the solution
+                if (ipm::stops(ipm::verdict_no_rows(d.ng), status)) break;      // no inequality rows: the Newton point is the solution
                 rows_apply(d, c, w.x, w.s, w.u, w.rg);
                 __syncthreads();
                 double zmin = INFINITY, zmax = -INFINITY;
@@ -1261,10 +1264,11 @@ __device__ __forceinline__ int solve(const QPDims &dfull, const QPConst &c, cons
                 });
                 zmin = wg::reduce(zmin, 2, L.red);
                 zmax = wg::reduce(zmax, 1, L.red);
-                const double sh_t = zmax >= 0.0 ? 1.0 + zmax : 0.0, sh_l = zmin <= 0.0 ? 1.0 - zmin : 0.0;
+                const ipm::Shift sh = ipm::start_shift(zmin, zmax);
                 for_rows(d, [&](int row, bool, int, int) {
-                    const double g = w.rg[row];
-                    w.t[row] = -g + sh_t; w.lam[row] = g + sh_l;
+                    double t, lam;
+                    ipm::start_cold(w.rg[row], sh, t, lam);
+                    w.t[row] = t; w.lam[row] = lam;
                 });
                 __syncthreads();
                 scales();
@@ -1272,33 +1276,25 @@ __device__ __forceinline__ int solve(const QPDims &dfull, const QPConst &c, cons
                 continue;
             }
             if (mode == PRED) {
-                // a factorisation that breaks down in the last digits of an already converged iterate
-                // (weights D = lam/t up to 1e13) is accepted at the looser 1e-8 certificate
-                if (!ok) { status = near_opt ? 0 : 2; break; }
-                if (!(mu == mu)) { status = near_opt ? 0 : 5; break; }
-                if (!(rd == rd)) { status = near_opt ? 0 : 6; break; }
+                if (ipm::stops(ipm::verdict_failed(ok, mu, rd, near_opt), status)) break;
                 if (q.dbg && tid == 0) { gptr g = q.dbg + 8 * it; g[0] = mu; g[1] = rd; g[2] = rp; g[3] = sd; g[4] = sp; }
-                const double ltol = fmax(d.tol, 1e-9);     // linear residuals: round-off floor (see the port)
-                if (rd <= ltol * sd && rp <= ltol * sp && mu <= d.tol) { status = 0; break; }
-                near_opt = (rd <= 1e-8 * sd && rp <= 1e-8 * sp && mu <= 1e-8);
-                if (it >= d.max_iter) { status = 1; break; }
+                if (ipm::stops(ipm::verdict_converged(mu, rd, rp, sd, sp, d.tol, it, d.max_iter, near_opt), status)) break;
                 // predictor direction on the rows
                 rows_apply(d, c, w.dx, w.ds, w.du, w.dt);
                 __syncthreads();
                 for_rows(d, [&](int row, bool, int, int) {
-                    const double t = w.t[row], lam = w.lam[row], rga = w.rg[row] + w.dt[row];
-                    const double dl = (-lam * t + lam * rga) / (t + dreg * lam);
-                    w.dlam[row] = dl;
-                    w.dt[row] = -rga + dreg * dl;
+                    double dl, dt;
+                    ipm::direction(true, w.t[row], w.lam[row], w.rg[row], 0.0, w.dt[row], dreg, dl, dt);
+                    w.dlam[row] = dl; w.dt[row] = dt;
                 });
                 __syncthreads();
-                const double a_aff = fmin(1.0, max_step(d, w, L));
+                const double a_aff = ipm::step_affine(max_step(d, w, L));
                 double ma = 0.0;
                 for_rows(d, [&](int row, bool, int, int) {
-                    ma += (w.lam[row] + a_aff * w.dlam[row]) * (w.t[row] + a_aff * w.dt[row]);
+                    ma += ipm::affine_term(w.t[row], w.lam[row], w.dt[row], w.dlam[row], a_aff);
                 });
                 const double mu_aff = wg::reduce(ma, 0, L.red) / d.ng;
-                sig = mu > 0.0 ? (mu_aff / mu) * (mu_aff / mu) * (mu_aff / mu) : 0.0;
+                sig = ipm::centring(mu_aff, mu);
                 if (q.dbg && tid == 0) { gptr g = q.dbg + 8 * it; g[5] = a_aff; g[6] = sig; }
                 mode = CORR;
                 continue;
@@ -1307,20 +1303,20 @@ __device__ __forceinline__ int solve(const QPDims &dfull, const QPConst &c, cons
             rows_apply(d, c, w.dx, w.ds, w.du, w.dt);
             __syncthreads();
             for_rows(d, [&](int row, bool, int, int) {
-                const double t = w.t[row], lam = w.lam[row], rga = w.rg[row] + w.dt[row];
-                const double dl = (-w.rc[row] + lam * rga) / (t + dreg * lam);
-                w.dlam[row] = dl;
-                w.dt[row] = -rga + dreg * dl;
+                double dl, dt;
+                ipm::direction(false, w.t[row], w.lam[row], w.rg[row], w.rc[row], w.dt[row], dreg, dl, dt);
+                w.dlam[row] = dl; w.dt[row] = dt;
             });
             __syncthreads();
-            const double a = fmin(1.0, 0.99 * max_step(d, w, L));   // stay strictly interior
+            const double a = ipm::step_length(max_step(d, w, L));
             if (q.dbg && tid == 0) { gptr g = q.dbg + 8 * it; g[7] = a; }
             for (int e = tid; e < (N + 1) * n; e += nt) w.x[e] += a * w.dx[e];
             for (int e = tid; e < N * m; e += nt) w.u[e] += a * w.du[e];
             for (int e = tid; e <= N; e += nt) w.s[e] = (e == 0) ? s0 : w.s[e] + a * w.ds[e];
             for_rows(d, [&](int row, bool, int, int) {
-                w.t[row] += a * w.dt[row];
-                w.lam[row] += a * w.dlam[row];
+                double t = w.t[row], lam = w.lam[row];
+                ipm::advance(a, w.dt[row], w.dlam[row], t, lam);
+                w.t[row] = t; w.lam[row] = lam;
             });
             __syncthreads();
             ++it;

@@ -1305,6 +1305,35 @@ __device__ __forceinline__ void newton_solve(const QPDims &d, const GP &g, Lds &
     newton_back<MSEL>(d, g, L, pf);
 }
 
+// The condensation (G, free response) depends on the linearisation only: when the region sequence of this QP equals
+// the one G was built from (a rejected SCP step: only delta / omega change, gusto.py:341 `update(full=new)`; or an
+// accepted step whose trajectory stays in the same regions) it is still in LDS / the L2 block.  `x0` does not change
+// inside a solve; the single-QP kernel (no region index) always condenses.  `from`: the sequence G was built from (L.goff, the half-size
+// layout's L.goffg; L.flag[2] != 0: there is one).  The vote goes through L.flag[3] (__syncthreads_and brings static LDS of its own: the
+// carve uses all 160 KB) behind two barriers; a caller that uses L.flag[3] for something else afterwards adds its own.
+template <class IP>
+__device__ __forceinline__ bool same_regions(const QPDyn &dyn, Lds &L, IP from, int N, int tid, int nt) {
+    if (dyn.idx == nullptr) return false;
+    int same = L.flag[2];
+    for (int k = tid; k < N; k += nt) same = same && (from[k] == L.idxl[k]);
+    if (tid == 0) L.flag[3] = 1;
+    __syncthreads();
+    if (!same) L.flag[3] = 0;
+    __syncthreads();
+    return L.flag[3] != 0;
+}
+
+// Lower Cholesky factor (row-major in Lk) of a symmetric positive SEMI-definite 2 x 2 block in closed form (oracle/condensed_ipm.py:
+// chol_psd): a pivot that has cancelled to nothing -- 1e-14 of the larger diagonal entry -- gets a zero column.
+__device__ __forceinline__ void chol2_psd(double S00, double S01, double S11, lptr Lk) {
+    const double dmax = fmax(fabs(S00), fabs(S11));
+    const double l00 = S00 > 1e-14 * dmax ? sqrt(S00) : 0.0;
+    const double l10 = l00 > 0.0 ? S01 / l00 : 0.0;
+    const double v = fma(-l10, l10, S11);
+    const double l11 = v > 1e-14 * dmax ? sqrt(v) : 0.0;
+    Lk[0] = l00; Lk[1] = 0.0; Lk[2] = l10; Lk[3] = l11;
+}
+
 // ------------------------------------------------------------------ the QP without its trust-region rows
 // Results: w.u, and -- after the final rollout of solve_qp below -- w.x.  Returns 0 optimal, 1 max iterations, 2 numerical failure.
 template <int MSEL, int NSEL>
@@ -1313,11 +1342,7 @@ __device__ __forceinline__ int ipm(const QPDims &dfull, const QPConst &c, const 
     int tid = SRH_TID;                                       // re-read at the top of every interior-point iteration (dev_la.h: SRH_TID)
     const int nt = blockDim.x;
     QPDims d = dfull;
-    d.tr = 0;
-    d.nrx = d.nX;
-    d.RX = d.nrx + d.nXf;
-    d.NR = d.N * d.RX + d.N * d.nU;
-    d.ng = d.N * d.nrx + d.nXf + d.N * d.nU;
+    drop_trust_region_rows(d);
     QPWork w;
     qp_carve(w, work_base, d);
     wout = w;
@@ -1341,20 +1366,7 @@ __device__ __forceinline__ int ipm(const QPDims &dfull, const QPConst &c, const 
     for (int e = tid; e < d.nU * m; e += nt) L.UA[e] = c.UA[e];
     for (int e = tid; e < (d.nX + d.nXf) * po; e += nt) L.Tx[e] = e < d.nX * po ? c.Tx[e] : c.Txf[e - d.nX * po];
     __syncthreads();
-    // The condensation (G, free response) depends on the linearisation only: when the region sequence of this QP equals
-    // the one G was built from (a rejected SCP step: only delta / omega change, gusto.py:341 `update(full=new)`; or an
-    // accepted step whose trajectory stays in the same regions) it is still in LDS / the L2 block.  `x0` does not change
-    // inside a solve; the single-QP kernel (no region index) always condenses.
-    bool reuse = false;
-    if (dyn.idx != nullptr) {
-        int same = L.flag[2];
-        for (int k = tid; k < N; k += nt) same = same && (L.goff[k] == L.idxl[k]);
-        if (tid == 0) L.flag[3] = 1;                       // (__syncthreads_and brings static LDS of its own: the carve uses all 160 KB)
-        __syncthreads();
-        if (!same) L.flag[3] = 0;
-        __syncthreads();
-        reuse = L.flag[3] != 0;
-    }
+    const bool reuse = same_regions(dyn, L, L.goff, N, tid, nt);
     if (!reuse) {
     rollout<MSEL, NSEL>(d, dyn, q.x0, (cgptr) nullptr, w.x, L);
     QL_LAP(0);
@@ -1401,22 +1413,16 @@ __device__ __forceinline__ int ipm(const QPDims &dfull, const QPConst &c, const 
         for (int qi = 0; qi < QR; ++qi) {
             if (!rv[qi]) continue;
             const int e = tid + nt * qi;
+            double D, rho;                                  // of this row, to L2 for the stage sums
             if (mode == INIT) {
-                const double gq = row_val(qi, L.y, L.u) - rh[qi];
-                w.D[e] = 1.0; w.rho[e] = gq; rlam[qi] = 0.0;
+                ipm::init_row(row_val(qi, L.y, L.u) - rh[qi], 1.0, D, rho, rlam[qi]);
+                w.D[e] = D; w.rho[e] = rho;
             } else if (mode == PRED) {
-                const double gq = row_val(qi, L.y, L.u) - rh[qi];
-                const double t = rt[qi], lam = rlam[qi], rg = gq + t;
-                rrg[qi] = rg;
-                const double D = lam / (t + dreg * lam);
-                w.D[e] = D; w.rho[e] = D * (rg + dreg * lam); w.lam[e] = lam;
-                musum += lam * t;
-                rpm = fmax(rpm, fabs(rg));
+                ipm::pred_row(row_val(qi, L.y, L.u) - rh[qi], rt[qi], rlam[qi], dreg, rrg[qi], D, rho, musum, rpm);
+                w.D[e] = D; w.rho[e] = rho; w.lam[e] = rlam[qi];
             } else {
-                const double t = rt[qi], lam = rlam[qi];
-                const double rc = lam * t + rdt[qi] * rdl[qi] - sig * mu;
-                rrc[qi] = rc;
-                w.rho[e] = lam + (lam * rrg[qi] - rc) / (t + dreg * lam);
+                ipm::corr_row(rt[qi], rlam[qi], rrg[qi], rdt[qi], rdl[qi], sig, mu, dreg, rrc[qi], rho);
+                w.rho[e] = rho;
             }
         }
         if (mode == PRED) {
@@ -1448,11 +1454,11 @@ __device__ __forceinline__ int ipm(const QPDims &dfull, const QPConst &c, const 
         }
         QL_LAP(6);
         if (mode == INIT) {
-            if (!ok) { status = 2; break; }
+            if (ipm::stops(ipm::verdict_system(ok), status)) break;
             for (int e = tid; e < nm; e += nt) L.u[e] += L.du[e];
             for (int e = tid; e < ldG; e += nt) L.y[e] += L.dy[e];
             __syncthreads();
-            if (d.ng == 0) { status = 0; break; }
+            if (ipm::stops(ipm::verdict_no_rows(d.ng), status)) break;
             double zmin = INFINITY, zmax = -INFINITY;
 #pragma unroll
             for (int qi = 0; qi < QR; ++qi) {
@@ -1463,18 +1469,10 @@ __device__ __forceinline__ int ipm(const QPDims &dfull, const QPConst &c, const 
             }
             zmin = wg::reduce(zmin, 2, L.red);
             zmax = wg::reduce(zmax, 1, L.red);
-            const double sh_t = zmax >= 0.0 ? 1.0 + zmax : 0.0, sh_l = zmin <= 0.0 ? 1.0 - zmin : 0.0;
+            const ipm::Shift sh = ipm::start_shift(zmin, zmax);
 #pragma unroll
-            for (int qi = 0; qi < QR; ++qi) { rt[qi] = -rrg[qi] + sh_t; rlam[qi] = rrg[qi] + sh_l; }
-            for (int e = tid; e < d.n; e += nt) {
-                double gq = 0.0;
-                if (q.z) for (int a = 0; a < d.nz; ++a) gq = fma(c.HtQz2[e * d.nz + a], -q.z[d.nz + a], gq);
-                sd = fmax(sd, fabs(gq));
-            }
-            for (int e = tid; e < d.nU; e += nt) sp = fmax(sp, fabs(c.Ub[e]));
-            sd = fmax(wg::reduce(sd, 1, L.red), q.omega);
-            sp = fmax(wg::reduce(sp, 1, L.red), fabs(q.delta));
-            dreg = d.reg / sd;
+            for (int qi = 0; qi < QR; ++qi) ipm::start_cold(rrg[qi], sh, rt[qi], rlam[qi]);
+            qp::residual_scales(d, c, q, tid, nt, sd, sp, dreg, [&](double &a, double &b) { a = wg::reduce(a, 1, L.red); b = wg::reduce(b, 1, L.red); });
             mode = PRED;
             continue;
         }
@@ -1483,42 +1481,33 @@ __device__ __forceinline__ int ipm(const QPDims &dfull, const QPConst &c, const 
 #pragma unroll
             for (int qi = 0; qi < QR; ++qi) {
                 if (!rv[qi]) continue;
-                const double t = rt[qi], lam = rlam[qi], rga = rrg[qi] + row_val(qi, L.dy, L.du);
-                const double dl = ((mode == PRED ? -lam * t : -rrc[qi]) + lam * rga) / (t + dreg * lam);
-                const double dtv = -rga + dreg * dl;
-                rdl[qi] = dl; rdt[qi] = dtv;
-                if (dtv < 0.0) amax = fmin(amax, -t / dtv);
-                if (dl < 0.0) amax = fmin(amax, -lam / dl);
+                ipm::direction(mode == PRED, rt[qi], rlam[qi], rrg[qi], rrc[qi], row_val(qi, L.dy, L.du), dreg, rdl[qi], rdt[qi]);
+                ipm::step_bound(rt[qi], rlam[qi], rdt[qi], rdl[qi], amax);
             }
         }
         amax = wg::reduce(amax, 2, L.red);
         if (mode == PRED) {
-            if (!ok) { status = near_opt ? 0 : 2; break; }
-            if (!(mu == mu)) { status = near_opt ? 0 : 5; break; }
-            if (!(rd == rd)) { status = near_opt ? 0 : 6; break; }
+            if (ipm::stops(ipm::verdict_failed(ok, mu, rd, near_opt), status)) break;
             if (q.dbg && tid == 0) { gptr gd = q.dbg + 8 * it; gd[0] = mu; gd[1] = rd; gd[2] = rp; gd[3] = sd; gd[4] = sp; }
-            const double ltol = fmax(d.tol, 1e-9);
-            if (rd <= ltol * sd && rp <= ltol * sp && mu <= d.tol) { status = 0; break; }
-            near_opt = (rd <= 1e-8 * sd && rp <= 1e-8 * sp && mu <= 1e-8);
-            if (it >= d.max_iter) { status = 1; break; }
-            const double a_aff = fmin(1.0, amax);
+            if (ipm::stops(ipm::verdict_converged(mu, rd, rp, sd, sp, d.tol, it, d.max_iter, near_opt), status)) break;
+            const double a_aff = ipm::step_affine(amax);
             double ma = 0.0;
 #pragma unroll
             for (int qi = 0; qi < QR; ++qi)
-                if (rv[qi]) ma += (rlam[qi] + a_aff * rdl[qi]) * (rt[qi] + a_aff * rdt[qi]);
+                if (rv[qi]) ma += ipm::affine_term(rt[qi], rlam[qi], rdt[qi], rdl[qi], a_aff);
             const double mu_aff = wg::reduce(ma, 0, L.red) / d.ng;
-            sig = mu > 0.0 ? (mu_aff / mu) * (mu_aff / mu) * (mu_aff / mu) : 0.0;
+            sig = ipm::centring(mu_aff, mu);
             if (q.dbg && tid == 0) { gptr gd = q.dbg + 8 * it; gd[5] = a_aff; gd[6] = sig; }
             mode = CORR;
             continue;
         }
-        if (!ok) { status = 2; break; }
-        const double a = fmin(1.0, 0.99 * amax);
+        if (ipm::stops(ipm::verdict_system(ok), status)) break;
+        const double a = ipm::step_length(amax);
         if (q.dbg && tid == 0) { gptr gd = q.dbg + 8 * it; gd[7] = a; }
         for (int e = tid; e < nm; e += nt) L.u[e] += a * L.du[e];
         for (int e = tid; e < ldG; e += nt) L.y[e] += a * L.dy[e];
 #pragma unroll
-        for (int qi = 0; qi < QR; ++qi) { rt[qi] += a * rdt[qi]; rlam[qi] += a * rdl[qi]; }
+        for (int qi = 0; qi < QR; ++qi) ipm::advance(a, rdt[qi], rdl[qi], rt[qi], rlam[qi]);
         __syncthreads();
         ++it;
         mode = PRED;
@@ -1572,11 +1561,7 @@ __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, co
     int tid = SRH_TID;                                       // re-read at the top of every interior-point iteration (dev_la.h: SRH_TID)
     const int nt = blockDim.x;
     QPDims d = dfull;
-    d.tr = 0;
-    d.nrx = d.nX;
-    d.RX = d.nrx + d.nXf;
-    d.NR = d.N * d.RX + d.N * d.nU;
-    d.ng = d.N * d.nrx + d.nXf + d.N * d.nU;
+    drop_trust_region_rows(d);
     QPWork w;
     qp_carve(w, work_base, d);
     wout = w;
@@ -1596,7 +1581,6 @@ __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, co
     // by its linearisation point only and shares most of the active set: the interior point starts from that point (u as it
     // is, slacks from THIS QP's rows, multipliers kept, both at least WARM_FLOOR from zero) and skips the initial Newton system.
     // 7-9 interior-point iterations instead of 15-18 at C2 / C5, same minimiser (oracle/condensed_ipm.py: solve(warm=...)).
-    constexpr double WARM_FLOOR = 1e-2;
     if (warm) { for (int e = tid; e < nm; e += nt) L.u[e] = w.u[e]; }
     else { for (int e = tid; e < nm; e += nt) { w.u[e] = 0.0; L.u[e] = 0.0; } }
     for (int e = tid; e < ldG + YPAD; e += nt) { L.ya[e] = 0.0; L.yd[e] = 0.0; L.yg[e] = 0.0; }     // padding stays zero for good
@@ -1607,15 +1591,8 @@ __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, co
 #endif
     if (tid < 5) L.flag[3 + tid] = 0;                          // counters of the two wave sets (Waves, tile_cholesky_set; [3]: idle between the region tests of two QPs)
     __syncthreads();
-    bool reuse = false;
+    const bool reuse = same_regions(dyn, L, L.goff, N, tid, nt);
     if (dyn.idx != nullptr) {
-        int same = L.flag[2];
-        for (int k = tid; k < N; k += nt) same = same && (L.goff[k] == L.idxl[k]);
-        if (tid == 0) L.flag[3] = 1;
-        __syncthreads();
-        if (!same) L.flag[3] = 0;
-        __syncthreads();
-        reuse = L.flag[3] != 0;
         __syncthreads();
         if (tid == 0) L.flag[3] = 0;                           // tile_cholesky_set's early-tile counter from here on
     }
@@ -1681,25 +1658,12 @@ __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, co
     double mu = 0.0, rp = 0.0, sig = 0.0, sd = 1.0, sp = 1.0, dreg = 0.0;
     bool near_opt = false;
     const bool ya_const = d.nX + d.nXf == 0;                  // no state rows: L.ya is the same in the predictor and the corrector (newton_front)
-    auto scales = [&]() {                                     // residual scales and the dual regularisation (once per QP)
-        for (int e = tid; e < d.n; e += nt) {
-            double gq = 0.0;
-            if (q.z) for (int a = 0; a < nz; ++a) gq = fma(c.HtQz2[e * nz + a], -q.z[nz + a], gq);
-            sd = fmax(sd, fabs(gq));
-        }
-        for (int e = tid; e < d.nU; e += nt) sp = fmax(sp, fabs(c.Ub[e]));
-        reduce2(sd, 1, sp, 1, L.red);
-        sd = fmax(sd, q.omega);
-        sp = fmax(sp, fabs(q.delta));
-        dreg = d.reg / sd;
-    };
+    auto scales = [&]() { qp::residual_scales(d, c, q, tid, nt, sd, sp, dreg, [&](double &a, double &b) { reduce2(a, 1, b, 1, L.red); }); };
     if (warm && d.ng > 0) {
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
             if (s2 >= nrow) continue;
-            const double gq = row_val(s2, L.y, L.u) - rh[s2];
-            rt[s2] = fmax(-gq, WARM_FLOOR);
-            rlam[s2] = poison ? INFINITY : fmax(w.lam[lslot + s2], WARM_FLOOR);
+            ipm::start_warm(row_val(s2, L.y, L.u) - rh[s2], [&] { return w.lam[lslot + s2]; }, poison, rt[s2], rlam[s2]);
         }
         scales();
         mode = PRED;
@@ -1713,23 +1677,9 @@ __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, co
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
             if (s2 >= nrow) continue;
-            if (mode == INIT) {
-                const double gq = row_val(s2, L.y, L.u) - rh[s2];
-                Dw[s2] = 1.0; rho[s2] = gq; rlam[s2] = 0.0;
-            } else if (mode == PRED) {
-                const double gq = row_val(s2, L.y, L.u) - rh[s2];
-                const double t = rt[s2], lam = rlam[s2], rg = gq + t;
-                rrg[s2] = rg;
-                Dw[s2] = lam / (t + dreg * lam);
-                rho[s2] = Dw[s2] * (rg + dreg * lam);
-                musum += lam * t;
-                rpm = fmax(rpm, fabs(rg));
-            } else {
-                const double t = rt[s2], lam = rlam[s2];
-                const double rc = lam * t + rdt[s2] * rdl[s2] - sig * mu;
-                rrc[s2] = rc;
-                rho[s2] = lam + (lam * rrg[s2] - rc) / (t + dreg * lam);
-            }
+            if (mode == INIT) ipm::init_row(row_val(s2, L.y, L.u) - rh[s2], 1.0, Dw[s2], rho[s2], rlam[s2]);
+            else if (mode == PRED) ipm::pred_row(row_val(s2, L.y, L.u) - rh[s2], rt[s2], rlam[s2], dreg, rrg[s2], Dw[s2], rho[s2], musum, rpm);
+            else ipm::corr_row(rt[s2], rlam[s2], rrg[s2], rdt[s2], rdl[s2], sig, mu, dreg, rrc[s2], rho[s2]);
         }
         if (isu) {
             const double du0 = r2bb * (L.u[tid] - udv);
@@ -1745,16 +1695,7 @@ __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, co
             const double y0 = L.y[(kx - 1) * 2], y1 = L.y[(kx - 1) * 2 + 1];
             if (mode != CORR) {
                 const double a00 = gsum<GX>(ca[0] * Dw[0] * ca[0]), a01 = gsum<GX>(ca[0] * Dw[0] * ca[1]), a11 = gsum<GX>(ca[1] * Dw[0] * ca[1]);
-                if (xlead) {
-                    const double S00 = s00 + a00, S01 = s01 + a01, S11 = s11 + a11;
-                    const double dmax = fmax(fabs(S00), fabs(S11));
-                    const double l00 = S00 > 1e-14 * dmax ? sqrt(S00) : 0.0;
-                    const double l10 = l00 > 0.0 ? S01 / l00 : 0.0;
-                    const double v = fma(-l10, l10, S11);
-                    const double l11 = v > 1e-14 * dmax ? sqrt(v) : 0.0;
-                    lptr Lk = L.Ls + (size_t)(kx - 1) * 4;
-                    Lk[0] = l00; Lk[1] = 0.0; Lk[2] = l10; Lk[3] = l11;
-                }
+                if (xlead) chol2_psd(s00 + a00, s01 + a01, s11 + a11, L.Ls + (size_t)(kx - 1) * 4);
             }
             const double r0 = gsum<GX>(ca[0] * rho[0]), r1 = gsum<GX>(ca[1] * rho[0]);
             double l0 = 0.0, l1 = 0.0;
@@ -1824,11 +1765,11 @@ __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, co
         QB_LAP(6);
         // ---------------- use the direction
         if (mode == INIT) {
-            if (!ok) { status = 2; break; }
+            if (ipm::stops(ipm::verdict_system(ok), status)) break;
             for (int e = tid; e < nm; e += nt) L.u[e] += L.du[e];
             for (int e = tid; e < ldG; e += nt) L.y[e] += L.dy[e];
             __syncthreads();
-            if (d.ng == 0) { status = 0; break; }
+            if (ipm::stops(ipm::verdict_no_rows(d.ng), status)) break;
             double zmin = INFINITY, zmax = -INFINITY;
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
@@ -1838,9 +1779,9 @@ __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, co
                 zmin = fmin(zmin, gq); zmax = fmax(zmax, gq);
             }
             reduce2(zmin, 2, zmax, 1, L.red);
-            const double sh_t = zmax >= 0.0 ? 1.0 + zmax : 0.0, sh_l = zmin <= 0.0 ? 1.0 - zmin : 0.0;
+            const ipm::Shift sh = ipm::start_shift(zmin, zmax);
 #pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) { rt[s2] = -rrg[s2] + sh_t; rlam[s2] = rrg[s2] + sh_l; }
+            for (int s2 = 0; s2 < 2; ++s2) ipm::start_cold(rrg[s2], sh, rt[s2], rlam[s2]);
             scales();
             mode = PRED;
             continue;
@@ -1850,47 +1791,38 @@ __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, co
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
                 if (s2 >= nrow) continue;
-                const double t = rt[s2], lam = rlam[s2], rga = rrg[s2] + row_val(s2, L.dy, L.du);
-                const double dl = ((mode == PRED ? -lam * t : -rrc[s2]) + lam * rga) / (t + dreg * lam);
-                const double dtv = -rga + dreg * dl;
-                rdl[s2] = dl; rdt[s2] = dtv;
-                if (dtv < 0.0) amax = fmin(amax, -t / dtv);
-                if (dl < 0.0) amax = fmin(amax, -lam / dl);
+                ipm::direction(mode == PRED, rt[s2], rlam[s2], rrg[s2], rrc[s2], row_val(s2, L.dy, L.du), dreg, rdl[s2], rdt[s2]);
+                ipm::step_bound(rt[s2], rlam[s2], rdt[s2], rdl[s2], amax);
             }
         }
         QB_LAP(18);
         reduce2(amax, 2, dummy, 0, L.red);
         QB_LAP(19);
         if (mode == PRED) {
-            if (!ok) { status = near_opt ? 0 : 2; break; }
-            if (!(mu == mu)) { status = near_opt ? 0 : 5; break; }
-            if (!(rd == rd)) { status = near_opt ? 0 : 6; break; }
+            if (ipm::stops(ipm::verdict_failed(ok, mu, rd, near_opt), status)) break;
             if (q.dbg && tid == 0) { gptr gd = q.dbg + 8 * it; gd[0] = mu; gd[1] = rd; gd[2] = rp; gd[3] = sd; gd[4] = sp; }
-            const double ltol = fmax(d.tol, 1e-9);
-            if (rd <= ltol * sd && rp <= ltol * sp && mu <= d.tol) { status = 0; break; }
-            near_opt = (rd <= 1e-8 * sd && rp <= 1e-8 * sp && mu <= 1e-8);
-            if (it >= d.max_iter) { status = 1; break; }
-            const double a_aff = fmin(1.0, amax);
+            if (ipm::stops(ipm::verdict_converged(mu, rd, rp, sd, sp, d.tol, it, d.max_iter, near_opt), status)) break;
+            const double a_aff = ipm::step_affine(amax);
             double ma = 0.0;
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2)
-                if (s2 < nrow) ma += (rlam[s2] + a_aff * rdl[s2]) * (rt[s2] + a_aff * rdt[s2]);
+                if (s2 < nrow) ma += ipm::affine_term(rt[s2], rlam[s2], rdt[s2], rdl[s2], a_aff);
             QB_LAP(20);
             reduce2(ma, 0, dummy, 0, L.red);
             QB_LAP(21);
             const double mu_aff = ma / d.ng;
-            sig = mu > 0.0 ? (mu_aff / mu) * (mu_aff / mu) * (mu_aff / mu) : 0.0;
+            sig = ipm::centring(mu_aff, mu);
             if (q.dbg && tid == 0) { gptr gd = q.dbg + 8 * it; gd[5] = a_aff; gd[6] = sig; }
             mode = CORR;
             continue;
         }
-        if (!ok) { status = 2; break; }
-        const double a = fmin(1.0, 0.99 * amax);
+        if (ipm::stops(ipm::verdict_system(ok), status)) break;
+        const double a = ipm::step_length(amax);
         if (q.dbg && tid == 0) { gptr gd = q.dbg + 8 * it; gd[7] = a; }
         for (int e = tid; e < nm; e += nt) L.u[e] += a * L.du[e];
         for (int e = tid; e < ldG; e += nt) L.y[e] += a * L.dy[e];
 #pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) { rt[s2] += a * rdt[s2]; rlam[s2] += a * rdl[s2]; }
+        for (int s2 = 0; s2 < 2; ++s2) ipm::advance(a, rdt[s2], rdl[s2], rt[s2], rlam[s2]);
         __syncthreads();
         ++it;
         mode = PRED;
@@ -1937,11 +1869,7 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
     int tid = SRH_TID;                                       // re-read at the top of every interior-point iteration (dev_la.h: SRH_TID)
     const int nt = blockDim.x;
     QPDims d = dfull;
-    d.tr = 0;
-    d.nrx = d.nX;
-    d.RX = d.nrx + d.nXf;
-    d.NR = d.N * d.RX + d.N * d.nU;
-    d.ng = d.N * d.nrx + d.nXf + d.N * d.nU;
+    drop_trust_region_rows(d);
     QPWork w;
     qp_carve(w, work_base, d);
     wout = w;
@@ -1962,7 +1890,6 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
 #else
 #define Q4_LAP(x) ((void)0)
 #endif
-    constexpr double WARM_FLOOR = 1e-2;
     if (warm) { for (int e = tid; e < nm; e += nt) L.u[e] = w.u[e]; }
     else { for (int e = tid; e < nm; e += nt) { w.u[e] = 0.0; L.u[e] = 0.0; } }
     for (int e = tid; e < ldG + L.ypad; e += nt) { L.ya[e] = 0.0; L.yd[e] = 0.0; L.yg[e] = 0.0; }     // padding stays zero for good
@@ -1970,15 +1897,8 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
     for (int k = tid; k < N; k += nt) L.idxl[k] = dyn.idx ? dyn.idx[k] : k;
     if (tid < 5) L.flag[3 + tid] = 0;                          // counters of the two wave sets (Waves, tile_cholesky_set)
     __syncthreads();
-    bool reuse = false;
+    const bool reuse = same_regions(dyn, L, L.goffg, N, tid, nt);
     if (dyn.idx != nullptr) {
-        int same = L.flag[2];
-        for (int k = tid; k < N; k += nt) same = same && (L.goffg[k] == L.idxl[k]);
-        if (tid == 0) L.flag[3] = 1;
-        __syncthreads();
-        if (!same) L.flag[3] = 0;
-        __syncthreads();
-        reuse = L.flag[3] != 0;
         __syncthreads();
         if (tid == 0) L.flag[3] = 0;                           // tile_cholesky_set's early-tile counter from here on
     }
@@ -2045,30 +1965,13 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
     double mu = 0.0, rp = 0.0, sig = 0.0, sd = 1.0, sp = 1.0, dreg = 0.0;
     bool near_opt = false;
     const bool ya_const = d.nX + d.nXf == 0;                  // no state rows: L.ya is the same in the predictor and the corrector (newton_front)
-    auto scales = [&]() {                                     // residual scales and the dual regularisation (once per QP)
-        for (int e = tid; e < d.n; e += nt) {
-            double gq = 0.0;
-            if (q.z) for (int a = 0; a < nz; ++a) gq = fma(c.HtQz2[e * nz + a], -q.z[nz + a], gq);
-            sd = fmax(sd, fabs(gq));
-        }
-        for (int e = tid; e < d.nU; e += nt) sp = fmax(sp, fabs(c.Ub[e]));
-        reduce2(sd, 1, sp, 1, L.red);
-        sd = fmax(sd, q.omega);
-        sp = fmax(sp, fabs(q.delta));
-        dreg = d.reg / sd;
-    };
+    auto scales = [&]() { qp::residual_scales(d, c, q, tid, nt, sd, sp, dreg, [&](double &a, double &b) { reduce2(a, 1, b, 1, L.red); }); };
     if (warm && d.ng > 0) {
         if (isu) {
 #pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                tu[s2] = fmax(-(cu[s2] * L.u[tid] - hu[s2]), WARM_FLOOR);
-                lu[s2] = poison ? INFINITY : fmax(w.lam[lsu + s2], WARM_FLOOR);
-            }
+            for (int s2 = 0; s2 < 2; ++s2) ipm::start_warm(cu[s2] * L.u[tid] - hu[s2], [&] { return w.lam[lsu + s2]; }, poison, tu[s2], lu[s2]);
         }
-        if (xrow) {
-            txr = fmax(-(yval(L.y) - hx), WARM_FLOOR);
-            lxr = poison ? INFINITY : fmax(w.lam[lsx], WARM_FLOOR);
-        }
+        if (xrow) ipm::start_warm(yval(L.y) - hx, [&] { return w.lam[lsx]; }, poison, txr, lxr);
         scales();
         mode = PRED;
     }
@@ -2082,37 +1985,15 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
             const double uv = L.u[tid];
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
-                if (mode == INIT) {
-                    Du[s2] = 1.0; rhu[s2] = cu[s2] * uv - hu[s2]; lu[s2] = 0.0;
-                } else if (mode == PRED) {
-                    const double gq = cu[s2] * uv - hu[s2], t = tu[s2], lam = lu[s2], rg = gq + t;
-                    gu[s2] = rg;
-                    Du[s2] = lam / (t + dreg * lam);
-                    rhu[s2] = Du[s2] * (rg + dreg * lam);
-                    musum += lam * t;
-                    rpm = fmax(rpm, fabs(rg));
-                } else {
-                    const double t = tu[s2], lam = lu[s2], rc = lam * t + dtu[s2] * dlu[s2] - sig * mu;
-                    ru[s2] = rc;
-                    rhu[s2] = lam + (lam * gu[s2] - rc) / (t + dreg * lam);
-                }
+                if (mode == INIT) ipm::init_row(cu[s2] * uv - hu[s2], 1.0, Du[s2], rhu[s2], lu[s2]);
+                else if (mode == PRED) ipm::pred_row(cu[s2] * uv - hu[s2], tu[s2], lu[s2], dreg, gu[s2], Du[s2], rhu[s2], musum, rpm);
+                else ipm::corr_row(tu[s2], lu[s2], gu[s2], dtu[s2], dlu[s2], sig, mu, dreg, ru[s2], rhu[s2]);
             }
         }
         if (xrow) {
-            if (mode == INIT) {
-                Dx = 1.0; rhx = yval(L.y) - hx; lxr = 0.0;
-            } else if (mode == PRED) {
-                const double gq = yval(L.y) - hx, t = txr, lam = lxr, rg = gq + t;
-                gxr = rg;
-                Dx = lam / (t + dreg * lam);
-                rhx = Dx * (rg + dreg * lam);
-                musum += lam * t;
-                rpm = fmax(rpm, fabs(rg));
-            } else {
-                const double t = txr, lam = lxr, rc = lam * t + dtx * dlx - sig * mu;
-                rcx = rc;
-                rhx = lam + (lam * gxr - rc) / (t + dreg * lam);
-            }
+            if (mode == INIT) ipm::init_row(yval(L.y) - hx, 1.0, Dx, rhx, lxr);
+            else if (mode == PRED) ipm::pred_row(yval(L.y) - hx, txr, lxr, dreg, gxr, Dx, rhx, musum, rpm);
+            else ipm::corr_row(txr, lxr, gxr, dtx, dlx, sig, mu, dreg, rcx, rhx);
         }
         if (isu) {
             const double du0 = r2bb * (L.u[tid] - udv);
@@ -2128,16 +2009,7 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
             const double y0 = L.y[(kx - 1) * 2], y1 = L.y[(kx - 1) * 2 + 1];
             if (mode != CORR) {
                 const double a00 = gsum<GX>(cx[0] * Dx * cx[0]), a01 = gsum<GX>(cx[0] * Dx * cx[1]), a11 = gsum<GX>(cx[1] * Dx * cx[1]);
-                if (xlead) {
-                    const double S00 = s00 + a00, S01 = s01 + a01, S11 = s11 + a11;
-                    const double dmax = fmax(fabs(S00), fabs(S11));
-                    const double l00 = S00 > 1e-14 * dmax ? sqrt(S00) : 0.0;
-                    const double l10 = l00 > 0.0 ? S01 / l00 : 0.0;
-                    const double v = fma(-l10, l10, S11);
-                    const double l11 = v > 1e-14 * dmax ? sqrt(v) : 0.0;
-                    lptr Lk = L.Ls + (size_t)(kx - 1) * 4;
-                    Lk[0] = l00; Lk[1] = 0.0; Lk[2] = l10; Lk[3] = l11;
-                }
+                if (xlead) chol2_psd(s00 + a00, s01 + a01, s11 + a11, L.Ls + (size_t)(kx - 1) * 4);
             }
             const double r0 = gsum<GX>(cx[0] * rhx), r1 = gsum<GX>(cx[1] * rhx);
             double l0 = 0.0, l1 = 0.0;
@@ -2185,11 +2057,11 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
         Q4_LAP(6);
         // ---------------- use the direction
         if (mode == INIT) {
-            if (!ok) { status = 2; break; }
+            if (ipm::stops(ipm::verdict_system(ok), status)) break;
             for (int e = tid; e < nm; e += nt) L.u[e] += L.du[e];
             for (int e = tid; e < ldG; e += nt) L.y[e] += L.dy[e];
             __syncthreads();
-            if (d.ng == 0) { status = 0; break; }
+            if (ipm::stops(ipm::verdict_no_rows(d.ng), status)) break;
             double zmin = INFINITY, zmax = -INFINITY;
             if (isu) {
                 const double uv = L.u[tid];
@@ -2198,10 +2070,10 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
             }
             if (xrow) { gxr = yval(L.y) - hx; zmin = fmin(zmin, gxr); zmax = fmax(zmax, gxr); }
             reduce2(zmin, 2, zmax, 1, L.red);
-            const double sh_t = zmax >= 0.0 ? 1.0 + zmax : 0.0, sh_l = zmin <= 0.0 ? 1.0 - zmin : 0.0;
+            const ipm::Shift sh = ipm::start_shift(zmin, zmax);
 #pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) { tu[s2] = -gu[s2] + sh_t; lu[s2] = gu[s2] + sh_l; }
-            txr = -gxr + sh_t; lxr = gxr + sh_l;
+            for (int s2 = 0; s2 < 2; ++s2) ipm::start_cold(gu[s2], sh, tu[s2], lu[s2]);
+            ipm::start_cold(gxr, sh, txr, lxr);
             scales();
             mode = PRED;
             continue;
@@ -2212,52 +2084,38 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
                 const double duv = L.du[tid];
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2) {
-                    const double t = tu[s2], lam = lu[s2], rga = gu[s2] + cu[s2] * duv;
-                    const double dl = ((mode == PRED ? -lam * t : -ru[s2]) + lam * rga) / (t + dreg * lam);
-                    const double dtv = -rga + dreg * dl;
-                    dlu[s2] = dl; dtu[s2] = dtv;
-                    if (dtv < 0.0) amax = fmin(amax, -t / dtv);
-                    if (dl < 0.0) amax = fmin(amax, -lam / dl);
+                    ipm::direction(mode == PRED, tu[s2], lu[s2], gu[s2], ru[s2], cu[s2] * duv, dreg, dlu[s2], dtu[s2]);
+                    ipm::step_bound(tu[s2], lu[s2], dtu[s2], dlu[s2], amax);
                 }
             }
             if (xrow) {
-                const double t = txr, lam = lxr, rga = gxr + yval(L.dy);
-                const double dl = ((mode == PRED ? -lam * t : -rcx) + lam * rga) / (t + dreg * lam);
-                const double dtv = -rga + dreg * dl;
-                dlx = dl; dtx = dtv;
-                if (dtv < 0.0) amax = fmin(amax, -t / dtv);
-                if (dl < 0.0) amax = fmin(amax, -lam / dl);
+                ipm::direction(mode == PRED, txr, lxr, gxr, rcx, yval(L.dy), dreg, dlx, dtx);
+                ipm::step_bound(txr, lxr, dtx, dlx, amax);
             }
         }
         reduce2(amax, 2, dummy, 0, L.red);
         if (mode == PRED) {
-            if (!ok) { status = near_opt ? 0 : 2; break; }
-            if (!(mu == mu)) { status = near_opt ? 0 : 5; break; }
-            if (!(rd == rd)) { status = near_opt ? 0 : 6; break; }
-            const double ltol = fmax(d.tol, 1e-9);
-            if (rd <= ltol * sd && rp <= ltol * sp && mu <= d.tol) { status = 0; break; }
-            near_opt = (rd <= 1e-8 * sd && rp <= 1e-8 * sp && mu <= 1e-8);
-            if (it >= d.max_iter) { status = 1; break; }
-            const double a_aff = fmin(1.0, amax);
+            if (ipm::stops(ipm::verdict(ok, mu, rd, rp, sd, sp, d.tol, it, d.max_iter, near_opt), status)) break;
+            const double a_aff = ipm::step_affine(amax);
             double ma = 0.0;
             if (isu) {
 #pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) ma += (lu[s2] + a_aff * dlu[s2]) * (tu[s2] + a_aff * dtu[s2]);
+                for (int s2 = 0; s2 < 2; ++s2) ma += ipm::affine_term(tu[s2], lu[s2], dtu[s2], dlu[s2], a_aff);
             }
-            if (xrow) ma += (lxr + a_aff * dlx) * (txr + a_aff * dtx);
+            if (xrow) ma += ipm::affine_term(txr, lxr, dtx, dlx, a_aff);
             reduce2(ma, 0, dummy, 0, L.red);
             const double mu_aff = ma / d.ng;
-            sig = mu > 0.0 ? (mu_aff / mu) * (mu_aff / mu) * (mu_aff / mu) : 0.0;
+            sig = ipm::centring(mu_aff, mu);
             mode = CORR;
             continue;
         }
-        if (!ok) { status = 2; break; }
-        const double a = fmin(1.0, 0.99 * amax);
+        if (ipm::stops(ipm::verdict_system(ok), status)) break;
+        const double a = ipm::step_length(amax);
         for (int e = tid; e < nm; e += nt) L.u[e] += a * L.du[e];
         for (int e = tid; e < ldG; e += nt) L.y[e] += a * L.dy[e];
 #pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) { tu[s2] += a * dtu[s2]; lu[s2] += a * dlu[s2]; }
-        txr += a * dtx; lxr += a * dlx;
+        for (int s2 = 0; s2 < 2; ++s2) ipm::advance(a, dtu[s2], dlu[s2], tu[s2], lu[s2]);
+        ipm::advance(a, dtx, dlx, txr, lxr);
         __syncthreads();
         ++it;
         mode = PRED;
@@ -2318,11 +2176,7 @@ __device__ __forceinline__ int ipm_wave(const QPDims &dfull, const QPConst &c, c
     int tid = SRH_TID;                                       // re-read at the top of every interior-point iteration (dev_la.h: SRH_TID)
     const int nt = blockDim.x;
     QPDims d = dfull;
-    d.tr = 0;
-    d.nrx = d.nX;
-    d.RX = d.nrx + d.nXf;
-    d.NR = d.N * d.RX + d.N * d.nU;
-    d.ng = d.N * d.nrx + d.nXf + d.N * d.nU;
+    drop_trust_region_rows(d);
     QPWork w;
     qp_carve(w, work_base, d);
     wout = w;
@@ -2337,23 +2191,13 @@ __device__ __forceinline__ int ipm_wave(const QPDims &dfull, const QPConst &c, c
 #define QW_LAP(x) ((void)0)
 #endif
     // ---- the preamble of ipm_box: starting point, condensation (all waves)
-    constexpr double WARM_FLOOR = 1e-2;
     if (warm) { for (int e = tid; e < nm; e += nt) L.u[e] = w.u[e]; }
     else { for (int e = tid; e < nm; e += nt) { w.u[e] = 0.0; L.u[e] = 0.0; } }
     for (int e = tid; e < ldG + YPAD; e += nt) { L.ya[e] = 0.0; L.yd[e] = 0.0; L.yg[e] = 0.0; }
     for (int e = tid; e <= N; e += nt) w.s[e] = 0.0;
     for (int k = tid; k < N; k += nt) L.idxl[k] = dyn.idx ? dyn.idx[k] : k;
     __syncthreads();
-    bool reuse = false;
-    if (dyn.idx != nullptr) {
-        int same = L.flag[2];
-        for (int k = tid; k < N; k += nt) same = same && (L.goff[k] == L.idxl[k]);
-        if (tid == 0) L.flag[3] = 1;
-        __syncthreads();
-        if (!same) L.flag[3] = 0;
-        __syncthreads();
-        reuse = L.flag[3] != 0;
-    }
+    const bool reuse = same_regions(dyn, L, L.goff, N, tid, nt);
     if (!reuse) {
         rollout<MSEL, NSEL>(d, dyn, q.x0, (cgptr) nullptr, w.x, L);
         QW_LAP(0);
@@ -2432,29 +2276,13 @@ __device__ __forceinline__ int ipm_wave(const QPDims &dfull, const QPConst &c, c
         int mode = INIT;
         double mu = 0.0, rp = 0.0, sig = 0.0, sd = 1.0, sp = 1.0, dreg = 0.0;
         bool near_opt = false;
-        auto scales = [&]() {
-            for (int e = lane; e < d.n; e += 64) {
-                double gq = 0.0;
-                if (q.z) for (int a = 0; a < nz; ++a) gq = fma(c.HtQz2[e * nz + a], -q.z[nz + a], gq);
-                sd = fmax(sd, fabs(gq));
-            }
-            for (int e = lane; e < d.nU; e += 64) sp = fmax(sp, fabs(c.Ub[e]));
-            sd = fmax(wg::wave_max(sd), q.omega);
-            sp = fmax(wg::wave_max(sp), fabs(q.delta));
-            dreg = d.reg / sd;
-        };
+        auto scales = [&]() { qp::residual_scales(d, c, q, lane, 64, sd, sp, dreg, [](double &a, double &b) { a = wg::wave_max(a); b = wg::wave_max(b); }); };
         if (warm && d.ng > 0) {
             if (isu) {
 #pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) {
-                    tu[s2] = fmax(-(cu[s2] * u_r - hu[s2]), WARM_FLOOR);
-                    lu[s2] = poison ? INFINITY : fmax(w.lam[lsu + s2], WARM_FLOOR);
-                }
+                for (int s2 = 0; s2 < 2; ++s2) ipm::start_warm(cu[s2] * u_r - hu[s2], [&] { return w.lam[lsu + s2]; }, poison, tu[s2], lu[s2]);
             }
-            if (xrow) {
-                tx = fmax(-(yval(L.y) - hx), WARM_FLOOR);
-                lx = poison ? INFINITY : fmax(w.lam[lsx], WARM_FLOOR);
-            }
+            if (xrow) ipm::start_warm(yval(L.y) - hx, [&] { return w.lam[lsx]; }, poison, tx, lx);
             scales();
             mode = PRED;
         }
@@ -2466,20 +2294,9 @@ __device__ __forceinline__ int ipm_wave(const QPDims &dfull, const QPConst &c, c
             if (isu) {
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2) {
-                    if (mode == INIT) {
-                        Du[s2] = 1.0; rhu[s2] = cu[s2] * u_r - hu[s2]; lu[s2] = 0.0;
-                    } else if (mode == PRED) {
-                        const double gq = cu[s2] * u_r - hu[s2], t = tu[s2], lam = lu[s2], rg = gq + t;
-                        gu[s2] = rg;
-                        Du[s2] = lam / (t + dreg * lam);
-                        rhu[s2] = Du[s2] * (rg + dreg * lam);
-                        musum += lam * t;
-                        rpm = fmax(rpm, fabs(rg));
-                    } else {
-                        const double t = tu[s2], lam = lu[s2], rc = lam * t + dtu[s2] * dlu[s2] - sig * mu;
-                        ru[s2] = rc;
-                        rhu[s2] = lam + (lam * gu[s2] - rc) / (t + dreg * lam);
-                    }
+                    if (mode == INIT) ipm::init_row(cu[s2] * u_r - hu[s2], 1.0, Du[s2], rhu[s2], lu[s2]);
+                    else if (mode == PRED) ipm::pred_row(cu[s2] * u_r - hu[s2], tu[s2], lu[s2], dreg, gu[s2], Du[s2], rhu[s2], musum, rpm);
+                    else ipm::corr_row(tu[s2], lu[s2], gu[s2], dtu[s2], dlu[s2], sig, mu, dreg, ru[s2], rhu[s2]);
                 }
                 const double du0 = r2bb * (u_r - udv);
                 if (mode != CORR) {
@@ -2493,35 +2310,15 @@ __device__ __forceinline__ int ipm_wave(const QPDims &dfull, const QPConst &c, c
                 if (mode == PRED) tb_r = fma(cu[1], lu[1], fma(cu[0], lu[0], du0));
             }
             if (xrow) {
-                if (mode == INIT) {
-                    Dx = 1.0; rhx = yval(L.y) - hx; lx = 0.0;
-                } else if (mode == PRED) {
-                    const double gq = yval(L.y) - hx, t = tx, lam = lx, rg = gq + t;
-                    gx = rg;
-                    Dx = lam / (t + dreg * lam);
-                    rhx = Dx * (rg + dreg * lam);
-                    musum += lam * t;
-                    rpm = fmax(rpm, fabs(rg));
-                } else {
-                    const double t = tx, lam = lx, rc = lam * t + dtx * dlx - sig * mu;
-                    rcx = rc;
-                    rhx = lam + (lam * gx - rc) / (t + dreg * lam);
-                }
+                if (mode == INIT) ipm::init_row(yval(L.y) - hx, 1.0, Dx, rhx, lx);
+                else if (mode == PRED) ipm::pred_row(yval(L.y) - hx, tx, lx, dreg, gx, Dx, rhx, musum, rpm);
+                else ipm::corr_row(tx, lx, gx, dtx, dlx, sig, mu, dreg, rcx, rhx);
             }
             {   // whole stage groups (every lane executes the DPP sums; lanes without a row contribute zeros)
                 const double y0 = isx ? L.y[(kx - 1) * 2] : 0.0, y1 = isx ? L.y[(kx - 1) * 2 + 1] : 0.0;
                 if (mode != CORR) {
                     const double a00 = gsum<GX>(cx[0] * Dx * cx[0]), a01 = gsum<GX>(cx[0] * Dx * cx[1]), a11 = gsum<GX>(cx[1] * Dx * cx[1]);
-                    if (xlead) {
-                        const double S00 = s00 + a00, S01 = s01 + a01, S11 = s11 + a11;
-                        const double dmax = fmax(fabs(S00), fabs(S11));
-                        const double l00 = S00 > 1e-14 * dmax ? sqrt(S00) : 0.0;
-                        const double l10 = l00 > 0.0 ? S01 / l00 : 0.0;
-                        const double v = fma(-l10, l10, S11);
-                        const double l11 = v > 1e-14 * dmax ? sqrt(v) : 0.0;
-                        lptr Lk = L.Ls + (size_t)(kx - 1) * 4;
-                        Lk[0] = l00; Lk[1] = 0.0; Lk[2] = l10; Lk[3] = l11;
-                    }
+                    if (xlead) chol2_psd(s00 + a00, s01 + a01, s11 + a11, L.Ls + (size_t)(kx - 1) * 4);
                 }
                 const double r0 = gsum<GX>(cx[0] * rhx), r1 = gsum<GX>(cx[1] * rhx);
                 double l0 = 0.0, l1 = 0.0;
@@ -2644,11 +2441,11 @@ __device__ __forceinline__ int ipm_wave(const QPDims &dfull, const QPConst &c, c
             }
             // ---------------- use the direction
             if (mode == INIT) {
-                if (!ok) { status = 2; break; }
+                if (ipm::stops(ipm::verdict_system(ok), status)) break;
                 u_r += du_r;
                 if (lane < 16) L.y[lane] += L.dy[lane];
                 wave_fence();
-                if (d.ng == 0) { status = 0; break; }
+                if (ipm::stops(ipm::verdict_no_rows(d.ng), status)) break;
                 double zmin = INFINITY, zmax = -INFINITY;
                 if (isu) {
 #pragma unroll
@@ -2656,10 +2453,10 @@ __device__ __forceinline__ int ipm_wave(const QPDims &dfull, const QPConst &c, c
                 }
                 if (xrow) { gx = yval(L.y) - hx; zmin = fmin(zmin, gx); zmax = fmax(zmax, gx); }
                 zmin = wg::wave_min(zmin); zmax = wg::wave_max(zmax);
-                const double sh_t = zmax >= 0.0 ? 1.0 + zmax : 0.0, sh_l = zmin <= 0.0 ? 1.0 - zmin : 0.0;
+                const ipm::Shift sh = ipm::start_shift(zmin, zmax);
 #pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) { tu[s2] = -gu[s2] + sh_t; lu[s2] = gu[s2] + sh_l; }
-                tx = -gx + sh_t; lx = gx + sh_l;
+                for (int s2 = 0; s2 < 2; ++s2) ipm::start_cold(gu[s2], sh, tu[s2], lu[s2]);
+                ipm::start_cold(gx, sh, tx, lx);
                 scales();
                 mode = PRED;
                 continue;
@@ -2669,54 +2466,41 @@ __device__ __forceinline__ int ipm_wave(const QPDims &dfull, const QPConst &c, c
                 if (isu) {
 #pragma unroll
                     for (int s2 = 0; s2 < 2; ++s2) {
-                        const double t = tu[s2], lam = lu[s2], rga = gu[s2] + cu[s2] * du_r;
-                        const double dl = ((mode == PRED ? -lam * t : -ru[s2]) + lam * rga) / (t + dreg * lam);
-                        const double dtv = -rga + dreg * dl;
-                        dlu[s2] = dl; dtu[s2] = dtv;
-                        if (dtv < 0.0) amax = fmin(amax, -t / dtv);
-                        if (dl < 0.0) amax = fmin(amax, -lam / dl);
+                        ipm::direction(mode == PRED, tu[s2], lu[s2], gu[s2], ru[s2], cu[s2] * du_r, dreg, dlu[s2], dtu[s2]);
+                        ipm::step_bound(tu[s2], lu[s2], dtu[s2], dlu[s2], amax);
                     }
                 }
                 if (xrow) {
-                    const double t = tx, lam = lx, rga = gx + yval(L.dy);
-                    const double dl = ((mode == PRED ? -lam * t : -rcx) + lam * rga) / (t + dreg * lam);
-                    const double dtv = -rga + dreg * dl;
-                    dlx = dl; dtx = dtv;
-                    if (dtv < 0.0) amax = fmin(amax, -t / dtv);
-                    if (dl < 0.0) amax = fmin(amax, -lam / dl);
+                    ipm::direction(mode == PRED, tx, lx, gx, rcx, yval(L.dy), dreg, dlx, dtx);
+                    ipm::step_bound(tx, lx, dtx, dlx, amax);
                 }
             }
             amax = wg::wave_min(amax);
             if (mode == PRED) {
-                if (!ok) { status = near_opt ? 0 : 2; break; }
-                if (!(mu == mu)) { status = near_opt ? 0 : 5; break; }
-                if (!(rd == rd)) { status = near_opt ? 0 : 6; break; }
+                if (ipm::stops(ipm::verdict_failed(ok, mu, rd, near_opt), status)) break;
                 if (q.dbg && lane == 0) { gptr gd = q.dbg + 8 * it; gd[0] = mu; gd[1] = rd; gd[2] = rp; gd[3] = sd; gd[4] = sp; }
-                const double ltol = fmax(d.tol, 1e-9);
-                if (rd <= ltol * sd && rp <= ltol * sp && mu <= d.tol) { status = 0; break; }
-                near_opt = (rd <= 1e-8 * sd && rp <= 1e-8 * sp && mu <= 1e-8);
-                if (it >= d.max_iter) { status = 1; break; }
-                const double a_aff = fmin(1.0, amax);
+                if (ipm::stops(ipm::verdict_converged(mu, rd, rp, sd, sp, d.tol, it, d.max_iter, near_opt), status)) break;
+                const double a_aff = ipm::step_affine(amax);
                 double ma = 0.0;
                 if (isu) {
 #pragma unroll
-                    for (int s2 = 0; s2 < 2; ++s2) ma += (lu[s2] + a_aff * dlu[s2]) * (tu[s2] + a_aff * dtu[s2]);
+                    for (int s2 = 0; s2 < 2; ++s2) ma += ipm::affine_term(tu[s2], lu[s2], dtu[s2], dlu[s2], a_aff);
                 }
-                if (xrow) ma += (lx + a_aff * dlx) * (tx + a_aff * dtx);
+                if (xrow) ma += ipm::affine_term(tx, lx, dtx, dlx, a_aff);
                 const double mu_aff = wg::wave_sum(ma) / d.ng;
-                sig = mu > 0.0 ? (mu_aff / mu) * (mu_aff / mu) * (mu_aff / mu) : 0.0;
+                sig = ipm::centring(mu_aff, mu);
                 if (q.dbg && lane == 0) { gptr gd = q.dbg + 8 * it; gd[5] = a_aff; gd[6] = sig; }
                 mode = CORR;
                 continue;
             }
-            if (!ok) { status = 2; break; }
-            const double a = fmin(1.0, 0.99 * amax);
+            if (ipm::stops(ipm::verdict_system(ok), status)) break;
+            const double a = ipm::step_length(amax);
             if (q.dbg && lane == 0) { gptr gd = q.dbg + 8 * it; gd[7] = a; }
             u_r += a * du_r;
             if (lane < 16) L.y[lane] += a * L.dy[lane];
 #pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) { tu[s2] += a * dtu[s2]; lu[s2] += a * dlu[s2]; }
-            tx += a * dtx; lx += a * dlx;
+            for (int s2 = 0; s2 < 2; ++s2) ipm::advance(a, dtu[s2], dlu[s2], tu[s2], lu[s2]);
+            ipm::advance(a, dtx, dlx, tx, lx);
             wave_fence();
             ++it;
             mode = PRED;

@@ -163,3 +163,19 @@ def gusto_rule_replay(params, N, n_x, script):
     check(lib().sgusto_rule_replay(C.byref(par), C.c_int(N), C.c_int(n_x), C.c_int(script.shape[0]), dptr(script), dptr(steps),
                                    C.byref(iters), C.byref(status), C.byref(converged)), 'sgusto_rule_replay')
     return steps[:iters.value], iters.value, status.value, bool(converged.value)
+
+
+IPM_PHASES = ('init', 'cold', 'warm', 'pred', 'corr', 'direction', 'affine', 'advance', 'scales', 'verdict')
+
+
+def ipm_rule_replay(phase, rows, par):
+    """sqp_ipm_rule_replay: the interior point's row rule as the seven QP kernels run it (csrc/ipm_rule.h), evaluated on the host -- no
+    GPU needed.  phase: a name of IPM_PHASES; rows (n x 8): g, t, lambda, rg, rc, dt, dlambda, a.d (the verdict's script: ok, mu, rd, rp,
+    iteration, row count); par: up to 8 numbers (include/sofacontrol_hip.h lists both per phase).  Returns (out (n x 8), scal (8))."""
+    rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, 8)
+    p8 = np.zeros(8)
+    p8[:len(par)] = par
+    out, scal = np.zeros((rows.shape[0], 8)), np.zeros(8)
+    check(lib().sqp_ipm_rule_replay(C.c_int(IPM_PHASES.index(phase)), C.c_int(rows.shape[0]), dptr(rows), dptr(p8), dptr(out), dptr(scal)),
+          'sqp_ipm_rule_replay')
+    return out, scal
