@@ -282,7 +282,9 @@ int sric_tvlqr(const double *A, const double *B, int n_steps, int n_x, int n_u, 
 int sric_tvlqr_tpwl(stpwl_t *h, const double *xbar, int n_steps, const double *Q, const double *R,
                     double *K, double *P);
 /* solve_riccati (lqr.py:6-21): fixed point until ||L - L_old||_F <= tol (reference: 1e-4);
- * `batch` independent (A,B) pairs share Q, R.  L (batch x n_u x n_x), P (batch x n_x x n_x). */
+ * `batch` independent (A,B) pairs share Q, R.  L (batch x n_u x n_x), P (batch x n_x x n_x).  SRH_ENUMERIC, naming the
+ * first such problem, when R + B^T P B is not positive definite at some iteration (L, P are then left unwritten);
+ * reaching max_iter is not an error (the reference has none): iters = max_iter. */
 int sric_dare_fixed_point(const double *A, const double *B, int64_t batch, int n_x, int n_u,
                           const double *Q, const double *R, double tol, int max_iter, double *L,
                           double *P, int32_t *iters);

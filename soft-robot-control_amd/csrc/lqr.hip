@@ -129,7 +129,7 @@ __global__ __launch_bounds__(NT) void tvlqr_kernel(const double *A, const double
 // ------------------------------------------------------------------ fixed-point DARE (lqr.py:6-21)
 __global__ __launch_bounds__(NT) void dare_fp_kernel(const double *A, const double *B, int n, int m, const double *Q,
                                                      const double *R, double tol, int max_iter, double *Lout,
-                                                     double *Pout, int *iters) {
+                                                     double *Pout, int *iters, int *status) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     LqrLds L;
     lqr_carve(L, (lptr)smem, n, m);
@@ -138,19 +138,19 @@ __global__ __launch_bounds__(NT) void dare_fp_kernel(const double *A, const doub
     for (int e = SRH_TID; e < n * n; e += blockDim.x) L.P[e] = 0.0;
     __syncthreads();
     // L = solve(R + B'PB, B'PA) with P = 0 (no sign): zeros; L_old = inf
-    bool first = true;
-    int it = 0;
+    bool first = true, converged = false;
+    int it = 0, st = 0;
     // BK holds the previous gain (m x n) -- needs m*n <= n*m doubles
     for (int e = SRH_TID; e < m * n; e += blockDim.x) L.BK[e] = 0.0;
     __syncthreads();
     while (it < max_iter) {
         // gain of the current P:  Kk = -(R + B'PB)^-1 B'PA  ; W = P A, Kt = B'PA
-        if (!lqr_gain(L, Ag, Bg, Rg, n, m)) break;
+        if (!lqr_gain(L, Ag, Bg, Rg, n, m)) { st = 2; break; }        // R + B'PB not positive definite: L.Kk is not a gain
         if (!first) {
             double d2 = 0.0;
             for (int e = SRH_TID; e < m * n; e += blockDim.x) { const double d = L.Kk[e] - L.BK[e]; d2 = fma(d, d, d2); }
             d2 = wg::reduce(d2, 0, L.red);
-            if (sqrt(d2) <= tol) break;
+            if (sqrt(d2) <= tol) { converged = true; break; }
         }
         first = false;
         for (int e = SRH_TID; e < m * n; e += blockDim.x) L.BK[e] = L.Kk[e];
@@ -167,9 +167,11 @@ __global__ __launch_bounds__(NT) void dare_fp_kernel(const double *A, const doub
         __syncthreads();
         ++it;
     }
+    // max_iter reached: L.Kk is still the gain of the previous P -- the reference returns the gain of the P it returns
+    if (st == 0 && !converged && !lqr_gain(L, Ag, Bg, Rg, n, m)) st = 2;
     for (int e = SRH_TID; e < m * n; e += blockDim.x) Lout[p * m * n + e] = L.Kk[e];
     for (int e = SRH_TID; e < n * n; e += blockDim.x) Pout[p * n * n + e] = L.P[e];
-    if (SRH_TID == 0 && iters) iters[p] = it;
+    if (SRH_TID == 0) { if (iters) iters[p] = it; status[p] = st; }
 }
 
 // ------------------------------------------------------------------ DARE by structure-preserving doubling
@@ -1163,20 +1165,28 @@ int sric_dare_fixed_point(const double *A, const double *B, int64_t batch, int n
                           const double *R, double tol, int max_iter, double *L, double *P, int32_t *iters) {
     SRH_REQUIRE(A && B && Q && R && L && P, "sric_dare_fixed_point: null argument");
     SRH_REQUIRE(batch > 0 && n_x > 0 && n_u > 0 && n_u <= 16, "sric_dare_fixed_point: bad dimensions");
-    srh::DevBuf dA, dB, dQ, dR, dL, dP, dI;
+    srh::DevBuf dA, dB, dQ, dR, dL, dP, dI, dS;
     int rc;
     if ((rc = dA.upload(A, sizeof(double) * batch * n_x * n_x)) || (rc = dB.upload(B, sizeof(double) * batch * n_x * n_u)) ||
         (rc = dQ.upload(Q, sizeof(double) * n_x * n_x)) || (rc = dR.upload(R, sizeof(double) * n_u * n_u)) ||
         (rc = dL.alloc(sizeof(double) * batch * n_u * n_x)) || (rc = dP.alloc(sizeof(double) * batch * n_x * n_x)) ||
-        (rc = dI.alloc(sizeof(int32_t) * batch)))
+        (rc = dI.alloc(sizeof(int32_t) * batch)) || (rc = dS.alloc(sizeof(int32_t) * batch)))
         return rc;
     const size_t lds = srh::lds_request(lqr_lds_doubles(n_x, n_u) * sizeof(double));
     SRH_REQUIRE(lds <= 160 * 1024, "sric_dare_fixed_point: state dimension too large for LDS");
     SRH_CHECK_HIP(hipFuncSetAttribute((const void *)dare_fp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     dare_fp_kernel<<<(unsigned)batch, NT, lds>>>(dA.as<double>(), dB.as<double>(), n_x, n_u, dQ.as<double>(), dR.as<double>(),
-                                                 tol, max_iter, dL.as<double>(), dP.as<double>(), dI.as<int>());
+                                                 tol, max_iter, dL.as<double>(), dP.as<double>(), dI.as<int>(), dS.as<int>());
     SRH_CHECK_HIP(hipGetLastError());
     SRH_CHECK_HIP(hipStreamSynchronize(nullptr));
+    // a failed factorisation leaves no gain to return (max_iter reached is not an error: the reference has none)
+    std::vector<int32_t> st((size_t)batch);
+    if ((rc = dS.download(st.data(), sizeof(int32_t) * batch))) return rc;
+    for (int64_t i = 0; i < batch; ++i)
+        if (st[i] != 0) {
+            srh::set_error("sric_dare_fixed_point: problem %lld: R + B^T P B is not positive definite", (long long)i);
+            return SRH_ENUMERIC;
+        }
     if ((rc = dL.download(L, sizeof(double) * batch * n_u * n_x)) || (rc = dP.download(P, sizeof(double) * batch * n_x * n_x))) return rc;
     if (iters) return dI.download(iters, sizeof(int32_t) * batch);
     return SRH_OK;

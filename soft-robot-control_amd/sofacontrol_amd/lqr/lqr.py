@@ -24,6 +24,19 @@ def solve_riccati(A, B, Q, R):
     return L[0], P[0]
 
 
+def tvlqr(A, B, Q, R):
+    """Finite-horizon TV-LQR for explicit per-step (A_i, B_i), i = 0..n-1 in forward time order, terminal P = Q
+    (traj_tracking_lqr.py:18-48 without the TPWL lookup, `sric_tvlqr`): K (n, n_u, n_x), P (n + 1, n_x, n_x), u = +K x."""
+    A, B = _lib.f64(A), _lib.f64(B)
+    steps, n, m = B.shape
+    if A.shape != (steps, n, n):
+        raise RuntimeError('tvlqr: A %s does not match B %s' % (A.shape, B.shape))
+    K = np.empty((steps, m, n)); P = np.empty((steps + 1, n, n))
+    _lib.check(_lib.lib().sric_tvlqr(_lib.dptr(A), _lib.dptr(B), C.c_int(steps), C.c_int(n), C.c_int(m),
+                                     _lib.dptr(_lib.f64(Q)), _lib.dptr(_lib.f64(R)), _lib.dptr(K), _lib.dptr(P)), 'sric_tvlqr')
+    return K, P
+
+
 def _doubling(A, B, Q, R, tol, max_iter):
     A = _lib.f64(np.atleast_3d(A).reshape(-1, A.shape[-2], A.shape[-1]))
     B = _lib.f64(np.atleast_3d(B).reshape(-1, B.shape[-2], B.shape[-1]))

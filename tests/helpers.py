@@ -75,3 +75,25 @@ def assembly_points(n_f, m, q_ref, seed, count=3):
         pts.append(dict(K=K, D=D, M=M, S=S, H=H, b=b, f=f, q=q, v=v, q_next=q + 0.01 * v,
                         v_next=v + 0.01 * rng.standard_normal(n_f), u=rng.uniform(0, 100, m), t=0.01 * i, dt=0.01))
     return pts
+
+
+def ilqr_batch_equals_singles(il, x0s, z_targets, u_warms, u_lasts):
+    """Solve B DIFFERENT iLQR problems in one launch -- x0s (B, n_x), z_targets (B, N+1, n_z), u_warms (B, N, n_u) or
+    None, u_lasts (B, n_u) -- and each of them alone: x, u, K, cost and iters of every member must equal its single
+    solve bit for bit (one workgroup per problem, nothing shared).  The members must differ, or a kernel that reads
+    problem 0's inputs or work slice for every problem would pass."""
+    Bn = len(x0s)
+    for a in (x0s, z_targets, u_lasts) + (() if u_warms is None else (u_warms,)):
+        assert len(a) == Bn and all(not np.array_equal(a[0], a[b]) for b in range(1, Bn))
+    il.set_target(np.asarray(z_targets))
+    il.set_u_last(np.asarray(u_lasts))
+    xb, ub, Kb = il.ilqr_computation(np.asarray(x0s), None if u_warms is None else np.asarray(u_warms))
+    cb, ib = il.cost.copy(), il.iters.copy()
+    assert xb.shape[0] == ub.shape[0] == Kb.shape[0] == len(cb) == len(ib) == Bn
+    for b in range(Bn):
+        il.set_target(np.asarray(z_targets[b]))
+        il.set_u_last(np.asarray(u_lasts[b]))
+        x, u, K = il.ilqr_computation(np.asarray(x0s[b]), None if u_warms is None else np.asarray(u_warms[b]))
+        assert int(il.iters[0]) == int(ib[b]), (b, int(il.iters[0]), int(ib[b]))
+        np.testing.assert_array_equal(xb[b], x); np.testing.assert_array_equal(ub[b], u)
+        np.testing.assert_array_equal(Kb[b], K); np.testing.assert_array_equal(cb[b], il.cost[0])

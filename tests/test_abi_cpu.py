@@ -57,7 +57,7 @@ def test_host_mirror_surface_matches_reference_names():
                        (pod, ['POD', 'pod_config', 'load_POD', 'run_POD', 'get_snapshots', 'process_snapshots', 'compute_POD']),
                        (tpwl, ['TPWL', 'TPWLATV']), (gusto, ['GuSTO']), (locp, ['LOCP']),
                        (sa, ['runGuSTOSolverStandAlone', 'GuSTOSolverNode']), (mt, ['TPWLGuSTO']),
-                       (ilqr, ['iLQR']), (lqr, ['solve_riccati', 'dare', 'DLQR']), (tt, ['TrajTrackingLQR']),
+                       (ilqr, ['iLQR']), (lqr, ['solve_riccati', 'dare', 'tvlqr', 'DLQR']), (tt, ['TrajTrackingLQR']),
                        (utils, ['QuadraticCost', 'qv2x', 'x2qv', 'Polyhedron', 'HyperRectangle', 'arr2np', 'np2arr'])]:
         for n in names:
             assert hasattr(mod, n), (mod.__name__, n)

@@ -5,7 +5,7 @@ import contextlib
 import numpy as np
 import pytest
 
-from helpers import golden_problem, product_tpwl
+from helpers import golden_problem, product_tpwl, ilqr_batch_equals_singles
 
 pytestmark = pytest.mark.gpu
 
@@ -58,6 +58,7 @@ def test_ilqr_full_solve(golden, tag, N):
     il.set_target(g[tag + '_z_target'])
     x, u, K = il.ilqr_computation(g[tag + '_x0'], g[tag + '_uw'])
     assert int(il.iters[0]) == int(g[tag + '_iters'])
+    # 1e-6: R = 1e-3 I against a rank-deficient Qz limits the float64 reference itself ("Exact LQ tests of the Riccati and iLQR kernels")
     close(x, g[tag + '_sol_x'], 1e-6); close(u, g[tag + '_sol_u'], 1e-6); close(K, g[tag + '_sol_K'], 1e-6)
     x, u, K = il.ilqr_computation(g[tag + '_x0'])
     assert int(il.iters[0]) == int(g[tag + '_iters0'])
@@ -65,6 +66,12 @@ def test_ilqr_full_solve(golden, tag, N):
     # batched: two problems in one launch equal the single solves
     xb, ub, Kb = il.ilqr_computation(np.stack([g[tag + '_x0'], g[tag + '_x0']]))
     np.testing.assert_array_equal(xb[0], x); np.testing.assert_array_equal(xb[1], x)
+    # ... and three DIFFERENT problems (x0, target, warm start, u_last) equal theirs: the pair above cannot see a stride bug
+    rng = np.random.default_rng(N)
+    f = lambda v: np.stack([v * (1.0 + 0.1 * k * rng.standard_normal(v.shape)) for k in range(3)])
+    z_ref = np.asarray(tp.z_ref)
+    ilqr_batch_equals_singles(il, f(g[tag + '_x0']), z_ref + f(g[tag + '_z_target'] - z_ref), f(g[tag + '_uw']),
+                              f(g[tag + '_uw'][0]))
 
 
 @pytest.mark.parametrize('case', ['reference', 'include_input_var_constraint', 'do_linesearch', 'regularize', 'state_regularization', 'all_off'])
@@ -89,6 +96,7 @@ def test_ilqr_config_switches(golden, case):
         # (ilqr.py:109-115) waits for the sign of that rounding noise: the count may differ by one, the result may not
         slack = 1 if case == 'all_off' else 0
         assert abs(int(il.iters[0]) - int(g[key + '_iters'])) <= slack, (key, int(il.iters[0]), int(g[key + '_iters']))
+        # 1e-6: R = 1e-3 I against a rank-deficient Qz limits the float64 reference itself ("Exact LQ tests of the Riccati and iLQR kernels")
         close(x, g[key + '_x'], 1e-6); close(u, g[key + '_u'], 1e-6); close(K, g[key + '_K'], 1e-5)
 
 
@@ -118,6 +126,7 @@ def test_ilqr_diamond_sizes_vs_oracle(r, m):
     o = olqr.ILQR(model, Ad, Bd, dd, H, z_ref, Qz, R, 10 * Qz, N)
     xo, uo, Ko = o.solve(x0, zt)
     assert int(il.iters[0]) == len(o.trace) - 1
+    # 1e-6: R = 1e-3 I against a rank-deficient Qz limits the float64 reference itself ("Exact LQ tests of the Riccati and iLQR kernels")
     close(x, xo, 1e-6); close(u, uo, 1e-6); close(K, Ko, 1e-5)
 
 
