@@ -3,40 +3,13 @@
 // DARE), sofacontrol/lqr/ilqr.py:27-300 + sofacontrol/lqr/config.py (iLQR).
 #include "tpwl_host.h"
 #include "ssm_host.h"
+#include "dare_sda.h"
 
 namespace {
 
 constexpr int NT = 512;
 
-// ---- tiny dense helpers (row-major, any address space, runtime sizes; one output per thread-iteration)
-// C (M x N) = alpha * op(A) * op(B) + beta * C0 ; op = transpose flag.  Ends with __syncthreads().
-template <bool TA, bool TB, typename CP, typename AP, typename BP>
-__device__ inline void mm(CP C, int ldc, AP A, int lda, BP B, int ldb, int M, int N, int K) {
-    for (int e = SRH_TID; e < M * N; e += blockDim.x) {
-        const int i = e / N, j = e - i * N;
-        double acc = 0.0;
-        int k = 0;
-        // 8 independent operand pairs in flight per trip: with one or two waves per SIMD the dependent
-        // load -> fma chain of a rolled loop is bound by the LDS / L2 latency of every single k
-        for (; k + 8 <= K; k += 8) {
-            double av[8], bv[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                av[q] = TA ? A[(k + q) * lda + i] : A[i * lda + k + q];
-                bv[q] = TB ? B[j * ldb + k + q] : B[(k + q) * ldb + j];
-            }
-#pragma unroll
-            for (int q = 0; q < 8; ++q) acc = fma(av[q], bv[q], acc);
-        }
-        for (; k < K; ++k) {
-            const double a = TA ? A[k * lda + i] : A[i * lda + k];
-            const double b = TB ? B[j * ldb + k] : B[k * ldb + j];
-            acc = fma(a, b, acc);
-        }
-        C[i * ldc + j] = acc;
-    }
-    __syncthreads();
-}
+using sda::mm;          // the tiny dense product (row-major, any address space, runtime sizes), shared with the doubling loop
 
 // Cholesky (thread 0) + solve helper for m <= 16 on LDS
 __device__ inline bool chol16(lptr Q, lptr Lb, int m, liptr flag) { return wg::chol_factor(Q, Lb, m, flag, false); }
@@ -184,14 +157,9 @@ __global__ __launch_bounds__(NT) void dare_fp_kernel(const double *A, const doub
 // slots (W / scratch, A -> V1, G -> V2, H, A_next) in LDS when they fit (n <= 62), else in the per-problem HBM
 // workspace next to the copies of A_k, G_k that the products read through L2; W^-1 by Gauss-Jordan elimination with
 // partial pivoting (physical row swaps) on the tableau [W | A | G]; all products on the VALU (mm), generic pointers.
-struct SdaTail {
-    lptr Rq, Lc, Bt, Yn;     // R (m x m), its Cholesky factor, B^T (m x n), -R^-1 B^T (m x n)
-    lptr fcol, prow, jrow;   // Gauss-Jordan: multipliers (n), pivot row (3n), old row j (3n)
-    lptr red;
-    liptr flag, ipiv;
-};
-
-__host__ __device__ inline size_t sda_tail_doubles(int n, int m) { return 512 + 2 * (size_t)m * n + 7 * (size_t)n + 16 + 8; }
+// m-wide head of the LDS tail behind the slots: R (m x m, m <= 16) and its Cholesky factor in 256 doubles each, B^T and
+// -R^-1 B^T (m x n); then the rows of sda::Rows
+__host__ __device__ inline size_t sda_tail_doubles(int n, int m) { return 512 + 2 * (size_t)m * n + sda::rows_doubles(n); }
 
 __global__ __launch_bounds__(NT) void dare_sda_kernel(const double *A, const double *B, int n, int m, const double *Q,
                                                       const double *R, double tol, int max_iter, double *work,
@@ -199,127 +167,27 @@ __global__ __launch_bounds__(NT) void dare_sda_kernel(const double *A, const dou
                                                       int *status) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const size_t p = blockIdx.x;
-    const int ld = n | 1, tid = SRH_TID, nt = blockDim.x;
-    const size_t nn = (size_t)n * ld;
-    double *wk = work + p * (7 * nn);
-    double *gA = wk, *gG = wk + nn;
-    double *sm = (double *)smem;
-    double *S1, *S2, *S3, *S4, *S5;
-    lptr tail;
-    if (lds_slots) {
-        S1 = sm; S2 = sm + nn; S3 = sm + 2 * nn; S4 = sm + 3 * nn; S5 = sm + 4 * nn;
-        tail = (lptr)smem + 5 * nn;
-    } else {
-        S1 = wk + 2 * nn; S2 = wk + 3 * nn; S3 = wk + 4 * nn; S4 = wk + 5 * nn; S5 = wk + 6 * nn;
-        tail = (lptr)smem;
-    }
-    SdaTail T;
-    {
-        lptr q = tail;
-        auto take = [&](size_t c) { lptr r0 = q; q += c; return r0; };
-        T.Rq = take(256); T.Lc = take(256); T.Bt = take((size_t)m * n); T.Yn = take((size_t)m * n);
-        T.fcol = take(n); T.prow = take(3 * (size_t)n); T.jrow = take(3 * (size_t)n); T.red = take(16);
-        T.flag = (liptr)take(4); T.ipiv = (liptr)take(4);
-    }
+    const int tid = SRH_TID, nt = blockDim.x;
+    sda::Slots S;
+    sda::Rows T;
+    const lptr Rq = sda::carve_slots(S, smem, work, p, n, lds_slots), Lc = Rq + 256, Bt = Lc + 256, Yn = Bt + (size_t)m * n;
+    sda::carve_rows(T, Yn + (size_t)m * n, n);
     cgptr Ag = (cgptr)A + p * n * n, Bg = (cgptr)B + p * n * m, Qg = (cgptr)Q, Rg = (cgptr)R;
-    int st = 0, it = 0;
+    int st = 0;
 
     // ---- G0 = B R^-1 B^T, H0 = Q, A0 = A
-    for (int e = tid; e < m * m; e += nt) T.Rq[e] = Rg[e];
-    for (int e = tid; e < m * n; e += nt) T.Bt[e] = Bg[(e % n) * m + e / n];
+    for (int e = tid; e < m * m; e += nt) Rq[e] = Rg[e];
+    for (int e = tid; e < m * n; e += nt) Bt[e] = Bg[(e % n) * m + e / n];
     __syncthreads();
-    if (!wg::chol_factor(T.Rq, T.Lc, m, T.flag, false)) st = 2;
+    if (!wg::chol_factor(Rq, Lc, m, T.flag, false)) st = 2;
     if (st == 0) {
-        for (int j = tid; j < n; j += nt) wg::chol_solve_neg(T.Lc, m, T.Bt + j, n, T.Yn + j, n);
+        for (int j = tid; j < n; j += nt) wg::chol_solve_neg(Lc, m, Bt + j, n, Yn + j, n);
         __syncthreads();
-        for (int e = tid; e < n * n; e += nt) {
-            const int r = e / n, c = e - r * n;
-            double g = 0.0;
-            for (int a = 0; a < m; ++a) g = fma(-T.Bt[a * n + r], T.Yn[a * n + c], g);
-            S3[r * ld + c] = g; gG[r * ld + c] = g;
-            const double av = Ag[e];
-            S2[r * ld + c] = av; gA[r * ld + c] = av;
-            S4[r * ld + c] = Qg[e];
-        }
-        __syncthreads();
+        sda::start(S, Ag, Qg, Bt, Yn, n, m);
     }
-    while (st == 0 && it < max_iter) {
-        // W = I + G H
-        mm<false, false>(S1, ld, S3, ld, S4, ld, n, n, n);
-        for (int e = tid; e < n; e += nt) S1[e * ld + e] += 1.0;
-        __syncthreads();
-        // [V1 V2] = W^-1 [A G]: Gauss-Jordan with partial pivoting on [S1 | S2 | S3]
-        for (int j = 0; j < n && st == 0; ++j) {
-            if (tid < 64) {
-                double best = -1.0;
-                int bi = j;
-                for (int i = j + tid; i < n; i += 64) {
-                    const double v = fabs(S1[i * ld + j]);
-                    if (v > best) { best = v; bi = i; }
-                }
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const double ob = __shfl_xor(best, o, 64);
-                    const int oi = __shfl_xor(bi, o, 64);
-                    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-                }
-                if (tid == 0) { T.ipiv[0] = bi; T.ipiv[1] = (best > 1e-300 && best < 1e300) ? 1 : 0; }
-            }
-            __syncthreads();
-            const int pv = T.ipiv[0];
-            if (T.ipiv[1] == 0) { st = 3; break; }
-            // snapshot: pivot row (old row pv), old row j, multipliers of every row as they will sit after the swap
-            for (int c = tid; c < 3 * n; c += nt) {
-                double *blk = c < n ? S1 : (c < 2 * n ? S2 : S3);
-                const int cc = c < n ? c : (c < 2 * n ? c - n : c - 2 * n);
-                T.prow[c] = blk[pv * ld + cc];
-                T.jrow[c] = blk[j * ld + cc];
-            }
-            for (int i = tid; i < n; i += nt) T.fcol[i] = S1[(i == pv ? j : i) * ld + j];
-            __syncthreads();
-            const double rp = 1.0 / T.prow[j];
-            for (int e = tid; e < 3 * n * n; e += nt) {
-                const int i = e / (3 * n), c = e - i * 3 * n;
-                double *blk = c < n ? S1 : (c < 2 * n ? S2 : S3);
-                const int cc = c < n ? c : (c < 2 * n ? c - n : c - 2 * n);
-                const double pr = T.prow[c] * rp;
-                double v;
-                if (i == j) v = pr;
-                else {
-                    const double src = (i == pv) ? T.jrow[c] : blk[i * ld + cc];
-                    v = fma(-T.fcol[i], pr, src);
-                }
-                blk[i * ld + cc] = v;
-            }
-            __syncthreads();
-        }
-        if (st != 0) break;
-        mm<false, false>(S5, ld, gA, ld, S2, ld, n, n, n);            // A_next = A V1
-        mm<false, false>(S1, ld, gA, ld, S3, ld, n, n, n);            // T2 = A V2
-        mm<false, true>(S3, ld, S1, ld, gA, ld, n, n, n);             // T2 A^T  (V2 is dead)
-        for (int e = tid; e < n * n; e += nt) { const int r = e / n, c = e - r * n; S3[r * ld + c] += gG[r * ld + c]; }
-        mm<false, false>(S1, ld, S4, ld, S2, ld, n, n, n);            // T3 = H V1
-        mm<true, false>(S2, ld, gA, ld, S1, ld, n, n, n);             // A^T T3  (V1 is dead)
-        double dmax = 0.0, hmax = 0.0;
-        for (int e = tid; e < n * n; e += nt) {
-            const int r = e / n, c = e - r * n;
-            const double d = S2[r * ld + c], h = S4[r * ld + c] + d;
-            S4[r * ld + c] = h;
-            dmax = fmax(dmax, fabs(d)); hmax = fmax(hmax, fabs(h));
-            const double an = S5[r * ld + c];
-            S2[r * ld + c] = an; gA[r * ld + c] = an;
-            gG[r * ld + c] = S3[r * ld + c];
-        }
-        dmax = wg::reduce(dmax, 1, T.red);
-        hmax = wg::reduce(hmax, 1, T.red);
-        __syncthreads();
-        ++it;
-        if (!(dmax == dmax) || !(hmax < 1e300)) { st = 3; break; }
-        if (dmax <= tol * hmax) break;
-    }
-    if (st == 0 && it >= max_iter) st = 1;
-    for (int e = tid; e < n * n; e += nt) { const int r = e / n, c = e - r * n; Pout[p * n * n + e] = S4[r * ld + c]; }
-    __syncthreads();
+    const sda::Result res = sda::iterate(S, T, n, tol, max_iter, st, Pout + p * n * n);
+    st = res.st;
+    const int it = res.it;
     // gain K = -(R + B^T P B)^-1 B^T P A from the converged P (the fixed-point kernel's routine, its own LDS carve)
     LqrLds L;
     lqr_carve(L, (lptr)smem, n, m);
@@ -1165,70 +1033,19 @@ int sric_dare_fixed_point(const double *A, const double *B, int64_t batch, int n
                           const double *R, double tol, int max_iter, double *L, double *P, int32_t *iters) {
     SRH_REQUIRE(A && B && Q && R && L && P, "sric_dare_fixed_point: null argument");
     SRH_REQUIRE(batch > 0 && n_x > 0 && n_u > 0 && n_u <= 16, "sric_dare_fixed_point: bad dimensions");
-    srh::DevBuf dA, dB, dQ, dR, dL, dP, dI, dS;
-    int rc;
-    if ((rc = dA.upload(A, sizeof(double) * batch * n_x * n_x)) || (rc = dB.upload(B, sizeof(double) * batch * n_x * n_u)) ||
-        (rc = dQ.upload(Q, sizeof(double) * n_x * n_x)) || (rc = dR.upload(R, sizeof(double) * n_u * n_u)) ||
-        (rc = dL.alloc(sizeof(double) * batch * n_u * n_x)) || (rc = dP.alloc(sizeof(double) * batch * n_x * n_x)) ||
-        (rc = dI.alloc(sizeof(int32_t) * batch)) || (rc = dS.alloc(sizeof(int32_t) * batch)))
-        return rc;
     const size_t lds = srh::lds_request(lqr_lds_doubles(n_x, n_u) * sizeof(double));
     SRH_REQUIRE(lds <= 160 * 1024, "sric_dare_fixed_point: state dimension too large for LDS");
-    SRH_CHECK_HIP(hipFuncSetAttribute((const void *)dare_fp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    dare_fp_kernel<<<(unsigned)batch, NT, lds>>>(dA.as<double>(), dB.as<double>(), n_x, n_u, dQ.as<double>(), dR.as<double>(),
-                                                 tol, max_iter, dL.as<double>(), dP.as<double>(), dI.as<int>(), dS.as<int>());
-    SRH_CHECK_HIP(hipGetLastError());
-    SRH_CHECK_HIP(hipStreamSynchronize(nullptr));
-    // a failed factorisation leaves no gain to return (max_iter reached is not an error: the reference has none)
-    std::vector<int32_t> st((size_t)batch);
-    if ((rc = dS.download(st.data(), sizeof(int32_t) * batch))) return rc;
-    for (int64_t i = 0; i < batch; ++i)
-        if (st[i] != 0) {
-            srh::set_error("sric_dare_fixed_point: problem %lld: R + B^T P B is not positive definite", (long long)i);
-            return SRH_ENUMERIC;
-        }
-    if ((rc = dL.download(L, sizeof(double) * batch * n_u * n_x)) || (rc = dP.download(P, sizeof(double) * batch * n_x * n_x))) return rc;
-    if (iters) return dI.download(iters, sizeof(int32_t) * batch);
-    return SRH_OK;
+    return sda::run(sda::Launch("sric_dare_fixed_point", dare_fp_kernel, NT, lds), A, B, batch, n_x, n_u, Q, R, tol, max_iter, L, P, iters);
 }
 
 int sric_dare(const double *A, const double *B, int64_t batch, int n_x, int n_u, const double *Q, const double *R,
               double tol, int max_iter, double *L, double *P, int32_t *iters) {
     SRH_REQUIRE(A && B && Q && R && L && P, "sric_dare: null argument");
     SRH_REQUIRE(batch > 0 && n_x > 0 && n_u > 0 && n_u <= 16, "sric_dare: bad dimensions");
-    const int ld = n_x | 1;
-    const size_t nn = (size_t)n_x * ld;
-    srh::DevBuf dA, dB, dQ, dR, dL, dP, dI, dS, dW;
-    int rc;
-    if ((rc = dA.upload(A, sizeof(double) * batch * n_x * n_x)) || (rc = dB.upload(B, sizeof(double) * batch * n_x * n_u)) ||
-        (rc = dQ.upload(Q, sizeof(double) * n_x * n_x)) || (rc = dR.upload(R, sizeof(double) * n_u * n_u)) ||
-        (rc = dL.alloc(sizeof(double) * batch * n_u * n_x)) || (rc = dP.alloc(sizeof(double) * batch * n_x * n_x)) ||
-        (rc = dI.alloc(sizeof(int32_t) * batch)) || (rc = dS.alloc(sizeof(int32_t) * batch)) ||
-        (rc = dW.alloc(sizeof(double) * batch * 7 * nn)))
-        return rc;
     const size_t gain_lds = lqr_lds_doubles(n_x, n_u) * sizeof(double);
     const size_t tail = sda_tail_doubles(n_x, n_u) * sizeof(double);
     SRH_REQUIRE(gain_lds <= 160 * 1024 && tail <= 160 * 1024, "sric_dare: state dimension too large for LDS");
-    const int lds_slots = (5 * nn * sizeof(double) + tail <= 160 * 1024 && !getenv("SRH_DARE_HBM_SLOTS")) ? 1 : 0;
-    const size_t lds = srh::lds_request(std::max(gain_lds, (lds_slots ? 5 * nn * sizeof(double) : 0) + tail));
-    SRH_CHECK_HIP(hipFuncSetAttribute((const void *)dare_sda_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    dare_sda_kernel<<<(unsigned)batch, NT, lds>>>(dA.as<double>(), dB.as<double>(), n_x, n_u, dQ.as<double>(), dR.as<double>(),
-                                                  tol, max_iter, dW.as<double>(), lds_slots, dL.as<double>(), dP.as<double>(),
-                                                  dI.as<int>(), dS.as<int>());
-    SRH_CHECK_HIP(hipGetLastError());
-    SRH_CHECK_HIP(hipStreamSynchronize(nullptr));
-    std::vector<int32_t> st((size_t)batch);
-    if ((rc = dS.download(st.data(), sizeof(int32_t) * batch))) return rc;
-    for (int64_t i = 0; i < batch; ++i)
-        if (st[i] != 0) {
-            srh::set_error("sric_dare: problem %lld: %s", (long long)i,
-                           st[i] == 1 ? "no convergence within max_iter doubling steps"
-                                      : (st[i] == 2 ? "R or R + B^T P B is not positive definite" : "singular I + G H (not stabilisable / detectable?)"));
-            return SRH_ENUMERIC;
-        }
-    if ((rc = dL.download(L, sizeof(double) * batch * n_u * n_x)) || (rc = dP.download(P, sizeof(double) * batch * n_x * n_x))) return rc;
-    if (iters) return dI.download(iters, sizeof(int32_t) * batch);
-    return SRH_OK;
+    return sda::run(sda::Launch("sric_dare", dare_sda_kernel, NT, tail, gain_lds), A, B, batch, n_x, n_u, Q, R, tol, max_iter, L, P, iters);
 }
 
 static int ilqr_impl(stpwl_t *ht, sssm_t *hs, int ssm_mode, double dt, int N, int64_t batch, const double *x0,

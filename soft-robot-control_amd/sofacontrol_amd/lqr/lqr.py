@@ -6,16 +6,22 @@ import numpy as np
 from .. import _lib
 
 
-def _fixed_point(A, B, Q, R, tol, max_iter):
-    A = _lib.f64(np.atleast_3d(A).reshape(-1, A.shape[-2], A.shape[-1]))
-    B = _lib.f64(np.atleast_3d(B).reshape(-1, B.shape[-2], B.shape[-1]))
+def _dare_call(entry, A, B, Q, R, tol, max_iter):
+    """One of the three DARE entry points (`sric_dare_fixed_point`, `sric_dare`, `sric_dare_wide`: one argument list) on a
+    single (A, B) pair or a stack of them: stacked (L, P, iterations)."""
+    A, B = np.asarray(A), np.asarray(B)
+    A = _lib.f64(A.reshape(-1, A.shape[-2], A.shape[-1]))
+    B = _lib.f64(B.reshape(-1, B.shape[-2], B.shape[-1]))
     batch, n, m = B.shape
     L = np.empty((batch, m, n)); P = np.empty((batch, n, n)); it = np.empty(batch, dtype=np.int32)
-    _lib.check(_lib.lib().sric_dare_fixed_point(_lib.dptr(A), _lib.dptr(B), C.c_int64(batch), C.c_int(n), C.c_int(m),
-                                                _lib.dptr(_lib.f64(Q)), _lib.dptr(_lib.f64(R)), C.c_double(tol),
-                                                C.c_int(max_iter), _lib.dptr(L), _lib.dptr(P), _lib.iptr(it)),
-               'sric_dare_fixed_point')
+    _lib.check(getattr(_lib.lib(), entry)(_lib.dptr(A), _lib.dptr(B), C.c_int64(batch), C.c_int(n), C.c_int(m),
+                                          _lib.dptr(_lib.f64(Q)), _lib.dptr(_lib.f64(R)), C.c_double(tol), C.c_int(max_iter),
+                                          _lib.dptr(L), _lib.dptr(P), _lib.iptr(it)), entry)
     return L, P, it
+
+
+def _fixed_point(A, B, Q, R, tol, max_iter):
+    return _dare_call('sric_dare_fixed_point', A, B, Q, R, tol, max_iter)
 
 
 def solve_riccati(A, B, Q, R):
@@ -37,21 +43,10 @@ def tvlqr(A, B, Q, R):
     return K, P
 
 
-def _doubling(A, B, Q, R, tol, max_iter):
-    A = _lib.f64(np.atleast_3d(A).reshape(-1, A.shape[-2], A.shape[-1]))
-    B = _lib.f64(np.atleast_3d(B).reshape(-1, B.shape[-2], B.shape[-1]))
-    batch, n, m = B.shape
-    L = np.empty((batch, m, n)); P = np.empty((batch, n, n)); it = np.empty(batch, dtype=np.int32)
-    _lib.check(_lib.lib().sric_dare(_lib.dptr(A), _lib.dptr(B), C.c_int64(batch), C.c_int(n), C.c_int(m),
-                                    _lib.dptr(_lib.f64(Q)), _lib.dptr(_lib.f64(R)), C.c_double(tol), C.c_int(max_iter),
-                                    _lib.dptr(L), _lib.dptr(P), _lib.iptr(it)), 'sric_dare')
-    return L, P, it
-
-
 def dare(Ad, Bd, Q, R):
     """lqr.py:24-31 (scipy.linalg.solve_discrete_are in the reference): the stabilising DARE solution and its gain
     K = -(R + B'PB)^-1 B'PA, by the structure-preserving doubling algorithm on the device (`sric_dare`)."""
-    L, P, _ = _doubling(Ad, Bd, Q, R, 1e-14, 100)
+    L, P, _ = _dare_call('sric_dare', Ad, Bd, Q, R, 1e-14, 100)
     return L[0], P[0]
 
 
@@ -59,21 +54,14 @@ def dare_wide(Ad, Bd, Q, R):
     """`dare` for an input block of up to 64 columns (`sric_dare_wide`, csrc/dare_wide.hip): what the ROMPC observer asks
     for, dare(A_d.T, C.T, Q, R) with one "input" per measurement (baselines/rompc/observer.py:27).  Same doubling steps,
     tolerance and sign (u = +K x); a stack of (A_d, B_d) pairs returns stacked (K, P)."""
-    Ad, Bd = np.asarray(Ad), np.asarray(Bd)
-    A = _lib.f64(Ad.reshape(-1, Ad.shape[-2], Ad.shape[-1]))
-    B = _lib.f64(Bd.reshape(-1, Bd.shape[-2], Bd.shape[-1]))
-    batch, n, m = B.shape
-    K = np.empty((batch, m, n)); P = np.empty((batch, n, n)); it = np.empty(batch, dtype=np.int32)
-    _lib.check(_lib.lib().sric_dare_wide(_lib.dptr(A), _lib.dptr(B), C.c_int64(batch), C.c_int(n), C.c_int(m),
-                                         _lib.dptr(_lib.f64(Q)), _lib.dptr(_lib.f64(R)), C.c_double(1e-14), C.c_int(100),
-                                         _lib.dptr(K), _lib.dptr(P), _lib.iptr(it)), 'sric_dare_wide')
-    return (K, P) if Bd.ndim == 3 else (K[0], P[0])
+    K, P, _ = _dare_call('sric_dare_wide', Ad, Bd, Q, R, 1e-14, 100)
+    return (K, P) if np.ndim(Bd) == 3 else (K[0], P[0])
 
 
 def dare_batch(Ad, Bd, Q, R, tol=1e-14):
     """Gains for a stack of (A_d, B_d) pairs in one launch (the per-point gains of the scp controller,
     tpwl/controllers.py:238-246)."""
-    L, P, _ = _doubling(Ad, Bd, Q, R, tol, 100)
+    L, P, _ = _dare_call('sric_dare', Ad, Bd, Q, R, tol, 100)
     return L, P
 
 

@@ -163,3 +163,16 @@ def dare_case(n, m, seed=None):
     A = np.stack([0.9 * orthogonal(n, rng) for _ in range(3)])
     B = rng.standard_normal((3, n, m))
     return A, B, G @ G.T + np.eye(n), 0.5 * (np.eye(m) + 0.1 * np.ones((m, m)))
+
+
+def dare_modes_case(n, m, rho, rank_q, seed):
+    """The doubling DARE tests' problem (tests/test_lqr_gpu.py, tests/test_rompc_gpu.py): a diagonalisable A whose slowest mode
+    sits at |lambda| = rho, randn B, a state cost of rank `rank_q`, R = 1e-2 diag(0.5 .. 2).  Returns A, B, Q, R."""
+    rng = np.random.default_rng(seed)
+    V = rng.standard_normal((n, n))
+    lam = rho * rng.uniform(0.3, 1.0, n)
+    lam[0] = rho
+    A = np.real(V @ np.diag(lam) @ np.linalg.inv(V))
+    B = rng.standard_normal((n, m))
+    Cq = rng.standard_normal((rank_q, n))
+    return A, B, Cq.T @ Cq, np.diag(rng.uniform(0.5, 2.0, m)) * 1e-2

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from helpers import golden_problem, product_tpwl, ilqr_batch_equals_singles
+from lq_cases import dare_modes_case
 
 pytestmark = pytest.mark.gpu
 
@@ -175,17 +176,6 @@ def test_baseline_config_c1_r5_horizon10():
         Po = Q + Kk.T @ R @ Kk + Acl.T @ Po @ Acl
 
 
-def _dare_case(n, m, rho, rank_q, seed):
-    rng = np.random.default_rng(seed)
-    V = rng.standard_normal((n, n))
-    lam = rho * rng.uniform(0.3, 1.0, n)
-    lam[0] = rho                                     # the slowest mode sits at |lambda| = rho
-    A = np.real(V @ np.diag(lam) @ np.linalg.inv(V))
-    B = rng.standard_normal((n, m))
-    Cq = rng.standard_normal((rank_q, n))
-    return A, B, Cq.T @ Cq, np.diag(rng.uniform(0.5, 2.0, m)) * 1e-2
-
-
 @pytest.mark.parametrize('n,m,rho,rank_q', [(8, 2, 0.9, 8), (20, 3, 0.9999, 20), (60, 4, 0.999, 2), (60, 8, 1.02, 6),
                                              (72, 4, 0.99, 3), (33, 16, 0.95, 33)])
 def test_dare_doubling_vs_scipy(n, m, rho, rank_q, monkeypatch):
@@ -194,13 +184,13 @@ def test_dare_doubling_vs_scipy(n, m, rho, rank_q, monkeypatch):
     the forced HBM-slot path at a size that would fit LDS."""
     import scipy.linalg as sl
     from sofacontrol_amd.lqr.lqr import dare, dare_batch
-    A, B, Q, R = _dare_case(n, m, rho, rank_q, 100 * n + m)
+    A, B, Q, R = dare_modes_case(n, m, rho, rank_q, 100 * n + m)
     K, P = dare(A, B, Q, R)
     Ps = sl.solve_discrete_are(A, B, Q, R)
     Ks = -np.linalg.solve(R + B.T @ Ps @ B, B.T @ Ps @ A)
     close(P, Ps, 1e-9); close(K, Ks, 1e-8)
     assert np.abs(np.linalg.eigvals(A + B @ K)).max() < 1.0
-    A2, B2, _, _ = _dare_case(n, m, min(rho, 0.97), rank_q, 7 * n + m)
+    A2, B2, _, _ = dare_modes_case(n, m, min(rho, 0.97), rank_q, 7 * n + m)
     Kb, Pb = dare_batch(np.stack([A, A2]), np.stack([B, B2]), Q, R)
     np.testing.assert_array_equal(Pb[0], P)
     close(Pb[1], sl.solve_discrete_are(A2, B2, Q, R), 1e-9)
@@ -215,3 +205,35 @@ def test_dare_reports_failure():
     A = np.diag([1.5, 0.5]); B = np.array([[0.0], [1.0]])        # the unstable mode is not controllable
     with pytest.raises(Exception):
         dare(A, B, np.eye(2), np.eye(1))
+
+
+@pytest.mark.parametrize('n,m,rho,rank_q', [(1, 1, 0.9, 1), (2, 2, 1.02, 1), (9, 3, 0.9999, 2), (17, 16, 0.95, 17)])
+def test_dare_narrow_and_wide_share_the_loop(n, m, rho, rank_q, monkeypatch):
+    """sric_dare and sric_dare_wide run one doubling loop (csrc/dare_sda.h) around their own factor of R, m x n solve and gain
+    phase: the wide kernel's pieces at small n_u, where its loops run empty, on the narrow kernel's inputs, with the slots in
+    LDS and forced into HBM, each against scipy.  The first two cases take no row swap in the elimination, the last two 30 and
+    91 (a numpy statement of the doubling with the kernels' pivot rule, which is 1e-16 .. 2e-13 from scipy in P and at most
+    1.3e-12 in K on these cases).  The iteration counts are printed, not compared: the two kernels round G0 differently."""
+    import scipy.linalg as sl
+    from sofacontrol_amd.lqr.lqr import dare, dare_wide, _dare_call
+    A, B, Q, R = dare_modes_case(n, m, rho, rank_q, 100 * n + m)
+    Ps = sl.solve_discrete_are(A, B, Q, R)
+    Ks = -np.linalg.solve(R + B.T @ Ps @ B, B.T @ Ps @ A)
+    for slots in ('lds', 'hbm'):
+        if slots == 'hbm':
+            monkeypatch.setenv('SRH_DARE_HBM_SLOTS', '1')
+        for name, solve in (('dare', dare), ('dare_wide', dare_wide)):
+            K, P = solve(A, B, Q, R)
+            print('%s (%d, %d) %s slots: P err %.3e of %.3e, K err %.3e of %.3e' % (name, n, m, slots, np.abs(P - Ps).max(), np.abs(Ps).max(),
+                                                                                   np.abs(K - Ks).max(), np.abs(Ks).max()))
+            assert K.shape == (m, n) and P.shape == (n, n)
+            close(P, Ps, 1e-9); close(K, Ks, 1e-8)
+            assert np.abs(np.linalg.eigvals(A + B @ K)).max() < 1.0
+    monkeypatch.delenv('SRH_DARE_HBM_SLOTS')
+    print('doubling steps (%d, %d): sric_dare %d, sric_dare_wide %d' % (
+        n, m, _dare_call('sric_dare', A, B, Q, R, 1e-14, 100)[2][0], _dare_call('sric_dare_wide', A, B, Q, R, 1e-14, 100)[2][0]))
+    if (n, m) == (9, 3):
+        A2, B2, _, _ = dare_modes_case(n, m, 0.97, rank_q, 7 * n + m)
+        K, P = dare_wide(A, B, Q, R)
+        Kb, Pb = dare_wide(np.stack([A, A2]), np.stack([B, B2]), Q, R)
+        np.testing.assert_array_equal(Pb[0], P); np.testing.assert_array_equal(Kb[0], K)

@@ -7,6 +7,8 @@ import contextlib
 import numpy as np
 import pytest
 
+from lq_cases import dare_modes_case
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,24 +28,12 @@ def g(golden):
 
 
 # ------------------------------------------------------------------------------------------------ dare_wide
-def _dare_case(n, m, rho, rank_q, seed):
-    """The generator of tests/test_lqr_gpu.py."""
-    rng = np.random.default_rng(seed)
-    V = rng.standard_normal((n, n))
-    lam = rho * rng.uniform(0.3, 1.0, n)
-    lam[0] = rho                                     # the slowest mode sits at |lambda| = rho
-    A = np.real(V @ np.diag(lam) @ np.linalg.inv(V))
-    B = rng.standard_normal((n, m))
-    Cq = rng.standard_normal((rank_q, n))
-    return A, B, Cq.T @ Cq, np.diag(rng.uniform(0.5, 2.0, m)) * 1e-2
-
-
 @pytest.mark.parametrize('n,m,rho,rank_q', [(8, 30, 0.98, 2), (12, 17, 0.9, 12), (20, 64, 0.9999, 20), (60, 30, 0.999, 2),
                                              (72, 30, 0.99, 3), (33, 48, 1.02, 6), (80, 64, 0.95, 5)])
 def test_dare_wide_vs_scipy(n, m, rho, rank_q):
     import scipy.linalg as sl
     from sofacontrol_amd.lqr.lqr import dare_wide
-    A, B, Q, R = _dare_case(n, m, rho, rank_q, 100 * n + m)
+    A, B, Q, R = dare_modes_case(n, m, rho, rank_q, 100 * n + m)
     K, P = dare_wide(A, B, Q, R)
     Ps = sl.solve_discrete_are(A, B, Q, R)
     Ks = -np.linalg.solve(R + B.T @ Ps @ B, B.T @ Ps @ A)
@@ -56,8 +46,8 @@ def test_dare_wide_vs_scipy(n, m, rho, rank_q):
 def test_dare_wide_batched_and_failures():
     import scipy.linalg as sl
     from sofacontrol_amd.lqr.lqr import dare, dare_wide
-    A, B, Q, R = _dare_case(12, 17, 0.9, 12, 1217)
-    A2, B2, _, _ = _dare_case(12, 17, 0.8, 12, 7 * 12 + 17)
+    A, B, Q, R = dare_modes_case(12, 17, 0.9, 12, 1217)
+    A2, B2, _, _ = dare_modes_case(12, 17, 0.8, 12, 7 * 12 + 17)
     K, P = dare_wide(A, B, Q, R)
     Kb, Pb = dare_wide(np.stack([A, A2]), np.stack([B, B2]), Q, R)
     assert Kb.shape == (2, 17, 12) and Pb.shape == (2, 12, 12)
