@@ -198,6 +198,12 @@ int stpwl_rollout(stpwl_t *h, const double *x0, const double *U, int N, int64_t 
  * receding-horizon solve (scp/ros.py:78-79) without leaving the device */
 int stpwl_rollout_dev(stpwl_t *h, const double *x0_dev, const double *U_dev, int N, int64_t batch,
                       double *X_dev, double *Z_dev, void *stream);
+/* The kernel a rollout of N stages and `batch` rollouts of this handle launches (a host function).  staged: 1 the region's panel
+ * [A_d^T | B_d^T | d_d] stays in LDS and is reloaded when the nearest point changes, 0 the plain kernel that reads it from L2 at every
+ * stage (layouts above 64 KB of LDS, n_x > 82 at n_u = 4; or a handle created under SRH_TPWL_ROLLOUT_PLAIN=1).  held: 1 the point
+ * table sits in registers of one wave (staged, w_v = 0, P <= 64, r <= 32), 0 the general nearest-point search.  lds_bytes: the dynamic
+ * LDS of the launch.  Both kernels give the same X and Z bit for bit.  Any output may be NULL. */
+int stpwl_rollout_plan(stpwl_t *h, int N, int64_t batch, int *staged, int *held, size_t *lds_bytes);
 /* TPWLGuSTO.get_characteristic_vals (scp/models/tpwl.py:66-84): x_char, f_char (n_x,) */
 int stpwl_characteristic(stpwl_t *h, double *x_char, double *f_char);
 

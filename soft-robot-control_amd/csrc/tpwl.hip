@@ -148,6 +148,127 @@ __global__ __launch_bounds__(256) void rollout_kernel(TpwlDev T, const double *_
     }
 }
 
+// The same rollout with the region's panel [A_d^T | B_d^T | d_d] in LDS, reloaded (coalesced 16-byte loads) only when the nearest point
+// changes, and both products of a stage under one barrier.  rollout_kernel reads the panel (31 KB at n_x = 60) from L2 at every stage
+// and runs wg::matTvec twice: four barriers and two L2-fed products per stage.  The sums are those of the two wg::matTvec calls, in
+// their order: with S = blockDim / n slices, slice s accumulates the rows s, s + S, ... by fma from 0.0; x' = d + p[0] + ... + p[S-1],
+// then the input product's partials are added to x' the same way.  X and Z are bit-identical to rollout_kernel's.
+// HELD (w_v = 0, P <= 64, r <= 32, hence n <= 64: wave 0 owns the whole state): lane i of wave 0 keeps ITS table point in registers for
+// the rollout and lane c < r the coordinate x[r + c] of the state the wave has just summed; the coordinates are broadcast with v_readlane as in
+// tpwl::nearest_many -- same sums in the order j = 0, 1, ..., same sqrt, first minimum, index 0 for a state that is not a number --
+// and the barrier between a stage's sums and the next search is not needed.  Otherwise wave 0 calls tpwl::nearest_wave on the LDS state.
+typedef double tpwl_d2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ void stage_copy16(lptr dst, cgptr src, int count) {            // count even, both 16-byte aligned
+    auto d2 = (__attribute__((address_space(3))) tpwl_d2 *)dst;
+    auto s2 = (const __attribute__((address_space(1))) tpwl_d2 *)src;
+    for (int e = threadIdx.x; e < (count >> 1); e += blockDim.x) d2[e] = s2[e];
+}
+
+template <bool HELD>
+__global__ __launch_bounds__(256) void rollout_staged_kernel(TpwlDev T, const double *__restrict__ x0,
+                                                             const double *__restrict__ U, int N,
+                                                             double *__restrict__ X, double *__restrict__ Z) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int n = T.n, m = T.m, r = T.r;
+    lptr xc = (lptr)smem;                                // n
+    lptr uc = xc + n;                                    // m
+    lptr pa = uc + ((m + 3) & ~3);                       // blockDim: partial sums of A x
+    lptr pb = pa + blockDim.x;                           // blockDim: partial sums of B u
+    liptr ip = (liptr)(pb + blockDim.x);                 // (two doubles)
+    lptr At = pb + blockDim.x + 2;                       // n x n   the panel of region `cur`: every offset is even (n = 2 r)
+    lptr Bt = At + n * n;                                // m x n
+    lptr dl = Bt + m * n;                                // n
+    const int64_t b = blockIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int S = max(1, (int)blockDim.x / n), j = threadIdx.x % n, s = threadIdx.x / n;          // wg::matTvec's slices
+    double *Xb = X + b * (size_t)(N + 1) * n;
+    for (int e = threadIdx.x; e < n; e += blockDim.x) { xc[e] = x0[b * n + e]; Xb[e] = xc[e]; }
+    // tq[c]: coordinate c of the lane's point, 0.0 for c >= r; xq: coordinate r + lane of the state (its position part), 0.0 for lane >= r.
+    // A term c >= r of the search is then fma(0.0, 0.0, sq) = sq exactly, so the sums run in blocks of eight without a test per term.
+    double tq[32], xq = 0.0;
+    if constexpr (HELD) {
+        if (wave == 0) {
+            const int pl = lane < T.P ? lane : T.P - 1;
+#pragma unroll
+            for (int c = 0; c < 32; ++c) {
+                const double t = T.qT[(c < r ? c : r - 1) * T.P + pl];                     // unconditional (clamped) loads: all in flight at once
+                tq[c] = c < r ? t : 0.0;
+            }
+            if (lane < r) xq = x0[b * n + r + lane];
+        }
+    }
+    __syncthreads();
+    int cur = -1;
+    for (int k = 0; k < N; ++k) {
+        if (wave == 0) {
+            int i;
+            if constexpr (HELD) {
+                double sq = 0.0;
+#pragma unroll
+                for (int c0 = 0; c0 < 32; c0 += 8) {
+                    if (c0 < r) {
+#pragma unroll
+                        for (int c = c0; c < c0 + 8; ++c) {
+                            const int lo = __builtin_amdgcn_readlane(__double2loint(xq), c), hi = __builtin_amdgcn_readlane(__double2hiint(xq), c);
+                            const double e = tq[c] - __hiloint2double(hi, lo);
+                            sq = fma(e, e, sq);
+                        }
+                    }
+                }
+                const double dist = lane < T.P ? T.w_q * sqrt(sq) : INFINITY;
+                const double dmin = wg::wave_min(dist);
+                const int imin = (int)wg::wave_min(dist == dmin ? (double)lane : 1e9);        // first minimum (np.argmin)
+                i = imin < T.P ? imin : 0;                                                    // (a state that is not a number: no minimum)
+            } else {
+                i = tpwl::nearest_wave(T, xc);
+            }
+            if (lane == 0) *ip = i;
+        } else if (wave == 1) {
+            if (lane < m) uc[lane] = U[(b * N + k) * m + lane];                               // (m <= 16)
+        }
+        __syncthreads();
+        const int i = *ip;
+        if (i != cur) {                                  // (the same for every thread)
+            stage_copy16(At, T.AdT + (size_t)i * n * n, n * n);
+            stage_copy16(Bt, T.BdT + (size_t)i * m * n, m * n);
+            stage_copy16(dl, T.dd + (size_t)i * n, n);
+            cur = i;
+            __syncthreads();
+        }
+        if (s < S) {
+            double a = 0.0, c = 0.0;
+#pragma unroll 4
+            for (int q = s; q < n; q += S) a = fma(At[q * n + j], xc[q], a);
+            for (int q = s; q < m; q += S) c = fma(Bt[q * n + j], uc[q], c);
+            pa[s * n + j] = a;
+            pb[s * n + j] = c;
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < n) {
+            double v = dl[threadIdx.x];
+            for (int q = 0; q < S; ++q) v += pa[q * n + threadIdx.x];
+            for (int q = 0; q < S; ++q) v += pb[q * n + threadIdx.x];
+            xc[threadIdx.x] = v;
+            Xb[(size_t)(k + 1) * n + threadIdx.x] = v;
+        }
+        if constexpr (HELD) {
+            if (wave == 0) xq = lane < r ? xc[r + lane] : 0.0;                                // (written just above by this wave: LDS keeps a wave's order)
+        }
+        if constexpr (!HELD) __syncthreads();            // (HELD: only wave 0 touches the state before the next barrier)
+    }
+    if constexpr (HELD) __syncthreads();
+    if (Z != nullptr && T.H != nullptr) {
+        double *Zb = Z + b * (size_t)(N + 1) * T.nz;
+        for (int e = threadIdx.x; e < (N + 1) * T.nz; e += blockDim.x) {
+            const int k = e / T.nz, a = e % T.nz;
+            double sum = 0.0;
+            for (int c = 0; c < n; ++c) sum = fma(T.H[a * n + c], Xb[(size_t)k * n + c], sum);
+            Zb[e] = sum + T.z_ref[a];
+        }
+    }
+}
+
 // f_i = A_c[j] x_i + B_c[j] u_i + d_c[j] at the stored points, j = nearest(x_i)  (models/tpwl.py:77-82)
 __global__ __launch_bounds__(64) void char_kernel(TpwlDev T, double *__restrict__ xabs, double *__restrict__ fabs_) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -180,6 +301,31 @@ std::vector<double> transpose_batch(const double *src, int P, int rows, int cols
             for (int j = 0; j < cols; ++j)
                 out[((size_t)p * cols + j) * rows + i] = src[((size_t)p * rows + i) * cols + j];
     return out;
+}
+
+// Which kernel a rollout of the handle launches, and its dynamic LDS.  staged: the region panel in LDS (rollout_staged_kernel) when the
+// layout fits the 64 KB a launch may ask for without an attribute (n_x <= 82 at n_u = 4) and the handle was not created under
+// SRH_TPWL_ROLLOUT_PLAIN=1; held: the point table in registers (the limits of tpwl::nearest_many).
+struct RolloutPlan { bool staged, held; size_t lds; };
+
+RolloutPlan rollout_plan(const stpwl *h) {
+    const size_t n = h->n, m = h->m, vec = 2 * n + ((m + 3) & ~(size_t)3) + 256;              // state(s), input, one partial buffer
+    const size_t plain = sizeof(double) * vec + 16;
+    const size_t staged = srh::lds_request(sizeof(double) * (vec + 256 + 2 + n * n + m * n));   // + second partial buffer, index, panel (d_d in the second state's place)
+    RolloutPlan p;
+    p.staged = !h->rollout_plain && staged <= (size_t)64 * 1024;
+    p.held = p.staged && h->w_v == 0.0 && h->P <= 64 && h->r <= 32;
+    p.lds = p.staged ? staged : plain;
+    return p;
+}
+
+int rollout_launch(const stpwl *h, const double *x0, const double *U, int N, int64_t batch, double *X, double *Z, hipStream_t stream) {
+    const RolloutPlan p = rollout_plan(h);
+    if (!p.staged) rollout_kernel<<<(unsigned)batch, 256, p.lds, stream>>>(h->view(), x0, U, N, X, Z);
+    else if (p.held) rollout_staged_kernel<true><<<(unsigned)batch, 256, p.lds, stream>>>(h->view(), x0, U, N, X, Z);
+    else rollout_staged_kernel<false><<<(unsigned)batch, 256, p.lds, stream>>>(h->view(), x0, U, N, X, Z);
+    SRH_CHECK_HIP(hipGetLastError());
+    return SRH_OK;
 }
 
 }  // namespace
@@ -226,6 +372,7 @@ int stpwl_create(stpwl_t **out, int P, int r, int n_u, const double *q, const do
     stpwl *h = new stpwl();
     h->P = P; h->r = r; h->n = 2 * r; h->m = n_u; h->nz = 0;
     h->w_q = w_q; h->w_v = w_v;
+    if (const char *e = getenv("SRH_TPWL_ROLLOUT_PLAIN")) h->rollout_plain = atoi(e) != 0;        // (once per handle: nothing is read per launch)
     const int n = h->n, m = h->m;
     auto qT = transpose_batch(q, 1, P, r);
     auto vT = transpose_batch(v, 1, P, r);
@@ -358,10 +505,7 @@ int stpwl_rollout(stpwl_t *h, const double *x0, const double *U, int N, int64_t 
         (rc = dX.alloc(sizeof(double) * batch * (N + 1) * n)))
         return rc;
     if (Z && (rc = dZ.alloc(sizeof(double) * batch * (N + 1) * h->nz))) return rc;
-    size_t lds = sizeof(double) * (2 * n + ((m + 3) & ~3) + 256) + 16;
-    rollout_kernel<<<(unsigned)batch, 256, lds>>>(h->view(), d0.as<double>(), dU.as<double>(), N, dX.as<double>(),
-                                                 Z ? dZ.as<double>() : nullptr);
-    SRH_CHECK_HIP(hipGetLastError());
+    if ((rc = rollout_launch(h, d0.as<double>(), dU.as<double>(), N, batch, dX.as<double>(), Z ? dZ.as<double>() : nullptr, nullptr))) return rc;
     SRH_CHECK_HIP(hipStreamSynchronize(nullptr));
     if ((rc = dX.download(X, sizeof(double) * batch * (N + 1) * n))) return rc;
     if (Z) return dZ.download(Z, sizeof(double) * batch * (N + 1) * h->nz);
@@ -375,9 +519,16 @@ int stpwl_rollout_dev(stpwl_t *h, const double *x0_dev, const double *U_dev, int
     SRH_REQUIRE(N >= 0 && batch >= 0, "stpwl_rollout_dev: negative size");
     SRH_REQUIRE(Z_dev == nullptr || h->nz > 0, "stpwl_rollout_dev: Need to set output or meas. model");
     if (batch == 0) return SRH_OK;
-    const size_t lds = sizeof(double) * (2 * h->n + ((h->m + 3) & ~3) + 256) + 16;
-    rollout_kernel<<<(unsigned)batch, 256, lds, (hipStream_t)stream>>>(h->view(), x0_dev, U_dev, N, X_dev, Z_dev);
-    SRH_CHECK_HIP(hipGetLastError());
+    return rollout_launch(h, x0_dev, U_dev, N, batch, X_dev, Z_dev, (hipStream_t)stream);
+}
+
+int stpwl_rollout_plan(stpwl_t *h, int N, int64_t batch, int *staged, int *held, size_t *lds_bytes) {
+    SRH_REQUIRE(h, "stpwl_rollout_plan: null handle");
+    SRH_REQUIRE(N >= 0 && batch >= 0, "stpwl_rollout_plan: negative size");
+    const RolloutPlan p = rollout_plan(h);           // (the same for every horizon and batch: one workgroup per rollout)
+    if (staged) *staged = p.staged ? 1 : 0;
+    if (held) *held = p.held ? 1 : 0;
+    if (lds_bytes) *lds_bytes = p.lds;
     return SRH_OK;
 }
 

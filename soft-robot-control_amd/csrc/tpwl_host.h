@@ -9,5 +9,6 @@ struct stpwl {
     bool has_discrete = false;
     srh::DevBuf qT, vT, u, Ac, Bc, dc, AcT, BcT, Ad, Bd, dd, AdT, BdT, H, z_ref;
     std::vector<double> H_host, zref_host;
+    bool rollout_plain = false;          // SRH_TPWL_ROLLOUT_PLAIN=1 when the handle was created: rollouts keep the L2-fed kernel (tpwl.hip)
     TpwlDev view() const;
 };

@@ -188,6 +188,15 @@ def ekf_handle_plan(h):
     return _ekf_plan_dict(path, lds, gain)
 
 
+def tpwl_rollout_plan(h, N, batch):
+    """stpwl_rollout_plan: the kernel a rollout of the TPWL handle h launches (csrc/tpwl.hip), on the host.  {'staged': region panel in
+    LDS | plain kernel, 'held': point table in registers | general nearest-point search, 'lds_bytes'}.  A handle created under
+    SRH_TPWL_ROLLOUT_PLAIN=1 stays plain."""
+    staged, held, lds = C.c_int(0), C.c_int(0), C.c_size_t(0)
+    check(lib().stpwl_rollout_plan(h, C.c_int(N), C.c_int64(batch), C.byref(staged), C.byref(held), C.byref(lds)), 'stpwl_rollout_plan')
+    return {'staged': bool(staged.value), 'held': bool(held.value), 'lds_bytes': int(lds.value)}
+
+
 IPM_PHASES = ('init', 'cold', 'warm', 'pred', 'corr', 'direction', 'affine', 'advance', 'scales', 'verdict')
 
 
