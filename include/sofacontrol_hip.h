@@ -262,7 +262,9 @@ typedef struct sssm sssm_t;
 int sssm_num_monomials(int dim, int order);
 int sssm_exponents(int dim, int order, int32_t *exps);            /* (n_mon x dim) exponent table */
 /* SSM.__init__ (ssm.py:24-71): r_coeff (n_x x n_rom), B (n_x x n_u), rd_coeff / Bd or NULL, w_coeff
- * (n_o x n_ssm), v_coeff (n_x x n_ssm), z_ref (n_o); n_rom / n_ssm = sssm_num_monomials(n_x / n_o, order) */
+ * (n_o x n_ssm), v_coeff (n_x x n_ssm), z_ref (n_o); n_rom / n_ssm = sssm_num_monomials(n_x / n_o, order).
+ * Limits (SRH_EINVAL): 0 < n_x <= 32; 0 < n_u <= n_x | 1 (n_x + 1 for even n_x, n_x for odd: the discretisation scratch);
+ * 0 < rom_order, ssm_order <= 7 (the kernels keep order + 1 level offsets in eight slots); the bases must fit the 160 KB LDS. */
 int sssm_create(sssm_t **out, int n_x, int n_u, int n_o, int rom_order, int ssm_order,
                 const double *r_coeff, const double *B, const double *rd_coeff, const double *Bd,
                 const double *w_coeff, const double *v_coeff, const double *z_ref);
@@ -270,7 +272,12 @@ int sssm_destroy(sssm_t *h);
 /* bookkeeping performance matrix H (n_o x n_x) used by iLQR cost Hessians (ssm.py:69-70; zeros by default) */
 int sssm_set_output(sssm_t *h, const double *H);
 /* SSMDynamics.get_jacobians / get_continuous_jacobians / get_discrete_jacobians (ssm.py:198-218) for B
- * points: X (B x n_x), U (B x n_u) -> A (B x n_x x n_x), Bm (B x n_x x n_u), d (B x n_x) */
+ * points: X (B x n_x), U (B x n_u) -> A (B x n_x x n_x), Bm (B x n_x x n_u), d (B x n_x).
+ * SSSM_BE and SSSM_BIL form sep = inv(A_c) (A_d - I) (ssm.py:279-301; np.linalg.inv raises on a singular A_c): the downloaded results
+ * are scanned on the host, and a non-finite value returns SRH_ENUMERIC with "singular" and the index of the first such problem in
+ * the message (the outputs have been written; the other problems' entries are valid).  sssm_rollout scans X the same way.  The
+ * device-resident paths -- silqr_solve_ssm and the GuSTO-SSM plan -- run the same discretisation inside their kernels and are NOT
+ * covered by this check. */
 int sssm_linearize(sssm_t *h, const double *X, const double *U, int64_t B, int mode, double dt,
                    double *A, double *Bm, double *d);
 /* reduced_dynamics / reduced_dynamics_discrete (ssm.py:167-178): F (B x n_x) */

@@ -5,6 +5,7 @@
 #include "ssm_host.h"
 
 #include <algorithm>
+#include <cmath>
 #include <functional>
 #include <map>
 
@@ -232,7 +233,11 @@ int sssm_create(sssm_t **out, int n_x, int n_u, int n_o, int rom_order, int ssm_
     SRH_REQUIRE(out && r_coeff && B && w_coeff && v_coeff && z_ref, "sssm_create: null argument");
     SRH_REQUIRE(n_x > 0 && n_x <= 32 && n_u > 0 && n_u <= n_x + 16 && n_o > 0 && rom_order > 0 && ssm_order > 0,
                 "sssm_create: need 0 < n_x <= 32, n_u > 0, n_o > 0, orders > 0");
-    SRH_REQUIRE(n_u <= (n_x | 1), "sssm_create: n_u > n_x is not supported by the discretisation scratch");
+    // SsmLds::lvr / lvs (ssm_dev.h) hold order + 1 level offsets in eight slots
+    SRH_REQUIRE(rom_order <= SSM_MAX_ORDER && ssm_order <= SSM_MAX_ORDER,
+                "sssm_create: rom_order and ssm_order must be <= %d (got %d, %d)", SSM_MAX_ORDER, rom_order, ssm_order);
+    // B_d = sep B goes through an n_x x (n_x | 1) scratch panel (ssm::discretize)
+    SRH_REQUIRE(n_u <= (n_x | 1), "sssm_create: need n_u <= n_x | 1 (= %d) for the discretisation scratch, got n_u = %d", n_x | 1, n_u);
     auto *h = new sssm();
     h->n = n_x; h->m = n_u; h->no = n_o;
     auto er = ssm_exponents(n_x, rom_order), es = ssm_exponents(n_o, ssm_order);
@@ -285,6 +290,14 @@ int sssm_set_output(sssm_t *h, const double *H) {
     return h->H.upload(H, sizeof(double) * h->no * h->n);
 }
 
+// index of the first problem (rows of `per` doubles) with a non-finite entry, or -1
+static int64_t first_non_finite(const double *v, int64_t problems, size_t per) {
+    for (int64_t b = 0; b < problems; ++b)
+        for (size_t e = 0; e < per; ++e)
+            if (!std::isfinite(v[(size_t)b * per + e])) return b;
+    return -1;
+}
+
 static int check_mode(const sssm *h, int mode) {
     SRH_REQUIRE(mode >= SSM_CONT && mode <= SSM_DISCRETE_MAP, "self.discr_method must be in [fe, be, bil, zoh]");
     SRH_REQUIRE(mode != SSM_DISCRETE_MAP || h->has_discrete, "sssm: model has no discrete map (rd_coeff, Bd)");
@@ -310,6 +323,17 @@ int sssm_linearize(sssm_t *h, const double *X, const double *U, int64_t B, int m
     if ((rc = dA.download(A, sizeof(double) * B * n * n)) || (rc = dB.download(Bm, sizeof(double) * B * n * m)) ||
         (rc = dd.download(d, sizeof(double) * B * n)))
         return rc;
+    if (mode == SSM_BE || mode == SSM_BIL) {
+        // sep = inv(A_c) (A_d - I): a zero pivot of A_c (or of I - h A_c) divides through in the kernel (np.linalg.inv raises)
+        int64_t bad = -1;
+        for (int64_t b : {first_non_finite(A, B, n * n), first_non_finite(Bm, B, n * m), first_non_finite(d, B, n)})
+            if (b >= 0 && (bad < 0 || b < bad)) bad = b;
+        if (bad >= 0) {
+            srh::set_error("sssm_linearize: singular continuous Jacobian A_c or I - h A_c (non-finite A_d, B_d or d_d) at problem %lld",
+                           (long long)bad);
+            return SRH_ENUMERIC;
+        }
+    }
     return SRH_OK;
 }
 
@@ -381,6 +405,12 @@ int sssm_rollout(sssm_t *h, const double *x0, const double *U, int N, int64_t ba
     SRH_CHECK_HIP(hipStreamSynchronize(nullptr));
     if ((rc = dX.download(X, sizeof(double) * batch * (N + 1) * n))) return rc;
     if (Z && (rc = dZ.download(Z, sizeof(double) * batch * (N + 1) * no))) return rc;
+    const int64_t bad = first_non_finite(X, batch, (size_t)(N + 1) * n);
+    if (bad >= 0) {
+        srh::set_error("sssm_rollout: non-finite state (singular continuous Jacobian A_c or I - h A_c in modes be / bil) at problem %lld",
+                       (long long)bad);
+        return SRH_ENUMERIC;
+    }
     return SRH_OK;
 }
 

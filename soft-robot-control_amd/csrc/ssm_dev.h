@@ -22,6 +22,9 @@ struct SsmDev {
     cgptr H;                   // bookkeeping performance matrix (no x n) (zeros unless the user sets it)
 };
 
+// highest polynomial order of either basis: the staged form (SsmLds) keeps the order + 1 level offsets in fixed arrays
+constexpr int SSM_MAX_ORDER = 7;
+
 // discretisation modes of sssm_linearize / rollout (ssm.py:279-301 and the `discrete` flag 212-218)
 enum { SSM_CONT = 0, SSM_FE = 1, SSM_BE = 2, SSM_BIL = 3, SSM_DISCRETE_MAP = 4 };
 
@@ -382,7 +385,7 @@ struct SsmLds {
     lptr Bg;                   // (n x m) input matrix of the map in use
     liptr er, dmr, pr, vr;     // rom basis tables: exponents (nr x n), derivative monomial (nr x n), parent, variable (nr)
     liptr es, dms, ps, vs;     // ssm basis tables
-    int lvr[8], lvs[8];        // first monomial of every degree (order <= 6)
+    int lvr[SSM_MAX_ORDER + 1], lvs[SSM_MAX_ORDER + 1];        // first monomial of every degree: order + 1 offsets (sssm_create refuses order > SSM_MAX_ORDER)
     // compact derivative lists of the rom basis (jacobians_l): column j of D = d phi / d x has a structural non-zero only where
     // x_j divides the monomial (cubic basis in 10 variables: 66 of 285).  List (j, g), g = k mod 4, holds those monomials k in
     // increasing order, jcap slots each (padded): jk = k, jq = index of the monomial e_k - 1_j (-2: the constant 1, -1: padding),
@@ -426,7 +429,7 @@ __device__ inline void stage(SsmLds &T, lptr base, const SsmDev &S, bool discret
     for (int e = tid; e < nr; e += nt) { T.pr[e] = S.pr[e]; T.vr[e] = S.vr[e]; }
     for (int e = tid; e < ns * no; e += nt) { T.es[e] = S.es[e]; T.dms[e] = S.dms[e]; }
     for (int e = tid; e < ns; e += nt) { T.ps[e] = S.ps[e]; T.vs[e] = S.vs[e]; }
-    for (int q = 0; q < 8; ++q) { T.lvr[q] = q <= S.order_r ? S.lvr[q] : 0; T.lvs[q] = q <= S.order_s ? S.lvs[q] : 0; }
+    for (int q = 0; q <= SSM_MAX_ORDER; ++q) { T.lvr[q] = q <= S.order_r ? S.lvr[q] : 0; T.lvs[q] = q <= S.order_s ? S.lvs[q] : 0; }
     __syncthreads();
     if (jcap > 0) {                                              // one thread per list (j, g): scan its monomials in increasing order
         for (int l = tid; l < 4 * n; l += nt) {
