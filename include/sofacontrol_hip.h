@@ -509,12 +509,22 @@ int sgusto_plan_warm_across_active(const sgusto_plan_t *plan, int *active);
  * [x ; zeta] (n_x = n + n_o, H = [0 I], x_scale = 0 on zeta) when the model's output map is nonlinear, else the plain QP with the
  * constant H; `mode`: discretisation as sssm_linearize; Hm (n_z x n): model.H of zopt = H xopt (gusto.py:486); XA / Xb (nX x n): the state
  * polyhedron as GuSTO.state_constraints_violated applies it to the states (gusto.py:185-201), or NULL.  Arrays as sgusto_solve with
- * n_x = the model's n.  status: 0 ok, 1 a QP could not be solved, 2 omega > omega_max, 3 max iterations. */
+ * n_x = the model's n.  status: 0 ok, 1 a QP could not be solved, 2 omega > omega_max, 3 max iterations.
+ * Input-rate rows (prob->ndU > 0: dUA (ndU x n_u), dUb; dU.A (u_{k+1} - u_k) <= dU.b, k = 0..N-2, locp.py:305-308) are taken where the
+ * one-wave QP in the space of the inputs has room for them (sgusto_ssm_rate_rows_fit; not under SRH_GUSTO_SSM_NO_DENSE), refused
+ * otherwise.  With them a rollout whose QP needs its trust-region rows -- the relaxed minimiser leaves the trust region, or the step
+ * before it ended on its boundary and was rejected -- ends with status -78 (SSM_NEEDS_HOST), xopt / uopt = the initial trajectory:
+ * the caller solves that rollout again by other means (GuSTO: the host loop); no rate row is ever dropped. */
 typedef struct sgusto_ssm_plan sgusto_ssm_plan_t;
 int sgusto_ssm_plan_create(sgusto_ssm_plan_t **plan, sssm_t *model, const slocp_problem *prob, const sgusto_params *par, double dt,
                            int mode, int64_t batch, const double *f_char, const double *Hm, int nX, const double *XA, const double *Xb,
                            int max_trace);
 int sgusto_ssm_plan_destroy(sgusto_ssm_plan_t *plan);
+/* Host arithmetic only (no GPU): *fits = 1 when a plan whose QP has these dimensions (n_x: the QP's state, the augmented one when the
+ * outputs are carried) takes ndU rate rows -- N n_u <= 16, N (nU + nX) + (N - 1) ndU <= 64 rows, no terminal rows, a small model:
+ * the rule of the dense one-wave QP (csrc/locp_dense_u.h: qdu::limit), which sgusto_ssm_plan_create applies.  ndU = 0: whether
+ * that QP runs at all. */
+int sgusto_ssm_rate_rows_fit(int N, int n_x, int n_u, int n_z, int nU, int nX, int nXf, int ndU, int *fits);
 int sgusto_ssm_plan_set_max_iters(sgusto_ssm_plan_t *plan, int max_gusto_iters);
 int sgusto_ssm_plan_set_warm_across(sgusto_ssm_plan_t *plan, int on);   /* as sgusto_plan_set_warm_across (locp.py:181) */
 /* as sgusto_plan_warm_across_active: *active = 1 when warm_across was requested and the plan's shape runs the lean one-wave interior point

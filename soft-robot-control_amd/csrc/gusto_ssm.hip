@@ -17,6 +17,9 @@
 //   tests       trust region, model accuracy (continuous Jacobians at the old and at the new point, gusto.py:203-223), state rows,
 //               convergence, acceptance -- gusto.py:371-473 with the same rules and order as gusto_kernel.
 // The linearisation scratch and the QP's layouts share the workgroup's LDS (they never live at the same time).
+// Input-rate rows dU.A (u_{k+1} - u_k) <= dU.b (locp.py:305-308) are rows of the one-wave QP in the space of the inputs (locp_dense_u.h) and of
+// nothing else: qp::solve, which takes over when the trust region binds, does not know them.  A plan with rate rows therefore never runs
+// qp::solve -- such a rollout ends with status SSM_NEEDS_HOST and its initial trajectory, and the caller solves it again (GuSTO: the host loop).
 #include "scp_types.h"
 #include "ssm_host.h"
 #include "locp_dense_u.h"
@@ -40,6 +43,8 @@ struct SsmGustoBatch {
     int mode;                           // discretisation of the model (SSM_FE ... SSM_DISCRETE_MAP)
     double *Jopt;
     int host_args;                      // the arguments sit in pinned host memory (zero-copy solve): copies in the work block
+    int ndU;                            // rows of the rate polyhedron (0: none), dUA (ndU x n_u), dUb (ndU): constant per plan, rows of qdu::solve only
+    const double *dUA, *dUb;
 };
 
 // offsets (doubles) of the SCP loop's arrays behind the QP's own work arrays
@@ -429,8 +434,9 @@ __global__ __launch_bounds__(SSM_THREADS) void gusto_ssm_kernel(QPDims d, QPCons
     gptr lamd = base + gw.lamd;
     double qdbg[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};              // phase clocks of the last dense one-wave QP (SRH_GUSTO_TRACE_QIT=1: trace row 1)
     GustoState s = gusto_start(par);
-    bool tr_hot = false;
+    bool tr_hot = false, needs_host = false;
     int status = 0;
+    const qdu::Rate rate{b.ndU, b.dUA, b.dUb};
     while (gusto_running(par, s)) {
         tid = SRH_TID;
         QPData q{(cgptr)x0a, (cgptr)xka, zp, (cgptr)nullptr, udp, s.delta, s.omega, (gptr)nullptr};
@@ -443,11 +449,14 @@ __global__ __launch_bounds__(SSM_THREADS) void gusto_ssm_kernel(QPDims d, QPCons
             // N n_u <= 16: the QP without its trust-region rows in the space of the inputs on one wave, whatever the cost's rank (locp_dense_u.h)
             for (int attempt = 0; attempt < 2; ++attempt) {
                 const bool warm = have_warm && attempt == 0;
-                st = qdu::solve(d, c, dyn, q, w, (lptr)smem, lamd, &J, &qit, warm ? 1 : 0, qdbg);
+                st = qdu::solve(d, c, rate, dyn, q, w, (lptr)smem, lamd, &J, &qit, warm ? 1 : 0, qdbg);
                 if (st == 0 || st == 100 || !warm) break;
             }
             have_warm = st == 0;
         }
+        // rate rows (the plan runs the dense one-wave QP then): the relaxed minimiser leaves the trust region (100), the step before this
+        // one ended on its boundary (tr_hot: st = -1), or the interior point failed cold -- the QP that is left knows no rate rows
+        if (b.ndU > 0 && st != 0) { needs_host = true; have_warm = false; break; }
         if constexpr (GXL > 0) {
             if (!tr_hot && !dense_u) {
                 ql::Lds LL;
@@ -634,6 +643,12 @@ __global__ __launch_bounds__(SSM_THREADS) void gusto_ssm_kernel(QPDims d, QPCons
         }
     }
     status = gusto_final_status(par, s, status);
+    if (needs_host) {                                      // unsolved: the caller's initial trajectory goes back out
+        status = SSM_NEEDS_HOST;
+        __syncthreads();
+        for (int e = tid; e < (N + 1) * n; e += nt) xk[e] = b.x_init[p * (size_t)(N + 1) * n + e];
+        for (int e = tid; e < N * m; e += nt) uk[e] = b.u_init[p * (size_t)N * m + e];
+    }
     gusto_write_out(b.xopt, b.uopt, b.zopt, p, N, n, m, nz, b.Hm, xk, uk, tid, nt);
     if (tid == 0) { rec[SSM_REC_WARM] = have_warm ? 1.0 : 0.0; b.iters[p] = s.itr; b.status[p] = status; if (b.Jopt) b.Jopt[p] = s.J_prev; }
 }
@@ -646,7 +661,8 @@ struct sgusto_ssm_plan {
     GustoPar par{};
     int64_t batch = 0;
     int n = 0, mode = 0, nXv = 0, max_trace = 0;
-    srh::DevBuf fs, Hm, XA, Xb, work, Jopt;
+    srh::DevBuf fs, Hm, XA, Xb, work, Jopt, dUA, dUb;
+    int ndU = 0;                        // rows of the rate polyhedron, in the plan's own buffers dUA / dUb (QPConst does not carry them)
     size_t work_stride = 0, lds = 0;
     int red_off = 0, tab_off = 0;       // (doubles) reduction scratch / model tables behind the aliased layouts (tab_off = 0: tables stay in L2)
     int lean_gx = 0;                    // > 0: the lean one-wave interior point runs first (template argument GXL of the kernel)
@@ -692,7 +708,8 @@ int sgusto_ssm_plan_create(sgusto_ssm_plan_t **out, sssm_t *model, const slocp_p
     SRH_REQUIRE(prob->n_x == model->n || prob->n_x == model->n + model->no,
                 "sgusto_ssm_plan_create: the QP's state has %d entries; the model has n = %d states (+ %d outputs when they are carried)",
                 prob->n_x, model->n, model->no);
-    SRH_REQUIRE(prob->Qzf == nullptr && prob->ndU == 0, "sgusto_ssm_plan_create: terminal cost / rate rows are not on this path");
+    SRH_REQUIRE(prob->Qzf == nullptr, "sgusto_ssm_plan_create: a terminal cost is not on this path");
+    SRH_REQUIRE(prob->ndU >= 0 && (prob->ndU == 0 || (prob->dUA && prob->dUb)), "sgusto_ssm_plan_create: ndU > 0 needs dUA and dUb");
     SRH_REQUIRE(mode >= SSM_FE && mode <= SSM_DISCRETE_MAP, "sgusto_ssm_plan_create: mode %d", mode);
     SRH_REQUIRE(mode != SSM_DISCRETE_MAP || model->has_discrete, "sgusto_ssm_plan_create: the model has no discrete map");
     SRH_REQUIRE(nX == 0 || (XA && Xb), "sgusto_ssm_plan_create: nX > 0 needs XA and Xb");
@@ -703,9 +720,19 @@ int sgusto_ssm_plan_create(sgusto_ssm_plan_t **out, sssm_t *model, const slocp_p
     pl->mode = mode;
     pl->nXv = nX;
     pl->max_trace = max_trace;
-    int rc = build_consts(prob, pl->C);
+    // the rate rows stay out of the constants every SCP kernel shares: they are rows of the dense one-wave QP, from the plan's own buffers
+    slocp_problem prob0 = *prob;
+    prob0.ndU = 0; prob0.dUA = nullptr; prob0.dUb = nullptr;
+    int rc = build_consts(&prob0, pl->C);
     if (rc) return rc;
     QPDims &d = pl->C.dims;
+    if (prob->ndU > 0) {
+        SRH_REQUIRE(!getenv("SRH_GUSTO_SSM_NO_DENSE"), "sgusto_ssm_plan_create: rate rows live in the dense one-wave QP, which SRH_GUSTO_SSM_NO_DENSE switches off");
+        const char *lim = qdu::limit(d, prob->ndU);
+        SRH_REQUIRE(lim == nullptr, "sgusto_ssm_plan_create: %d rate rows are not on this path for N = %d, n_u = %d, nU = %d, nX = %d: the one-wave QP in the space "
+                    "of the inputs needs %s", prob->ndU, d.N, d.m, d.nU, d.nX, lim ? lim : "");
+        pl->ndU = prob->ndU;
+    }
     // the lean one-wave interior point when the problem has its shape (lean.hip: lean_matches for NST < 0) and an instantiation exists
     {
         const int RXa = d.nX + d.nXf, gx = RXa == 0 ? 1 : (RXa <= 2 ? 2 : (RXa <= 4 ? 4 : 8));
@@ -721,7 +748,7 @@ int sgusto_ssm_plan_create(sgusto_ssm_plan_t **out, sssm_t *model, const slocp_p
     pl->work_stride = (doubles + 3) & ~(size_t)3;
     const SsmDev S = model->view();
     const size_t a = qp_kernel_lds_bytes(d), s2 = ssm_gusto_scratch_doubles(S) * sizeof(double);
-    pl->dense_u = (qdu::applies(d) && prob->Qzf == nullptr && !getenv("SRH_GUSTO_SSM_NO_DENSE")) ? 1 : 0;
+    pl->dense_u = (qdu::applies(d, pl->ndU) && prob->Qzf == nullptr && !getenv("SRH_GUSTO_SSM_NO_DENSE")) ? 1 : 0;
     if (pl->dense_u) pl->lean_gx = 0;               // (one one-wave QP per kernel: the instantiation without the lean interior point is the smaller one)
     const size_t a2 = pl->lean_gx ? lean_kernel_lds_bytes(d) : 0;
     const size_t a3 = pl->dense_u ? qdu::lds_doubles(d) * sizeof(double) : 0;
@@ -755,6 +782,7 @@ int sgusto_ssm_plan_create(sgusto_ssm_plan_t **out, sssm_t *model, const slocp_p
         (rc = pl->work.alloc(sizeof(double) * pl->work_stride * batch)) || (rc = pl->Jopt.alloc(sizeof(double) * batch)))
         return rc;
     if (nX > 0 && ((rc = pl->XA.upload(XA, sizeof(double) * nX * n)) || (rc = pl->Xb.upload(Xb, sizeof(double) * nX)))) return rc;
+    if (pl->ndU > 0 && ((rc = pl->dUA.upload(prob->dUA, sizeof(double) * pl->ndU * d.m)) || (rc = pl->dUb.upload(prob->dUb, sizeof(double) * pl->ndU)))) return rc;
     SRH_CHECK_HIP(hipMemset(pl->work.p, 0, sizeof(double) * pl->work_stride * batch));
     const PinLayout PL = pin_layout(pl.get());
     SRH_CHECK_HIP(hipHostMalloc((void **)&pl->pin, PL.total, hipHostMallocDefault));
@@ -764,6 +792,17 @@ int sgusto_ssm_plan_create(sgusto_ssm_plan_t **out, sssm_t *model, const slocp_p
 }
 
 int sgusto_ssm_plan_destroy(sgusto_ssm_plan_t *pl) { delete pl; return SRH_OK; }
+
+/* Whether a plan of these QP dimensions takes ndU rate rows (qdu::limit, the rule sgusto_ssm_plan_create applies): host arithmetic only. */
+int sgusto_ssm_rate_rows_fit(int N, int n_x, int n_u, int n_z, int nU, int nX, int nXf, int ndU, int *fits) {
+    SRH_REQUIRE(fits, "sgusto_ssm_rate_rows_fit: null argument");
+    SRH_REQUIRE(N >= 1 && n_x >= 1 && n_u >= 1 && n_z >= 1 && nU >= 0 && nX >= 0 && nXf >= 0 && ndU >= 0,
+                "sgusto_ssm_rate_rows_fit: need N, n_x, n_u, n_z >= 1 and row counts >= 0");
+    QPDims d{};
+    d.N = N; d.n = n_x; d.m = n_u; d.nz = n_z; d.nU = nU; d.nX = nX; d.nXf = nXf;
+    *fits = qdu::applies(d, ndU) ? 1 : 0;
+    return SRH_OK;
+}
 
 /* sgusto_plan_set_warm_across for the SSM plan: the first QP of a solve starts from the minimiser / multipliers the rollout's previous solve left
  * (the reference's warm_start=True, locp.py:181); only where the lean one-wave interior point runs. */
@@ -795,7 +834,8 @@ int sgusto_ssm_plan_solve_dev(sgusto_ssm_plan_t *pl, const double *x0, const dou
     SRH_REQUIRE(pl && x0 && u_init && x_init && xopt && uopt && zopt && iters && status, "sgusto_ssm_plan_solve_dev: null argument");
     SsmGustoBatch b{x0, u_init, x_init, z, u_des, pl->fs.as<double>(), pl->Hm.as<double>(), pl->nXv ? pl->XA.as<double>() : nullptr,
                     pl->nXv ? pl->Xb.as<double>() : nullptr, pl->nXv, xopt, uopt, zopt, iters, status, trace, pl->work.as<double>(),
-                    pl->work_stride, pl->n, pl->mode, pl->Jopt.as<double>(), 0};
+                    pl->work_stride, pl->n, pl->mode, pl->Jopt.as<double>(), 0, pl->ndU, pl->ndU ? pl->dUA.as<double>() : nullptr,
+                    pl->ndU ? pl->dUb.as<double>() : nullptr};
     GustoPar keep = pl->par;
     if (!trace) pl->par.max_trace = 0;
     const int rc = ssm_gusto_launch(pl, b, (hipStream_t)stream);
@@ -816,7 +856,8 @@ int sgusto_ssm_plan_solve(sgusto_ssm_plan_t *pl, const double *x0, const double 
     const PinArgs P = pin_stage(PL, pl->pin, dp, x0, u_init, x_init, z, nullptr, u_des, want_trace);
     SsmGustoBatch b{P.x0, P.u_init, P.x_init, P.z, P.ud, pl->fs.as<double>(), pl->Hm.as<double>(), pl->nXv ? pl->XA.as<double>() : nullptr,
                     pl->nXv ? pl->Xb.as<double>() : nullptr, pl->nXv, P.xopt, P.uopt, P.zopt, P.iters, P.status, P.trace, pl->work.as<double>(),
-                    pl->work_stride, pl->n, pl->mode, pl->Jopt.as<double>(), 1};
+                    pl->work_stride, pl->n, pl->mode, pl->Jopt.as<double>(), 1, pl->ndU, pl->ndU ? pl->dUA.as<double>() : nullptr,
+                    pl->ndU ? pl->dUb.as<double>() : nullptr};
     GustoPar keep = pl->par;
     if (!want_trace) pl->par.max_trace = 0;
     if (want_trace) for (size_t i = 0; i < (size_t)pl->batch * pl->max_trace * 4; ++i) reinterpret_cast<double *>(pl->pin + PL.trace)[i] = NAN;

@@ -6,13 +6,17 @@
 // 160 k clocks per iteration for a problem with 12 unknowns.  For N n_u <= 16 the whole QP fits one 16 x 16 tile in the space of u whatever
 // the cost looks like:
 //     minimise  (u - ud)^T Rb (u - ud) + sum_k (H x_k - z_k)^T Qz (H x_k - z_k)     x = x_free + S u            (locp.py:218-263, no 1/2)
-//     s.t.      C u <= h          rows: U.A u_k <= U.b (locp.py:300-303),  X.A x_k <= X.b, k = 1..N (locp.py:330-333) through S
+//     s.t.      C u <= h          rows: U.A u_k <= U.b (locp.py:300-303),  X.A x_k <= X.b, k = 1..N (locp.py:330-333) through S,
+//                                 dU.A (u_{k+1} - u_k) <= dU.b, k = 0..N-2 (locp.py:305-308): in this space one more row of C each, no coupling
 // with the dense Hessian Hq = 2 (Rb + G^T Qb G), G = H S (N n_z x N n_u), and the interior point of ql::ipm_box / ipm_wave -- same starting
 // point (unit-weight Newton step, shifts), weights D = lambda / (t + dreg lambda), Mehrotra predictor / corrector with step 0.99, stopping
 // rule and warm start -- on the Newton systems (Hq + C^T D C) du = -(grad + C^T rho): one MFMA Gram product per factorisation (operands: the
 // rows' coefficients in the MFMA layout, constant per QP, times sqrt(D) from LDS), Jacobi scaling, qpc::chol16, two 16 x 16 products per
 // solve.  One row per lane (<= 64 rows), everything else in a few KB of LDS; the other waves of the workgroup wait at the barrier behind it.
 // The per-stage matrices come from global memory (gusto_ssm.hip writes them per SCP iteration; per-stage or region-indexed: QPDyn).
+// Row order: [U rows (stage, row) | X rows (stage, row) | rate rows (k, r)]; rate row (k, r) holds +dU.A[r][b] at column (k + 1) n_u + b and
+// -dU.A[r][b] at column k n_u + b, right-hand side dU.b[r].  Without rate rows the layout and the arithmetic are those of round 6.  The
+// rate polyhedron is an argument of its own (Rate), not part of QPDims / QPConst, which every SCP kernel shares.
 #pragma once
 #include "locp_lean.h"
 
@@ -27,10 +31,20 @@ constexpr int CS = 17;                 // row stride of C in LDS (odd: lane = ro
 __host__ __device__ inline size_t stage_doubles(const QPDims &d) {
     return (size_t)d.N * d.n * (d.n + d.m + 1) + (size_t)d.nz * d.n + (size_t)d.nX * d.n;
 }
-__host__ __device__ inline bool applies(const QPDims &d) {
-    return d.N * d.m <= NU && d.N * d.nz <= NYM && d.N * (d.nU + d.nX) <= 64 && d.nXf == 0 && d.n <= 64 && d.N <= 8 && d.nz <= 16 && d.m <= 16 &&
-           stage_doubles(d) <= 6144;            // the stage matrices, H and X.A are staged in LDS (48 KB at most): small models
+// the rate polyhedron dU.A (u_{k+1} - u_k) <= dU.b of a plan: ndU rows, dUA (ndU x n_u), dUb (ndU); ndU = 0: none
+struct Rate { int ndU; const double *dUA, *dUb; };
+// The one statement of where this QP applies (the kernel's plan, sgusto_ssm_rate_rows_fit and through it GuSTO's Python predicate):
+// nullptr when it does, else the limit that was exceeded.  ndU: rows of the rate polyhedron (one row of C per stage pair and row).
+__host__ __device__ inline const char *limit(const QPDims &d, int ndU = 0) {
+    if (!(d.N * d.m <= NU)) return "N n_u <= 16 (the inputs of the horizon fill one tile)";
+    if (!(d.N * d.nz <= NYM)) return "N n_z <= 48";
+    if (!(d.N * (d.nU + d.nX) + (d.N - 1) * ndU <= 64)) return "N (nU + nX) + (N - 1) ndU <= 64 (one row per lane)";
+    if (!(d.nXf == 0)) return "no terminal state rows (nXf = 0)";
+    if (!(d.n <= 64 && d.N <= 8 && d.nz <= 16 && d.m <= 16)) return "n_x <= 64, N <= 8, n_z <= 16, n_u <= 16";
+    if (!(stage_doubles(d) <= 6144)) return "the stage matrices, H and X.A in 48 KB of LDS";     // they are staged in LDS: small models
+    return nullptr;
 }
+__host__ __device__ inline bool applies(const QPDims &d, int ndU = 0) { return limit(d, ndU) == nullptr; }
 // LDS doubles: S (2 x n x 16) | G (NYM x 16) | C (64 x 17) | W = Qb G (NYM x 16) | Hq, M, Rinv tiles (3 x 16 x 17) | xf ((N + 1) n) | vectors
 __host__ __device__ inline size_t lds_doubles(const QPDims &d) {
     return 2 * (size_t)d.n * 16 + 2 * (size_t)NYM * 16 + 64 * CS + 3 * 16 * TS + (size_t)(d.N + 1) * d.n + NYM + 8 * 64 + 16 + stage_doubles(d);
@@ -39,10 +53,11 @@ __host__ __device__ inline size_t lds_doubles(const QPDims &d) {
 // returns 0: w.x / w.u hold the minimiser of the FULL QP (converged, inside the trust region), J_out its objective; 100: the minimiser of
 // the relaxed QP leaves the trust region; anything else: interior point not converged.  `lam` (64 doubles of the rollout's work block): the
 // multipliers of the last converged solve (warm != 0 starts from w.u and them).
-__device__ __forceinline__ int solve(const QPDims &d, const QPConst &c, const QPDyn &dyn, const QPData &q, QPWork &w, lptr lds, gptr lam,
-                                     double *J_out, int *it_out, int warm, double *dbg = nullptr) {
+__device__ __forceinline__ int solve(const QPDims &d, const QPConst &c, const Rate &rt, const QPDyn &dyn, const QPData &q, QPWork &w, lptr lds,
+                                     gptr lam, double *J_out, int *it_out, int warm, double *dbg = nullptr) {
     const int tid = SRH_TID;
-    const int N = d.N, n = d.n, m = d.m, nz = d.nz, nu = N * m, ny = N * nz, nrU = N * d.nU, nr = nrU + N * d.nX;
+    const int N = d.N, n = d.n, m = d.m, nz = d.nz, nu = N * m, ny = N * nz, nrU = N * d.nU, nrX = nrU + N * d.nX, ndU = rt.ndU;
+    const int nr = nrX + (N - 1) * ndU;
     // the arrays of the interior point first, at compile-time offsets from one base (one address register, the rest in the instructions'
     // offset fields); the arrays whose size follows the model (set-up and tail only) behind them
     lptr Gl = lds, Cl = Gl + NYM * 16, Hl = Cl + 64 * CS, Tl = Hl + 16 * TS, Rl = Tl + 16 * TS, ey = Rl + 16 * TS, ul = ey + NYM, dul = ul + 64,
@@ -122,6 +137,13 @@ __device__ __forceinline__ int solve(const QPDims &d, const QPConst &c, const QP
             const int r = e >> 4, col = e & 15, k = r / d.nU, rr = r - k * d.nU;
             Cl[r * CS + col] = (col < nu && col / m == k) ? c.UA[(size_t)rr * m + (col - k * m)] : 0.0;
         }
+        // rate rows behind them: dU.A on the inputs of stage k + 1, -dU.A on those of stage k
+        for (int e = lane; e < (nr - nrX) * 16; e += 64) {
+            const int r = e >> 4, col = e & 15, k = r / ndU, rr = r - k * ndU, ck = col / m;
+            double v = 0.0;
+            if (col < nu && (ck == k || ck == k + 1)) { v = rt.dUA[(size_t)rr * m + (col - ck * m)]; if (ck == k) v = -v; }
+            Cl[(nrX + r) * CS + col] = v;
+        }
         // output errors of the free response, e_y = H xf_k - z_k (k = 1..N), and the constant of the objective (k = 0)
         for (int e = lane; e < ny; e += 64) {
             const int k = e / nz + 1, a = e - (k - 1) * nz;
@@ -137,13 +159,13 @@ __device__ __forceinline__ int solve(const QPDims &d, const QPConst &c, const QP
         const bool isrow = lane < nr;
         double hr = 0.0;
         if (lane < nrU) hr = c.Ub[lane % d.nU];
-        else if (isrow) {
+        else if (lane < nrX) {
             const int rl = lane - nrU, k = rl / d.nX + 1, rr = rl - (k - 1) * d.nX;
             double v = c.Xb[rr];
 #pragma unroll 4
             for (int j = 0; j < n; ++j) v = fma(-Xsl[(size_t)rr * n + j], xf[(size_t)k * n + j], v);
             hr = v;
-        }
+        } else if (isrow) hr = rt.dUb[(lane - nrX) % ndU];
         // W = Qb G (column l16, rows of this lane's k-group), Hq[i][l16] = 2 (sum_ya G[ya][i] W[ya] + R)
         for (int ya = kk; ya < ny; ya += 4) {
             const int k = ya / nz, a = ya - k * nz;
@@ -255,7 +277,11 @@ __device__ __forceinline__ int solve(const QPDims &d, const QPConst &c, const QP
         int mode = INIT;
         double mu = 0.0, rp = 0.0, sig = 0.0, sd = 1.0, sp = 1.0, dreg = 0.0;
         bool near_opt = false;
-        auto scales = [&]() { qp::residual_scales(d, c, q, lane, 64, sd, sp, dreg, [](double &a, double &b) { a = wg::wave_max(a); b = wg::wave_max(b); }); };
+        // (the primal scale takes |dU.b| into its maximum next to |U.b|: this lane's share goes in with sp)
+        auto scales = [&]() {
+            for (int e = lane; e < ndU; e += 64) sp = fmax(sp, fabs(rt.dUb[e]));
+            qp::residual_scales(d, c, q, lane, 64, sd, sp, dreg, [](double &a, double &b) { a = wg::wave_max(a); b = wg::wave_max(b); });
+        };
         if (warm && nr > 0) {
             if (isrow) ipm::start_warm(row_dot(ul) - hr, [&] { return lam[lane]; }, false, tr_, lr);
             scales();

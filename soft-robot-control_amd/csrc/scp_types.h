@@ -58,6 +58,7 @@ struct LocpBatch {
 namespace {
 
 constexpr int LEAN_PENDING = -77;       // status of a QP / rollout the lean kernel hands to the fused kernel
+constexpr int SSM_NEEDS_HOST = -78;     // status of a rollout the SSM kernel returns unsolved: rate rows present and the trust region binding (gusto_ssm.hip)
 constexpr int GUSTO_REC = 10;           // doubles of the TPWL kernels' resume record behind the SCP loop's index arrays; its slots:
 enum GustoRecSlot {
     REC_PENDING = 0,                    // 1.0: the lean kernel handed this rollout over, the slots below hold its SCP state

@@ -6,8 +6,10 @@ and re-linearisation -- runs inside ONE persistent HIP kernel (csrc/gusto.hip: g
 workgroup per rollout; `batch` independent rollouts (different x0 / targets, same model) can be solved
 by one launch with `GuSTO.solve_batch`.  An SSM polynomial model (scp/models/ssm.py adapter: the reference's hardware loop,
 examples/hardware/diamond_SSM.py:353-361) has its own persistent kernel (csrc/gusto_ssm.hip: analytic linearisation of the
-dynamics and of the output map inside the loop).  Any other TemplateModel -- a user's Python dynamics, weighting-mode TPWL,
-input-rate rows -- runs the SCP rules on the host around the device QP (`LOCP`): still no CPU arithmetic for the QP."""
+dynamics and of the output map inside the loop; input-rate rows dU ride along as rows of its one-wave QP where they fit, and a rollout
+whose trust region binds under them comes back with status SSM_NEEDS_HOST and is re-solved by the host loop).  Any other TemplateModel
+-- a user's Python dynamics, weighting-mode TPWL, input-rate rows on a TPWL model -- runs the SCP rules on the host around the device QP
+(`LOCP`): still no CPU arithmetic for the QP."""
 import ctypes as C
 import os
 import time
@@ -30,6 +32,7 @@ GAMMA_FAIL = 5
 OMEGA_MAX = 1e10
 MAX_ITERS = 500
 CONVERGE = 0.1
+SSM_NEEDS_HOST = -78      # csrc/scp_types.h: status of a rollout the SSM kernel hands back to the host loop (rate rows, trust region binding)
 
 
 class GuSTO:
@@ -73,22 +76,29 @@ class GuSTO:
         self.x_k = None
         self.u_k = None
         self.nonlinear_observer = model.nonlinear_observer
-        # input-rate constraints couple the stages: they go through the generic loop around the (augmented) device QP; so does the
-        # input_nullspace term (locp.py:258-261: a norm over the whole input sequence, LOCP._solve_nullspace)
+        # input-rate constraints couple the stages: on a TPWL model they go through the generic loop around the (augmented) device
+        # QP; so does the input_nullspace term (locp.py:258-261: a norm over the whole input sequence, LOCP._solve_nullspace)
         nullspace = kwargs.get('input_nullspace') is not None
         self._fused = (isinstance(model, TPWLGuSTO) and not self.nonlinear_observer and dU is None and not nullspace and
                        getattr(model.dyn_sys, 'tpwl_method', 'nn') == 'nn')
-        # an SSM model: the whole solve in csrc/gusto_ssm.hip (no terminal cost, no rate rows; the state polyhedron is applied to the
-        # states by the reference's own test, gusto.py:185-201, so its matrix must have n_x columns)
-        self._ssm = (isinstance(model, SSMGuSTO) and dU is None and Qzf is None and Xf is None and not nullspace and
+        # an SSM model: the whole solve in csrc/gusto_ssm.hip (no terminal cost; the state polyhedron is applied to the states by the
+        # reference's own test, gusto.py:185-201, so its matrix must have n_x columns; rate rows dU where the one-wave QP in the space
+        # of the inputs has room for them: _ssm_rate_rows_fit)
+        self._ssm = (isinstance(model, SSMGuSTO) and Qzf is None and Xf is None and not nullspace and
                      (X is None or np.asarray(X.A).shape[1] == self.n_x) and hasattr(model.dyn_sys, 'handle') and
-                     not os.environ.get('SRH_GUSTO_SSM_HOST_LOOP'))          # (that knob: the host loop, for A/B runs and tests)
+                     not os.environ.get('SRH_GUSTO_SSM_HOST_LOOP') and       # (that knob: the host loop, for A/B runs and tests)
+                     (dU is None or self._ssm_rate_rows_fit(U, X, dU)))
+        # what the host loop's LOCP is built from when a rollout comes back from the SSM kernel (_ssm_hand_back: lazily, on first need)
+        self._locp_args = dict(verbose=(verbose == 2), warm_start=warm_start, x_char=self.x_char,
+                               nonlinear_observer=self.nonlinear_observer, **kwargs)
+        self._handed_to_host = 0
         self._plan = C.c_void_p()
         self.trace = None
         self.iters = None
         self.status = None
         if self._ssm:
-            self._create_ssm_plan(model, N, dt, Qz, R, U, X)
+            self.locp = None
+            self._create_ssm_plan(model, N, dt, Qz, R, U, X, dU)
             self._fused = True
         elif self._fused:
             prob, self._keep = make_problem(N, model.H, Qz, R, Qzf, U, X, Xf, dU, None, True)
@@ -121,14 +131,36 @@ class GuSTO:
                     warnings.warn('GuSTO(keep_solver_state=True): this plan\'s kernels (%s) start every solve cold -- only the lean kernels '
                                   'with box input rows keep the solver state between solves' % self.kernel_info['kernel'])
 
-    def _create_ssm_plan(self, model, N, dt, Qz, R, U, X):
+    def _ssm_rate_rows_fit(self, U, X, dU):
+        """Whether the SSM plan takes the rate polyhedron dU (sgusto_ssm_rate_rows_fit: the predicate sgusto_ssm_plan_create applies,
+        on the QP's dimensions as _create_ssm_plan poses it -- the augmented state when the observer is nonlinear); the rows live in
+        the dense one-wave QP only, so SRH_GUSTO_SSM_NO_DENSE switches them off with it."""
+        if os.environ.get('SRH_GUSTO_SSM_NO_DENSE'):
+            return False
+        rows = lambda P: 0 if P is None else int(np.asarray(P.A).shape[0])
+        n_qp = self.n_x + (self.n_z if self.nonlinear_observer else 0)
+        fits = C.c_int(0)
+        _lib.check(_lib.lib().sgusto_ssm_rate_rows_fit(C.c_int(self.N), C.c_int(n_qp), C.c_int(self.n_u), C.c_int(self.n_z),
+                                                       C.c_int(rows(U)), C.c_int(rows(X)), C.c_int(0), C.c_int(rows(dU)),
+                                                       C.byref(fits)), 'sgusto_ssm_rate_rows_fit')
+        return bool(fits.value)
+
+    def _create_ssm_plan(self, model, N, dt, Qz, R, U, X, dU=None):
         """The resident plan of csrc/gusto_ssm.hip.  With a nonlinear output map the QP is posed in the augmented state [x ; zeta]
         (LOCP._init_augmented: H_a = [0 I], X on zeta, zero trust-region scale on zeta) -- the same problem data the host loop
-        handed to the QP kernel; the kernel fills the per-stage matrices itself."""
+        handed to the QP kernel; the kernel fills the per-stage matrices itself.  The rate polyhedron dU goes into the problem as it
+        is (rows on the inputs alone: no augmentation); the plan keeps it in buffers of its own."""
         sys_ = model.dyn_sys
         proto = LOCP(N, model.H, Qz, R, Qzf=None, U=U, X=X, Xf=None, dU=None, x_char=self.x_char,
                      nonlinear_observer=self.nonlinear_observer)
         self._keep = (proto, proto._prob, proto._keep)
+        self._rate_rows = 0
+        if dU is not None:
+            dUA = _lib.f64(np.asarray(dU.A).reshape(-1, self.n_u))
+            dUb = _lib.f64(np.asarray(dU.b).reshape(dUA.shape[0]))
+            proto._prob.ndU, proto._prob.dUA, proto._prob.dUb = dUA.shape[0], _lib.dptr(dUA), _lib.dptr(dUb)
+            self._keep += (dUA, dUb)
+            self._rate_rows = int(dUA.shape[0])
         Hm = _lib.f64(np.asarray(model.H).reshape(self.n_z, self.n_x))
         fc = _lib.f64(self.f_char)
         nX = 0 if X is None else int(np.asarray(X.A).shape[0])
@@ -196,7 +228,10 @@ class GuSTO:
         'single_region_qps' (resident TPWL plan): QPs of the last solve whose horizon lay in one TPWL region and were
         condensed by the single-region recursion (sgusto_plan_single_region_qps)."""
         if self._ssm:
-            return {'family': 'ssm', 'kernel': 'gusto_ssm_kernel', 'lean': None, 'fused': None, 'handed_over': 0}
+            # 'rate_rows': rows of dU in the kernel's QP; 'handed_to_host': rollouts the kernel returned with SSM_NEEDS_HOST since the plan
+            # was created (each re-solved by the host loop: _ssm_hand_back)
+            return {'family': 'ssm', 'kernel': 'gusto_ssm_kernel', 'lean': None, 'fused': None, 'handed_over': 0,
+                    'rate_rows': self._rate_rows, 'handed_to_host': self._handed_to_host}
         if not self._fused:
             return self.locp.kernel_info
         info = _lib.SrhKernelInfo()
@@ -297,6 +332,8 @@ class GuSTO:
             _lib.check(_lib.lib().sgusto_ssm_plan_solve(self._plan, _lib.dptr(x0), _lib.dptr(u_init), _lib.dptr(x_init), _lib.dptr(z),
                                                         _lib.dptr(u), _lib.dptr(xo), _lib.dptr(uo), _lib.dptr(zo), _lib.iptr(iters),
                                                         _lib.iptr(status), _lib.dptr(trace)), 'sgusto_ssm_plan_solve')
+            if self._rate_rows and np.any(status == SSM_NEEDS_HOST):
+                self._ssm_hand_back((x0, u_init, x_init, z, u), xo, uo, zo, iters, status, trace)
             self.locp_solve_time = time.time() - t0
             self.iters, self.status, self.trace = iters, status, trace
             self.xopt, self.uopt, self.zopt = xo, uo, zo
@@ -311,6 +348,24 @@ class GuSTO:
         self.iters, self.status, self.trace = iters, status, trace
         self.xopt, self.uopt, self.zopt = xo, uo, zo
         return xo, uo, zo
+
+    def _ssm_hand_back(self, args, xo, uo, zo, iters, status, trace):
+        """The rollouts the SSM kernel ended with SSM_NEEDS_HOST -- rate rows present and the trust region binding, where the kernel's
+        full-row QP knows no rate rows and must not drop them -- solved again from their original arguments by the host loop around
+        the state-augmented QP (LOCP with dU, built on first need); result, iteration count, status and trace are installed in place."""
+        x0, u_init, x_init, z, u = args
+        if self.locp is None:
+            self.locp = LOCP(self.N, self.model.H, self.Qz, self.R, Qzf=None, U=self.U, X=self.X, Xf=None, dU=self.dU, **self._locp_args)
+        for b in np.flatnonzero(status == SSM_NEEDS_HOST):
+            self._solve_host_loop(x0[b], u_init[b], x_init[b], None if z is None else z[b], None, None if u is None else u[b])
+            xo[b], uo[b], zo[b] = self.xopt, self.uopt, self.zopt
+            status[b], iters[b], log = self._host_result
+            if trace is not None:
+                trace[b] = np.nan
+                rows = min(len(log), trace.shape[1])
+                if rows:
+                    trace[b, :rows] = np.asarray(log[:rows], dtype=np.float64).reshape(-1, 4)
+            self._handed_to_host += 1
 
     # ---- asynchronous solve (fused plans): the request runs on the plan's own HIP stream
     def solve_begin(self, x0, u_init, x_init, z=None, zf=None, u=None):
@@ -417,6 +472,7 @@ class GuSTO:
                 self.xopt, self.uopt = np.copy(self.x_k), np.copy(self.u_k)
                 self.zopt = (self.model.dyn_sys.C_map(self.xopt.T) if self.nonlinear_observer
                              else np.transpose(self.model.H @ self.xopt.T))
+                self._host_result = (1, itr, log)
                 return
             t_locp += stats.solve_time
             x_new, u_new, _ = self.locp.get_solution()
@@ -435,6 +491,8 @@ class GuSTO:
         self.xopt, self.uopt = np.copy(self.x_k), np.copy(self.u_k)
         self.zopt = np.transpose(self.model.H @ self.xopt.T)
         self.locp_solve_time = t_locp
+        # (status as the kernels report it, csrc/scp_types.h: gusto_final_status)
+        self._host_result = (2 if st['omega'] > self.omega_max else (3 if not self.is_valid_iteration(itr - 1) else 0), itr, log)
         self.iters = np.array([itr], dtype=np.int32)
         if self.max_trace > 0:
             self.trace = np.full((1, max(self.max_trace, len(log)), 4), np.nan)

@@ -1,7 +1,9 @@
 """The reference's hardware loop (examples/hardware/diamond_SSM.py:353-361: SSM n_x = 6, n_u = 4, N = 3, dt = 0.02,
 max_gusto_iters = 0) through GuSTO.solve: median / p95 wall time per call, on the device path (csrc/gusto_ssm.hip) and -- with
 SRH_GUSTO_SSM_HOST_LOOP=1 -- on the host loop around the device QP.  SRH_GUSTO_SSM_NO_LEAN=1: the device path without the lean
-one-wave interior point.  Usage (GPU box, repo root): python tools/time_ssm_rti.py [--batch B]"""
+one-wave interior point.  --rate R: the driver's input-rate box dU = HyperRectangle([R] * 4, [-R] * 4) (diamond_SSM.py:338-339; rows of the
+kernel's one-wave QP on the device path, the state-augmented QP on the host loop).  --json FILE: the figures as one JSON object.
+Usage (GPU box, repo root): python tools/time_ssm_rti.py [--batch B] [--three] [--keep] [--rate R] [--json FILE]"""
 import os
 import sys
 import time
@@ -39,17 +41,19 @@ if '--three' in sys.argv:          # the driver's own cost: x, y, z of the end e
     Qz6[2, 2] = 100.0
 R6 = 0.003 * np.eye(m4)
 U = HyperRectangle([1500.0] * m4, [0.0] * m4)
+RATE = float(sys.argv[sys.argv.index('--rate') + 1]) if '--rate' in sys.argv else None
+dU = None if RATE is None else HyperRectangle([RATE] * m4, [-RATE] * m4)
 x06 = np.zeros(n6)
 u6 = np.zeros((N3, m4))
 xi6, _ = s6.rollout(x06, u6, dt2)
 z6 = np.tile(np.array([0.02, -0.01, 0.015 if '--three' in sys.argv else 0.0, 0, 0, 0.0]), (N3 + 1, 1))
 KEEP = '--keep' in sys.argv          # keep_solver_state=True: the reference's warm_start semantics across calls
 if B == 1:
-    g6 = GuSTO(gm6, N3, dt2, Qz6, R6, x06, u6, xi6, z=z6, U=U, verbose=0, max_gusto_iters=0, convg_thresh=1e-3, keep_solver_state=KEEP)
+    g6 = GuSTO(gm6, N3, dt2, Qz6, R6, x06, u6, xi6, z=z6, U=U, dU=dU, verbose=0, max_gusto_iters=0, convg_thresh=1e-3, keep_solver_state=KEEP)
     call = lambda: g6.solve(x06, u6, xi6, z6, None, None)
 else:
     xb, ub, xib, zb = np.tile(x06, (B, 1)), np.tile(u6, (B, 1, 1)), np.tile(xi6, (B, 1, 1)), np.tile(z6, (B, 1, 1))
-    g6 = GuSTO(gm6, N3, dt2, Qz6, R6, xb, ub, xib, z=zb, U=U, verbose=0, max_gusto_iters=0, convg_thresh=1e-3, batch=B, first_solve_cap=5)
+    g6 = GuSTO(gm6, N3, dt2, Qz6, R6, xb, ub, xib, z=zb, U=U, dU=dU, verbose=0, max_gusto_iters=0, convg_thresh=1e-3, batch=B, first_solve_cap=5)
     call = lambda: g6.solve_batch(xb, ub, xib, zb)
 ts = []
 for _ in range(200):
@@ -57,9 +61,17 @@ for _ in range(200):
     call()
     ts.append(time.perf_counter() - t0)
 ts = np.sort(np.array(ts[20:])) * 1e3
-print('SSM GuSTO real-time iteration%s, batch %d, path %s: median %.3f ms, p95 %.3f ms, min %.3f ms per call; iters %s; kernel %s' %
-      (' (solver state kept)' if KEEP else '', B, 'device' if getattr(g6, '_ssm', False) else 'host loop', np.median(ts), ts[int(len(ts) * 0.95)], ts[0], g6.iters[:4],
-       g6.kernel_info))
+PATH = 'device' if getattr(g6, '_ssm', False) else 'host loop'
+print('SSM GuSTO real-time iteration%s%s, batch %d, path %s: median %.3f ms, p95 %.3f ms, min %.3f ms per call; iters %s; kernel %s' %
+      (' (solver state kept)' if KEEP else '', '' if RATE is None else ', rate box %g' % RATE, B, PATH, np.median(ts), ts[int(len(ts) * 0.95)], ts[0],
+       g6.iters[:4], g6.kernel_info))
+if '--json' in sys.argv:
+    import json
+    with open(sys.argv[sys.argv.index('--json') + 1], 'w') as fh:
+        json.dump(dict(path=PATH, rate=RATE, three='--three' in sys.argv, batch=B, keep=KEEP, timed_calls=len(ts), median_ms=float(np.median(ts)),
+                       p95_ms=float(ts[int(len(ts) * 0.95)]), min_ms=float(ts[0]), iters=[int(v) for v in g6.iters[:4]],
+                       du_max=float(np.abs(np.diff(g6.uopt.reshape(-1, N3, m4), axis=1)).max()),
+                       kernel_info={k: v for k, v in g6.kernel_info.items() if isinstance(v, (int, str, type(None)))}), fh)
 if os.environ.get('SRH_GUSTO_TRACE_QIT') and g6.trace is not None:
     print('   shader clocks of the last call: linearise %.0f, QP %.0f, tests %.0f; interior-point iterations + 1000 (pass + 1): %.0f' % tuple(g6.trace[0, 0]))
     if np.isfinite(g6.trace[0, 1, 0]) and g6.trace[0, 1, 0] > 0:      # a library built with -DQDU_CLOCKS=1 (locp_dense_u.h)
