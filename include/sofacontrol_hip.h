@@ -322,6 +322,16 @@ int sric_dare(const double *A, const double *B, int64_t batch, int n_x, int n_u,
  * workgroup.  n_x as far as sric_dare goes (above 62 or so the five n x n slots move from LDS to the HBM workspace). */
 int sric_dare_wide(const double *A, const double *B, int64_t batch, int n_x, int n_u, const double *Q, const double *R,
                    double tol, int max_iter, double *L, double *P, int32_t *iters);
+/* CLQR (lqr.py:57-64: control.lqr, slycot's continuous Riccati solver, in the reference): the stabilising solution P of
+ * A^T P + P A - P B R^-1 B^T P + Q = 0 and the gain K = -R^-1 B^T P, stated for u = +K x like every gain of this library
+ * (control.lqr returns -K).  A Cayley transform with the shift gamma = 1.5 max(||A||_inf, 1e-3) brings the equation to the doubling
+ * loop of sric_dare: same stopping rule, iters = doubling steps, same shapes, `batch` continuous (A, B) pairs under one (Q, R),
+ * 1 <= n_u <= 16.  SRH_ENUMERIC, naming the first such problem, when R is not positive definite, when A - gamma I, the start's
+ * second pivot matrix or I + G H is singular or a value is not finite, and when min(max_iter, 48) steps do not converge to a fixed
+ * point whose closed loop A + B K is stable (a pair that is not stabilisable ends in one of the last two; convergence later than
+ * step 48 would mean a stability margin below gamma 2^-45, which the rounding of the start cannot tell from none). */
+int sric_care(const double *A, const double *B, int64_t batch, int n_x, int n_u, const double *Q, const double *R,
+              double tol, int max_iter, double *K, double *P, int32_t *iters);
 
 /* =====================================================================================================
  * iLQR.                          reference: sofacontrol/lqr/ilqr.py, sofacontrol/lqr/config.py

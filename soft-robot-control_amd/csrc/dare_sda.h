@@ -3,9 +3,11 @@
 //   G = B R^-1 B^T, H = Q;   W = I + G H,  [V1 V2] = W^-1 [A G]
 //   A <- A V1,   G <- G + A V2 A^T,   H <- H + A^T (H V1)            ->   H converges quadratically to P
 // Here: the product routine `mm`, the carve of the five n x n slots and of the Gauss-Jordan rows behind each kernel's own m-wide
-// head, the G0 / A0 / H0 fill, the iteration from its `while` to the write-out of P, and the host launcher of the three DARE entry
-// points (sric_dare, sric_dare_wide, sric_dare_fixed_point).  What is m wide stays in the kernels: the factor of R, the m x n solve
-// and the gain phase with its status handling.
+// head, the G0 / A0 / H0 fill, the pivoted elimination on a three-block tableau, the iteration from its `while` to the write-out of
+// P, and the host launcher of the three DARE entry points (sric_dare, sric_dare_wide, sric_dare_fixed_point).  What is m wide stays
+// in the kernels: the factor of R, the m x n solve and the gain phase with its status handling.
+// care_sda_kernel (care.hip, sric_care) brings the continuous equation to the same loop by a Cayley transform: its start phase runs
+// `eliminate` twice and then calls `iterate` and `run` as the DARE kernels do.
 // The operation order and grouping of every expression is what the kernels' results depend on bit for bit: keep it.
 #pragma once
 #include "common.h"
@@ -101,8 +103,61 @@ __device__ __forceinline__ void start(const Slots &s, cgptr Ag, cgptr Qg, clptr 
     __syncthreads();
 }
 
-// status of a problem: 0 converged, 1 max_iter doubling steps without convergence, 2 R or R + B^T P B not positive definite,
-// 3 singular I + G H
+// [S2 S3] <- S1^-1 [S2 S3] (and S1 <- I): Gauss-Jordan elimination with partial pivoting (physical row swaps) on the tableau
+// [S1 | S2 | S3] of three n x n blocks -- [W | A | G] in `iterate`, the two tableaus of the Cayley start in care.hip.  false (to every
+// thread) at a pivot that is zero or not finite.  The blocks must be visible to the workgroup; ends synchronised.
+__device__ __forceinline__ bool eliminate(double *S1, double *S2, double *S3, const Rows &T, int n, int ld) {
+    const int tid = SRH_TID, nt = blockDim.x;
+    for (int j = 0; j < n; ++j) {
+        if (tid < 64) {
+            double best = -1.0;
+            int bi = j;
+            for (int i = j + tid; i < n; i += 64) {
+                const double v = fabs(S1[i * ld + j]);
+                if (v > best) { best = v; bi = i; }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const double ob = __shfl_xor(best, o, 64);
+                const int oi = __shfl_xor(bi, o, 64);
+                if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+            }
+            if (tid == 0) { T.ipiv[0] = bi; T.ipiv[1] = (best > 1e-300 && best < 1e300) ? 1 : 0; }
+        }
+        __syncthreads();
+        const int pv = T.ipiv[0];
+        if (T.ipiv[1] == 0) return false;
+        // snapshot: pivot row (old row pv), old row j, multipliers of every row as they will sit after the swap
+        for (int c = tid; c < 3 * n; c += nt) {
+            double *blk = c < n ? S1 : (c < 2 * n ? S2 : S3);
+            const int cc = c < n ? c : (c < 2 * n ? c - n : c - 2 * n);
+            T.prow[c] = blk[pv * ld + cc];
+            T.jrow[c] = blk[j * ld + cc];
+        }
+        for (int i = tid; i < n; i += nt) T.fcol[i] = S1[(i == pv ? j : i) * ld + j];
+        __syncthreads();
+        const double rp = 1.0 / T.prow[j];
+        for (int e = tid; e < 3 * n * n; e += nt) {
+            const int i = e / (3 * n), c = e - i * 3 * n;
+            double *blk = c < n ? S1 : (c < 2 * n ? S2 : S3);
+            const int cc = c < n ? c : (c < 2 * n ? c - n : c - 2 * n);
+            const double pr = T.prow[c] * rp;
+            double v;
+            if (i == j) v = pr;
+            else {
+                const double src = (i == pv) ? T.jrow[c] : blk[i * ld + cc];
+                v = fma(-T.fcol[i], pr, src);
+            }
+            blk[i * ld + cc] = v;
+        }
+        __syncthreads();
+    }
+    return true;
+}
+
+// status of a problem: 0 converged, 1 max_iter doubling steps without convergence (care.hip: or a converged fixed point that is not
+// stabilising), 2 R or R + B^T P B not positive definite, 3 singular I + G H (care.hip: or A - gamma I, W of the Cayley start), or
+// a value that is not finite
 struct Result { int st, it; };
 
 // The doubling steps (none if the caller's factorisation of R already failed: st != 0) and the write-out of H = P (n x n, dense)
@@ -116,52 +171,8 @@ __device__ __forceinline__ Result iterate(const Slots &s, const Rows &T, int n, 
         mm<false, false>(S1, ld, S3, ld, S4, ld, n, n, n);
         for (int e = tid; e < n; e += nt) S1[e * ld + e] += 1.0;
         __syncthreads();
-        // [V1 V2] = W^-1 [A G]: Gauss-Jordan with partial pivoting (physical row swaps) on [S1 | S2 | S3]
-        for (int j = 0; j < n && st == 0; ++j) {
-            if (tid < 64) {
-                double best = -1.0;
-                int bi = j;
-                for (int i = j + tid; i < n; i += 64) {
-                    const double v = fabs(S1[i * ld + j]);
-                    if (v > best) { best = v; bi = i; }
-                }
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const double ob = __shfl_xor(best, o, 64);
-                    const int oi = __shfl_xor(bi, o, 64);
-                    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-                }
-                if (tid == 0) { T.ipiv[0] = bi; T.ipiv[1] = (best > 1e-300 && best < 1e300) ? 1 : 0; }
-            }
-            __syncthreads();
-            const int pv = T.ipiv[0];
-            if (T.ipiv[1] == 0) { st = 3; break; }
-            // snapshot: pivot row (old row pv), old row j, multipliers of every row as they will sit after the swap
-            for (int c = tid; c < 3 * n; c += nt) {
-                double *blk = c < n ? S1 : (c < 2 * n ? S2 : S3);
-                const int cc = c < n ? c : (c < 2 * n ? c - n : c - 2 * n);
-                T.prow[c] = blk[pv * ld + cc];
-                T.jrow[c] = blk[j * ld + cc];
-            }
-            for (int i = tid; i < n; i += nt) T.fcol[i] = S1[(i == pv ? j : i) * ld + j];
-            __syncthreads();
-            const double rp = 1.0 / T.prow[j];
-            for (int e = tid; e < 3 * n * n; e += nt) {
-                const int i = e / (3 * n), c = e - i * 3 * n;
-                double *blk = c < n ? S1 : (c < 2 * n ? S2 : S3);
-                const int cc = c < n ? c : (c < 2 * n ? c - n : c - 2 * n);
-                const double pr = T.prow[c] * rp;
-                double v;
-                if (i == j) v = pr;
-                else {
-                    const double src = (i == pv) ? T.jrow[c] : blk[i * ld + cc];
-                    v = fma(-T.fcol[i], pr, src);
-                }
-                blk[i * ld + cc] = v;
-            }
-            __syncthreads();
-        }
-        if (st != 0) break;
+        // [V1 V2] = W^-1 [A G]
+        if (!eliminate(S1, S2, S3, T, n, ld)) { st = 3; break; }
         mm<false, false>(S5, ld, gA, ld, S2, ld, n, n, n);            // A_next = A V1
         mm<false, false>(S1, ld, gA, ld, S3, ld, n, n, n);            // T2 = A V2
         mm<false, true>(S3, ld, S1, ld, gA, ld, n, n, n);             // T2 A^T  (V2 is dead)
@@ -205,10 +216,15 @@ struct Launch {
     size_t tail_lds;        // bytes of LDS behind the five slots
     size_t min_lds;         // bytes of LDS the kernel carves whatever the slots (the gain phase's LqrLds)
     bool doubling;          // a DoublingKernel: takes the workspace and reports the doubling's statuses
+    // the texts of statuses 1, 2 and 3 (sric_care sets its own after construction)
+    const char *stalled = "no convergence within max_iter doubling steps";
+    const char *not_pd = "R or R + B^T P B is not positive definite";
+    const char *singular = "singular I + G H (not stabilisable / detectable?)";
     Launch(const char *name_, DoublingKernel k, int threads_, size_t tail_lds_, size_t min_lds_)
         : name(name_), kernel((const void *)k), threads(threads_), tail_lds(tail_lds_), min_lds(min_lds_), doubling(true) {}
     Launch(const char *name_, FixedPointKernel k, int threads_, size_t lds_)
-        : name(name_), kernel((const void *)k), threads(threads_), tail_lds(0), min_lds(lds_), doubling(false) {}
+        : name(name_), kernel((const void *)k), threads(threads_), tail_lds(0), min_lds(lds_), doubling(false),
+          not_pd("R + B^T P B is not positive definite") {}
 };
 
 inline int run(const Launch &k, const double *A, const double *B, int64_t batch, int n_x, int n_u, const double *Q, const double *R,
@@ -239,9 +255,8 @@ inline int run(const Launch &k, const double *A, const double *B, int64_t batch,
     for (int64_t i = 0; i < batch; ++i)
         if (st[i] != 0) {
             srh::set_error("%s: problem %lld: %s", k.name, (long long)i,
-                           st[i] == 1 ? "no convergence within max_iter doubling steps"
-                                      : (st[i] == 2 ? (k.doubling ? "R or R + B^T P B is not positive definite" : "R + B^T P B is not positive definite")
-                                                    : "singular I + G H (not stabilisable / detectable?)"));
+                           st[i] == 1 ? k.stalled
+                                      : (st[i] == 2 ? k.not_pd : k.singular));
             return SRH_ENUMERIC;
         }
     if ((rc = dL.download(L, sizeof(double) * batch * n_u * n_x)) || (rc = dP.download(P, sizeof(double) * batch * n_x * n_x))) return rc;

@@ -1,4 +1,4 @@
-"""Infinite-horizon discrete LQR gains on the device (sofacontrol/lqr/lqr.py:6-54)."""
+"""Infinite-horizon discrete and continuous LQR gains on the device (sofacontrol/lqr/lqr.py:6-64)."""
 import ctypes as C
 
 import numpy as np
@@ -7,8 +7,8 @@ from .. import _lib
 
 
 def _dare_call(entry, A, B, Q, R, tol, max_iter):
-    """One of the three DARE entry points (`sric_dare_fixed_point`, `sric_dare`, `sric_dare_wide`: one argument list) on a
-    single (A, B) pair or a stack of them: stacked (L, P, iterations)."""
+    """One of the Riccati entry points (`sric_dare_fixed_point`, `sric_dare`, `sric_dare_wide`, `sric_care`: one argument list)
+    on a single (A, B) pair or a stack of them: stacked (L, P, iterations)."""
     A, B = np.asarray(A), np.asarray(B)
     A = _lib.f64(A.reshape(-1, A.shape[-2], A.shape[-1]))
     B = _lib.f64(B.reshape(-1, B.shape[-2], B.shape[-1]))
@@ -65,6 +65,20 @@ def dare_batch(Ad, Bd, Q, R, tol=1e-14):
     return L, P
 
 
+def care(A, B, Q, R):
+    """lqr.py:63 (control.lqr, i.e. slycot's continuous Riccati solver, in the reference): the stabilising solution P of
+    A'P + P A - P B R^-1 B'P + Q = 0 and its gain K = -R^-1 B'P on the continuous pair (A, B), by a Cayley transform and the
+    doubling loop of `dare` on the device (`sric_care`).  u = +K x as everywhere in this package; control.lqr returns -K."""
+    K, P, _ = _dare_call('sric_care', A, B, Q, R, 1e-14, 100)
+    return K[0], P[0]
+
+
+def care_batch(A, B, Q, R, tol=1e-14):
+    """Continuous-time gains for a stack of (A, B) pairs in one launch: stacked (K, P)."""
+    K, P, _ = _dare_call('sric_care', A, B, Q, R, tol, 100)
+    return K, P
+
+
 class DLQR:
     """lqr.py:34-54."""
 
@@ -83,3 +97,12 @@ class DLQR:
         Ad, Bd, _ = self.model.discretize_dynamics(A_c=A, B_c=B, d_c=np.zeros(self.model.get_state_dim()), dt=self.dt)
         K, _ = solve_riccati(Ad, Bd, Q, R)
         return K
+
+
+class CLQR(DLQR):
+    """lqr.py:57-64: infinite-horizon continuous LQR about one operating point; no discretisation.  The gain is stated for
+    u = u_bar + K (x - x_bar), the form StateCLQR applies (the reference hands control.lqr's gain, made for u = -K x, to that same
+    form: INTEGRATION.md, "Behavioural notes")."""
+
+    def compute_gain_matrix(self, A, B, Q, R):
+        return care(A, B, Q, R)[0]

@@ -24,7 +24,7 @@ from .observer import FullStateObserver
 from .. import closed_loop_controller
 from ..lqr.ilqr import iLQR
 from ..lqr.traj_tracking_lqr import TrajTrackingLQR
-from ..lqr.lqr import DLQR, dare_batch
+from ..lqr.lqr import CLQR, DLQR, dare_batch
 
 _GRID = 4            # decimals of the control clock (the reference compares times rounded to 1e-4 s)
 
@@ -389,3 +389,8 @@ class StateDLQR(TemplateController):
     def compute_input(self, t_step, x_belief):
         self.u = self.u_bar + self.K @ (x_belief - self.x_bar)
         return self.u
+
+
+class StateCLQR(StateDLQR):
+    """Infinite-horizon continuous LQR about one (A, B, x, u) operating point (controllers.py:440-444)."""
+    LQR_type = CLQR
