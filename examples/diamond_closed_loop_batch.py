@@ -1,0 +1,89 @@
+"""The problem of examples/diamond_closed_loop.py as B closed loops at once: the C2 Diamond shape (synthetic TPWL model, the model
+itself as the plant at dt_sim = 0.01), seeded initial states and target phases, the scp controller's per-point DARE gains -- a
+Monte-Carlo validation of the controller.  All loops stay on the device (scp.closed_loop.ClosedLoopBatch): one launch sequence and
+one host wait for the whole run; state feedback is perfect (no observer inside the loop).
+
+    python examples/diamond_closed_loop_batch.py [--batch 256] [--periods 20] [--seed 0]
+
+Needs an MI355X (no CPU fallback)."""
+import argparse
+import contextlib
+import io
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'soft-robot-control_amd'))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--batch', type=int, default=256)
+    ap.add_argument('--periods', type=int, default=20, help='re-planning periods of 10 steps of 0.01 s')
+    ap.add_argument('--seed', type=int, default=0)
+    args = ap.parse_args()
+
+    import workloads as wl
+    from scipy.interpolate import interp1d
+    from sofacontrol_amd.lqr.lqr import dare_batch
+    from sofacontrol_amd.measurement_models import linearModel
+    from sofacontrol_amd.scp.closed_loop import ClosedLoopBatch
+    from sofacontrol_amd.scp.gusto import GuSTO
+    from sofacontrol_amd.scp.models.tpwl import TPWLGuSTO
+    from sofacontrol_amd.tpwl.tpwl import TPWLATV
+    from sofacontrol_amd.utils import HyperRectangle, Polyhedron
+
+    w = wl.diamond_c2()
+    n_f, r = w['U'].shape
+    m, N, dt, dt_sim, n_keep, B = w['m'], w['N'], w['dt'], 0.01, 10, args.batch
+    Hf = linearModel(nodes=[1354], num_nodes=n_f // 3).C.tocsr()              # tip velocity + position (diamond.py:269)
+    data = dict(w['tab'], rom_info=dict(type='POD', U=w['U'], q_ref=w['q_ref'], v_ref=w['v_ref']))
+    model = TPWLATV(data=data, params=dict(tpwl_method='nn', dist_weights={'q': 1.0, 'v': 0.0}), Hf=Hf, discr_method='zoh')
+    gm = TPWLGuSTO(model)
+    with contextlib.redirect_stdout(io.StringIO()):
+        gm.pre_discretize(dt)
+    H = np.asarray(model.H)
+    # the gains of the scp controller (tpwl/controllers.py: _point_gains): DARE at every table point, discretised at dt_sim
+    tab = model.tpwl_dict
+    Ad, Bd, dd = model.discretize_batch(np.stack(tab['A_c']), np.stack(tab['B_c']), np.stack(tab['d_c']), dt_sim)
+    model.handle_for(dt_sim, tables=(Ad, Bd, dd))                            # the plant: the same model stepped at dt_sim
+    K, _ = dare_batch(Ad, Bd, H.T @ w['Qz'] @ H + 1e-3 * np.eye(2 * r), 1e-4 * np.eye(m))
+
+    rng = np.random.default_rng(args.seed)
+    x0 = 0.5 * rng.standard_normal((B, 2 * r))
+    phase = rng.uniform(0.0, float(w['t'][-1]) / 2, B)
+    u_init = np.zeros((B, N, m))
+    x_init, _ = gm.rollout(x0, u_init, dt)
+    zi = interp1d(w['t'], w['z'], axis=0, bounds_error=False, fill_value=(w['z'][0], w['z'][-1]))
+    xc, fc = gm.get_characteristic_vals()
+    gusto = GuSTO(gm, N, dt, w['Qz'], w['R'], x0, u_init, x_init, z=zi(phase[:, None] + dt * np.arange(N + 1)),
+                  U=HyperRectangle([1500.] * m, [0.] * m), X=Polyhedron(w['XA'], w['Xb']), x_char=xc, f_char=fc, convg_thresh=1e-3,
+                  max_gusto_iters=3, batch=B, first_solve_cap=1, max_trace=0)
+    loop = ClosedLoopBatch(gusto, model, dt_sim, n_keep, t=w['t'], z=w['z'], phase=phase, K=K, max_steps_per_run=args.periods * n_keep)
+    loop.reset(x0)
+    t0 = time.perf_counter()
+    res = loop.run(args.periods, record_x=False)
+    wall = time.perf_counter() - t0
+
+    target = zi(phase[:, None] + res.t[None, :])                              # (B, S + 1, 6)
+    err = np.linalg.norm((res.z - target)[:, 1:, 3:5], axis=2)
+    rms = np.sqrt(np.mean(err ** 2, axis=1))
+    print('%d loops x %d periods (%.2f s each), %d host wait(s), %.1f ms per period' %
+          (B, args.periods, args.periods * n_keep * dt_sim, loop.stats()['waits_last_run'], 1e3 * wall / args.periods))
+    print('tip tracking rms (x, y) per loop: median %.3f, best %.3f, worst %.3f   (target amplitude %.1f)' %
+          (np.median(rms), rms.min(), rms.max(), np.abs(w['z'][:, 3:5]).max()))
+    for b in range(min(B, 8)):
+        print('  loop %d: phase %.2f s, rms %.3f, SCP iterations per period %.1f' % (b, phase[b], rms[b], res.iters[:, b].mean()))
+    names = {0: 'converged', 1: 'QP failed', 2: 'omega > omega_max', 3: 'max iterations'}
+    codes, counts = np.unique(res.status, return_counts=True)
+    print('solve status over %d solves: ' % res.status.size + ', '.join('%s %d' % (names.get(int(c), str(int(c))), n) for c, n in zip(codes, counts)))
+    sat = (res.u <= 1e-6) | (res.u >= 1500.0 - 1e-6)
+    print('input outside (0, 1500) on %.1f%% of the steps (the loop does not clip: the reference does not)' % (100 * sat.any(axis=2).mean()))
+
+
+if __name__ == '__main__':
+    main()

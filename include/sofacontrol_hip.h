@@ -554,6 +554,10 @@ int sgusto_plan_variant(const sgusto_plan_t *plan, int *split, int *n_u_fixed, i
  * SCP step, gusto.py:340-370; +inf for a rollout that never accepted a step): J (batch).  What a sharded batch gathers to
  * pick its best rollout (distributed.gather_rollout_costs).  Waits for the solve. */
 int sgusto_plan_costs(sgusto_plan_t *plan, double *J);
+/* The same costs copied device-to-device into J_dev (batch) on `stream`, behind the solve enqueued there: no host wait. */
+int sgusto_plan_costs_dev(sgusto_plan_t *plan, double *J_dev, void *stream);
+/* The shapes a plan was created with (any output may be NULL); has_Qzf = 1 when the problem has a terminal cost (zf is read). */
+int sgusto_plan_dims(const sgusto_plan_t *plan, int *N, int *n_x, int *n_u, int *n_z, int64_t *batch, double *dt, int *has_Qzf);
 /* srh_kernel_info of a GuSTO plan (see slocp_plan_info). */
 int sgusto_plan_info(sgusto_plan_t *plan, srh_kernel_info *info);
 /* QPs of the plan's LAST solve that the lean kernel condensed by the single-region recursion (every stage of the horizon in
@@ -583,6 +587,57 @@ int sgusto_plan_solve_end(sgusto_plan_t *plan, double *xopt, double *uopt, doubl
  * to the last device-to-host copy on the plan's stream (HIP events) -- the solver's own time, what the reference reports
  * as its solve time (scp/ros.py:116-124), independent of when the caller came back for the result; -1 before the first. */
 int sgusto_plan_last_async_ms(sgusto_plan_t *plan, double *ms);
+
+/* Batched closed loop on a resident TPWL GuSTO plan (csrc/gusto_loop.hip): every rollout b of the plan's batch is its own
+ * receding-horizon loop -- plan, apply n_keep inputs to a TPWL plant discretised at dt_sim, shift, re-plan from the plant state
+ * (the reference's `mpc=True` policy, tpwl/controllers.py:269-274, with perfect state feedback) -- and nothing but the run's
+ * records crosses PCIe.  Period k (k counts from the last reset; t_k = t_start + k (n_keep dt_sim)):
+ *   x0      = the plant state
+ *   guess   k = 0: u_init = 0, x_init = the zero-input rollout of the PLANNER's model from x0 (scp/standalone.py:32-33);
+ *           k > 0: the previous xopt / uopt from row idx0 on, their last row held over the rest (scp/ros.py:110-114), idx0 = the
+ *           first j with t_{k-1} + dt j >= t_k
+ *   target  z[b][j] = the installed table (t, z) interpolated linearly at (t_k + phase[b]) + dt j, j = 0..N, clamped to its first /
+ *           last row outside the table (standalone.py:29); zf = z[b][N] when the plan has a terminal cost; u_des alike on rows 0..N-1
+ *   solve   sgusto_plan_solve_dev; a rollout that ends with status 1 / 2 / 3 goes on with what the kernel returned
+ *   advance for s = 0..n_keep-1, tau = s dt_sim, j = min((int)(tau / dt), N - 1), theta = (tau - j dt) / dt:
+ *           x_bar = xopt[j] + theta (xopt[j+1] - xopt[j]); u_bar the same on [uopt ; uopt[N-1]] (controllers.py:299);
+ *           u = u_bar + K[i] (x - x_bar), i = nearest point of the PLANNER's table at x_bar (controllers.py:330-331), or u = u_bar
+ *           without gains;  x <- A_d[p] x + B_d[p] u + d_d[p] (+ w), p = nearest point of the PLANT's table at x;  z = H x, H the
+ *           planner model's output map (as zopt = H xopt, gusto.py:486).
+ * The schedule (t_k, idx0, j, theta) is the same for every rollout and is computed on the host in double precision
+ * (sgusto_loop_schedule: host arithmetic only).  f64 throughout; n_x <= 128, n_u <= 16.  The plan and both models must outlive the
+ * loop; the plan's iteration cap is the one in force when sgusto_loop_run is called.
+ * create refuses n_keep dt_sim > N dt (the shift would find no row), a plant of other dimensions or without discrete tables, and a
+ * planner model without an output map of the plan's n_z.  max_steps_per_run bounds periods * n_keep of one run (the pinned record
+ * blocks are sized by it). */
+typedef struct sgusto_loop sgusto_loop_t;
+int sgusto_loop_create(sgusto_loop_t **out, sgusto_plan_t *plan, stpwl_t *planner_model, stpwl_t *plant, double dt_sim, int n_keep,
+                       int64_t max_steps_per_run);
+int sgusto_loop_destroy(sgusto_loop_t *h);
+/* t (T, increasing), z (T x n_z), u_des (T x n_u) or NULL, phase (batch) or NULL = zeros */
+int sgusto_loop_set_target(sgusto_loop_t *h, int T, const double *t, const double *z, const double *u_des, const double *phase);
+int sgusto_loop_set_feedback(sgusto_loop_t *h, const double *K);          /* P x n_u x n_x of the planner's points; NULL: none */
+int sgusto_loop_reset(sgusto_loop_t *h, const double *x0, double t_start);        /* x0 (batch x n_x) */
+/* `periods` periods enqueued on the handle's own stream, the records copied back once, ONE blocking wait.  W (periods x n_keep x
+ * batch x n_x) or NULL: added to the plant's next state, uploaded once.  With S = periods n_keep: X_cl (batch x (S + 1) x n_x) or
+ * NULL, Z_cl (batch x (S + 1) x n_z), U_cl (batch x S x n_u), row 0 = the state the run started from; iters, status, J
+ * (periods x batch).  A following run continues: time, plant states, previous plan. */
+int sgusto_loop_run(sgusto_loop_t *h, int periods, const double *W, double *X_cl, double *Z_cl, double *U_cl, int32_t *iters,
+                    int32_t *status, double *J);
+/* The solver inputs / the plan of the last period (any may be NULL; zf, u_des are left alone when the loop has none). */
+int sgusto_loop_last_inputs(sgusto_loop_t *h, double *x0, double *u_init, double *x_init, double *z, double *zf, double *u_des);
+int sgusto_loop_last_plan(sgusto_loop_t *h, double *xopt, double *uopt);
+/* The advance kernel alone -- the launch sgusto_loop_run makes -- on host-supplied plans: xopt (batch x (N+1) x n_x), uopt (batch x N
+ * x n_u), x (batch x n_x), W (n_keep x batch x n_x) or NULL -> X (batch x n_keep x n_x), Z (batch x n_keep x n_z), U (batch x n_keep
+ * x n_u), and the points picked at every sub-step, idx_plant / idx_gain (batch x n_keep; idx_gain = -1 without gains; either may be
+ * NULL).  The loop's own state is not touched. */
+int sgusto_loop_advance(sgusto_loop_t *h, const double *xopt, const double *uopt, const double *x, const double *W, double *X,
+                        double *Z, double *U, int32_t *idx_plant, int32_t *idx_gain);
+/* periods run since the last reset, and the blocking host waits of the last run */
+int sgusto_loop_stats(sgusto_loop_t *h, int64_t *steps, int64_t *waits_last_run);
+/* The schedule of period k (no GPU): *t_k, *idx0 (0 for k = 0), j (n_keep), theta (n_keep).  Any output may be NULL. */
+int sgusto_loop_schedule(int N, double dt, double dt_sim, int n_keep, double t_start, int64_t k, double *t_k, int *idx0, int32_t *j,
+                         double *theta);
 
 /* =====================================================================================================
  * Koopman baseline. reference: sofacontrol/baselines/koopman/koopman_utils.py, koopman/koopman.py, baselines/ros.py:139-235

@@ -532,6 +532,26 @@ int sgusto_plan_costs(sgusto_plan_t *pl, double *J) {
     return pl->Jopt.download(J, sizeof(double) * pl->batch);
 }
 
+int sgusto_plan_costs_dev(sgusto_plan_t *pl, double *J_dev, void *stream) {
+    SRH_REQUIRE(pl && J_dev, "sgusto_plan_costs_dev: null argument");
+    SRH_REQUIRE(pl->solved, "sgusto_plan_costs_dev: no solve yet");
+    SRH_CHECK_HIP(hipMemcpyAsync(J_dev, pl->Jopt.p, sizeof(double) * pl->batch, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return SRH_OK;
+}
+
+int sgusto_plan_dims(const sgusto_plan_t *pl, int *N, int *n_x, int *n_u, int *n_z, int64_t *batch, double *dt, int *has_Qzf) {
+    SRH_REQUIRE(pl, "sgusto_plan_dims: null plan");
+    const QPDims &d = pl->C.dims;
+    if (N) *N = d.N;
+    if (n_x) *n_x = d.n;
+    if (n_u) *n_u = d.m;
+    if (n_z) *n_z = d.nz;
+    if (batch) *batch = pl->batch;
+    if (dt) *dt = pl->par.dt;
+    if (has_Qzf) *has_Qzf = pl->C.Qzf.p != nullptr ? 1 : 0;
+    return SRH_OK;
+}
+
 int sgusto_plan_info(sgusto_plan_t *pl, srh_kernel_info *info) {
     SRH_REQUIRE(pl && info, "sgusto_plan_info: null argument");
     SRH_REQUIRE(!pl->pending, "sgusto_plan_info: an asynchronous request is in flight on this plan (call sgusto_plan_solve_end first)");

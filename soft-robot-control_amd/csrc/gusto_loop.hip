@@ -1,0 +1,547 @@
+// Batched closed loop on a resident TPWL GuSTO plan: every rollout of the plan's batch is its own receding-horizon loop -- plan, apply
+// n_keep inputs to a TPWL plant, shift, re-plan from the plant state -- and a whole run of periods is one launch sequence on the handle's
+// stream with one host wait.  Reference: sofacontrol/scp/standalone.py:29-33 (targets, first guess), scp/ros.py:109-114 (shift),
+// tpwl/controllers.py:298-333 (the scp controller's interpolated plan and feedback law), tpwl/tpwl.py:160-168, 336-339 (plant step).
+// The solve itself is sgusto_plan_solve_dev (gusto.hip); this unit is the glue around it: loop_prepare_kernel turns the previous
+// period's output into the next solve's input, loop_advance_kernel runs the plant under the feedback law for the n_keep sub-steps.
+#include "tpwl_host.h"
+
+namespace {
+
+typedef double loop_d2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ void panel_copy16(lptr dst, cgptr src, int count) {            // count even, both 16-byte aligned
+    auto d2 = (__attribute__((address_space(3))) loop_d2 *)dst;
+    auto s2 = (const __attribute__((address_space(1))) loop_d2 *)src;
+    for (int e = threadIdx.x; e < (count >> 1); e += blockDim.x) d2[e] = s2[e];
+}
+
+// Row `a` of the table (tt (T), ty (T x ld)) at tq: scipy's interp1d(kind='linear', bounds_error=False, fill_value=(y[0], y[-1])) --
+// i = searchsorted(tt, tq) (first tt[i] >= tq) clipped to 1..T-1, slope (y[i] - y[i-1]) / (tt[i] - tt[i-1]), slope (tq - tt[i-1]) + y[i-1];
+// the first / last row outside the table.  A tq that is not a number picks i = 1 and gives not-a-number: no index leaves the table.
+__device__ __forceinline__ double table_at(cgptr tt, cgptr ty, int T, int ld, int a, double tq) {
+    if (tq < tt[0]) return ty[a];
+    if (tq > tt[T - 1]) return ty[(size_t)(T - 1) * ld + a];
+    int lo = 0, hi = T;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (tt[mid] < tq) lo = mid + 1; else hi = mid;
+    }
+    const int i = min(max(lo, 1), T - 1);
+    const double t0 = tt[i - 1], y0 = ty[(size_t)(i - 1) * ld + a];
+    const double slope = (ty[(size_t)i * ld + a] - y0) / (tt[i] - t0);
+    return slope * (tq - t0) + y0;
+}
+
+// t0 + dt k with the product and the sum rounded on their own (no fused multiply-add): numpy's statement of the query times
+__device__ __forceinline__ double query_time(double t0, double dt, int k) {
+#pragma clang fp contract(off)
+    const double s = dt * (double)k;
+    return t0 + s;
+}
+
+struct PrepArgs {
+    int N, n, m, nz, T;
+    int first, idx0;                    // first period after a reset: no shift (the guess is the planner's zero-input rollout)
+    double tk, dt;
+    const double *xcur, *xopt, *uopt;   // plant states (B x n), previous plan
+    const double *tt, *tz, *tu, *phase; // target table (tz / tu / phase may be null)
+    const double *H;                    // (nz x n) of the planner's model
+    double *x0, *x_init, *u_init, *z, *zf, *ud;
+    double *Xrec, *Zrec;                // row 0 of the run's records (null: not this period / not wanted)
+    int64_t rec_rows;                   // rows per rollout of Xrec / Zrec
+};
+
+// one workgroup per rollout: x0 <- plant state, the shifted guess, the target window
+__global__ __launch_bounds__(256) void loop_prepare_kernel(PrepArgs a) {
+    const size_t b = blockIdx.x;
+    const int N = a.N, n = a.n, m = a.m, nz = a.nz, tid = threadIdx.x;
+    cgptr xc = (cgptr)a.xcur + b * n;
+    gptr x0 = (gptr)a.x0 + b * n;
+    for (int e = tid; e < n; e += 256) {
+        const double v = xc[e];
+        x0[e] = v;
+        if (a.Xrec) ((gptr)a.Xrec)[b * (size_t)a.rec_rows * n + e] = v;
+    }
+    if (a.Zrec) {
+        cgptr H = (cgptr)a.H;
+        for (int e = tid; e < nz; e += 256) {
+            double v = 0.0;
+            for (int c = 0; c < n; ++c) v = fma(H[e * n + c], xc[c], v);
+            ((gptr)a.Zrec)[b * (size_t)a.rec_rows * nz + e] = v;
+        }
+    }
+    if (!a.first) {
+        // rows idx0.. of the previous plan move to the front, its last row is held over the rest (ros.py:110-114)
+        cgptr xo = (cgptr)a.xopt + b * (size_t)(N + 1) * n, uo = (cgptr)a.uopt + b * (size_t)N * m;
+        gptr xi = (gptr)a.x_init + b * (size_t)(N + 1) * n, ui = (gptr)a.u_init + b * (size_t)N * m;
+        for (int e = tid; e < (N + 1) * n; e += 256) {
+            const int k = e / n, c = e - k * n;
+            xi[e] = xo[(size_t)min(k + a.idx0, N) * n + c];
+        }
+        for (int e = tid; e < N * m; e += 256) {
+            const int k = e / m, c = e - k * m;
+            ui[e] = uo[(size_t)min(k + a.idx0, N - 1) * m + c];
+        }
+    }
+    if (a.tz || a.tu) {
+        const double t0 = a.tk + (a.phase ? ((cgptr)a.phase)[b] : 0.0);
+        cgptr tt = (cgptr)a.tt;
+        if (a.tz) {
+            gptr z = (gptr)a.z + b * (size_t)(N + 1) * nz;
+            for (int e = tid; e < (N + 1) * nz; e += 256) {
+                const int k = e / nz, c = e - k * nz;
+                const double v = table_at(tt, (cgptr)a.tz, a.T, nz, c, query_time(t0, a.dt, k));
+                z[e] = v;
+                if (a.zf && k == N) ((gptr)a.zf)[b * nz + c] = v;
+            }
+        }
+        if (a.tu) {
+            gptr ud = (gptr)a.ud + b * (size_t)N * m;
+            for (int e = tid; e < N * m; e += 256) {
+                const int k = e / m, c = e - k * m;
+                ud[e] = table_at(tt, (cgptr)a.tu, a.T, m, c, query_time(t0, a.dt, k));
+            }
+        }
+    }
+}
+
+struct AdvArgs {
+    int N, n_keep, nz;
+    const double *xopt, *uopt;          // the plans (B x (N+1) x n), (B x N x m)
+    const double *K;                    // (P x m x n) gains at the planner's points, or null
+    const double *H;                    // (nz x n)
+    const double *W;                    // (steps x B x n) disturbances, or null; this launch reads steps w_step0 ..
+    const int32_t *js;                  // (n_keep) plan interval of every sub-step
+    const double *theta;                // (n_keep) position inside it
+    const double *x_in;                 // (B x n)
+    double *x_out;                      // (B x n) or null (may be x_in)
+    double *X, *Z, *U;                  // records: row row0 + s of rollout b (X may be null)
+    int32_t *ip, *ig;                   // (B x n_keep) points picked, or null
+    int64_t rows_x, row0_x, rows_u, row0_u, B, w_step0;
+};
+
+// One workgroup per rollout, all n_keep sub-steps.  The plant's region panel [A_d^T | B_d^T | d_d] sits in LDS and is reloaded only when
+// the plant's nearest point changes (as rollout_staged_kernel, tpwl.hip); the state, the plan point x_bar and x - x_bar stay in LDS
+// for the whole launch.  Per sub-step: waves 0-2 interpolate the plan; wave 0 searches the plant's table at x while wave 1 searches the
+// planner's at x_bar (tpwl::nearest_wave both: one tie rule); the four waves form K (x - x_bar) a row each; the products of the step are
+// wg::matTvec's slices (slice s sums rows s, s + S, ... by fma from 0.0; x' = d + partials of A x in slice order + partials of B u).
+__global__ __launch_bounds__(256) void loop_advance_kernel(TpwlDev TP, TpwlDev TL, AdvArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int n = TL.n, m = TL.m, N = a.N, nz = a.nz;
+    lptr xc = (lptr)smem;                                // n      plant state
+    lptr xb = xc + n;                                    // n      x_bar
+    lptr dx = xb + n;                                    // n      x - x_bar
+    lptr ub = dx + n;                                    // 16     u_bar
+    lptr uc = ub + 16;                                   // 16     u
+    lptr pa = uc + 16;                                   // 256    partial sums of A x
+    lptr pb = pa + 256;                                  // 256    partial sums of B u
+    liptr ip = (liptr)(pb + 256);                        // (two doubles) plant point, gain point
+    lptr At = pb + 256 + 2;                              // n x n  the panel of region `cur`: every offset is even (n = 2 r)
+    lptr Bt = At + n * n;                                // m x n
+    lptr dl = Bt + m * n;                                // n
+    const size_t b = blockIdx.x;
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int S = max(1, 256 / n), j = tid % n, sl = tid / n;
+    cgptr xo = (cgptr)a.xopt + b * (size_t)(N + 1) * n, uo = (cgptr)a.uopt + b * (size_t)N * m;
+    cgptr Kt = (cgptr)a.K, H = (cgptr)a.H, Wd = (cgptr)a.W, thg = (cgptr)a.theta, xin = (cgptr)a.x_in;
+    cgiptr jsg = (cgiptr)a.js;
+    for (int e = tid; e < n; e += 256) xc[e] = xin[b * n + e];
+    __syncthreads();
+    int cur = -1;
+    for (int s = 0; s < a.n_keep; ++s) {
+        const int js = jsg[s];
+        const double th = thg[s];
+        if (tid < n) {                                   // (n <= 128: waves 0 and 1)
+            const double lo = xo[(size_t)js * n + tid], hi = xo[(size_t)(js + 1) * n + tid];
+            const double v = lo + th * (hi - lo);
+            xb[tid] = v;
+            dx[tid] = xc[tid] - v;
+        } else if (tid >= 128 && tid < 128 + m) {        // the input is held over the last interval (controllers.py:299)
+            const int e = tid - 128;
+            const double lo = uo[(size_t)js * m + e], hi = uo[(size_t)min(js + 1, N - 1) * m + e];
+            ub[e] = lo + th * (hi - lo);
+        }
+        __syncthreads();
+        if (wave == 0) {
+            const int i = tpwl::nearest_wave(TL, xc);
+            if (lane == 0) ip[0] = (unsigned)i < (unsigned)TL.P ? i : 0;           // (a state that is not a number: no minimum)
+        } else if (wave == 1 && Kt != nullptr) {
+            const int i = tpwl::nearest_wave(TP, xb);
+            if (lane == 0) ip[1] = (unsigned)i < (unsigned)TP.P ? i : 0;
+        }
+        __syncthreads();
+        const int p = ip[0];
+        if (p != cur) {                                  // (the same for every thread; the barrier below covers the copies)
+            panel_copy16(At, TL.AdT + (size_t)p * n * n, n * n);
+            panel_copy16(Bt, TL.BdT + (size_t)p * m * n, m * n);
+            panel_copy16(dl, TL.dd + (size_t)p * n, n);
+            cur = p;
+        }
+        if (Kt != nullptr) {
+            cgptr Kg = Kt + (size_t)ip[1] * m * n;
+            for (int e = wave; e < m; e += 4) {
+                double acc = 0.0;
+                for (int c = lane; c < n; c += 64) acc = fma(Kg[e * n + c], dx[c], acc);
+                acc = wg::wave_sum(acc);
+                if (lane == 0) uc[e] = ub[e] + acc;
+            }
+        } else if (tid < m) {
+            uc[tid] = ub[tid];
+        }
+        __syncthreads();
+        if (sl < S) {
+            double va = 0.0, vb = 0.0;
+#pragma unroll 4
+            for (int q = sl; q < n; q += S) va = fma(At[q * n + j], xc[q], va);
+            for (int q = sl; q < m; q += S) vb = fma(Bt[q * n + j], uc[q], vb);
+            pa[sl * n + j] = va;
+            pb[sl * n + j] = vb;
+        }
+        __syncthreads();
+        if (tid < n) {
+            double v = dl[tid];
+            for (int q = 0; q < S; ++q) v += pa[q * n + tid];
+            for (int q = 0; q < S; ++q) v += pb[q * n + tid];
+            if (Wd != nullptr) v += Wd[((size_t)(a.w_step0 + s) * a.B + b) * n + tid];
+            xc[tid] = v;
+            if (a.X) ((gptr)a.X)[(b * (size_t)a.rows_x + a.row0_x + s) * n + tid] = v;
+        } else if (tid >= 128 && tid < 128 + m) {
+            ((gptr)a.U)[(b * (size_t)a.rows_u + a.row0_u + s) * m + (tid - 128)] = uc[tid - 128];
+        } else if (tid == 255) {
+            if (a.ip) a.ip[b * a.n_keep + s] = p;
+            if (a.ig) a.ig[b * a.n_keep + s] = Kt != nullptr ? ip[1] : -1;
+        }
+        __syncthreads();
+        // z = H x, the sum of gusto_write_out (zopt = H xopt).  xc is next written behind two barriers of the next sub-step.
+        for (int e = tid; e < nz; e += 256) {
+            double v = 0.0;
+            for (int c = 0; c < n; ++c) v = fma(H[e * n + c], xc[c], v);
+            ((gptr)a.Z)[(b * (size_t)a.rows_x + a.row0_x + s) * nz + e] = v;
+        }
+    }
+    if (a.x_out)
+        for (int e = tid; e < n; e += 256) ((gptr)a.x_out)[b * n + e] = xc[e];
+}
+
+size_t advance_lds_bytes(int n, int m) {
+    return srh::lds_request(sizeof(double) * ((size_t)3 * n + 16 + 16 + 256 + 256 + 2 + (size_t)n * n + (size_t)m * n + n));
+}
+
+struct PinBuf {
+    char *p = nullptr;
+    size_t cap = 0;
+    ~PinBuf() { if (p) (void)hipHostFree(p); }
+    int need(size_t bytes) {
+        if (bytes <= cap) return SRH_OK;
+        if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
+        SRH_CHECK_HIP(hipHostMalloc((void **)&p, bytes, hipHostMallocDefault));
+        cap = bytes;
+        return SRH_OK;
+    }
+};
+
+}  // namespace
+
+struct sgusto_loop {
+    sgusto_plan_t *plan = nullptr;
+    stpwl *planner = nullptr, *plant = nullptr;
+    int N = 0, n = 0, m = 0, nz = 0, n_keep = 0, T = 0;
+    int64_t B = 0, max_steps = 0;
+    double dt = 0.0, dt_sim = 0.0, t_start = 0.0;
+    bool has_Qzf = false, has_z = false, has_ud = false, has_phase = false, has_K = false, have_state = false;
+    int64_t k = 0;                      // periods since the last reset
+    int64_t waits = 0;                  // blocking host waits of the last run
+    size_t lds = 0;
+    hipStream_t stream = nullptr;
+    srh::DevBuf x0, u_init, x_init, z, zf, ud, xopt, uopt, zopt, xcur, tt, tz, tu, phase, K, js, theta;
+    srh::DevBuf Xrec, Zrec, Urec, Irec, Srec, Jrec, Wd;
+    PinBuf pX, pZ, pU, pI, pS, pJ, pW;
+    ~sgusto_loop() {
+        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+    }
+    AdvArgs adv_args() const {
+        AdvArgs a{};
+        a.N = N; a.n_keep = n_keep; a.nz = nz;
+        a.K = has_K ? K.as<double>() : nullptr;
+        a.H = planner->H.as<double>();
+        a.js = js.as<int32_t>(); a.theta = theta.as<double>();
+        a.B = B;
+        return a;
+    }
+    int launch_advance(const AdvArgs &a) const {
+        loop_advance_kernel<<<(unsigned)B, 256, lds, stream>>>(planner->view(), plant->view(), a);
+        SRH_CHECK_HIP(hipGetLastError());
+        return SRH_OK;
+    }
+};
+
+extern "C" {
+
+int sgusto_loop_schedule(int N, double dt, double dt_sim, int n_keep, double t_start, int64_t k, double *t_k, int *idx0, int32_t *j,
+                         double *theta) {
+#pragma clang fp contract(off)          // every product and sum rounded on its own, as the numpy statement of the schedule
+    SRH_REQUIRE(N >= 1 && dt > 0.0 && dt_sim > 0.0 && n_keep >= 1 && k >= 0, "sgusto_loop_schedule: bad argument");
+    const double step = (double)n_keep * dt_sim;
+    const double tk = t_start + (double)k * step;
+    if (t_k) *t_k = tk;
+    if (idx0) {
+        *idx0 = 0;
+        if (k > 0) {
+            // (at n_keep dt_sim == N dt the two sums may round an ulp apart and no row reaches t_k: the last row is held throughout)
+            const double tp = t_start + (double)(k - 1) * step;
+            int i0 = N;
+            for (int i = 0; i <= N; ++i) {
+                const double ti = tp + dt * (double)i;
+                if (ti >= tk) { i0 = i; break; }
+            }
+            *idx0 = i0;
+        }
+    }
+    for (int s = 0; s < n_keep; ++s) {
+        const double tau = (double)s * dt_sim;
+        const double q = tau / dt;
+        const int js = std::min((int)q, N - 1);
+        if (j) j[s] = js;
+        if (theta) {
+            const double back = (double)js * dt;
+            theta[s] = (tau - back) / dt;
+        }
+    }
+    return SRH_OK;
+}
+
+int sgusto_loop_create(sgusto_loop_t **out, sgusto_plan_t *plan, stpwl_t *planner_model, stpwl_t *plant, double dt_sim, int n_keep,
+                       int64_t max_steps_per_run) {
+    SRH_REQUIRE(out && plan && planner_model && plant, "sgusto_loop_create: null argument");
+    int N, n, m, nz, has_Qzf;
+    int64_t B;
+    double dt;
+    int rc = sgusto_plan_dims(plan, &N, &n, &m, &nz, &B, &dt, &has_Qzf);
+    if (rc) return rc;
+    SRH_REQUIRE(n <= 128 && m <= 16, "sgusto_loop_create: n_x = %d, n_u = %d exceed the limits n_x <= 128, n_u <= 16", n, m);
+    SRH_REQUIRE(planner_model->n == n && planner_model->m == m && planner_model->has_discrete,
+                "sgusto_loop_create: the planner's model (n_x = %d, n_u = %d) is not the pre-discretised model of the plan (n_x = %d, n_u = %d)",
+                planner_model->n, planner_model->m, n, m);
+    SRH_REQUIRE(planner_model->nz == nz && planner_model->H.p, "sgusto_loop_create: the planner's model has no output map of the plan's n_z = %d", nz);
+    SRH_REQUIRE(plant->n == n && plant->m == m, "sgusto_loop_create: the plant has n_x = %d, n_u = %d, the plan n_x = %d, n_u = %d",
+                plant->n, plant->m, n, m);
+    SRH_REQUIRE(plant->has_discrete, "sgusto_loop_create: the plant has not been pre-discretised at dt_sim");
+    SRH_REQUIRE(dt_sim > 0.0 && n_keep >= 1, "sgusto_loop_create: need dt_sim > 0 and n_keep >= 1");
+    SRH_REQUIRE(!((double)n_keep * dt_sim > (double)N * dt),
+                "sgusto_loop_create: n_keep * dt_sim = %g exceeds the horizon N * dt = %g (the shift of the previous plan would find no row)",
+                (double)n_keep * dt_sim, (double)N * dt);
+    SRH_REQUIRE(max_steps_per_run >= n_keep, "sgusto_loop_create: max_steps_per_run = %lld is below n_keep = %d", (long long)max_steps_per_run, n_keep);
+    sgusto_loop *h = new sgusto_loop();
+    h->plan = plan; h->planner = planner_model; h->plant = plant;
+    h->N = N; h->n = n; h->m = m; h->nz = nz; h->n_keep = n_keep; h->B = B; h->max_steps = max_steps_per_run;
+    h->dt = dt; h->dt_sim = dt_sim; h->has_Qzf = has_Qzf != 0;
+    h->lds = advance_lds_bytes(n, m);
+    std::vector<int32_t> js(n_keep);
+    std::vector<double> th(n_keep);
+    (void)sgusto_loop_schedule(N, dt, dt_sim, n_keep, 0.0, 0, nullptr, nullptr, js.data(), th.data());
+    const size_t D = sizeof(double), S = (size_t)max_steps_per_run, P = S / n_keep, Bz = (size_t)B;
+    auto fail = [&](int code) { delete h; return code; };
+    if (h->lds > (size_t)160 * 1024) {
+        srh::set_error("sgusto_loop_create: the advance kernel needs %zu bytes of LDS (160 KiB available)", h->lds);
+        return fail(SRH_EINVAL);
+    }
+    if (hipFuncSetAttribute((const void *)loop_advance_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds) != hipSuccess ||
+        hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
+        srh::set_error("sgusto_loop_create: could not set up the advance kernel / the stream: %s", hipGetErrorString(hipGetLastError()));
+        return fail(SRH_EHIP);
+    }
+    if ((rc = h->x0.alloc(D * Bz * n)) || (rc = h->u_init.alloc(D * Bz * N * m)) || (rc = h->x_init.alloc(D * Bz * (N + 1) * n)) ||
+        (rc = h->z.alloc(D * Bz * (N + 1) * nz)) || (rc = h->zf.alloc(D * Bz * nz)) || (rc = h->ud.alloc(D * Bz * N * m)) ||
+        (rc = h->xopt.alloc(D * Bz * (N + 1) * n)) || (rc = h->uopt.alloc(D * Bz * N * m)) || (rc = h->zopt.alloc(D * Bz * (N + 1) * nz)) ||
+        (rc = h->xcur.alloc(D * Bz * n)) || (rc = h->js.upload(js.data(), sizeof(int32_t) * n_keep)) ||
+        (rc = h->theta.upload(th.data(), D * n_keep)) || (rc = h->Zrec.alloc(D * Bz * (S + 1) * nz)) || (rc = h->Urec.alloc(D * Bz * S * m)) ||
+        (rc = h->Irec.alloc(sizeof(int32_t) * P * Bz)) || (rc = h->Srec.alloc(sizeof(int32_t) * P * Bz)) || (rc = h->Jrec.alloc(D * P * Bz)) ||
+        (rc = h->pZ.need(D * Bz * (S + 1) * nz)) || (rc = h->pU.need(D * Bz * S * m)) || (rc = h->pI.need(sizeof(int32_t) * P * Bz)) ||
+        (rc = h->pS.need(sizeof(int32_t) * P * Bz)) || (rc = h->pJ.need(D * P * Bz)))
+        return fail(rc);
+    *out = h;
+    return SRH_OK;
+}
+
+int sgusto_loop_destroy(sgusto_loop_t *h) {
+    delete h;
+    return SRH_OK;
+}
+
+int sgusto_loop_set_target(sgusto_loop_t *h, int T, const double *t, const double *z, const double *u_des, const double *phase) {
+    SRH_REQUIRE(h && t && (z || u_des), "sgusto_loop_set_target: null argument");
+    SRH_REQUIRE(T >= 2, "sgusto_loop_set_target: the table needs at least two rows");
+    for (int i = 1; i < T; ++i) SRH_REQUIRE(t[i] > t[i - 1], "sgusto_loop_set_target: t must increase (row %d)", i);
+    SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
+    int rc;
+    if ((rc = h->tt.upload(t, sizeof(double) * T))) return rc;
+    if (z && (rc = h->tz.upload(z, sizeof(double) * T * h->nz))) return rc;
+    if (u_des && (rc = h->tu.upload(u_des, sizeof(double) * T * h->m))) return rc;
+    if (phase && (rc = h->phase.upload(phase, sizeof(double) * h->B))) return rc;
+    h->T = T; h->has_z = z != nullptr; h->has_ud = u_des != nullptr; h->has_phase = phase != nullptr;
+    return SRH_OK;
+}
+
+int sgusto_loop_set_feedback(sgusto_loop_t *h, const double *K) {
+    SRH_REQUIRE(h, "sgusto_loop_set_feedback: null handle");
+    SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
+    h->has_K = false;
+    if (!K) return SRH_OK;
+    int rc = h->K.upload(K, sizeof(double) * h->planner->P * h->m * h->n);
+    if (rc) return rc;
+    h->has_K = true;
+    return SRH_OK;
+}
+
+int sgusto_loop_reset(sgusto_loop_t *h, const double *x0, double t_start) {
+    SRH_REQUIRE(h && x0, "sgusto_loop_reset: null argument");
+    SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
+    SRH_CHECK_HIP(hipMemcpy(h->xcur.p, x0, sizeof(double) * h->B * h->n, hipMemcpyHostToDevice));
+    h->t_start = t_start; h->k = 0; h->have_state = true;
+    return SRH_OK;
+}
+
+int sgusto_loop_run(sgusto_loop_t *h, int periods, const double *W, double *X_cl, double *Z_cl, double *U_cl, int32_t *iters,
+                    int32_t *status, double *J) {
+    SRH_REQUIRE(h && Z_cl && U_cl && iters && status && J, "sgusto_loop_run: null argument");
+    SRH_REQUIRE(periods >= 1, "sgusto_loop_run: periods must be positive");
+    SRH_REQUIRE(h->have_state, "sgusto_loop_run: no plant state yet (call sgusto_loop_reset first)");
+    const int N = h->N, n = h->n, m = h->m, nz = h->nz, nk = h->n_keep;
+    const size_t D = sizeof(double), B = (size_t)h->B, S = (size_t)periods * nk;
+    SRH_REQUIRE((int64_t)S <= h->max_steps, "sgusto_loop_run: periods * n_keep = %lld exceeds max_steps_per_run = %lld", (long long)S,
+                (long long)h->max_steps);
+    int rc;
+    if (X_cl && ((rc = h->pX.need(D * B * (h->max_steps + 1) * n)) || (!h->Xrec.p && (rc = h->Xrec.alloc(D * B * (h->max_steps + 1) * n))))) return rc;
+    if (W && ((rc = h->pW.need(D * h->max_steps * B * n)) || (!h->Wd.p && (rc = h->Wd.alloc(D * h->max_steps * B * n))))) return rc;
+    h->waits = 0;
+    hipStream_t st = h->stream;
+    // from here on work is enqueued on the handle's stream: on any error it is drained before returning
+    auto body = [&]() -> int {
+        if (W) {
+            memcpy(h->pW.p, W, D * S * B * n);
+            SRH_CHECK_HIP(hipMemcpyAsync(h->Wd.p, h->pW.p, D * S * B * n, hipMemcpyHostToDevice, st));
+        }
+        for (int p = 0; p < periods; ++p) {
+            const int64_t k = h->k + p;
+            PrepArgs a{};
+            a.N = N; a.n = n; a.m = m; a.nz = nz; a.T = h->T;
+            a.first = k == 0 ? 1 : 0;
+            a.dt = h->dt;
+            (void)sgusto_loop_schedule(N, h->dt, h->dt_sim, nk, h->t_start, k, &a.tk, &a.idx0, nullptr, nullptr);
+            a.xcur = h->xcur.as<double>(); a.xopt = h->xopt.as<double>(); a.uopt = h->uopt.as<double>();
+            a.tt = h->tt.as<double>();
+            a.tz = h->has_z ? h->tz.as<double>() : nullptr;
+            a.tu = h->has_ud ? h->tu.as<double>() : nullptr;
+            a.phase = h->has_phase ? h->phase.as<double>() : nullptr;
+            a.H = h->planner->H.as<double>();
+            a.x0 = h->x0.as<double>(); a.x_init = h->x_init.as<double>(); a.u_init = h->u_init.as<double>();
+            a.z = h->z.as<double>(); a.zf = (h->has_z && h->has_Qzf) ? h->zf.as<double>() : nullptr; a.ud = h->ud.as<double>();
+            a.Xrec = (p == 0 && X_cl) ? h->Xrec.as<double>() : nullptr;
+            a.Zrec = p == 0 ? h->Zrec.as<double>() : nullptr;
+            a.rec_rows = (int64_t)S + 1;
+            if (a.first) SRH_CHECK_HIP(hipMemsetAsync(h->u_init.p, 0, D * B * N * m, st));
+            loop_prepare_kernel<<<(unsigned)B, 256, 0, st>>>(a);
+            SRH_CHECK_HIP(hipGetLastError());
+            // scp/standalone.py:32-33: the first guess is the planner's own zero-input rollout from x0
+            if (a.first && (rc = stpwl_rollout_dev(h->planner, a.x0, a.u_init, N, (int64_t)B, a.x_init, nullptr, (void *)st))) return rc;
+            if ((rc = sgusto_plan_solve_dev(h->plan, a.x0, a.u_init, a.x_init, h->has_z ? a.z : nullptr, a.zf, h->has_ud ? a.ud : nullptr,
+                                            h->xopt.as<double>(), h->uopt.as<double>(), h->zopt.as<double>(), h->Irec.as<int32_t>() + p * B,
+                                            h->Srec.as<int32_t>() + p * B, nullptr, (void *)st)) ||
+                (rc = sgusto_plan_costs_dev(h->plan, h->Jrec.as<double>() + p * B, (void *)st)))
+                return rc;
+            AdvArgs v = h->adv_args();
+            v.xopt = a.xopt; v.uopt = a.uopt;
+            v.W = W ? h->Wd.as<double>() : nullptr; v.w_step0 = (int64_t)p * nk;
+            v.x_in = h->xcur.as<double>(); v.x_out = h->xcur.as<double>();
+            v.X = X_cl ? h->Xrec.as<double>() : nullptr; v.Z = h->Zrec.as<double>(); v.U = h->Urec.as<double>();
+            v.rows_x = (int64_t)S + 1; v.row0_x = (int64_t)p * nk + 1; v.rows_u = (int64_t)S; v.row0_u = (int64_t)p * nk;
+            if ((rc = h->launch_advance(v))) return rc;
+        }
+        if (X_cl) SRH_CHECK_HIP(hipMemcpyAsync(h->pX.p, h->Xrec.p, D * B * (S + 1) * n, hipMemcpyDeviceToHost, st));
+        SRH_CHECK_HIP(hipMemcpyAsync(h->pZ.p, h->Zrec.p, D * B * (S + 1) * nz, hipMemcpyDeviceToHost, st));
+        SRH_CHECK_HIP(hipMemcpyAsync(h->pU.p, h->Urec.p, D * B * S * m, hipMemcpyDeviceToHost, st));
+        SRH_CHECK_HIP(hipMemcpyAsync(h->pI.p, h->Irec.p, sizeof(int32_t) * periods * B, hipMemcpyDeviceToHost, st));
+        SRH_CHECK_HIP(hipMemcpyAsync(h->pS.p, h->Srec.p, sizeof(int32_t) * periods * B, hipMemcpyDeviceToHost, st));
+        SRH_CHECK_HIP(hipMemcpyAsync(h->pJ.p, h->Jrec.p, D * periods * B, hipMemcpyDeviceToHost, st));
+        h->waits += 1;
+        SRH_CHECK_HIP(hipStreamSynchronize(st));
+        return SRH_OK;
+    };
+    if ((rc = body())) {
+        (void)hipStreamSynchronize(st);
+        h->have_state = false;          // part of a run was enqueued: the state is not the one the caller knows
+        return rc;
+    }
+    if (X_cl) memcpy(X_cl, h->pX.p, D * B * (S + 1) * n);
+    memcpy(Z_cl, h->pZ.p, D * B * (S + 1) * nz);
+    memcpy(U_cl, h->pU.p, D * B * S * m);
+    memcpy(iters, h->pI.p, sizeof(int32_t) * periods * B);
+    memcpy(status, h->pS.p, sizeof(int32_t) * periods * B);
+    memcpy(J, h->pJ.p, D * periods * B);
+    h->k += periods;
+    return SRH_OK;
+}
+
+int sgusto_loop_last_inputs(sgusto_loop_t *h, double *x0, double *u_init, double *x_init, double *z, double *zf, double *u_des) {
+    SRH_REQUIRE(h, "sgusto_loop_last_inputs: null handle");
+    SRH_REQUIRE(h->have_state && h->k > 0, "sgusto_loop_last_inputs: no period has run since the last reset");
+    const size_t D = sizeof(double), B = (size_t)h->B, N = h->N, n = h->n, m = h->m, nz = h->nz;
+    SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
+    int rc;
+    if (x0 && (rc = h->x0.download(x0, D * B * n))) return rc;
+    if (u_init && (rc = h->u_init.download(u_init, D * B * N * m))) return rc;
+    if (x_init && (rc = h->x_init.download(x_init, D * B * (N + 1) * n))) return rc;
+    if (z && h->has_z && (rc = h->z.download(z, D * B * (N + 1) * nz))) return rc;
+    if (zf && h->has_z && h->has_Qzf && (rc = h->zf.download(zf, D * B * nz))) return rc;
+    if (u_des && h->has_ud && (rc = h->ud.download(u_des, D * B * N * m))) return rc;
+    return SRH_OK;
+}
+
+int sgusto_loop_last_plan(sgusto_loop_t *h, double *xopt, double *uopt) {
+    SRH_REQUIRE(h, "sgusto_loop_last_plan: null handle");
+    SRH_REQUIRE(h->have_state && h->k > 0, "sgusto_loop_last_plan: no period has run since the last reset");
+    const size_t D = sizeof(double), B = (size_t)h->B, N = h->N;
+    SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
+    int rc;
+    if (xopt && (rc = h->xopt.download(xopt, D * B * (N + 1) * h->n))) return rc;
+    if (uopt && (rc = h->uopt.download(uopt, D * B * N * h->m))) return rc;
+    return SRH_OK;
+}
+
+int sgusto_loop_advance(sgusto_loop_t *h, const double *xopt, const double *uopt, const double *x, const double *W, double *X,
+                        double *Z, double *U, int32_t *idx_plant, int32_t *idx_gain) {
+    SRH_REQUIRE(h && xopt && uopt && x && X && Z && U, "sgusto_loop_advance: null argument");
+    const size_t D = sizeof(double), B = (size_t)h->B, N = h->N, n = h->n, m = h->m, nz = h->nz, nk = h->n_keep;
+    srh::DevBuf dxo, duo, dx, dW, dX, dZ, dU, dp, dg;
+    int rc;
+    if ((rc = dxo.upload(xopt, D * B * (N + 1) * n)) || (rc = duo.upload(uopt, D * B * N * m)) || (rc = dx.upload(x, D * B * n)) ||
+        (W && (rc = dW.upload(W, D * nk * B * n))) || (rc = dX.alloc(D * B * nk * n)) || (rc = dZ.alloc(D * B * nk * nz)) ||
+        (rc = dU.alloc(D * B * nk * m)) || (rc = dp.alloc(sizeof(int32_t) * B * nk)) || (rc = dg.alloc(sizeof(int32_t) * B * nk)))
+        return rc;
+    AdvArgs v = h->adv_args();
+    v.xopt = dxo.as<double>(); v.uopt = duo.as<double>();
+    v.W = W ? dW.as<double>() : nullptr; v.w_step0 = 0;
+    v.x_in = dx.as<double>(); v.x_out = nullptr;
+    v.X = dX.as<double>(); v.Z = dZ.as<double>(); v.U = dU.as<double>();
+    v.ip = dp.as<int32_t>(); v.ig = dg.as<int32_t>();
+    v.rows_x = (int64_t)nk; v.row0_x = 0; v.rows_u = (int64_t)nk; v.row0_u = 0;
+    rc = h->launch_advance(v);
+    // (the temporaries go back to the allocation cache when this returns: wait for the kernel whatever it answered)
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    if (rc) return rc;
+    SRH_CHECK_HIP(e);
+    if ((rc = dX.download(X, D * B * nk * n)) || (rc = dZ.download(Z, D * B * nk * nz)) || (rc = dU.download(U, D * B * nk * m))) return rc;
+    if (idx_plant && (rc = dp.download(idx_plant, sizeof(int32_t) * B * nk))) return rc;
+    if (idx_gain && (rc = dg.download(idx_gain, sizeof(int32_t) * B * nk))) return rc;
+    return SRH_OK;
+}
+
+int sgusto_loop_stats(sgusto_loop_t *h, int64_t *steps, int64_t *waits_last_run) {
+    SRH_REQUIRE(h, "sgusto_loop_stats: null handle");
+    if (steps) *steps = h->k;
+    if (waits_last_run) *waits_last_run = h->waits;
+    return SRH_OK;
+}
+
+}  // extern "C"

@@ -211,3 +211,22 @@ def ipm_rule_replay(phase, rows, par):
     check(lib().sqp_ipm_rule_replay(C.c_int(IPM_PHASES.index(phase)), C.c_int(rows.shape[0]), dptr(rows), dptr(p8), dptr(out), dptr(scal)),
           'sqp_ipm_rule_replay')
     return out, scal
+
+
+def gusto_plan_dims(plan):
+    """sgusto_plan_dims: the shapes a resident GuSTO plan was created with, {'N', 'n_x', 'n_u', 'n_z', 'batch', 'dt', 'has_Qzf'}."""
+    N, n, m, nz, hq = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+    B, dt = C.c_int64(0), C.c_double(0.0)
+    check(lib().sgusto_plan_dims(plan, C.byref(N), C.byref(n), C.byref(m), C.byref(nz), C.byref(B), C.byref(dt), C.byref(hq)),
+          'sgusto_plan_dims')
+    return {'N': N.value, 'n_x': n.value, 'n_u': m.value, 'n_z': nz.value, 'batch': B.value, 'dt': dt.value, 'has_Qzf': bool(hq.value)}
+
+
+def gusto_loop_schedule(N, dt, dt_sim, n_keep, t_start, k):
+    """sgusto_loop_schedule: the schedule of period k of a batched closed loop as the library computes it (csrc/gusto_loop.hip), on the
+    host -- no GPU needed.  Returns (t_k, idx0, j (n_keep, int32), theta (n_keep)); scp.closed_loop.schedule is the numpy statement."""
+    t_k, idx0 = C.c_double(0.0), C.c_int(0)
+    j, theta = np.zeros(n_keep, dtype=np.int32), np.zeros(n_keep)
+    check(lib().sgusto_loop_schedule(C.c_int(N), C.c_double(dt), C.c_double(dt_sim), C.c_int(n_keep), C.c_double(t_start), C.c_int64(k),
+                                     C.byref(t_k), C.byref(idx0), iptr(j), dptr(theta)), 'sgusto_loop_schedule')
+    return t_k.value, idx0.value, j, theta

@@ -1,0 +1,162 @@
+"""Batched closed-loop GuSTO: `batch` receding-horizon loops resident on the device (csrc/gusto_loop.hip).
+
+Every rollout of a resident TPWL `GuSTO(batch=B)` is its own loop -- plan, apply `n_keep` inputs to a TPWL plant pre-discretised at
+`dt_sim` under the scp controller's feedback law u = u_bar(t) + K[i_near(x_bar(t))] (x - x_bar(t)) (tpwl/controllers.py:298-333), shift
+the plan (scp/ros.py:110-114), re-plan from the plant state: the reference's `mpc=True` policy with perfect state feedback.  `run(periods)`
+is one launch sequence on the handle's stream and ONE host wait; only the records of the run cross PCIe.  What is shared by all loops --
+the times of a period -- is computed on the host in float64 (`schedule`)."""
+import collections
+import ctypes as C
+
+import numpy as np
+
+from .. import _lib
+
+Schedule = collections.namedtuple('Schedule', 't_k idx0 j theta')
+
+
+def schedule(N, dt, dt_sim, n_keep, t_start=0.0, k=0):
+    """The schedule of period k, shared by all loops; plain numpy float64 arithmetic, no GPU and no library call.
+    t_k = t_start + k (n_keep dt_sim); idx0 = the first row j of the previous plan's times t_{k-1} + dt arange(N + 1) that is >= t_k
+    (scp/ros.py:109; 0 for k = 0; N when rounding at n_keep dt_sim == N dt leaves no such row, where the reference's argwhere would
+    raise: the last row is then held throughout); for the sub-steps s = 0..n_keep-1 at tau = s dt_sim into the period: the plan
+    interval j = min(int(tau / dt), N - 1) and the position theta = (tau - j dt) / dt inside it."""
+    N, n_keep, k = int(N), int(n_keep), int(k)
+    dt, dt_sim, t_start = float(dt), float(dt_sim), float(t_start)
+    step = n_keep * dt_sim
+    t_k = t_start + k * step
+    idx0 = 0
+    if k > 0:
+        topt_prev = (t_start + (k - 1) * step) + dt * np.arange(N + 1)
+        hits = np.argwhere(topt_prev >= t_k)
+        idx0 = int(hits[0, 0]) if len(hits) else N
+    tau = np.arange(n_keep) * dt_sim
+    j = np.minimum((tau / dt).astype(np.int64), N - 1)
+    theta = (tau - j * dt) / dt
+    return Schedule(t_k, idx0, j, theta)
+
+
+class ClosedLoopResult:
+    """Records of one `run`: x (B, S + 1, n_x) or None, z (B, S + 1, n_z), u (B, S, n_u) with S = periods n_keep (row 0: the state the run
+    started from); iters, status, J (periods, B) of the solves; t (S + 1,) the times of the rows."""
+
+    def __init__(self, x, z, u, iters, status, J, t):
+        self.x, self.z, self.u, self.iters, self.status, self.J, self.t = x, z, u, iters, status, J, t
+
+
+class ClosedLoopBatch:
+    def __init__(self, gusto, plant, dt_sim, n_keep, t=None, z=None, u=None, phase=None, K=None, max_steps_per_run=None):
+        """gusto: a GuSTO on a TPWLGuSTO model with batch=B (the fused resident plan); plant: a TPWLATV (it may be the planner's own
+        dyn_sys), stepped at dt_sim; n_keep: plant steps per period (the reference's N_replan with the controller clock at dt_sim).
+        t (T,), z (T, n_z), u (T, n_u): the target table, interpolated as scp/standalone.py:29-31 does; phase (B,): a time offset of
+        every loop's target; K: the per-point gains of the scp controller (list of (n_u, n_x), or (P, n_u, n_x)), None: u = u_bar.
+        max_steps_per_run: the longest run in plant steps (sizes the record blocks; default 16 periods)."""
+        if not (getattr(gusto, '_fused', False) and not getattr(gusto, '_ssm', False)):
+            raise RuntimeError('ClosedLoopBatch needs a GuSTO on a TPWLGuSTO model with a fused resident plan (not an SSM plan, not '
+                               'the host loop): there is no device rollout / solve to chain otherwise')
+        n_keep = int(n_keep)
+        if n_keep < 1 or not dt_sim > 0:
+            raise RuntimeError('ClosedLoopBatch: need n_keep >= 1 and dt_sim > 0')
+        if n_keep * float(dt_sim) > gusto.N * float(gusto.dt):
+            raise RuntimeError('ClosedLoopBatch: n_keep * dt_sim = %g exceeds the horizon N * dt = %g (the shift of the previous plan '
+                               'would find no row)' % (n_keep * float(dt_sim), gusto.N * float(gusto.dt)))
+        self.gusto, self.plant = gusto, plant                  # (kept alive: the handle points into both)
+        self.B, self.N, self.dt = gusto.batch, gusto.N, float(gusto.dt)
+        self.n_x, self.n_u, self.n_z = gusto.n_x, gusto.n_u, gusto.n_z
+        self.dt_sim, self.n_keep = float(dt_sim), n_keep
+        self.max_steps_per_run = int(max_steps_per_run) if max_steps_per_run is not None else 16 * n_keep
+        self.has_z, self.has_u, self.has_zf = z is not None, u is not None, z is not None and gusto.Qzf is not None
+        self.has_K = K is not None
+        self.t_start, self._k = 0.0, None
+        self._h = C.c_void_p()
+        lib = _lib.lib()
+        _lib.check(lib.sgusto_loop_create(C.byref(self._h), gusto.plan, gusto.model.dyn_sys.handle_for(self.dt),
+                                          plant.handle_for(self.dt_sim), C.c_double(self.dt_sim), C.c_int(n_keep),
+                                          C.c_int64(self.max_steps_per_run)), 'sgusto_loop_create')
+        if z is not None or u is not None:
+            if t is None:
+                raise RuntimeError('ClosedLoopBatch: a target table needs its times t')
+            t = _lib.f64(np.asarray(t).reshape(-1))
+            T = t.shape[0]
+            z = None if z is None else _lib.f64(np.asarray(z).reshape(T, self.n_z))
+            u = None if u is None else _lib.f64(np.asarray(u).reshape(T, self.n_u))
+            phase = None if phase is None else _lib.f64(np.asarray(phase).reshape(self.B))
+            _lib.check(lib.sgusto_loop_set_target(self._h, C.c_int(T), _lib.dptr(t), _lib.dptr(z), _lib.dptr(u), _lib.dptr(phase)),
+                       'sgusto_loop_set_target')
+        if K is not None:
+            K = _lib.f64(np.stack([np.asarray(k) for k in K]).reshape(-1, self.n_u, self.n_x))
+            if K.shape[0] != gusto.model.dyn_sys.num_points:
+                raise RuntimeError('ClosedLoopBatch: K has %d gains, the planner\'s model %d points' % (K.shape[0], gusto.model.dyn_sys.num_points))
+            _lib.check(lib.sgusto_loop_set_feedback(self._h, _lib.dptr(K)), 'sgusto_loop_set_feedback')
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.lib().sgusto_loop_destroy(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass
+
+    def reset(self, x0, t_start=0.0):
+        x0 = _lib.f64(np.asarray(x0).reshape(self.B, self.n_x))
+        _lib.check(_lib.lib().sgusto_loop_reset(self._h, _lib.dptr(x0), C.c_double(float(t_start))), 'sgusto_loop_reset')
+        self.t_start, self._k = float(t_start), 0
+
+    def run(self, periods, W=None, record_x=True):
+        """`periods` periods from where the last run ended.  W (periods, n_keep, B, n_x): added to the plant's next state."""
+        periods = int(periods)
+        B, S = self.B, periods * self.n_keep
+        if periods >= 1 and S <= self.max_steps_per_run:       # (what does not fit is refused by the library, with its message)
+            x = np.empty((B, S + 1, self.n_x)) if record_x else None
+            z, u = np.empty((B, S + 1, self.n_z)), np.empty((B, S, self.n_u))
+            iters, status = np.empty((periods, B), dtype=np.int32), np.empty((periods, B), dtype=np.int32)
+            J = np.empty((periods, B))
+            W = None if W is None else _lib.f64(np.asarray(W).reshape(periods, self.n_keep, B, self.n_x))
+        else:
+            x = W = None
+            z = u = J = np.empty(1)
+            iters = status = np.empty(1, dtype=np.int32)
+        lib = _lib.lib()
+        _lib.check(lib.sgusto_plan_set_max_iters(self.gusto.plan, C.c_int(int(self.gusto.max_gusto_iters))), 'set_max_iters')
+        _lib.check(lib.sgusto_loop_run(self._h, C.c_int(periods), _lib.dptr(W), _lib.dptr(x), _lib.dptr(z), _lib.dptr(u), _lib.iptr(iters),
+                                       _lib.iptr(status), _lib.dptr(J)), 'sgusto_loop_run')
+        t = schedule(self.N, self.dt, self.dt_sim, self.n_keep, self.t_start, self._k).t_k + self.dt_sim * np.arange(S + 1)
+        self._k += periods
+        return ClosedLoopResult(x, z, u, iters, status, J, t)
+
+    def step(self):
+        return self.run(1)
+
+    def last_inputs(self):
+        """The solver inputs of the last period: dict x0, u_init, x_init, z, zf, u (None where the loop has none)."""
+        B, N = self.B, self.N
+        x0, ui, xi = np.empty((B, self.n_x)), np.empty((B, N, self.n_u)), np.empty((B, N + 1, self.n_x))
+        z = np.empty((B, N + 1, self.n_z)) if self.has_z else None
+        zf = np.empty((B, self.n_z)) if self.has_zf else None
+        ud = np.empty((B, N, self.n_u)) if self.has_u else None
+        _lib.check(_lib.lib().sgusto_loop_last_inputs(self._h, _lib.dptr(x0), _lib.dptr(ui), _lib.dptr(xi), _lib.dptr(z), _lib.dptr(zf),
+                                                      _lib.dptr(ud)), 'sgusto_loop_last_inputs')
+        return dict(x0=x0, u_init=ui, x_init=xi, z=z, zf=zf, u=ud)
+
+    def last_plan(self):
+        xo, uo = np.empty((self.B, self.N + 1, self.n_x)), np.empty((self.B, self.N, self.n_u))
+        _lib.check(_lib.lib().sgusto_loop_last_plan(self._h, _lib.dptr(xo), _lib.dptr(uo)), 'sgusto_loop_last_plan')
+        return xo, uo
+
+    def stats(self):
+        steps, waits = C.c_int64(0), C.c_int64(0)
+        _lib.check(_lib.lib().sgusto_loop_stats(self._h, C.byref(steps), C.byref(waits)), 'sgusto_loop_stats')
+        return {'steps': steps.value, 'waits_last_run': waits.value}
+
+    def _advance(self, xopt, uopt, x, W=None):
+        """The advance kernel alone on host-supplied plans (for tests): xopt (B, N+1, n_x), uopt (B, N, n_u), x (B, n_x), W (n_keep, B,
+        n_x) -> X (B, n_keep, n_x), Z, U, and the points picked, idx_plant, idx_gain (B, n_keep; -1 without gains)."""
+        B, N, nk = self.B, self.N, self.n_keep
+        xopt = _lib.f64(np.asarray(xopt).reshape(B, N + 1, self.n_x)); uopt = _lib.f64(np.asarray(uopt).reshape(B, N, self.n_u))
+        x = _lib.f64(np.asarray(x).reshape(B, self.n_x))
+        W = None if W is None else _lib.f64(np.asarray(W).reshape(nk, B, self.n_x))
+        X, Z, U = np.empty((B, nk, self.n_x)), np.empty((B, nk, self.n_z)), np.empty((B, nk, self.n_u))
+        ip, ig = np.empty((B, nk), dtype=np.int32), np.empty((B, nk), dtype=np.int32)
+        _lib.check(_lib.lib().sgusto_loop_advance(self._h, _lib.dptr(xopt), _lib.dptr(uopt), _lib.dptr(x), _lib.dptr(W), _lib.dptr(X),
+                                                  _lib.dptr(Z), _lib.dptr(U), _lib.iptr(ip), _lib.iptr(ig)), 'sgusto_loop_advance')
+        return X, Z, U, ip, ig
