@@ -1,9 +1,11 @@
 """The problem of examples/diamond_closed_loop.py as B closed loops at once: the C2 Diamond shape (synthetic TPWL model, the model
 itself as the plant at dt_sim = 0.01), seeded initial states and target phases, the scp controller's per-point DARE gains -- a
 Monte-Carlo validation of the controller.  All loops stay on the device (scp.closed_loop.ClosedLoopBatch): one launch sequence and
-one host wait for the whole run; state feedback is perfect (no observer inside the loop).
+one host wait for the whole run.  Without --observer state feedback is perfect; with it every loop carries its own extended Kalman
+filter (tpwl.observer.DiscreteEKFObserverBatch) on five measured nodes (n_y = 30) with measurement noise and a wrong initial
+estimate, plans from the estimate and controls from it -- the loop the reference's drivers close.
 
-    python examples/diamond_closed_loop_batch.py [--batch 256] [--periods 20] [--seed 0]
+    python examples/diamond_closed_loop_batch.py [--batch 256] [--periods 20] [--seed 0] [--observer]
 
 Needs an MI355X (no CPU fallback)."""
 import argparse
@@ -25,6 +27,7 @@ def main():
     ap.add_argument('--batch', type=int, default=256)
     ap.add_argument('--periods', type=int, default=20, help='re-planning periods of 10 steps of 0.01 s')
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--observer', action='store_true', help='output feedback: one EKF per loop on five measured nodes, noise, wrong initial estimate')
     args = ap.parse_args()
 
     import workloads as wl
@@ -34,6 +37,7 @@ def main():
     from sofacontrol_amd.scp.closed_loop import ClosedLoopBatch
     from sofacontrol_amd.scp.gusto import GuSTO
     from sofacontrol_amd.scp.models.tpwl import TPWLGuSTO
+    from sofacontrol_amd.tpwl.observer import DiscreteEKFObserverBatch
     from sofacontrol_amd.tpwl.tpwl import TPWLATV
     from sofacontrol_amd.utils import HyperRectangle, Polyhedron
 
@@ -42,7 +46,8 @@ def main():
     m, N, dt, dt_sim, n_keep, B = w['m'], w['N'], w['dt'], 0.01, 10, args.batch
     Hf = linearModel(nodes=[1354], num_nodes=n_f // 3).C.tocsr()              # tip velocity + position (diamond.py:269)
     data = dict(w['tab'], rom_info=dict(type='POD', U=w['U'], q_ref=w['q_ref'], v_ref=w['v_ref']))
-    model = TPWLATV(data=data, params=dict(tpwl_method='nn', dist_weights={'q': 1.0, 'v': 0.0}), Hf=Hf, discr_method='zoh')
+    Cf = linearModel(nodes=[1354, 200, 600, 1000, 1500], num_nodes=n_f // 3).C.tocsr() if args.observer else None
+    model = TPWLATV(data=data, params=dict(tpwl_method='nn', dist_weights={'q': 1.0, 'v': 0.0}), Hf=Hf, Cf=Cf, discr_method='zoh')
     gm = TPWLGuSTO(model)
     with contextlib.redirect_stdout(io.StringIO()):
         gm.pre_discretize(dt)
@@ -63,11 +68,21 @@ def main():
     gusto = GuSTO(gm, N, dt, w['Qz'], w['R'], x0, u_init, x_init, z=zi(phase[:, None] + dt * np.arange(N + 1)),
                   U=HyperRectangle([1500.] * m, [0.] * m), X=Polyhedron(w['XA'], w['Xb']), x_char=xc, f_char=fc, convg_thresh=1e-3,
                   max_gusto_iters=3, batch=B, first_solve_cap=1, max_trace=0)
-    loop = ClosedLoopBatch(gusto, model, dt_sim, n_keep, t=w['t'], z=w['z'], phase=phase, K=K, max_steps_per_run=args.periods * n_keep)
-    loop.reset(x0)
-    t0 = time.perf_counter()
-    res = loop.run(args.periods, record_x=False)
-    wall = time.perf_counter() - t0
+    observer = DiscreteEKFObserverBatch(model, B, W=100.0 * np.eye(2 * r), V=np.eye(30)) if args.observer else None
+    loop = ClosedLoopBatch(gusto, model, dt_sim, n_keep, t=w['t'], z=w['z'], phase=phase, K=K, max_steps_per_run=args.periods * n_keep,
+                           observer=observer)
+    if args.observer:
+        x_hat0 = x0 + 0.1 * rng.standard_normal(x0.shape)                     # where a first update at t = 0 would have left the filters
+        noise = 0.05 * rng.standard_normal((args.periods, n_keep, B, 30))
+        loop.reset_observed(x0, x_hat0)
+        t0 = time.perf_counter()
+        res = loop.run_observed(args.periods, V=noise)
+        wall = time.perf_counter() - t0
+    else:
+        loop.reset(x0)
+        t0 = time.perf_counter()
+        res = loop.run(args.periods, record_x=False)
+        wall = time.perf_counter() - t0
 
     target = zi(phase[:, None] + res.t[None, :])                              # (B, S + 1, 6)
     err = np.linalg.norm((res.z - target)[:, 1:, 3:5], axis=2)
@@ -78,6 +93,13 @@ def main():
           (np.median(rms), rms.min(), rms.max(), np.abs(w['z'][:, 3:5]).max()))
     for b in range(min(B, 8)):
         print('  loop %d: phase %.2f s, rms %.3f, SCP iterations per period %.1f' % (b, phase[b], rms[b], res.iters[:, b].mean()))
+    if args.observer:
+        # W = 100 I trusts the measurements: their noise reaches the weakly observed directions of the state amplified, the outputs hardly
+        e = np.linalg.norm(res.x_hat - res.x, axis=2)                         # (B, S + 1)
+        ez = np.linalg.norm((res.x_hat - res.x) @ H.T, axis=2)
+        print('estimate error over the loops, start -> end (median): state |x_hat - x| %.3f -> %.3f, tip output |H (x_hat - x)| %.3f -> %.3f; '
+              'filters that reported a failure: %d' % (np.median(e[:, 0]), np.median(e[:, -1]), np.median(ez[:, 0]), np.median(ez[:, -1]),
+                                                       int(res.ekf_status.any(axis=0).sum())))
     names = {0: 'converged', 1: 'QP failed', 2: 'omega > omega_max', 3: 'max iterations'}
     codes, counts = np.unique(res.status, return_counts=True)
     print('solve status over %d solves: ' % res.status.size + ', '.join('%s %d' % (names.get(int(c), str(int(c))), n) for c, n in zip(codes, counts)))

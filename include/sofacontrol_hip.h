@@ -242,6 +242,32 @@ int sekf_step(sekf_t *h, const double *u, const double *y, const double *A_d, co
 int sekf_step_projected(sekf_t *h, srom_t *rom, const double *x_full, const double *u, const double *y,
                         double *x_reduced_out, double *x_hat_out);
 
+/* `batch` filters over one model, stepped by one launch (workgroup b is filter b; the kernels are those of sekf_step, chosen by the
+ * same rule: sekf_plan).  C, y_ref, W, V and the model's tables are shared by all filters; the estimate x (batch x n_x), the covariance
+ * Sigma (batch x n_x x n_x) and a status word (batch int32: 0, or 1 after a step whose innovation covariance was not positive definite)
+ * are per filter and resident.  Each predictor takes the table point nearest to its own filter's estimate.  Nearest-point models only:
+ * the explicit (A_d, B_d, d_d) form of sekf_step is not batched.  Sigma0 (n_x x n_x) is installed in every filter, the estimates start
+ * at zero.  Limits (SRH_EINVAL, the message names the one missed): batch >= 1, 0 < n_y <= n_x, a shape sekf_plan does not refuse.
+ * The model handle must outlive the filters. */
+typedef struct sekf_batch sekf_batch_t;
+int sekf_batch_create(sekf_batch_t **out, stpwl_t *model, const double *C, const double *y_ref, int n_y,
+                      const double *Sigma0, const double *W, const double *V, int64_t batch);
+int sekf_batch_destroy(sekf_batch_t *h);
+/* what sekf_batch_create decided (as sekf_handle_plan) and the number of filters.  Any output may be NULL. */
+int sekf_batch_plan(sekf_batch_t *h, int *path, size_t *lds_bytes, int *gain_form, int64_t *batch);
+/* overwrite the estimates x (batch x n_x) and/or the covariances Sigma (batch x n_x x n_x); either may be NULL */
+int sekf_batch_set_state(sekf_batch_t *h, const double *x, const double *Sigma);
+/* x (batch x n_x), Sigma (batch x n_x x n_x), status (batch int32: of each filter's last step); any may be NULL */
+int sekf_batch_get_state(sekf_batch_t *h, double *x, double *Sigma, int *status);
+/* idx (batch int32): the table point each filter's last predictor took (the one nearest to its own estimate); -1 before the first */
+int sekf_batch_last_points(sekf_batch_t *h, int32_t *idx);
+/* sekf_step for every filter: u (batch x n_u) != NULL runs the predictors (the model must be pre-discretised: SRH_EINVAL otherwise),
+ * y (batch x n_y) != NULL the updates.  One upload through a pinned block, one launch, one copy back, one host wait.  A filter whose
+ * innovation covariance is not positive definite sets its status word and keeps its x and Sigma; the others are unaffected.  x_out
+ * (batch x n_x, optional) receives the resident estimate of every filter in either case.  Returns SRH_ENUMERIC when any filter
+ * failed (the message counts them and names the first). */
+int sekf_batch_step(sekf_batch_t *h, const double *u, const double *y, double *x_out);
+
 /* Polyhedron(with_reproject=True).project_to_polyhedron (utils.py:364-407; the measurement re-projection of
  * SSM/controllers.py:96-97): Euclidean projection of `batch` points X (batch x n) onto {p : A p <= b}, A (n_rows x n)
  * row-major, n <= 16, n_rows <= 64; exact (interior point to a 1e-13 gap; the reference hands the same QP to OSQP).
@@ -633,6 +659,35 @@ int sgusto_loop_last_plan(sgusto_loop_t *h, double *xopt, double *uopt);
  * NULL).  The loop's own state is not touched. */
 int sgusto_loop_advance(sgusto_loop_t *h, const double *xopt, const double *uopt, const double *x, const double *W, double *X,
                         double *Z, double *U, int32_t *idx_plant, int32_t *idx_gain);
+/* ---- the observed loop: output feedback through `batch` extended Kalman filters (sekf_batch_t) inside the loop, as the reference's
+ * TemplateController.evaluate closes it (tpwl/controllers.py:85-117: observer.update(u_prev, y, dt) at every simulation step, plan and
+ * control from observer.x).  Period k as above with three changes: the solver's x0 is the estimate x_hat; the law reads the estimate,
+ * u = u_bar + K[i] (x_hat - x_bar); and after the plant step of sub-step s
+ *           y = C x + y_ref (+ v_s);  (x_hat, Sigma) <- predictor with this u on the FILTER model's region nearest to x_hat, then the
+ *           update with y  (C, y_ref and the filter's model are the observer's own; its model need not be the plant).
+ * A filter whose innovation covariance is not positive definite keeps its estimate; the loop goes on and the status is recorded.
+ * Launches of a period: prepare -> solve -> costs -> n_keep x (advance of one sub-step -> batched filter step -> record), all on the
+ * handle's stream; still ONE host wait per run.
+ * set_observer: the filters of the loop (NULL detaches them); refused unless batch, n_x and n_u are the loop's and the filter's model is
+ * pre-discretised.  The observer must outlive the loop, and nothing else may step it while a run is in flight. */
+int sgusto_loop_set_observer(sgusto_loop_t *h, sekf_batch_t *observer);
+/* x0 (batch x n_x) plant states, x_hat0 (batch x n_x) estimates or NULL = x0: where the reference's first observer.update at t = 0
+ * leaves the filters.  Every filter's covariance is re-installed from Sigma0. */
+int sgusto_loop_reset_observed(sgusto_loop_t *h, const double *x0, const double *x_hat0, double t_start);
+/* sgusto_loop_run with the filters in the loop.  V (periods x n_keep x batch x n_y) or NULL: measurement noise.  Xhat (batch x (S + 1)
+ * x n_x): row 0 the estimates the run started from, row s + 1 the estimate after sub-step s; Y_cl (batch x S x n_y); ekf_status
+ * (periods x batch): the OR of the period's filter statuses.  Needs sgusto_loop_reset_observed; sgusto_loop_run refuses to continue
+ * such a state. */
+int sgusto_loop_run_observed(sgusto_loop_t *h, int periods, const double *W, const double *V, double *X_cl, double *Z_cl, double *U_cl,
+                             int32_t *iters, int32_t *status, double *J, double *Xhat, double *Y_cl, int32_t *ekf_status);
+/* The observed sub-step chain of one period alone -- the launches sgusto_loop_run_observed makes -- on host-supplied plans, states x and
+ * estimates x_hat (batch x n_x), W (n_keep x batch x n_x) / V (n_keep x batch x n_y) or NULL -> X, Z, U as sgusto_loop_advance, Xhat
+ * (batch x n_keep x n_x) the estimate after every sub-step, Y (batch x n_keep x n_y), the three points picked at every sub-step
+ * (plant at x, gain at x_bar, filter at x_hat; batch x n_keep, any may be NULL) and ekf_status (batch, or NULL).  The attached filters
+ * are started from x_hat and Sigma0 and left where the chain ends: the loop needs a reset afterwards. */
+int sgusto_loop_advance_observed(sgusto_loop_t *h, const double *xopt, const double *uopt, const double *x, const double *x_hat, const double *W,
+                                 const double *V, double *X, double *Z, double *U, double *Xhat, double *Y, int32_t *idx_plant,
+                                 int32_t *idx_gain, int32_t *idx_filter, int32_t *ekf_status);
 /* periods run since the last reset, and the blocking host waits of the last run */
 int sgusto_loop_stats(sgusto_loop_t *h, int64_t *steps, int64_t *waits_last_run);
 /* The schedule of period k (no GPU): *t_k, *idx0 (0 for k = 0), j (n_keep), theta (n_keep).  Any output may be NULL. */

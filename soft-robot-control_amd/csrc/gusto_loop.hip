@@ -6,6 +6,16 @@
 // period's output into the next solve's input, loop_advance_kernel runs the plant under the feedback law for the n_keep sub-steps.
 #include "tpwl_host.h"
 
+// observer.hip: the batched filter's device-side step and what the observed loop needs of its handle
+int sekf_batch_step_dev(sekf_batch *h, const double *u_dev, int64_t su, const double *y_dev, int64_t sy, int32_t *pick_dev, int64_t sp,
+                        hipStream_t stream);
+int sekf_batch_install_sigma0(sekf_batch *h);
+void sekf_batch_dims(const sekf_batch *h, int *n, int *m, int *ny, int64_t *batch, stpwl **model);
+double *sekf_batch_x_dev(sekf_batch *h);
+int *sekf_batch_status_dev(sekf_batch *h);
+const double *sekf_batch_C_dev(sekf_batch *h);
+const double *sekf_batch_yref_dev(sekf_batch *h);
+
 namespace {
 
 typedef double loop_d2 __attribute__((ext_vector_type(2)));
@@ -44,7 +54,8 @@ struct PrepArgs {
     int N, n, m, nz, T;
     int first, idx0;                    // first period after a reset: no shift (the guess is the planner's zero-input rollout)
     double tk, dt;
-    const double *xcur, *xopt, *uopt;   // plant states (B x n), previous plan
+    const double *xcur, *xopt, *uopt;   // the states the plans start from (B x n: the plant's, or the filters' estimates), previous plan
+    const double *xplant;               // observed loop: the plant states, for row 0 of the records (null: xcur)
     const double *tt, *tz, *tu, *phase; // target table (tz / tu / phase may be null)
     const double *H;                    // (nz x n) of the planner's model
     double *x0, *x_init, *u_init, *z, *zf, *ud;
@@ -57,17 +68,17 @@ __global__ __launch_bounds__(256) void loop_prepare_kernel(PrepArgs a) {
     const size_t b = blockIdx.x;
     const int N = a.N, n = a.n, m = a.m, nz = a.nz, tid = threadIdx.x;
     cgptr xc = (cgptr)a.xcur + b * n;
+    cgptr xr = a.xplant ? (cgptr)a.xplant + b * n : xc;
     gptr x0 = (gptr)a.x0 + b * n;
     for (int e = tid; e < n; e += 256) {
-        const double v = xc[e];
-        x0[e] = v;
-        if (a.Xrec) ((gptr)a.Xrec)[b * (size_t)a.rec_rows * n + e] = v;
+        x0[e] = xc[e];
+        if (a.Xrec) ((gptr)a.Xrec)[b * (size_t)a.rec_rows * n + e] = xr[e];
     }
     if (a.Zrec) {
         cgptr H = (cgptr)a.H;
         for (int e = tid; e < nz; e += 256) {
             double v = 0.0;
-            for (int c = 0; c < n; ++c) v = fma(H[e * n + c], xc[c], v);
+            for (int c = 0; c < n; ++c) v = fma(H[e * n + c], xr[c], v);
             ((gptr)a.Zrec)[b * (size_t)a.rec_rows * nz + e] = v;
         }
     }
@@ -119,6 +130,12 @@ struct AdvArgs {
     double *X, *Z, *U;                  // records: row row0 + s of rollout b (X may be null)
     int32_t *ip, *ig;                   // (B x n_keep) points picked, or null
     int64_t rows_x, row0_x, rows_u, row0_u, B, w_step0;
+    int s0, s1;                         // the sub-steps of this launch: s0 <= s < s1 (the whole period without an observer)
+    // with an observer (loop_advance_kernel<true>): the law reads the estimate, and every sub-step ends with a measurement
+    const double *xhat;                 // (B x n) the filters' estimates
+    const double *C, *y_ref, *Vn;       // (ny x n), (ny) or null, (steps x B x ny) measurement noise or null (indexed as W)
+    double *Y;                          // (B x rows_u x ny) record, rows as U: the batched filter reads its y from it
+    int ny;
 };
 
 // One workgroup per rollout, all n_keep sub-steps.  The plant's region panel [A_d^T | B_d^T | d_d] sits in LDS and is reloaded only when
@@ -126,6 +143,10 @@ struct AdvArgs {
 // for the whole launch.  Per sub-step: waves 0-2 interpolate the plan; wave 0 searches the plant's table at x while wave 1 searches the
 // planner's at x_bar (tpwl::nearest_wave both: one tie rule); the four waves form K (x - x_bar) a row each; the products of the step are
 // wg::matTvec's slices (slice s sums rows s, s + S, ... by fma from 0.0; x' = d + partials of A x in slice order + partials of B u).
+// OBS: the observed loop's sub-step.  The law reads the filter's estimate x_hat in place of x, and the sub-step ends with the measurement
+// y = C x' + y_ref (+ v).  The filter itself is another kernel (512 threads, up to 160 KB of LDS), so a launch then covers one sub-step
+// and the region panel is loaded per launch.
+template <bool OBS>
 __global__ __launch_bounds__(256) void loop_advance_kernel(TpwlDev TP, TpwlDev TL, AdvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int n = TL.n, m = TL.m, N = a.N, nz = a.nz;
@@ -140,6 +161,8 @@ __global__ __launch_bounds__(256) void loop_advance_kernel(TpwlDev TP, TpwlDev T
     lptr At = pb + 256 + 2;                              // n x n  the panel of region `cur`: every offset is even (n = 2 r)
     lptr Bt = At + n * n;                                // m x n
     lptr dl = Bt + m * n;                                // n
+    lptr xh = dl + n;                                    // n      OBS: the estimate
+    clptr xl = OBS ? xh : xc;                            //        what the law reads
     const size_t b = blockIdx.x;
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int S = max(1, 256 / n), j = tid % n, sl = tid / n;
@@ -147,16 +170,18 @@ __global__ __launch_bounds__(256) void loop_advance_kernel(TpwlDev TP, TpwlDev T
     cgptr Kt = (cgptr)a.K, H = (cgptr)a.H, Wd = (cgptr)a.W, thg = (cgptr)a.theta, xin = (cgptr)a.x_in;
     cgiptr jsg = (cgiptr)a.js;
     for (int e = tid; e < n; e += 256) xc[e] = xin[b * n + e];
+    if (OBS)
+        for (int e = tid; e < n; e += 256) xh[e] = ((cgptr)a.xhat)[b * n + e];
     __syncthreads();
     int cur = -1;
-    for (int s = 0; s < a.n_keep; ++s) {
+    for (int s = a.s0; s < a.s1; ++s) {
         const int js = jsg[s];
         const double th = thg[s];
         if (tid < n) {                                   // (n <= 128: waves 0 and 1)
             const double lo = xo[(size_t)js * n + tid], hi = xo[(size_t)(js + 1) * n + tid];
             const double v = lo + th * (hi - lo);
             xb[tid] = v;
-            dx[tid] = xc[tid] - v;
+            dx[tid] = xl[tid] - v;
         } else if (tid >= 128 && tid < 128 + m) {        // the input is held over the last interval (controllers.py:299)
             const int e = tid - 128;
             const double lo = uo[(size_t)js * m + e], hi = uo[(size_t)min(js + 1, N - 1) * m + e];
@@ -219,13 +244,32 @@ __global__ __launch_bounds__(256) void loop_advance_kernel(TpwlDev TP, TpwlDev T
             for (int c = 0; c < n; ++c) v = fma(H[e * n + c], xc[c], v);
             ((gptr)a.Z)[(b * (size_t)a.rows_x + a.row0_x + s) * nz + e] = v;
         }
+        if (OBS) {
+            cgptr Cg = (cgptr)a.C, yr = (cgptr)a.y_ref, Vn = (cgptr)a.Vn;
+            for (int e = tid; e < a.ny; e += 256) {
+                double v = 0.0;
+                for (int c = 0; c < n; ++c) v = fma(Cg[e * n + c], xc[c], v);
+                if (yr != nullptr) v += yr[e];
+                if (Vn != nullptr) v += Vn[((size_t)(a.w_step0 + s) * a.B + b) * a.ny + e];
+                ((gptr)a.Y)[(b * (size_t)a.rows_u + a.row0_u + s) * a.ny + e] = v;
+            }
+        }
     }
     if (a.x_out)
         for (int e = tid; e < n; e += 256) ((gptr)a.x_out)[b * n + e] = xc[e];
 }
 
-size_t advance_lds_bytes(int n, int m) {
-    return srh::lds_request(sizeof(double) * ((size_t)3 * n + 16 + 16 + 256 + 256 + 2 + (size_t)n * n + (size_t)m * n + n));
+size_t advance_lds_bytes(int n, int m, bool observed) {
+    return srh::lds_request(sizeof(double) * ((size_t)3 * n + 16 + 16 + 256 + 256 + 2 + (size_t)n * n + (size_t)m * n + n + (observed ? n : 0)));
+}
+
+// After a batched filter step: the estimates into row `row` of the record (B x rows x n), and the filters' status words into the
+// period's entry of the status record -- assigned at the period's first sub-step, or-ed at the others.
+__global__ __launch_bounds__(64) void loop_estimate_record_kernel(const double *xhat, const int *status, double *Xhat, int32_t *E, int n,
+                                                                  int64_t rows, int64_t row, int first) {
+    const size_t b = blockIdx.x;
+    for (int e = threadIdx.x; e < n; e += 64) Xhat[(b * (size_t)rows + row) * n + e] = xhat[b * n + e];
+    if (threadIdx.x == 0) E[b] = first ? status[b] : (E[b] | status[b]);
 }
 
 struct PinBuf {
@@ -250,6 +294,12 @@ struct sgusto_loop {
     int64_t B = 0, max_steps = 0;
     double dt = 0.0, dt_sim = 0.0, t_start = 0.0;
     bool has_Qzf = false, has_z = false, has_ud = false, has_phase = false, has_K = false, have_state = false;
+    // the observed loop: the attached filters (sgusto_loop_set_observer) and whether the state is an observed one (plant states and
+    // estimates installed together by sgusto_loop_reset_observed)
+    sekf_batch *obs = nullptr;
+    int ny = 0;
+    bool observed_state = false;
+    size_t lds_obs = 0;
     int64_t k = 0;                      // periods since the last reset
     int64_t waits = 0;                  // blocking host waits of the last run
     size_t lds = 0;
@@ -257,6 +307,8 @@ struct sgusto_loop {
     srh::DevBuf x0, u_init, x_init, z, zf, ud, xopt, uopt, zopt, xcur, tt, tz, tu, phase, K, js, theta;
     srh::DevBuf Xrec, Zrec, Urec, Irec, Srec, Jrec, Wd;
     PinBuf pX, pZ, pU, pI, pS, pJ, pW;
+    srh::DevBuf XHrec, Yrec, Erec, Vd;  // observed loop: estimates (B x (S + 1) x n), measurements (B x S x ny), filter status (P x B), noise
+    PinBuf pXH, pY, pE, pV;
     ~sgusto_loop() {
         if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
     }
@@ -267,11 +319,32 @@ struct sgusto_loop {
         a.H = planner->H.as<double>();
         a.js = js.as<int32_t>(); a.theta = theta.as<double>();
         a.B = B;
+        a.s0 = 0; a.s1 = n_keep;
         return a;
     }
     int launch_advance(const AdvArgs &a) const {
-        loop_advance_kernel<<<(unsigned)B, 256, lds, stream>>>(planner->view(), plant->view(), a);
+        loop_advance_kernel<false><<<(unsigned)B, 256, lds, stream>>>(planner->view(), plant->view(), a);
         SRH_CHECK_HIP(hipGetLastError());
+        return SRH_OK;
+    }
+    // The observed sub-step chain of one period on the handle's stream: n_keep x (advance of one sub-step under the law at the estimate,
+    // with its measurement -> one step of every filter from the recorded u and y -> the estimates and the status into their records).
+    // v: the arguments of the whole period (records, plan, W / Vn, x_in / x_out); XH / xh_rows / xh_row0: the estimate record and the
+    // row of sub-step 0's estimate; E: the period's status entry (B); pick: (B x n_keep) filter regions or null.
+    int launch_observed_chain(AdvArgs v, double *XH, int64_t xh_rows, int64_t xh_row0, int32_t *E, int32_t *pick) const {
+        v.xhat = sekf_batch_x_dev(obs); v.C = sekf_batch_C_dev(obs); v.y_ref = sekf_batch_yref_dev(obs); v.ny = ny;
+        int rc;
+        for (int s = 0; s < n_keep; ++s) {
+            v.s0 = s; v.s1 = s + 1;
+            loop_advance_kernel<true><<<(unsigned)B, 256, lds_obs, stream>>>(planner->view(), plant->view(), v);
+            SRH_CHECK_HIP(hipGetLastError());
+            if ((rc = sekf_batch_step_dev(obs, v.U + (size_t)(v.row0_u + s) * m, v.rows_u * m, v.Y + (size_t)(v.row0_u + s) * ny, v.rows_u * ny,
+                                          pick ? pick + s : nullptr, n_keep, stream)))
+                return rc;
+            loop_estimate_record_kernel<<<(unsigned)B, 64, 0, stream>>>(v.xhat, sekf_batch_status_dev(obs), XH, E, n, xh_rows, xh_row0 + s,
+                                                                       s == 0 ? 1 : 0);
+            SRH_CHECK_HIP(hipGetLastError());
+        }
         return SRH_OK;
     }
 };
@@ -336,7 +409,7 @@ int sgusto_loop_create(sgusto_loop_t **out, sgusto_plan_t *plan, stpwl_t *planne
     h->plan = plan; h->planner = planner_model; h->plant = plant;
     h->N = N; h->n = n; h->m = m; h->nz = nz; h->n_keep = n_keep; h->B = B; h->max_steps = max_steps_per_run;
     h->dt = dt; h->dt_sim = dt_sim; h->has_Qzf = has_Qzf != 0;
-    h->lds = advance_lds_bytes(n, m);
+    h->lds = advance_lds_bytes(n, m, false);
     std::vector<int32_t> js(n_keep);
     std::vector<double> th(n_keep);
     (void)sgusto_loop_schedule(N, dt, dt_sim, n_keep, 0.0, 0, nullptr, nullptr, js.data(), th.data());
@@ -346,7 +419,7 @@ int sgusto_loop_create(sgusto_loop_t **out, sgusto_plan_t *plan, stpwl_t *planne
         srh::set_error("sgusto_loop_create: the advance kernel needs %zu bytes of LDS (160 KiB available)", h->lds);
         return fail(SRH_EINVAL);
     }
-    if (hipFuncSetAttribute((const void *)loop_advance_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds) != hipSuccess ||
+    if (hipFuncSetAttribute((const void *)loop_advance_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds) != hipSuccess ||
         hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
         srh::set_error("sgusto_loop_create: could not set up the advance kernel / the stream: %s", hipGetErrorString(hipGetLastError()));
         return fail(SRH_EHIP);
@@ -398,15 +471,14 @@ int sgusto_loop_reset(sgusto_loop_t *h, const double *x0, double t_start) {
     SRH_REQUIRE(h && x0, "sgusto_loop_reset: null argument");
     SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
     SRH_CHECK_HIP(hipMemcpy(h->xcur.p, x0, sizeof(double) * h->B * h->n, hipMemcpyHostToDevice));
-    h->t_start = t_start; h->k = 0; h->have_state = true;
+    h->t_start = t_start; h->k = 0; h->have_state = true; h->observed_state = false;
     return SRH_OK;
 }
 
-int sgusto_loop_run(sgusto_loop_t *h, int periods, const double *W, double *X_cl, double *Z_cl, double *U_cl, int32_t *iters,
-                    int32_t *status, double *J) {
-    SRH_REQUIRE(h && Z_cl && U_cl && iters && status && J, "sgusto_loop_run: null argument");
-    SRH_REQUIRE(periods >= 1, "sgusto_loop_run: periods must be positive");
-    SRH_REQUIRE(h->have_state, "sgusto_loop_run: no plant state yet (call sgusto_loop_reset first)");
+// sgusto_loop_run and sgusto_loop_run_observed: Xhat != null is the observed loop (Vn, Y_cl, ekf_status belong to it)
+static int loop_run(sgusto_loop_t *h, int periods, const double *W, const double *Vn, double *X_cl, double *Z_cl, double *U_cl, int32_t *iters,
+                    int32_t *status, double *J, double *Xhat, double *Y_cl, int32_t *ekf_status) {
+    const bool observed = Xhat != nullptr;
     const int N = h->N, n = h->n, m = h->m, nz = h->nz, nk = h->n_keep;
     const size_t D = sizeof(double), B = (size_t)h->B, S = (size_t)periods * nk;
     SRH_REQUIRE((int64_t)S <= h->max_steps, "sgusto_loop_run: periods * n_keep = %lld exceeds max_steps_per_run = %lld", (long long)S,
@@ -414,6 +486,9 @@ int sgusto_loop_run(sgusto_loop_t *h, int periods, const double *W, double *X_cl
     int rc;
     if (X_cl && ((rc = h->pX.need(D * B * (h->max_steps + 1) * n)) || (!h->Xrec.p && (rc = h->Xrec.alloc(D * B * (h->max_steps + 1) * n))))) return rc;
     if (W && ((rc = h->pW.need(D * h->max_steps * B * n)) || (!h->Wd.p && (rc = h->Wd.alloc(D * h->max_steps * B * n))))) return rc;
+    const size_t ny = (size_t)h->ny;
+    if (Vn && ((rc = h->pV.need(D * h->max_steps * B * ny)) || (!h->Vd.p && (rc = h->Vd.alloc(D * h->max_steps * B * ny))))) return rc;
+    double *xhat = observed ? sekf_batch_x_dev(h->obs) : nullptr;
     h->waits = 0;
     hipStream_t st = h->stream;
     // from here on work is enqueued on the handle's stream: on any error it is drained before returning
@@ -422,6 +497,12 @@ int sgusto_loop_run(sgusto_loop_t *h, int periods, const double *W, double *X_cl
             memcpy(h->pW.p, W, D * S * B * n);
             SRH_CHECK_HIP(hipMemcpyAsync(h->Wd.p, h->pW.p, D * S * B * n, hipMemcpyHostToDevice, st));
         }
+        if (Vn) {
+            memcpy(h->pV.p, Vn, D * S * B * ny);
+            SRH_CHECK_HIP(hipMemcpyAsync(h->Vd.p, h->pV.p, D * S * B * ny, hipMemcpyHostToDevice, st));
+        }
+        if (observed)              // row 0 of the estimate record: the estimates the run starts from
+            SRH_CHECK_HIP(hipMemcpy2DAsync(h->XHrec.p, D * (S + 1) * n, xhat, D * n, D * n, B, hipMemcpyDeviceToDevice, st));
         for (int p = 0; p < periods; ++p) {
             const int64_t k = h->k + p;
             PrepArgs a{};
@@ -429,7 +510,9 @@ int sgusto_loop_run(sgusto_loop_t *h, int periods, const double *W, double *X_cl
             a.first = k == 0 ? 1 : 0;
             a.dt = h->dt;
             (void)sgusto_loop_schedule(N, h->dt, h->dt_sim, nk, h->t_start, k, &a.tk, &a.idx0, nullptr, nullptr);
-            a.xcur = h->xcur.as<double>(); a.xopt = h->xopt.as<double>(); a.uopt = h->uopt.as<double>();
+            // with an observer the plan starts from the estimate; row 0 of the records is the plant's state all the same
+            a.xcur = observed ? xhat : h->xcur.as<double>(); a.xplant = observed ? h->xcur.as<double>() : nullptr;
+            a.xopt = h->xopt.as<double>(); a.uopt = h->uopt.as<double>();
             a.tt = h->tt.as<double>();
             a.tz = h->has_z ? h->tz.as<double>() : nullptr;
             a.tu = h->has_ud ? h->tu.as<double>() : nullptr;
@@ -456,7 +539,19 @@ int sgusto_loop_run(sgusto_loop_t *h, int periods, const double *W, double *X_cl
             v.x_in = h->xcur.as<double>(); v.x_out = h->xcur.as<double>();
             v.X = X_cl ? h->Xrec.as<double>() : nullptr; v.Z = h->Zrec.as<double>(); v.U = h->Urec.as<double>();
             v.rows_x = (int64_t)S + 1; v.row0_x = (int64_t)p * nk + 1; v.rows_u = (int64_t)S; v.row0_u = (int64_t)p * nk;
-            if ((rc = h->launch_advance(v))) return rc;
+            if (!observed) {
+                if ((rc = h->launch_advance(v))) return rc;
+            } else {
+                v.Vn = Vn ? h->Vd.as<double>() : nullptr; v.Y = h->Yrec.as<double>();
+                if ((rc = h->launch_observed_chain(v, h->XHrec.as<double>(), (int64_t)S + 1, (int64_t)p * nk + 1, h->Erec.as<int32_t>() + p * B,
+                                                   nullptr)))
+                    return rc;
+            }
+        }
+        if (observed) {
+            SRH_CHECK_HIP(hipMemcpyAsync(h->pXH.p, h->XHrec.p, D * B * (S + 1) * n, hipMemcpyDeviceToHost, st));
+            SRH_CHECK_HIP(hipMemcpyAsync(h->pY.p, h->Yrec.p, D * B * S * ny, hipMemcpyDeviceToHost, st));
+            SRH_CHECK_HIP(hipMemcpyAsync(h->pE.p, h->Erec.p, sizeof(int32_t) * periods * B, hipMemcpyDeviceToHost, st));
         }
         if (X_cl) SRH_CHECK_HIP(hipMemcpyAsync(h->pX.p, h->Xrec.p, D * B * (S + 1) * n, hipMemcpyDeviceToHost, st));
         SRH_CHECK_HIP(hipMemcpyAsync(h->pZ.p, h->Zrec.p, D * B * (S + 1) * nz, hipMemcpyDeviceToHost, st));
@@ -479,8 +574,70 @@ int sgusto_loop_run(sgusto_loop_t *h, int periods, const double *W, double *X_cl
     memcpy(iters, h->pI.p, sizeof(int32_t) * periods * B);
     memcpy(status, h->pS.p, sizeof(int32_t) * periods * B);
     memcpy(J, h->pJ.p, D * periods * B);
+    if (observed) {
+        memcpy(Xhat, h->pXH.p, D * B * (S + 1) * n);
+        memcpy(Y_cl, h->pY.p, D * B * S * ny);
+        memcpy(ekf_status, h->pE.p, sizeof(int32_t) * periods * B);
+    }
     h->k += periods;
     return SRH_OK;
+}
+
+int sgusto_loop_run(sgusto_loop_t *h, int periods, const double *W, double *X_cl, double *Z_cl, double *U_cl, int32_t *iters,
+                    int32_t *status, double *J) {
+    SRH_REQUIRE(h && Z_cl && U_cl && iters && status && J, "sgusto_loop_run: null argument");
+    SRH_REQUIRE(periods >= 1, "sgusto_loop_run: periods must be positive");
+    SRH_REQUIRE(h->have_state, "sgusto_loop_run: no plant state yet (call sgusto_loop_reset first)");
+    SRH_REQUIRE(!h->observed_state, "sgusto_loop_run: the loop was reset with estimates (sgusto_loop_reset_observed): continue it with "
+                "sgusto_loop_run_observed, or call sgusto_loop_reset");
+    return loop_run(h, periods, W, nullptr, X_cl, Z_cl, U_cl, iters, status, J, nullptr, nullptr, nullptr);
+}
+
+int sgusto_loop_set_observer(sgusto_loop_t *h, sekf_batch_t *observer) {
+    SRH_REQUIRE(h, "sgusto_loop_set_observer: null handle");
+    SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
+    h->obs = nullptr; h->observed_state = false;
+    if (!observer) return SRH_OK;
+    int n, m, ny;
+    int64_t B;
+    stpwl *model;
+    sekf_batch_dims(observer, &n, &m, &ny, &B, &model);
+    SRH_REQUIRE(B == h->B, "sgusto_loop_set_observer: the observer has batch = %lld filters, the loop %lld members", (long long)B, (long long)h->B);
+    SRH_REQUIRE(n == h->n && m == h->m, "sgusto_loop_set_observer: the observer's model has n_x = %d, n_u = %d, the loop n_x = %d, n_u = %d", n, m,
+                h->n, h->m);
+    SRH_REQUIRE(model->has_discrete, "sgusto_loop_set_observer: the observer's model has not been pre-discretised (at dt_sim)");
+    const size_t D = sizeof(double), S = (size_t)h->max_steps, P = S / h->n_keep, Bz = (size_t)h->B;
+    h->lds_obs = advance_lds_bytes(h->n, h->m, true);
+    SRH_REQUIRE(h->lds_obs <= (size_t)160 * 1024, "sgusto_loop_set_observer: the observed advance kernel needs %zu bytes of LDS (160 KiB available)",
+                h->lds_obs);
+    SRH_CHECK_HIP(hipFuncSetAttribute((const void *)loop_advance_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_obs));
+    int rc;
+    if ((rc = h->XHrec.alloc(D * Bz * (S + 1) * n)) || (rc = h->Yrec.alloc(D * Bz * S * ny)) || (rc = h->Erec.alloc(sizeof(int32_t) * P * Bz)) ||
+        (rc = h->pXH.need(D * Bz * (S + 1) * n)) || (rc = h->pY.need(D * Bz * S * ny)) || (rc = h->pE.need(sizeof(int32_t) * P * Bz)))
+        return rc;
+    h->obs = observer; h->ny = ny;
+    return SRH_OK;
+}
+
+int sgusto_loop_reset_observed(sgusto_loop_t *h, const double *x0, const double *x_hat0, double t_start) {
+    SRH_REQUIRE(h && x0, "sgusto_loop_reset_observed: null argument");
+    SRH_REQUIRE(h->obs, "sgusto_loop_reset_observed: no observer attached (sgusto_loop_set_observer)");
+    int rc = sgusto_loop_reset(h, x0, t_start);
+    if (rc) return rc;
+    h->have_state = false;
+    SRH_CHECK_HIP(hipMemcpy(sekf_batch_x_dev(h->obs), x_hat0 ? x_hat0 : x0, sizeof(double) * h->B * h->n, hipMemcpyHostToDevice));
+    if ((rc = sekf_batch_install_sigma0(h->obs))) return rc;
+    h->have_state = true; h->observed_state = true;
+    return SRH_OK;
+}
+
+int sgusto_loop_run_observed(sgusto_loop_t *h, int periods, const double *W, const double *V, double *X_cl, double *Z_cl, double *U_cl,
+                             int32_t *iters, int32_t *status, double *J, double *Xhat, double *Y_cl, int32_t *ekf_status) {
+    SRH_REQUIRE(h && Z_cl && U_cl && iters && status && J && Xhat && Y_cl && ekf_status, "sgusto_loop_run_observed: null argument");
+    SRH_REQUIRE(periods >= 1, "sgusto_loop_run_observed: periods must be positive");
+    SRH_REQUIRE(h->obs, "sgusto_loop_run_observed: no observer attached (sgusto_loop_set_observer)");
+    SRH_REQUIRE(h->have_state && h->observed_state, "sgusto_loop_run_observed: no plant state and estimate yet (call sgusto_loop_reset_observed first)");
+    return loop_run(h, periods, W, V, X_cl, Z_cl, U_cl, iters, status, J, Xhat, Y_cl, ekf_status);
 }
 
 int sgusto_loop_last_inputs(sgusto_loop_t *h, double *x0, double *u_init, double *x_init, double *z, double *zf, double *u_des) {
@@ -534,6 +691,46 @@ int sgusto_loop_advance(sgusto_loop_t *h, const double *xopt, const double *uopt
     if ((rc = dX.download(X, D * B * nk * n)) || (rc = dZ.download(Z, D * B * nk * nz)) || (rc = dU.download(U, D * B * nk * m))) return rc;
     if (idx_plant && (rc = dp.download(idx_plant, sizeof(int32_t) * B * nk))) return rc;
     if (idx_gain && (rc = dg.download(idx_gain, sizeof(int32_t) * B * nk))) return rc;
+    return SRH_OK;
+}
+
+int sgusto_loop_advance_observed(sgusto_loop_t *h, const double *xopt, const double *uopt, const double *x, const double *x_hat, const double *W,
+                                 const double *V, double *X, double *Z, double *U, double *Xhat, double *Y, int32_t *idx_plant,
+                                 int32_t *idx_gain, int32_t *idx_filter, int32_t *ekf_status) {
+    SRH_REQUIRE(h && xopt && uopt && x && x_hat && X && Z && U && Xhat && Y, "sgusto_loop_advance_observed: null argument");
+    SRH_REQUIRE(h->obs, "sgusto_loop_advance_observed: no observer attached (sgusto_loop_set_observer)");
+    const size_t D = sizeof(double), B = (size_t)h->B, N = h->N, n = h->n, m = h->m, nz = h->nz, nk = h->n_keep, ny = h->ny;
+    SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
+    // the attached filters start from x_hat and Sigma0; the loop's own state is no longer the one the caller knows
+    h->have_state = false;
+    SRH_CHECK_HIP(hipMemcpy(sekf_batch_x_dev(h->obs), x_hat, D * B * n, hipMemcpyHostToDevice));
+    srh::DevBuf dxo, duo, dx, dW, dV, dX, dZ, dU, dXH, dY, dp, dg, df, dE;
+    int rc;
+    if ((rc = sekf_batch_install_sigma0(h->obs)) || (rc = dxo.upload(xopt, D * B * (N + 1) * n)) || (rc = duo.upload(uopt, D * B * N * m)) ||
+        (rc = dx.upload(x, D * B * n)) || (W && (rc = dW.upload(W, D * nk * B * n))) || (V && (rc = dV.upload(V, D * nk * B * ny))) ||
+        (rc = dX.alloc(D * B * nk * n)) || (rc = dZ.alloc(D * B * nk * nz)) || (rc = dU.alloc(D * B * nk * m)) || (rc = dXH.alloc(D * B * nk * n)) ||
+        (rc = dY.alloc(D * B * nk * ny)) || (rc = dp.alloc(sizeof(int32_t) * B * nk)) || (rc = dg.alloc(sizeof(int32_t) * B * nk)) ||
+        (rc = df.alloc(sizeof(int32_t) * B * nk)) || (rc = dE.alloc(sizeof(int32_t) * B)))
+        return rc;
+    AdvArgs v = h->adv_args();
+    v.xopt = dxo.as<double>(); v.uopt = duo.as<double>();
+    v.W = W ? dW.as<double>() : nullptr; v.Vn = V ? dV.as<double>() : nullptr; v.w_step0 = 0;
+    v.x_in = dx.as<double>(); v.x_out = dx.as<double>();          // the plant state travels from launch to launch
+    v.X = dX.as<double>(); v.Z = dZ.as<double>(); v.U = dU.as<double>(); v.Y = dY.as<double>();
+    v.ip = dp.as<int32_t>(); v.ig = dg.as<int32_t>();
+    v.rows_x = (int64_t)nk; v.row0_x = 0; v.rows_u = (int64_t)nk; v.row0_u = 0;
+    rc = h->launch_observed_chain(v, dXH.as<double>(), (int64_t)nk, 0, dE.as<int32_t>(), df.as<int32_t>());
+    // (the temporaries go back to the allocation cache when this returns: wait for the kernels whatever they answered)
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    if (rc) return rc;
+    SRH_CHECK_HIP(e);
+    if ((rc = dX.download(X, D * B * nk * n)) || (rc = dZ.download(Z, D * B * nk * nz)) || (rc = dU.download(U, D * B * nk * m)) ||
+        (rc = dXH.download(Xhat, D * B * nk * n)) || (rc = dY.download(Y, D * B * nk * ny)))
+        return rc;
+    if (idx_plant && (rc = dp.download(idx_plant, sizeof(int32_t) * B * nk))) return rc;
+    if (idx_gain && (rc = dg.download(idx_gain, sizeof(int32_t) * B * nk))) return rc;
+    if (idx_filter && (rc = df.download(idx_filter, sizeof(int32_t) * B * nk))) return rc;
+    if (ekf_status && (rc = dE.download(ekf_status, sizeof(int32_t) * B))) return rc;
     return SRH_OK;
 }
 

@@ -1,6 +1,7 @@
 // Discrete extended Kalman filter over the TPWL model, state and covariance resident in HBM.
 // Reference: sofacontrol/tpwl/observer.py:33-126 (DiscreteEKFObserver): predict_state 97-106,
-// update_state 108-126.  One workgroup per filter step; every matrix of the step lives in LDS.
+// update_state 108-126.  One workgroup per filter step; every matrix of the step lives in LDS.  A batch of filters over one model
+// (sekf_batch) is the same kernels launched with one workgroup per filter.
 #include "tpwl_host.h"
 
 // pod.hip: two-phase staged projection (enqueue on a stream; read the pinned mirror once that stream has drained)
@@ -26,6 +27,39 @@ struct sekf {
     }
 };
 
+// `batch` filters over one model, one launch per step: workgroup b is filter b.  C, y_ref, W, V and the model tables are shared;
+// x, Sigma and the status word are per filter.
+struct sekf_batch {
+    stpwl *model = nullptr;
+    int n = 0, m = 0, ny = 0, batch = 0;
+    // xs: [x (batch x n) | status (batch int32)]: one copy back; uy: [u (batch x m) | y (batch x ny)]: the host step's inputs;
+    // pick: the table point of each filter's last predictor (batch int32)
+    srh::DevBuf C, y_ref, W, V, Sigma0, Sigma, xs, uy, pick;
+    size_t lds = 0;
+    int path = 0, gain_form = 0;
+    double *pin_in = nullptr, *pin_out = nullptr;               // pinned mirrors of uy and xs
+    int *status_dev() const { return (int *)(xs.as<double>() + (size_t)batch * n); }
+    size_t xs_bytes() const { return sizeof(double) * (size_t)batch * n + sizeof(int) * (size_t)batch; }
+    ~sekf_batch() {
+        if (pin_in) (void)hipHostFree(pin_in);
+        if (pin_out) (void)hipHostFree(pin_out);
+    }
+};
+
+// One step of every filter of the batch on `stream`, from device inputs: one launch, no copy, no wait (gusto_loop.hip chains it behind
+// its advance kernel).  u_dev / y_dev: filter b reads u_dev + b su (n_u entries) and y_dev + b sy (n_y entries); NULL: no predictor / no
+// update.  pick_dev (optional): the table point filter b's predictor took goes to pick_dev[b sp].
+int sekf_batch_step_dev(sekf_batch *h, const double *u_dev, int64_t su, const double *y_dev, int64_t sy, int32_t *pick_dev, int64_t sp,
+                        hipStream_t stream);
+// Sigma0 into every filter (device copies on stream 0, waited for)
+int sekf_batch_install_sigma0(sekf_batch *h);
+// shapes, and the resident estimates (batch x n_x) and status words (batch) the step kernels write
+void sekf_batch_dims(const sekf_batch *h, int *n, int *m, int *ny, int64_t *batch, stpwl **model);
+double *sekf_batch_x_dev(sekf_batch *h);
+int *sekf_batch_status_dev(sekf_batch *h);
+const double *sekf_batch_C_dev(sekf_batch *h);
+const double *sekf_batch_yref_dev(sekf_batch *h);          // NULL: no y_ref
+
 namespace {
 
 struct EkfArgs {
@@ -37,9 +71,20 @@ struct EkfArgs {
     const double *Aext, *Bext, *dext;   // explicit (A_d, B_d, d_d) instead of the nearest-point tables
     int do_predict, do_update;
     int *status;
+    // the batched launch (grid = filters): element strides from one filter's x, Sigma, u, y and status word to the next (all zero
+    // for the one-filter entry points, whose grid is 1), and the table point each predictor took (one int per filter, or null)
+    long long sx, sS, su, sy, sst, sp;
+    int *pick;
 };
 
 constexpr int EKF_NT = 512;
+
+// workgroup blockIdx.x is filter blockIdx.x: C, y_ref, W, V and the model tables are shared, everything else moves by its stride
+__device__ __forceinline__ void ekf_select_filter(EkfArgs &a) {
+    const long long f = blockIdx.x;
+    a.x += f * a.sx; a.Sigma += f * a.sS; a.u += f * a.su; a.y += f * a.sy; a.status += f * a.sst;
+    if (a.pick != nullptr) a.pick += f * a.sp;
+}
 
 // length of each of ekf_kernel's four vector panels (state, predicted state, innovation, input): the input has n_u entries, and a
 // model may have more inputs than states (stpwl_create: n_u <= 16, any r)
@@ -76,6 +121,7 @@ __device__ __forceinline__ double dotk(clptr a, int sa, clptr b, int sb, int K) 
 
 __global__ __launch_bounds__(EKF_NT) void ekf_kernel(EkfArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    ekf_select_filter(a);
     const int n = a.n, m = a.m, ny = a.ny, ld = a.ld, ldy = a.ldy;
     const int tid = threadIdx.x, nt = blockDim.x;
     lptr Sg = (lptr)smem;                 // Sigma            (n x ld)
@@ -105,7 +151,7 @@ __global__ __launch_bounds__(EKF_NT) void ekf_kernel(EkfArgs a) {
         } else {
             if (tid < 64) {
                 const int i = tpwl::nearest_wave(a.T, xv);
-                if (tid == 0) ip[0] = i;
+                if (tid == 0) { ip[0] = i; if (a.pick != nullptr) *a.pick = i; }
             }
             __syncthreads();
             const int i = ip[0];
@@ -359,6 +405,7 @@ __host__ __device__ inline bool ekf_gain_gj_fits(int n, int ny, int nw, int ny16
 template <int NSEL>      // n_x fixed at compile time (the Diamond models at r = 30 / 36), or 0: any size
 __global__ __launch_bounds__(EKF_NT) void ekf_mfma_kernel(EkfArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    ekf_select_filter(a);
     const int n = NSEL > 0 ? NSEL : a.n, m = a.m, ny = a.ny;
     const EkfMfmaDims D = ekf_mfma_dims(n, ny);
     const int n16 = D.n16, ny16 = D.ny16, ld = D.ld, ldy = D.ldy, NK = D.NK, NKy = D.NKy;
@@ -405,7 +452,7 @@ __global__ __launch_bounds__(EKF_NT) void ekf_mfma_kernel(EkfArgs a) {
         __builtin_amdgcn_wave_barrier();
         if (table) {
             const int i = tpwl::nearest_wave(a.T, xv);
-            if (tid == 0) ip[0] = i;
+            if (tid == 0) { ip[0] = i; if (a.pick != nullptr) *a.pick = i; }
         }
     } else {
         const int t2 = tid - 64, nt2 = nt - 64;
@@ -604,6 +651,7 @@ __host__ __device__ inline size_t ekf_wide_doubles(int n, int ny) {
 
 __global__ __launch_bounds__(EKF_NT) void ekf_wide_kernel(EkfArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    ekf_select_filter(a);
     const int n = a.n, m = a.m, ny = a.ny;
     const int n16 = (n + 15) & ~15, ny16 = (ny + 15) & ~15, NK = (n + 3) & ~3, NKy = (ny + 3) & ~3, ld = n16 + 1, ldy = ny16 + 1;
     const int tid = threadIdx.x, nt = blockDim.x;
@@ -640,7 +688,7 @@ __global__ __launch_bounds__(EKF_NT) void ekf_wide_kernel(EkfArgs a) {
         __builtin_amdgcn_wave_barrier();
         if (table) {
             const int i = tpwl::nearest_wave(a.T, xv);
-            if (tid == 0) ip[0] = i;
+            if (tid == 0) { ip[0] = i; if (a.pick != nullptr) *a.pick = i; }
         }
     } else {
         const int t2 = tid - 64, nt2 = nt - 64;
@@ -941,6 +989,101 @@ int sekf_step(sekf_t *h, const double *u, const double *y, const double *A_d, co
     return ekf_collect(h, x_out, "sekf_step");
 }
 
+int sekf_batch_create(sekf_batch_t **out, stpwl_t *model, const double *C, const double *y_ref, int n_y, const double *Sigma0,
+                      const double *W, const double *V, int64_t batch) {
+    SRH_REQUIRE(out && model && C && Sigma0 && W && V, "sekf_batch_create: null argument");
+    SRH_REQUIRE(batch >= 1 && batch <= INT32_MAX, "sekf_batch_create: need batch >= 1 filters, got %lld", (long long)batch);
+    SRH_REQUIRE(n_y > 0 && n_y <= model->n, "sekf_batch_create: need 0 < n_y <= n_x");
+    const EkfPlan plan = ekf_plan(model->n, n_y, model->m);
+    SRH_REQUIRE(plan.path != EKF_REFUSED, "sekf_batch_create: the filter step of n_x = %d, n_y = %d does not fit the 160 KB LDS (n_x too large)",
+                model->n, n_y);
+    auto *h = new sekf_batch();
+    h->model = model; h->n = model->n; h->m = model->m; h->ny = n_y; h->batch = (int)batch;
+    h->path = plan.path; h->gain_form = plan.gain_form; h->lds = plan.lds;
+    const size_t n = h->n, B = (size_t)batch, nuy = B * (size_t)(h->m + n_y);
+    int rc;
+    if ((rc = h->C.upload(C, sizeof(double) * n_y * n)) || (rc = h->W.upload(W, sizeof(double) * n * n)) ||
+        (rc = h->V.upload(V, sizeof(double) * n_y * n_y)) || (rc = h->Sigma0.upload(Sigma0, sizeof(double) * n * n)) ||
+        (rc = h->Sigma.alloc(sizeof(double) * B * n * n)) || (rc = h->xs.alloc(h->xs_bytes())) || (rc = h->uy.alloc(sizeof(double) * nuy)) ||
+        (rc = h->pick.alloc(sizeof(int) * B)) ||
+        (y_ref && (rc = h->y_ref.upload(y_ref, sizeof(double) * n_y)))) {
+        delete h;
+        return rc;
+    }
+    auto fail = [&](const char *what) { srh::set_error("sekf_batch_create: %s failed", what); delete h; return SRH_EHIP; };
+    if (hipMemset(h->xs.p, 0, h->xs_bytes()) != hipSuccess || hipMemset(h->pick.p, 0xff, sizeof(int) * B) != hipSuccess) return fail("hipMemset");
+    if ((rc = sekf_batch_install_sigma0(h))) { delete h; return rc; }
+    if (hipHostMalloc((void **)&h->pin_in, sizeof(double) * nuy, hipHostMallocDefault) != hipSuccess) return fail("hipHostMalloc");
+    if (hipHostMalloc((void **)&h->pin_out, h->xs_bytes(), hipHostMallocDefault) != hipSuccess) return fail("hipHostMalloc");
+    if (hipFuncSetAttribute(ekf_kernel_of(h->path), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds) != hipSuccess)
+        return fail("hipFuncSetAttribute");
+    *out = h;
+    return SRH_OK;
+}
+
+int sekf_batch_destroy(sekf_batch_t *h) {
+    delete h;
+    return SRH_OK;
+}
+
+int sekf_batch_plan(sekf_batch_t *h, int *path, size_t *lds_bytes_out, int *gain_form, int64_t *batch) {
+    SRH_REQUIRE(h, "sekf_batch_plan: null argument");
+    if (path) *path = h->path;
+    if (lds_bytes_out) *lds_bytes_out = h->lds;
+    if (gain_form) *gain_form = h->gain_form;
+    if (batch) *batch = h->batch;
+    return SRH_OK;
+}
+
+int sekf_batch_set_state(sekf_batch_t *h, const double *x, const double *Sigma) {
+    SRH_REQUIRE(h && (x || Sigma), "sekf_batch_set_state: null argument");
+    const size_t B = (size_t)h->batch, n = (size_t)h->n;
+    if (x) SRH_CHECK_HIP(hipMemcpy(h->xs.p, x, sizeof(double) * B * n, hipMemcpyHostToDevice));
+    if (Sigma) SRH_CHECK_HIP(hipMemcpy(h->Sigma.p, Sigma, sizeof(double) * B * n * n, hipMemcpyHostToDevice));
+    return SRH_OK;
+}
+
+int sekf_batch_get_state(sekf_batch_t *h, double *x, double *Sigma, int *status) {
+    SRH_REQUIRE(h, "sekf_batch_get_state: null argument");
+    const size_t B = (size_t)h->batch, n = (size_t)h->n;
+    if (x) SRH_CHECK_HIP(hipMemcpy(x, h->xs.p, sizeof(double) * B * n, hipMemcpyDeviceToHost));
+    if (Sigma) SRH_CHECK_HIP(hipMemcpy(Sigma, h->Sigma.p, sizeof(double) * B * n * n, hipMemcpyDeviceToHost));
+    if (status) SRH_CHECK_HIP(hipMemcpy(status, h->status_dev(), sizeof(int) * B, hipMemcpyDeviceToHost));
+    return SRH_OK;
+}
+
+int sekf_batch_last_points(sekf_batch_t *h, int32_t *idx) {
+    SRH_REQUIRE(h && idx, "sekf_batch_last_points: null argument");
+    SRH_CHECK_HIP(hipMemcpy(idx, h->pick.p, sizeof(int32_t) * (size_t)h->batch, hipMemcpyDeviceToHost));
+    return SRH_OK;
+}
+
+int sekf_batch_step(sekf_batch_t *h, const double *u, const double *y, double *x_out) {
+    SRH_REQUIRE(h, "sekf_batch_step: null argument");
+    SRH_REQUIRE(u || y, "sekf_batch_step: need inputs (predict) and/or measurements (update)");
+    const size_t B = (size_t)h->batch, n = (size_t)h->n, m = (size_t)h->m, ny = (size_t)h->ny;
+    double *su = h->uy.as<double>(), *sy = su + B * m;
+    if (u) memcpy(h->pin_in, u, sizeof(double) * B * m);
+    if (y) memcpy(h->pin_in + B * m, y, sizeof(double) * B * ny);
+    SRH_CHECK_HIP(hipMemcpyAsync(su, h->pin_in, sizeof(double) * B * (m + ny), hipMemcpyHostToDevice, nullptr));
+    int rc = sekf_batch_step_dev(h, u ? su : nullptr, (int64_t)m, y ? sy : nullptr, (int64_t)ny, h->pick.as<int>(), 1, nullptr);
+    if (rc) return rc;
+    SRH_CHECK_HIP(hipMemcpyAsync(h->pin_out, h->xs.p, h->xs_bytes(), hipMemcpyDeviceToHost, nullptr));
+    SRH_CHECK_HIP(hipStreamSynchronize(nullptr));
+    // a failed filter kept its estimate: x_out is the resident state of every filter either way
+    if (x_out) memcpy(x_out, h->pin_out, sizeof(double) * B * n);
+    const int *st = (const int *)(h->pin_out + B * n);
+    size_t failed = 0, first = 0;
+    for (size_t b = B; b-- > 0;)
+        if (st[b] != 0) { ++failed; first = b; }
+    if (failed) {
+        srh::set_error("sekf_batch_step: innovation covariance S is not positive definite in %zu of %zu filters (first: filter %zu); "
+                       "they keep their state, sekf_batch_get_state has the status of each", failed, B, first);
+        return SRH_ENUMERIC;
+    }
+    return SRH_OK;
+}
+
 int sekf_step_projected(sekf_t *h, srom_t *rom, const double *x_full, const double *u, const double *y,
                         double *x_reduced_out, double *x_hat_out) {
     SRH_REQUIRE(h && rom && x_full && x_reduced_out, "sekf_step_projected: null argument");
@@ -965,3 +1108,45 @@ int sekf_step_projected(sekf_t *h, srom_t *rom, const double *x_full, const doub
 }
 
 }  // extern "C"
+
+int sekf_batch_install_sigma0(sekf_batch *h) {
+    const size_t nn = (size_t)h->n * h->n;
+    for (size_t b = 0; b < (size_t)h->batch; ++b)
+        SRH_CHECK_HIP(hipMemcpyAsync(h->Sigma.as<double>() + b * nn, h->Sigma0.p, sizeof(double) * nn, hipMemcpyDeviceToDevice, nullptr));
+    SRH_CHECK_HIP(hipStreamSynchronize(nullptr));
+    return SRH_OK;
+}
+
+int sekf_batch_step_dev(sekf_batch *h, const double *u_dev, int64_t su, const double *y_dev, int64_t sy, int32_t *pick_dev, int64_t sp,
+                        hipStream_t stream) {
+    SRH_REQUIRE(h && (u_dev || y_dev), "sekf_batch_step: null argument");
+    SRH_REQUIRE(!u_dev || h->model->has_discrete, "sekf_batch_step: model has not been pre-discretised (the batched filter takes the "
+                "nearest-point discrete tables only)");
+    const int n = h->n, m = h->m, ny = h->ny;
+    EkfArgs a{};
+    a.T = h->model->view();
+    a.n = n; a.m = m; a.ny = ny; a.ld = n | 1; a.ldy = ny | 1;
+    a.C = h->C.as<double>(); a.y_ref = h->y_ref.p ? h->y_ref.as<double>() : nullptr;
+    a.W = h->W.as<double>(); a.V = h->V.as<double>();
+    a.x = h->xs.as<double>(); a.Sigma = h->Sigma.as<double>();
+    // a missing operand is never read (do_predict / do_update); it still gets a valid address and no stride
+    a.u = u_dev ? u_dev : h->uy.as<double>(); a.y = y_dev ? y_dev : h->uy.as<double>();
+    a.do_predict = u_dev != nullptr; a.do_update = y_dev != nullptr;
+    a.status = h->status_dev(); a.pick = pick_dev;
+    a.sx = n; a.sS = (long long)n * n; a.su = u_dev ? su : 0; a.sy = y_dev ? sy : 0; a.sst = 1; a.sp = sp;
+    const dim3 grid((unsigned)h->batch);
+    if (h->path == EKF_MFMA60) ekf_mfma_kernel<60><<<grid, EKF_NT, h->lds, stream>>>(a);
+    else if (h->path == EKF_MFMA) ekf_mfma_kernel<0><<<grid, EKF_NT, h->lds, stream>>>(a);
+    else if (h->path == EKF_WIDE) ekf_wide_kernel<<<grid, EKF_NT, h->lds, stream>>>(a);
+    else ekf_kernel<<<grid, EKF_NT, h->lds, stream>>>(a);
+    SRH_CHECK_HIP(hipGetLastError());
+    return SRH_OK;
+}
+
+void sekf_batch_dims(const sekf_batch *h, int *n, int *m, int *ny, int64_t *batch, stpwl **model) {
+    *n = h->n; *m = h->m; *ny = h->ny; *batch = h->batch; *model = h->model;
+}
+double *sekf_batch_x_dev(sekf_batch *h) { return h->xs.as<double>(); }
+int *sekf_batch_status_dev(sekf_batch *h) { return h->status_dev(); }
+const double *sekf_batch_C_dev(sekf_batch *h) { return h->C.as<double>(); }
+const double *sekf_batch_yref_dev(sekf_batch *h) { return h->y_ref.p ? h->y_ref.as<double>() : nullptr; }

@@ -4,7 +4,11 @@ Every rollout of a resident TPWL `GuSTO(batch=B)` is its own loop -- plan, apply
 `dt_sim` under the scp controller's feedback law u = u_bar(t) + K[i_near(x_bar(t))] (x - x_bar(t)) (tpwl/controllers.py:298-333), shift
 the plan (scp/ros.py:110-114), re-plan from the plant state: the reference's `mpc=True` policy with perfect state feedback.  `run(periods)`
 is one launch sequence on the handle's stream and ONE host wait; only the records of the run cross PCIe.  What is shared by all loops --
-the times of a period -- is computed on the host in float64 (`schedule`)."""
+the times of a period -- is computed on the host in float64 (`schedule`).
+
+With `observer=` (a tpwl.observer.DiscreteEKFObserverBatch) the loop is the reference's output-feedback loop (tpwl/controllers.py:85-117):
+the plans start from the filters' estimates, the law reads the estimate, and every plant step is followed by a measurement
+y = C x + y_ref (+ v) and one step of every filter -- still one host wait per run."""
 import collections
 import ctypes as C
 
@@ -40,17 +44,23 @@ class ClosedLoopResult:
     """Records of one `run`: x (B, S + 1, n_x) or None, z (B, S + 1, n_z), u (B, S, n_u) with S = periods n_keep (row 0: the state the run
     started from); iters, status, J (periods, B) of the solves; t (S + 1,) the times of the rows."""
 
-    def __init__(self, x, z, u, iters, status, J, t):
+    def __init__(self, x, z, u, iters, status, J, t, x_hat=None, y=None, ekf_status=None):
         self.x, self.z, self.u, self.iters, self.status, self.J, self.t = x, z, u, iters, status, J, t
+        # the observed loop (None without an observer): x_hat (B, S + 1, n_x) the estimates, row 0 those the run started from; y (B, S,
+        # n_y) the measurements; ekf_status (periods, B) the OR of the period's filter statuses
+        self.x_hat, self.y, self.ekf_status = x_hat, y, ekf_status
 
 
 class ClosedLoopBatch:
-    def __init__(self, gusto, plant, dt_sim, n_keep, t=None, z=None, u=None, phase=None, K=None, max_steps_per_run=None):
+    def __init__(self, gusto, plant, dt_sim, n_keep, t=None, z=None, u=None, phase=None, K=None, max_steps_per_run=None, observer=None):
         """gusto: a GuSTO on a TPWLGuSTO model with batch=B (the fused resident plan); plant: a TPWLATV (it may be the planner's own
         dyn_sys), stepped at dt_sim; n_keep: plant steps per period (the reference's N_replan with the controller clock at dt_sim).
         t (T,), z (T, n_z), u (T, n_u): the target table, interpolated as scp/standalone.py:29-31 does; phase (B,): a time offset of
         every loop's target; K: the per-point gains of the scp controller (list of (n_u, n_x), or (P, n_u, n_x)), None: u = u_bar.
-        max_steps_per_run: the longest run in plant steps (sizes the record blocks; default 16 periods)."""
+        max_steps_per_run: the longest run in plant steps (sizes the record blocks; default 16 periods).
+        observer: a DiscreteEKFObserverBatch of the same batch, n_x and n_u; its model is stepped at dt_sim (it may be the planner's
+        dyn_sys, and it need not be the plant).  The loop binds it to dt_sim and steps it on its own stream: do not step it elsewhere
+        while the loop is in use."""
         if not (getattr(gusto, '_fused', False) and not getattr(gusto, '_ssm', False)):
             raise RuntimeError('ClosedLoopBatch needs a GuSTO on a TPWLGuSTO model with a fused resident plan (not an SSM plan, not '
                                'the host loop): there is no device rollout / solve to chain otherwise')
@@ -60,7 +70,12 @@ class ClosedLoopBatch:
         if n_keep * float(dt_sim) > gusto.N * float(gusto.dt):
             raise RuntimeError('ClosedLoopBatch: n_keep * dt_sim = %g exceeds the horizon N * dt = %g (the shift of the previous plan '
                                'would find no row)' % (n_keep * float(dt_sim), gusto.N * float(gusto.dt)))
-        self.gusto, self.plant = gusto, plant                  # (kept alive: the handle points into both)
+        if observer is not None:
+            shape = (getattr(observer, 'batch', None), getattr(observer, 'state_dim', None), getattr(observer, 'input_dim', None))
+            if shape != (gusto.batch, gusto.n_x, gusto.n_u):
+                raise RuntimeError('ClosedLoopBatch: the observer has batch = %s, n_x = %s, n_u = %s; the loop needs batch = %d, n_x = %d, '
+                                   'n_u = %d' % (shape + (gusto.batch, gusto.n_x, gusto.n_u)))
+        self.gusto, self.plant, self.observer = gusto, plant, observer       # (kept alive: the handle points into all three)
         self.B, self.N, self.dt = gusto.batch, gusto.N, float(gusto.dt)
         self.n_x, self.n_u, self.n_z = gusto.n_x, gusto.n_u, gusto.n_z
         self.dt_sim, self.n_keep = float(dt_sim), n_keep
@@ -88,6 +103,11 @@ class ClosedLoopBatch:
             if K.shape[0] != gusto.model.dyn_sys.num_points:
                 raise RuntimeError('ClosedLoopBatch: K has %d gains, the planner\'s model %d points' % (K.shape[0], gusto.model.dyn_sys.num_points))
             _lib.check(lib.sgusto_loop_set_feedback(self._h, _lib.dptr(K)), 'sgusto_loop_set_feedback')
+        self.n_y = None
+        if observer is not None:
+            observer.bind(self.dt_sim)
+            self.n_y = observer.meas_dim
+            _lib.check(lib.sgusto_loop_set_observer(self._h, observer._h), 'sgusto_loop_set_observer')
 
     def __del__(self):
         try:
@@ -98,12 +118,33 @@ class ClosedLoopBatch:
             pass
 
     def reset(self, x0, t_start=0.0):
+        """Plant states x0 (B, n_x) at t_start.  With an observer: reset_observed(x0, None, t_start) -- the estimates start at x0."""
+        if self.observer is not None:
+            return self.reset_observed(x0, None, t_start)
         x0 = _lib.f64(np.asarray(x0).reshape(self.B, self.n_x))
         _lib.check(_lib.lib().sgusto_loop_reset(self._h, _lib.dptr(x0), C.c_double(float(t_start))), 'sgusto_loop_reset')
         self.t_start, self._k = float(t_start), 0
 
+    def reset_observed(self, x0, x_hat0=None, t_start=0.0):
+        """Plant states x0 and estimates x_hat0 (B, n_x; None: x0) at t_start.  x_hat0 is the caller's statement of where the reference's
+        first observer.update at t = 0 leaves the filters; their covariances are re-installed from Sigma0, so a run is reproducible."""
+        if self.observer is None:
+            raise RuntimeError('ClosedLoopBatch.reset_observed: the loop has no observer (ClosedLoopBatch(..., observer=...))')
+        x0 = _lib.f64(np.asarray(x0).reshape(self.B, self.n_x))
+        if x_hat0 is not None:
+            x_hat0 = np.asarray(x_hat0)
+            if x_hat0.shape != (self.B, self.n_x):
+                raise RuntimeError('ClosedLoopBatch.reset_observed: x_hat0 must have shape (B, n_x) = %s, got %s' % ((self.B, self.n_x), x_hat0.shape))
+            x_hat0 = _lib.f64(x_hat0)
+        _lib.check(_lib.lib().sgusto_loop_reset_observed(self._h, _lib.dptr(x0), _lib.dptr(x_hat0), C.c_double(float(t_start))),
+                   'sgusto_loop_reset_observed')
+        self.t_start, self._k = float(t_start), 0
+
     def run(self, periods, W=None, record_x=True):
-        """`periods` periods from where the last run ended.  W (periods, n_keep, B, n_x): added to the plant's next state."""
+        """`periods` periods from where the last run ended.  W (periods, n_keep, B, n_x): added to the plant's next state.
+        With an observer: run_observed without measurement noise."""
+        if self.observer is not None:
+            return self.run_observed(periods, W=W, V=None, record_x=record_x)
         periods = int(periods)
         B, S = self.B, periods * self.n_keep
         if periods >= 1 and S <= self.max_steps_per_run:       # (what does not fit is refused by the library, with its message)
@@ -123,6 +164,38 @@ class ClosedLoopBatch:
         t = schedule(self.N, self.dt, self.dt_sim, self.n_keep, self.t_start, self._k).t_k + self.dt_sim * np.arange(S + 1)
         self._k += periods
         return ClosedLoopResult(x, z, u, iters, status, J, t)
+
+    def run_observed(self, periods, W=None, V=None, record_x=True):
+        """run with the filters in the loop.  V (periods, n_keep, B, n_y): measurement noise, None: zero.  The result carries x_hat, y
+        and ekf_status."""
+        if self.observer is None:
+            raise RuntimeError('ClosedLoopBatch.run_observed: the loop has no observer (ClosedLoopBatch(..., observer=...))')
+        periods = int(periods)
+        B, S = self.B, periods * self.n_keep
+        if V is not None:
+            V = np.asarray(V)
+            if V.shape != (periods, self.n_keep, B, self.n_y):
+                raise RuntimeError('ClosedLoopBatch.run_observed: V must have shape (periods, n_keep, B, n_y) = %s, got %s'
+                                   % ((periods, self.n_keep, B, self.n_y), V.shape))
+            V = _lib.f64(V)
+        if periods >= 1 and S <= self.max_steps_per_run:       # (what does not fit is refused by the library, with its message)
+            x = np.empty((B, S + 1, self.n_x)) if record_x else None
+            z, u = np.empty((B, S + 1, self.n_z)), np.empty((B, S, self.n_u))
+            iters, status, es = (np.empty((periods, B), dtype=np.int32) for _ in range(3))
+            J, xh, y = np.empty((periods, B)), np.empty((B, S + 1, self.n_x)), np.empty((B, S, self.n_y))
+            W = None if W is None else _lib.f64(np.asarray(W).reshape(periods, self.n_keep, B, self.n_x))
+        else:
+            x = W = V = None
+            z = u = J = xh = y = np.empty(1)
+            iters = status = es = np.empty(1, dtype=np.int32)
+        lib = _lib.lib()
+        _lib.check(lib.sgusto_plan_set_max_iters(self.gusto.plan, C.c_int(int(self.gusto.max_gusto_iters))), 'set_max_iters')
+        _lib.check(lib.sgusto_loop_run_observed(self._h, C.c_int(periods), _lib.dptr(W), _lib.dptr(V), _lib.dptr(x), _lib.dptr(z), _lib.dptr(u),
+                                                _lib.iptr(iters), _lib.iptr(status), _lib.dptr(J), _lib.dptr(xh), _lib.dptr(y), _lib.iptr(es)),
+                   'sgusto_loop_run_observed')
+        t = schedule(self.N, self.dt, self.dt_sim, self.n_keep, self.t_start, self._k).t_k + self.dt_sim * np.arange(S + 1)
+        self._k += periods
+        return ClosedLoopResult(x, z, u, iters, status, J, t, x_hat=xh, y=y, ekf_status=es)
 
     def step(self):
         return self.run(1)
@@ -160,3 +233,23 @@ class ClosedLoopBatch:
         _lib.check(_lib.lib().sgusto_loop_advance(self._h, _lib.dptr(xopt), _lib.dptr(uopt), _lib.dptr(x), _lib.dptr(W), _lib.dptr(X),
                                                   _lib.dptr(Z), _lib.dptr(U), _lib.iptr(ip), _lib.iptr(ig)), 'sgusto_loop_advance')
         return X, Z, U, ip, ig
+
+    def _advance_observed(self, xopt, uopt, x, x_hat, W=None, V=None):
+        """The observed sub-step chain alone on host-supplied plans, states and estimates (for tests; the filters start from x_hat and
+        Sigma0, and the loop needs a reset afterwards) -> dict X, Z, U, Xhat (B, n_keep, .), Y (B, n_keep, n_y), idx_plant, idx_gain,
+        idx_filter (B, n_keep), ekf_status (B,)."""
+        B, N, nk = self.B, self.N, self.n_keep
+        xopt = _lib.f64(np.asarray(xopt).reshape(B, N + 1, self.n_x)); uopt = _lib.f64(np.asarray(uopt).reshape(B, N, self.n_u))
+        x, x_hat = _lib.f64(np.asarray(x).reshape(B, self.n_x)), _lib.f64(np.asarray(x_hat).reshape(B, self.n_x))
+        W = None if W is None else _lib.f64(np.asarray(W).reshape(nk, B, self.n_x))
+        V = None if V is None else _lib.f64(np.asarray(V).reshape(nk, B, self.n_y))
+        X, Z, U = np.empty((B, nk, self.n_x)), np.empty((B, nk, self.n_z)), np.empty((B, nk, self.n_u))
+        Xh, Y = np.empty((B, nk, self.n_x)), np.empty((B, nk, self.n_y))
+        ip, ig, jf = (np.empty((B, nk), dtype=np.int32) for _ in range(3))
+        es = np.empty(B, dtype=np.int32)
+        _lib.check(_lib.lib().sgusto_loop_advance_observed(self._h, _lib.dptr(xopt), _lib.dptr(uopt), _lib.dptr(x), _lib.dptr(x_hat), _lib.dptr(W),
+                                                           _lib.dptr(V), _lib.dptr(X), _lib.dptr(Z), _lib.dptr(U), _lib.dptr(Xh), _lib.dptr(Y),
+                                                           _lib.iptr(ip), _lib.iptr(ig), _lib.iptr(jf), _lib.iptr(es)),
+                   'sgusto_loop_advance_observed')
+        self._k = None
+        return dict(X=X, Z=Z, U=U, Xhat=Xh, Y=Y, idx_plant=ip, idx_gain=ig, idx_filter=jf, ekf_status=es)
