@@ -221,7 +221,8 @@ int sekf_destroy(sekf_t *h);
  * n_y measurements runs.  path: 0 refused (bad sizes, or the step does not fit the 160 KB LDS), 1 VALU (ekf_kernel),
  * 2 MFMA generic (ekf_mfma_kernel<0>), 3 MFMA n_x = 60 (ekf_mfma_kernel<60>), 4 wide (ekf_wide_kernel).  lds_bytes: the
  * dynamic LDS of the launch (for the VALU layout with the largest n_u a model can have, 16; 0 when refused).  gain_form:
- * 0 Gauss-Jordan elimination on all waves, 1 one-wave Cholesky.  Honours SRH_EKF_NO_MFMA.  Any output may be NULL. */
+ * 0 Gauss-Jordan elimination on all waves (paths 2 to 4: a shape is put there only if the elimination fits it), 1 one-wave
+ * Cholesky (path 1).  Honours SRH_EKF_NO_MFMA.  Any output may be NULL. */
 int sekf_plan(int n_x, int n_y, int *path, size_t *lds_bytes, int *gain_form);
 /* the same for a live handle: what sekf_create decided (with the model's own n_u) */
 int sekf_handle_plan(sekf_t *h, int *path, size_t *lds_bytes, int *gain_form);

@@ -4,17 +4,7 @@
 // tpwl/controllers.py:298-333 (the scp controller's interpolated plan and feedback law), tpwl/tpwl.py:160-168, 336-339 (plant step).
 // The solve itself is sgusto_plan_solve_dev (gusto.hip); this unit is the glue around it: loop_prepare_kernel turns the previous
 // period's output into the next solve's input, loop_advance_kernel runs the plant under the feedback law for the n_keep sub-steps.
-#include "tpwl_host.h"
-
-// observer.hip: the batched filter's device-side step and what the observed loop needs of its handle
-int sekf_batch_step_dev(sekf_batch *h, const double *u_dev, int64_t su, const double *y_dev, int64_t sy, int32_t *pick_dev, int64_t sp,
-                        hipStream_t stream);
-int sekf_batch_install_sigma0(sekf_batch *h);
-void sekf_batch_dims(const sekf_batch *h, int *n, int *m, int *ny, int64_t *batch, stpwl **model);
-double *sekf_batch_x_dev(sekf_batch *h);
-int *sekf_batch_status_dev(sekf_batch *h);
-const double *sekf_batch_C_dev(sekf_batch *h);
-const double *sekf_batch_yref_dev(sekf_batch *h);
+#include "observer_host.h"
 
 namespace {
 
@@ -332,7 +322,7 @@ struct sgusto_loop {
     // v: the arguments of the whole period (records, plan, W / Vn, x_in / x_out); XH / xh_rows / xh_row0: the estimate record and the
     // row of sub-step 0's estimate; E: the period's status entry (B); pick: (B x n_keep) filter regions or null.
     int launch_observed_chain(AdvArgs v, double *XH, int64_t xh_rows, int64_t xh_row0, int32_t *E, int32_t *pick) const {
-        v.xhat = sekf_batch_x_dev(obs); v.C = sekf_batch_C_dev(obs); v.y_ref = sekf_batch_yref_dev(obs); v.ny = ny;
+        v.xhat = obs->x_dev(); v.C = obs->C.as<double>(); v.y_ref = obs->yref_dev(); v.ny = ny;
         int rc;
         for (int s = 0; s < n_keep; ++s) {
             v.s0 = s; v.s1 = s + 1;
@@ -341,7 +331,7 @@ struct sgusto_loop {
             if ((rc = sekf_batch_step_dev(obs, v.U + (size_t)(v.row0_u + s) * m, v.rows_u * m, v.Y + (size_t)(v.row0_u + s) * ny, v.rows_u * ny,
                                           pick ? pick + s : nullptr, n_keep, stream)))
                 return rc;
-            loop_estimate_record_kernel<<<(unsigned)B, 64, 0, stream>>>(v.xhat, sekf_batch_status_dev(obs), XH, E, n, xh_rows, xh_row0 + s,
+            loop_estimate_record_kernel<<<(unsigned)B, 64, 0, stream>>>(v.xhat, obs->status_dev(), XH, E, n, xh_rows, xh_row0 + s,
                                                                        s == 0 ? 1 : 0);
             SRH_CHECK_HIP(hipGetLastError());
         }
@@ -488,7 +478,7 @@ static int loop_run(sgusto_loop_t *h, int periods, const double *W, const double
     if (W && ((rc = h->pW.need(D * h->max_steps * B * n)) || (!h->Wd.p && (rc = h->Wd.alloc(D * h->max_steps * B * n))))) return rc;
     const size_t ny = (size_t)h->ny;
     if (Vn && ((rc = h->pV.need(D * h->max_steps * B * ny)) || (!h->Vd.p && (rc = h->Vd.alloc(D * h->max_steps * B * ny))))) return rc;
-    double *xhat = observed ? sekf_batch_x_dev(h->obs) : nullptr;
+    double *xhat = observed ? h->obs->x_dev() : nullptr;
     h->waits = 0;
     hipStream_t st = h->stream;
     // from here on work is enqueued on the handle's stream: on any error it is drained before returning
@@ -598,14 +588,12 @@ int sgusto_loop_set_observer(sgusto_loop_t *h, sekf_batch_t *observer) {
     SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
     h->obs = nullptr; h->observed_state = false;
     if (!observer) return SRH_OK;
-    int n, m, ny;
-    int64_t B;
-    stpwl *model;
-    sekf_batch_dims(observer, &n, &m, &ny, &B, &model);
-    SRH_REQUIRE(B == h->B, "sgusto_loop_set_observer: the observer has batch = %lld filters, the loop %lld members", (long long)B, (long long)h->B);
+    const int n = observer->n, m = observer->m, ny = observer->ny;
+    SRH_REQUIRE(observer->batch == h->B, "sgusto_loop_set_observer: the observer has batch = %lld filters, the loop %lld members",
+                (long long)observer->batch, (long long)h->B);
     SRH_REQUIRE(n == h->n && m == h->m, "sgusto_loop_set_observer: the observer's model has n_x = %d, n_u = %d, the loop n_x = %d, n_u = %d", n, m,
                 h->n, h->m);
-    SRH_REQUIRE(model->has_discrete, "sgusto_loop_set_observer: the observer's model has not been pre-discretised (at dt_sim)");
+    SRH_REQUIRE(observer->model->has_discrete, "sgusto_loop_set_observer: the observer's model has not been pre-discretised (at dt_sim)");
     const size_t D = sizeof(double), S = (size_t)h->max_steps, P = S / h->n_keep, Bz = (size_t)h->B;
     h->lds_obs = advance_lds_bytes(h->n, h->m, true);
     SRH_REQUIRE(h->lds_obs <= (size_t)160 * 1024, "sgusto_loop_set_observer: the observed advance kernel needs %zu bytes of LDS (160 KiB available)",
@@ -625,7 +613,7 @@ int sgusto_loop_reset_observed(sgusto_loop_t *h, const double *x0, const double 
     int rc = sgusto_loop_reset(h, x0, t_start);
     if (rc) return rc;
     h->have_state = false;
-    SRH_CHECK_HIP(hipMemcpy(sekf_batch_x_dev(h->obs), x_hat0 ? x_hat0 : x0, sizeof(double) * h->B * h->n, hipMemcpyHostToDevice));
+    SRH_CHECK_HIP(hipMemcpy(h->obs->x_dev(), x_hat0 ? x_hat0 : x0, sizeof(double) * h->B * h->n, hipMemcpyHostToDevice));
     if ((rc = sekf_batch_install_sigma0(h->obs))) return rc;
     h->have_state = true; h->observed_state = true;
     return SRH_OK;
@@ -703,7 +691,7 @@ int sgusto_loop_advance_observed(sgusto_loop_t *h, const double *xopt, const dou
     SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
     // the attached filters start from x_hat and Sigma0; the loop's own state is no longer the one the caller knows
     h->have_state = false;
-    SRH_CHECK_HIP(hipMemcpy(sekf_batch_x_dev(h->obs), x_hat, D * B * n, hipMemcpyHostToDevice));
+    SRH_CHECK_HIP(hipMemcpy(h->obs->x_dev(), x_hat, D * B * n, hipMemcpyHostToDevice));
     srh::DevBuf dxo, duo, dx, dW, dV, dX, dZ, dU, dXH, dY, dp, dg, df, dE;
     int rc;
     if ((rc = sekf_batch_install_sigma0(h->obs)) || (rc = dxo.upload(xopt, D * B * (N + 1) * n)) || (rc = duo.upload(uopt, D * B * N * m)) ||

@@ -2,63 +2,11 @@
 // Reference: sofacontrol/tpwl/observer.py:33-126 (DiscreteEKFObserver): predict_state 97-106,
 // update_state 108-126.  One workgroup per filter step; every matrix of the step lives in LDS.  A batch of filters over one model
 // (sekf_batch) is the same kernels launched with one workgroup per filter.
-#include "tpwl_host.h"
+#include "observer_host.h"
 
 // pod.hip: two-phase staged projection (enqueue on a stream; read the pinned mirror once that stream has drained)
 int srom_stage_project(srom *h, int which, const double *X, int64_t B, hipStream_t stream);
 int srom_stage_collect(srom *h, double *out, int64_t B, int which);
-
-struct sekf {
-    stpwl *model = nullptr;
-    int n = 0, m = 0, ny = 0;
-    srh::DevBuf C, y_ref, W, V, x, Sigma, scratch, ext;
-    size_t lds = 0;
-    int path = 0, gain_form = 0;          // the kernel of this filter: ekf_plan (EKF_VALU .. EKF_WIDE)
-    // pinned host mirrors of the per-step input (u, y) and output (x, status): one copy each way per step
-    double *pin_in = nullptr, *pin_out = nullptr;
-    hipStream_t side = nullptr;          // sekf_step_projected: the projection runs beside the filter kernel
-
-    hipEvent_t side_gate = nullptr;    // orders the side stream behind earlier work of stream 0 on the same rom
-    ~sekf() {
-        if (side) (void)hipStreamDestroy(side);
-        if (side_gate) (void)hipEventDestroy(side_gate);
-        if (pin_in) (void)hipHostFree(pin_in);
-        if (pin_out) (void)hipHostFree(pin_out);
-    }
-};
-
-// `batch` filters over one model, one launch per step: workgroup b is filter b.  C, y_ref, W, V and the model tables are shared;
-// x, Sigma and the status word are per filter.
-struct sekf_batch {
-    stpwl *model = nullptr;
-    int n = 0, m = 0, ny = 0, batch = 0;
-    // xs: [x (batch x n) | status (batch int32)]: one copy back; uy: [u (batch x m) | y (batch x ny)]: the host step's inputs;
-    // pick: the table point of each filter's last predictor (batch int32)
-    srh::DevBuf C, y_ref, W, V, Sigma0, Sigma, xs, uy, pick;
-    size_t lds = 0;
-    int path = 0, gain_form = 0;
-    double *pin_in = nullptr, *pin_out = nullptr;               // pinned mirrors of uy and xs
-    int *status_dev() const { return (int *)(xs.as<double>() + (size_t)batch * n); }
-    size_t xs_bytes() const { return sizeof(double) * (size_t)batch * n + sizeof(int) * (size_t)batch; }
-    ~sekf_batch() {
-        if (pin_in) (void)hipHostFree(pin_in);
-        if (pin_out) (void)hipHostFree(pin_out);
-    }
-};
-
-// One step of every filter of the batch on `stream`, from device inputs: one launch, no copy, no wait (gusto_loop.hip chains it behind
-// its advance kernel).  u_dev / y_dev: filter b reads u_dev + b su (n_u entries) and y_dev + b sy (n_y entries); NULL: no predictor / no
-// update.  pick_dev (optional): the table point filter b's predictor took goes to pick_dev[b sp].
-int sekf_batch_step_dev(sekf_batch *h, const double *u_dev, int64_t su, const double *y_dev, int64_t sy, int32_t *pick_dev, int64_t sp,
-                        hipStream_t stream);
-// Sigma0 into every filter (device copies on stream 0, waited for)
-int sekf_batch_install_sigma0(sekf_batch *h);
-// shapes, and the resident estimates (batch x n_x) and status words (batch) the step kernels write
-void sekf_batch_dims(const sekf_batch *h, int *n, int *m, int *ny, int64_t *batch, stpwl **model);
-double *sekf_batch_x_dev(sekf_batch *h);
-int *sekf_batch_status_dev(sekf_batch *h);
-const double *sekf_batch_C_dev(sekf_batch *h);
-const double *sekf_batch_yref_dev(sekf_batch *h);          // NULL: no y_ref
 
 namespace {
 
@@ -84,6 +32,20 @@ __device__ __forceinline__ void ekf_select_filter(EkfArgs &a) {
     const long long f = blockIdx.x;
     a.x += f * a.sx; a.Sigma += f * a.sS; a.u += f * a.su; a.y += f * a.sy; a.status += f * a.sst;
     if (a.pick != nullptr) a.pick += f * a.sp;
+}
+
+// the exit of a failed factorisation / elimination (ip[1] set): the status word says so, x and Sigma keep their values in HBM
+__device__ __forceinline__ bool ekf_failed(const EkfArgs &a, liptr ip) {
+    if (ip[1] == 0) return false;
+    if (threadIdx.x == 0) *a.status = 1;
+    return true;
+}
+
+// a step without an update: the covariance panel (pitch ld) and the state panel go back to HBM as they are
+__device__ __forceinline__ void ekf_store_no_update(const EkfArgs &a, int n, clptr Sg, int ld, clptr xv) {
+    const int tid = threadIdx.x, nt = blockDim.x;
+    for (int e = tid; e < n * n; e += nt) a.Sigma[e] = Sg[(e / n) * ld + e % n];
+    for (int e = tid; e < n; e += nt) a.x[e] = xv[e];
 }
 
 // length of each of ekf_kernel's four vector panels (state, predicted state, innovation, input): the input has n_u entries, and a
@@ -227,10 +189,7 @@ __global__ __launch_bounds__(EKF_NT) void ekf_kernel(EkfArgs a) {
             }
         }
         __syncthreads();
-        if (ip[1] != 0) {
-            if (tid == 0) *a.status = 1;
-            return;
-        }
+        if (ekf_failed(a, ip)) return;
         // K row i: solve k S = M1_i  <=>  S k^T = M1_i^T  (S = L L^T), in place; the inner products run with
         // several operand pairs in flight (dotk), only the ny substitution steps are sequential
         for (int i = tid; i < n; i += nt) {
@@ -263,7 +222,7 @@ __global__ __launch_bounds__(EKF_NT) void ekf_kernel(EkfArgs a) {
 //   U = Sigma A^T (Lm = Sigma, symmetric; Rm = A^T from the transposed table), Sigma^- = A U (Lm = A^T, Rm = U),
 //   M1 = Sigma^- C^T (Lm = Sigma^-, Rm = C^T), CS = C Sigma^- (Lm = C^T, Rm = Sigma^-), S = C M1 (Lm = C^T, Rm = M1),
 //   Sigma = Sigma^- - K CS with K^T = S^-1 CS (Lm = K^T, Rm = CS).
-// S^-1 through the Cholesky factor and its explicit triangular inverse, both by one wave (n_y <= 64).
+// K^T by ekf_gain_gj<4, 2>, whose precondition on (n_x, n_y) is part of the dispatch (ekf_gain_fits, ekf_plan).
 struct EkfMfmaDims {
     int n16, ny16, ld, ldy, NK, NKy;
 };
@@ -388,18 +347,50 @@ __device__ __forceinline__ bool ekf_gain_gj(clptr Sm, int ldy, int ny, clptr CS,
 #define EKF_LAP(i) ((void)0)
 #endif
 
-// Whether ekf_mfma_kernel takes the Gauss-Jordan gain (ekf_gain_gj<4, 2>: four rows per wave, two register chunks of 64 columns, its
-// double buffer inside the two cleared panels Li | LiT) or its one-wave Cholesky branch.  nw: waves of the workgroup.  One statement
-// of the condition for the kernel and for the host's ekf_plan; every shape the dispatch puts on the MFMA path satisfies it
-// (tests/test_ekf_reference_cpu.py enumerates them), so the Cholesky branch is dead code.
-// The kernel expands the macro in place and the host goes through the inline predicate: called as a function -- always_inline
-// included -- the same condition reaches the branch as a value and hipcc (ROCm 7.2) allocates the registers of both instantiations
-// differently; the device assembly of this kernel was to stay what it was.
-#define EKF_GAIN_GJ_FITS(n, ny, nw, ny16, ldy) \
-    ((ny) <= 4 * (nw) && (ny) <= 64 && (ny) + (n) <= 128 && 2 * ((ny) + (n) + 4 * (nw)) + 128 <= 2 * (ny16) * (ldy))
+// ---- what ekf_mfma_kernel and ekf_wide_kernel share line for line (their product sequences, panel carves and B u + d differ)
+// Every global operand that does not depend on the nearest-point index is requested at kernel entry, into registers, so that the
+// HBM / L2 latency (~2-4 k clocks each when exposed) is paid once: W, C, V, y - y_ref.  K slots per thread: K blockDim.x >= count.
+template <int K>
+__device__ __forceinline__ void ekf_preload(double (&reg)[K], const double *g, int count) {
+    const int tid = threadIdx.x, nt = blockDim.x;
+#pragma unroll
+    for (int k = 0; k < K; ++k) reg[k] = tid + k * nt < count ? g[tid + k * nt] : 0.0;
+}
 
-__host__ __device__ inline bool ekf_gain_gj_fits(int n, int ny, int nw, int ny16, int ldy) {
-    return EKF_GAIN_GJ_FITS(n, ny, nw, ny16, ldy);
+// P (rows x cols, pitch ldp) += the preloaded matrix
+template <int K>
+__device__ __forceinline__ void ekf_add_preloaded(lptr P, int ldp, int rows, int cols, const double (&reg)[K]) {
+    const int tid = threadIdx.x, nt = blockDim.x;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int e = tid + k * nt;
+        if (e < rows * cols) P[(e / cols) * ldp + e % cols] += reg[k];
+    }
+}
+
+// wave 0 at kernel entry: state and input into their panels, the failure flag cleared and, for a table predictor, the nearest table
+// point into ip[0] (and to the caller's pick).  The other waves fill the panels meanwhile: none of these LDS words is theirs.
+__device__ __forceinline__ void ekf_wave0_prologue(const EkfArgs &a, int n, int m, lptr xv, lptr uv, liptr ip) {
+    const int tid = threadIdx.x;
+    for (int e = tid; e < n; e += 64) xv[e] = a.x[e];
+    if (a.do_predict)
+        for (int e = tid; e < m; e += 64) uv[e] = a.u[e];
+    if (tid == 0) ip[1] = 0;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (a.do_predict && a.Aext == nullptr) {
+        const int i = tpwl::nearest_wave(a.T, xv);
+        if (tid == 0) { ip[0] = i; if (a.pick != nullptr) *a.pick = i; }
+    }
+}
+
+// waves 1..: Sigma (n x n) into its zero-padded panel (rows x ld)
+__device__ __forceinline__ void ekf_load_sigma(lptr SG, int rows, int ld, int n, const double *Sigma) {
+    const int t2 = threadIdx.x - 64, nt2 = blockDim.x - 64;
+    for (int e = t2; e < rows * ld; e += nt2) {
+        const int i = e / ld, j = e - i * ld;
+        SG[e] = (i < n && j < n) ? Sigma[i * n + j] : 0.0;
+    }
 }
 
 template <int NSEL>      // n_x fixed at compile time (the Diamond models at r = 30 / 36), or 0: any size
@@ -409,58 +400,34 @@ __global__ __launch_bounds__(EKF_NT) void ekf_mfma_kernel(EkfArgs a) {
     const int n = NSEL > 0 ? NSEL : a.n, m = a.m, ny = a.ny;
     const EkfMfmaDims D = ekf_mfma_dims(n, ny);
     const int n16 = D.n16, ny16 = D.ny16, ld = D.ld, ldy = D.ldy, NK = D.NK, NKy = D.NKy;
-    const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63;
+    const int tid = threadIdx.x, nt = blockDim.x;
     lptr SG = (lptr)smem;                       // Sigma, then Sigma^-                         (n16 x ld)
     lptr AT = SG + (size_t)n16 * ld;            // A^T, then C^T, then K CS                    (n16 x ld)
-    lptr UU = AT + (size_t)n16 * ld;            // U = Sigma A^T, then M1, then Y | K^T        (n16 x ld)
+    lptr UU = AT + (size_t)n16 * ld;            // U = Sigma A^T, then M1, then K^T            (n16 x ld)
     lptr CS = UU + (size_t)n16 * ld;            // C Sigma^-                                   (ny16 x ld)
-    lptr Sm = CS + (size_t)ny16 * ld;           // S, then its Cholesky factor L (lower)       (ny16 x ldy)
-    lptr Li = Sm + (size_t)ny16 * ldy;          // L^-1 (lower)
-    lptr LiT = Li + (size_t)ny16 * ldy;         // L^-T
+    lptr Sm = CS + (size_t)ny16 * ld;           // S                                           (ny16 x ldy)
+    lptr GB = Sm + (size_t)ny16 * ldy;          // elimination buffer                          (2 ny16 x ldy)
     const int nv = n16 > ny16 ? n16 : ny16;
-    lptr xv = LiT + (size_t)ny16 * ldy, xn = xv + nv, iv = xn + nv, uv = iv + nv;
+    lptr xv = GB + 2 * (size_t)ny16 * ldy, xn = xv + nv, iv = xn + nv, uv = iv + nv;
     liptr ip = (liptr)(uv + nv);
 
 #ifdef SRH_PROFILE
     long long ekp[16] = {0}, ekl = clock64();
 #endif
-    // Every global operand that does not depend on the nearest-point index is requested now, into registers, so that
-    // the HBM / L2 latency (~2-4 k clocks each when exposed) is paid once: W, C, V, y - y_ref.  n <= 64, nt = 512:
-    // at most 8 entries per thread each.
-    constexpr int PQ = 8;
+    constexpr int PQ = 8;                       // n <= 64, nt = 512: at most 8 entries of an n x n matrix per thread
     double wreg[PQ], creg[PQ], vreg[PQ], yreg = 0.0;
-    if (a.do_predict) {
-#pragma unroll
-        for (int k = 0; k < PQ; ++k) wreg[k] = tid + k * nt < n * n ? a.W[tid + k * nt] : 0.0;
-    }
+    if (a.do_predict) ekf_preload(wreg, a.W, n * n);
     if (a.do_update) {
-#pragma unroll
-        for (int k = 0; k < PQ; ++k) creg[k] = tid + k * nt < ny * n ? a.C[tid + k * nt] : 0.0;
-#pragma unroll
-        for (int k = 0; k < PQ; ++k) vreg[k] = tid + k * nt < ny * ny ? a.V[tid + k * nt] : 0.0;
+        ekf_preload(creg, a.C, ny * n);
+        ekf_preload(vreg, a.V, ny * ny);
         if (tid < ny) yreg = a.y[tid] - (a.y_ref ? a.y_ref[tid] : 0.0);
     }
     // wave 0: state, input and the nearest-point search; the other waves: Sigma into its zero-padded panel and the
     // clearing of every other panel (the two never touch the same LDS words, so one barrier ends both)
-    const bool table = a.do_predict && a.Aext == nullptr;
-    if (tid < 64) {
-        for (int e = tid; e < n; e += 64) xv[e] = a.x[e];
-        if (a.do_predict)
-            for (int e = tid; e < m; e += 64) uv[e] = a.u[e];
-        if (tid == 0) ip[1] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (table) {
-            const int i = tpwl::nearest_wave(a.T, xv);
-            if (tid == 0) { ip[0] = i; if (a.pick != nullptr) *a.pick = i; }
-        }
-    } else {
-        const int t2 = tid - 64, nt2 = nt - 64;
-        for (int e = t2; e < n16 * ld; e += nt2) {
-            const int i = e / ld, j = e - i * ld;
-            SG[e] = (i < n && j < n) ? a.Sigma[i * n + j] : 0.0;
-        }
-        for (int e = t2; e < 2 * n16 * ld + ny16 * ld + 3 * ny16 * ldy; e += nt2) AT[e] = 0.0;
+    if (tid < 64) ekf_wave0_prologue(a, n, m, xv, uv, ip);
+    else {
+        ekf_load_sigma(SG, n16, ld, n, a.Sigma);
+        for (int e = tid - 64; e < 2 * n16 * ld + ny16 * ld + 3 * ny16 * ldy; e += nt - 64) AT[e] = 0.0;
     }
     __syncthreads();
     EKF_LAP(0);
@@ -490,11 +457,7 @@ __global__ __launch_bounds__(EKF_NT) void ekf_mfma_kernel(EkfArgs a) {
         wg::mfma_atb(UU, ld, SG, AT, NK, n16 >> 4, n16 >> 4, ld, n);            // U = Sigma A^T
         wg::mfma_atb(SG, ld, AT, UU, NK, n16 >> 4, n16 >> 4, ld, n);            // Sigma^- = A U
         EKF_LAP(4);
-#pragma unroll
-        for (int k = 0; k < PQ; ++k) {
-            const int e = tid + k * nt;
-            if (e < n * n) SG[(e / n) * ld + e % n] += wreg[k];
-        }
+        ekf_add_preloaded(SG, ld, n, n, wreg);
         for (int e = tid; e < n; e += nt) xv[e] = xn[e];
         __syncthreads();
     }
@@ -515,91 +478,33 @@ __global__ __launch_bounds__(EKF_NT) void ekf_mfma_kernel(EkfArgs a) {
         wg::mfma_atb(Sm, ldy, AT, UU, NK, ny16 >> 4, ny16 >> 4, ld, ny);          // C M1               (ny x ny)
         // CS = C Sigma^- = M1^T: Sigma^- = A (Sigma A^T) + W is symmetric up to the rounding of the two products
         for (int e = tid; e < ny * n; e += nt) CS[(e / n) * ld + e % n] = UU[(e % n) * ld + e / n];
-#pragma unroll
-        for (int k = 0; k < PQ; ++k) {
-            const int e = tid + k * nt;
-            if (e < ny * ny) Sm[(e / ny) * ldy + e % ny] += vreg[k];
-        }
+        ekf_add_preloaded(Sm, ldy, ny, ny, vreg);
         __syncthreads();
         EKF_LAP(7);
-        lptr Y = UU, KT = UU + (size_t)ny16 * ld;
-        if (EKF_GAIN_GJ_FITS(n, ny, nt >> 6, ny16, ldy)) {
-            for (int e = tid; e < ny16 * ld; e += nt) KT[e] = 0.0;          // M1 is dead: S and CS are built
-            __syncthreads();
-            (void)ekf_gain_gj<4, 2>(Sm, ldy, ny, CS, ld, n, KT, Li, ip + 1);     // Li, LiT: one cleared 2-panel buffer
-            __syncthreads();
-            EKF_LAP(8);
-            if (ip[1] != 0) {
-                if (tid == 0) *a.status = 1;
-                return;
-            }
-        } else {
-            if (tid < 64) {
-                // left-looking Cholesky, lane = row: column j of L from the finished columns < j (no trailing update)
-                bool ok = true;
-                for (int j = 0; j < ny; ++j) {
-                    double sj = 0.0;
-                    if (lane >= j && lane < ny) sj = Sm[lane * ldy + j] - dotk(Sm + lane * ldy, 1, Sm + j * ldy, 1, j);
-                    const double djj = __shfl(sj, j, 64);
-                    if (!(djj > 0.0)) { ok = false; break; }                              // uniform
-                    const double rj = sqrt(djj);
-                    if (lane >= j && lane < ny) Sm[lane * ldy + j] = (lane == j) ? rj : sj / rj;
-                    __builtin_amdgcn_wave_barrier();
-                }
-                if (!ok && tid == 0) ip[1] = 1;
-                if (ok) {
-                    // L^-1, lane = column c: row i from rows < i (entries above the diagonal stay zero)
-                    for (int i = 0; i < ny; ++i) {
-                        if (lane <= i && lane < ny) {
-                            const double sdot = dotk(Sm + i * ldy, 1, Li + lane, ldy, i);
-                            const double v = ((lane == i) ? 1.0 : -sdot) / Sm[i * ldy + i];
-                            Li[i * ldy + lane] = v;
-                            LiT[lane * ldy + i] = v;
-                        }
-                        __builtin_amdgcn_wave_barrier();
-                    }
-                }
-            }
-            __syncthreads();
-            EKF_LAP(8);
-            if (ip[1] != 0) {
-                if (tid == 0) *a.status = 1;
-                return;
-            }
-            // Y = L^-1 CS (rows 0.. of UU), K^T = L^-T Y (rows ny16.. of UU)
-            for (int e = tid; e < ny * n; e += nt) {
-                const int i = e / n, j = e % n;
-                Y[i * ld + j] = dotk(Li + i * ldy, 1, CS + j, ld, i + 1);
-            }
-            for (int e = tid; e < (ny16 - ny) * ld; e += nt) Y[ny * ld + e] = 0.0;
-            __syncthreads();
-            for (int e = tid; e < ny16 * ld; e += nt) {
-                const int i = e / ld, j = e % ld;
-                double v = 0.0;
-                if (i < ny && j < n) v = dotk(LiT + i * ldy + i, 1, Y + (size_t)i * ld + j, ld, ny - i);
-                KT[e] = v;
-            }
-            __syncthreads();
-            EKF_LAP(9);
-        }
+        lptr KT = UU + (size_t)ny16 * ld;                                         // K^T (ny16 x ld): rows ny16.. of UU, M1 is dead
+        for (int e = tid; e < ny16 * ld; e += nt) KT[e] = 0.0;
+        __syncthreads();
+        (void)ekf_gain_gj<4, 2>(Sm, ldy, ny, CS, ld, n, KT, GB, ip + 1);
+        __syncthreads();
+        EKF_LAP(8);
+        if (ekf_failed(a, ip)) return;
         for (int i = tid; i < n; i += nt) xn[i] = xv[i] + dotk(KT + i, ld, iv, 1, ny);
         wg::mfma_atb(AT, ld, KT, CS, NKy, n16 >> 4, n16 >> 4, ld, n);              // K CS
-        EKF_LAP(10);
+        EKF_LAP(9);
         for (int e = tid; e < n * n; e += nt) {
             const int i = e / n, j = e % n;
             a.Sigma[e] = SG[i * ld + j] - AT[i * ld + j];
         }
         for (int e = tid; e < n; e += nt) a.x[e] = xn[e];
     } else {
-        for (int e = tid; e < n * n; e += nt) a.Sigma[e] = SG[(e / n) * ld + e % n];
-        for (int e = tid; e < n; e += nt) a.x[e] = xv[e];
+        ekf_store_no_update(a, n, SG, ld, xv);
     }
     if (tid == 0) *a.status = 0;
 #ifdef SRH_PROFILE
-    EKF_LAP(11);
+    EKF_LAP(10);
     if (tid == 0)
-        printf("ekf clocks: load %lld nearest %lld Aload %lld xn %lld pred-mfma %lld W %lld Cload+innov %lld upd-mfma %lld chol+inv %lld Y+KT %lld KCS %lld store %lld\n",
-               ekp[0], ekp[1], ekp[2], ekp[3], ekp[4], ekp[5], ekp[6], ekp[7], ekp[8], ekp[9], ekp[10], ekp[11]);
+        printf("ekf clocks: load %lld nearest %lld Aload %lld xn %lld pred-mfma %lld W %lld Cload+innov %lld upd-mfma %lld gain %lld KCS %lld store %lld\n",
+               ekp[0], ekp[1], ekp[2], ekp[3], ekp[4], ekp[5], ekp[6], ekp[7], ekp[8], ekp[9], ekp[10]);
 #endif
 }
 
@@ -667,36 +572,16 @@ __global__ __launch_bounds__(EKF_NT) void ekf_wide_kernel(EkfArgs a) {
 
     constexpr int PQ = 16;                      // n <= 80: at most 13 entries of an n x n matrix per thread
     double wreg[PQ], creg[PQ / 2], vreg[2], yreg = 0.0;
-    if (a.do_predict) {
-#pragma unroll
-        for (int k = 0; k < PQ; ++k) wreg[k] = tid + k * nt < n * n ? a.W[tid + k * nt] : 0.0;
-    }
+    if (a.do_predict) ekf_preload(wreg, a.W, n * n);
     if (a.do_update) {
-#pragma unroll
-        for (int k = 0; k < PQ / 2; ++k) creg[k] = tid + k * nt < ny * n ? a.C[tid + k * nt] : 0.0;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) vreg[k] = tid + k * nt < ny * ny ? a.V[tid + k * nt] : 0.0;
+        ekf_preload(creg, a.C, ny * n);
+        ekf_preload(vreg, a.V, ny * ny);
         if (tid < ny) yreg = a.y[tid] - (a.y_ref ? a.y_ref[tid] : 0.0);
     }
-    const bool table = a.do_predict && a.Aext == nullptr;
-    if (tid < 64) {
-        for (int e = tid; e < n; e += 64) xv[e] = a.x[e];
-        if (a.do_predict)
-            for (int e = tid; e < m; e += 64) uv[e] = a.u[e];
-        if (tid == 0) ip[1] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (table) {
-            const int i = tpwl::nearest_wave(a.T, xv);
-            if (tid == 0) { ip[0] = i; if (a.pick != nullptr) *a.pick = i; }
-        }
-    } else {
-        const int t2 = tid - 64, nt2 = nt - 64;
-        for (int e = t2; e < NK * ld; e += nt2) {
-            const int i = e / ld, j = e - i * ld;
-            SG[e] = (i < n && j < n) ? a.Sigma[i * n + j] : 0.0;
-        }
-        for (int e = t2; e < NK * ld + ny16 * ld + NK * ldy + 3 * ny16 * ldy; e += nt2) UU[e] = 0.0;
+    if (tid < 64) ekf_wave0_prologue(a, n, m, xv, uv, ip);
+    else {
+        ekf_load_sigma(SG, NK, ld, n, a.Sigma);
+        for (int e = tid - 64; e < NK * ld + ny16 * ld + NK * ldy + 3 * ny16 * ldy; e += nt - 64) UU[e] = 0.0;
     }
     __syncthreads();
 
@@ -746,11 +631,7 @@ __global__ __launch_bounds__(EKF_NT) void ekf_wide_kernel(EkfArgs a) {
             }
             __syncthreads();
         }
-#pragma unroll
-        for (int k = 0; k < PQ; ++k) {
-            const int e = tid + k * nt;
-            if (e < n * n) SG[(e / n) * ld + e % n] += wreg[k];
-        }
+        ekf_add_preloaded(SG, ld, n, n, wreg);
         if (tid < n) xv[tid] = xn[tid];
         __syncthreads();
     }
@@ -771,21 +652,14 @@ __global__ __launch_bounds__(EKF_NT) void ekf_wide_kernel(EkfArgs a) {
         ekf_mm<false, false>(UU, ld, NK, ny, SG, ld, n, CT, ldy, ny, NK, n16 >> 4, ny16 >> 4, none, false);   // M1 = Sigma^- C^T
         ekf_mm<false, false>(Sm, ldy, ny16, ny, CT, ldy, ny, UU, ld, ny, NK, ny16 >> 4, ny16 >> 4, none, false);   // C M1
         for (int e = tid; e < ny * n; e += nt) CS[(e / n) * ld + e % n] = UU[(e % n) * ld + e / n];             // C Sigma^- = M1^T
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int e = tid + k * nt;
-            if (e < ny * ny) Sm[(e / ny) * ldy + e % ny] += vreg[k];
-        }
+        ekf_add_preloaded(Sm, ldy, ny, ny, vreg);
         __syncthreads();
         lptr KT = UU;                                                                              // K^T (ny16 x ld), M1 is dead
         for (int e = tid; e < ny16 * ld; e += nt) KT[e] = 0.0;
         __syncthreads();
         (void)ekf_gain_gj<4, 2>(Sm, ldy, ny, CS, ld, n, KT, GB, ip + 1);
         __syncthreads();
-        if (ip[1] != 0) {
-            if (tid == 0) *a.status = 1;
-            return;
-        }
+        if (ekf_failed(a, ip)) return;
         if (tid < n) {
             double acc = 0.0;
             for (int k = 0; k < ny; ++k) acc = fma(KT[k * ld + tid], iv[k], acc);
@@ -796,8 +670,7 @@ __global__ __launch_bounds__(EKF_NT) void ekf_wide_kernel(EkfArgs a) {
         ekf_mm<false, false>(SG, ld, 0, 0, KT, ld, n, CS, ld, n, NKy, n16 >> 4, n16 >> 4, sub, true);            // Sigma^- - K C Sigma^-
         if (tid < n) a.x[tid] = xn[tid];
     } else {
-        for (int e = tid; e < n * n; e += nt) a.Sigma[e] = SG[(e / n) * ld + e % n];
-        if (tid < n) a.x[tid] = xv[tid];
+        ekf_store_no_update(a, n, SG, ld, xv);
     }
     if (tid == 0) *a.status = 0;
 }
@@ -809,42 +682,46 @@ size_t lds_bytes(int n, int ny, int m) {
 }
 
 // ---- the dispatch: which kernel serves (n_x, n_y), its dynamic LDS and the form of its gain.  The one statement of the rule:
-// sekf_create launches what this returns, sekf_plan reports it.
+// the create functions launch what this returns, sekf_plan reports it.
 enum { EKF_REFUSED = 0, EKF_VALU = 1, EKF_MFMA = 2, EKF_MFMA60 = 3, EKF_WIDE = 4 };
 constexpr size_t EKF_LDS_MAX = 160 * 1024;
 constexpr int EKF_MAX_INPUTS = 16;          // stpwl_create: n_u <= 16
 
 struct EkfPlan {
-    int path = EKF_REFUSED, gain_form = 0;   // gain_form: 0 Gauss-Jordan on all waves, 1 one-wave Cholesky
+    int path = EKF_REFUSED, gain_form = 0;   // gain_form: 0 Gauss-Jordan on all waves (paths 2 to 4), 1 one-wave Cholesky (path 1)
     size_t lds = 0;
 };
+
+// The precondition of ekf_gain_gj<4, 2>, the gain of ekf_mfma_kernel and ekf_wide_kernel: four rows per wave hold the n_y rows of
+// the tableau, its n_y + n_x columns fit two register chunks of 64, the pivot is in chunk 0, and the double buffer (2 x (n_y + n_x +
+// 4 nw) doubles inside 128 cleared ones more) fits the two ny16 x ldy panels both kernels carve for it.
+bool ekf_gain_fits(int n, int ny) {
+    const int nw = EKF_NT / 64, ny16 = (ny + 15) & ~15, ldy = ny16 + 1;
+    return ny <= 4 * nw && ny <= 64 && ny + n <= 128 && 2 * (ny + n + 4 * nw) + 128 <= 2 * ny16 * ldy;
+}
 
 EkfPlan ekf_plan(int n, int ny, int m) {
     EkfPlan p;
     if (!(ny > 0 && ny <= n) || n > 4096 || m < 1) return p;          // (n > 4096: far past any LDS, and the products below stay small)
-    const bool no_mfma = getenv("SRH_EKF_NO_MFMA") != nullptr;
+    const bool mfma = getenv("SRH_EKF_NO_MFMA") == nullptr && ekf_gain_fits(n, ny);
     int path = EKF_VALU;
     size_t lds = lds_bytes(n, ny, m);
-    if (ny <= 64 && 2 * ((ny + 15) & ~15) <= ((n + 15) & ~15) && sizeof(double) * ekf_mfma_doubles(n, ny) <= EKF_LDS_MAX && !no_mfma) {
+    if (mfma && ny <= 64 && 2 * ((ny + 15) & ~15) <= ((n + 15) & ~15) && sizeof(double) * ekf_mfma_doubles(n, ny) <= EKF_LDS_MAX) {
         path = n == 60 ? EKF_MFMA60 : EKF_MFMA;
         lds = sizeof(double) * ekf_mfma_doubles(n, ny);
     }
-    if (path == EKF_VALU && n > 64 && n <= 80 && ny <= 32 && sizeof(double) * ekf_wide_doubles(n, ny) <= EKF_LDS_MAX && !no_mfma) {
+    if (mfma && path == EKF_VALU && n > 64 && n <= 80 && ny <= 32 && sizeof(double) * ekf_wide_doubles(n, ny) <= EKF_LDS_MAX) {
         path = EKF_WIDE;
         lds = sizeof(double) * ekf_wide_doubles(n, ny);
     }
     lds = srh::lds_request(lds);
     if (lds > EKF_LDS_MAX) return p;
     p.path = path; p.lds = lds;
-    if (path == EKF_VALU) p.gain_form = 1;
-    else if (path == EKF_WIDE) p.gain_form = 0;                       // ekf_wide_kernel has the elimination only
-    else {
-        const EkfMfmaDims d = ekf_mfma_dims(n, ny);
-        p.gain_form = ekf_gain_gj_fits(n, ny, EKF_NT >> 6, d.ny16, d.ldy) ? 0 : 1;
-    }
+    p.gain_form = path == EKF_VALU ? 1 : 0;
     return p;
 }
 
+// the one table of the kernels: hipFuncSetAttribute at creation and every launch go through it
 const void *ekf_kernel_of(int path) {
     switch (path) {
         case EKF_MFMA60: return (const void *)ekf_mfma_kernel<60>;
@@ -854,39 +731,151 @@ const void *ekf_kernel_of(int path) {
     }
 }
 
+int ekf_launch(int path, unsigned grid, size_t lds, hipStream_t stream, EkfArgs a) {
+    void *args[] = {&a};
+    SRH_CHECK_HIP(hipLaunchKernel(ekf_kernel_of(path), dim3(grid), dim3(EKF_NT), args, lds, stream));
+    return SRH_OK;
+}
+
+// Sigma0 into every filter (device copies on stream 0, waited for)
+int ekf_install_sigma0(EkfFilters *h) {
+    const size_t nn = (size_t)h->n * h->n;
+    for (size_t b = 0; b < (size_t)h->batch; ++b)
+        SRH_CHECK_HIP(hipMemcpyAsync(h->Sigma.as<double>() + b * nn, h->Sigma0.p, sizeof(double) * nn, hipMemcpyDeviceToDevice, nullptr));
+    SRH_CHECK_HIP(hipStreamSynchronize(nullptr));
+    return SRH_OK;
+}
+
+// What sekf_create and sekf_batch_create share: the plan, the uploads, x = 0 and status = 0, the pinned mirrors, the kernel's LDS
+// limit.  resident (sekf_batch): Sigma0 stays on the device for sekf_batch_install_sigma0 and every filter records its table point
+// (-1 before the first predictor); the single filter uploads Sigma0 straight into its Sigma and has no pick.  On an error the caller
+// deletes the handle.
+int ekf_filters_init(EkfFilters *h, const char *who, stpwl *model, const double *C, const double *y_ref, int n_y, const double *Sigma0,
+                     const double *W, const double *V, int64_t batch, bool resident) {
+    SRH_REQUIRE(model && C && Sigma0 && W && V, "%s: null argument", who);
+    SRH_REQUIRE(batch >= 1 && batch <= INT32_MAX, "%s: need batch >= 1 filters, got %lld", who, (long long)batch);
+    SRH_REQUIRE(n_y > 0 && n_y <= model->n, "%s: need 0 < n_y <= n_x", who);
+    const EkfPlan plan = ekf_plan(model->n, n_y, model->m);
+    SRH_REQUIRE(plan.path != EKF_REFUSED, "%s: the filter step of n_x = %d, n_y = %d does not fit the 160 KB LDS (n_x too large)", who,
+                model->n, n_y);
+    h->model = model; h->n = model->n; h->m = model->m; h->ny = n_y; h->batch = (int)batch;
+    h->path = plan.path; h->gain_form = plan.gain_form; h->lds = plan.lds;
+    const size_t D = sizeof(double), n = h->n, B = (size_t)batch, nn = D * n * n, nuy = D * B * (size_t)(h->m + n_y);
+    int rc;
+    if ((rc = h->C.upload(C, D * n_y * n)) || (rc = h->W.upload(W, nn)) || (rc = h->V.upload(V, D * n_y * n_y)) ||
+        (y_ref && (rc = h->y_ref.upload(y_ref, D * n_y))) || (rc = h->xs.alloc(h->xs_bytes())) || (rc = h->uy.alloc(nuy)))
+        return rc;
+    if (resident) {
+        if ((rc = h->Sigma0.upload(Sigma0, nn)) || (rc = h->Sigma.alloc(B * nn)) || (rc = h->pick.alloc(sizeof(int) * B))) return rc;
+        SRH_CHECK_HIP(hipMemset(h->pick.p, 0xff, sizeof(int) * B));
+        if ((rc = ekf_install_sigma0(h))) return rc;
+    } else if ((rc = h->Sigma.upload(Sigma0, nn))) return rc;
+    SRH_CHECK_HIP(hipMemset(h->xs.p, 0, h->xs_bytes()));
+    SRH_CHECK_HIP(hipHostMalloc((void **)&h->pin_in, nuy, hipHostMallocDefault));
+    SRH_CHECK_HIP(hipHostMalloc((void **)&h->pin_out, h->xs_bytes(), hipHostMallocDefault));
+    SRH_CHECK_HIP(hipFuncSetAttribute(ekf_kernel_of(h->path), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds));
+    return SRH_OK;
+}
+
+int ekf_handle_plan(const EkfFilters *h, int *path, size_t *lds_bytes_out, int *gain_form, int64_t *batch) {
+    if (path) *path = h->path;
+    if (lds_bytes_out) *lds_bytes_out = h->lds;
+    if (gain_form) *gain_form = h->gain_form;
+    if (batch) *batch = h->batch;
+    return SRH_OK;
+}
+
+// into and out of the buffers creation made (never re-allocated: xs carries the status words behind the estimates)
+int ekf_set_state(EkfFilters *h, const double *x, const double *Sigma) {
+    const size_t B = (size_t)h->batch, n = (size_t)h->n;
+    if (x) SRH_CHECK_HIP(hipMemcpy(h->xs.p, x, sizeof(double) * B * n, hipMemcpyHostToDevice));
+    if (Sigma) SRH_CHECK_HIP(hipMemcpy(h->Sigma.p, Sigma, sizeof(double) * B * n * n, hipMemcpyHostToDevice));
+    return SRH_OK;
+}
+
+int ekf_get_state(EkfFilters *h, double *x, double *Sigma, int *status) {
+    const size_t B = (size_t)h->batch, n = (size_t)h->n;
+    if (x) SRH_CHECK_HIP(hipMemcpy(x, h->xs.p, sizeof(double) * B * n, hipMemcpyDeviceToHost));
+    if (Sigma) SRH_CHECK_HIP(hipMemcpy(Sigma, h->Sigma.p, sizeof(double) * B * n * n, hipMemcpyDeviceToHost));
+    if (status) SRH_CHECK_HIP(hipMemcpy(status, h->status_dev(), sizeof(int) * B, hipMemcpyDeviceToHost));
+    return SRH_OK;
+}
+
+// One step of every filter of the handle on `stream`, from device inputs: the argument block and the launch.  A missing operand is
+// never read (do_predict / do_update); it still gets a valid address and no stride.  ext: the device block [A_d | B_d | d_d] of an
+// explicit predictor, or null.
+int ekf_step_dev(EkfFilters *h, const double *u_dev, int64_t su, const double *y_dev, int64_t sy, const double *ext, int32_t *pick_dev,
+                 int64_t sp, hipStream_t stream) {
+    const int n = h->n, m = h->m, ny = h->ny;
+    EkfArgs a{};
+    a.T = h->model->view();
+    a.n = n; a.m = m; a.ny = ny; a.ld = n | 1; a.ldy = ny | 1;
+    a.C = h->C.as<double>(); a.y_ref = h->yref_dev();
+    a.W = h->W.as<double>(); a.V = h->V.as<double>();
+    a.x = h->x_dev(); a.Sigma = h->Sigma.as<double>();
+    a.u = u_dev ? u_dev : h->uy.as<double>(); a.y = y_dev ? y_dev : h->uy.as<double>();
+    if (ext && u_dev) { a.Aext = ext; a.Bext = ext + (size_t)n * n; a.dext = a.Bext + (size_t)n * m; }
+    a.do_predict = u_dev != nullptr; a.do_update = y_dev != nullptr;
+    a.status = h->status_dev(); a.pick = pick_dev;
+    a.sx = n; a.sS = (long long)n * n; a.su = u_dev ? su : 0; a.sy = y_dev ? sy : 0; a.sst = 1; a.sp = sp;
+    return ekf_launch(h->path, (unsigned)h->batch, h->lds, stream, a);
+}
+
+// The host step on stream 0: u (batch x m) and y (batch x ny) through the pinned block in one upload, one launch, [x | status] copied
+// back to its mirror.  The caller waits for stream 0 and reads the mirror.
+int ekf_enqueue(EkfFilters *h, const double *u, const double *y, const double *ext) {
+    const size_t B = (size_t)h->batch, m = (size_t)h->m, ny = (size_t)h->ny;
+    double *su = h->uy.as<double>(), *sy = su + B * m;
+    if (u) memcpy(h->pin_in, u, sizeof(double) * B * m);
+    if (y) memcpy(h->pin_in + B * m, y, sizeof(double) * B * ny);
+    SRH_CHECK_HIP(hipMemcpyAsync(su, h->pin_in, sizeof(double) * B * (m + ny), hipMemcpyHostToDevice, nullptr));
+    int rc = ekf_step_dev(h, u ? su : nullptr, (int64_t)m, y ? sy : nullptr, (int64_t)ny, ext, h->pick.as<int>(), 1, nullptr);
+    if (rc) return rc;
+    SRH_CHECK_HIP(hipMemcpyAsync(h->pin_out, h->xs.p, h->xs_bytes(), hipMemcpyDeviceToHost, nullptr));
+    return SRH_OK;
+}
+
+// the single filter, after stream 0 has drained: status check and the state estimate out of the pinned mirror
+int ekf_collect(sekf *h, double *x_out, const char *who) {
+    int status = 0;
+    memcpy(&status, h->pin_out + h->n, sizeof(int));
+    if (status != 0) {
+        srh::set_error("%s: innovation covariance S is not positive definite", who);
+        return SRH_ENUMERIC;
+    }
+    if (x_out) memcpy(x_out, h->pin_out, sizeof(double) * h->n);
+    return SRH_OK;
+}
+
+// a batched predictor reads the model's discrete tables
+int ekf_batch_needs_tables(const sekf_batch *h) {
+    SRH_REQUIRE(h->model->has_discrete, "sekf_batch_step: model has not been pre-discretised (the batched filter takes the "
+                "nearest-point discrete tables only)");
+    return SRH_OK;
+}
+
+template <typename H>
+int ekf_create(H **out, const char *who, stpwl *model, const double *C, const double *y_ref, int n_y, const double *Sigma0, const double *W,
+               const double *V, int64_t batch, bool resident) {
+    SRH_REQUIRE(out, "%s: null argument", who);
+    H *h = new H();
+    const int rc = ekf_filters_init(h, who, model, C, y_ref, n_y, Sigma0, W, V, batch, resident);
+    if (rc) { delete h; return rc; }
+    *out = h;
+    return SRH_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int sekf_create(sekf_t **out, stpwl_t *model, const double *C, const double *y_ref, int n_y, const double *Sigma0,
                 const double *W, const double *V) {
-    SRH_REQUIRE(out && model && C && Sigma0 && W && V, "sekf_create: null argument");
-    SRH_REQUIRE(n_y > 0 && n_y <= model->n, "sekf_create: need 0 < n_y <= n_x");
-    auto *h = new sekf();
-    h->model = model; h->n = model->n; h->m = model->m; h->ny = n_y;
-    const EkfPlan plan = ekf_plan(h->n, n_y, h->m);
-    h->path = plan.path; h->gain_form = plan.gain_form; h->lds = plan.lds;
-    if (plan.path == EKF_REFUSED) {
-        delete h;
-        srh::set_error("sekf_create: the filter step does not fit the 160 KB LDS (n_x too large)");
-        return SRH_EINVAL;
-    }
-    const size_t n = h->n;
-    int rc;
-    if ((rc = h->C.upload(C, sizeof(double) * n_y * n)) || (rc = h->W.upload(W, sizeof(double) * n * n)) ||
-        (rc = h->V.upload(V, sizeof(double) * n_y * n_y)) || (rc = h->Sigma.upload(Sigma0, sizeof(double) * n * n)) ||
-        (rc = h->x.alloc(sizeof(double) * (n + 1))) || (rc = h->scratch.alloc(sizeof(double) * (h->m + n_y) + 64)) ||
-        (rc = h->ext.alloc(sizeof(double) * (n * n + n * h->m + n)))) {
-        delete h;
-        return rc;
-    }
-    if (y_ref && (rc = h->y_ref.upload(y_ref, sizeof(double) * n_y))) { delete h; return rc; }
-    SRH_CHECK_HIP(hipMemset(h->x.p, 0, sizeof(double) * (n + 1)));
-    SRH_CHECK_HIP(hipHostMalloc((void **)&h->pin_in, sizeof(double) * (h->m + n_y) + 64, hipHostMallocDefault));
-    SRH_CHECK_HIP(hipHostMalloc((void **)&h->pin_out, sizeof(double) * (n + 2), hipHostMallocDefault));
-    SRH_CHECK_HIP(hipFuncSetAttribute(ekf_kernel_of(h->path), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds));
-    *out = h;
-    return SRH_OK;
+    int rc = ekf_create(out, "sekf_create", model, C, y_ref, n_y, Sigma0, W, V, 1, false);
+    if (rc) return rc;
+    const size_t n = (*out)->n;
+    if ((rc = (*out)->ext.alloc(sizeof(double) * (n * n + n * (*out)->m + n)))) { delete *out; *out = nullptr; }
+    return rc;
 }
 
 int sekf_plan(int n_x, int n_y, int *path, size_t *lds_bytes_out, int *gain_form) {
@@ -899,10 +888,7 @@ int sekf_plan(int n_x, int n_y, int *path, size_t *lds_bytes_out, int *gain_form
 
 int sekf_handle_plan(sekf_t *h, int *path, size_t *lds_bytes_out, int *gain_form) {
     SRH_REQUIRE(h, "sekf_handle_plan: null argument");
-    if (path) *path = h->path;
-    if (lds_bytes_out) *lds_bytes_out = h->lds;
-    if (gain_form) *gain_form = h->gain_form;
-    return SRH_OK;
+    return ekf_handle_plan(h, path, lds_bytes_out, gain_form, nullptr);
 }
 
 int sekf_destroy(sekf_t *h) {
@@ -912,69 +898,12 @@ int sekf_destroy(sekf_t *h) {
 
 int sekf_set_state(sekf_t *h, const double *x, const double *Sigma) {
     SRH_REQUIRE(h && (x || Sigma), "sekf_set_state: null argument");
-    // into the buffers sekf_create made: h->x carries the status word behind its n_x doubles, and DevBuf::upload would replace it by
-    // a block of n_x doubles only -- for 8 n_x a multiple of 256 (n_x = 32, 64: the size class of the device pool) one without room
-    // for the status word the kernel writes and the step copies back
-    if (x) SRH_CHECK_HIP(hipMemcpy(h->x.p, x, sizeof(double) * h->n, hipMemcpyHostToDevice));
-    if (Sigma) SRH_CHECK_HIP(hipMemcpy(h->Sigma.p, Sigma, sizeof(double) * h->n * h->n, hipMemcpyHostToDevice));
-    return SRH_OK;
+    return ekf_set_state(h, x, Sigma);
 }
 
 int sekf_get_state(sekf_t *h, double *x, double *Sigma) {
     SRH_REQUIRE(h, "sekf_get_state: null argument");
-    int rc;
-    if (x && (rc = h->x.download(x, sizeof(double) * h->n))) return rc;
-    if (Sigma && (rc = h->Sigma.download(Sigma, sizeof(double) * h->n * h->n))) return rc;
-    return SRH_OK;
-}
-
-// enqueue one predictor/update on stream 0 (inputs through the pinned mirror, state and status copied back to it)
-static int ekf_enqueue(sekf *h, const double *u, const double *y, const double *A_d, const double *B_d,
-                       const double *d_d) {
-    const bool ext = A_d != nullptr;
-    const int n = h->n, m = h->m, ny = h->ny;
-    // scratch layout (device): [u (m) | y (ny)]; h->x holds x (n) and, behind it, the status word: one copy back
-    double *su = h->scratch.as<double>();
-    double *sy = su + m;
-    int *st = (int *)(h->x.as<double>() + n);
-    if (u) memcpy(h->pin_in, u, sizeof(double) * m);
-    if (y) memcpy(h->pin_in + m, y, sizeof(double) * ny);
-    SRH_CHECK_HIP(hipMemcpyAsync(su, h->pin_in, sizeof(double) * (m + ny), hipMemcpyHostToDevice, nullptr));
-    double *e = h->ext.as<double>();
-    if (ext && u) {
-        SRH_CHECK_HIP(hipMemcpy(e, A_d, sizeof(double) * n * n, hipMemcpyHostToDevice));
-        SRH_CHECK_HIP(hipMemcpy(e + (size_t)n * n, B_d, sizeof(double) * n * m, hipMemcpyHostToDevice));
-        SRH_CHECK_HIP(hipMemcpy(e + (size_t)n * n + (size_t)n * m, d_d, sizeof(double) * n, hipMemcpyHostToDevice));
-    }
-    EkfArgs a{};
-    a.T = h->model->view();
-    a.n = n; a.m = m; a.ny = ny; a.ld = n | 1; a.ldy = ny | 1;
-    a.C = h->C.as<double>(); a.y_ref = h->y_ref.p ? h->y_ref.as<double>() : nullptr;
-    a.W = h->W.as<double>(); a.V = h->V.as<double>();
-    a.x = h->x.as<double>(); a.Sigma = h->Sigma.as<double>();
-    a.u = su; a.y = sy;
-    if (ext && u) { a.Aext = e; a.Bext = e + (size_t)n * n; a.dext = e + (size_t)n * n + (size_t)n * m; }
-    a.do_predict = u != nullptr; a.do_update = y != nullptr;
-    a.status = st;
-    if (h->path == EKF_MFMA60) ekf_mfma_kernel<60><<<1, EKF_NT, h->lds>>>(a);
-    else if (h->path == EKF_MFMA) ekf_mfma_kernel<0><<<1, EKF_NT, h->lds>>>(a);
-    else if (h->path == EKF_WIDE) ekf_wide_kernel<<<1, EKF_NT, h->lds>>>(a);
-    else ekf_kernel<<<1, EKF_NT, h->lds>>>(a);
-    SRH_CHECK_HIP(hipGetLastError());
-    SRH_CHECK_HIP(hipMemcpyAsync(h->pin_out, h->x.p, sizeof(double) * (n + 1), hipMemcpyDeviceToHost, nullptr));
-    return SRH_OK;
-}
-
-// after stream 0 has drained: status check and the state estimate out of the pinned mirror
-static int ekf_collect(sekf *h, double *x_out, const char *who) {
-    int status = 0;
-    memcpy(&status, h->pin_out + h->n, sizeof(int));
-    if (status != 0) {
-        srh::set_error("%s: innovation covariance S is not positive definite", who);
-        return SRH_ENUMERIC;
-    }
-    if (x_out) memcpy(x_out, h->pin_out, sizeof(double) * h->n);
-    return SRH_OK;
+    return ekf_get_state(h, x, Sigma, nullptr);
 }
 
 int sekf_step(sekf_t *h, const double *u, const double *y, const double *A_d, const double *B_d, const double *d_d,
@@ -983,7 +912,15 @@ int sekf_step(sekf_t *h, const double *u, const double *y, const double *A_d, co
     SRH_REQUIRE(u || y, "sekf_step: need an input (predict) and/or a measurement (update)");
     SRH_REQUIRE(!A_d || (B_d && d_d), "sekf_step: A_d given without B_d, d_d");
     SRH_REQUIRE(!u || A_d || h->model->has_discrete, "sekf_step: model has not been pre-discretised");
-    int rc = ekf_enqueue(h, u, y, A_d, B_d, d_d);
+    double *e = nullptr;
+    if (A_d && u) {
+        const size_t n = h->n, m = h->m;
+        e = h->ext.as<double>();
+        SRH_CHECK_HIP(hipMemcpy(e, A_d, sizeof(double) * n * n, hipMemcpyHostToDevice));
+        SRH_CHECK_HIP(hipMemcpy(e + n * n, B_d, sizeof(double) * n * m, hipMemcpyHostToDevice));
+        SRH_CHECK_HIP(hipMemcpy(e + n * n + n * m, d_d, sizeof(double) * n, hipMemcpyHostToDevice));
+    }
+    int rc = ekf_enqueue(h, u, y, e);
     if (rc) return rc;
     SRH_CHECK_HIP(hipStreamSynchronize(nullptr));
     return ekf_collect(h, x_out, "sekf_step");
@@ -991,34 +928,7 @@ int sekf_step(sekf_t *h, const double *u, const double *y, const double *A_d, co
 
 int sekf_batch_create(sekf_batch_t **out, stpwl_t *model, const double *C, const double *y_ref, int n_y, const double *Sigma0,
                       const double *W, const double *V, int64_t batch) {
-    SRH_REQUIRE(out && model && C && Sigma0 && W && V, "sekf_batch_create: null argument");
-    SRH_REQUIRE(batch >= 1 && batch <= INT32_MAX, "sekf_batch_create: need batch >= 1 filters, got %lld", (long long)batch);
-    SRH_REQUIRE(n_y > 0 && n_y <= model->n, "sekf_batch_create: need 0 < n_y <= n_x");
-    const EkfPlan plan = ekf_plan(model->n, n_y, model->m);
-    SRH_REQUIRE(plan.path != EKF_REFUSED, "sekf_batch_create: the filter step of n_x = %d, n_y = %d does not fit the 160 KB LDS (n_x too large)",
-                model->n, n_y);
-    auto *h = new sekf_batch();
-    h->model = model; h->n = model->n; h->m = model->m; h->ny = n_y; h->batch = (int)batch;
-    h->path = plan.path; h->gain_form = plan.gain_form; h->lds = plan.lds;
-    const size_t n = h->n, B = (size_t)batch, nuy = B * (size_t)(h->m + n_y);
-    int rc;
-    if ((rc = h->C.upload(C, sizeof(double) * n_y * n)) || (rc = h->W.upload(W, sizeof(double) * n * n)) ||
-        (rc = h->V.upload(V, sizeof(double) * n_y * n_y)) || (rc = h->Sigma0.upload(Sigma0, sizeof(double) * n * n)) ||
-        (rc = h->Sigma.alloc(sizeof(double) * B * n * n)) || (rc = h->xs.alloc(h->xs_bytes())) || (rc = h->uy.alloc(sizeof(double) * nuy)) ||
-        (rc = h->pick.alloc(sizeof(int) * B)) ||
-        (y_ref && (rc = h->y_ref.upload(y_ref, sizeof(double) * n_y)))) {
-        delete h;
-        return rc;
-    }
-    auto fail = [&](const char *what) { srh::set_error("sekf_batch_create: %s failed", what); delete h; return SRH_EHIP; };
-    if (hipMemset(h->xs.p, 0, h->xs_bytes()) != hipSuccess || hipMemset(h->pick.p, 0xff, sizeof(int) * B) != hipSuccess) return fail("hipMemset");
-    if ((rc = sekf_batch_install_sigma0(h))) { delete h; return rc; }
-    if (hipHostMalloc((void **)&h->pin_in, sizeof(double) * nuy, hipHostMallocDefault) != hipSuccess) return fail("hipHostMalloc");
-    if (hipHostMalloc((void **)&h->pin_out, h->xs_bytes(), hipHostMallocDefault) != hipSuccess) return fail("hipHostMalloc");
-    if (hipFuncSetAttribute(ekf_kernel_of(h->path), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds) != hipSuccess)
-        return fail("hipFuncSetAttribute");
-    *out = h;
-    return SRH_OK;
+    return ekf_create(out, "sekf_batch_create", model, C, y_ref, n_y, Sigma0, W, V, batch, true);
 }
 
 int sekf_batch_destroy(sekf_batch_t *h) {
@@ -1028,28 +938,17 @@ int sekf_batch_destroy(sekf_batch_t *h) {
 
 int sekf_batch_plan(sekf_batch_t *h, int *path, size_t *lds_bytes_out, int *gain_form, int64_t *batch) {
     SRH_REQUIRE(h, "sekf_batch_plan: null argument");
-    if (path) *path = h->path;
-    if (lds_bytes_out) *lds_bytes_out = h->lds;
-    if (gain_form) *gain_form = h->gain_form;
-    if (batch) *batch = h->batch;
-    return SRH_OK;
+    return ekf_handle_plan(h, path, lds_bytes_out, gain_form, batch);
 }
 
 int sekf_batch_set_state(sekf_batch_t *h, const double *x, const double *Sigma) {
     SRH_REQUIRE(h && (x || Sigma), "sekf_batch_set_state: null argument");
-    const size_t B = (size_t)h->batch, n = (size_t)h->n;
-    if (x) SRH_CHECK_HIP(hipMemcpy(h->xs.p, x, sizeof(double) * B * n, hipMemcpyHostToDevice));
-    if (Sigma) SRH_CHECK_HIP(hipMemcpy(h->Sigma.p, Sigma, sizeof(double) * B * n * n, hipMemcpyHostToDevice));
-    return SRH_OK;
+    return ekf_set_state(h, x, Sigma);
 }
 
 int sekf_batch_get_state(sekf_batch_t *h, double *x, double *Sigma, int *status) {
     SRH_REQUIRE(h, "sekf_batch_get_state: null argument");
-    const size_t B = (size_t)h->batch, n = (size_t)h->n;
-    if (x) SRH_CHECK_HIP(hipMemcpy(x, h->xs.p, sizeof(double) * B * n, hipMemcpyDeviceToHost));
-    if (Sigma) SRH_CHECK_HIP(hipMemcpy(Sigma, h->Sigma.p, sizeof(double) * B * n * n, hipMemcpyDeviceToHost));
-    if (status) SRH_CHECK_HIP(hipMemcpy(status, h->status_dev(), sizeof(int) * B, hipMemcpyDeviceToHost));
-    return SRH_OK;
+    return ekf_get_state(h, x, Sigma, status);
 }
 
 int sekf_batch_last_points(sekf_batch_t *h, int32_t *idx) {
@@ -1061,14 +960,10 @@ int sekf_batch_last_points(sekf_batch_t *h, int32_t *idx) {
 int sekf_batch_step(sekf_batch_t *h, const double *u, const double *y, double *x_out) {
     SRH_REQUIRE(h, "sekf_batch_step: null argument");
     SRH_REQUIRE(u || y, "sekf_batch_step: need inputs (predict) and/or measurements (update)");
-    const size_t B = (size_t)h->batch, n = (size_t)h->n, m = (size_t)h->m, ny = (size_t)h->ny;
-    double *su = h->uy.as<double>(), *sy = su + B * m;
-    if (u) memcpy(h->pin_in, u, sizeof(double) * B * m);
-    if (y) memcpy(h->pin_in + B * m, y, sizeof(double) * B * ny);
-    SRH_CHECK_HIP(hipMemcpyAsync(su, h->pin_in, sizeof(double) * B * (m + ny), hipMemcpyHostToDevice, nullptr));
-    int rc = sekf_batch_step_dev(h, u ? su : nullptr, (int64_t)m, y ? sy : nullptr, (int64_t)ny, h->pick.as<int>(), 1, nullptr);
+    if (u && ekf_batch_needs_tables(h)) return SRH_EINVAL;
+    const size_t B = (size_t)h->batch, n = (size_t)h->n;
+    int rc = ekf_enqueue(h, u, y, nullptr);
     if (rc) return rc;
-    SRH_CHECK_HIP(hipMemcpyAsync(h->pin_out, h->xs.p, h->xs_bytes(), hipMemcpyDeviceToHost, nullptr));
     SRH_CHECK_HIP(hipStreamSynchronize(nullptr));
     // a failed filter kept its estimate: x_out is the resident state of every filter either way
     if (x_out) memcpy(x_out, h->pin_out, sizeof(double) * B * n);
@@ -1099,7 +994,7 @@ int sekf_step_projected(sekf_t *h, srom_t *rom, const double *x_full, const doub
     // the two halves are independent (the filter never reads the projected state): filter on stream 0 -- enqueued
     // first, its one-workgroup kernel is the long pole -- projection on the side stream, one wait for each
     auto drain = [&](int code) { (void)hipStreamSynchronize(h->side); (void)hipStreamSynchronize(nullptr); return code; };
-    if ((rc = ekf_enqueue(h, u, y, nullptr, nullptr, nullptr))) return drain(rc);
+    if ((rc = ekf_enqueue(h, u, y, nullptr))) return drain(rc);
     if ((rc = srom_stage_project(rom, SROM_X, x_full, 1, h->side))) return drain(rc);
     if (hipStreamSynchronize(h->side) != hipSuccess) { srh::set_error("sekf_step_projected: side stream failed"); return drain(SRH_EHIP); }
     if ((rc = srom_stage_collect(rom, x_reduced_out, 1, SROM_X))) return drain(rc);
@@ -1109,44 +1004,11 @@ int sekf_step_projected(sekf_t *h, srom_t *rom, const double *x_full, const doub
 
 }  // extern "C"
 
-int sekf_batch_install_sigma0(sekf_batch *h) {
-    const size_t nn = (size_t)h->n * h->n;
-    for (size_t b = 0; b < (size_t)h->batch; ++b)
-        SRH_CHECK_HIP(hipMemcpyAsync(h->Sigma.as<double>() + b * nn, h->Sigma0.p, sizeof(double) * nn, hipMemcpyDeviceToDevice, nullptr));
-    SRH_CHECK_HIP(hipStreamSynchronize(nullptr));
-    return SRH_OK;
-}
+int sekf_batch_install_sigma0(sekf_batch *h) { return ekf_install_sigma0(h); }
 
 int sekf_batch_step_dev(sekf_batch *h, const double *u_dev, int64_t su, const double *y_dev, int64_t sy, int32_t *pick_dev, int64_t sp,
                         hipStream_t stream) {
     SRH_REQUIRE(h && (u_dev || y_dev), "sekf_batch_step: null argument");
-    SRH_REQUIRE(!u_dev || h->model->has_discrete, "sekf_batch_step: model has not been pre-discretised (the batched filter takes the "
-                "nearest-point discrete tables only)");
-    const int n = h->n, m = h->m, ny = h->ny;
-    EkfArgs a{};
-    a.T = h->model->view();
-    a.n = n; a.m = m; a.ny = ny; a.ld = n | 1; a.ldy = ny | 1;
-    a.C = h->C.as<double>(); a.y_ref = h->y_ref.p ? h->y_ref.as<double>() : nullptr;
-    a.W = h->W.as<double>(); a.V = h->V.as<double>();
-    a.x = h->xs.as<double>(); a.Sigma = h->Sigma.as<double>();
-    // a missing operand is never read (do_predict / do_update); it still gets a valid address and no stride
-    a.u = u_dev ? u_dev : h->uy.as<double>(); a.y = y_dev ? y_dev : h->uy.as<double>();
-    a.do_predict = u_dev != nullptr; a.do_update = y_dev != nullptr;
-    a.status = h->status_dev(); a.pick = pick_dev;
-    a.sx = n; a.sS = (long long)n * n; a.su = u_dev ? su : 0; a.sy = y_dev ? sy : 0; a.sst = 1; a.sp = sp;
-    const dim3 grid((unsigned)h->batch);
-    if (h->path == EKF_MFMA60) ekf_mfma_kernel<60><<<grid, EKF_NT, h->lds, stream>>>(a);
-    else if (h->path == EKF_MFMA) ekf_mfma_kernel<0><<<grid, EKF_NT, h->lds, stream>>>(a);
-    else if (h->path == EKF_WIDE) ekf_wide_kernel<<<grid, EKF_NT, h->lds, stream>>>(a);
-    else ekf_kernel<<<grid, EKF_NT, h->lds, stream>>>(a);
-    SRH_CHECK_HIP(hipGetLastError());
-    return SRH_OK;
+    if (u_dev && ekf_batch_needs_tables(h)) return SRH_EINVAL;
+    return ekf_step_dev(h, u_dev, su, y_dev, sy, nullptr, pick_dev, sp, stream);
 }
-
-void sekf_batch_dims(const sekf_batch *h, int *n, int *m, int *ny, int64_t *batch, stpwl **model) {
-    *n = h->n; *m = h->m; *ny = h->ny; *batch = h->batch; *model = h->model;
-}
-double *sekf_batch_x_dev(sekf_batch *h) { return h->xs.as<double>(); }
-int *sekf_batch_status_dev(sekf_batch *h) { return h->status_dev(); }
-const double *sekf_batch_C_dev(sekf_batch *h) { return h->C.as<double>(); }
-const double *sekf_batch_yref_dev(sekf_batch *h) { return h->y_ref.p ? h->y_ref.as<double>() : nullptr; }

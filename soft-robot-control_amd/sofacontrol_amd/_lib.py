@@ -175,7 +175,7 @@ def _ekf_plan_dict(path, lds, gain):
 def ekf_plan(n_x, n_y):
     """sekf_plan: the kernel sekf_create chooses for a filter of n_x states and n_y measurements (csrc/observer.hip), on the host --
     no GPU needed.  {'path': 0 refused | 1 VALU | 2 MFMA generic | 3 MFMA <60> | 4 wide, 'kernel': its name, 'lds_bytes',
-    'gain_form': 0 Gauss-Jordan on all waves | 1 one-wave Cholesky}.  Honours SRH_EKF_NO_MFMA."""
+    'gain_form': 0 Gauss-Jordan on all waves (paths 2 to 4) | 1 one-wave Cholesky (path 1)}.  Honours SRH_EKF_NO_MFMA."""
     path, lds, gain = C.c_int(0), C.c_size_t(0), C.c_int(0)
     check(lib().sekf_plan(C.c_int(n_x), C.c_int(n_y), C.byref(path), C.byref(lds), C.byref(gain)), 'sekf_plan')
     return _ekf_plan_dict(path, lds, gain)

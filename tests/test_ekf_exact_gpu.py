@@ -130,6 +130,24 @@ def test_ekf_200_steps_and_symmetry(s, monkeypatch):
     assert worst <= tol, (worst, tol)
 
 
+def test_failed_step_through_the_abi_leaves_x_out_unwritten(monkeypatch):
+    """sekf_step on a failed update: SRH_ENUMERIC with its message, and the caller's x_out is not written (the batched step fills it
+    either way: tests/test_ekf_batch_gpu.py).  The smallest VALU shape with more than one pivot."""
+    monkeypatch.delenv('SRH_EKF_NO_MFMA', raising=False)
+    c = ec.case(ec.spec(('valu', 4, 3, 8)))
+    flt = DeviceFilter(c)
+    L = flt.lib
+    flt.set_x(c['resets'][0])
+    flt.ekf.Sigma = ec.indefinite_sigmas(c)[0][1]
+    y, x_out = L.f64(c['y'][0]), np.full(c['n'], -7.25)
+    rc = L.lib().sekf_step(flt.ekf._h, None, L.dptr(y), None, None, None, L.dptr(x_out))
+    msg = L.lib().srh_last_error().decode()
+    print('ekf_exact failed sekf_step: rc %d, message %r, x_out %s' % (rc, msg, x_out))
+    assert rc == -4 and msg == 'sekf_step: ' + NOT_PD
+    np.testing.assert_array_equal(x_out, np.full(c['n'], -7.25))
+    np.testing.assert_array_equal(flt.state()[0], c['resets'][0])
+
+
 @pytest.mark.parametrize('shape', ec.INDEFINITE, ids=str)
 def test_ekf_failure_exit_leaves_the_state_untouched(shape, monkeypatch):
     """An update whose innovation covariance is not positive definite -- at the first pivot (Sigma = -1e3 I) and at the

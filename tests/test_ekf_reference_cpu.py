@@ -4,7 +4,8 @@ tests/test_ekf_exact_gpu.py may hold the kernels of csrc/observer.hip to a toler
   - at every table-path predictor the two nearest table points are more than 1e-6 (relative) apart, so the device and the
     reference pick the same point; every table case visits at least three points;
   - every case carries the label of the kernel that sekf_plan (the dispatch of sekf_create, a host function) gives it;
-  - the one-wave Cholesky branch of ekf_mfma_kernel is selected for no shape the MFMA path accepts."""
+  - every shape on an MFMA or wide path has the Gauss-Jordan gain (ekf_mfma_kernel once had a one-wave Cholesky branch no shape
+    could reach; the elimination's precondition is now part of the dispatch) and the LDS carve of its layout."""
 import numpy as np
 import pytest
 
@@ -112,12 +113,32 @@ def test_plan_edges_and_refusals(monkeypatch):
     for n, ny in ((8, 6), (30, 30), (4, 3)):
         want = 8 * (3 * n * (n | 1) + ny * (n | 1) + ny * (ny | 1) + 4 * max(n, ny, 16) + 8)
         assert plan(n, ny)['lds_bytes'] == -(-want // 2560) * 2560
+    # the MFMA and wide layouts on every shape of paths 2 to 4 (doubles, in whole 2560-byte units), and on each of them the
+    # precondition of the elimination ekf_gain_gj<4, 2> that both kernels run: nw = 8 waves of four rows each, two register chunks
+    # of 64 columns, a double buffer of 2 (n_y + n_x + 4 nw) + 128 doubles inside the two ny16 x ldy panels carved for it
+    nw, seen = 512 // 64, {2: 0, 3: 0, 4: 0}
+    for n in range(1, 130):
+        for ny in range(1, n + 1):
+            p = plan(n, ny)
+            if p['path'] not in seen:
+                continue
+            seen[p['path']] += 1
+            n16, ny16, NK = -(-n // 16) * 16, -(-ny // 16) * 16, -(-n // 4) * 4
+            ld, ldy = n16 + 1, ny16 + 1
+            if p['path'] == code['wide']:
+                want = 2 * NK * ld + ny16 * ld + NK * ldy + 3 * ny16 * ldy + 4 * n16 + 8
+            else:
+                want = 3 * n16 * ld + ny16 * ld + 3 * ny16 * ldy + 4 * max(n16, ny16) + 8
+            assert p['lds_bytes'] == -(-8 * want // 2560) * 2560, (n, ny, p)
+            assert ny <= 4 * nw and ny <= 64 and ny + n <= 128 and 2 * (ny + n + 4 * nw) + 128 <= 2 * ny16 * ldy, (n, ny, p)
+    assert seen == {2: 992, 3: 32, 4: 384}, seen
+    assert plan(60, 30)['lds_bytes'] == 145920 and plan(72, 30)['lds_bytes'] == 161280
 
 
 def test_mfma_cholesky_fallback_is_unreachable(monkeypatch):
-    """Every (n_x, n_y) with n_y <= n_x < 130 that the dispatch puts on an MFMA kernel takes the Gauss-Jordan gain: the
-    one-wave Cholesky / triangular-inverse branch of ekf_mfma_kernel is dead code (DESIGN.md records it as a removal
-    candidate)."""
+    """Every (n_x, n_y) with n_y <= n_x < 130 that the dispatch puts on an MFMA kernel takes the Gauss-Jordan gain.  This
+    showed the one-wave Cholesky / triangular-inverse branch ekf_mfma_kernel once had to be dead code; the branch is gone,
+    and the count of shapes per path pins that removing it moved no shape to another kernel."""
     monkeypatch.delenv('SRH_EKF_NO_MFMA', raising=False)
     seen = {2: 0, 3: 0, 4: 0}
     for n in range(1, 130):

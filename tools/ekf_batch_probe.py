@@ -49,7 +49,8 @@ def stat(v):
     return dict(median=float(np.median(v)), min=float(v.min()), max=float(v.max()), n=int(len(v)))
 
 
-def probe(B, model, seed=0):
+def probe(B, model, seed=0, handles=True):
+    """handles=False: contender (a) alone (tools/ekf_handle_ab.py times it on two builds of the library)."""
     from sofacontrol_amd import _lib
     lib, f64, dptr = _lib.lib(), _lib.f64, _lib.dptr
     n, m, ny = model.get_state_dim(), model.get_input_dim(), model.C.shape[0]
@@ -65,13 +66,13 @@ def probe(B, model, seed=0):
     _lib.check(lib.sekf_batch_create(C.byref(hb), mh, dptr(Cm), dptr(yr), C.c_int(ny), dptr(S0), dptr(W), dptr(V), C.c_int64(B)), 'sekf_batch_create')
     _lib.check(lib.sekf_batch_set_state(hb, dptr(x0), None), 'sekf_batch_set_state')
     hs = []
-    for b in range(B):
+    for b in range(B if handles else 0):
         h = C.c_void_p()
         _lib.check(lib.sekf_create(C.byref(h), mh, dptr(Cm), dptr(yr), C.c_int(ny), dptr(S0), dptr(W), dptr(V)), 'sekf_create')
         _lib.check(lib.sekf_set_state(h, dptr(x0[b]), None), 'sekf_set_state')
         hs.append(h)
     xb, x1 = np.empty((B, n)), np.empty((B, n))
-    up = [[(dptr(u[k, b]), dptr(y[k, b]), dptr(x1[b])) for b in range(B)] for k in range(steps)]
+    up = [[(dptr(u[k, b]), dptr(y[k, b]), dptr(x1[b])) for b in range(len(hs))] for k in range(steps)]
     timed_handles = TIMED_HANDLES_4096 if B >= 4096 else TIMED
     ta, tb, tb2, equal = [], [], [], True
     for k in range(steps):
@@ -80,6 +81,8 @@ def probe(B, model, seed=0):
         t1 = time.perf_counter()
         if k >= WARM:
             ta.append(1e3 * (t1 - t0))
+        if not handles:
+            continue
         if k == 0:                          # the first step of every handle, and the comparison
             for b in range(B):
                 _lib.check(lib.sekf_step(hs[b], up[k][b][0], up[k][b][1], None, None, None, up[k][b][2]), 'sekf_step')
@@ -101,6 +104,8 @@ def probe(B, model, seed=0):
     for h in hs:
         lib.sekf_destroy(h)
     lib.sekf_batch_destroy(hb)
+    if not handles:
+        return dict(batch=B, failed_filters=int(st.sum()), batched_ms_per_step=stat(ta))
     a, b1, b2 = stat(ta), stat(tb), stat(tb2)
     spread = abs(b1['median'] - b2['median'])
     D = 8
