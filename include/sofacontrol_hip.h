@@ -318,6 +318,10 @@ int sssm_reduce(sssm_t *h, const double *Z, int64_t B, double *X);
  * X (batch x (N+1) x n_x), Z (batch x (N+1) x n_o, includes z_ref) or NULL */
 int sssm_rollout(sssm_t *h, const double *x0, const double *U, int N, int64_t batch, int mode, double dt,
                  double *X, double *Z);
+/* The same rollout on device arrays, asynchronous on `stream`: the one launch sssm_rollout makes, no copy, no wait and no scan of X
+ * for non-finite states (sssm_rollout is this between its copies). */
+int sssm_rollout_dev(sssm_t *h, const double *x0_dev, const double *U_dev, int N, int64_t batch, int mode, double dt, double *X_dev,
+                     double *Z_dev, void *stream);
 
 /* =====================================================================================================
  * Riccati recursions.             reference: sofacontrol/lqr/lqr.py, sofacontrol/lqr/traj_tracking_lqr.py
@@ -572,6 +576,13 @@ int sgusto_ssm_plan_solve(sgusto_ssm_plan_t *plan, const double *x0, const doubl
 int sgusto_ssm_plan_solve_dev(sgusto_ssm_plan_t *plan, const double *x0_dev, const double *u_init_dev, const double *x_init_dev,
                               const double *z_dev, const double *u_des_dev, double *xopt_dev, double *uopt_dev, double *zopt_dev,
                               int32_t *iters_dev, int32_t *status_dev, double *trace_dev, void *stream);
+/* The shapes an SSM plan was created with (any output may be NULL): n_x = the MODEL's n (not the QP's augmented state), mode = the
+ * discretisation of the plan's model, ndU = the rows of its rate polyhedron. */
+int sgusto_ssm_plan_dims(const sgusto_ssm_plan_t *plan, int *N, int *n_x, int *n_u, int *n_z, int64_t *batch, double *dt, int *mode,
+                         int *ndU);
+/* As sgusto_plan_costs_dev: the LOCP value of the solution each rollout of the plan's LAST solve returned, copied device-to-device
+ * into J_dev (batch) on `stream`, behind the solve enqueued there: no host wait. */
+int sgusto_ssm_plan_costs_dev(sgusto_ssm_plan_t *plan, double *J_dev, void *stream);
 
 /* Which kernel instantiation a solve of this plan launches: split (1: split W panel, n_x > 64), n_u_fixed / n_x_fixed
  * = the compile-time n_u / n_x of the instantiation (0: that extent is a run-time value; 0, 0 = the all-sizes
@@ -694,6 +705,56 @@ int sgusto_loop_stats(sgusto_loop_t *h, int64_t *steps, int64_t *waits_last_run)
 /* The schedule of period k (no GPU): *t_k, *idx0 (0 for k = 0), j (n_keep), theta (n_keep).  Any output may be NULL. */
 int sgusto_loop_schedule(int N, double dt, double dt_sim, int n_keep, double t_start, int64_t k, double *t_k, int *idx0, int32_t *j,
                          double *theta);
+
+/* Batched closed loop on a resident SSM GuSTO plan (csrc/gusto_ssm_loop.hip): the loop of the reference's hardware driver
+ * (examples/hardware/diamond_SSM.py:353-361, SSM/controllers.py: the scp controller applies u = u_bar(t) with no feedback gain, the
+ * SSMObserver is the polynomial map x_hat = W_map(y - z_ref)), one per rollout b of the plan's batch.  Period k as sgusto_loop's
+ * (same schedule: sgusto_loop_schedule; same shift and target window: one prepare kernel for both units) with
+ *   x0      = the estimate x_hat (observe = 1) or the plant state (observe = 0)
+ *   guess   k = 0: u_init = 0, x_init = the zero-input rollout of the PLANNER's model at dt (sssm_rollout_dev in the plan's mode)
+ *   target  z in the shifted coordinates of the plan (without z_ref); an SSM plan has no terminal cost, so there is no zf
+ *   solve   sgusto_ssm_plan_solve_dev with trace = NULL; whatever status a rollout ends with, it goes on with what the kernel returned
+ *   advance ONE launch for all n_keep sub-steps, s = 0..n_keep-1 with (j, theta) of the schedule:
+ *           u      = [uopt ; uopt[N-1]] interpolated at (j, theta)                      (SSM/controllers.py:204, 237)
+ *           x     <- A_d x + B_d u + d_d (+ w), (A_d, B_d, d_d) the PLANT's Jacobians at (x, u) discretised at dt_sim in plant_mode
+ *                    (1 fe, 2 be, 3 bil, 4 its discrete map; ssm.py:198-218, 279-301)
+ *           zeta   = C_plant(x)                  the record Z: without z_ref, like the plan's z
+ *           y      = (zeta + z_ref_plant) + v    in this order of additions
+ *           x_hat  = V_planner phi_s(y - z_ref_planner)                                 (SSMObserver.update with the controller's model)
+ * f64 throughout.  The plant may be the planner's model or another one of the same n_x, n_u, n_o (= n_x); its tables, the planner's V
+ * and z_ref and the work area live in LDS for the launch: what exceeds 160 KiB is refused at creation with the byte count.  create also
+ * refuses a plan with rate rows (a rollout whose trust region binds comes back with status -78 for the host loop, which a device loop
+ * cannot serve), a plant of other dimensions or without a discrete map when plant_mode = 4, n_u > 16, and n_keep dt_sim > N dt.
+ * The plan and both models must outlive the loop; the plan's iteration cap is the one in force when sgusto_ssm_loop_run is called. */
+typedef struct sgusto_ssm_loop sgusto_ssm_loop_t;
+int sgusto_ssm_loop_create(sgusto_ssm_loop_t **out, sgusto_ssm_plan_t *plan, sssm_t *planner_model, sssm_t *plant, int plant_mode,
+                           double dt_sim, int n_keep, int observe, int64_t max_steps_per_run);
+int sgusto_ssm_loop_destroy(sgusto_ssm_loop_t *h);
+/* t (T, increasing), z (T x n_z), u_des (T x n_u) or NULL, phase (batch) or NULL = zeros */
+int sgusto_ssm_loop_set_target(sgusto_ssm_loop_t *h, int T, const double *t, const double *z, const double *u_des, const double *phase);
+/* x0 (batch x n_x) plant states, v0 (batch x n_o) or NULL: the noise of the first measurement.  The advance kernel, launched with zero
+ * sub-steps, forms zeta0 = C_plant(x0), y0 = (zeta0 + z_ref_plant) + v0 and x_hat0 = W_map(y0 - z_ref_planner): the reference's first
+ * observer.update before its first compute_policy.  Waits for the launch. */
+int sgusto_ssm_loop_reset(sgusto_ssm_loop_t *h, const double *x0, const double *v0, double t_start);
+/* `periods` periods (prepare -> solve -> costs -> advance each) enqueued on the handle's own stream, the records copied back once, ONE
+ * blocking wait.  W (periods x n_keep x batch x n_x), V (periods x n_keep x batch x n_o) or NULL.  With S = periods n_keep: X_cl
+ * (batch x (S + 1) x n_x) or NULL, Z_cl, Y_cl (batch x (S + 1) x n_o), Xhat (batch x (S + 1) x n_x), U_cl (batch x S x n_u); row 0 =
+ * where the run started (after a reset: x0, zeta0, y0, x_hat0); iters, status, J (periods x batch).  A following run continues. */
+int sgusto_ssm_loop_run(sgusto_ssm_loop_t *h, int periods, const double *W, const double *V, double *X_cl, double *Z_cl, double *U_cl,
+                        double *Y_cl, double *Xhat, int32_t *iters, int32_t *status, double *J);
+/* The solver inputs / the plan of the last period (any may be NULL; z, u_des are left alone when the loop has none). */
+int sgusto_ssm_loop_last_inputs(sgusto_ssm_loop_t *h, double *x0, double *u_init, double *x_init, double *z, double *u_des);
+int sgusto_ssm_loop_last_plan(sgusto_ssm_loop_t *h, double *xopt, double *uopt);
+/* periods run since the last reset, and the blocking host waits of the last run */
+int sgusto_ssm_loop_stats(sgusto_ssm_loop_t *h, int64_t *steps, int64_t *waits_last_run);
+/* The advance kernel alone -- the launch sgusto_ssm_loop_run makes -- on host arrays, through temporary buffers, without a plan or a
+ * loop handle: j, theta (n_keep) of the schedule, uopt (batch x N x n_u), x (batch x n_x), W (n_keep x batch x n_x) / V (n_keep x
+ * batch x n_o) or NULL -> X, Xhat (batch x n_keep x n_x), Z, Y (batch x n_keep x n_o), U (batch x n_keep x n_u) after every sub-step.
+ * xopt (batch x (N+1) x n_x) is accepted for symmetry with sgusto_loop_advance and not read: the law has no gain.  observer_model:
+ * the model whose V and z_ref form x_hat (it may be the plant). */
+int sgusto_ssm_loop_advance(sssm_t *plant, int plant_mode, sssm_t *observer_model, double dt_sim, int N, int n_keep, int64_t batch,
+                            const int32_t *j, const double *theta, const double *xopt, const double *uopt, const double *x,
+                            const double *W, const double *V, double *X, double *Z, double *U, double *Y, double *Xhat);
 
 /* =====================================================================================================
  * Koopman baseline. reference: sofacontrol/baselines/koopman/koopman_utils.py, koopman/koopman.py, baselines/ros.py:139-235

@@ -1,0 +1,115 @@
+// What the two closed-loop units (gusto_loop.hip: TPWL plans, gusto_ssm_loop.hip: SSM plans) share, stated once: the target table's
+// interpolation, the query times, and loop_prepare_kernel -- the kernel that turns the previous period's output into the next solve's
+// input (x0, the shifted guess, the target window) -- with the pinned block their copies back go through.  Each unit gets its own
+// instance of the kernel (anonymous namespace); an SSM loop passes no H (it has no linear output map) and no zf (no terminal cost).
+#pragma once
+#include "common.h"
+#include "dev_la.h"
+
+namespace {
+
+// Row `a` of the table (tt (T), ty (T x ld)) at tq: scipy's interp1d(kind='linear', bounds_error=False, fill_value=(y[0], y[-1])) --
+// i = searchsorted(tt, tq) (first tt[i] >= tq) clipped to 1..T-1, slope (y[i] - y[i-1]) / (tt[i] - tt[i-1]), slope (tq - tt[i-1]) + y[i-1];
+// the first / last row outside the table.  A tq that is not a number picks i = 1 and gives not-a-number: no index leaves the table.
+__device__ __forceinline__ double table_at(cgptr tt, cgptr ty, int T, int ld, int a, double tq) {
+    if (tq < tt[0]) return ty[a];
+    if (tq > tt[T - 1]) return ty[(size_t)(T - 1) * ld + a];
+    int lo = 0, hi = T;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (tt[mid] < tq) lo = mid + 1; else hi = mid;
+    }
+    const int i = min(max(lo, 1), T - 1);
+    const double t0 = tt[i - 1], y0 = ty[(size_t)(i - 1) * ld + a];
+    const double slope = (ty[(size_t)i * ld + a] - y0) / (tt[i] - t0);
+    return slope * (tq - t0) + y0;
+}
+
+// t0 + dt k with the product and the sum rounded on their own (no fused multiply-add): numpy's statement of the query times
+__device__ __forceinline__ double query_time(double t0, double dt, int k) {
+#pragma clang fp contract(off)
+    const double s = dt * (double)k;
+    return t0 + s;
+}
+
+struct PrepArgs {
+    int N, n, m, nz, T;
+    int first, idx0;                    // first period after a reset: no shift (the guess is the planner's zero-input rollout)
+    double tk, dt;
+    const double *xcur, *xopt, *uopt;   // the states the plans start from (B x n: the plant's, or the filters' estimates), previous plan
+    const double *xplant;               // observed loop: the plant states, for row 0 of the records (null: xcur)
+    const double *tt, *tz, *tu, *phase; // target table (tz / tu / phase may be null)
+    const double *H;                    // (nz x n) of the planner's model
+    double *x0, *x_init, *u_init, *z, *zf, *ud;
+    double *Xrec, *Zrec;                // row 0 of the run's records (null: not this period / not wanted)
+    int64_t rec_rows;                   // rows per rollout of Xrec / Zrec
+};
+
+// one workgroup per rollout: x0 <- plant state, the shifted guess, the target window
+__global__ __launch_bounds__(256) void loop_prepare_kernel(PrepArgs a) {
+    const size_t b = blockIdx.x;
+    const int N = a.N, n = a.n, m = a.m, nz = a.nz, tid = threadIdx.x;
+    cgptr xc = (cgptr)a.xcur + b * n;
+    cgptr xr = a.xplant ? (cgptr)a.xplant + b * n : xc;
+    gptr x0 = (gptr)a.x0 + b * n;
+    for (int e = tid; e < n; e += 256) {
+        x0[e] = xc[e];
+        if (a.Xrec) ((gptr)a.Xrec)[b * (size_t)a.rec_rows * n + e] = xr[e];
+    }
+    if (a.Zrec) {
+        cgptr H = (cgptr)a.H;
+        for (int e = tid; e < nz; e += 256) {
+            double v = 0.0;
+            for (int c = 0; c < n; ++c) v = fma(H[e * n + c], xr[c], v);
+            ((gptr)a.Zrec)[b * (size_t)a.rec_rows * nz + e] = v;
+        }
+    }
+    if (!a.first) {
+        // rows idx0.. of the previous plan move to the front, its last row is held over the rest (ros.py:110-114)
+        cgptr xo = (cgptr)a.xopt + b * (size_t)(N + 1) * n, uo = (cgptr)a.uopt + b * (size_t)N * m;
+        gptr xi = (gptr)a.x_init + b * (size_t)(N + 1) * n, ui = (gptr)a.u_init + b * (size_t)N * m;
+        for (int e = tid; e < (N + 1) * n; e += 256) {
+            const int k = e / n, c = e - k * n;
+            xi[e] = xo[(size_t)min(k + a.idx0, N) * n + c];
+        }
+        for (int e = tid; e < N * m; e += 256) {
+            const int k = e / m, c = e - k * m;
+            ui[e] = uo[(size_t)min(k + a.idx0, N - 1) * m + c];
+        }
+    }
+    if (a.tz || a.tu) {
+        const double t0 = a.tk + (a.phase ? ((cgptr)a.phase)[b] : 0.0);
+        cgptr tt = (cgptr)a.tt;
+        if (a.tz) {
+            gptr z = (gptr)a.z + b * (size_t)(N + 1) * nz;
+            for (int e = tid; e < (N + 1) * nz; e += 256) {
+                const int k = e / nz, c = e - k * nz;
+                const double v = table_at(tt, (cgptr)a.tz, a.T, nz, c, query_time(t0, a.dt, k));
+                z[e] = v;
+                if (a.zf && k == N) ((gptr)a.zf)[b * nz + c] = v;
+            }
+        }
+        if (a.tu) {
+            gptr ud = (gptr)a.ud + b * (size_t)N * m;
+            for (int e = tid; e < N * m; e += 256) {
+                const int k = e / m, c = e - k * m;
+                ud[e] = table_at(tt, (cgptr)a.tu, a.T, m, c, query_time(t0, a.dt, k));
+            }
+        }
+    }
+}
+
+struct PinBuf {
+    char *p = nullptr;
+    size_t cap = 0;
+    ~PinBuf() { if (p) (void)hipHostFree(p); }
+    int need(size_t bytes) {
+        if (bytes <= cap) return SRH_OK;
+        if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
+        SRH_CHECK_HIP(hipHostMalloc((void **)&p, bytes, hipHostMallocDefault));
+        cap = bytes;
+        return SRH_OK;
+    }
+};
+
+}  // namespace

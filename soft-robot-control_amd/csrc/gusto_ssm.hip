@@ -844,6 +844,29 @@ int sgusto_ssm_plan_solve_dev(sgusto_ssm_plan_t *pl, const double *x0, const dou
     return rc;
 }
 
+/* The shapes the plan was created with (any output may be NULL); n_x is the MODEL's n, not the QP's augmented state. */
+int sgusto_ssm_plan_dims(const sgusto_ssm_plan_t *pl, int *N, int *n_x, int *n_u, int *n_z, int64_t *batch, double *dt, int *mode, int *ndU) {
+    SRH_REQUIRE(pl, "sgusto_ssm_plan_dims: null plan");
+    const QPDims &d = pl->C.dims;
+    if (N) *N = d.N;
+    if (n_x) *n_x = pl->n;
+    if (n_u) *n_u = d.m;
+    if (n_z) *n_z = d.nz;
+    if (batch) *batch = pl->batch;
+    if (dt) *dt = pl->par.dt;
+    if (mode) *mode = pl->mode;
+    if (ndU) *ndU = pl->ndU;
+    return SRH_OK;
+}
+
+/* As sgusto_plan_costs_dev: Jopt of the last solve, device to device on `stream`, behind the solve enqueued there. */
+int sgusto_ssm_plan_costs_dev(sgusto_ssm_plan_t *pl, double *J_dev, void *stream) {
+    SRH_REQUIRE(pl && J_dev, "sgusto_ssm_plan_costs_dev: null argument");
+    SRH_REQUIRE(pl->solved, "sgusto_ssm_plan_costs_dev: no solve yet");
+    SRH_CHECK_HIP(hipMemcpyAsync(J_dev, pl->Jopt.p, sizeof(double) * pl->batch, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return SRH_OK;
+}
+
 /* Host-pointer form: the arguments go through the plan's pinned block (memcpy in, ONE launch, ONE stream synchronisation, memcpy
  * out) -- the kernel copies what it reads more than once into its work block. */
 int sgusto_ssm_plan_solve(sgusto_ssm_plan_t *pl, const double *x0, const double *u_init, const double *x_init, const double *z,

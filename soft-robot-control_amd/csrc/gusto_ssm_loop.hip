@@ -1,0 +1,475 @@
+// Batched closed loop on a resident SSM GuSTO plan: every rollout of the plan's batch is its own receding-horizon loop of the reference's
+// hardware driver -- plan, apply n_keep interpolated inputs to an SSM plant, measure, estimate, shift, re-plan from the estimate -- and a
+// whole run of periods is one launch sequence on the handle's stream with one host wait.  Reference: examples/hardware/diamond_SSM.py:
+// 353-361 (the loop), scp/ros.py:78-79, 109-114 (first guess, shift), SSM/controllers.py:204, 237 (u = u_bar(t), no gain) and its
+// SSMObserver (x_hat = W_map(y - z_ref)), SSM/ssm.py:198-218, 279-301 (plant step).
+// The solve is sgusto_ssm_plan_solve_dev (gusto_ssm.hip), the first guess sssm_rollout_dev (ssm.hip), shift and target window the
+// prepare kernel shared with gusto_loop.hip (gusto_loop_prep.h).  New here: ssm_loop_advance_kernel.  Because the observer is a map and
+// not a filter, the whole sub-step -- input from the plan, plant step, measurement, estimate -- is one kernel for all n_keep sub-steps.
+#include "ssm_host.h"
+#include "gusto_loop_prep.h"
+
+#include <algorithm>
+
+namespace {
+
+constexpr int SL_NT = 256;
+
+struct SsmAdvArgs {
+    int N, n_keep, mode;                // horizon of the plan, sub-steps of this launch (0: none), the plant's discretisation
+    int init;                           // 1: measure and estimate at x_in before the sub-steps (reset: row 0 of the records)
+    int same;                           // the observer's model is the plant: its ssm basis is staged once
+    double dt_sim;
+    const double *uopt;                 // the plans' inputs (B x N x m)
+    const int32_t *js;                  // (n_keep) plan interval of every sub-step
+    const double *theta;                // (n_keep) position inside it
+    const double *W, *Vn;               // (steps x B x n), (steps x B x no) or null; this launch reads steps w_step0 ..
+    const double *v0;                   // init: (B x no) noise of the first measurement, or null
+    const double *x_in;                 // (B x n)
+    double *x_out, *z_out, *y_out, *xh_out;     // where the launch ends (B x .), any may be null (x_out may be x_in)
+    double *X, *Z, *U, *Y, *Xhat;       // records: row row0 + s of rollout b (any may be null)
+    int64_t rows_x, row0_x, rows_u, row0_u, B, w_step0;
+};
+
+// What the kernel reads of the observer's model (the planner's): the observed -> reduced map and the ssm basis it is written in
+struct SsmObsDev {
+    int ns, order_s;
+    const int *ps, *vs, *lvs;           // parent / variable of every monomial, first index of every degree (ssm::basis)
+    cgptr Vc, z_ref;                    // v_coeff (n x ns), z_ref (no)
+};
+
+SsmObsDev obs_view(const sssm *h) {
+    const SsmDev S = h->view();
+    return SsmObsDev{S.ns, S.order_s, S.ps, S.vs, S.lvs, S.Vc, S.z_ref};
+}
+
+// LDS of the launch in doubles: [work area | x, x', x_hat, u, zeta, y, y - z_ref, the two z_ref | A, B, d | V of the observer's model |
+// the plant's tables (ssm::stage) | the observer's ssm basis when it is another model]
+size_t ssm_loop_front_doubles(int n, int m, int no, int nr, int ns_max) {
+    return ssm::work_doubles(n, m, no, nr, ns_max) + 3 * (size_t)n + 16 + 5 * (size_t)no + (size_t)n * n + (size_t)n * m + n;
+}
+
+size_t ssm_loop_lds_bytes(const sssm *plant, const sssm *obs) {
+    const int ns_max = std::max(plant->ns, obs->ns);
+    size_t d = ssm_loop_front_doubles(plant->n, plant->m, plant->no, plant->nr, ns_max) + (size_t)plant->n * obs->ns +
+               ssm::lds_tab_doubles(plant->n, plant->no, plant->nr, plant->ns, 0);
+    if (obs != plant) d += (size_t)obs->ns + 1;
+    return srh::lds_request(sizeof(double) * (d + 2));
+}
+
+// One workgroup per loop, all n_keep sub-steps of a period.  S: the plant, P: the model of the observer (the planner's).  The plant's
+// coefficient rows and the evaluation tables of both its bases are staged once per launch (ssm::stage), V and z_ref of the observer's
+// model behind them; x, u, y and x_hat stay in LDS between sub-steps and only the records go to HBM.  Per sub-step: the input from the
+// plan; the plant's continuous Jacobians at (x, u) from the staged tables (ssm::jacobians_l) discretised at dt_sim on the elimination
+// paths of ssm::discretize; x' = A_d x + B_d u + d_d (+ w) in the sums of ssm_rollout_kernel; then `measure`: zeta = C_plant(x')
+// (ssm::observe_l), y = (zeta + z_ref_plant) + v, x_hat = V phi_s(y - z_ref_observer).  With init = 1 `measure` runs once at x_in first:
+// a launch of zero sub-steps is the reset's first observer update, so the maps are stated once.
+__global__ __launch_bounds__(SL_NT) void ssm_loop_advance_kernel(SsmDev S, SsmObsDev P, SsmAdvArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int n = S.n, m = S.m, no = S.no, N = a.N, tid = threadIdx.x, nt = SL_NT;
+    const size_t b = blockIdx.x;
+    const bool dm = a.mode == SSM_DISCRETE_MAP;
+    SsmDev Sc = S;
+    Sc.ns = max(S.ns, P.ns);                               // the work area's monomial vector serves both ssm bases
+    ssm::Work w;
+    ssm::carve(w, (lptr)smem, Sc);
+    lptr xs = (lptr)smem + ssm::work_doubles(n, m, no, S.nr, Sc.ns);
+    lptr xn = xs + n, xh = xn + n, us = xh + n;            // n each, u: 16
+    lptr zs = us + 16, ys = zs + no, yd = ys + no, zrl = yd + no, zrp = zrl + no;       // no each
+    lptr Al = zrp + no, Bl = Al + (size_t)n * n, dl = Bl + (size_t)n * m;
+    lptr Vl = dl + n;                                      // n x P.ns
+    lptr tab = Vl + (size_t)n * P.ns;
+    SsmLds T;
+    ssm::stage(T, tab, S, dm, 0);
+    liptr pps = T.ps, pvs = T.vs;                          // parent / variable tables of the observer's ssm basis
+    int plv[SSM_MAX_ORDER + 1];
+    for (int q = 0; q <= SSM_MAX_ORDER; ++q) plv[q] = a.same ? T.lvs[q] : (q <= P.order_s ? P.lvs[q] : 0);
+    if (!a.same) {
+        pps = (liptr)(tab + ssm::lds_tab_doubles(n, no, S.nr, S.ns, 0));
+        pvs = pps + P.ns;
+        for (int e = tid; e < P.ns; e += nt) { pps[e] = P.ps[e]; pvs[e] = P.vs[e]; }
+    }
+    for (int e = tid; e < n * P.ns; e += nt) Vl[e] = P.Vc[e];
+    for (int e = tid; e < no; e += nt) { zrl[e] = S.z_ref[e]; zrp[e] = P.z_ref[e]; }
+    for (int e = tid; e < n; e += nt) xs[e] = ((cgptr)a.x_in)[b * n + e];
+    __syncthreads();
+
+    // zeta, y and x_hat of the state in xs; v (no) or null; rows of the records or null.  Ends with a sync.
+    auto measure = [&](cgptr v, gptr Zr, gptr Yr, gptr XHr) {
+        ssm::observe_l(S, T, xs, w, zs);
+        for (int e = tid; e < no; e += nt) {
+            double y = zs[e] + zrl[e];
+            if (v != nullptr) y += v[e];
+            ys[e] = y;
+            yd[e] = y - zrp[e];
+            if (Zr != nullptr) Zr[e] = zs[e];
+            if (Yr != nullptr) Yr[e] = y;
+        }
+        __syncthreads();
+        ssm::basis_l(pps, pps, pvs, pps, plv, P.order_s, P.ns, no, yd, w.phi, (lptr) nullptr);      // (no derivative table: only parent / variable are read)
+        const int g8 = tid & 7;
+        for (int o0 = 0; o0 < n; o0 += nt / 8) {           // eight lanes per row, as ssm::observe_l
+            const int o = o0 + (tid >> 3);
+            double acc = 0.0;
+            if (o < n) for (int k = g8; k < P.ns; k += 8) acc = fma(Vl[(size_t)o * P.ns + k], w.phi[k], acc);
+            acc = wg::group_sum<8>(acc);
+            if (g8 == 0 && o < n) {
+                xh[o] = acc;
+                if (XHr != nullptr) XHr[o] = acc;
+            }
+        }
+        __syncthreads();
+    };
+
+    if (a.init) measure(a.v0 ? (cgptr)a.v0 + b * no : (cgptr) nullptr, (gptr) nullptr, (gptr) nullptr, (gptr) nullptr);
+    cgptr uo = (cgptr)a.uopt + b * (size_t)N * m, Wd = (cgptr)a.W, Vd = (cgptr)a.Vn, thg = (cgptr)a.theta;
+    cgiptr jsg = (cgiptr)a.js;
+    for (int s = 0; s < a.n_keep; ++s) {
+        const int js = jsg[s];
+        const double th = thg[s];
+        if (tid < m) {                                     // the input is held over the last interval (SSM/controllers.py:204)
+            const double lo = uo[(size_t)js * m + tid], hi = uo[(size_t)min(js + 1, N - 1) * m + tid];
+            const double v = lo + th * (hi - lo);
+            us[tid] = v;
+            if (a.U) ((gptr)a.U)[(b * (size_t)a.rows_u + a.row0_u + s) * m + tid] = v;
+        }
+        __syncthreads();
+        ssm::jacobians_l(S, T, dm, xs, us, w, Al, n, Bl, dl);
+        ssm::discretize(S, a.mode, a.dt_sim, w, Al, n, Bl, dl);
+        for (int i = tid; i < n; i += nt) {
+            double ax = 0.0, bu = 0.0;
+            for (int j = 0; j < n; ++j) ax = fma(Al[i * n + j], xs[j], ax);
+            for (int j = 0; j < m; ++j) bu = fma(Bl[i * m + j], us[j], bu);
+            double v = ax + bu + dl[i];
+            if (Wd != nullptr) v += Wd[((size_t)(a.w_step0 + s) * a.B + b) * n + i];
+            xn[i] = v;
+        }
+        __syncthreads();
+        const size_t row = b * (size_t)a.rows_x + a.row0_x + s;
+        for (int e = tid; e < n; e += nt) {
+            xs[e] = xn[e];
+            if (a.X) ((gptr)a.X)[row * n + e] = xn[e];
+        }
+        __syncthreads();
+        measure(Vd != nullptr ? Vd + ((size_t)(a.w_step0 + s) * a.B + b) * no : (cgptr) nullptr, a.Z ? (gptr)a.Z + row * no : (gptr) nullptr,
+                a.Y ? (gptr)a.Y + row * no : (gptr) nullptr, a.Xhat ? (gptr)a.Xhat + row * n : (gptr) nullptr);
+    }
+    for (int e = tid; e < n; e += nt) {
+        if (a.x_out) ((gptr)a.x_out)[b * n + e] = xs[e];
+        if (a.xh_out) ((gptr)a.xh_out)[b * n + e] = xh[e];
+    }
+    for (int e = tid; e < no; e += nt) {
+        if (a.z_out) ((gptr)a.z_out)[b * no + e] = zs[e];
+        if (a.y_out) ((gptr)a.y_out)[b * no + e] = ys[e];
+    }
+}
+
+// what both the loop and the stand-alone entry ask of the two models; `who` names the caller in the message
+int ssm_loop_check_models(const char *who, const sssm *plant, int plant_mode, const sssm *obs, size_t *lds) {
+    SRH_REQUIRE(plant_mode >= SSM_FE && plant_mode <= SSM_DISCRETE_MAP, "%s: plant_mode %d is not one of fe (1), be (2), bil (3), discrete map (4)", who,
+                plant_mode);
+    SRH_REQUIRE(plant_mode != SSM_DISCRETE_MAP || plant->has_discrete, "%s: the plant has no discrete map (rd_coeff, Bd) for plant_mode = 4", who);
+    SRH_REQUIRE(plant->n == obs->n && plant->m == obs->m && plant->no == obs->no,
+                "%s: the plant has n_x = %d, n_u = %d, n_o = %d, the planner's model n_x = %d, n_u = %d, n_o = %d", who, plant->n, plant->m, plant->no,
+                obs->n, obs->m, obs->no);
+    SRH_REQUIRE(plant->n == plant->no, "%s: the reduced -> observed map needs n_x == n_o (n_x = %d, n_o = %d)", who, plant->n, plant->no);
+    SRH_REQUIRE(plant->m <= 16, "%s: n_u = %d exceeds the limit n_u <= 16 of the staged input matrix", who, plant->m);
+    *lds = ssm_loop_lds_bytes(plant, obs);
+    SRH_REQUIRE(*lds <= (size_t)160 * 1024, "%s: the advance kernel needs %zu bytes of LDS for the plant's tables, the observer's V and the work area "
+                "(160 KiB = 163840 available)", who, *lds);
+    return SRH_OK;
+}
+
+int ssm_loop_launch(const sssm *plant, const sssm *obs, size_t lds, const SsmAdvArgs &a, hipStream_t st) {
+    SRH_CHECK_HIP(hipFuncSetAttribute((const void *)ssm_loop_advance_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    ssm_loop_advance_kernel<<<(unsigned)a.B, SL_NT, lds, st>>>(plant->view(), obs_view(obs), a);
+    SRH_CHECK_HIP(hipGetLastError());
+    return SRH_OK;
+}
+
+}  // namespace
+
+struct sgusto_ssm_loop {
+    sgusto_ssm_plan_t *plan = nullptr;
+    sssm *planner = nullptr, *plant = nullptr;
+    int N = 0, n = 0, m = 0, nz = 0, no = 0, n_keep = 0, T = 0, plan_mode = 0, plant_mode = 0;
+    int64_t B = 0, max_steps = 0;
+    double dt = 0.0, dt_sim = 0.0, t_start = 0.0;
+    bool observe = true, has_z = false, has_ud = false, has_phase = false, have_state = false;
+    int64_t k = 0;                      // periods since the last reset
+    int64_t waits = 0;                  // blocking host waits of the last run
+    size_t lds = 0;
+    hipStream_t stream = nullptr;
+    srh::DevBuf x0, u_init, x_init, z, ud, xopt, uopt, zopt, tt, tz, tu, phase, js, theta;
+    srh::DevBuf xcur, zcur, ycur, xhcur, v0;        // where the loops stand: plant state, its output, the last measurement, the estimate
+    srh::DevBuf Xrec, Zrec, Urec, Yrec, XHrec, Irec, Srec, Jrec, Wd, Vd;
+    PinBuf pX, pZ, pU, pY, pXH, pI, pS, pJ, pW, pV;
+    ~sgusto_ssm_loop() {
+        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+    }
+    SsmAdvArgs adv_args() const {
+        SsmAdvArgs a{};
+        a.N = N; a.n_keep = n_keep; a.mode = plant_mode; a.same = planner == plant ? 1 : 0;
+        a.dt_sim = dt_sim;
+        a.js = js.as<int32_t>(); a.theta = theta.as<double>();
+        a.B = B;
+        return a;
+    }
+};
+
+extern "C" {
+
+int sgusto_ssm_loop_create(sgusto_ssm_loop_t **out, sgusto_ssm_plan_t *plan, sssm_t *planner_model, sssm_t *plant, int plant_mode, double dt_sim,
+                           int n_keep, int observe, int64_t max_steps_per_run) {
+    SRH_REQUIRE(out && plan && planner_model && plant, "sgusto_ssm_loop_create: null argument");
+    int N, n, m, nz, mode, ndU;
+    int64_t B;
+    double dt;
+    int rc = sgusto_ssm_plan_dims(plan, &N, &n, &m, &nz, &B, &dt, &mode, &ndU);
+    if (rc) return rc;
+    SRH_REQUIRE(ndU == 0, "sgusto_ssm_loop_create: the plan has %d input-rate rows (dU): a rollout whose trust region binds under them returns status -78 "
+                "for the host loop, which a loop resident on the device cannot serve", ndU);
+    SRH_REQUIRE(planner_model->n == n && planner_model->m == m, "sgusto_ssm_loop_create: the planner's model (n_x = %d, n_u = %d) is not the model of the "
+                "plan (n_x = %d, n_u = %d)", planner_model->n, planner_model->m, n, m);
+    size_t lds = 0;
+    if ((rc = ssm_loop_check_models("sgusto_ssm_loop_create", plant, plant_mode, planner_model, &lds))) return rc;
+    SRH_REQUIRE(dt_sim > 0.0 && n_keep >= 1, "sgusto_ssm_loop_create: need dt_sim > 0 and n_keep >= 1");
+    SRH_REQUIRE(!((double)n_keep * dt_sim > (double)N * dt),
+                "sgusto_ssm_loop_create: n_keep * dt_sim = %g exceeds the horizon N * dt = %g (the shift of the previous plan would find no row)",
+                (double)n_keep * dt_sim, (double)N * dt);
+    SRH_REQUIRE(max_steps_per_run >= n_keep, "sgusto_ssm_loop_create: max_steps_per_run = %lld is below n_keep = %d", (long long)max_steps_per_run, n_keep);
+    sgusto_ssm_loop *h = new sgusto_ssm_loop();
+    h->plan = plan; h->planner = planner_model; h->plant = plant;
+    h->N = N; h->n = n; h->m = m; h->nz = nz; h->no = plant->no; h->n_keep = n_keep; h->B = B; h->max_steps = max_steps_per_run;
+    h->plan_mode = mode; h->plant_mode = plant_mode; h->observe = observe != 0;
+    h->dt = dt; h->dt_sim = dt_sim; h->lds = lds;
+    std::vector<int32_t> js(n_keep);
+    std::vector<double> th(n_keep);
+    (void)sgusto_loop_schedule(N, dt, dt_sim, n_keep, 0.0, 0, nullptr, nullptr, js.data(), th.data());
+    const size_t D = sizeof(double), S = (size_t)max_steps_per_run, P = S / n_keep, Bz = (size_t)B, no = (size_t)plant->no;
+    auto fail = [&](int code) { delete h; return code; };
+    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
+        srh::set_error("sgusto_ssm_loop_create: could not create the stream: %s", hipGetErrorString(hipGetLastError()));
+        return fail(SRH_EHIP);
+    }
+    if ((rc = h->x0.alloc(D * Bz * n)) || (rc = h->u_init.alloc(D * Bz * N * m)) || (rc = h->x_init.alloc(D * Bz * (N + 1) * n)) ||
+        (rc = h->z.alloc(D * Bz * (N + 1) * nz)) || (rc = h->ud.alloc(D * Bz * N * m)) || (rc = h->xopt.alloc(D * Bz * (N + 1) * n)) ||
+        (rc = h->uopt.alloc(D * Bz * N * m)) || (rc = h->zopt.alloc(D * Bz * (N + 1) * nz)) || (rc = h->xcur.alloc(D * Bz * n)) ||
+        (rc = h->zcur.alloc(D * Bz * no)) || (rc = h->ycur.alloc(D * Bz * no)) || (rc = h->xhcur.alloc(D * Bz * n)) || (rc = h->v0.alloc(D * Bz * no)) ||
+        (rc = h->js.upload(js.data(), sizeof(int32_t) * n_keep)) || (rc = h->theta.upload(th.data(), D * n_keep)) ||
+        (rc = h->Zrec.alloc(D * Bz * (S + 1) * no)) || (rc = h->Yrec.alloc(D * Bz * (S + 1) * no)) || (rc = h->XHrec.alloc(D * Bz * (S + 1) * n)) ||
+        (rc = h->Urec.alloc(D * Bz * S * m)) || (rc = h->Irec.alloc(sizeof(int32_t) * P * Bz)) || (rc = h->Srec.alloc(sizeof(int32_t) * P * Bz)) ||
+        (rc = h->Jrec.alloc(D * P * Bz)) || (rc = h->pZ.need(D * Bz * (S + 1) * no)) || (rc = h->pY.need(D * Bz * (S + 1) * no)) ||
+        (rc = h->pXH.need(D * Bz * (S + 1) * n)) || (rc = h->pU.need(D * Bz * S * m)) || (rc = h->pI.need(sizeof(int32_t) * P * Bz)) ||
+        (rc = h->pS.need(sizeof(int32_t) * P * Bz)) || (rc = h->pJ.need(D * P * Bz)))
+        return fail(rc);
+    *out = h;
+    return SRH_OK;
+}
+
+int sgusto_ssm_loop_destroy(sgusto_ssm_loop_t *h) {
+    delete h;
+    return SRH_OK;
+}
+
+int sgusto_ssm_loop_set_target(sgusto_ssm_loop_t *h, int T, const double *t, const double *z, const double *u_des, const double *phase) {
+    SRH_REQUIRE(h && t && (z || u_des), "sgusto_ssm_loop_set_target: null argument");
+    SRH_REQUIRE(T >= 2, "sgusto_ssm_loop_set_target: the table needs at least two rows");
+    for (int i = 1; i < T; ++i) SRH_REQUIRE(t[i] > t[i - 1], "sgusto_ssm_loop_set_target: t must increase (row %d)", i);
+    SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
+    int rc;
+    if ((rc = h->tt.upload(t, sizeof(double) * T))) return rc;
+    if (z && (rc = h->tz.upload(z, sizeof(double) * T * h->nz))) return rc;
+    if (u_des && (rc = h->tu.upload(u_des, sizeof(double) * T * h->m))) return rc;
+    if (phase && (rc = h->phase.upload(phase, sizeof(double) * h->B))) return rc;
+    h->T = T; h->has_z = z != nullptr; h->has_ud = u_des != nullptr; h->has_phase = phase != nullptr;
+    return SRH_OK;
+}
+
+int sgusto_ssm_loop_reset(sgusto_ssm_loop_t *h, const double *x0, const double *v0, double t_start) {
+    SRH_REQUIRE(h && x0, "sgusto_ssm_loop_reset: null argument");
+    SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
+    h->have_state = false;
+    const size_t D = sizeof(double), B = (size_t)h->B;
+    SRH_CHECK_HIP(hipMemcpy(h->xcur.p, x0, D * B * h->n, hipMemcpyHostToDevice));
+    if (v0) SRH_CHECK_HIP(hipMemcpy(h->v0.p, v0, D * B * h->no, hipMemcpyHostToDevice));
+    // the first observer update: the advance kernel with zero sub-steps
+    SsmAdvArgs a = h->adv_args();
+    a.n_keep = 0; a.init = 1;
+    a.v0 = v0 ? h->v0.as<double>() : nullptr;
+    a.x_in = h->xcur.as<double>();
+    a.z_out = h->zcur.as<double>(); a.y_out = h->ycur.as<double>(); a.xh_out = h->xhcur.as<double>();
+    const int rc = ssm_loop_launch(h->plant, h->planner, h->lds, a, h->stream);
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    if (rc) return rc;
+    SRH_CHECK_HIP(e);
+    h->t_start = t_start; h->k = 0; h->have_state = true;
+    return SRH_OK;
+}
+
+int sgusto_ssm_loop_run(sgusto_ssm_loop_t *h, int periods, const double *W, const double *V, double *X_cl, double *Z_cl, double *U_cl, double *Y_cl,
+                        double *Xhat, int32_t *iters, int32_t *status, double *J) {
+    SRH_REQUIRE(h && Z_cl && U_cl && Y_cl && Xhat && iters && status && J, "sgusto_ssm_loop_run: null argument");
+    SRH_REQUIRE(periods >= 1, "sgusto_ssm_loop_run: periods must be positive");
+    SRH_REQUIRE(h->have_state, "sgusto_ssm_loop_run: no plant state yet (call sgusto_ssm_loop_reset first)");
+    const int N = h->N, n = h->n, m = h->m, nz = h->nz, nk = h->n_keep;
+    const size_t D = sizeof(double), B = (size_t)h->B, S = (size_t)periods * nk, no = (size_t)h->no;
+    SRH_REQUIRE((int64_t)S <= h->max_steps, "sgusto_ssm_loop_run: periods * n_keep = %lld exceeds max_steps_per_run = %lld", (long long)S,
+                (long long)h->max_steps);
+    int rc;
+    if (X_cl && ((rc = h->pX.need(D * B * (h->max_steps + 1) * n)) || (!h->Xrec.p && (rc = h->Xrec.alloc(D * B * (h->max_steps + 1) * n))))) return rc;
+    if (W && ((rc = h->pW.need(D * h->max_steps * B * n)) || (!h->Wd.p && (rc = h->Wd.alloc(D * h->max_steps * B * n))))) return rc;
+    if (V && ((rc = h->pV.need(D * h->max_steps * B * no)) || (!h->Vd.p && (rc = h->Vd.alloc(D * h->max_steps * B * no))))) return rc;
+    h->waits = 0;
+    hipStream_t st = h->stream;
+    // from here on work is enqueued on the handle's stream: on any error it is drained before returning
+    auto body = [&]() -> int {
+        if (W) {
+            memcpy(h->pW.p, W, D * S * B * n);
+            SRH_CHECK_HIP(hipMemcpyAsync(h->Wd.p, h->pW.p, D * S * B * n, hipMemcpyHostToDevice, st));
+        }
+        if (V) {
+            memcpy(h->pV.p, V, D * S * B * no);
+            SRH_CHECK_HIP(hipMemcpyAsync(h->Vd.p, h->pV.p, D * S * B * no, hipMemcpyHostToDevice, st));
+        }
+        // row 0 of the records: where the loops stand
+        if (X_cl) SRH_CHECK_HIP(hipMemcpy2DAsync(h->Xrec.p, D * (S + 1) * n, h->xcur.p, D * n, D * n, B, hipMemcpyDeviceToDevice, st));
+        SRH_CHECK_HIP(hipMemcpy2DAsync(h->Zrec.p, D * (S + 1) * no, h->zcur.p, D * no, D * no, B, hipMemcpyDeviceToDevice, st));
+        SRH_CHECK_HIP(hipMemcpy2DAsync(h->Yrec.p, D * (S + 1) * no, h->ycur.p, D * no, D * no, B, hipMemcpyDeviceToDevice, st));
+        SRH_CHECK_HIP(hipMemcpy2DAsync(h->XHrec.p, D * (S + 1) * n, h->xhcur.p, D * n, D * n, B, hipMemcpyDeviceToDevice, st));
+        for (int p = 0; p < periods; ++p) {
+            const int64_t k = h->k + p;
+            PrepArgs a{};
+            a.N = N; a.n = n; a.m = m; a.nz = nz; a.T = h->T;
+            a.first = k == 0 ? 1 : 0;
+            a.dt = h->dt;
+            (void)sgusto_loop_schedule(N, h->dt, h->dt_sim, nk, h->t_start, k, &a.tk, &a.idx0, nullptr, nullptr);
+            // the plan starts from the estimate (the reference's loop) or from the plant state (perfect state feedback)
+            a.xcur = h->observe ? h->xhcur.as<double>() : h->xcur.as<double>();
+            a.xopt = h->xopt.as<double>(); a.uopt = h->uopt.as<double>();
+            a.tt = h->tt.as<double>();
+            a.tz = h->has_z ? h->tz.as<double>() : nullptr;
+            a.tu = h->has_ud ? h->tu.as<double>() : nullptr;
+            a.phase = h->has_phase ? h->phase.as<double>() : nullptr;
+            a.x0 = h->x0.as<double>(); a.x_init = h->x_init.as<double>(); a.u_init = h->u_init.as<double>();
+            a.z = h->z.as<double>(); a.ud = h->ud.as<double>();      // (no H, no zf, no record rows: the advance kernel writes the records)
+            if (a.first) SRH_CHECK_HIP(hipMemsetAsync(h->u_init.p, 0, D * B * N * m, st));
+            loop_prepare_kernel<<<(unsigned)B, 256, 0, st>>>(a);
+            SRH_CHECK_HIP(hipGetLastError());
+            // scp/ros.py:78-79: the first guess is the planner's own zero-input rollout from x0
+            if (a.first && (rc = sssm_rollout_dev(h->planner, a.x0, a.u_init, N, (int64_t)B, h->plan_mode, h->dt, a.x_init, nullptr, (void *)st))) return rc;
+            if ((rc = sgusto_ssm_plan_solve_dev(h->plan, a.x0, a.u_init, a.x_init, h->has_z ? a.z : nullptr, h->has_ud ? a.ud : nullptr,
+                                                h->xopt.as<double>(), h->uopt.as<double>(), h->zopt.as<double>(), h->Irec.as<int32_t>() + p * B,
+                                                h->Srec.as<int32_t>() + p * B, nullptr, (void *)st)) ||
+                (rc = sgusto_ssm_plan_costs_dev(h->plan, h->Jrec.as<double>() + p * B, (void *)st)))
+                return rc;
+            SsmAdvArgs v = h->adv_args();
+            v.uopt = a.uopt;
+            v.W = W ? h->Wd.as<double>() : nullptr; v.Vn = V ? h->Vd.as<double>() : nullptr; v.w_step0 = (int64_t)p * nk;
+            v.x_in = h->xcur.as<double>();
+            v.x_out = h->xcur.as<double>(); v.z_out = h->zcur.as<double>(); v.y_out = h->ycur.as<double>(); v.xh_out = h->xhcur.as<double>();
+            v.X = X_cl ? h->Xrec.as<double>() : nullptr; v.Z = h->Zrec.as<double>(); v.U = h->Urec.as<double>();
+            v.Y = h->Yrec.as<double>(); v.Xhat = h->XHrec.as<double>();
+            v.rows_x = (int64_t)S + 1; v.row0_x = (int64_t)p * nk + 1; v.rows_u = (int64_t)S; v.row0_u = (int64_t)p * nk;
+            if ((rc = ssm_loop_launch(h->plant, h->planner, h->lds, v, st))) return rc;
+        }
+        if (X_cl) SRH_CHECK_HIP(hipMemcpyAsync(h->pX.p, h->Xrec.p, D * B * (S + 1) * n, hipMemcpyDeviceToHost, st));
+        SRH_CHECK_HIP(hipMemcpyAsync(h->pZ.p, h->Zrec.p, D * B * (S + 1) * no, hipMemcpyDeviceToHost, st));
+        SRH_CHECK_HIP(hipMemcpyAsync(h->pY.p, h->Yrec.p, D * B * (S + 1) * no, hipMemcpyDeviceToHost, st));
+        SRH_CHECK_HIP(hipMemcpyAsync(h->pXH.p, h->XHrec.p, D * B * (S + 1) * n, hipMemcpyDeviceToHost, st));
+        SRH_CHECK_HIP(hipMemcpyAsync(h->pU.p, h->Urec.p, D * B * S * m, hipMemcpyDeviceToHost, st));
+        SRH_CHECK_HIP(hipMemcpyAsync(h->pI.p, h->Irec.p, sizeof(int32_t) * periods * B, hipMemcpyDeviceToHost, st));
+        SRH_CHECK_HIP(hipMemcpyAsync(h->pS.p, h->Srec.p, sizeof(int32_t) * periods * B, hipMemcpyDeviceToHost, st));
+        SRH_CHECK_HIP(hipMemcpyAsync(h->pJ.p, h->Jrec.p, D * periods * B, hipMemcpyDeviceToHost, st));
+        h->waits += 1;
+        SRH_CHECK_HIP(hipStreamSynchronize(st));
+        return SRH_OK;
+    };
+    if ((rc = body())) {
+        (void)hipStreamSynchronize(st);
+        h->have_state = false;          // part of a run was enqueued: the state is not the one the caller knows
+        return rc;
+    }
+    if (X_cl) memcpy(X_cl, h->pX.p, D * B * (S + 1) * n);
+    memcpy(Z_cl, h->pZ.p, D * B * (S + 1) * no);
+    memcpy(Y_cl, h->pY.p, D * B * (S + 1) * no);
+    memcpy(Xhat, h->pXH.p, D * B * (S + 1) * n);
+    memcpy(U_cl, h->pU.p, D * B * S * m);
+    memcpy(iters, h->pI.p, sizeof(int32_t) * periods * B);
+    memcpy(status, h->pS.p, sizeof(int32_t) * periods * B);
+    memcpy(J, h->pJ.p, D * periods * B);
+    h->k += periods;
+    return SRH_OK;
+}
+
+int sgusto_ssm_loop_last_inputs(sgusto_ssm_loop_t *h, double *x0, double *u_init, double *x_init, double *z, double *u_des) {
+    SRH_REQUIRE(h, "sgusto_ssm_loop_last_inputs: null handle");
+    SRH_REQUIRE(h->have_state && h->k > 0, "sgusto_ssm_loop_last_inputs: no period has run since the last reset");
+    const size_t D = sizeof(double), B = (size_t)h->B, N = h->N, n = h->n, m = h->m, nz = h->nz;
+    SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
+    int rc;
+    if (x0 && (rc = h->x0.download(x0, D * B * n))) return rc;
+    if (u_init && (rc = h->u_init.download(u_init, D * B * N * m))) return rc;
+    if (x_init && (rc = h->x_init.download(x_init, D * B * (N + 1) * n))) return rc;
+    if (z && h->has_z && (rc = h->z.download(z, D * B * (N + 1) * nz))) return rc;
+    if (u_des && h->has_ud && (rc = h->ud.download(u_des, D * B * N * m))) return rc;
+    return SRH_OK;
+}
+
+int sgusto_ssm_loop_last_plan(sgusto_ssm_loop_t *h, double *xopt, double *uopt) {
+    SRH_REQUIRE(h, "sgusto_ssm_loop_last_plan: null handle");
+    SRH_REQUIRE(h->have_state && h->k > 0, "sgusto_ssm_loop_last_plan: no period has run since the last reset");
+    const size_t D = sizeof(double), B = (size_t)h->B, N = h->N;
+    SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
+    int rc;
+    if (xopt && (rc = h->xopt.download(xopt, D * B * (N + 1) * h->n))) return rc;
+    if (uopt && (rc = h->uopt.download(uopt, D * B * N * h->m))) return rc;
+    return SRH_OK;
+}
+
+int sgusto_ssm_loop_stats(sgusto_ssm_loop_t *h, int64_t *steps, int64_t *waits_last_run) {
+    SRH_REQUIRE(h, "sgusto_ssm_loop_stats: null handle");
+    if (steps) *steps = h->k;
+    if (waits_last_run) *waits_last_run = h->waits;
+    return SRH_OK;
+}
+
+int sgusto_ssm_loop_advance(sssm_t *plant, int plant_mode, sssm_t *observer_model, double dt_sim, int N, int n_keep, int64_t batch, const int32_t *j,
+                            const double *theta, const double *xopt, const double *uopt, const double *x, const double *W, const double *V, double *X,
+                            double *Z, double *U, double *Y, double *Xhat) {
+    SRH_REQUIRE(plant && observer_model && j && theta && uopt && x && X && Z && U && Y && Xhat, "sgusto_ssm_loop_advance: null argument");
+    SRH_REQUIRE(N >= 1 && n_keep >= 1 && batch >= 1 && dt_sim > 0.0, "sgusto_ssm_loop_advance: need N, n_keep, batch >= 1 and dt_sim > 0");
+    for (int s = 0; s < n_keep; ++s)
+        SRH_REQUIRE(j[s] >= 0 && j[s] <= N - 1, "sgusto_ssm_loop_advance: j[%d] = %d is not an interval 0..N-1 of the plan (N = %d)", s, j[s], N);
+    (void)xopt;                         // (the law u = u_bar(t) has no gain: the plan's states are not read)
+    size_t lds = 0;
+    int rc;
+    if ((rc = ssm_loop_check_models("sgusto_ssm_loop_advance", plant, plant_mode, observer_model, &lds))) return rc;
+    const size_t D = sizeof(double), B = (size_t)batch, n = plant->n, m = plant->m, no = plant->no, nk = n_keep;
+    srh::DevBuf dj, dth, duo, dx, dW, dV, dX, dZ, dU, dY, dXH;
+    if ((rc = dj.upload(j, sizeof(int32_t) * nk)) || (rc = dth.upload(theta, D * nk)) || (rc = duo.upload(uopt, D * B * N * m)) ||
+        (rc = dx.upload(x, D * B * n)) || (W && (rc = dW.upload(W, D * nk * B * n))) || (V && (rc = dV.upload(V, D * nk * B * no))) ||
+        (rc = dX.alloc(D * B * nk * n)) || (rc = dZ.alloc(D * B * nk * no)) || (rc = dU.alloc(D * B * nk * m)) || (rc = dY.alloc(D * B * nk * no)) ||
+        (rc = dXH.alloc(D * B * nk * n)))
+        return rc;
+    SsmAdvArgs a{};
+    a.N = N; a.n_keep = n_keep; a.mode = plant_mode; a.same = observer_model == plant ? 1 : 0;
+    a.dt_sim = dt_sim;
+    a.js = dj.as<int32_t>(); a.theta = dth.as<double>();
+    a.uopt = duo.as<double>();
+    a.W = W ? dW.as<double>() : nullptr; a.Vn = V ? dV.as<double>() : nullptr;
+    a.x_in = dx.as<double>();
+    a.X = dX.as<double>(); a.Z = dZ.as<double>(); a.U = dU.as<double>(); a.Y = dY.as<double>(); a.Xhat = dXH.as<double>();
+    a.rows_x = (int64_t)nk; a.rows_u = (int64_t)nk; a.B = batch;
+    rc = ssm_loop_launch(plant, observer_model, lds, a, nullptr);
+    // (the temporaries go back to the allocation cache when this returns: wait for the kernel whatever it answered)
+    const hipError_t e = hipStreamSynchronize(nullptr);
+    if (rc) return rc;
+    SRH_CHECK_HIP(e);
+    if ((rc = dX.download(X, D * B * nk * n)) || (rc = dZ.download(Z, D * B * nk * no)) || (rc = dU.download(U, D * B * nk * m)) ||
+        (rc = dY.download(Y, D * B * nk * no)) || (rc = dXH.download(Xhat, D * B * nk * n)))
+        return rc;
+    return SRH_OK;
+}
+
+}  // extern "C"

@@ -384,6 +384,20 @@ int sssm_reduce(sssm_t *h, const double *Z, int64_t B, double *X) {
     return dX.download(X, sizeof(double) * B * h->n);
 }
 
+int sssm_rollout_dev(sssm_t *h, const double *x0_dev, const double *U_dev, int N, int64_t batch, int mode, double dt, double *X_dev,
+                     double *Z_dev, void *stream) {
+    SRH_REQUIRE(h && x0_dev && U_dev && X_dev, "sssm_rollout_dev: null argument");
+    SRH_REQUIRE(N >= 0 && batch >= 0, "sssm_rollout_dev: negative size");
+    SRH_REQUIRE(mode != SSM_CONT, "sssm_rollout_dev: need a discretisation mode");
+    SRH_REQUIRE(Z_dev == nullptr || h->n == h->no, "sssm_rollout_dev: the reduced -> observed map needs n_x == n_o");
+    int rc;
+    if ((rc = check_mode(h, mode))) return rc;
+    if (batch == 0) return SRH_OK;
+    ssm_rollout_kernel<<<(unsigned)batch, SSM_NT, h->lds, (hipStream_t)stream>>>(h->view(), x0_dev, U_dev, N, mode, dt, X_dev, Z_dev);
+    SRH_CHECK_HIP(hipGetLastError());
+    return SRH_OK;
+}
+
 int sssm_rollout(sssm_t *h, const double *x0, const double *U, int N, int64_t batch, int mode, double dt, double *X,
                  double *Z) {
     SRH_REQUIRE(h && x0 && U && X, "sssm_rollout: null argument");
@@ -399,9 +413,8 @@ int sssm_rollout(sssm_t *h, const double *x0, const double *U, int N, int64_t ba
         (rc = dX.alloc(sizeof(double) * batch * (N + 1) * n)))
         return rc;
     if (Z && (rc = dZ.alloc(sizeof(double) * batch * (N + 1) * no))) return rc;
-    ssm_rollout_kernel<<<(unsigned)batch, SSM_NT, h->lds>>>(h->view(), d0.as<double>(), dU.as<double>(), N, mode, dt,
-                                                            dX.as<double>(), Z ? dZ.as<double>() : nullptr);
-    SRH_CHECK_HIP(hipGetLastError());
+    if ((rc = sssm_rollout_dev(h, d0.as<double>(), dU.as<double>(), N, batch, mode, dt, dX.as<double>(), Z ? dZ.as<double>() : nullptr, nullptr)))
+        return rc;
     SRH_CHECK_HIP(hipStreamSynchronize(nullptr));
     if ((rc = dX.download(X, sizeof(double) * batch * (N + 1) * n))) return rc;
     if (Z && (rc = dZ.download(Z, sizeof(double) * batch * (N + 1) * no))) return rc;
