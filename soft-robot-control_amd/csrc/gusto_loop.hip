@@ -2,10 +2,11 @@
 // n_keep inputs to a TPWL plant, shift, re-plan from the plant state -- and a whole run of periods is one launch sequence on the handle's
 // stream with one host wait.  Reference: sofacontrol/scp/standalone.py:29-33 (targets, first guess), scp/ros.py:109-114 (shift),
 // tpwl/controllers.py:298-333 (the scp controller's interpolated plan and feedback law), tpwl/tpwl.py:160-168, 336-339 (plant step).
-// The solve itself is sgusto_plan_solve_dev (gusto.hip); this unit is the glue around it: loop_prepare_kernel turns the previous
-// period's output into the next solve's input, loop_advance_kernel runs the plant under the feedback law for the n_keep sub-steps.
+// The solve itself is sgusto_plan_solve_dev (gusto.hip); this unit is the glue around it: loop_prepare_kernel (gusto_loop_prep.h) turns
+// the previous period's output into the next solve's input, loop_advance_kernel runs the plant under the feedback law for the n_keep
+// sub-steps.  The host shell of a handle and of a run -- shared with gusto_ssm_loop.hip -- is gusto_loop_host.h.
 #include "observer_host.h"
-#include "gusto_loop_prep.h"
+#include "gusto_loop_host.h"
 
 namespace {
 
@@ -174,31 +175,20 @@ __global__ __launch_bounds__(64) void loop_estimate_record_kernel(const double *
 
 }  // namespace
 
-struct sgusto_loop {
+struct sgusto_loop : LoopCore {
     sgusto_plan_t *plan = nullptr;
     stpwl *planner = nullptr, *plant = nullptr;
-    int N = 0, n = 0, m = 0, nz = 0, n_keep = 0, T = 0;
-    int64_t B = 0, max_steps = 0;
-    double dt = 0.0, dt_sim = 0.0, t_start = 0.0;
-    bool has_Qzf = false, has_z = false, has_ud = false, has_phase = false, has_K = false, have_state = false;
+    bool has_Qzf = false, has_K = false;
     // the observed loop: the attached filters (sgusto_loop_set_observer) and whether the state is an observed one (plant states and
     // estimates installed together by sgusto_loop_reset_observed)
     sekf_batch *obs = nullptr;
     int ny = 0;
     bool observed_state = false;
     size_t lds_obs = 0;
-    int64_t k = 0;                      // periods since the last reset
-    int64_t waits = 0;                  // blocking host waits of the last run
-    size_t lds = 0;
-    hipStream_t stream = nullptr;
-    srh::DevBuf x0, u_init, x_init, z, zf, ud, xopt, uopt, zopt, xcur, tt, tz, tu, phase, K, js, theta;
-    srh::DevBuf Xrec, Zrec, Urec, Irec, Srec, Jrec, Wd;
-    PinBuf pX, pZ, pU, pI, pS, pJ, pW;
-    srh::DevBuf XHrec, Yrec, Erec, Vd;  // observed loop: estimates (B x (S + 1) x n), measurements (B x S x ny), filter status (P x B), noise
-    PinBuf pXH, pY, pE, pV;
-    ~sgusto_loop() {
-        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
-    }
+    srh::DevBuf K, zf;
+    LoopRec Erec;                       // observed loop: the filters' status (P x B); Y is (B x S x ny) here
+    __attribute__((always_inline)) sgusto_loop() { recs.push_back(&Erec); }       // (inlined: no constructor among the library's dynamic symbols)
+    ~sgusto_loop() { drain(); }
     AdvArgs adv_args() const {
         AdvArgs a{};
         a.N = N; a.n_keep = n_keep; a.nz = nz;
@@ -287,38 +277,21 @@ int sgusto_loop_create(sgusto_loop_t **out, sgusto_plan_t *plan, stpwl_t *planne
     SRH_REQUIRE(plant->n == n && plant->m == m, "sgusto_loop_create: the plant has n_x = %d, n_u = %d, the plan n_x = %d, n_u = %d",
                 plant->n, plant->m, n, m);
     SRH_REQUIRE(plant->has_discrete, "sgusto_loop_create: the plant has not been pre-discretised at dt_sim");
-    SRH_REQUIRE(dt_sim > 0.0 && n_keep >= 1, "sgusto_loop_create: need dt_sim > 0 and n_keep >= 1");
-    SRH_REQUIRE(!((double)n_keep * dt_sim > (double)N * dt),
-                "sgusto_loop_create: n_keep * dt_sim = %g exceeds the horizon N * dt = %g (the shift of the previous plan would find no row)",
-                (double)n_keep * dt_sim, (double)N * dt);
-    SRH_REQUIRE(max_steps_per_run >= n_keep, "sgusto_loop_create: max_steps_per_run = %lld is below n_keep = %d", (long long)max_steps_per_run, n_keep);
+    if ((rc = loop_check_periods("sgusto_loop_create", N, dt, dt_sim, n_keep, max_steps_per_run))) return rc;
     sgusto_loop *h = new sgusto_loop();
     h->plan = plan; h->planner = planner_model; h->plant = plant;
-    h->N = N; h->n = n; h->m = m; h->nz = nz; h->n_keep = n_keep; h->B = B; h->max_steps = max_steps_per_run;
-    h->dt = dt; h->dt_sim = dt_sim; h->has_Qzf = has_Qzf != 0;
+    h->has_Qzf = has_Qzf != 0;
     h->lds = advance_lds_bytes(n, m, false);
-    std::vector<int32_t> js(n_keep);
-    std::vector<double> th(n_keep);
-    (void)sgusto_loop_schedule(N, dt, dt_sim, n_keep, 0.0, 0, nullptr, nullptr, js.data(), th.data());
-    const size_t D = sizeof(double), S = (size_t)max_steps_per_run, P = S / n_keep, Bz = (size_t)B;
+    const char *what = "set up the advance kernel / the stream";
     auto fail = [&](int code) { delete h; return code; };
     if (h->lds > (size_t)160 * 1024) {
         srh::set_error("sgusto_loop_create: the advance kernel needs %zu bytes of LDS (160 KiB available)", h->lds);
         return fail(SRH_EINVAL);
     }
-    if (hipFuncSetAttribute((const void *)loop_advance_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds) != hipSuccess ||
-        hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        srh::set_error("sgusto_loop_create: could not set up the advance kernel / the stream: %s", hipGetErrorString(hipGetLastError()));
-        return fail(SRH_EHIP);
-    }
-    if ((rc = h->x0.alloc(D * Bz * n)) || (rc = h->u_init.alloc(D * Bz * N * m)) || (rc = h->x_init.alloc(D * Bz * (N + 1) * n)) ||
-        (rc = h->z.alloc(D * Bz * (N + 1) * nz)) || (rc = h->zf.alloc(D * Bz * nz)) || (rc = h->ud.alloc(D * Bz * N * m)) ||
-        (rc = h->xopt.alloc(D * Bz * (N + 1) * n)) || (rc = h->uopt.alloc(D * Bz * N * m)) || (rc = h->zopt.alloc(D * Bz * (N + 1) * nz)) ||
-        (rc = h->xcur.alloc(D * Bz * n)) || (rc = h->js.upload(js.data(), sizeof(int32_t) * n_keep)) ||
-        (rc = h->theta.upload(th.data(), D * n_keep)) || (rc = h->Zrec.alloc(D * Bz * (S + 1) * nz)) || (rc = h->Urec.alloc(D * Bz * S * m)) ||
-        (rc = h->Irec.alloc(sizeof(int32_t) * P * Bz)) || (rc = h->Srec.alloc(sizeof(int32_t) * P * Bz)) || (rc = h->Jrec.alloc(D * P * Bz)) ||
-        (rc = h->pZ.need(D * Bz * (S + 1) * nz)) || (rc = h->pU.need(D * Bz * S * m)) || (rc = h->pI.need(sizeof(int32_t) * P * Bz)) ||
-        (rc = h->pS.need(sizeof(int32_t) * P * Bz)) || (rc = h->pJ.need(D * P * Bz)))
+    if (hipFuncSetAttribute((const void *)loop_advance_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds) != hipSuccess)
+        return fail(loop_setup_failed("sgusto_loop_create", what));
+    if ((rc = h->setup("sgusto_loop_create", what, N, n, m, nz, B, dt, dt_sim, n_keep, max_steps_per_run, nz)) ||
+        (rc = h->zf.alloc(sizeof(double) * B * nz)))
         return fail(rc);
     *out = h;
     return SRH_OK;
@@ -330,17 +303,7 @@ int sgusto_loop_destroy(sgusto_loop_t *h) {
 }
 
 int sgusto_loop_set_target(sgusto_loop_t *h, int T, const double *t, const double *z, const double *u_des, const double *phase) {
-    SRH_REQUIRE(h && t && (z || u_des), "sgusto_loop_set_target: null argument");
-    SRH_REQUIRE(T >= 2, "sgusto_loop_set_target: the table needs at least two rows");
-    for (int i = 1; i < T; ++i) SRH_REQUIRE(t[i] > t[i - 1], "sgusto_loop_set_target: t must increase (row %d)", i);
-    SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
-    int rc;
-    if ((rc = h->tt.upload(t, sizeof(double) * T))) return rc;
-    if (z && (rc = h->tz.upload(z, sizeof(double) * T * h->nz))) return rc;
-    if (u_des && (rc = h->tu.upload(u_des, sizeof(double) * T * h->m))) return rc;
-    if (phase && (rc = h->phase.upload(phase, sizeof(double) * h->B))) return rc;
-    h->T = T; h->has_z = z != nullptr; h->has_ud = u_des != nullptr; h->has_phase = phase != nullptr;
-    return SRH_OK;
+    return loop_set_target(h, "sgusto_loop_set_target", T, t, z, u_des, phase);
 }
 
 int sgusto_loop_set_feedback(sgusto_loop_t *h, const double *K) {
@@ -366,108 +329,33 @@ int sgusto_loop_reset(sgusto_loop_t *h, const double *x0, double t_start) {
 static int loop_run(sgusto_loop_t *h, int periods, const double *W, const double *Vn, double *X_cl, double *Z_cl, double *U_cl, int32_t *iters,
                     int32_t *status, double *J, double *Xhat, double *Y_cl, int32_t *ekf_status) {
     const bool observed = Xhat != nullptr;
-    const int N = h->N, n = h->n, m = h->m, nz = h->nz, nk = h->n_keep;
-    const size_t D = sizeof(double), B = (size_t)h->B, S = (size_t)periods * nk;
-    SRH_REQUIRE((int64_t)S <= h->max_steps, "sgusto_loop_run: periods * n_keep = %lld exceeds max_steps_per_run = %lld", (long long)S,
-                (long long)h->max_steps);
-    int rc;
-    if (X_cl && ((rc = h->pX.need(D * B * (h->max_steps + 1) * n)) || (!h->Xrec.p && (rc = h->Xrec.alloc(D * B * (h->max_steps + 1) * n))))) return rc;
-    if (W && ((rc = h->pW.need(D * h->max_steps * B * n)) || (!h->Wd.p && (rc = h->Wd.alloc(D * h->max_steps * B * n))))) return rc;
-    const size_t ny = (size_t)h->ny;
-    if (Vn && ((rc = h->pV.need(D * h->max_steps * B * ny)) || (!h->Vd.p && (rc = h->Vd.alloc(D * h->max_steps * B * ny))))) return rc;
-    double *xhat = observed ? h->obs->x_dev() : nullptr;
-    h->waits = 0;
-    hipStream_t st = h->stream;
-    // from here on work is enqueued on the handle's stream: on any error it is drained before returning
-    auto body = [&]() -> int {
-        if (W) {
-            memcpy(h->pW.p, W, D * S * B * n);
-            SRH_CHECK_HIP(hipMemcpyAsync(h->Wd.p, h->pW.p, D * S * B * n, hipMemcpyHostToDevice, st));
-        }
-        if (Vn) {
-            memcpy(h->pV.p, Vn, D * S * B * ny);
-            SRH_CHECK_HIP(hipMemcpyAsync(h->Vd.p, h->pV.p, D * S * B * ny, hipMemcpyHostToDevice, st));
-        }
-        if (observed)              // row 0 of the estimate record: the estimates the run starts from
-            SRH_CHECK_HIP(hipMemcpy2DAsync(h->XHrec.p, D * (S + 1) * n, xhat, D * n, D * n, B, hipMemcpyDeviceToDevice, st));
-        for (int p = 0; p < periods; ++p) {
-            const int64_t k = h->k + p;
-            PrepArgs a{};
-            a.N = N; a.n = n; a.m = m; a.nz = nz; a.T = h->T;
-            a.first = k == 0 ? 1 : 0;
-            a.dt = h->dt;
-            (void)sgusto_loop_schedule(N, h->dt, h->dt_sim, nk, h->t_start, k, &a.tk, &a.idx0, nullptr, nullptr);
-            // with an observer the plan starts from the estimate; row 0 of the records is the plant's state all the same
-            a.xcur = observed ? xhat : h->xcur.as<double>(); a.xplant = observed ? h->xcur.as<double>() : nullptr;
-            a.xopt = h->xopt.as<double>(); a.uopt = h->uopt.as<double>();
-            a.tt = h->tt.as<double>();
-            a.tz = h->has_z ? h->tz.as<double>() : nullptr;
-            a.tu = h->has_ud ? h->tu.as<double>() : nullptr;
-            a.phase = h->has_phase ? h->phase.as<double>() : nullptr;
-            a.H = h->planner->H.as<double>();
-            a.x0 = h->x0.as<double>(); a.x_init = h->x_init.as<double>(); a.u_init = h->u_init.as<double>();
-            a.z = h->z.as<double>(); a.zf = (h->has_z && h->has_Qzf) ? h->zf.as<double>() : nullptr; a.ud = h->ud.as<double>();
-            a.Xrec = (p == 0 && X_cl) ? h->Xrec.as<double>() : nullptr;
-            a.Zrec = p == 0 ? h->Zrec.as<double>() : nullptr;
-            a.rec_rows = (int64_t)S + 1;
-            if (a.first) SRH_CHECK_HIP(hipMemsetAsync(h->u_init.p, 0, D * B * N * m, st));
-            loop_prepare_kernel<<<(unsigned)B, 256, 0, st>>>(a);
-            SRH_CHECK_HIP(hipGetLastError());
-            // scp/standalone.py:32-33: the first guess is the planner's own zero-input rollout from x0
-            if (a.first && (rc = stpwl_rollout_dev(h->planner, a.x0, a.u_init, N, (int64_t)B, a.x_init, nullptr, (void *)st))) return rc;
-            if ((rc = sgusto_plan_solve_dev(h->plan, a.x0, a.u_init, a.x_init, h->has_z ? a.z : nullptr, a.zf, h->has_ud ? a.ud : nullptr,
-                                            h->xopt.as<double>(), h->uopt.as<double>(), h->zopt.as<double>(), h->Irec.as<int32_t>() + p * B,
-                                            h->Srec.as<int32_t>() + p * B, nullptr, (void *)st)) ||
-                (rc = sgusto_plan_costs_dev(h->plan, h->Jrec.as<double>() + p * B, (void *)st)))
-                return rc;
-            AdvArgs v = h->adv_args();
-            v.xopt = a.xopt; v.uopt = a.uopt;
-            v.W = W ? h->Wd.as<double>() : nullptr; v.w_step0 = (int64_t)p * nk;
-            v.x_in = h->xcur.as<double>(); v.x_out = h->xcur.as<double>();
-            v.X = X_cl ? h->Xrec.as<double>() : nullptr; v.Z = h->Zrec.as<double>(); v.U = h->Urec.as<double>();
-            v.rows_x = (int64_t)S + 1; v.row0_x = (int64_t)p * nk + 1; v.rows_u = (int64_t)S; v.row0_u = (int64_t)p * nk;
-            if (!observed) {
-                if ((rc = h->launch_advance(v))) return rc;
-            } else {
-                v.Vn = Vn ? h->Vd.as<double>() : nullptr; v.Y = h->Yrec.as<double>();
-                if ((rc = h->launch_observed_chain(v, h->XHrec.as<double>(), (int64_t)S + 1, (int64_t)p * nk + 1, h->Erec.as<int32_t>() + p * B,
-                                                   nullptr)))
-                    return rc;
-            }
-        }
-        if (observed) {
-            SRH_CHECK_HIP(hipMemcpyAsync(h->pXH.p, h->XHrec.p, D * B * (S + 1) * n, hipMemcpyDeviceToHost, st));
-            SRH_CHECK_HIP(hipMemcpyAsync(h->pY.p, h->Yrec.p, D * B * S * ny, hipMemcpyDeviceToHost, st));
-            SRH_CHECK_HIP(hipMemcpyAsync(h->pE.p, h->Erec.p, sizeof(int32_t) * periods * B, hipMemcpyDeviceToHost, st));
-        }
-        if (X_cl) SRH_CHECK_HIP(hipMemcpyAsync(h->pX.p, h->Xrec.p, D * B * (S + 1) * n, hipMemcpyDeviceToHost, st));
-        SRH_CHECK_HIP(hipMemcpyAsync(h->pZ.p, h->Zrec.p, D * B * (S + 1) * nz, hipMemcpyDeviceToHost, st));
-        SRH_CHECK_HIP(hipMemcpyAsync(h->pU.p, h->Urec.p, D * B * S * m, hipMemcpyDeviceToHost, st));
-        SRH_CHECK_HIP(hipMemcpyAsync(h->pI.p, h->Irec.p, sizeof(int32_t) * periods * B, hipMemcpyDeviceToHost, st));
-        SRH_CHECK_HIP(hipMemcpyAsync(h->pS.p, h->Srec.p, sizeof(int32_t) * periods * B, hipMemcpyDeviceToHost, st));
-        SRH_CHECK_HIP(hipMemcpyAsync(h->pJ.p, h->Jrec.p, D * periods * B, hipMemcpyDeviceToHost, st));
-        h->waits += 1;
-        SRH_CHECK_HIP(hipStreamSynchronize(st));
-        return SRH_OK;
-    };
-    if ((rc = body())) {
-        (void)hipStreamSynchronize(st);
-        h->have_state = false;          // part of a run was enqueued: the state is not the one the caller knows
-        return rc;
-    }
-    if (X_cl) memcpy(X_cl, h->pX.p, D * B * (S + 1) * n);
-    memcpy(Z_cl, h->pZ.p, D * B * (S + 1) * nz);
-    memcpy(U_cl, h->pU.p, D * B * S * m);
-    memcpy(iters, h->pI.p, sizeof(int32_t) * periods * B);
-    memcpy(status, h->pS.p, sizeof(int32_t) * periods * B);
-    memcpy(J, h->pJ.p, D * periods * B);
-    if (observed) {
-        memcpy(Xhat, h->pXH.p, D * B * (S + 1) * n);
-        memcpy(Y_cl, h->pY.p, D * B * S * ny);
-        memcpy(ekf_status, h->pE.p, sizeof(int32_t) * periods * B);
-    }
-    h->k += periods;
-    return SRH_OK;
+    const size_t B = (size_t)h->B;
+    double *xhat = observed ? h->obs->x_dev() : nullptr, *xcur = h->xcur.as<double>();
+    h->Wd.host = (void *)W; h->Vd.host = (void *)Vn; h->Xrec.host = X_cl; h->Zrec.host = Z_cl; h->Urec.host = U_cl; h->Irec.host = iters;
+    h->Srec.host = status; h->Jrec.host = J; h->XHrec.host = Xhat; h->Yrec.host = Y_cl; h->Erec.host = ekf_status;
+    h->XHrec.row0 = xhat;               // row 0 of the estimate record: the estimates the run starts from
+    // with an observer the plan starts from the estimate; row 0 of the records (the prepare kernel's) is the plant's state all the same
+    const PrepUnit u{observed ? xhat : xcur, observed ? xcur : nullptr, h->planner->H.as<double>(),
+                     (h->has_z && h->has_Qzf) ? h->zf.as<double>() : nullptr, true};
+    return loop_run_periods(h, "sgusto_loop_run", periods, u, [&](int p, const PrepArgs &a, const LoopRows &r) -> int {
+        int rc;
+        // scp/standalone.py:32-33: the first guess is the planner's own zero-input rollout from x0
+        if (a.first && (rc = stpwl_rollout_dev(h->planner, a.x0, a.u_init, h->N, h->B, a.x_init, nullptr, (void *)h->stream))) return rc;
+        if ((rc = sgusto_plan_solve_dev(h->plan, a.x0, a.u_init, a.x_init, h->has_z ? a.z : nullptr, a.zf, h->has_ud ? a.ud : nullptr,
+                                        h->xopt.as<double>(), h->uopt.as<double>(), h->zopt.as<double>(), h->Irec.as<int32_t>() + p * B,
+                                        h->Srec.as<int32_t>() + p * B, nullptr, (void *)h->stream)) ||
+            (rc = sgusto_plan_costs_dev(h->plan, h->Jrec.as<double>() + p * B, (void *)h->stream)))
+            return rc;
+        AdvArgs v = h->adv_args();
+        v.xopt = a.xopt; v.uopt = a.uopt;
+        v.W = W ? h->Wd.as<double>() : nullptr; v.w_step0 = r.w_step0;
+        v.x_in = xcur; v.x_out = xcur;
+        v.X = X_cl ? h->Xrec.as<double>() : nullptr; v.Z = h->Zrec.as<double>(); v.U = h->Urec.as<double>();
+        v.rows_x = r.rows_x; v.row0_x = r.row0_x; v.rows_u = r.rows_u; v.row0_u = r.row0_u;
+        if (!observed) return h->launch_advance(v);
+        v.Vn = Vn ? h->Vd.as<double>() : nullptr; v.Y = h->Yrec.as<double>();
+        return h->launch_observed_chain(v, h->XHrec.as<double>(), r.rows_x, r.row0_x, h->Erec.as<int32_t>() + p * B, nullptr);
+    });
 }
 
 int sgusto_loop_run(sgusto_loop_t *h, int periods, const double *W, double *X_cl, double *Z_cl, double *U_cl, int32_t *iters,
@@ -491,15 +379,15 @@ int sgusto_loop_set_observer(sgusto_loop_t *h, sekf_batch_t *observer) {
     SRH_REQUIRE(n == h->n && m == h->m, "sgusto_loop_set_observer: the observer's model has n_x = %d, n_u = %d, the loop n_x = %d, n_u = %d", n, m,
                 h->n, h->m);
     SRH_REQUIRE(observer->model->has_discrete, "sgusto_loop_set_observer: the observer's model has not been pre-discretised (at dt_sim)");
-    const size_t D = sizeof(double), S = (size_t)h->max_steps, P = S / h->n_keep, Bz = (size_t)h->B;
     h->lds_obs = advance_lds_bytes(h->n, h->m, true);
     SRH_REQUIRE(h->lds_obs <= (size_t)160 * 1024, "sgusto_loop_set_observer: the observed advance kernel needs %zu bytes of LDS (160 KiB available)",
                 h->lds_obs);
     SRH_CHECK_HIP(hipFuncSetAttribute((const void *)loop_advance_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_obs));
+    const size_t D = sizeof(double);
+    h->XHrec.shape(D * n, 1); h->Yrec.shape(D * ny, 0); h->Erec.shape(sizeof(int32_t), 0, true); h->Vd.shape(D * ny, 0);
+    (void)h->Vd.d.alloc(0);             // (the noise block of another n_y is given back: the first run with noise allocates this one's)
     int rc;
-    if ((rc = h->XHrec.alloc(D * Bz * (S + 1) * n)) || (rc = h->Yrec.alloc(D * Bz * S * ny)) || (rc = h->Erec.alloc(sizeof(int32_t) * P * Bz)) ||
-        (rc = h->pXH.need(D * Bz * (S + 1) * n)) || (rc = h->pY.need(D * Bz * S * ny)) || (rc = h->pE.need(sizeof(int32_t) * P * Bz)))
-        return rc;
+    if ((rc = h->alloc_recs({&h->XHrec, &h->Yrec, &h->Erec}))) return rc;
     h->obs = observer; h->ny = ny;
     return SRH_OK;
 }
@@ -526,30 +414,13 @@ int sgusto_loop_run_observed(sgusto_loop_t *h, int periods, const double *W, con
 }
 
 int sgusto_loop_last_inputs(sgusto_loop_t *h, double *x0, double *u_init, double *x_init, double *z, double *zf, double *u_des) {
-    SRH_REQUIRE(h, "sgusto_loop_last_inputs: null handle");
-    SRH_REQUIRE(h->have_state && h->k > 0, "sgusto_loop_last_inputs: no period has run since the last reset");
-    const size_t D = sizeof(double), B = (size_t)h->B, N = h->N, n = h->n, m = h->m, nz = h->nz;
-    SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
-    int rc;
-    if (x0 && (rc = h->x0.download(x0, D * B * n))) return rc;
-    if (u_init && (rc = h->u_init.download(u_init, D * B * N * m))) return rc;
-    if (x_init && (rc = h->x_init.download(x_init, D * B * (N + 1) * n))) return rc;
-    if (z && h->has_z && (rc = h->z.download(z, D * B * (N + 1) * nz))) return rc;
-    if (zf && h->has_z && h->has_Qzf && (rc = h->zf.download(zf, D * B * nz))) return rc;
-    if (u_des && h->has_ud && (rc = h->ud.download(u_des, D * B * N * m))) return rc;
+    int rc = loop_last_inputs(h, "sgusto_loop_last_inputs", x0, u_init, x_init, z, u_des);
+    if (rc) return rc;
+    if (zf && h->has_z && h->has_Qzf && (rc = h->zf.download(zf, sizeof(double) * h->B * h->nz))) return rc;
     return SRH_OK;
 }
 
-int sgusto_loop_last_plan(sgusto_loop_t *h, double *xopt, double *uopt) {
-    SRH_REQUIRE(h, "sgusto_loop_last_plan: null handle");
-    SRH_REQUIRE(h->have_state && h->k > 0, "sgusto_loop_last_plan: no period has run since the last reset");
-    const size_t D = sizeof(double), B = (size_t)h->B, N = h->N;
-    SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
-    int rc;
-    if (xopt && (rc = h->xopt.download(xopt, D * B * (N + 1) * h->n))) return rc;
-    if (uopt && (rc = h->uopt.download(uopt, D * B * N * h->m))) return rc;
-    return SRH_OK;
-}
+int sgusto_loop_last_plan(sgusto_loop_t *h, double *xopt, double *uopt) { return loop_last_plan(h, "sgusto_loop_last_plan", xopt, uopt); }
 
 int sgusto_loop_advance(sgusto_loop_t *h, const double *xopt, const double *uopt, const double *x, const double *W, double *X,
                         double *Z, double *U, int32_t *idx_plant, int32_t *idx_gain) {
@@ -568,11 +439,7 @@ int sgusto_loop_advance(sgusto_loop_t *h, const double *xopt, const double *uopt
     v.X = dX.as<double>(); v.Z = dZ.as<double>(); v.U = dU.as<double>();
     v.ip = dp.as<int32_t>(); v.ig = dg.as<int32_t>();
     v.rows_x = (int64_t)nk; v.row0_x = 0; v.rows_u = (int64_t)nk; v.row0_u = 0;
-    rc = h->launch_advance(v);
-    // (the temporaries go back to the allocation cache when this returns: wait for the kernel whatever it answered)
-    const hipError_t e = hipStreamSynchronize(h->stream);
-    if (rc) return rc;
-    SRH_CHECK_HIP(e);
+    if ((rc = loop_wait(h->launch_advance(v), h->stream))) return rc;
     if ((rc = dX.download(X, D * B * nk * n)) || (rc = dZ.download(Z, D * B * nk * nz)) || (rc = dU.download(U, D * B * nk * m))) return rc;
     if (idx_plant && (rc = dp.download(idx_plant, sizeof(int32_t) * B * nk))) return rc;
     if (idx_gain && (rc = dg.download(idx_gain, sizeof(int32_t) * B * nk))) return rc;
@@ -604,11 +471,7 @@ int sgusto_loop_advance_observed(sgusto_loop_t *h, const double *xopt, const dou
     v.X = dX.as<double>(); v.Z = dZ.as<double>(); v.U = dU.as<double>(); v.Y = dY.as<double>();
     v.ip = dp.as<int32_t>(); v.ig = dg.as<int32_t>();
     v.rows_x = (int64_t)nk; v.row0_x = 0; v.rows_u = (int64_t)nk; v.row0_u = 0;
-    rc = h->launch_observed_chain(v, dXH.as<double>(), (int64_t)nk, 0, dE.as<int32_t>(), df.as<int32_t>());
-    // (the temporaries go back to the allocation cache when this returns: wait for the kernels whatever they answered)
-    const hipError_t e = hipStreamSynchronize(h->stream);
-    if (rc) return rc;
-    SRH_CHECK_HIP(e);
+    if ((rc = loop_wait(h->launch_observed_chain(v, dXH.as<double>(), (int64_t)nk, 0, dE.as<int32_t>(), df.as<int32_t>()), h->stream))) return rc;
     if ((rc = dX.download(X, D * B * nk * n)) || (rc = dZ.download(Z, D * B * nk * nz)) || (rc = dU.download(U, D * B * nk * m)) ||
         (rc = dXH.download(Xhat, D * B * nk * n)) || (rc = dY.download(Y, D * B * nk * ny)))
         return rc;
@@ -619,11 +482,6 @@ int sgusto_loop_advance_observed(sgusto_loop_t *h, const double *xopt, const dou
     return SRH_OK;
 }
 
-int sgusto_loop_stats(sgusto_loop_t *h, int64_t *steps, int64_t *waits_last_run) {
-    SRH_REQUIRE(h, "sgusto_loop_stats: null handle");
-    if (steps) *steps = h->k;
-    if (waits_last_run) *waits_last_run = h->waits;
-    return SRH_OK;
-}
+int sgusto_loop_stats(sgusto_loop_t *h, int64_t *steps, int64_t *waits_last_run) { return loop_stats(h, "sgusto_loop_stats", steps, waits_last_run); }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
-// What the two closed-loop units (gusto_loop.hip: TPWL plans, gusto_ssm_loop.hip: SSM plans) share, stated once: the target table's
-// interpolation, the query times, and loop_prepare_kernel -- the kernel that turns the previous period's output into the next solve's
-// input (x0, the shifted guess, the target window) -- with the pinned block their copies back go through.  Each unit gets its own
-// instance of the kernel (anonymous namespace); an SSM loop passes no H (it has no linear output map) and no zf (no terminal cost).
+// The device side of what the two closed-loop units (gusto_loop.hip: TPWL plans, gusto_ssm_loop.hip: SSM plans) share, stated once: the
+// target table's interpolation, the query times, and loop_prepare_kernel -- the kernel that turns the previous period's output into the
+// next solve's input (x0, the shifted guess, the target window).  Its one launch, and the host shell around it, is gusto_loop_host.h.
+// Each unit gets its own instance of the kernel (anonymous namespace); an SSM loop passes no H (it has no linear output map) and no zf
+// (no terminal cost).
 #pragma once
 #include "common.h"
 #include "dev_la.h"
@@ -98,18 +99,5 @@ __global__ __launch_bounds__(256) void loop_prepare_kernel(PrepArgs a) {
         }
     }
 }
-
-struct PinBuf {
-    char *p = nullptr;
-    size_t cap = 0;
-    ~PinBuf() { if (p) (void)hipHostFree(p); }
-    int need(size_t bytes) {
-        if (bytes <= cap) return SRH_OK;
-        if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
-        SRH_CHECK_HIP(hipHostMalloc((void **)&p, bytes, hipHostMallocDefault));
-        cap = bytes;
-        return SRH_OK;
-    }
-};
 
 }  // namespace

@@ -4,10 +4,11 @@
 // 353-361 (the loop), scp/ros.py:78-79, 109-114 (first guess, shift), SSM/controllers.py:204, 237 (u = u_bar(t), no gain) and its
 // SSMObserver (x_hat = W_map(y - z_ref)), SSM/ssm.py:198-218, 279-301 (plant step).
 // The solve is sgusto_ssm_plan_solve_dev (gusto_ssm.hip), the first guess sssm_rollout_dev (ssm.hip), shift and target window the
-// prepare kernel shared with gusto_loop.hip (gusto_loop_prep.h).  New here: ssm_loop_advance_kernel.  Because the observer is a map and
-// not a filter, the whole sub-step -- input from the plan, plant step, measurement, estimate -- is one kernel for all n_keep sub-steps.
+// prepare kernel shared with gusto_loop.hip (gusto_loop_prep.h), the host shell of a handle and of a run the one shared with it too
+// (gusto_loop_host.h).  New here: ssm_loop_advance_kernel.  Because the observer is a map and not a filter, the whole sub-step -- input
+// from the plan, plant step, measurement, estimate -- is one kernel for all n_keep sub-steps.
 #include "ssm_host.h"
-#include "gusto_loop_prep.h"
+#include "gusto_loop_host.h"
 
 #include <algorithm>
 
@@ -189,24 +190,14 @@ int ssm_loop_launch(const sssm *plant, const sssm *obs, size_t lds, const SsmAdv
 
 }  // namespace
 
-struct sgusto_ssm_loop {
+struct sgusto_ssm_loop : LoopCore {
     sgusto_ssm_plan_t *plan = nullptr;
     sssm *planner = nullptr, *plant = nullptr;
-    int N = 0, n = 0, m = 0, nz = 0, no = 0, n_keep = 0, T = 0, plan_mode = 0, plant_mode = 0;
-    int64_t B = 0, max_steps = 0;
-    double dt = 0.0, dt_sim = 0.0, t_start = 0.0;
-    bool observe = true, has_z = false, has_ud = false, has_phase = false, have_state = false;
-    int64_t k = 0;                      // periods since the last reset
-    int64_t waits = 0;                  // blocking host waits of the last run
-    size_t lds = 0;
-    hipStream_t stream = nullptr;
-    srh::DevBuf x0, u_init, x_init, z, ud, xopt, uopt, zopt, tt, tz, tu, phase, js, theta;
-    srh::DevBuf xcur, zcur, ycur, xhcur, v0;        // where the loops stand: plant state, its output, the last measurement, the estimate
-    srh::DevBuf Xrec, Zrec, Urec, Yrec, XHrec, Irec, Srec, Jrec, Wd, Vd;
-    PinBuf pX, pZ, pU, pY, pXH, pI, pS, pJ, pW, pV;
-    ~sgusto_ssm_loop() {
-        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
-    }
+    int no = 0, plan_mode = 0, plant_mode = 0;
+    bool observe = true;
+    srh::DevBuf zcur, ycur, xhcur, v0;  // where the loops stand beside the plant state xcur: its output, the last measurement, the estimate
+    __attribute__((always_inline)) sgusto_ssm_loop() {}        // (inlined: no constructor among the library's dynamic symbols)
+    ~sgusto_ssm_loop() { drain(); }
     SsmAdvArgs adv_args() const {
         SsmAdvArgs a{};
         a.N = N; a.n_keep = n_keep; a.mode = plant_mode; a.same = planner == plant ? 1 : 0;
@@ -232,37 +223,22 @@ int sgusto_ssm_loop_create(sgusto_ssm_loop_t **out, sgusto_ssm_plan_t *plan, sss
     SRH_REQUIRE(planner_model->n == n && planner_model->m == m, "sgusto_ssm_loop_create: the planner's model (n_x = %d, n_u = %d) is not the model of the "
                 "plan (n_x = %d, n_u = %d)", planner_model->n, planner_model->m, n, m);
     size_t lds = 0;
-    if ((rc = ssm_loop_check_models("sgusto_ssm_loop_create", plant, plant_mode, planner_model, &lds))) return rc;
-    SRH_REQUIRE(dt_sim > 0.0 && n_keep >= 1, "sgusto_ssm_loop_create: need dt_sim > 0 and n_keep >= 1");
-    SRH_REQUIRE(!((double)n_keep * dt_sim > (double)N * dt),
-                "sgusto_ssm_loop_create: n_keep * dt_sim = %g exceeds the horizon N * dt = %g (the shift of the previous plan would find no row)",
-                (double)n_keep * dt_sim, (double)N * dt);
-    SRH_REQUIRE(max_steps_per_run >= n_keep, "sgusto_ssm_loop_create: max_steps_per_run = %lld is below n_keep = %d", (long long)max_steps_per_run, n_keep);
+    if ((rc = ssm_loop_check_models("sgusto_ssm_loop_create", plant, plant_mode, planner_model, &lds)) ||
+        (rc = loop_check_periods("sgusto_ssm_loop_create", N, dt, dt_sim, n_keep, max_steps_per_run)))
+        return rc;
     sgusto_ssm_loop *h = new sgusto_ssm_loop();
     h->plan = plan; h->planner = planner_model; h->plant = plant;
-    h->N = N; h->n = n; h->m = m; h->nz = nz; h->no = plant->no; h->n_keep = n_keep; h->B = B; h->max_steps = max_steps_per_run;
-    h->plan_mode = mode; h->plant_mode = plant_mode; h->observe = observe != 0;
-    h->dt = dt; h->dt_sim = dt_sim; h->lds = lds;
-    std::vector<int32_t> js(n_keep);
-    std::vector<double> th(n_keep);
-    (void)sgusto_loop_schedule(N, dt, dt_sim, n_keep, 0.0, 0, nullptr, nullptr, js.data(), th.data());
-    const size_t D = sizeof(double), S = (size_t)max_steps_per_run, P = S / n_keep, Bz = (size_t)B, no = (size_t)plant->no;
-    auto fail = [&](int code) { delete h; return code; };
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        srh::set_error("sgusto_ssm_loop_create: could not create the stream: %s", hipGetErrorString(hipGetLastError()));
-        return fail(SRH_EHIP);
+    h->no = plant->no; h->plan_mode = mode; h->plant_mode = plant_mode; h->observe = observe != 0; h->lds = lds;
+    const size_t D = sizeof(double), Bz = (size_t)B, no = (size_t)plant->no;
+    // the output, the measurement and the estimate are recorded in every run, row 0 included: S + 1 rows, row 0 where the loops stand
+    h->XHrec.shape(D * n, 1); h->Yrec.shape(D * no, 1); h->Vd.shape(D * no, 0);
+    if ((rc = h->setup("sgusto_ssm_loop_create", "create the stream", N, n, m, nz, B, dt, dt_sim, n_keep, max_steps_per_run, no)) ||
+        (rc = h->alloc_recs({&h->Yrec, &h->XHrec})) || (rc = h->zcur.alloc(D * Bz * no)) || (rc = h->ycur.alloc(D * Bz * no)) ||
+        (rc = h->xhcur.alloc(D * Bz * n)) || (rc = h->v0.alloc(D * Bz * no))) {
+        delete h;
+        return rc;
     }
-    if ((rc = h->x0.alloc(D * Bz * n)) || (rc = h->u_init.alloc(D * Bz * N * m)) || (rc = h->x_init.alloc(D * Bz * (N + 1) * n)) ||
-        (rc = h->z.alloc(D * Bz * (N + 1) * nz)) || (rc = h->ud.alloc(D * Bz * N * m)) || (rc = h->xopt.alloc(D * Bz * (N + 1) * n)) ||
-        (rc = h->uopt.alloc(D * Bz * N * m)) || (rc = h->zopt.alloc(D * Bz * (N + 1) * nz)) || (rc = h->xcur.alloc(D * Bz * n)) ||
-        (rc = h->zcur.alloc(D * Bz * no)) || (rc = h->ycur.alloc(D * Bz * no)) || (rc = h->xhcur.alloc(D * Bz * n)) || (rc = h->v0.alloc(D * Bz * no)) ||
-        (rc = h->js.upload(js.data(), sizeof(int32_t) * n_keep)) || (rc = h->theta.upload(th.data(), D * n_keep)) ||
-        (rc = h->Zrec.alloc(D * Bz * (S + 1) * no)) || (rc = h->Yrec.alloc(D * Bz * (S + 1) * no)) || (rc = h->XHrec.alloc(D * Bz * (S + 1) * n)) ||
-        (rc = h->Urec.alloc(D * Bz * S * m)) || (rc = h->Irec.alloc(sizeof(int32_t) * P * Bz)) || (rc = h->Srec.alloc(sizeof(int32_t) * P * Bz)) ||
-        (rc = h->Jrec.alloc(D * P * Bz)) || (rc = h->pZ.need(D * Bz * (S + 1) * no)) || (rc = h->pY.need(D * Bz * (S + 1) * no)) ||
-        (rc = h->pXH.need(D * Bz * (S + 1) * n)) || (rc = h->pU.need(D * Bz * S * m)) || (rc = h->pI.need(sizeof(int32_t) * P * Bz)) ||
-        (rc = h->pS.need(sizeof(int32_t) * P * Bz)) || (rc = h->pJ.need(D * P * Bz)))
-        return fail(rc);
+    h->Xrec.row0 = h->xcur.p; h->Zrec.row0 = h->zcur.p; h->Yrec.row0 = h->ycur.p; h->XHrec.row0 = h->xhcur.p;
     *out = h;
     return SRH_OK;
 }
@@ -273,17 +249,7 @@ int sgusto_ssm_loop_destroy(sgusto_ssm_loop_t *h) {
 }
 
 int sgusto_ssm_loop_set_target(sgusto_ssm_loop_t *h, int T, const double *t, const double *z, const double *u_des, const double *phase) {
-    SRH_REQUIRE(h && t && (z || u_des), "sgusto_ssm_loop_set_target: null argument");
-    SRH_REQUIRE(T >= 2, "sgusto_ssm_loop_set_target: the table needs at least two rows");
-    for (int i = 1; i < T; ++i) SRH_REQUIRE(t[i] > t[i - 1], "sgusto_ssm_loop_set_target: t must increase (row %d)", i);
-    SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
-    int rc;
-    if ((rc = h->tt.upload(t, sizeof(double) * T))) return rc;
-    if (z && (rc = h->tz.upload(z, sizeof(double) * T * h->nz))) return rc;
-    if (u_des && (rc = h->tu.upload(u_des, sizeof(double) * T * h->m))) return rc;
-    if (phase && (rc = h->phase.upload(phase, sizeof(double) * h->B))) return rc;
-    h->T = T; h->has_z = z != nullptr; h->has_ud = u_des != nullptr; h->has_phase = phase != nullptr;
-    return SRH_OK;
+    return loop_set_target(h, "sgusto_ssm_loop_set_target", T, t, z, u_des, phase);
 }
 
 int sgusto_ssm_loop_reset(sgusto_ssm_loop_t *h, const double *x0, const double *v0, double t_start) {
@@ -299,10 +265,8 @@ int sgusto_ssm_loop_reset(sgusto_ssm_loop_t *h, const double *x0, const double *
     a.v0 = v0 ? h->v0.as<double>() : nullptr;
     a.x_in = h->xcur.as<double>();
     a.z_out = h->zcur.as<double>(); a.y_out = h->ycur.as<double>(); a.xh_out = h->xhcur.as<double>();
-    const int rc = ssm_loop_launch(h->plant, h->planner, h->lds, a, h->stream);
-    const hipError_t e = hipStreamSynchronize(h->stream);
+    const int rc = loop_wait(ssm_loop_launch(h->plant, h->planner, h->lds, a, h->stream), h->stream);
     if (rc) return rc;
-    SRH_CHECK_HIP(e);
     h->t_start = t_start; h->k = 0; h->have_state = true;
     return SRH_OK;
 }
@@ -312,126 +276,42 @@ int sgusto_ssm_loop_run(sgusto_ssm_loop_t *h, int periods, const double *W, cons
     SRH_REQUIRE(h && Z_cl && U_cl && Y_cl && Xhat && iters && status && J, "sgusto_ssm_loop_run: null argument");
     SRH_REQUIRE(periods >= 1, "sgusto_ssm_loop_run: periods must be positive");
     SRH_REQUIRE(h->have_state, "sgusto_ssm_loop_run: no plant state yet (call sgusto_ssm_loop_reset first)");
-    const int N = h->N, n = h->n, m = h->m, nz = h->nz, nk = h->n_keep;
-    const size_t D = sizeof(double), B = (size_t)h->B, S = (size_t)periods * nk, no = (size_t)h->no;
-    SRH_REQUIRE((int64_t)S <= h->max_steps, "sgusto_ssm_loop_run: periods * n_keep = %lld exceeds max_steps_per_run = %lld", (long long)S,
-                (long long)h->max_steps);
-    int rc;
-    if (X_cl && ((rc = h->pX.need(D * B * (h->max_steps + 1) * n)) || (!h->Xrec.p && (rc = h->Xrec.alloc(D * B * (h->max_steps + 1) * n))))) return rc;
-    if (W && ((rc = h->pW.need(D * h->max_steps * B * n)) || (!h->Wd.p && (rc = h->Wd.alloc(D * h->max_steps * B * n))))) return rc;
-    if (V && ((rc = h->pV.need(D * h->max_steps * B * no)) || (!h->Vd.p && (rc = h->Vd.alloc(D * h->max_steps * B * no))))) return rc;
-    h->waits = 0;
-    hipStream_t st = h->stream;
-    // from here on work is enqueued on the handle's stream: on any error it is drained before returning
-    auto body = [&]() -> int {
-        if (W) {
-            memcpy(h->pW.p, W, D * S * B * n);
-            SRH_CHECK_HIP(hipMemcpyAsync(h->Wd.p, h->pW.p, D * S * B * n, hipMemcpyHostToDevice, st));
-        }
-        if (V) {
-            memcpy(h->pV.p, V, D * S * B * no);
-            SRH_CHECK_HIP(hipMemcpyAsync(h->Vd.p, h->pV.p, D * S * B * no, hipMemcpyHostToDevice, st));
-        }
-        // row 0 of the records: where the loops stand
-        if (X_cl) SRH_CHECK_HIP(hipMemcpy2DAsync(h->Xrec.p, D * (S + 1) * n, h->xcur.p, D * n, D * n, B, hipMemcpyDeviceToDevice, st));
-        SRH_CHECK_HIP(hipMemcpy2DAsync(h->Zrec.p, D * (S + 1) * no, h->zcur.p, D * no, D * no, B, hipMemcpyDeviceToDevice, st));
-        SRH_CHECK_HIP(hipMemcpy2DAsync(h->Yrec.p, D * (S + 1) * no, h->ycur.p, D * no, D * no, B, hipMemcpyDeviceToDevice, st));
-        SRH_CHECK_HIP(hipMemcpy2DAsync(h->XHrec.p, D * (S + 1) * n, h->xhcur.p, D * n, D * n, B, hipMemcpyDeviceToDevice, st));
-        for (int p = 0; p < periods; ++p) {
-            const int64_t k = h->k + p;
-            PrepArgs a{};
-            a.N = N; a.n = n; a.m = m; a.nz = nz; a.T = h->T;
-            a.first = k == 0 ? 1 : 0;
-            a.dt = h->dt;
-            (void)sgusto_loop_schedule(N, h->dt, h->dt_sim, nk, h->t_start, k, &a.tk, &a.idx0, nullptr, nullptr);
-            // the plan starts from the estimate (the reference's loop) or from the plant state (perfect state feedback)
-            a.xcur = h->observe ? h->xhcur.as<double>() : h->xcur.as<double>();
-            a.xopt = h->xopt.as<double>(); a.uopt = h->uopt.as<double>();
-            a.tt = h->tt.as<double>();
-            a.tz = h->has_z ? h->tz.as<double>() : nullptr;
-            a.tu = h->has_ud ? h->tu.as<double>() : nullptr;
-            a.phase = h->has_phase ? h->phase.as<double>() : nullptr;
-            a.x0 = h->x0.as<double>(); a.x_init = h->x_init.as<double>(); a.u_init = h->u_init.as<double>();
-            a.z = h->z.as<double>(); a.ud = h->ud.as<double>();      // (no H, no zf, no record rows: the advance kernel writes the records)
-            if (a.first) SRH_CHECK_HIP(hipMemsetAsync(h->u_init.p, 0, D * B * N * m, st));
-            loop_prepare_kernel<<<(unsigned)B, 256, 0, st>>>(a);
-            SRH_CHECK_HIP(hipGetLastError());
-            // scp/ros.py:78-79: the first guess is the planner's own zero-input rollout from x0
-            if (a.first && (rc = sssm_rollout_dev(h->planner, a.x0, a.u_init, N, (int64_t)B, h->plan_mode, h->dt, a.x_init, nullptr, (void *)st))) return rc;
-            if ((rc = sgusto_ssm_plan_solve_dev(h->plan, a.x0, a.u_init, a.x_init, h->has_z ? a.z : nullptr, h->has_ud ? a.ud : nullptr,
-                                                h->xopt.as<double>(), h->uopt.as<double>(), h->zopt.as<double>(), h->Irec.as<int32_t>() + p * B,
-                                                h->Srec.as<int32_t>() + p * B, nullptr, (void *)st)) ||
-                (rc = sgusto_ssm_plan_costs_dev(h->plan, h->Jrec.as<double>() + p * B, (void *)st)))
-                return rc;
-            SsmAdvArgs v = h->adv_args();
-            v.uopt = a.uopt;
-            v.W = W ? h->Wd.as<double>() : nullptr; v.Vn = V ? h->Vd.as<double>() : nullptr; v.w_step0 = (int64_t)p * nk;
-            v.x_in = h->xcur.as<double>();
-            v.x_out = h->xcur.as<double>(); v.z_out = h->zcur.as<double>(); v.y_out = h->ycur.as<double>(); v.xh_out = h->xhcur.as<double>();
-            v.X = X_cl ? h->Xrec.as<double>() : nullptr; v.Z = h->Zrec.as<double>(); v.U = h->Urec.as<double>();
-            v.Y = h->Yrec.as<double>(); v.Xhat = h->XHrec.as<double>();
-            v.rows_x = (int64_t)S + 1; v.row0_x = (int64_t)p * nk + 1; v.rows_u = (int64_t)S; v.row0_u = (int64_t)p * nk;
-            if ((rc = ssm_loop_launch(h->plant, h->planner, h->lds, v, st))) return rc;
-        }
-        if (X_cl) SRH_CHECK_HIP(hipMemcpyAsync(h->pX.p, h->Xrec.p, D * B * (S + 1) * n, hipMemcpyDeviceToHost, st));
-        SRH_CHECK_HIP(hipMemcpyAsync(h->pZ.p, h->Zrec.p, D * B * (S + 1) * no, hipMemcpyDeviceToHost, st));
-        SRH_CHECK_HIP(hipMemcpyAsync(h->pY.p, h->Yrec.p, D * B * (S + 1) * no, hipMemcpyDeviceToHost, st));
-        SRH_CHECK_HIP(hipMemcpyAsync(h->pXH.p, h->XHrec.p, D * B * (S + 1) * n, hipMemcpyDeviceToHost, st));
-        SRH_CHECK_HIP(hipMemcpyAsync(h->pU.p, h->Urec.p, D * B * S * m, hipMemcpyDeviceToHost, st));
-        SRH_CHECK_HIP(hipMemcpyAsync(h->pI.p, h->Irec.p, sizeof(int32_t) * periods * B, hipMemcpyDeviceToHost, st));
-        SRH_CHECK_HIP(hipMemcpyAsync(h->pS.p, h->Srec.p, sizeof(int32_t) * periods * B, hipMemcpyDeviceToHost, st));
-        SRH_CHECK_HIP(hipMemcpyAsync(h->pJ.p, h->Jrec.p, D * periods * B, hipMemcpyDeviceToHost, st));
-        h->waits += 1;
-        SRH_CHECK_HIP(hipStreamSynchronize(st));
-        return SRH_OK;
-    };
-    if ((rc = body())) {
-        (void)hipStreamSynchronize(st);
-        h->have_state = false;          // part of a run was enqueued: the state is not the one the caller knows
-        return rc;
-    }
-    if (X_cl) memcpy(X_cl, h->pX.p, D * B * (S + 1) * n);
-    memcpy(Z_cl, h->pZ.p, D * B * (S + 1) * no);
-    memcpy(Y_cl, h->pY.p, D * B * (S + 1) * no);
-    memcpy(Xhat, h->pXH.p, D * B * (S + 1) * n);
-    memcpy(U_cl, h->pU.p, D * B * S * m);
-    memcpy(iters, h->pI.p, sizeof(int32_t) * periods * B);
-    memcpy(status, h->pS.p, sizeof(int32_t) * periods * B);
-    memcpy(J, h->pJ.p, D * periods * B);
-    h->k += periods;
-    return SRH_OK;
+    const size_t B = (size_t)h->B;
+    h->Wd.host = (void *)W; h->Vd.host = (void *)V; h->Xrec.host = X_cl; h->Zrec.host = Z_cl; h->Urec.host = U_cl; h->Yrec.host = Y_cl;
+    h->XHrec.host = Xhat; h->Irec.host = iters; h->Srec.host = status; h->Jrec.host = J;
+    // the plan starts from the estimate (the reference's loop) or from the plant state (perfect state feedback); no H, no zf, and row 0 of
+    // the records is where the loops stand (LoopRec::row0, set at create): the advance kernel writes the records
+    const PrepUnit u{h->observe ? h->xhcur.as<double>() : h->xcur.as<double>(), nullptr, nullptr, nullptr, false};
+    return loop_run_periods(h, "sgusto_ssm_loop_run", periods, u, [&](int p, const PrepArgs &a, const LoopRows &r) -> int {
+        int rc;
+        // scp/ros.py:78-79: the first guess is the planner's own zero-input rollout from x0
+        if (a.first && (rc = sssm_rollout_dev(h->planner, a.x0, a.u_init, h->N, h->B, h->plan_mode, h->dt, a.x_init, nullptr, (void *)h->stream)))
+            return rc;
+        if ((rc = sgusto_ssm_plan_solve_dev(h->plan, a.x0, a.u_init, a.x_init, h->has_z ? a.z : nullptr, h->has_ud ? a.ud : nullptr,
+                                            h->xopt.as<double>(), h->uopt.as<double>(), h->zopt.as<double>(), h->Irec.as<int32_t>() + p * B,
+                                            h->Srec.as<int32_t>() + p * B, nullptr, (void *)h->stream)) ||
+            (rc = sgusto_ssm_plan_costs_dev(h->plan, h->Jrec.as<double>() + p * B, (void *)h->stream)))
+            return rc;
+        SsmAdvArgs v = h->adv_args();
+        v.uopt = a.uopt;
+        v.W = W ? h->Wd.as<double>() : nullptr; v.Vn = V ? h->Vd.as<double>() : nullptr; v.w_step0 = r.w_step0;
+        v.x_in = h->xcur.as<double>();
+        v.x_out = h->xcur.as<double>(); v.z_out = h->zcur.as<double>(); v.y_out = h->ycur.as<double>(); v.xh_out = h->xhcur.as<double>();
+        v.X = X_cl ? h->Xrec.as<double>() : nullptr; v.Z = h->Zrec.as<double>(); v.U = h->Urec.as<double>();
+        v.Y = h->Yrec.as<double>(); v.Xhat = h->XHrec.as<double>();
+        v.rows_x = r.rows_x; v.row0_x = r.row0_x; v.rows_u = r.rows_u; v.row0_u = r.row0_u;
+        return ssm_loop_launch(h->plant, h->planner, h->lds, v, h->stream);
+    });
 }
 
 int sgusto_ssm_loop_last_inputs(sgusto_ssm_loop_t *h, double *x0, double *u_init, double *x_init, double *z, double *u_des) {
-    SRH_REQUIRE(h, "sgusto_ssm_loop_last_inputs: null handle");
-    SRH_REQUIRE(h->have_state && h->k > 0, "sgusto_ssm_loop_last_inputs: no period has run since the last reset");
-    const size_t D = sizeof(double), B = (size_t)h->B, N = h->N, n = h->n, m = h->m, nz = h->nz;
-    SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
-    int rc;
-    if (x0 && (rc = h->x0.download(x0, D * B * n))) return rc;
-    if (u_init && (rc = h->u_init.download(u_init, D * B * N * m))) return rc;
-    if (x_init && (rc = h->x_init.download(x_init, D * B * (N + 1) * n))) return rc;
-    if (z && h->has_z && (rc = h->z.download(z, D * B * (N + 1) * nz))) return rc;
-    if (u_des && h->has_ud && (rc = h->ud.download(u_des, D * B * N * m))) return rc;
-    return SRH_OK;
+    return loop_last_inputs(h, "sgusto_ssm_loop_last_inputs", x0, u_init, x_init, z, u_des);
 }
 
-int sgusto_ssm_loop_last_plan(sgusto_ssm_loop_t *h, double *xopt, double *uopt) {
-    SRH_REQUIRE(h, "sgusto_ssm_loop_last_plan: null handle");
-    SRH_REQUIRE(h->have_state && h->k > 0, "sgusto_ssm_loop_last_plan: no period has run since the last reset");
-    const size_t D = sizeof(double), B = (size_t)h->B, N = h->N;
-    SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
-    int rc;
-    if (xopt && (rc = h->xopt.download(xopt, D * B * (N + 1) * h->n))) return rc;
-    if (uopt && (rc = h->uopt.download(uopt, D * B * N * h->m))) return rc;
-    return SRH_OK;
-}
+int sgusto_ssm_loop_last_plan(sgusto_ssm_loop_t *h, double *xopt, double *uopt) { return loop_last_plan(h, "sgusto_ssm_loop_last_plan", xopt, uopt); }
 
 int sgusto_ssm_loop_stats(sgusto_ssm_loop_t *h, int64_t *steps, int64_t *waits_last_run) {
-    SRH_REQUIRE(h, "sgusto_ssm_loop_stats: null handle");
-    if (steps) *steps = h->k;
-    if (waits_last_run) *waits_last_run = h->waits;
-    return SRH_OK;
+    return loop_stats(h, "sgusto_ssm_loop_stats", steps, waits_last_run);
 }
 
 int sgusto_ssm_loop_advance(sssm_t *plant, int plant_mode, sssm_t *observer_model, double dt_sim, int N, int n_keep, int64_t batch, const int32_t *j,
@@ -461,11 +341,7 @@ int sgusto_ssm_loop_advance(sssm_t *plant, int plant_mode, sssm_t *observer_mode
     a.x_in = dx.as<double>();
     a.X = dX.as<double>(); a.Z = dZ.as<double>(); a.U = dU.as<double>(); a.Y = dY.as<double>(); a.Xhat = dXH.as<double>();
     a.rows_x = (int64_t)nk; a.rows_u = (int64_t)nk; a.B = batch;
-    rc = ssm_loop_launch(plant, observer_model, lds, a, nullptr);
-    // (the temporaries go back to the allocation cache when this returns: wait for the kernel whatever it answered)
-    const hipError_t e = hipStreamSynchronize(nullptr);
-    if (rc) return rc;
-    SRH_CHECK_HIP(e);
+    if ((rc = loop_wait(ssm_loop_launch(plant, observer_model, lds, a, nullptr), nullptr))) return rc;
     if ((rc = dX.download(X, D * B * nk * n)) || (rc = dZ.download(Z, D * B * nk * no)) || (rc = dU.download(U, D * B * nk * m)) ||
         (rc = dY.download(Y, D * B * nk * no)) || (rc = dXH.download(Xhat, D * B * nk * n)))
         return rc;

@@ -51,7 +51,107 @@ class ClosedLoopResult:
         self.x_hat, self.y, self.ekf_status = x_hat, y, ekf_status
 
 
-class ClosedLoopBatch:
+def _ptr(a):
+    return _lib.iptr(a) if a is not None and a.dtype == np.int32 else _lib.dptr(a)
+
+
+class _LoopBatch:
+    """What ClosedLoopBatch and SSMClosedLoopBatch share: the refusals that need no device, the target table, the arrays of a run, the
+    times of its rows and the period count, and the accessors of the last period.  `_sym`: the prefix of the class's entry points in the
+    library, `_max_iters`: the entry point that caps the plan's GuSTO iterations; has_zf stays None where a loop has no terminal target."""
+    _sym = _max_iters = has_zf = None
+
+    @classmethod
+    def _check_periods(cls, gusto, dt_sim, n_keep):
+        n_keep = int(n_keep)
+        if n_keep < 1 or not dt_sim > 0:
+            raise RuntimeError('%s: need n_keep >= 1 and dt_sim > 0' % cls.__name__)
+        if n_keep * float(dt_sim) > gusto.N * float(gusto.dt):
+            raise RuntimeError('%s: n_keep * dt_sim = %g exceeds the horizon N * dt = %g (the shift of the previous plan '
+                               'would find no row)' % (cls.__name__, n_keep * float(dt_sim), gusto.N * float(gusto.dt)))
+        return n_keep
+
+    def _shape(self, gusto, dt_sim, n_keep, max_steps_per_run, z, u):
+        self.B, self.N, self.dt = gusto.batch, gusto.N, float(gusto.dt)
+        self.n_x, self.n_u, self.n_z = gusto.n_x, gusto.n_u, gusto.n_z
+        self.dt_sim, self.n_keep = float(dt_sim), n_keep
+        self.max_steps_per_run = int(max_steps_per_run) if max_steps_per_run is not None else 16 * n_keep
+        self.has_z, self.has_u = z is not None, u is not None
+        self.t_start, self._k = 0.0, None
+        self._h = C.c_void_p()
+
+    def _call(self, entry, *args):
+        _lib.check(getattr(_lib.lib(), self._sym + entry)(self._h, *args), self._sym + entry)
+
+    def _set_target(self, t, z, u, phase):
+        if z is None and u is None:
+            return
+        if t is None:
+            raise RuntimeError('%s: a target table needs its times t' % type(self).__name__)
+        t = _lib.f64(np.asarray(t).reshape(-1))
+        T = t.shape[0]
+        z = None if z is None else _lib.f64(np.asarray(z).reshape(T, self.n_z))
+        u = None if u is None else _lib.f64(np.asarray(u).reshape(T, self.n_u))
+        phase = None if phase is None else _lib.f64(np.asarray(phase).reshape(self.B))
+        self._call('_set_target', C.c_int(T), _lib.dptr(t), _lib.dptr(z), _lib.dptr(u), _lib.dptr(phase))
+
+    def __del__(self):
+        try:
+            if self._h:
+                getattr(_lib.lib(), self._sym + '_destroy')(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass
+
+    def _records(self, periods, record_x, z_width, **more):
+        """(fits, the arrays a run of `periods` fills): x (or None), z (B, S + 1, z_width), u, iters, status, J and of `more` name -> (rows
+        beyond S, width), or None for an int32 (periods, B) record.  What does not fit is refused by the library, with its message: it is
+        handed dummies."""
+        B, S = self.B, periods * self.n_keep
+        fits = periods >= 1 and S <= self.max_steps_per_run
+        f64 = lambda *shape: np.empty(shape if fits else 1)
+        i32 = lambda: np.empty((periods, B) if fits else 1, dtype=np.int32)
+        r = dict(x=f64(B, S + 1, self.n_x) if fits and record_x else None, z=f64(B, S + 1, z_width), u=f64(B, S, self.n_u), iters=i32(), status=i32(),
+                 J=f64(periods, B))
+        r.update((k, i32() if v is None else f64(B, S + v[0], v[1])) for k, v in more.items())
+        return fits, r
+
+    def _run(self, entry, periods, arrays, r):
+        """The library's run on `arrays` (noise, then the records r in the entry point's order) -> ClosedLoopResult of r with its times."""
+        _lib.check(getattr(_lib.lib(), self._max_iters)(self.gusto.plan, C.c_int(int(self.gusto.max_gusto_iters))), 'set_max_iters')
+        self._call(entry, C.c_int(periods), *[_ptr(a) for a in arrays])
+        t = schedule(self.N, self.dt, self.dt_sim, self.n_keep, self.t_start, self._k).t_k + self.dt_sim * np.arange(periods * self.n_keep + 1)
+        self._k += periods
+        return ClosedLoopResult(r['x'], r['z'], r['u'], r['iters'], r['status'], r['J'], t, x_hat=r.get('x_hat'), y=r.get('y'), ekf_status=r.get('ekf_status'))
+
+    def step(self):
+        return self.run(1)
+
+    def last_inputs(self):
+        """The solver inputs of the last period: dict x0, u_init, x_init, z, zf (TPWL loops), u (None where the loop has none)."""
+        B, N = self.B, self.N
+        r = dict(x0=np.empty((B, self.n_x)), u_init=np.empty((B, N, self.n_u)), x_init=np.empty((B, N + 1, self.n_x)),
+                 z=np.empty((B, N + 1, self.n_z)) if self.has_z else None)
+        if self.has_zf is not None:
+            r['zf'] = np.empty((B, self.n_z)) if self.has_zf else None
+        r['u'] = np.empty((B, N, self.n_u)) if self.has_u else None
+        self._call('_last_inputs', *[_lib.dptr(a) for a in r.values()])
+        return r
+
+    def last_plan(self):
+        xo, uo = np.empty((self.B, self.N + 1, self.n_x)), np.empty((self.B, self.N, self.n_u))
+        self._call('_last_plan', _lib.dptr(xo), _lib.dptr(uo))
+        return xo, uo
+
+    def stats(self):
+        steps, waits = C.c_int64(0), C.c_int64(0)
+        self._call('_stats', C.byref(steps), C.byref(waits))
+        return {'steps': steps.value, 'waits_last_run': waits.value}
+
+
+class ClosedLoopBatch(_LoopBatch):
+    _sym, _max_iters = 'sgusto_loop', 'sgusto_plan_set_max_iters'
+
     def __init__(self, gusto, plant, dt_sim, n_keep, t=None, z=None, u=None, phase=None, K=None, max_steps_per_run=None, observer=None):
         """gusto: a GuSTO on a TPWLGuSTO model with batch=B (the fused resident plan); plant: a TPWLATV (it may be the planner's own
         dyn_sys), stepped at dt_sim; n_keep: plant steps per period (the reference's N_replan with the controller clock at dt_sim).
@@ -64,65 +164,37 @@ class ClosedLoopBatch:
         if not (getattr(gusto, '_fused', False) and not getattr(gusto, '_ssm', False)):
             raise RuntimeError('ClosedLoopBatch needs a GuSTO on a TPWLGuSTO model with a fused resident plan (not an SSM plan, not '
                                'the host loop): there is no device rollout / solve to chain otherwise')
-        n_keep = int(n_keep)
-        if n_keep < 1 or not dt_sim > 0:
-            raise RuntimeError('ClosedLoopBatch: need n_keep >= 1 and dt_sim > 0')
-        if n_keep * float(dt_sim) > gusto.N * float(gusto.dt):
-            raise RuntimeError('ClosedLoopBatch: n_keep * dt_sim = %g exceeds the horizon N * dt = %g (the shift of the previous plan '
-                               'would find no row)' % (n_keep * float(dt_sim), gusto.N * float(gusto.dt)))
+        n_keep = self._check_periods(gusto, dt_sim, n_keep)
         if observer is not None:
             shape = (getattr(observer, 'batch', None), getattr(observer, 'state_dim', None), getattr(observer, 'input_dim', None))
             if shape != (gusto.batch, gusto.n_x, gusto.n_u):
                 raise RuntimeError('ClosedLoopBatch: the observer has batch = %s, n_x = %s, n_u = %s; the loop needs batch = %d, n_x = %d, '
                                    'n_u = %d' % (shape + (gusto.batch, gusto.n_x, gusto.n_u)))
         self.gusto, self.plant, self.observer = gusto, plant, observer       # (kept alive: the handle points into all three)
-        self.B, self.N, self.dt = gusto.batch, gusto.N, float(gusto.dt)
-        self.n_x, self.n_u, self.n_z = gusto.n_x, gusto.n_u, gusto.n_z
-        self.dt_sim, self.n_keep = float(dt_sim), n_keep
-        self.max_steps_per_run = int(max_steps_per_run) if max_steps_per_run is not None else 16 * n_keep
-        self.has_z, self.has_u, self.has_zf = z is not None, u is not None, z is not None and gusto.Qzf is not None
-        self.has_K = K is not None
-        self.t_start, self._k = 0.0, None
-        self._h = C.c_void_p()
+        self._shape(gusto, dt_sim, n_keep, max_steps_per_run, z, u)
+        self.has_zf, self.has_K = z is not None and gusto.Qzf is not None, K is not None
         lib = _lib.lib()
         _lib.check(lib.sgusto_loop_create(C.byref(self._h), gusto.plan, gusto.model.dyn_sys.handle_for(self.dt),
                                           plant.handle_for(self.dt_sim), C.c_double(self.dt_sim), C.c_int(n_keep),
                                           C.c_int64(self.max_steps_per_run)), 'sgusto_loop_create')
-        if z is not None or u is not None:
-            if t is None:
-                raise RuntimeError('ClosedLoopBatch: a target table needs its times t')
-            t = _lib.f64(np.asarray(t).reshape(-1))
-            T = t.shape[0]
-            z = None if z is None else _lib.f64(np.asarray(z).reshape(T, self.n_z))
-            u = None if u is None else _lib.f64(np.asarray(u).reshape(T, self.n_u))
-            phase = None if phase is None else _lib.f64(np.asarray(phase).reshape(self.B))
-            _lib.check(lib.sgusto_loop_set_target(self._h, C.c_int(T), _lib.dptr(t), _lib.dptr(z), _lib.dptr(u), _lib.dptr(phase)),
-                       'sgusto_loop_set_target')
+        self._set_target(t, z, u, phase)
         if K is not None:
             K = _lib.f64(np.stack([np.asarray(k) for k in K]).reshape(-1, self.n_u, self.n_x))
             if K.shape[0] != gusto.model.dyn_sys.num_points:
                 raise RuntimeError('ClosedLoopBatch: K has %d gains, the planner\'s model %d points' % (K.shape[0], gusto.model.dyn_sys.num_points))
-            _lib.check(lib.sgusto_loop_set_feedback(self._h, _lib.dptr(K)), 'sgusto_loop_set_feedback')
+            self._call('_set_feedback', _lib.dptr(K))
         self.n_y = None
         if observer is not None:
             observer.bind(self.dt_sim)
             self.n_y = observer.meas_dim
-            _lib.check(lib.sgusto_loop_set_observer(self._h, observer._h), 'sgusto_loop_set_observer')
-
-    def __del__(self):
-        try:
-            if self._h:
-                _lib.lib().sgusto_loop_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
+            self._call('_set_observer', observer._h)
 
     def reset(self, x0, t_start=0.0):
         """Plant states x0 (B, n_x) at t_start.  With an observer: reset_observed(x0, None, t_start) -- the estimates start at x0."""
         if self.observer is not None:
             return self.reset_observed(x0, None, t_start)
         x0 = _lib.f64(np.asarray(x0).reshape(self.B, self.n_x))
-        _lib.check(_lib.lib().sgusto_loop_reset(self._h, _lib.dptr(x0), C.c_double(float(t_start))), 'sgusto_loop_reset')
+        self._call('_reset', _lib.dptr(x0), C.c_double(float(t_start)))
         self.t_start, self._k = float(t_start), 0
 
     def reset_observed(self, x0, x_hat0=None, t_start=0.0):
@@ -136,8 +208,7 @@ class ClosedLoopBatch:
             if x_hat0.shape != (self.B, self.n_x):
                 raise RuntimeError('ClosedLoopBatch.reset_observed: x_hat0 must have shape (B, n_x) = %s, got %s' % ((self.B, self.n_x), x_hat0.shape))
             x_hat0 = _lib.f64(x_hat0)
-        _lib.check(_lib.lib().sgusto_loop_reset_observed(self._h, _lib.dptr(x0), _lib.dptr(x_hat0), C.c_double(float(t_start))),
-                   'sgusto_loop_reset_observed')
+        self._call('_reset_observed', _lib.dptr(x0), _lib.dptr(x_hat0), C.c_double(float(t_start)))
         self.t_start, self._k = float(t_start), 0
 
     def run(self, periods, W=None, record_x=True):
@@ -146,24 +217,9 @@ class ClosedLoopBatch:
         if self.observer is not None:
             return self.run_observed(periods, W=W, V=None, record_x=record_x)
         periods = int(periods)
-        B, S = self.B, periods * self.n_keep
-        if periods >= 1 and S <= self.max_steps_per_run:       # (what does not fit is refused by the library, with its message)
-            x = np.empty((B, S + 1, self.n_x)) if record_x else None
-            z, u = np.empty((B, S + 1, self.n_z)), np.empty((B, S, self.n_u))
-            iters, status = np.empty((periods, B), dtype=np.int32), np.empty((periods, B), dtype=np.int32)
-            J = np.empty((periods, B))
-            W = None if W is None else _lib.f64(np.asarray(W).reshape(periods, self.n_keep, B, self.n_x))
-        else:
-            x = W = None
-            z = u = J = np.empty(1)
-            iters = status = np.empty(1, dtype=np.int32)
-        lib = _lib.lib()
-        _lib.check(lib.sgusto_plan_set_max_iters(self.gusto.plan, C.c_int(int(self.gusto.max_gusto_iters))), 'set_max_iters')
-        _lib.check(lib.sgusto_loop_run(self._h, C.c_int(periods), _lib.dptr(W), _lib.dptr(x), _lib.dptr(z), _lib.dptr(u), _lib.iptr(iters),
-                                       _lib.iptr(status), _lib.dptr(J)), 'sgusto_loop_run')
-        t = schedule(self.N, self.dt, self.dt_sim, self.n_keep, self.t_start, self._k).t_k + self.dt_sim * np.arange(S + 1)
-        self._k += periods
-        return ClosedLoopResult(x, z, u, iters, status, J, t)
+        fits, r = self._records(periods, record_x, self.n_z)
+        W = None if W is None or not fits else _lib.f64(np.asarray(W).reshape(periods, self.n_keep, self.B, self.n_x))
+        return self._run('_run', periods, [W] + list(r.values()), r)
 
     def run_observed(self, periods, W=None, V=None, record_x=True):
         """run with the filters in the loop.  V (periods, n_keep, B, n_y): measurement noise, None: zero.  The result carries x_hat, y
@@ -171,55 +227,15 @@ class ClosedLoopBatch:
         if self.observer is None:
             raise RuntimeError('ClosedLoopBatch.run_observed: the loop has no observer (ClosedLoopBatch(..., observer=...))')
         periods = int(periods)
-        B, S = self.B, periods * self.n_keep
         if V is not None:
             V = np.asarray(V)
-            if V.shape != (periods, self.n_keep, B, self.n_y):
+            if V.shape != (periods, self.n_keep, self.B, self.n_y):
                 raise RuntimeError('ClosedLoopBatch.run_observed: V must have shape (periods, n_keep, B, n_y) = %s, got %s'
-                                   % ((periods, self.n_keep, B, self.n_y), V.shape))
+                                   % ((periods, self.n_keep, self.B, self.n_y), V.shape))
             V = _lib.f64(V)
-        if periods >= 1 and S <= self.max_steps_per_run:       # (what does not fit is refused by the library, with its message)
-            x = np.empty((B, S + 1, self.n_x)) if record_x else None
-            z, u = np.empty((B, S + 1, self.n_z)), np.empty((B, S, self.n_u))
-            iters, status, es = (np.empty((periods, B), dtype=np.int32) for _ in range(3))
-            J, xh, y = np.empty((periods, B)), np.empty((B, S + 1, self.n_x)), np.empty((B, S, self.n_y))
-            W = None if W is None else _lib.f64(np.asarray(W).reshape(periods, self.n_keep, B, self.n_x))
-        else:
-            x = W = V = None
-            z = u = J = xh = y = np.empty(1)
-            iters = status = es = np.empty(1, dtype=np.int32)
-        lib = _lib.lib()
-        _lib.check(lib.sgusto_plan_set_max_iters(self.gusto.plan, C.c_int(int(self.gusto.max_gusto_iters))), 'set_max_iters')
-        _lib.check(lib.sgusto_loop_run_observed(self._h, C.c_int(periods), _lib.dptr(W), _lib.dptr(V), _lib.dptr(x), _lib.dptr(z), _lib.dptr(u),
-                                                _lib.iptr(iters), _lib.iptr(status), _lib.dptr(J), _lib.dptr(xh), _lib.dptr(y), _lib.iptr(es)),
-                   'sgusto_loop_run_observed')
-        t = schedule(self.N, self.dt, self.dt_sim, self.n_keep, self.t_start, self._k).t_k + self.dt_sim * np.arange(S + 1)
-        self._k += periods
-        return ClosedLoopResult(x, z, u, iters, status, J, t, x_hat=xh, y=y, ekf_status=es)
-
-    def step(self):
-        return self.run(1)
-
-    def last_inputs(self):
-        """The solver inputs of the last period: dict x0, u_init, x_init, z, zf, u (None where the loop has none)."""
-        B, N = self.B, self.N
-        x0, ui, xi = np.empty((B, self.n_x)), np.empty((B, N, self.n_u)), np.empty((B, N + 1, self.n_x))
-        z = np.empty((B, N + 1, self.n_z)) if self.has_z else None
-        zf = np.empty((B, self.n_z)) if self.has_zf else None
-        ud = np.empty((B, N, self.n_u)) if self.has_u else None
-        _lib.check(_lib.lib().sgusto_loop_last_inputs(self._h, _lib.dptr(x0), _lib.dptr(ui), _lib.dptr(xi), _lib.dptr(z), _lib.dptr(zf),
-                                                      _lib.dptr(ud)), 'sgusto_loop_last_inputs')
-        return dict(x0=x0, u_init=ui, x_init=xi, z=z, zf=zf, u=ud)
-
-    def last_plan(self):
-        xo, uo = np.empty((self.B, self.N + 1, self.n_x)), np.empty((self.B, self.N, self.n_u))
-        _lib.check(_lib.lib().sgusto_loop_last_plan(self._h, _lib.dptr(xo), _lib.dptr(uo)), 'sgusto_loop_last_plan')
-        return xo, uo
-
-    def stats(self):
-        steps, waits = C.c_int64(0), C.c_int64(0)
-        _lib.check(_lib.lib().sgusto_loop_stats(self._h, C.byref(steps), C.byref(waits)), 'sgusto_loop_stats')
-        return {'steps': steps.value, 'waits_last_run': waits.value}
+        fits, r = self._records(periods, record_x, self.n_z, x_hat=(1, self.n_x), y=(0, self.n_y), ekf_status=None)
+        W = None if W is None or not fits else _lib.f64(np.asarray(W).reshape(periods, self.n_keep, self.B, self.n_x))
+        return self._run('_run_observed', periods, [W, V if fits else None] + list(r.values()), r)
 
     def _advance(self, xopt, uopt, x, W=None):
         """The advance kernel alone on host-supplied plans (for tests): xopt (B, N+1, n_x), uopt (B, N, n_u), x (B, n_x), W (n_keep, B,

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from .. import _lib
-from .closed_loop import ClosedLoopResult, schedule
+from .closed_loop import ClosedLoopResult, _LoopBatch, schedule          # noqa: F401  (the result type and the one schedule, under this name too)
 
 _MODES = {'fe': 1, 'be': 2, 'bil': 3}
 
@@ -25,7 +25,9 @@ def _plant_mode(plant):
     return _MODES[plant.discr_method]
 
 
-class SSMClosedLoopBatch:
+class SSMClosedLoopBatch(_LoopBatch):
+    _sym, _max_iters = 'sgusto_ssm_loop', 'sgusto_ssm_plan_set_max_iters'
+
     def __init__(self, gusto, plant, dt_sim, n_keep, t=None, z=None, u=None, phase=None, observe=True, max_steps_per_run=None):
         """gusto: a GuSTO on an SSMGuSTO model with batch=B whose SSM plan is resident; plant: an SSMDynamics of the same n_x, n_u and n_o
         (it may be the planner's own dyn_sys, or another model), stepped at dt_sim in its own discretisation (fe, be, bil, or its discrete
@@ -39,43 +41,15 @@ class SSMClosedLoopBatch:
         if getattr(gusto, '_rate_rows', 0):
             raise RuntimeError('SSMClosedLoopBatch: the plan has %d input-rate rows (dU): a rollout whose trust region binds under them returns '
                                'status -78 for the host loop, which a loop resident on the device cannot serve' % gusto._rate_rows)
-        n_keep = int(n_keep)
-        if n_keep < 1 or not dt_sim > 0:
-            raise RuntimeError('SSMClosedLoopBatch: need n_keep >= 1 and dt_sim > 0')
-        if n_keep * float(dt_sim) > gusto.N * float(gusto.dt):
-            raise RuntimeError('SSMClosedLoopBatch: n_keep * dt_sim = %g exceeds the horizon N * dt = %g (the shift of the previous plan '
-                               'would find no row)' % (n_keep * float(dt_sim), gusto.N * float(gusto.dt)))
+        n_keep = self._check_periods(gusto, dt_sim, n_keep)
         self.gusto, self.plant = gusto, plant                      # (kept alive: the handle points into both)
-        self.B, self.N, self.dt = gusto.batch, gusto.N, float(gusto.dt)
-        self.n_x, self.n_u, self.n_z = gusto.n_x, gusto.n_u, gusto.n_z
-        self.n_o = plant.output_dim
-        self.dt_sim, self.n_keep, self.observe = float(dt_sim), n_keep, bool(observe)
-        self.max_steps_per_run = int(max_steps_per_run) if max_steps_per_run is not None else 16 * n_keep
-        self.has_z, self.has_u = z is not None, u is not None
-        self.t_start, self._k = 0.0, None
-        self._h = C.c_void_p()
+        self._shape(gusto, dt_sim, n_keep, max_steps_per_run, z, u)
+        self.n_o, self.observe = plant.output_dim, bool(observe)
         lib = _lib.lib()
         _lib.check(lib.sgusto_ssm_loop_create(C.byref(self._h), gusto.plan, gusto.model.dyn_sys.handle, plant.handle, C.c_int(_plant_mode(plant)),
                                               C.c_double(self.dt_sim), C.c_int(n_keep), C.c_int(1 if self.observe else 0),
                                               C.c_int64(self.max_steps_per_run)), 'sgusto_ssm_loop_create')
-        if z is not None or u is not None:
-            if t is None:
-                raise RuntimeError('SSMClosedLoopBatch: a target table needs its times t')
-            t = _lib.f64(np.asarray(t).reshape(-1))
-            T = t.shape[0]
-            z = None if z is None else _lib.f64(np.asarray(z).reshape(T, self.n_z))
-            u = None if u is None else _lib.f64(np.asarray(u).reshape(T, self.n_u))
-            phase = None if phase is None else _lib.f64(np.asarray(phase).reshape(self.B))
-            _lib.check(lib.sgusto_ssm_loop_set_target(self._h, C.c_int(T), _lib.dptr(t), _lib.dptr(z), _lib.dptr(u), _lib.dptr(phase)),
-                       'sgusto_ssm_loop_set_target')
-
-    def __del__(self):
-        try:
-            if self._h:
-                _lib.lib().sgusto_ssm_loop_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
+        self._set_target(t, z, u, phase)
 
     def _shaped(self, what, a, shape):
         """`a` as a contiguous float64 array of exactly `shape` (None passes through)."""
@@ -92,7 +66,7 @@ class SSMClosedLoopBatch:
         before its first compute_policy."""
         v0 = self._shaped('v0 (B, n_o)', v0, (self.B, self.n_o))
         x0 = _lib.f64(np.asarray(x0).reshape(self.B, self.n_x))
-        _lib.check(_lib.lib().sgusto_ssm_loop_reset(self._h, _lib.dptr(x0), _lib.dptr(v0), C.c_double(float(t_start))), 'sgusto_ssm_loop_reset')
+        self._call('_reset', _lib.dptr(x0), _lib.dptr(v0), C.c_double(float(t_start)))
         self.t_start, self._k = float(t_start), 0
 
     def run(self, periods, W=None, V=None, record_x=True):
@@ -100,49 +74,12 @@ class SSMClosedLoopBatch:
         n_keep, B, n_o): added to the measurement.  Returns a ClosedLoopResult with x (B, S + 1, n_x) or None, z, y (B, S + 1, n_o),
         x_hat (B, S + 1, n_x), u (B, S, n_u), S = periods n_keep, row 0 where the run started; iters, status, J (periods, B); t."""
         periods = int(periods)
-        B, S = self.B, periods * self.n_keep
-        W = self._shaped('W (periods, n_keep, B, n_x)', W, (periods, self.n_keep, B, self.n_x))
-        V = self._shaped('V (periods, n_keep, B, n_o)', V, (periods, self.n_keep, B, self.n_o))
-        if periods >= 1 and S <= self.max_steps_per_run:       # (what does not fit is refused by the library, with its message)
-            x = np.empty((B, S + 1, self.n_x)) if record_x else None
-            z, y, xh = np.empty((B, S + 1, self.n_o)), np.empty((B, S + 1, self.n_o)), np.empty((B, S + 1, self.n_x))
-            u = np.empty((B, S, self.n_u))
-            iters, status = np.empty((periods, B), dtype=np.int32), np.empty((periods, B), dtype=np.int32)
-            J = np.empty((periods, B))
-        else:
-            x = W = V = None
-            z = y = xh = u = J = np.empty(1)
-            iters = status = np.empty(1, dtype=np.int32)
-        lib = _lib.lib()
-        _lib.check(lib.sgusto_ssm_plan_set_max_iters(self.gusto.plan, C.c_int(int(self.gusto.max_gusto_iters))), 'set_max_iters')
-        _lib.check(lib.sgusto_ssm_loop_run(self._h, C.c_int(periods), _lib.dptr(W), _lib.dptr(V), _lib.dptr(x), _lib.dptr(z), _lib.dptr(u),
-                                           _lib.dptr(y), _lib.dptr(xh), _lib.iptr(iters), _lib.iptr(status), _lib.dptr(J)), 'sgusto_ssm_loop_run')
-        t = schedule(self.N, self.dt, self.dt_sim, self.n_keep, self.t_start, self._k).t_k + self.dt_sim * np.arange(S + 1)
-        self._k += periods
-        return ClosedLoopResult(x, z, u, iters, status, J, t, x_hat=xh, y=y)
-
-    def step(self):
-        return self.run(1)
-
-    def last_inputs(self):
-        """The solver inputs of the last period: dict x0, u_init, x_init, z, u (None where the loop has none)."""
-        B, N = self.B, self.N
-        x0, ui, xi = np.empty((B, self.n_x)), np.empty((B, N, self.n_u)), np.empty((B, N + 1, self.n_x))
-        z = np.empty((B, N + 1, self.n_z)) if self.has_z else None
-        ud = np.empty((B, N, self.n_u)) if self.has_u else None
-        _lib.check(_lib.lib().sgusto_ssm_loop_last_inputs(self._h, _lib.dptr(x0), _lib.dptr(ui), _lib.dptr(xi), _lib.dptr(z), _lib.dptr(ud)),
-                   'sgusto_ssm_loop_last_inputs')
-        return dict(x0=x0, u_init=ui, x_init=xi, z=z, u=ud)
-
-    def last_plan(self):
-        xo, uo = np.empty((self.B, self.N + 1, self.n_x)), np.empty((self.B, self.N, self.n_u))
-        _lib.check(_lib.lib().sgusto_ssm_loop_last_plan(self._h, _lib.dptr(xo), _lib.dptr(uo)), 'sgusto_ssm_loop_last_plan')
-        return xo, uo
-
-    def stats(self):
-        steps, waits = C.c_int64(0), C.c_int64(0)
-        _lib.check(_lib.lib().sgusto_ssm_loop_stats(self._h, C.byref(steps), C.byref(waits)), 'sgusto_ssm_loop_stats')
-        return {'steps': steps.value, 'waits_last_run': waits.value}
+        W = self._shaped('W (periods, n_keep, B, n_x)', W, (periods, self.n_keep, self.B, self.n_x))
+        V = self._shaped('V (periods, n_keep, B, n_o)', V, (periods, self.n_keep, self.B, self.n_o))
+        fits, r = self._records(periods, record_x, self.n_o, y=(1, self.n_o), x_hat=(1, self.n_x))
+        if not fits:
+            W = V = None
+        return self._run('_run', periods, [W, V] + [r[k] for k in ('x', 'z', 'u', 'y', 'x_hat', 'iters', 'status', 'J')], r)
 
 
 def advance(plant, observer_model, dt_sim, N, j, theta, uopt, x, W=None, V=None, xopt=None):

@@ -306,7 +306,35 @@ def test_one_wait_per_run_records_and_the_first_estimate(frac_run4):
         assert e <= cr.TOL_FLOOR
 
 
-# ---------------------------------------------------------------------------------------------------------------- 6. refusals
+# ---------------------------------------------------------------------------------------------------------------- 6. two units, one host shell
+def test_interleaved_tpwl_and_ssm_loops_equal_each_loop_alone():
+    """Both units run on the host shell of csrc/gusto_loop_host.h: a TPWL loop and an SSM loop driven in turn, with disturbance and noise,
+    give the records, bit for bit, of the same two runs of each loop alone -- nothing of a handle lives in a static or a shared block."""
+    import test_gusto_loop_gpu as tl
+
+    def tpwl():
+        cl, _, inp = tl.make_loop('frac', 3)
+        cl.reset(inp['x0'], T_START)
+        return cl, lambda k: cl.run(1, W=inp['W'][k:k + 1])
+
+    def ssm():
+        cl, _, inp = make_loop('frac', 3)
+        cl.reset(inp['x0'], T_START, v0=inp['v0'])
+        return cl, lambda k: cl.run(1, W=inp['W'][k:k + 1], V=inp['V'][k:k + 1])
+
+    (ct, rt), (cs, rs) = tpwl(), ssm()
+    alone_t, alone_s = [rt(0), rt(1)], [rs(0), rs(1)]
+    (ct, rt), (cs, rs) = tpwl(), ssm()
+    mixed = [rt(0), rs(0), rt(1), rs(1)]
+    assert ct.stats() == {'steps': 2, 'waits_last_run': 1} and cs.stats() == {'steps': 2, 'waits_last_run': 1}
+    for k in range(2):
+        tl.same(mixed[2 * k], alone_t[k])
+        same(mixed[2 * k + 1], alone_s[k])
+        np.testing.assert_array_equal(mixed[2 * k].t, alone_t[k].t); np.testing.assert_array_equal(mixed[2 * k + 1].t, alone_s[k].t)
+    assert not np.array_equal(alone_t[0].x, alone_t[1].x) and not np.array_equal(alone_s[0].x, alone_s[1].x)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 7. refusals
 def test_refusals():
     from sofacontrol_amd import _lib
     from sofacontrol_amd.scp.closed_loop_ssm import SSMClosedLoopBatch

@@ -47,8 +47,9 @@ def test_python_surface_and_the_one_schedule():
     # the schedule used is the TPWL loop's: the same function object, and no second statement in the module or in the new unit
     assert closed_loop_ssm.schedule is closed_loop.schedule
     assert 'def schedule' not in inspect.getsource(closed_loop_ssm)
-    unit = open(os.path.join(ROOT, 'soft-robot-control_amd', 'csrc', 'gusto_ssm_loop.hip')).read()
-    assert unit.count('sgusto_loop_schedule(') == 2 and 'int sgusto_loop_schedule' not in unit
+    csrc = os.path.join(ROOT, 'soft-robot-control_amd', 'csrc')
+    units = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith(('.hip', '.h'))}
+    assert sum(u.count('int sgusto_loop_schedule') for u in units.values()) == 1 and 'sgusto_loop_schedule' not in units['gusto_ssm_loop.hip']
     # the original loop still refuses SSM plans
     with pytest.raises(RuntimeError, match='fused resident plan'):
         closed_loop.ClosedLoopBatch(types.SimpleNamespace(_fused=True, _ssm=True, N=3, dt=0.02), None, 0.02, 2)

@@ -1,0 +1,209 @@
+"""Bit-level dump of the closed-loop units (csrc/gusto_loop.hip, csrc/gusto_ssm_loop.hip and the host shell they share,
+csrc/gusto_loop_host.h) for comparing two builds of the library (SRH_LIB_PATH selects one).
+
+Runs the loops of the test suites at their own smallest shapes through scp.closed_loop / scp.closed_loop_ssm and records every array
+that comes back, raw:
+  - TPWL (tests/test_gusto_loop_gpu.py: cl_cases.LOOPS 'frac' and 'zf-u', g6 model, B = 3): reset(x0, 0.1), run(2, W), run(2, W),
+    run(4, record_x=False), then _advance once on the last plan;
+  - observed TPWL (tests/test_gusto_loop_observer_gpu.py: the g6 loop, n_y = 6, B = 3): reset_observed, run_observed(2, W, V) twice, then
+    _advance_observed on the case 'g6-frac-3' of clobs_cases.CASES;
+  - SSM (tests/test_gusto_ssm_loop_gpu.py: 'hw' and 'frac', B = 3, observe True and False): reset with v0, run(2, W, V) twice, and the
+    stand-alone advance on one entry of ssm_loop_cases.ADVANCE;
+after every run also last_inputs(), last_plan() and stats().  The host-side refusals are recorded as text, message for message: run
+before reset, periods * n_keep over the cap, last_inputs before a period, the observed run without an observer, the SSM model mismatch.
+
+    python tools/loop_dump.py --out dumps/new        writes <out>.bin (the records, raw) and <out>.json (their index)
+    python tools/loop_dump.py --compare A B --log profiles/x.log    compares two dumps record by record, byte for byte; exit 1 on a difference
+
+One dump per process.  Needs the GPU (not for --compare)."""
+import argparse
+import ctypes as C
+import hashlib
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'soft-robot-control_amd'), os.path.join(ROOT, 'tests')]
+
+T_START = 0.1
+RESULT_FIELDS = ('x', 'z', 'u', 'iters', 'status', 'J', 't', 'x_hat', 'y', 'ekf_status')
+
+
+class Records(list):
+    def array(self, name, a):
+        self.append((name, b'' if a is None else np.ascontiguousarray(a).tobytes()))
+
+    def arrays(self, label, d):
+        for k, a in d.items():
+            self.array('%s/%s' % (label, k), a)
+
+    def after_run(self, label, cl, r):
+        self.arrays(label, {f: getattr(r, f) for f in RESULT_FIELDS})
+        self.arrays(label + '/last_inputs', cl.last_inputs())
+        self.arrays(label + '/last_plan', dict(zip(('xopt', 'uopt'), cl.last_plan())))
+        self.append((label + '/stats', json.dumps(cl.stats(), sort_keys=True).encode()))
+
+    def refusal(self, label, call):
+        try:
+            call()
+            text = 'NOT REFUSED'
+        except RuntimeError as e:
+            text = str(e)
+        self.append(('refusal/' + label, text.encode()))
+
+
+def dump_tpwl(rec):
+    import cl_cases as cc
+    import test_gusto_loop_gpu as tl
+    for name in ('frac', 'zf-u'):
+        cl, gu, inp = tl.make_loop(name, 3)
+        label = 'tpwl/' + name
+        if name == 'frac':
+            rec.refusal('tpwl/run_before_reset', lambda: cl.run(1))
+        cl.reset(inp['x0'], T_START)
+        if name == 'frac':
+            rec.refusal('tpwl/last_inputs_before_a_period', lambda: cl.last_inputs())
+        for q in range(2):
+            rec.after_run('%s/run2_%d' % (label, q), cl, cl.run(2, W=inp['W'][2 * q:2 * q + 2]))
+        cl.reset(inp['x0'], T_START)
+        rec.after_run(label + '/run4_no_x', cl, cl.run(cc.PERIODS, record_x=False))
+        xo, uo = cl.last_plan()
+        rec.arrays(label + '/advance', dict(zip(('X', 'Z', 'U', 'idx_plant', 'idx_gain'), cl._advance(xo, uo, cl.last_inputs()['x0']))))
+    cl, gu, inp = tl.make_loop('frac', 3, max_steps_per_run=30)
+    cl.reset(inp['x0'], T_START)
+    rec.refusal('tpwl/over_the_cap', lambda: cl.run(4))
+    # the library's own answer to an observed run on a loop without an observer (the class refuses earlier, with its own message)
+    from sofacontrol_amd import _lib
+    d, i = np.empty(1), np.empty(1, dtype=np.int32)
+    rec.refusal('tpwl/observed_run_without_an_observer/class', lambda: cl.run_observed(1))
+    rec.refusal('tpwl/observed_run_without_an_observer/library', lambda: _lib.check(_lib.lib().sgusto_loop_run_observed(
+        cl._h, C.c_int(1), None, None, None, _lib.dptr(d), _lib.dptr(d), _lib.iptr(i), _lib.iptr(i), _lib.dptr(d), _lib.dptr(d), _lib.dptr(d),
+        _lib.iptr(i)), 'sgusto_loop_run_observed'))
+
+
+def dump_observed(rec):
+    import clobs_cases as oc
+    import test_gusto_loop_observer_gpu as to
+    from sofacontrol_amd.scp.closed_loop import ClosedLoopBatch
+    cl, inp = to.make_loop('g6', (0, 1, 2))
+    rec.refusal('observed/run_before_reset', lambda: cl.run_observed(1))
+    cl.reset_observed(inp['x0'], inp['x_hat0'], T_START)
+    rec.refusal('observed/last_inputs_before_a_period', lambda: cl.last_inputs())
+    for q in range(2):
+        rec.after_run('observed/g6/run2_%d' % q, cl, cl.run_observed(2, W=inp['W'][2 * q:2 * q + 2], V=inp['V'][2 * q:2 * q + 2]))
+    rec.refusal('observed/over_the_cap', lambda: cl.run_observed(17))
+    cs = [c for c in oc.CASES if c[0] == 'g6-frac-3'][0]
+    name, mname, same, dt_sim, n_keep = cs[:5]
+    tp, gm = to.planner(mname)
+    c = oc.case(cs)
+    cl = ClosedLoopBatch(to.make_gusto(mname, oc.B, np.zeros((oc.B, gm.n_x))), tp, dt_sim, n_keep, K=c['K'], observer=to.make_observer(mname, same, oc.B))
+    rec.arrays('observed/advance/' + name, cl._advance_observed(c['xopt'], c['uopt'], c['x'], c['x_hat'], c['W'], c['V']))
+    rec.refusal('observed/run_behind_the_advance', lambda: cl.run_observed(1))
+
+
+def dump_ssm(rec):
+    import ssm_cases as sc
+    import ssm_loop_cases as slc
+    import test_gusto_ssm_loop_gpu as ts
+    from test_ssm_gpu import product_ssm
+    from sofacontrol_amd.scp import closed_loop_ssm
+    for name in ts.LOOPS:
+        for observe in (True, False):
+            cl, gu, inp = ts.make_loop(name, 3, observe=observe)
+            label = 'ssm/%s/%s' % (name, 'estimate' if observe else 'state')
+            if name == 'hw' and observe:
+                rec.refusal('ssm/run_before_reset', lambda: cl.run(1))
+            cl.reset(inp['x0'], T_START, v0=inp['v0'])
+            if name == 'hw' and observe:
+                rec.refusal('ssm/last_inputs_before_a_period', lambda: cl.last_inputs())
+            for q in range(2):
+                rec.after_run('%s/run2_%d' % (label, q), cl, cl.run(2, W=inp['W'][2 * q:2 * q + 2], V=inp['V'][2 * q:2 * q + 2]))
+    cl, gu, inp = ts.make_loop('frac', 3, max_steps_per_run=30)
+    cl.reset(inp['x0'], T_START)
+    rec.refusal('ssm/over_the_cap', lambda: cl.run(8))
+    hw = ts.make_gusto('hw', 3, ts.inputs('hw', 3)['x0'])
+    rec.refusal('ssm/model_mismatch', lambda: closed_loop_ssm.SSMClosedLoopBatch(hw, ts.models('frac')[1], 0.02, 2))
+    case = slc.ADVANCE[1]
+    s, method, dt_sim, dt, N, nk = case
+    planner = product_ssm(sc.oracle_model(sc.model(s)), discr='fe')
+    pm = sc.oracle_model(slc.plant_model(s))
+    plant = product_ssm(pm, discrete=True) if method == 'map' else product_ssm(pm, discr=method)
+    i = slc.inputs(case)
+    got = closed_loop_ssm.advance(plant, planner, dt_sim, N, i['j'], i['theta'], i['uopt'], i['x'], W=i['W'], V=i['V'])
+    rec.arrays('ssm/advance/' + slc.case_id(case), got)
+
+
+def dump(out):
+    from sofacontrol_amd import _lib
+    assert _lib.device_count() >= 1, 'no GPU visible'
+    _lib.set_device(0)
+    rec = Records()
+    dump_tpwl(rec)
+    dump_observed(rec)
+    dump_ssm(rec)
+    index, off = [], 0
+    with open(out + '.bin', 'wb') as f:
+        for name, b in rec:
+            f.write(b)
+            index.append(dict(name=name, offset=off, bytes=len(b), sha256=hashlib.sha256(b).hexdigest()))
+            off += len(b)
+    refusals = {name: b.decode() for name, b in rec if name.startswith('refusal/')}
+    with open(out + '.json', 'w') as f:
+        json.dump(dict(library=os.path.relpath(_lib.LIB_PATH, ROOT), refusals=refusals, records=index), f, indent=0)
+    print('loop_dump: %d records (%d refusals), %d bytes -> %s.bin (library %s)' % (len(index), len(refusals), off, out, os.path.relpath(_lib.LIB_PATH, ROOT)))
+
+
+def compare(a, b, log):
+    ja, jb = (json.load(open(p + '.json')) for p in (a, b))
+    ba, bb = (open(p + '.bin', 'rb').read() for p in (a, b))
+    lines = ['loop_dump --compare', 'A: %s (library %s)' % (a, ja['library']), 'B: %s (library %s)' % (b, jb['library'])]
+    same_index = [r['name'] for r in ja['records']] == [r['name'] for r in jb['records']]
+    lines.append('records: %d / %d, same names in the same order: %s' % (len(ja['records']), len(jb['records']), same_index))
+    per_group, differing = {}, []
+    if same_index:
+        for ra, rb in zip(ja['records'], jb['records']):
+            equal = ba[ra['offset']:ra['offset'] + ra['bytes']] == bb[rb['offset']:rb['offset'] + rb['bytes']]
+            parts = ra['name'].split('/')
+            group = '/'.join(parts[:1 if parts[0] == 'refusal' else 4 if parts[0] == 'ssm' and parts[1] != 'advance' else 3])
+            t = per_group.setdefault(group, [0, 0, 0])
+            t[0] += 1
+            t[1] += 0 if equal else 1
+            t[2] += ra['bytes']
+            if not equal:
+                differing.append(ra['name'])
+    for group, (total, bad, size) in per_group.items():
+        lines.append('%-44s %3d records, %7d bytes, %s' % (group, total, size, 'identical' if bad == 0 else '%d DIFFER' % bad))
+    lines.append('refusals, message for message:')
+    for name, text in ja['refusals'].items():
+        lines.append('  %-52s %s' % (name[len('refusal/'):], 'same: ' + text if jb['refusals'].get(name) == text else
+                                     'DIFFER: %r / %r' % (text, jb['refusals'].get(name))))
+    ok = same_index and not differing and ba == bb and ja['refusals'] == jb['refusals'] and 'NOT REFUSED' not in ja['refusals'].values()
+    lines += ['first differing records: %s' % differing[:8]] if differing else []
+    lines.append('whole files (%d / %d bytes) identical: %s' % (len(ba), len(bb), ba == bb))
+    lines.append('RESULT: %s' % ('identical, byte for byte' if ok else 'DIFFERENT'))
+    print('\n'.join(lines))
+    if log:
+        with open(log, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+    return 0 if ok else 1
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out')
+    ap.add_argument('--compare', nargs=2, metavar=('A', 'B'))
+    ap.add_argument('--log')
+    args = ap.parse_args()
+    if args.compare:
+        sys.exit(compare(args.compare[0], args.compare[1], args.log))
+    if not args.out:
+        ap.error('need --out or --compare')
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    dump(args.out)
+
+
+if __name__ == '__main__':
+    main()
