@@ -171,6 +171,11 @@ int stpwl_set_output(stpwl_t *h, const double *H, const double *z_ref, int n_z);
 /* TPWL.calc_nearest_point (tpwl.py:160-168) for B states X (B x n_x): idx (B,) int32 */
 int stpwl_nearest(stpwl_t *h, const double *X, int64_t B, int32_t *idx);
 int stpwl_nearest_dev(stpwl_t *h, const double *X_dev, int64_t B, int32_t *idx_dev, void *stream);
+/* The same search as the GuSTO kernels run it over the states of a horizon (tpwl::nearest_many, csrc/tpwl_dev.h): ONE workgroup of
+ * `threads` (256 or 512) for `count` >= 1 states X (count x n_x) -> idx (count,).  With w_v = 0, P <= 64, r <= 32 and at least two
+ * rounds of the workgroup's waves (count >= 2 threads / 64) the point table is held in registers; otherwise the wave search of
+ * stpwl_nearest.  Same indices either way.  For tests and records. */
+int stpwl_nearest_many(stpwl_t *h, const double *X, int count, int threads, int32_t *idx);
 /* TPWLATV.get_jacobians, nn branch (tpwl.py:251-265): gathers (A,B,d)[idx] of the discrete
  * (discrete=1) or continuous tables: A (B x n_x x n_x), Bm (B x n_x x n_u), d (B x n_x) */
 int stpwl_linearize(stpwl_t *h, const double *X, int64_t B, int discrete, double *A, double *Bm,

@@ -13,6 +13,11 @@ __global__ void nearest_kernel(TpwlDev T, const double *__restrict__ X, int64_t 
     if ((threadIdx.x & 63) == 0) idx[k] = i;
 }
 
+// tpwl::nearest_many as the GuSTO kernels call it (one workgroup, the states in a row-major block), for stpwl_nearest_many
+__global__ __launch_bounds__(512) void nearest_many_kernel(TpwlDev T, const double *__restrict__ X, int count, int32_t *__restrict__ idx) {
+    tpwl::nearest_many(T, (cgptr)X, T.n, count, (giptr)idx);
+}
+
 __global__ void gather_kernel(TpwlDev T, const int32_t *__restrict__ idx, int64_t B, int discrete,
                               double *__restrict__ A, double *__restrict__ Bm, double *__restrict__ d) {
     const int64_t b = blockIdx.x;
@@ -27,7 +32,8 @@ __global__ void gather_kernel(TpwlDev T, const int32_t *__restrict__ idx, int64_
 
 
 // softmin weights over the stored points (tpwl.py:170-191): w_i = exp(-beta d_i / d_min) / sum_j(...),
-// one-hot at the (first) minimum when d_min == 0.  One workgroup per query state; W (B x P).
+// one-hot at the first minimum (the rule of tpwl_dev.h) when d_min == 0.  One workgroup per query state; W (B x P).
+// A state that is not a number gives a row that is not a number (d_i / d_min is not one).
 __global__ __launch_bounds__(256) void weights_kernel(TpwlDev T, const double *__restrict__ X, int64_t B,
                                                       double beta, double *__restrict__ W) {
     __shared__ double rv[256];
@@ -35,17 +41,21 @@ __global__ __launch_bounds__(256) void weights_kernel(TpwlDev T, const double *_
     const int64_t b = blockIdx.x;
     const double *x = X + b * T.n;
     double *w = W + b * T.P;
-    double best = INFINITY;
-    int besti = 0x7fffffff;
+    double best = INFINITY;                              // no candidate yet (the rule of tpwl_dev.h)
+    int besti = 0;
     for (int i = threadIdx.x; i < T.P; i += blockDim.x) {
         double sq = 0.0, sv = 0.0;
         for (int j = 0; j < T.r; ++j) {
             const double e = T.qT[j * T.P + i] - x[T.r + j];
             sq = fma(e, e, sq);
-            const double f = T.vT[j * T.P + i] - x[j];
-            sv = fma(f, f, sv);
         }
-        const double d = T.w_q * sqrt(sq) + T.w_v * sqrt(sv);
+        if (T.w_v != 0.0) {                              // (the rule of tpwl_dev.h: w_v == 0 does not read the velocity)
+            for (int j = 0; j < T.r; ++j) {
+                const double f = T.vT[j * T.P + i] - x[j];
+                sv = fma(f, f, sv);
+            }
+        }
+        const double d = T.w_v != 0.0 ? T.w_q * sqrt(sq) + T.w_v * sqrt(sv) : T.w_q * sqrt(sq);     // (one expression, as ever: the same fma contraction)
         w[i] = d;
         if (d < best) { best = d; besti = i; }
     }
@@ -55,7 +65,7 @@ __global__ __launch_bounds__(256) void weights_kernel(TpwlDev T, const double *_
         if ((int)threadIdx.x < o) {
             const double ob = rv[threadIdx.x + o];
             const int oi = ri[threadIdx.x + o];
-            if (ob < rv[threadIdx.x] || (ob == rv[threadIdx.x] && oi < ri[threadIdx.x])) {
+            if (tpwl::goes_before(ob, oi, rv[threadIdx.x], ri[threadIdx.x])) {
                 rv[threadIdx.x] = ob; ri[threadIdx.x] = oi;
             }
         }
@@ -108,6 +118,22 @@ __global__ __launch_bounds__(256) void blend_kernel(TpwlDev T, const double *__r
     }
 }
 
+// wg::matTvec for len > blockDim.x, where its (slice, j) layout has one slice and no thread for the columns j >= blockDim.x: thread t takes
+// the columns t, t + blockDim.x, ...  The sums are those of wg::matTvec with one slice: rows 0, 1, ... by fma from 0.0, then add[j] + sum.
+// add may be y (each column is read and written by its own thread).  Ends with __syncthreads().
+template <typename MP, typename AP>
+__device__ inline void matTvec_strided(lptr y, MP M, int ldm, int rows, int len, clptr v, AP add) {
+    for (int j = threadIdx.x; j < len; j += blockDim.x) {
+        double acc = 0.0;
+#pragma unroll 4
+        for (int i = 0; i < rows; ++i) acc = fma(M[i * ldm + j], v[i], acc);
+        double r = add ? add[j] : 0.0;
+        r += acc;
+        y[j] = r;
+    }
+    __syncthreads();
+}
+
 // one workgroup per rollout: x_{k+1} = A_d[i_k] x_k + B_d[i_k] u_k + d_d[i_k], i_k = nearest(x_k)
 __global__ __launch_bounds__(256) void rollout_kernel(TpwlDev T, const double *__restrict__ x0,
                                                       const double *__restrict__ U, int N,
@@ -132,8 +158,13 @@ __global__ __launch_bounds__(256) void rollout_kernel(TpwlDev T, const double *_
         __syncthreads();
         const int i = *ip;
         // xn = A x + d  (via the transposed table: coalesced), then += B u
-        wg::matTvec(xn, T.AdT + (size_t)i * n * n, n, n, n, xc, T.dd + (size_t)i * n, part);
-        wg::matTvec(xn, T.BdT + (size_t)i * m * n, n, m, n, uc, (clptr)xn, part);
+        if (n <= (int)blockDim.x) {
+            wg::matTvec(xn, T.AdT + (size_t)i * n * n, n, n, n, xc, T.dd + (size_t)i * n, part);
+            wg::matTvec(xn, T.BdT + (size_t)i * m * n, n, m, n, uc, (clptr)xn, part);
+        } else {                                         // (n_x > 256: wg::matTvec has no thread for the columns past blockDim.x)
+            matTvec_strided(xn, T.AdT + (size_t)i * n * n, n, n, n, xc, T.dd + (size_t)i * n);
+            matTvec_strided(xn, T.BdT + (size_t)i * m * n, n, m, n, uc, (clptr)xn);
+        }
         for (int e = threadIdx.x; e < n; e += blockDim.x) { xc[e] = xn[e]; Xb[(size_t)(k + 1) * n + e] = xn[e]; }
         __syncthreads();
     }
@@ -217,9 +248,7 @@ __global__ __launch_bounds__(256) void rollout_staged_kernel(TpwlDev T, const do
                     }
                 }
                 const double dist = lane < T.P ? T.w_q * sqrt(sq) : INFINITY;
-                const double dmin = wg::wave_min(dist);
-                const int imin = (int)wg::wave_min(dist == dmin ? (double)lane : 1e9);        // first minimum (np.argmin)
-                i = imin < T.P ? imin : 0;                                                    // (a state that is not a number: no minimum)
+                i = tpwl::wave_first_min(dist, lane, T.P);
             } else {
                 i = tpwl::nearest_wave(T, xc);
             }
@@ -429,6 +458,19 @@ int stpwl_nearest(stpwl_t *h, const double *X, int64_t B, int32_t *idx) {
     if ((rc = stpwl_nearest_dev(h, dX.as<double>(), B, dI.as<int32_t>(), nullptr))) return rc;
     SRH_CHECK_HIP(hipStreamSynchronize(nullptr));
     return dI.download(idx, sizeof(int32_t) * B);
+}
+
+int stpwl_nearest_many(stpwl_t *h, const double *X, int count, int threads, int32_t *idx) {
+    SRH_REQUIRE(h && X && idx, "stpwl_nearest_many: null argument");
+    SRH_REQUIRE(count >= 1, "stpwl_nearest_many: need count >= 1");
+    SRH_REQUIRE(threads == 256 || threads == 512, "stpwl_nearest_many: threads must be 256 or 512");
+    srh::DevBuf dX, dI;
+    int rc;
+    if ((rc = dX.upload(X, sizeof(double) * count * h->n)) || (rc = dI.alloc(sizeof(int32_t) * count))) return rc;
+    nearest_many_kernel<<<1, threads>>>(h->view(), dX.as<double>(), count, dI.as<int32_t>());
+    SRH_CHECK_HIP(hipGetLastError());
+    SRH_CHECK_HIP(hipStreamSynchronize(nullptr));
+    return dI.download(idx, sizeof(int32_t) * count);
 }
 
 int stpwl_linearize(stpwl_t *h, const double *X, int64_t B, int discrete, double *A, double *Bm, double *d,

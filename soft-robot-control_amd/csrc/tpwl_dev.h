@@ -19,13 +19,31 @@ struct TpwlDev {
 
 namespace tpwl {
 
-// argmin_i w_q ||q_i - q|| + w_v ||v_i - v||, first minimum (np.argmin), for the state x (LDS or
-// global, x = [v; q]).  Executed by ONE wave (64 lanes); every lane returns the index.
+// THE POINT-SEARCH RULE, stated once for the four places that search the table (nearest_wave; the register-table branch of nearest_many;
+// the HELD search of rollout_staged_kernel and weights_kernel in tpwl.hip):
+//   d_i = w_q ||q_i - q|| + w_v ||v_i - v||, each squared norm summed by fma in the order j = 0, 1, ... from 0.0; with w_v == 0 the
+//   velocity part of the state is not read;
+//   the nearest point is the FIRST minimum of d (np.argmin: the smallest index among the minima), and 0 when there is none -- every
+//   d_i +inf or not a number (a diverged state, a NaN of a failed solve upstream): np.argmin gives 0 there too, and the index is always
+//   one of the table's.
+// A search keeps "no candidate yet" as (+inf, index 0): only a d < +inf takes its place, so a search that ends without a candidate ends
+// with 0, and in a comparison of two of them 0 stays.  (wave_first_min below has no such pair to start from and maps its own marker.)
+
+// candidate (da, ia) goes before (db, ib): nearer, or as near with the smaller index
+__device__ __forceinline__ bool goes_before(double da, int ia, double db, int ib) { return da < db || (da == db && ia < ib); }
+// first minimum over the lanes of ONE wave, lane i holding d_i (+inf in the lanes past the table); every lane returns the index
+__device__ __forceinline__ int wave_first_min(double dist, int lane, int P) {
+    const double dmin = wg::wave_min(dist);
+    const int imin = (int)wg::wave_min(dist == dmin ? (double)lane : 1e9);        // (1e9: no lane holds the minimum -- it is not a number)
+    return imin < P ? imin : 0;
+}
+
+// The rule for the state x (LDS or global, x = [v; q]).  Executed by ONE wave (64 lanes); every lane returns the index.
 template <typename XP>
 __device__ inline int nearest_wave(const TpwlDev &T, XP x) {
     const int lane = SRH_TID & 63;
-    double best = INFINITY;
-    int besti = 0x7fffffff;
+    double best = INFINITY;                              // no candidate yet
+    int besti = 0;
     // sum_j (tab[j][i] - x[xoff + j])^2 in the order j = 0, 1, ...: sixteen table / state loads are requested before the
     // first FMA (a rolled load -> FMA loop pays the L2 latency r times per point; same sums, same order)
     auto sqdist = [&](cgptr tab, int xoff, int i) {
@@ -59,7 +77,7 @@ __device__ inline int nearest_wave(const TpwlDev &T, XP x) {
     for (int o = 32; o > 0; o >>= 1) {
         const double ob = __shfl_xor(best, o, 64);
         const int oi = __shfl_xor(besti, o, 64);
-        if (ob < best || (ob == best && oi < besti)) { best = ob; besti = oi; }
+        if (goes_before(ob, oi, best, besti)) { best = ob; besti = oi; }
     }
     return besti;
 }
@@ -95,9 +113,8 @@ __device__ inline void nearest_many(const TpwlDev &T, XP X, int ldx, int count, 
                 }
             }
             const double dist = live ? T.w_q * sqrt(sq) : INFINITY;
-            const double dmin = wg::wave_min(dist);
-            const int imin = (int)wg::wave_min(dist == dmin ? (double)lane : 1e9);        // first minimum (np.argmin)
-            if (lane == 0) idx[k] = imin < T.P ? imin : 0;          // (a state that is not a number: no minimum)
+            const int imin = wave_first_min(dist, lane, T.P);
+            if (lane == 0) idx[k] = imin;
             k = kn;
             xv = xn;
         }

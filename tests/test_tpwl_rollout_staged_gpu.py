@@ -2,7 +2,8 @@
 created under SRH_TPWL_ROLLOUT_PLAIN=1 -- X and Z bit for bit -- and against oracle.tpwl.rollout at the tolerance of
 tests/test_tpwl_gpu.py (1e-10 of the largest value).  The handles are made through the C ABI with discrete tables of the test's own, so
 that the sequence of nearest points is under the test's control; inputs are random and non-zero (zero inputs never show the order of the
-B u sums); no state is non-finite (the plain kernel has no defined index for one)."""
+B u sums); no state is non-finite (every search gives index 0 for one -- the rule of csrc/tpwl_dev.h, tested through the index-only
+entry points in tests/test_tpwl_table_exact_gpu.py; a rollout from such a state only carries the NaN on)."""
 import ctypes as C
 import os
 
