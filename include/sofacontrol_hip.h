@@ -853,6 +853,59 @@ int srompc_stats(srompc_t *h, int64_t *steps, int64_t *waits_last_step);
 int srompc_set_timing(srompc_t *h, int on);
 int srompc_last_device_ms(srompc_t *h, double *ms);
 
+/* Batched closed loop of the ROMPC baseline (csrc/rompc_loop.hip; reference rompc.py:57-141, observer.py:37-40, baselines/ros.py:202-235):
+ * every problem b of the controller handle's batch is its own loop, resident on the device, ONE host wait per run.  B members, controller
+ * step dt_sim, QP horizon N at dt_mpc, n_replan sub-steps per period (n_replan dt_sim <= N dt_mpc); period p starts at t_p = t_start +
+ * p n_replan dt_sim (sgusto_loop_schedule).
+ *   request   x0_p = x_hat0 of the reset (p = 0), else the previous plan's states interpolated at tau = n_replan dt_sim (interval
+ *             j = min(int(tau / dt_mpc), N - 1), theta = (tau - j dt_mpc) / dt_mpc); targets: the window at (t_p + phase_b) + dt_mpc k,
+ *             zf its last row when the cost has Qzf, u_des N rows
+ *   solve     the trust-region-free QP with constant (A_mpc, B_mpc, d_mpc), all members in one launch, the horizon tiled once
+ *   chain     row 0 of the plan's states <- x0_p; a member whose QP status is non-zero gets the previous plan moved up one row with its
+ *             last row held (ros.py:223-227), in period 0 x0_0 in every state row and zero inputs; the status is recorded, the loop goes on
+ *   sub-steps s = 0..n_replan-1 at tau = s dt_sim, (j_s, theta_s) of the schedule, ubar_s / xbar_s = lo + theta (hi - lo), the input held
+ *             over the last interval, ONE launch for all of them:
+ *               y_s       = (C x_s + y_ref) + v_s
+ *               u_s       = ubar_s + K (x_hat_s - xbar_s)                                             (rompc.py:79)
+ *               x_hat_s+1 = [F | B | L] [x_hat_s ; u_s ; y_s - y_ref] + d, F = A - L C                 (the constants of the srompc_t handle)
+ *               x_s+1     = A_p[i] x_s + B_p[i] u_s + d_p[i] (+ w_s), i the plant's nearest point to x_s, or read from X_plant
+ * Not offered: the start-up phase before t_delay, the full-order state and its projection, input clipping, dU rows, input_nullspace.
+ * The batch is the controller's.  The loop reads the controller's gains and model at every reset and keeps its estimate in the
+ * controller's own buffer on the loop's stream: do not step the controller elsewhere between a reset and the end of the runs that follow.
+ * create refuses (with a message): a plant whose n_x or n_u differ from the controller's, n_u > 16, n_x > 128, a QP with a trust region
+ * or dU rows or beyond the limits of slocp_plan_create, n_replan dt_sim > N dt_mpc, an advance kernel beyond 160 KiB of LDS.  The
+ * controller and the plant must outlive the loop. */
+typedef struct srompc_loop srompc_loop_t;
+/* A_mpc (n_x x n_x), B_mpc (n_x x n_u), d_mpc (n_x): the QP's model at dt_mpc; plant: pre-discretised at dt_sim */
+int srompc_loop_create(srompc_loop_t **out, srompc_t *ctrl, const slocp_problem *prob, const double *A_mpc, const double *B_mpc,
+                       const double *d_mpc, double dt_mpc, stpwl_t *plant /* NULL: replay only */, double dt_sim, int n_replan,
+                       int64_t max_steps_per_run);
+int srompc_loop_destroy(srompc_loop_t *h);
+/* t (T, increasing), z (T x n_z of the QP), u_des (T x n_u) or NULL, phase (batch) or NULL = zeros */
+int srompc_loop_set_target(srompc_loop_t *h, int T, const double *t, const double *z, const double *u_des, const double *phase);
+/* x0 (batch x n_x) plant states at the first solve, x_hat0 (batch x n_x) the estimates there */
+int srompc_loop_reset(srompc_loop_t *h, const double *x0, const double *x_hat0 /* NULL: x0 */, double t_start);
+/* `periods` periods (prepare -> solve -> chain -> advance each) on the handle's stream, the records copied back once, ONE blocking wait.
+ * W (periods x n_replan x batch x n_x), V (periods x n_replan x batch x n_y) or NULL; X_plant (batch x (S + 1) x n_x) or NULL: the plant's
+ * states are read from it (row 0 is where the run starts and is not read; W is then not used).  With S = periods n_replan: X, XH, Xbar
+ * (batch x (S + 1) x n_x), Z (batch x (S + 1) x n_z of the controller; H x without z_ref), Y (batch x S x n_y), U, Ubar (batch x S x n_u);
+ * row 0 = where the run started; the last row of Xbar is the next request's x0; J, status, iters (periods x batch). */
+int srompc_loop_run(srompc_loop_t *h, int periods, const double *W, const double *V, const double *X_plant, double *X, double *XH, double *Y,
+                    double *Z, double *U, double *Ubar, double *Xbar, double *J, int32_t *status, int32_t *iters);      /* any record may be NULL */
+/* The solver inputs / the plan (after the chain fix-up) of the last period; any may be NULL */
+int srompc_loop_last_inputs(srompc_loop_t *h, double *x0, double *z, double *zf, double *u_des);
+int srompc_loop_last_plan(srompc_loop_t *h, double *xopt, double *uopt);
+int srompc_loop_stats(srompc_loop_t *h, int64_t *steps, int64_t *waits_last_run);
+/* The chain kernel alone on host arrays: the previous plan (NULL when first), the QP's answer xopt (batch x (N+1) x n_x), uopt (batch x N
+ * x n_u), the request's x0 (batch x n_x), status (batch) -> the plan after the fix-up and x0_next (batch x n_x). */
+int srompc_loop_chain(srompc_loop_t *h, const double *xopt_prev, const double *uopt_prev, const double *xopt, const double *uopt, const double *x0,
+                      const int32_t *status, int first, double *xopt_out, double *uopt_out, double *x0_next);
+/* The advance kernel alone on host arrays: plans, x, x_hat (batch x n_x), W (n_replan x batch x n_x) / V (n_replan x batch x n_y) or NULL,
+ * X_plant (batch x (n_replan + 1) x n_x) or NULL -> after every sub-step X, XH (batch x n_replan x n_x), Z (batch x n_replan x n_z); of
+ * every sub-step Y (batch x n_replan x n_y), U, Ubar (batch x n_replan x n_u), Xbar (batch x n_replan x n_x). */
+int srompc_loop_advance(srompc_loop_t *h, const double *xopt, const double *uopt, const double *x, const double *x_hat, const double *W,
+                        const double *V, const double *X_plant, double *X, double *XH, double *Y, double *Z, double *U, double *Ubar, double *Xbar);
+
 #ifdef __cplusplus
 }
 #endif

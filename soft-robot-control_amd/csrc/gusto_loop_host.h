@@ -1,4 +1,5 @@
-// The host shell of the two closed-loop units (gusto_loop.hip: TPWL plans, gusto_ssm_loop.hip: SSM plans), stated once: the handle's
+// The host shell of the closed-loop units (gusto_loop.hip: TPWL plans, gusto_ssm_loop.hip: SSM plans, rompc_loop.hip: the chained linear
+// MPC of the ROMPC baseline), stated once: the handle's
 // common part (LoopCore), the blocks of a run that cross PCIe as a table (LoopRec), the checks and set-up of a create, the bodies of
 // set_target / last_inputs / last_plan / stats, and the skeleton of a run (loop_run_periods: capacity, staging, per period the prepare
 // kernel and the unit's own part, the copy back, ONE wait, the drain on an error).  What a unit keeps: its advance kernels, which
@@ -71,6 +72,8 @@ struct LoopCore {
     LoopRec Xrec, Zrec, Urec, Irec, Srec, Jrec, XHrec, Yrec, Wd, Vd;
     // the records in the order of their copies back, largest first: the S + 1 row blocks, the inputs, then the per-period words
     std::vector<LoopRec *> recs{&Xrec, &Zrec, &Yrec, &XHrec, &Urec, &Irec, &Srec, &Jrec};
+    // the blocks of a run that go the other way, in front of the periods: the noise, and what a unit appends (a recorded plant)
+    std::vector<LoopRec *> ins{&Wd, &Vd};
     void drain() { if (stream) (void)hipStreamSynchronize(stream); }
     ~LoopCore() {
         drain();
@@ -184,13 +187,14 @@ int loop_run_periods(LoopCore *h, const char *who, int periods, const PrepUnit &
     const size_t D = sizeof(double), B = (size_t)h->B, S = (size_t)periods * nk, P = (size_t)periods;
     SRH_REQUIRE((int64_t)S <= h->max_steps, "%s: periods * n_keep = %lld exceeds max_steps_per_run = %lld", who, (long long)S, (long long)h->max_steps);
     int rc;
-    for (LoopRec *r : {&h->Xrec, &h->Wd, &h->Vd})          // the blocks only some runs ask for
+    if (h->Xrec.host && !h->Xrec.d.p && (rc = h->alloc_recs({&h->Xrec}))) return rc;          // the blocks only some runs ask for
+    for (LoopRec *r : h->ins)
         if (r->host && !r->d.p && (rc = h->alloc_recs({r}))) return rc;
     h->waits = 0;
     hipStream_t st = h->stream;
     // from here on work is enqueued on the handle's stream: on any error it is drained before returning
     auto body = [&]() -> int {
-        for (LoopRec *r : {&h->Wd, &h->Vd})
+        for (LoopRec *r : h->ins)
             if (r->host) {
                 memcpy(r->pin.p, r->host, r->bytes(B, S, P));
                 SRH_CHECK_HIP(hipMemcpyAsync(r->d.p, r->pin.p, r->bytes(B, S, P), hipMemcpyHostToDevice, st));

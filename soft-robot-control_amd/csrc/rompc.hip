@@ -14,7 +14,7 @@
 // 16-column block of the result per wave.  A problem's row of an MFMA result depends on that row of the operand alone, so a
 // problem computes the same bits alone, inside any batch, by T steps or by one replay.  Rows of a ragged last tile are never
 // read from or written to global memory (their LDS rows stay zero).
-#include "common.h"
+#include "rompc_host.h"
 #include "dev_la.h"
 
 #include <algorithm>
@@ -165,25 +165,6 @@ inline int up4(int v) { return (v + 3) / 4 * 4; }
 
 }  // namespace
 
-struct srompc {
-    int64_t batch = 0;
-    int n = 0, m = 0, ny = 0, nz = 0;
-    bool has_H = false;
-    std::vector<double> A, B, d, C, yref, H, zref, K, L;     // host copies: the fold is redone when the gains change
-    int n4 = 0, m4 = 0, ny4 = 0, ld1 = 0, ldk = 0, nconst = 0;
-    size_t lds = 0;
-    srh::DevBuf consts, in, res, xfull;
-    size_t in_doubles = 0, res_doubles = 0, xfull_doubles = 0;
-    double *pin_in = nullptr, *pin_out = nullptr, *pin_xf = nullptr;
-    hipStream_t stream = nullptr;
-    int64_t steps = 0, step_waits = 0;
-    bool timing = false;
-    hipEvent_t ev[2] = {nullptr, nullptr};      // first enqueue .. last copy of a call, when timing is on
-    double last_ms = -1.0;
-    double *est() const { return res.as<double>() + (size_t)batch * m; }            // res = [u | x_hat | z]
-    double *zres() const { return res.as<double>() + (size_t)batch * (m + n); }
-};
-
 // pack [F B L], K, Hz, d, y_ref, z_ref and send them to the device (blocking: set-up path)
 static int rompc_upload_consts(srompc *h) {
     const int n = h->n, m = h->m, ny = h->ny, nz = h->nz, ld1 = h->ld1, ldk = h->ldk;
@@ -191,9 +172,7 @@ static int rompc_upload_consts(srompc *h) {
     double *M1 = c.data(), *Kp = M1 + (size_t)n * ld1, *Hz = Kp + (size_t)m * ldk, *dv = Hz + (size_t)nz * ldk, *yr = dv + n, *zr = yr + ny;
     for (int i = 0; i < n; ++i) {
         for (int j = 0; j < n; ++j) {
-            double f = h->A[(size_t)i * n + j];
-            for (int k = 0; k < ny; ++k) f -= h->L[(size_t)i * ny + k] * h->C[(size_t)k * n + j];
-            M1[(size_t)i * ld1 + j] = f;
+            M1[(size_t)i * ld1 + j] = h->fold(i, j);
         }
         for (int j = 0; j < m; ++j) M1[(size_t)i * ld1 + h->n4 + j] = h->B[(size_t)i * m + j];
         for (int j = 0; j < ny; ++j) M1[(size_t)i * ld1 + h->n4 + h->m4 + j] = h->L[(size_t)i * ny + j];
