@@ -108,6 +108,11 @@ int srom_reduce_matrices_dev(srom_t *h, const double *const *M_dev, int count, d
 int srom_gramian_dev(const double *S_dev, int64_t n_s, int64_t n_f, int64_t lds, double *G_dev,
                      void *stream);
 int srom_gramian(const double *S, int64_t n_s, int64_t n_f, double *G);
+/* The launch srom_gramian_dev makes for this shape on a card of `cus` compute units (cus <= 0: ask the current device; with
+ * cus > 0 a host function, no GPU needed): ntile = 128 x 128 tiles per side (only the ntile (ntile + 1) / 2 on or above the
+ * diagonal are computed), nfull = tiles computed whole, ntail = tiles of a partial last round that are split ksplit ways
+ * along K and summed in part order (0: none, ksplit = 1); nfull + ntail = all tiles.  Any output pointer may be NULL. */
+int srom_gramian_plan(int64_t n_s, int64_t n_f, int cus, int *ntile, int *nfull, int *ntail, int *ksplit);
 /* process_snapshots (pod.py:157-178) on a resident snapshot matrix S (n_s x n_f, one snapshot per row, row pitch lds >= n_f).
  * Column statistics over the snapshots (each output n_f doubles on the device, any of them may be NULL):
  * min / max for 'normalize' (pod.py:165), mean for 'substract_mean' (pod.py:168). */
@@ -132,20 +137,27 @@ int srom_kmeans_lloyd_dev(const double *S_dev, int64_t n_s, int64_t n_f, int64_t
                           double tol, int32_t *labels_dev, double *inertia_out, int *iters_out, void *stream);
 /* eigh of the (symmetric) Gramian in place on the device (cyclic Jacobi kernels up to n = 2048, rocSOLVER dsyevd
  * above): on return row j of G_dev is
- * the eigenvector of the j-th smallest eigenvalue, w_dev (n) ascending.  Replaces the SVD of pod.py:190. */
+ * the eigenvector of the j-th smallest eigenvalue, w_dev (n) ascending.  Replaces the SVD of pod.py:190.
+ * n <= 128: a Gramian whose null space stalls the sweeps (rank far below n) is finished with the pairs of its null cluster --
+ * entries at or below n eps |diag| -- left alone; eigenvalues there are rounding noise of either sign. */
 int srom_eigh_dev(double *G_dev, int64_t n, double *w_dev, void *stream);
 /* The k LARGEST eigenpairs of the symmetric positive semidefinite G (n x n, left untouched) by blocked subspace iteration +
  * Rayleigh-Ritz (block = k + oversample <= 128; oversample < 0: max(16, k / 2)) -- what compute_POD keeps of the SVD
  * (pod.py:190-200) without the other n - k singular values: w_dev (k) descending; Wk_dev (n x k) = eigenvector columns
  * scaled by 1 / sqrt(w_i) (the input of srom_modes_dev) or NULL; Vt_dev (k x n) = eigenvector rows or NULL; *trace_out
  * = trace(G) (the truncation rule's denominator: tail energy = trace - sum w); *iters_out = subspace iterations until the
- * leading k eigenvalues settled to 1e-13 (<= 30), or 31 when they did not (no gap behind the block: take srom_eigh_dev). */
+ * leading k eigenvalues settled to 1e-13 (<= 30), or 31 when they did not (no gap behind the block: take srom_eigh_dev).
+ * k beyond the numerical rank: a column of Wk whose w_i <= 1e-28 w_0 or w_i <= 0 is zero (no division by a vanished sigma). */
 int srom_eigh_topk_dev(const double *G_dev, int64_t n, int k, int oversample, double *w_dev, double *Wk_dev,
                        double *Vt_dev, double *trace_out, int *iters_out, void *stream);
-/* W_k (n x k, row-major) = the k leading eigenvectors as columns, scaled by 1/sigma_i = 1/sqrt(w_i) */
+/* W_k (n x k, row-major) = the k leading eigenvectors as columns, scaled by 1/sigma_i = 1/sqrt(w_i); V_dev, w_dev as
+ * srom_eigh_dev leaves them (eigenvector rows, w ascending).  k beyond the numerical rank: a column whose w_i lies at or below
+ * the rounding noise of the eigensolver, w_i <= max(1e-28, n eps) w_max, or w_i <= 0, is zero, and so is that column of
+ * U = S^T W_k (no inf / NaN from a vanished sigma, no mode made of noise). */
 int srom_select_modes_dev(const double *V_dev, const double *w_dev, int64_t n, int k, double *Wk_dev,
                           void *stream);
-/* U_k = S^T W_k  (n_f x k) for eigenvector columns W_k (n_s x k, already scaled by 1/sigma). */
+/* U_k = S^T W_k  (n_f x k) for eigenvector columns W_k (n_s x k, already scaled by 1/sigma).  Needs 0 < k <= 64, n_s > 0,
+ * n_f > 0 and a row pitch lds >= n_f of S. */
 int srom_modes_dev(const double *S_dev, int64_t n_s, int64_t n_f, int64_t lds, const double *W_dev,
                    int k, double *U_dev, void *stream);
 

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "abt_dev.h"
+#include "mode_rule.h"
 
 extern "C" int srom_eigh_dev(double *G_dev, int64_t n, double *w_dev, void *stream);
 
@@ -53,13 +54,13 @@ __global__ __launch_bounds__(256) void wz_kernel(const double *__restrict__ Wm, 
 
 // from the eigen-decomposition of a b x b matrix (rows of V = eigenvectors, w ascending): Wm[i][:] = s_i V[b-1-i][:], i-th
 // LARGEST first; s_i = 1 / sqrt(w) (scale = 1: orthonormalisation through M = Z Z^T) or 1 (scale = 0: Ritz rotation).
-// est[i] = sqrt(w) (scale = 1) or w (scale = 0).  Directions whose eigenvalue has cancelled to nothing get a zero row.
+// est[i] = sqrt(w) (scale = 1) or w (scale = 0).  Directions whose eigenvalue has cancelled to nothing get a zero row (mode_rule.h).
 __global__ void build_w_kernel(const double *__restrict__ V, const double *__restrict__ w, int b, int scale, double *__restrict__ Wm,
                                double *__restrict__ est) {
     const int i = blockIdx.x, src = b - 1 - i;
     const double wi = w[src], wmax = w[b - 1];
     double s = 1.0;
-    if (scale) s = wi > 1e-28 * wmax && wi > 0.0 ? 1.0 / sqrt(wi) : 0.0;
+    if (scale) s = mode_is_live(wi, wmax) ? 1.0 / sqrt(wi) : 0.0;
     for (int l = threadIdx.x; l < b; l += blockDim.x) Wm[(size_t)i * b + l] = s * V[(size_t)src * b + l];
     if (threadIdx.x == 0) est[i] = scale ? sqrt(fmax(wi, 0.0)) : wi;
 }
@@ -90,12 +91,13 @@ __global__ void trace_kernel(const double *__restrict__ G, int64_t n, double *__
     if (threadIdx.x == 0) out[0] = red[0];
 }
 
-// Wk[j][i] = Vt[i][j] / sqrt(w_i)   (n x k, the layout srom_modes_dev takes)
+// Wk[j][i] = Vt[i][j] / sqrt(w_i)   (n x k, the layout srom_modes_dev takes; w descending), a zero column where w_i has cancelled to
+// nothing (mode_rule.h)
 __global__ void scale_cols_kernel(const double *__restrict__ Vt, const double *__restrict__ w, int64_t n, int k, double *__restrict__ Wk) {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int i = blockIdx.y;
     if (j >= n) return;
-    Wk[j * k + i] = Vt[(int64_t)i * n + j] / sqrt(fmax(w[i], 0.0));
+    Wk[j * k + i] = mode_is_live(w[i], w[0]) ? Vt[(int64_t)i * n + j] / sqrt(w[i]) : 0.0;
 }
 
 

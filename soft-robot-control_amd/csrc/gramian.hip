@@ -177,41 +177,72 @@ __global__ __launch_bounds__(256) void modes_kernel(const double *__restrict__ S
     }
 }
 
+// The launch of srom_gramian_dev on a card of `cus` compute units, stated once (srom_gramian_plan reports it).  Two workgroups of
+// gramian_kernel are resident per CU: when the last round of the launch is less than half full, its tiles are split along K so
+// that the tail costs a fraction of a round.
+struct GramPlan { int ntile, nfull, ntail, ksplit; };
+
+GramPlan gramian_plan(int64_t n_s, int64_t n_f, int cus) {
+    const int slots = 2 * cus;
+    const int ntile = (int)srh::cdiv(n_s, TB);
+    const int64_t nblk = (int64_t)ntile * (ntile + 1) / 2;
+    const int64_t nchunk = srh::cdiv(n_f, KC);
+    const int rem = (int)(nblk % slots);
+    GramPlan p{ntile, (int)nblk, 0, 1};
+    if (nblk > slots && rem > 0 && 2 * rem <= slots && nchunk >= 64) {
+        p.ksplit = std::min(8, slots / rem);
+        p.ntail = rem;
+        p.nfull = (int)nblk - rem;
+    }
+    return p;
+}
+
+// compute units of the current device (asked once; 256 where the runtime does not say)
+int device_cus(int *out) {
+    static int cus = 0;
+    if (cus == 0) {
+        int dev = 0, n = 0;
+        SRH_CHECK_HIP(hipGetDevice(&dev));
+        SRH_CHECK_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
+        cus = n > 0 ? n : 256;
+    }
+    *out = cus;
+    return SRH_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
+int srom_gramian_plan(int64_t n_s, int64_t n_f, int cus, int *ntile, int *nfull, int *ntail, int *ksplit) {
+    SRH_REQUIRE(n_s > 0 && n_f > 0, "srom_gramian_plan: bad dimensions");
+    if (cus <= 0) {
+        int rc = device_cus(&cus);
+        if (rc) return rc;
+    }
+    const GramPlan p = gramian_plan(n_s, n_f, cus);
+    if (ntile) *ntile = p.ntile;
+    if (nfull) *nfull = p.nfull;
+    if (ntail) *ntail = p.ntail;
+    if (ksplit) *ksplit = p.ksplit;
+    return SRH_OK;
+}
+
 int srom_gramian_dev(const double *S_dev, int64_t n_s, int64_t n_f, int64_t lds, double *G_dev, void *stream) {
     SRH_REQUIRE(S_dev && G_dev, "srom_gramian_dev: null argument");
     SRH_REQUIRE(n_s > 0 && n_f > 0 && lds >= n_f, "srom_gramian_dev: bad dimensions");
-    const int ntile = (int)srh::cdiv(n_s, TB);
-    const int64_t nblk = (int64_t)ntile * (ntile + 1) / 2;
+    int cus = 0, rc = device_cus(&cus);
+    if (rc) return rc;
+    const GramPlan pl = gramian_plan(n_s, n_f, cus);
+    const int ntile = pl.ntile, nfull = pl.nfull, ntail = pl.ntail, ksplit = pl.ksplit;
     const size_t lbytes = sizeof(double) * 4 * KC * LDT;
-    // two workgroups of this kernel are resident per CU: when the last round of the launch is less than half
-    // full, its tiles are split along K so that the tail costs a fraction of a round
-    static int slots = 0;
     static srh::DevBuf scratch;
     static size_t scratch_bytes = 0;
-    if (slots == 0) {
-        int dev = 0, cus = 0;
-        SRH_CHECK_HIP(hipGetDevice(&dev));
-        SRH_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        slots = 2 * (cus > 0 ? cus : 256);
-    }
-    const int64_t nchunk = srh::cdiv(n_f, KC);
-    const int rem = (int)(nblk % slots);
-    int ksplit = 1, ntail = 0;
-    if (nblk > slots && rem > 0 && 2 * rem <= slots && nchunk >= 64) {
-        ksplit = std::min(8, slots / rem);
-        ntail = rem;
-    }
-    const int nfull = (int)nblk - ntail;
     if (ntail > 0) {
         const size_t need = sizeof(double) * (size_t)ntail * ksplit * TB * TB;
         if (need > scratch_bytes) {
             SRH_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
-            int rc = scratch.alloc(need);
-            if (rc) return rc;
+            if ((rc = scratch.alloc(need))) return rc;
             scratch_bytes = need;
         }
     }
@@ -240,6 +271,7 @@ int srom_modes_dev(const double *S_dev, int64_t n_s, int64_t n_f, int64_t lds, c
                    void *stream) {
     SRH_REQUIRE(S_dev && W_dev && U_dev, "srom_modes_dev: null argument");
     SRH_REQUIRE(k > 0 && k <= 64, "srom_modes_dev: need 0 < k <= 64");
+    SRH_REQUIRE(n_s > 0 && n_f > 0 && lds >= n_f, "srom_modes_dev: bad dimensions");
     modes_kernel<<<(unsigned)srh::cdiv(n_f, 64), 256, sizeof(double) * 64 * k, (hipStream_t)stream>>>(S_dev, n_s, n_f, lds, W_dev, k, U_dev);
     SRH_CHECK_HIP(hipGetLastError());
     return SRH_OK;

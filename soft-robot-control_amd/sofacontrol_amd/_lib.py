@@ -197,6 +197,16 @@ def tpwl_rollout_plan(h, N, batch):
     return {'staged': bool(staged.value), 'held': bool(held.value), 'lds_bytes': int(lds.value)}
 
 
+def gramian_plan(n_s, n_f, cus=0):
+    """srom_gramian_plan: the launch srom_gramian_dev makes for an n_s x n_f snapshot matrix (csrc/gramian.hip) on a card of `cus`
+    compute units -- cus = 0 asks the current device, cus > 0 is answered on the host, no GPU needed.  {'ntile': 128-row tiles per
+    side, 'nfull': tiles computed whole, 'ntail': tiles of the partial last round split along K, 'ksplit': parts per such tile}."""
+    ntile, nfull, ntail, ksplit = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+    check(lib().srom_gramian_plan(C.c_int64(n_s), C.c_int64(n_f), C.c_int(cus), C.byref(ntile), C.byref(nfull), C.byref(ntail),
+                                  C.byref(ksplit)), 'srom_gramian_plan')
+    return {'ntile': ntile.value, 'nfull': nfull.value, 'ntail': ntail.value, 'ksplit': ksplit.value}
+
+
 IPM_PHASES = ('init', 'cold', 'warm', 'pred', 'corr', 'direction', 'affine', 'advance', 'scales', 'verdict')
 
 

@@ -320,7 +320,11 @@ def modes_from_gramian(S_rows, G, tol, rom_dim=None, eigh=None):
     W = W[:, ::-1]
     Sigma = np.sqrt(w)
     k = energy_truncation(Sigma, tol) if rom_dim is None else int(rom_dim)
-    Wk = np.ascontiguousarray(W[:, :k] / Sigma[:k])
+    # csrc/mode_rule.h: an eigenvalue at or below the rounding noise of the eigensolver, n eps w_max (rom_dim beyond the numerical
+    # rank), gives a zero column
+    live = (w[:k] > max(1e-28, len(w) * np.finfo(np.float64).eps) * w[0]) & (w[:k] > 0.0)
+    Wk = np.zeros((W.shape[0], k))
+    Wk[:, live] = W[:, :k][:, live] / Sigma[:k][live]
     return Wk, k, Sigma
 
 
