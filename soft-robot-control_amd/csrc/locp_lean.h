@@ -758,7 +758,9 @@ __device__ long long g_prof_waves[16];         // per-wave clocks of the Gram fi
 // copied into it once (g.gt == L.B, from gsrc) and the tiles read them from LDS instead of once per tile row and column they meet
 // from L2.  The tiles walk the stages in the same ascending order: same bits.  An epilogue must not write a tile into L.B while
 // another wave still reads staged rows there: the accumulators of ALL tiles of a wave stay in registers (GRAM_SLOTS tasks of at most
-// 4, 3, 1 tiles: 8 accumulators), one barrier, then the epilogues.  Register arrays want compile-time indices, so the tasks are not
+// 4, 3, 1 tiles: 8 accumulators) THROUGH the epilogues, which touch registers, L.Ls and L.ks only; one barrier ("every wave has read its
+// last staged row" and "L.ks is complete" at once), then each tile is stored once, already scaled -- no raw tile in L.B, no scaling pass
+// over the 28 tiles, one barrier less per fill.  Register arrays want compile-time indices, so the tasks are not
 // pulled here: c.gram_sched is the static table [wave][slot] of scp_host.h:lean_gram_slots.
 // STAGE with gtoep != null (wave-uniform; the packed G is the expansion of the Toeplitz generators g_b, ql::condense_single): operand
 // element (j, b, i) of the packed rows is g_b[i - 2 j].  The four vectors are staged instead of the rows -- each behind TOEP_FRONT zeros,
@@ -778,7 +780,7 @@ __device__ __forceinline__ void gram_t(const QPDims &d, const QPConst &c, const 
     const int goff0 = goff(g.j0, M, NP);
     lptr w2 = L.tc;                                            // 1 / D per packed row
 #ifdef SRH_PROFILE
-    long long gl[6] = {0, 0, 0, 0, 0, 0}, g0 = clock64(), g1;   // 1/D pass + barrier, descriptors, products, epilogue, barrier, scaling + barrier  (wave 0 -> L.Qu[4..7], L.Qu[13..14])
+    long long gl[6] = {0, 0, 0, 0, 0, 0}, g0 = clock64(), g1;   // 1/D pass + barrier, descriptors, products, epilogue, barrier, scaling + barrier (STAGE: scaled store + barrier)  (wave 0 -> L.Qu[4..7], L.Qu[13..14])
 #define GR_LAP(i) do { g1 = clock64(); gl[i] += g1 - g0; g0 = g1; } while (0)
 #else
 #define GR_LAP(i) ((void)0)
@@ -887,8 +889,10 @@ __device__ __forceinline__ void gram_t(const QPDims &d, const QPConst &c, const 
     // (the factors of the rows are the same for every tile of the task; the row r ^ 1 of an output stage sits in the neighbouring
     // row of 16 lanes: wg::xor16, two v_permlane16_swap instead of a ds_bpermute round trip; the scale factors of the Jacobi
     // scaling only where the tile is a diagonal one -- round 5: 13 k of the 40 k clocks of a Gram fill were this epilogue)
-    auto epilogue = [&](int I, int J0, int nJ, auto BASE, auto CAP) {
+    // STORE false (the staged fill): the finished raw tile stays in its accumulator -- registers, L.Ls and L.ks only, nothing goes to L.B
+    auto epilogue = [&](int I, int J0, int nJ, auto BASE, auto CAP, auto STORE) {
         constexpr int base = decltype(BASE)::value, cap = decltype(CAP)::value;
+        constexpr bool store = decltype(STORE)::value;
         double la0[4], la2[4], la3[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -919,8 +923,26 @@ __device__ __forceinline__ void gram_t(const QPDims &d, const QPConst &c, const 
                     const double ri = qpc::rsq3(dg ? v : 1.0);
                     if (dg) L.ks[gi] = ri;
                 }
-                T[r * TS + l16] = v;
+                if constexpr (store) T[r * TS + l16] = v;
+                else acc[base + t][q] = v;
             }
+        }
+    };
+    // ---- the staged fill's store: the tiles a wave kept in registers go to L.B once, already scaled to a unit diagonal -- the two
+    // multiplications of the scaling pass below in its association (T *= ks_I[r] * sc), behind the barrier that publishes L.ks
+    auto store_scaled = [&](int I, int J0, int nJ, auto BASE, auto CAP) {
+        constexpr int base = decltype(BASE)::value, cap = decltype(CAP)::value;
+        double ki[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) ki[q] = L.ks[16 * I + kk + 4 * q];
+#pragma unroll
+        for (int t = 0; t < cap; ++t) {
+            if (t >= nJ) continue;
+            const int J = J0 + t;
+            lptr T = L.B + (size_t)qpc::tile_index(I, J, KT) * TSZ;
+            const double sc = L.ks[16 * J + l16];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) T[(kk + 4 * q) * TS + l16] = acc[base + t][q] * (ki[q] * sc);
         }
     };
     constexpr std::integral_constant<int, 0> B0{};
@@ -939,8 +961,21 @@ __device__ __forceinline__ void gram_t(const QPDims &d, const QPConst &c, const 
             for (int t = 0; t < 4; ++t) acc[t] = {0.0, 0.0, 0.0, 0.0};
             products(I, J0, nJ, B0, C4, std::false_type{});
             GR_LAP(2);
-            epilogue(I, J0, nJ, B0, C4);
+            epilogue(I, J0, nJ, B0, C4, std::true_type{});
             GR_LAP(3);
+        }
+        __syncthreads();
+        GR_LAP(4);
+        // ---- symmetric scaling to a unit diagonal (see qpc::gram for why it matters): the upper tiles over the waves
+        for (int t = wave, I = 0, rowlen = KT; t < KT * (KT + 1) / 2; t += nt >> 6) {
+            int tt = t;
+            I = 0; rowlen = KT;
+            while (tt >= rowlen) { tt -= rowlen; ++I; --rowlen; }
+            const int J = I + tt;
+            lptr T = L.B + (size_t)qpc::tile_index(I, J, KT) * TSZ;
+            const double sc = L.ks[16 * J + l16];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { const int r = kk + 4 * q; T[r * TS + l16] *= L.ks[16 * I + r] * sc; }
         }
     } else {
         constexpr std::integral_constant<int, 4> B1{};
@@ -966,25 +1001,15 @@ __device__ __forceinline__ void gram_t(const QPDims &d, const QPConst &c, const 
             if (sn[2] > 0) products(sI[2], sJ[2], sn[2], B2, C1, std::false_type{});
         }
         GR_LAP(2);
-        __syncthreads();                                       // every wave has read its last staged row: L.B takes the tiles
-        GR_LAP(4);
-        if (sn[0] > 0) epilogue(sI[0], sJ[0], sn[0], B0, C4);
-        if (sn[1] > 0) epilogue(sI[1], sJ[1], sn[1], B1, C3);
-        if (sn[2] > 0) epilogue(sI[2], sJ[2], sn[2], B2, C1);
+        if (sn[0] > 0) epilogue(sI[0], sJ[0], sn[0], B0, C4, std::false_type{});
+        if (sn[1] > 0) epilogue(sI[1], sJ[1], sn[1], B1, C3, std::false_type{});
+        if (sn[2] > 0) epilogue(sI[2], sJ[2], sn[2], B2, C1, std::false_type{});
         GR_LAP(3);
-    }
-    __syncthreads();
-    GR_LAP(4);
-    // ---- symmetric scaling to a unit diagonal (see qpc::gram for why it matters): the upper tiles over the waves
-    for (int t = wave, I = 0, rowlen = KT; t < KT * (KT + 1) / 2; t += nt >> 6) {
-        int tt = t;
-        I = 0; rowlen = KT;
-        while (tt >= rowlen) { tt -= rowlen; ++I; --rowlen; }
-        const int J = I + tt;
-        lptr T = L.B + (size_t)qpc::tile_index(I, J, KT) * TSZ;
-        const double sc = L.ks[16 * J + l16];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { const int r = kk + 4 * q; T[r * TS + l16] *= L.ks[16 * I + r] * sc; }
+        __syncthreads();                                       // every wave has read its last staged row and published its part of L.ks: L.B takes the tiles
+        GR_LAP(4);
+        if (sn[0] > 0) store_scaled(sI[0], sJ[0], sn[0], B0, C4);
+        if (sn[1] > 0) store_scaled(sI[1], sJ[1], sn[1], B1, C3);
+        if (sn[2] > 0) store_scaled(sI[2], sJ[2], sn[2], B2, C1);
     }
     __syncthreads();
     GR_LAP(5);
@@ -2045,11 +2070,15 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
             if (half_of_wave(wv) == 0) tile_cholesky_set(d, L, W, L.flag + 5, L.flag + 3);
             else newton_front<MSEL, true>(d, g, L, gyd, W, pf, ya_const && mode == PRED);
             __syncthreads();
+#ifdef SRH_PROFILE
+            for (int i = 0; i < 5; ++i) prof[27 + i] += (long long)L.Qu[8 + i];
+#endif
             ok = L.flag[1] != 0;
             if (tid < 5) L.flag[3 + tid] = 0;
             if (gyd) rd = L.Qu[0];
-            if (ok) unit_tiles(d, L);
             Q4_LAP(5);
+            if (ok) unit_tiles(d, L);
+            Q4_LAP(32);                                        // (unit_tiles and its barrier alone; the factorisation up to the join is lap 5)
             if (ok) newton_back<MSEL>(d, g, L, pf);
         } else {
             newton_solve<MSEL>(d, g, L, (clptr) nullptr, &rd, pf, ya_const);
@@ -2132,7 +2161,7 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
     prof[24] += it; prof[25] += 1; prof[26] += warm ? 1 : 0;
     if (tid == 0 && blockIdx.x == 0) {
         printf("lean condense (this QP): mode %d clocks %lld interior-point iterations %d status %d\n", cond_mode, cond_clk, it, status);
-        printf("lean gram laps (this QP, wave 0, %d fills): 1/D+staging+barrier %.0f descriptors %.0f products %.0f epilogue %.0f barrier %.0f scaling+barrier %.0f\n",
+        printf("lean gram laps (this QP, wave 0, %d fills): 1/D+staging+barrier %.0f descriptors %.0f products %.0f epilogue A %.0f barrier %.0f store+barrier %.0f\n",
                ngram, L.Qu[4], L.Qu[5], L.Qu[6], L.Qu[7], L.Qu[13], L.Qu[14]);
         printf("lean gram per wave (cumulative) products:");
         for (int i = 0; i < 4; ++i) printf(" %lld", g_prof_waves[i]);

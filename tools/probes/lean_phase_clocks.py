@@ -62,7 +62,7 @@ def child(N, dt, with_X, cap):
                                     'ms_per_scp_iteration_median': sorted(t / max(1, i) for t, i in zip(ts, its))[reps // 2] * 1e3}), flush=True)
 
 
-LINE = re.compile(r'^lean (gusto clocks|qp laps|newton laps|step laps|qp tail|split)')
+LINE = re.compile(r'^lean (gusto clocks|qp laps|newton laps|step laps|qp tail|split|factor chain|unit tiles)')
 GRAM = re.compile(r'^lean gram laps \(this QP, wave 0(?:, (\d+) fills)?\): (.*)$')
 WAVES = re.compile(r'^lean gram per wave \(cumulative\) products:((?: \d+)+)  epilogue:((?: \d+)+)')
 
