@@ -10,14 +10,6 @@
 
 namespace {
 
-typedef double loop_d2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void panel_copy16(lptr dst, cgptr src, int count) {            // count even, both 16-byte aligned
-    auto d2 = (__attribute__((address_space(3))) loop_d2 *)dst;
-    auto s2 = (const __attribute__((address_space(1))) loop_d2 *)src;
-    for (int e = threadIdx.x; e < (count >> 1); e += blockDim.x) d2[e] = s2[e];
-}
-
 struct AdvArgs {
     int N, n_keep, nz;
     const double *xopt, *uopt;          // the plans (B x (N+1) x n), (B x N x m)
@@ -42,8 +34,8 @@ struct AdvArgs {
 // One workgroup per rollout, all n_keep sub-steps.  The plant's region panel [A_d^T | B_d^T | d_d] sits in LDS and is reloaded only when
 // the plant's nearest point changes (as rollout_staged_kernel, tpwl.hip); the state, the plan point x_bar and x - x_bar stay in LDS
 // for the whole launch.  Per sub-step: waves 0-2 interpolate the plan; wave 0 searches the plant's table at x while wave 1 searches the
-// planner's at x_bar (tpwl::nearest_wave both: one tie rule); the four waves form K (x - x_bar) a row each; the products of the step are
-// wg::matTvec's slices (slice s sums rows s, s + S, ... by fma from 0.0; x' = d + partials of A x in slice order + partials of B u).
+// planner's at x_bar (tpwl::nearest_wave both: one tie rule); the four waves form K (x - x_bar) a row each; the plant step is THE STEP
+// RULE of tpwl_dev.h, plan points, z and y the rules of gusto_loop_prep.h.
 // OBS: the observed loop's sub-step.  The law reads the filter's estimate x_hat in place of x, and the sub-step ends with the measurement
 // y = C x' + y_ref (+ v).  The filter itself is another kernel (512 threads, up to 160 KB of LDS), so a launch then covers one sub-step
 // and the region panel is loaded per launch.
@@ -56,13 +48,9 @@ __global__ __launch_bounds__(256) void loop_advance_kernel(TpwlDev TP, TpwlDev T
     lptr dx = xb + n;                                    // n      x - x_bar
     lptr ub = dx + n;                                    // 16     u_bar
     lptr uc = ub + 16;                                   // 16     u
-    lptr pa = uc + 16;                                   // 256    partial sums of A x
-    lptr pb = pa + 256;                                  // 256    partial sums of B u
-    liptr ip = (liptr)(pb + 256);                        // (two doubles) plant point, gain point
-    lptr At = pb + 256 + 2;                              // n x n  the panel of region `cur`: every offset is even (n = 2 r)
-    lptr Bt = At + n * n;                                // m x n
-    lptr dl = Bt + m * n;                                // n
-    lptr xh = dl + n;                                    // n      OBS: the estimate
+    tpwl::StepLds L;                                     //        partial sums, (two doubles) plant point and gain point, the panel of region `cur`
+    lptr xh = tpwl::step_carve(L, uc + 16, n, m, 256, 2);        // n      OBS: the estimate
+    liptr ip = (liptr)(L.pb + 256);
     clptr xl = OBS ? xh : xc;                            //        what the law reads
     const size_t b = blockIdx.x;
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -79,14 +67,11 @@ __global__ __launch_bounds__(256) void loop_advance_kernel(TpwlDev TP, TpwlDev T
         const int js = jsg[s];
         const double th = thg[s];
         if (tid < n) {                                   // (n <= 128: waves 0 and 1)
-            const double lo = xo[(size_t)js * n + tid], hi = xo[(size_t)(js + 1) * n + tid];
-            const double v = lo + th * (hi - lo);
+            const double v = plan_at(xo, n, js, js + 1, th, tid);
             xb[tid] = v;
             dx[tid] = xl[tid] - v;
         } else if (tid >= 128 && tid < 128 + m) {        // the input is held over the last interval (controllers.py:299)
-            const int e = tid - 128;
-            const double lo = uo[(size_t)js * m + e], hi = uo[(size_t)min(js + 1, N - 1) * m + e];
-            ub[e] = lo + th * (hi - lo);
+            ub[tid - 128] = plan_at(uo, m, js, min(js + 1, N - 1), th, tid - 128);
         }
         __syncthreads();
         if (wave == 0) {
@@ -98,12 +83,7 @@ __global__ __launch_bounds__(256) void loop_advance_kernel(TpwlDev TP, TpwlDev T
         }
         __syncthreads();
         const int p = ip[0];
-        if (p != cur) {                                  // (the same for every thread; the barrier below covers the copies)
-            panel_copy16(At, TL.AdT + (size_t)p * n * n, n * n);
-            panel_copy16(Bt, TL.BdT + (size_t)p * m * n, m * n);
-            panel_copy16(dl, TL.dd + (size_t)p * n, n);
-            cur = p;
-        }
+        tpwl::panel_load(L, TL, p, cur, n, m, tid, blockDim.x);            // (the same for every thread; the barrier below covers the copies)
         if (Kt != nullptr) {
             cgptr Kg = Kt + (size_t)ip[1] * m * n;
             for (int e = wave; e < m; e += 4) {
@@ -116,19 +96,10 @@ __global__ __launch_bounds__(256) void loop_advance_kernel(TpwlDev TP, TpwlDev T
             uc[tid] = ub[tid];
         }
         __syncthreads();
-        if (sl < S) {
-            double va = 0.0, vb = 0.0;
-#pragma unroll 4
-            for (int q = sl; q < n; q += S) va = fma(At[q * n + j], xc[q], va);
-            for (int q = sl; q < m; q += S) vb = fma(Bt[q * n + j], uc[q], vb);
-            pa[sl * n + j] = va;
-            pb[sl * n + j] = vb;
-        }
+        tpwl::step_slices(L, xc, uc, n, m, S, j, sl);
         __syncthreads();
         if (tid < n) {
-            double v = dl[tid];
-            for (int q = 0; q < S; ++q) v += pa[q * n + tid];
-            for (int q = 0; q < S; ++q) v += pb[q * n + tid];
+            double v = tpwl::step_sum(L, n, S, tid);
             if (Wd != nullptr) v += Wd[((size_t)(a.w_step0 + s) * a.B + b) * n + tid];
             xc[tid] = v;
             if (a.X) ((gptr)a.X)[(b * (size_t)a.rows_x + a.row0_x + s) * n + tid] = v;
@@ -139,21 +110,13 @@ __global__ __launch_bounds__(256) void loop_advance_kernel(TpwlDev TP, TpwlDev T
             if (a.ig) a.ig[b * a.n_keep + s] = Kt != nullptr ? ip[1] : -1;
         }
         __syncthreads();
-        // z = H x, the sum of gusto_write_out (zopt = H xopt).  xc is next written behind two barriers of the next sub-step.
-        for (int e = tid; e < nz; e += 256) {
-            double v = 0.0;
-            for (int c = 0; c < n; ++c) v = fma(H[e * n + c], xc[c], v);
-            ((gptr)a.Z)[(b * (size_t)a.rows_x + a.row0_x + s) * nz + e] = v;
-        }
+        // z = H x.  xc is next written behind two barriers of the next sub-step.
+        for (int e = tid; e < nz; e += 256) ((gptr)a.Z)[(b * (size_t)a.rows_x + a.row0_x + s) * nz + e] = out_row(H, e, n, xc);
         if (OBS) {
             cgptr Cg = (cgptr)a.C, yr = (cgptr)a.y_ref, Vn = (cgptr)a.Vn;
-            for (int e = tid; e < a.ny; e += 256) {
-                double v = 0.0;
-                for (int c = 0; c < n; ++c) v = fma(Cg[e * n + c], xc[c], v);
-                if (yr != nullptr) v += yr[e];
-                if (Vn != nullptr) v += Vn[((size_t)(a.w_step0 + s) * a.B + b) * a.ny + e];
-                ((gptr)a.Y)[(b * (size_t)a.rows_u + a.row0_u + s) * a.ny + e] = v;
-            }
+            for (int e = tid; e < a.ny; e += 256)
+                ((gptr)a.Y)[(b * (size_t)a.rows_u + a.row0_u + s) * a.ny + e] =
+                    measure_row(Cg, e, n, xc, yr, Vn, ((size_t)(a.w_step0 + s) * a.B + b) * a.ny + e);
         }
     }
     if (a.x_out)
@@ -161,7 +124,7 @@ __global__ __launch_bounds__(256) void loop_advance_kernel(TpwlDev TP, TpwlDev T
 }
 
 size_t advance_lds_bytes(int n, int m, bool observed) {
-    return srh::lds_request(sizeof(double) * ((size_t)3 * n + 16 + 16 + 256 + 256 + 2 + (size_t)n * n + (size_t)m * n + n + (observed ? n : 0)));
+    return srh::lds_request(sizeof(double) * ((size_t)3 * n + 16 + 16 + 2 + tpwl::step_doubles(n, m, 256) + (observed ? n : 0)));
 }
 
 // After a batched filter step: the estimates into row `row` of the record (B x rows x n), and the filters' status words into the

@@ -1,13 +1,38 @@
-// The device side of what the two closed-loop units (gusto_loop.hip: TPWL plans, gusto_ssm_loop.hip: SSM plans) share, stated once: the
-// target table's interpolation, the query times, and loop_prepare_kernel -- the kernel that turns the previous period's output into the
-// next solve's input (x0, the shifted guess, the target window).  Its one launch, and the host shell around it, is gusto_loop_host.h.
-// Each unit gets its own instance of the kernel (anonymous namespace); an SSM loop passes no H (it has no linear output map) and no zf
-// (no terminal cost).
+// The device side of what the three closed-loop units (gusto_loop.hip: TPWL plans, gusto_ssm_loop.hip: SSM plans, rompc_loop.hip: the
+// ROMPC baseline) share, stated once: the plan point of a sub-step, the output and measurement rows, the target table's interpolation,
+// the query times, and loop_prepare_kernel -- the kernel that turns the previous period's output into the next solve's input (x0, the
+// shifted guess, the target window).  Its one launch, and the host shell around it, is gusto_loop_host.h.  Each unit gets its own
+// instance of the kernel (anonymous namespace); an SSM loop passes no H (it has no linear output map) and no zf (no terminal cost).
 #pragma once
 #include "common.h"
 #include "dev_la.h"
 
 namespace {
+
+// THE PLAN POINT of a sub-step: lo + theta (hi - lo), in this association, of the plan's rows j_lo and j_hi (rows x ld) at column c.
+// States pass j_hi = j + 1; inputs pass j_hi = min(j + 1, N - 1): the input is held over the last interval (controllers.py:299).
+__device__ __forceinline__ double lerp(double lo, double hi, double th) { return lo + th * (hi - lo); }
+__device__ __forceinline__ double plan_at(cgptr rows, int ld, int j_lo, int j_hi, double th, int c) {
+    return lerp(rows[(size_t)j_lo * ld + c], rows[(size_t)j_hi * ld + c], th);
+}
+
+// THE OUTPUT ROW e of M x (z = H x, y = C x; M (rows x n) row-major, x in LDS or global): by fma from 0.0 in the order c = 0, 1, ... --
+// the sum of gusto_write_out (zopt = H xopt).
+template <typename MP, typename XP>
+__device__ __forceinline__ double out_row(MP M, int e, int n, XP x) {
+    double v = 0.0;
+    for (int c = 0; c < n; ++c) v = fma(M[e * n + c], x[c], v);
+    return v;
+}
+
+// The measurement ((C x)_e + y_ref[e]) + noise[iv], in this order; y_ref and noise may each be null (that addend is then left out)
+template <typename XP>
+__device__ __forceinline__ double measure_row(cgptr Cm, int e, int n, XP x, cgptr y_ref, cgptr noise, size_t iv) {
+    double v = out_row(Cm, e, n, x);
+    if (y_ref != nullptr) v += y_ref[e];
+    if (noise != nullptr) v += noise[iv];
+    return v;
+}
 
 // Row `a` of the table (tt (T), ty (T x ld)) at tq: scipy's interp1d(kind='linear', bounds_error=False, fill_value=(y[0], y[-1])) --
 // i = searchsorted(tt, tq) (first tt[i] >= tq) clipped to 1..T-1, slope (y[i] - y[i-1]) / (tt[i] - tt[i-1]), slope (tq - tt[i-1]) + y[i-1];
@@ -59,11 +84,7 @@ __global__ __launch_bounds__(256) void loop_prepare_kernel(PrepArgs a) {
     }
     if (a.Zrec) {
         cgptr H = (cgptr)a.H;
-        for (int e = tid; e < nz; e += 256) {
-            double v = 0.0;
-            for (int c = 0; c < n; ++c) v = fma(H[e * n + c], xr[c], v);
-            ((gptr)a.Zrec)[b * (size_t)a.rec_rows * nz + e] = v;
-        }
+        for (int e = tid; e < nz; e += 256) ((gptr)a.Zrec)[b * (size_t)a.rec_rows * nz + e] = out_row(H, e, n, xr);
     }
     if (!a.first) {
         // rows idx0.. of the previous plan move to the front, its last row is held over the rest (ros.py:110-114)

@@ -129,8 +129,7 @@ __global__ __launch_bounds__(SL_NT) void ssm_loop_advance_kernel(SsmDev S, SsmOb
         const int js = jsg[s];
         const double th = thg[s];
         if (tid < m) {                                     // the input is held over the last interval (SSM/controllers.py:204)
-            const double lo = uo[(size_t)js * m + tid], hi = uo[(size_t)min(js + 1, N - 1) * m + tid];
-            const double v = lo + th * (hi - lo);
+            const double v = plan_at(uo, m, js, min(js + 1, N - 1), th, tid);
             us[tid] = v;
             if (a.U) ((gptr)a.U)[(b * (size_t)a.rows_u + a.row0_u + s) * m + tid] = v;
         }

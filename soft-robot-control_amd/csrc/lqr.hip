@@ -446,9 +446,7 @@ __global__ __launch_bounds__(NTH) void ilqr_kernel(TpwlDev T, SsmDev S, IlqrArgs
                 cost += 0.5 * c;     // every lane of wave 0 carries the running cost; thread 0 publishes it
             }
             if constexpr (MODEL == 0) {
-                const size_t i = (size_t)*L.flag;
-                wg::matTvec(L.v2, T.AdT + i * n * n, n, n, n, (clptr)L.v1, T.dd + i * n, part);
-                wg::matTvec(L.v2, T.BdT + i * m * n, n, m, n, (clptr)L.u1, (clptr)L.v2, part);
+                tpwl::step_l2(L.v2, T, (size_t)*L.flag, n, m, (clptr)L.v1, (clptr)L.u1, part);           // (the L2-fed step of tpwl_dev.h)
             } else {
                 gptr lt = lo + (size_t)t * lstride;
                 for (int e = tid; e < n * n; e += nt) lt[e] = Al[e];

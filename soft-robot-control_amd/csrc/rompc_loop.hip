@@ -31,14 +31,6 @@
 
 namespace {
 
-typedef double rl_d2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void rl_panel_copy16(lptr dst, cgptr src, int count) {         // count even, both 16-byte aligned
-    auto d2 = (__attribute__((address_space(3))) rl_d2 *)dst;
-    auto s2 = (const __attribute__((address_space(1))) rl_d2 *)src;
-    for (int e = SRH_TID; e < (count >> 1); e += 256) d2[e] = s2[e];
-}
-
 // `count` copies of src (len) behind one another: the constant horizon of the QP
 __global__ __launch_bounds__(256) void rompc_tile_kernel(const double *src, int64_t len, int64_t count, double *dst) {
     const int64_t e = (int64_t)blockIdx.x * 256 + SRH_TID;
@@ -87,12 +79,9 @@ __global__ __launch_bounds__(256) void rompc_chain_kernel(ChainArgs a) {
         if (e < N * m) v = input_at(e / m, e % m);
         if (e < N * m) uo[e] = v;
     }
-    // the next request: lo + theta (hi - lo) of rows j_end, j_end + 1.  Row 0 is x0 in every branch, rows >= 1 are read from xprev /
-    // xsol, which this kernel writes only where xsol is xout -- and there with the value read.
-    for (int c = tid; c < n; c += 256) {
-        const double lo = state_at(a.j_end, c), hi = state_at(a.j_end + 1, c);
-        ((gptr)a.x0_next)[b * n + c] = lo + a.th_end * (hi - lo);
-    }
+    // the next request: the plan point (gusto_loop_prep.h) of rows j_end, j_end + 1.  Row 0 is x0 in every branch, rows >= 1 are read
+    // from xprev / xsol, which this kernel writes only where xsol is xout -- and there with the value read.
+    for (int c = tid; c < n; c += 256) ((gptr)a.x0_next)[b * n + c] = lerp(state_at(a.j_end, c), state_at(a.j_end + 1, c), a.th_end);
 }
 
 struct RlAdvArgs {
@@ -118,9 +107,8 @@ struct RlAdvArgs {
 // the point (2) | the plant's panel A^T, B^T, d (plant only).  n, m, n + m + ny are padded to even so that the panel is 16-byte aligned.
 __host__ __device__ inline int rl_even(int v) { return (v + 1) & ~1; }
 size_t rl_advance_lds_bytes(int n, int m, int ny, bool plant) {
-    size_t d = 2 * (size_t)rl_even(n) + rl_even(n + m + ny) + 16 + 3 * 256 + 2;
-    if (plant) d += (size_t)n * n + (size_t)m * n + n;
-    return srh::lds_request(sizeof(double) * d);
+    const size_t d = 2 * (size_t)rl_even(n) + rl_even(n + m + ny) + 16 + 256 + 2;
+    return srh::lds_request(sizeof(double) * (d + (plant ? tpwl::step_doubles(n, m, 256) : 2 * 256)));
 }
 
 // One workgroup of 256 threads per member, all n_keep sub-steps of a period.  The plant's region panel [A_d^T | B_d^T | d_d] sits in LDS
@@ -128,12 +116,11 @@ size_t rl_advance_lds_bytes(int n, int m, int ny, bool plant) {
 // operand v = [x_hat ; u ; y - y_ref] stay in LDS for the whole launch (x_hat - x_bar is formed where K reads it).  The controller's
 // constants -- [F B L]^T, K, C, H -- are read from global memory through L2: every workgroup reads the same 59 KB at the Diamond shape.
 // Fixed summation orders:
-//   y_e    = (sum_c C[e][c] x[c] by fma from 0.0, c = 0, 1, ...) + y_ref[e], then + v_e; v's last block holds y_e - y_ref[e]
+//   y_e    = measure_row (gusto_loop_prep.h): (C x)_e + y_ref[e], then + v_e; v's last block holds y_e - y_ref[e]
 //   u_e    = ubar_e + wave_sum over lanes of (sum over c = lane, lane + 64, ... of K[e][c] (x_hat[c] - x_bar[c]) by fma from 0.0)
-//   x'     = d_p + (partials of A x in slice order) + (partials of B u in slice order) (+ w): wg::matTvec's slices, slice q of S =
-//            256 / n sums rows q, q + S, ... by fma from 0.0
-//   x_hat' = d + (partials of [F B L] v in slice order), the same slices over the n + m + ny rows of [F B L]^T
-//   z_e    = sum_c H[e][c] x'[c] by fma from 0.0, c = 0, 1, ...
+//   x'     = THE STEP RULE of tpwl_dev.h (+ w)
+//   x_hat' = d + (partials of [F B L] v in slice order), the step rule's slices over the n + m + ny rows of [F B L]^T
+//   z_e    = out_row (gusto_loop_prep.h) of H x'
 __global__ __launch_bounds__(256) void rompc_loop_advance_kernel(TpwlDev TL, RlAdvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int n = a.n, m = a.m, ny = a.ny, nz = a.nz, N = a.N, nv = n + m + ny;
@@ -141,13 +128,10 @@ __global__ __launch_bounds__(256) void rompc_loop_advance_kernel(TpwlDev TL, RlA
     lptr xb = xc + rl_even(n);                           // n      x_bar
     lptr vh = xb + rl_even(n);                           // nv     [x_hat ; u ; y - y_ref]
     lptr ub = vh + rl_even(nv);                          // 16     u_bar
-    lptr pa = ub + 16;                                   // 256    partial sums of A x
-    lptr pb = pa + 256;                                  // 256    partial sums of B u
-    lptr ph = pb + 256;                                  // 256    partial sums of [F B L] v
+    tpwl::StepLds L;                                     //        partial sums of A x, B u | ph, ip | the panel of region `cur`
+    tpwl::step_carve(L, ub + 16, n, m, 256, 256 + 2);
+    lptr ph = L.pb + 256;                                // 256    partial sums of [F B L] v
     liptr ip = (liptr)(ph + 256);                        // (two doubles) plant point
-    lptr At = ph + 256 + 2;                              // n x n  the panel of region `cur`
-    lptr Bt = At + n * n;                                // m x n
-    lptr dl = Bt + m * n;                                // n
     lptr xh = vh, uc = vh + n, yd = vh + n + m;
     const size_t b = blockIdx.x;
     const int tid = SRH_TID, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -162,25 +146,19 @@ __global__ __launch_bounds__(256) void rompc_loop_advance_kernel(TpwlDev TL, RlA
     }
     __syncthreads();
     if (a.z0 && a.Z)
-        for (int e = tid; e < nz; e += 256) {
-            double v = 0.0;
-            for (int c = 0; c < n; ++c) v = fma(Hz[e * n + c], xc[c], v);
-            ((gptr)a.Z)[(b * (size_t)a.rows_x + a.row0_x - 1) * nz + e] = v;
-        }
+        for (int e = tid; e < nz; e += 256) ((gptr)a.Z)[(b * (size_t)a.rows_x + a.row0_x - 1) * nz + e] = out_row(Hz, e, n, xc);
     int cur = -1;
     for (int s = 0; s < a.n_keep; ++s) {
         const int js = jsg[s];
         const double th = thg[s];
         const size_t rx = b * (size_t)a.rows_x + a.row0_x + s, ru = b * (size_t)a.rows_u + a.row0_u + s;
         if (tid < n) {                                   // (n <= 128: waves 0 and 1)
-            const double lo = xo[(size_t)js * n + tid], hi = xo[(size_t)(js + 1) * n + tid];
-            const double v = lo + th * (hi - lo);
+            const double v = plan_at(xo, n, js, js + 1, th, tid);
             xb[tid] = v;
             if (a.Xbar) ((gptr)a.Xbar)[(rx - 1) * n + tid] = v;
         } else if (tid >= 128 && tid < 128 + m) {        // the input is held over the last interval
             const int e = tid - 128;
-            const double lo = uo[(size_t)js * m + e], hi = uo[(size_t)min(js + 1, N - 1) * m + e];
-            const double v = lo + th * (hi - lo);
+            const double v = plan_at(uo, m, js, min(js + 1, N - 1), th, e);
             ub[e] = v;
             if (a.Ubar) ((gptr)a.Ubar)[ru * m + e] = v;
         }
@@ -189,10 +167,8 @@ __global__ __launch_bounds__(256) void rompc_loop_advance_kernel(TpwlDev TL, RlA
             if (lane == 0) ip[0] = (unsigned)i < (unsigned)TL.P ? i : 0;           // (a state that is not a number: no minimum)
         }
         for (int e = tid; e < ny; e += 256) {            // 1. the measurement of the current plant state
-            double v = 0.0;
-            for (int c = 0; c < n; ++c) v = fma(Cg[e * n + c], xc[c], v);
-            v += yr[e];
-            if (Vd != nullptr) v += Vd[((size_t)(a.w_step0 + s) * a.B + b) * ny + e];
+            __builtin_assume(yr != nullptr);             // (a controller always has its y_ref: no test of it in measure_row)
+            const double v = measure_row(Cg, e, n, xc, yr, Vd, ((size_t)(a.w_step0 + s) * a.B + b) * ny + e);
             yd[e] = v - yr[e];
             if (a.Y) ((gptr)a.Y)[ru * ny + e] = v;
         }
@@ -200,12 +176,7 @@ __global__ __launch_bounds__(256) void rompc_loop_advance_kernel(TpwlDev TL, RlA
         int p = 0;
         if (a.plant) {
             p = ip[0];
-            if (p != cur) {                              // (the same for every thread; the barrier below covers the copies)
-                rl_panel_copy16(At, TL.AdT + (size_t)p * n * n, n * n);
-                rl_panel_copy16(Bt, TL.BdT + (size_t)p * m * n, m * n);
-                rl_panel_copy16(dl, TL.dd + (size_t)p * n, n);
-                cur = p;
-            }
+            tpwl::panel_load(L, TL, p, cur, n, m, SRH_TID, 256);           // (the same for every thread; the barrier below covers the copies)
         }
         for (int e = wave; e < m; e += 4) {              // 2. u = ubar + K (x_hat - xbar)
             double acc = 0.0;
@@ -223,22 +194,13 @@ __global__ __launch_bounds__(256) void rompc_loop_advance_kernel(TpwlDev TL, RlA
 #pragma unroll 4
             for (int q = sl; q < nv; q += S) vh_ = fma(Mt[(size_t)q * n + j], vh[q], vh_);
             ph[sl * n + j] = vh_;
-            if (a.plant) {
-                double va = 0.0, vb = 0.0;
-#pragma unroll 4
-                for (int q = sl; q < n; q += S) va = fma(At[q * n + j], xc[q], va);
-                for (int q = sl; q < m; q += S) vb = fma(Bt[q * n + j], uc[q], vb);
-                pa[sl * n + j] = va;
-                pb[sl * n + j] = vb;
-            }
+            if (a.plant) tpwl::step_slices(L, xc, uc, n, m, S, j, sl);
         }
         __syncthreads();
         if (tid < n) {
             double v;
             if (a.plant) {
-                v = dl[tid];
-                for (int q = 0; q < S; ++q) v += pa[q * n + tid];
-                for (int q = 0; q < S; ++q) v += pb[q * n + tid];
+                v = tpwl::step_sum(L, n, S, tid);
                 if (Wd != nullptr) v += Wd[((size_t)(a.w_step0 + s) * a.B + b) * n + tid];
             } else {
                 v = Xp[(rx)*n + tid];
@@ -253,11 +215,7 @@ __global__ __launch_bounds__(256) void rompc_loop_advance_kernel(TpwlDev TL, RlA
         __syncthreads();
         // z = H x'.  x is next written behind three barriers of the next sub-step.
         if (a.Z)
-            for (int e = tid; e < nz; e += 256) {
-                double v = 0.0;
-                for (int c = 0; c < n; ++c) v = fma(Hz[e * n + c], xc[c], v);
-                ((gptr)a.Z)[rx * nz + e] = v;
-            }
+            for (int e = tid; e < nz; e += 256) ((gptr)a.Z)[rx * nz + e] = out_row(Hz, e, n, xc);
     }
     for (int e = tid; e < n; e += 256) {
         if (a.x_out) ((gptr)a.x_out)[b * n + e] = xc[e];

@@ -118,22 +118,6 @@ __global__ __launch_bounds__(256) void blend_kernel(TpwlDev T, const double *__r
     }
 }
 
-// wg::matTvec for len > blockDim.x, where its (slice, j) layout has one slice and no thread for the columns j >= blockDim.x: thread t takes
-// the columns t, t + blockDim.x, ...  The sums are those of wg::matTvec with one slice: rows 0, 1, ... by fma from 0.0, then add[j] + sum.
-// add may be y (each column is read and written by its own thread).  Ends with __syncthreads().
-template <typename MP, typename AP>
-__device__ inline void matTvec_strided(lptr y, MP M, int ldm, int rows, int len, clptr v, AP add) {
-    for (int j = threadIdx.x; j < len; j += blockDim.x) {
-        double acc = 0.0;
-#pragma unroll 4
-        for (int i = 0; i < rows; ++i) acc = fma(M[i * ldm + j], v[i], acc);
-        double r = add ? add[j] : 0.0;
-        r += acc;
-        y[j] = r;
-    }
-    __syncthreads();
-}
-
 // one workgroup per rollout: x_{k+1} = A_d[i_k] x_k + B_d[i_k] u_k + d_d[i_k], i_k = nearest(x_k)
 __global__ __launch_bounds__(256) void rollout_kernel(TpwlDev T, const double *__restrict__ x0,
                                                       const double *__restrict__ U, int N,
@@ -157,14 +141,9 @@ __global__ __launch_bounds__(256) void rollout_kernel(TpwlDev T, const double *_
         for (int e = threadIdx.x; e < m; e += blockDim.x) uc[e] = U[(b * N + k) * m + e];
         __syncthreads();
         const int i = *ip;
-        // xn = A x + d  (via the transposed table: coalesced), then += B u
-        if (n <= (int)blockDim.x) {
-            wg::matTvec(xn, T.AdT + (size_t)i * n * n, n, n, n, xc, T.dd + (size_t)i * n, part);
-            wg::matTvec(xn, T.BdT + (size_t)i * m * n, n, m, n, uc, (clptr)xn, part);
-        } else {                                         // (n_x > 256: wg::matTvec has no thread for the columns past blockDim.x)
-            matTvec_strided(xn, T.AdT + (size_t)i * n * n, n, n, n, xc, T.dd + (size_t)i * n);
-            matTvec_strided(xn, T.BdT + (size_t)i * m * n, n, m, n, uc, (clptr)xn);
-        }
+        // xn = A x + d  (via the transposed table: coalesced), then += B u: the L2-fed step of tpwl_dev.h
+        if (n <= (int)blockDim.x) tpwl::step_l2(xn, T, i, n, m, xc, uc, part);
+        else tpwl::step_l2_strided(xn, T, i, n, m, xc, uc, threadIdx.x, blockDim.x);      // (n_x > 256: wg::matTvec has no thread for the columns past blockDim.x)
         for (int e = threadIdx.x; e < n; e += blockDim.x) { xc[e] = xn[e]; Xb[(size_t)(k + 1) * n + e] = xn[e]; }
         __syncthreads();
     }
@@ -181,21 +160,12 @@ __global__ __launch_bounds__(256) void rollout_kernel(TpwlDev T, const double *_
 
 // The same rollout with the region's panel [A_d^T | B_d^T | d_d] in LDS, reloaded (coalesced 16-byte loads) only when the nearest point
 // changes, and both products of a stage under one barrier.  rollout_kernel reads the panel (31 KB at n_x = 60) from L2 at every stage
-// and runs wg::matTvec twice: four barriers and two L2-fed products per stage.  The sums are those of the two wg::matTvec calls, in
-// their order: with S = blockDim / n slices, slice s accumulates the rows s, s + S, ... by fma from 0.0; x' = d + p[0] + ... + p[S-1],
-// then the input product's partials are added to x' the same way.  X and Z are bit-identical to rollout_kernel's.
+// and runs wg::matTvec twice: four barriers and two L2-fed products per stage.  Both are THE STEP RULE of tpwl_dev.h: X and Z are
+// bit-identical to rollout_kernel's.
 // HELD (w_v = 0, P <= 64, r <= 32, hence n <= 64: wave 0 owns the whole state): lane i of wave 0 keeps ITS table point in registers for
 // the rollout and lane c < r the coordinate x[r + c] of the state the wave has just summed; the coordinates are broadcast with v_readlane as in
 // tpwl::nearest_many -- same sums in the order j = 0, 1, ..., same sqrt, first minimum, index 0 for a state that is not a number --
 // and the barrier between a stage's sums and the next search is not needed.  Otherwise wave 0 calls tpwl::nearest_wave on the LDS state.
-typedef double tpwl_d2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void stage_copy16(lptr dst, cgptr src, int count) {            // count even, both 16-byte aligned
-    auto d2 = (__attribute__((address_space(3))) tpwl_d2 *)dst;
-    auto s2 = (const __attribute__((address_space(1))) tpwl_d2 *)src;
-    for (int e = threadIdx.x; e < (count >> 1); e += blockDim.x) d2[e] = s2[e];
-}
-
 template <bool HELD>
 __global__ __launch_bounds__(256) void rollout_staged_kernel(TpwlDev T, const double *__restrict__ x0,
                                                              const double *__restrict__ U, int N,
@@ -204,12 +174,9 @@ __global__ __launch_bounds__(256) void rollout_staged_kernel(TpwlDev T, const do
     const int n = T.n, m = T.m, r = T.r;
     lptr xc = (lptr)smem;                                // n
     lptr uc = xc + n;                                    // m
-    lptr pa = uc + ((m + 3) & ~3);                       // blockDim: partial sums of A x
-    lptr pb = pa + blockDim.x;                           // blockDim: partial sums of B u
-    liptr ip = (liptr)(pb + blockDim.x);                 // (two doubles)
-    lptr At = pb + blockDim.x + 2;                       // n x n   the panel of region `cur`: every offset is even (n = 2 r)
-    lptr Bt = At + n * n;                                // m x n
-    lptr dl = Bt + m * n;                                // n
+    tpwl::StepLds L;                                     // partial sums, (two doubles) the point, the panel of region `cur`: every offset is even (n = 2 r)
+    tpwl::step_carve(L, uc + ((m + 3) & ~3), n, m, blockDim.x, 2);
+    liptr ip = (liptr)(L.pb + blockDim.x);
     const int64_t b = blockIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int S = max(1, (int)blockDim.x / n), j = threadIdx.x % n, s = threadIdx.x / n;          // wg::matTvec's slices
@@ -258,26 +225,14 @@ __global__ __launch_bounds__(256) void rollout_staged_kernel(TpwlDev T, const do
         }
         __syncthreads();
         const int i = *ip;
-        if (i != cur) {                                  // (the same for every thread)
-            stage_copy16(At, T.AdT + (size_t)i * n * n, n * n);
-            stage_copy16(Bt, T.BdT + (size_t)i * m * n, m * n);
-            stage_copy16(dl, T.dd + (size_t)i * n, n);
-            cur = i;
+        if (i != cur) {                                  // (the same for every thread; the test is stated here too: the barrier is this kernel's)
+            tpwl::panel_load(L, T, i, cur, n, m, threadIdx.x, blockDim.x);
             __syncthreads();
         }
-        if (s < S) {
-            double a = 0.0, c = 0.0;
-#pragma unroll 4
-            for (int q = s; q < n; q += S) a = fma(At[q * n + j], xc[q], a);
-            for (int q = s; q < m; q += S) c = fma(Bt[q * n + j], uc[q], c);
-            pa[s * n + j] = a;
-            pb[s * n + j] = c;
-        }
+        tpwl::step_slices(L, xc, uc, n, m, S, j, s);
         __syncthreads();
         if ((int)threadIdx.x < n) {
-            double v = dl[threadIdx.x];
-            for (int q = 0; q < S; ++q) v += pa[q * n + threadIdx.x];
-            for (int q = 0; q < S; ++q) v += pb[q * n + threadIdx.x];
+            const double v = tpwl::step_sum(L, n, S, threadIdx.x);
             xc[threadIdx.x] = v;
             Xb[(size_t)(k + 1) * n + threadIdx.x] = v;
         }
@@ -338,9 +293,9 @@ std::vector<double> transpose_batch(const double *src, int P, int rows, int cols
 struct RolloutPlan { bool staged, held; size_t lds; };
 
 RolloutPlan rollout_plan(const stpwl *h) {
-    const size_t n = h->n, m = h->m, vec = 2 * n + ((m + 3) & ~(size_t)3) + 256;              // state(s), input, one partial buffer
-    const size_t plain = sizeof(double) * vec + 16;
-    const size_t staged = srh::lds_request(sizeof(double) * (vec + 256 + 2 + n * n + m * n));   // + second partial buffer, index, panel (d_d in the second state's place)
+    const size_t n = h->n, m = h->m, um = (m + 3) & ~(size_t)3;
+    const size_t plain = sizeof(double) * (2 * n + um + 256) + 16;                              // two states, input, one partial buffer, index
+    const size_t staged = srh::lds_request(sizeof(double) * (n + um + 2 + tpwl::step_doubles(h->n, h->m, 256)));      // state, input, index, the step's
     RolloutPlan p;
     p.staged = !h->rollout_plain && staged <= (size_t)64 * 1024;
     p.held = p.staged && h->w_v == 0.0 && h->P <= 64 && h->r <= 32;

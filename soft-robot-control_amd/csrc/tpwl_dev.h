@@ -127,4 +127,96 @@ __device__ inline void nearest_many(const TpwlDev &T, XP X, int ldx, int count, 
     __syncthreads();
 }
 
+// THE STEP RULE, stated once for the kernels that step a TPWL plant (rollout_kernel and rollout_staged_kernel in tpwl.hip,
+// loop_advance_kernel in gusto_loop.hip, rompc_loop_advance_kernel in rompc_loop.hip, the TPWL forward pass of ilqr_kernel in lqr.hip):
+//   x' = d_d[i] + A_d[i] x + B_d[i] u, i the nearest point to x, read from the transposed tables (coalesced along the columns);
+//   with len = n columns and S = max(1, threads / n) slices, slice s sums the rows s, s + S, ... of a product by fma from 0.0
+//   (wg::matTvec's slices; for n > threads one slice, and thread t takes the columns t, t + threads, ...);
+//   x'[t] = d[t] + p_A[0][t] + ... + p_A[S-1][t], then + p_B[0][t] + ... + p_B[S-1][t]: first the partials of A x, then those of B u, each
+//   in slice order.  A disturbance w is added behind that by the caller.
+// The L2-fed step (step_l2) is two wg::matTvec calls, the second adding onto the first.  The staged step keeps the region's panel
+// [A_d^T | B_d^T | d_d] in LDS (StepLds), reloads it only when the point changes (panel_load) and forms both products under one barrier
+// (step_slices, the caller's barrier, step_sum).  The staged helpers read no thread index and hold no barrier: thread index, slice, column
+// and thread count are the caller's, so each kernel keeps its own reads and its own barriers (wg::matTvec has its own of both).
+typedef double d2 __attribute__((ext_vector_type(2)));
+
+// 16-byte copy of `count` doubles from global memory into LDS (count even, both 16-byte aligned)
+__device__ __forceinline__ void copy16(lptr dst, cgptr src, int count, int tid, int nt) {
+    auto d = (__attribute__((address_space(3))) d2 *)dst;
+    auto s = (const __attribute__((address_space(1))) d2 *)src;
+    for (int e = tid; e < (count >> 1); e += nt) d[e] = s[e];
+}
+
+// LDS of the staged step: two partial buffers of nt doubles, the panel.  A kernel may keep `gap` doubles of its own between pb and At
+// (the point words; every panel offset stays even).
+struct StepLds { lptr pa, pb, At, Bt, dl; };
+__host__ __device__ inline size_t step_doubles(int n, int m, int nt) { return 2 * (size_t)nt + (size_t)n * n + (size_t)m * n + n; }
+// returns the first double behind the panel
+__device__ __forceinline__ lptr step_carve(StepLds &L, lptr base, int n, int m, int nt, int gap) {
+    L.pa = base;                                         // nt     partial sums of A x
+    L.pb = L.pa + nt;                                    // nt     partial sums of B u
+    L.At = L.pb + nt + gap;                              // n x n  the panel of the region
+    L.Bt = L.At + n * n;                                 // m x n
+    L.dl = L.Bt + m * n;                                 // n
+    return L.dl + n;
+}
+
+// the panel of point p unless it is the one loaded (cur); true when it loaded.  The same for every thread; no barrier.
+__device__ __forceinline__ bool panel_load(const StepLds &L, const TpwlDev &T, int p, int &cur, int n, int m, int tid, int nt) {
+    if (p == cur) return false;
+    copy16(L.At, T.AdT + (size_t)p * n * n, n * n, tid, nt);
+    copy16(L.Bt, T.BdT + (size_t)p * m * n, m * n, tid, nt);
+    copy16(L.dl, T.dd + (size_t)p * n, n, tid, nt);
+    cur = p;
+    return true;
+}
+
+// slice sl of both products for column j
+__device__ __forceinline__ void step_slices(const StepLds &L, clptr xc, clptr uc, int n, int m, int S, int j, int sl) {
+    if (sl < S) {
+        double a = 0.0, c = 0.0;
+#pragma unroll 4
+        for (int q = sl; q < n; q += S) a = fma(L.At[q * n + j], xc[q], a);
+        for (int q = sl; q < m; q += S) c = fma(L.Bt[q * n + j], uc[q], c);
+        L.pa[sl * n + j] = a;
+        L.pb[sl * n + j] = c;
+    }
+}
+
+// x'[t], behind the barrier that follows step_slices
+__device__ __forceinline__ double step_sum(const StepLds &L, int n, int S, int t) {
+    double v = L.dl[t];
+    for (int q = 0; q < S; ++q) v += L.pa[q * n + t];
+    for (int q = 0; q < S; ++q) v += L.pb[q * n + t];
+    return v;
+}
+
+// xn = d_d[i] + A_d[i] xc + B_d[i] uc from the tables in L2, n <= threads (wg::matTvec: ends with __syncthreads())
+__device__ __forceinline__ void step_l2(lptr xn, const TpwlDev &T, size_t i, int n, int m, clptr xc, clptr uc, lptr part) {
+    wg::matTvec(xn, T.AdT + i * n * n, n, n, n, xc, T.dd + i * n, part);
+    wg::matTvec(xn, T.BdT + i * m * n, n, m, n, uc, (clptr)xn, part);
+}
+
+// wg::matTvec for len > nt threads, where its (slice, j) layout has one slice and no thread for the columns j >= nt: thread t takes the
+// columns t, t + nt, ...  The sums are those of the rule with one slice: rows 0, 1, ... by fma from 0.0, then add[j] + sum.
+// add may be y (each column is read and written by its own thread).  Ends with __syncthreads().
+template <typename MP, typename AP, typename NT>
+__device__ inline void matTvec_strided(lptr y, MP M, int ldm, int rows, int len, clptr v, AP add, int tid, NT nt) {
+    for (int j = tid; j < len; j += nt) {
+        double acc = 0.0;
+#pragma unroll 4
+        for (int i = 0; i < rows; ++i) acc = fma(M[i * ldm + j], v[i], acc);
+        double r = add ? add[j] : 0.0;
+        r += acc;
+        y[j] = r;
+    }
+    __syncthreads();
+}
+// step_l2 for n > nt threads (nt of the caller's type: blockDim.x is unsigned)
+template <typename NT>
+__device__ __forceinline__ void step_l2_strided(lptr xn, const TpwlDev &T, size_t i, int n, int m, clptr xc, clptr uc, int tid, NT nt) {
+    matTvec_strided(xn, T.AdT + i * n * n, n, n, n, xc, T.dd + i * n, tid, nt);
+    matTvec_strided(xn, T.BdT + i * m * n, n, m, n, uc, (clptr)xn, tid, nt);
+}
+
 }  // namespace tpwl

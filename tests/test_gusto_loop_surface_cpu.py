@@ -83,6 +83,25 @@ def test_the_period_skeleton_and_the_record_copies_are_stated_once():
     assert sum(u.count('hipStreamCreateWithFlags') for f, u in units.items() if f.startswith('gusto_loop') or f == 'gusto_ssm_loop.hip') == 1
 
 
+def test_the_plant_step_and_the_plan_point_are_stated_once():
+    """The staged plant step lives in tpwl_dev.h alone -- its 16-byte copy and its slice product -- no kernel that steps a TPWL plant forms
+    a panel address itself, and the plan point's interpolation is written in one file.  (pod.hip has a two-double vector type of its own
+    for the POD products: it includes none of the TPWL headers.)"""
+    csrc = os.path.join(ROOT, 'soft-robot-control_amd', 'csrc')
+    units = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith(('.hip', '.h'))}
+    holding = lambda text: sorted(f for f, u in units.items() if text in u)
+    assert [f for f in holding('ext_vector_type(2)') if f != 'pod.hip'] == ['tpwl_dev.h']
+    assert holding('At[q * n + j]') == ['tpwl_dev.h']
+    kernels_of_tpwl = units['tpwl.hip'].split('std::vector<double> transpose_batch')[0]
+    assert '__global__' in kernels_of_tpwl and 'rollout_staged_kernel' in kernels_of_tpwl
+    for f, text in (('gusto_loop.hip', units['gusto_loop.hip']), ('rompc_loop.hip', units['rompc_loop.hip']), ('lqr.hip', units['lqr.hip']),
+                    ('tpwl.hip', kernels_of_tpwl)):
+        assert 'AdT +' not in text and 'BdT +' not in text, f
+    assert holding('th * (hi - lo)') == ['gusto_loop_prep.h']
+    for f in ('stage_copy16', 'panel_copy16', 'rl_panel_copy16'):
+        assert not holding(f), f
+
+
 def test_refusals_on_the_host():
     """Argument checks that come before any device call."""
     from sofacontrol_amd import _lib

@@ -1,5 +1,6 @@
-"""Bit-level dump of the closed-loop units (csrc/gusto_loop.hip, csrc/gusto_ssm_loop.hip and the host shell they share,
-csrc/gusto_loop_host.h) for comparing two builds of the library (SRH_LIB_PATH selects one).
+"""Bit-level dump of the closed-loop units (csrc/gusto_loop.hip, csrc/gusto_ssm_loop.hip, csrc/rompc_loop.hip and the host shell they
+share, csrc/gusto_loop_host.h) and of the TPWL rollout kernels (csrc/tpwl.hip) for comparing two builds of the library (SRH_LIB_PATH
+selects one).
 
 Runs the loops of the test suites at their own smallest shapes through scp.closed_loop / scp.closed_loop_ssm and records every array
 that comes back, raw:
@@ -9,6 +10,10 @@ that comes back, raw:
     _advance_observed on the case 'g6-frac-3' of clobs_cases.CASES;
   - SSM (tests/test_gusto_ssm_loop_gpu.py: 'hw' and 'frac', B = 3, observe True and False): reset with v0, run(2, W, V) twice, and the
     stand-alone advance on one entry of ssm_loop_cases.ADVANCE;
+  - ROMPC (tests/test_rompc_loop_gpu.py: 'frac' and 'zf-u', g6 model, B = 3): reset(x0, x_hat0, 0.1), run(2, W, V) twice, then _chain (first
+    and later period) and _advance alone on the entries 'g6-frac-10', 'r36-5-10', 'm8-frac-10' and 'g6-replay' of rompc_loop_cases.ADVANCE;
+  - rollout (tests/test_tpwl_rollout_staged_gpu.py: every entry of SHAPES -- staged with the held table, staged with the wave search,
+    plain above 64 KB -- and the velocity-weighted model): X and Z of the staged handle and of the plain one;
 after every run also last_inputs(), last_plan() and stats().  The host-side refusals are recorded as text, message for message: run
 before reset, periods * n_keep over the cap, last_inputs before a period, the observed run without an observer, the SSM model mismatch.
 
@@ -40,8 +45,8 @@ class Records(list):
         for k, a in d.items():
             self.array('%s/%s' % (label, k), a)
 
-    def after_run(self, label, cl, r):
-        self.arrays(label, {f: getattr(r, f) for f in RESULT_FIELDS})
+    def after_run(self, label, cl, r, fields=RESULT_FIELDS):
+        self.arrays(label, {f: getattr(r, f) for f in fields})
         self.arrays(label + '/last_inputs', cl.last_inputs())
         self.arrays(label + '/last_plan', dict(zip(('xopt', 'uopt'), cl.last_plan())))
         self.append((label + '/stats', json.dumps(cl.stats(), sort_keys=True).encode()))
@@ -136,6 +141,41 @@ def dump_ssm(rec):
     rec.arrays('ssm/advance/' + slc.case_id(case), got)
 
 
+def dump_rompc(rec):
+    import rompc_loop_cases as rc
+    import test_rompc_loop_gpu as tr
+    for name in tr.LOOPS:
+        cl, inp = tr.make_loop(name, 3)
+        label = 'rompc/' + name
+        if name == 'frac':
+            rec.refusal('rompc/run_before_reset', lambda: cl.run(1))
+        cl.reset(inp['x0'], inp['x_hat0'], T_START)
+        for q in range(2):
+            rec.after_run('%s/run2_%d' % (label, q), cl, cl.run(2, W=inp['W'][2 * q:2 * q + 2], V=inp['V'][2 * q:2 * q + 2]), tr.FIELDS + ('t',))
+    for name in ('g6-frac-10', 'r36-5-10', 'm8-frac-10', 'g6-replay'):
+        case = [c for c in rc.ADVANCE if c[0] == name][0]
+        c, cl = rc.advance_case(case), tr.advance_loop(case)
+        rec.arrays('rompc/advance/' + name, cl._advance(c['xopt'], c['uopt'], c['x'], c['x_hat'], W=c['W'], V=c['V'], X_plant=c['X_plant']))
+        if name != 'g6-replay':
+            k = rc.chain_case(case[2], cl.N, cl.n_x, cl.n_u, case[-1])
+            for first in (True, False):
+                got = cl._chain(k['xsol'], k['usol'], k['x0'], k['status'], None if first else k['xprev'], None if first else k['uprev'], first=first)
+                rec.arrays('rompc/chain/%s_%s' % (name, 'first' if first else 'later'), dict(zip(('xopt', 'uopt', 'x0_next'), got)))
+
+
+def dump_rollout(rec):
+    import test_tpwl_rollout_staged_gpu as tg
+    cases = [('-'.join(map(str, s)), tg.shape_case(*s), path) for s, path in tg.SHAPES] + [('6-3-12-12-3-wv', tg.shape_case(6, 3, 12, 12, 3, w_v=0.5), (True, False))]
+    for name, c, path in cases:
+        batch, N = c['u'].shape[0], c['u'].shape[1]
+        plan = c['staged'].plan(N, batch)
+        kind = 'plain' if not plan['staged'] else 'held' if plan['held'] else 'wave'
+        assert (plan['staged'], plan['held']) == path, (name, plan)
+        rec.append(('rollout/%s/%s/plan' % (kind, name), json.dumps(plan, sort_keys=True).encode()))
+        for which in ('staged', 'plain'):
+            rec.arrays('rollout/%s/%s/%s_handle' % (kind, name, which), dict(zip(('X', 'Z'), c[which].rollout(c['x0'], c['u']))))
+
+
 def dump(out):
     from sofacontrol_amd import _lib
     assert _lib.device_count() >= 1, 'no GPU visible'
@@ -144,6 +184,8 @@ def dump(out):
     dump_tpwl(rec)
     dump_observed(rec)
     dump_ssm(rec)
+    dump_rompc(rec)
+    dump_rollout(rec)
     index, off = [], 0
     with open(out + '.bin', 'wb') as f:
         for name, b in rec:
@@ -167,7 +209,7 @@ def compare(a, b, log):
         for ra, rb in zip(ja['records'], jb['records']):
             equal = ba[ra['offset']:ra['offset'] + ra['bytes']] == bb[rb['offset']:rb['offset'] + rb['bytes']]
             parts = ra['name'].split('/')
-            group = '/'.join(parts[:1 if parts[0] == 'refusal' else 4 if parts[0] == 'ssm' and parts[1] != 'advance' else 3])
+            group = '/'.join(parts[:1 if parts[0] == 'refusal' else 2 if parts[0] == 'rollout' else 4 if parts[0] == 'ssm' and parts[1] != 'advance' else 3])
             t = per_group.setdefault(group, [0, 0, 0])
             t[0] += 1
             t[1] += 0 if equal else 1

@@ -1,7 +1,8 @@
 """A/B of two builds of the library on the host path of a closed-loop period (csrc/gusto_loop_host.h and the two units around it): the
 median period of run(1) over 3 warm-up and 20 timed periods of
   - contender (a) of tools/gusto_ssm_loop_probe.py (SSMClosedLoopBatch, the hardware driver's shape) at B = 1, 256, 4096;
-  - the unobserved and the observed TPWL loop of tools/gusto_loop_observer_probe.py (ClosedLoopBatch.run / run_observed) at B = 256.
+  - the unobserved and the observed TPWL loop of tools/gusto_loop_observer_probe.py (ClosedLoopBatch.run / run_observed) at B = 256;
+  - the ROMPC loop of tools/rompc_loop_probe.py (ROMPCClosedLoopBatch.run, the Diamond shape with the TPWL model as the plant) at B = 256.
 
     python tools/loop_host_ab.py --parent <library built from the parent commit> [--rounds 5] [--out profiles/loop_host_ab.json]
 
@@ -10,6 +11,8 @@ alternates parent, new, parent, new, ... (`new` is the in-tree library); every m
 build and the parent's own spread over its rounds, smallest to largest; the new build passes when its median lies inside that spread
 (below it is reported as such: faster is no failure).  Needs the GPU."""
 import argparse
+import contextlib
+import io
 import json
 import os
 import subprocess
@@ -19,10 +22,11 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, 'soft-robot-control_amd'), os.path.join(ROOT, 'tools')]
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'soft-robot-control_amd'), os.path.join(ROOT, 'tools'), os.path.join(ROOT, 'examples')]
 
-SSM_BATCHES, TPWL_BATCH = (1, 256, 4096), 256
-FIGURES = ['ssm_period_ms_B%d' % B for B in SSM_BATCHES] + ['tpwl_period_ms_B%d' % TPWL_BATCH, 'tpwl_observed_period_ms_B%d' % TPWL_BATCH]
+SSM_BATCHES, TPWL_BATCH, ROMPC_BATCH = (1, 256, 4096), 256, 256
+FIGURES = ['ssm_period_ms_B%d' % B for B in SSM_BATCHES] + ['tpwl_period_ms_B%d' % TPWL_BATCH, 'tpwl_observed_period_ms_B%d' % TPWL_BATCH,
+                                                                'rompc_period_ms_B%d' % ROMPC_BATCH]
 
 
 def median_period_ms(period, warm, timed):
@@ -37,7 +41,9 @@ def median_period_ms(period, warm, timed):
 def measure():
     import gusto_loop_observer_probe as op
     import gusto_ssm_loop_probe as sp
+    import rompc_loop_probe as rp
     import workloads as wl
+    from diamond_rompc_closed_loop_batch import diamond_rompc
     from sofacontrol_amd import _lib
     from sofacontrol_amd.scp.closed_loop import ClosedLoopBatch
     from sofacontrol_amd.scp.closed_loop_ssm import SSMClosedLoopBatch
@@ -58,6 +64,13 @@ def measure():
     out['tpwl_period_ms_B%d' % TPWL_BATCH] = median_period_ms(lambda k: cu.run(1, record_x=False), op.WARM, op.TIMED)
     co.reset_observed(p['x0'], p['x_hat0'])
     out['tpwl_observed_period_ms_B%d' % TPWL_BATCH] = median_period_ms(lambda k: co.run_observed(1, V=p['V'][k:k + 1], record_x=False), op.WARM, op.TIMED)
+    rng = np.random.default_rng(0)
+    with contextlib.redirect_stdout(io.StringIO()):
+        loop, _, _, _ = diamond_rompc(ROMPC_BATCH, rp.NK, phase=rng.uniform(0.0, 1.0, ROMPC_BATCH))
+    x0 = 0.5 * rng.standard_normal((ROMPC_BATCH, loop.n_x))
+    loop.reset(x0, x0 + 0.1 * rng.standard_normal(x0.shape))
+    out['rompc_period_ms_B%d' % ROMPC_BATCH] = median_period_ms(lambda k: loop.run(1), op.WARM, op.TIMED)
+    assert loop.stats()['waits_last_run'] == 1
     print('LOOP_HOST_AB ' + json.dumps(out), flush=True)
 
 
