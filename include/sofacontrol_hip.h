@@ -918,6 +918,70 @@ int srompc_loop_chain(srompc_loop_t *h, const double *xopt_prev, const double *u
 int srompc_loop_advance(srompc_loop_t *h, const double *xopt, const double *uopt, const double *x, const double *x_hat, const double *W,
                         const double *V, const double *X_plant, double *X, double *XH, double *Y, double *Z, double *U, double *Ubar, double *Xbar);
 
+/* =====================================================================================================
+ * Batched closed-loop Koopman MPC resident on the device (csrc/koopman_loop.hip).  reference: sofacontrol/baselines/koopman/koopman.py:
+ * 75-170 (compute_policy, evaluate), koopman_utils.py:16-47 (add_measurement, get_zeta), baselines/ros.py:202-235 (the MPC node and its
+ * failure shift).  Every problem of an skoop_t handle's batch is its own loop.  THE POLICY: controller step Ts (the model's), simulation
+ * step dt_sim with Ts = r dt_sim, r an integer >= 1; rollout_horizon = rh controller steps per period (rh <= N), n_keep = rh r sub-steps;
+ * period p starts at t_p = t_start + p n_keep dt_sim (sgusto_loop_schedule, t_k only).
+ *   reset     the ring of every member <- the `delays` older raw samples (y_hist, u_hist), oldest first, then the sample at the first
+ *             solve: y_0 = (C x0 + y_ref) + v0 (or y0 given when there is no plant) pushed with u_prev0 (add_measurement(y, u_prev) in
+ *             front of the first compute_policy); row 0 of the Y record is y_0
+ *   request   x0_p = W psi(zeta) of the ring as it stands (the ring lift of skoop_ring_lift_dev); targets: the window at
+ *             (t_p + phase_b) + Ts k, zf its last row when the cost has Qzf, u_des N rows
+ *   solve     the trust-region-free QP on the constant (A, B), d = 0, all members in one launch, the horizon tiled once
+ *   fix-up    a member whose QP status is non-zero goes on with the previous plan moved up ONE row, its last row held (ros.py:223-227,
+ *             whatever rh is); in period 0 x0 in every state row and the scaled-down u0 in every input row; the status is recorded
+ *   sub-steps s = 0..n_keep-1, ONE launch for all of them:
+ *               u_s     = uopt[s / r] * u_factor + u_offset            (scale_up of the plan row of the controller step that has fired)
+ *               x_s+1   = A_p[i] x_s + B_p[i] u_s + d_p[i] (+ w_s), i the plant's nearest point to x_s
+ *               y_s+1   = (C x_s+1 + y_ref) + v_s, or read from Y_plant
+ *               push (y_s+1, u_s) -- with U_applied: (y_s+1, U_applied_s) -- scaled down, into the member's ring
+ * Not offered: the start-up phase before t_delay, the Y= re-projection of the measurement, input clipping, dU rows, input_nullspace,
+ * nonlinear_observer, weighting-mode plants, the lifted model as its own plant.  The reference reads its input tape at its own knots,
+ * so input_hold changes nothing and is not a parameter.
+ * The loop works on the skoop_t handle's ring and advances its head and count: do not push to the handle elsewhere between a reset and
+ * the end of the runs that follow.  create refuses (with a message): n_lift > 96, n_u > 16, a plant with n_x > 128 or n_u != the
+ * model's, a plant without C or y_ref, a QP with a trust region or dU rows or whose n_x is not the lift's width,
+ * |Ts / dt_sim - round(Ts / dt_sim)| > 1e-9, rollout_horizon outside 1..N, an advance kernel beyond 160 KiB of LDS.  The lift handle and
+ * the plant must outlive the loop.
+ * ===================================================================================================== */
+typedef struct skoop_loop skoop_loop_t;
+/* A (n_lift x n_lift), B (n_lift x n_u): the lifted model at Ts; plant: pre-discretised at dt_sim; C (n_y x n_plant), y_ref (n_y): the
+ * plant's measurement (NULL without a plant); u0 (n_u) raw, NULL: zeros */
+int skoop_loop_create(skoop_loop_t **out, skoop_t *h, const slocp_problem *prob, const double *A, const double *B, double Ts,
+                      stpwl_t *plant /* NULL: replay only */, const double *C, const double *y_ref, const double *u0, double dt_sim,
+                      int rollout_horizon, int64_t max_steps_per_run);
+int skoop_loop_destroy(skoop_loop_t *h);
+/* t (T, increasing), z (T x n_z of the QP), u_des (T x n_u, scaled down as the QP's inputs are) or NULL, phase (batch) or NULL = zeros */
+int skoop_loop_set_target(skoop_loop_t *h, int T, const double *t, const double *z, const double *u_des, const double *phase);
+/* x0 (batch x n_plant) plant states at the first solve, or y0 (batch x n_y) without a plant; y_hist (batch x delays x n_y), u_hist
+ * (batch x delays x n_u) raw, oldest first (NULL when delays = 0); u_prev0 (batch x n_u) raw, NULL: u0; v0 (batch x n_y) or NULL */
+int skoop_loop_reset(skoop_loop_t *h, const double *x0, const double *y0, const double *y_hist, const double *u_hist,
+                     const double *u_prev0, const double *v0, double t_start);
+/* `periods` periods (prepare -> lift -> solve -> fix-up -> advance each) on the handle's stream, the records copied back once, ONE
+ * blocking wait.  W (periods x n_keep x batch x n_plant), V (periods x n_keep x batch x n_y) or NULL; Y_plant (batch x (S + 1) x n_y) or
+ * NULL: the measurements are read from it (row 0 is where the run starts and is not read); U_applied (batch x S x n_u) or NULL: the
+ * inputs pushed into the ring.  With S = periods n_keep: X (batch x (S + 1) x n_plant), Y (batch x (S + 1) x n_y), U (batch x S x n_u),
+ * all raw, row 0 = where the run started; Xlift (periods x batch x n_lift) the requests; J, status, iters (periods x batch). */
+int skoop_loop_run(skoop_loop_t *h, int periods, const double *W, const double *V, const double *Y_plant, const double *U_applied,
+                   double *X, double *Y, double *U, double *Xlift, double *J, int32_t *status, int32_t *iters);   /* any record may be NULL */
+/* The solver inputs / the plan (after the fix-up) of the last period; any may be NULL */
+int skoop_loop_last_inputs(skoop_loop_t *h, double *x0, double *z, double *zf, double *u_des);
+int skoop_loop_last_plan(skoop_loop_t *h, double *xopt, double *uopt);
+int skoop_loop_stats(skoop_loop_t *h, int64_t *steps, int64_t *waits_last_run);
+/* The fix-up kernel alone on host arrays: the previous plan (NULL when first), the QP's answer xopt (batch x (N+1) x n_lift), uopt
+ * (batch x N x n_u), the request's x0 (batch x n_lift), status (batch) -> the plan after the fix-up. */
+int skoop_loop_fixup(skoop_loop_t *h, const double *xopt_prev, const double *uopt_prev, const double *xopt, const double *uopt,
+                     const double *x0, const int32_t *status, int first, double *xopt_out, double *uopt_out);
+/* The advance kernel alone: plans uopt (batch x N x n_u), plant states x (batch x n_plant; NULL without a plant), W (n_keep x batch x
+ * n_plant) / V (n_keep x batch x n_y) or NULL, Y_plant (batch x (n_keep + 1) x n_y), U_applied (batch x n_keep x n_u) or NULL -> after
+ * every sub-step X (batch x n_keep x n_plant; NULL without a plant), Y (batch x n_keep x n_y), of every sub-step U (batch x n_keep x
+ * n_u) and the plant's point idx (batch x n_keep; -1 without a plant).  It pushes into the lift handle's ring as it stands and advances
+ * its head and count; the loop needs a reset before its next run. */
+int skoop_loop_advance(skoop_loop_t *h, const double *uopt, const double *x, const double *W, const double *V, const double *Y_plant,
+                       const double *U_applied, double *X, double *Y, double *U, int32_t *idx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,9 +25,10 @@ __device__ __forceinline__ double out_row(MP M, int e, int n, XP x) {
     return v;
 }
 
-// The measurement ((C x)_e + y_ref[e]) + noise[iv], in this order; y_ref and noise may each be null (that addend is then left out)
-template <typename XP>
-__device__ __forceinline__ double measure_row(cgptr Cm, int e, int n, XP x, cgptr y_ref, cgptr noise, size_t iv) {
+// The measurement ((C x)_e + y_ref[e]) + noise[iv], in this order; y_ref and noise may each be null (that addend is then left out).
+// C and y_ref are in global memory or in LDS.
+template <typename MP, typename XP, typename RP>
+__device__ __forceinline__ double measure_row(MP Cm, int e, int n, XP x, RP y_ref, cgptr noise, size_t iv) {
     double v = out_row(Cm, e, n, x);
     if (y_ref != nullptr) v += y_ref[e];
     if (noise != nullptr) v += noise[iv];
