@@ -202,7 +202,10 @@ int stpwl_linearize_weighted(stpwl_t *h, const double *X, int64_t B, double beta
 /* TPWL.discretize_dynamics (tpwl.py:272-297; zoh: sofacontrol/utils.py:302-335 zoh_affine) for `batch` continuous affine models
  * xdot = A x + B u + d at once: the stored points of pre_discretize (tpwl.py:299-322), the blended model of weighting-mode TPWL
  * (tpwl.py:244-250).  method: 0 fe, 1 be, 2 bil, 3 zoh.  A (batch x n x n), B (batch x n x m), d (batch x n) -> same shapes.
- * SRH_ENUMERIC if a model's I - c A is singular. */
+ * SRH_ENUMERIC if a model's I - c A is singular ("singular matrix (model i)"), and, for be, bil and zoh, if A, B or d of a model
+ * holds a NaN or an Inf anywhere ("non-finite model (model i)": tested on the inputs as they are loaded, so it takes precedence over
+ * "singular" for that model); i is the lowest failing index of the batch, the models that did not fail are written, the failed ones'
+ * outputs are left untouched.  fe is elementwise, as the reference is: non-finite entries pass through and the call returns SRH_OK. */
 int stpwl_discretize(int method, int n, int m, int64_t batch, const double *A, const double *B, const double *d, double dt,
                      double *Ad, double *Bd, double *dd);
 int stpwl_discretize_dev(int method, int n, int m, int64_t batch, const double *A_dev, const double *B_dev, const double *d_dev,

@@ -38,6 +38,9 @@ __device__ __forceinline__ void dz_product(const double *__restrict__ X, const d
     __syncthreads();
 }
 
+// A NaN or an Inf, by its exponent field (no comparison, no fmax / fmin: both drop a NaN operand)
+__device__ __forceinline__ bool dz_nonfinite(double v) { return (__double2hiint(v) & 0x7ff00000) == 0x7ff00000; }
+
 // Gauss-Jordan with partial pivoting on the LDS tableau T (rows x ld): the first `rows` columns hold the matrix, columns rows..cols-1
 // the right-hand sides; on return those columns hold the solutions.  Returns false on a zero pivot.
 __device__ inline bool dz_gauss_jordan(lptr T, int rows, int cols, int ld, lptr red, liptr ired) {
@@ -107,15 +110,22 @@ __global__ __launch_bounds__(DZ_NT) void discretize_kernel(DiscArgs a) {
         const int cols = 2 * n + m + 1, ld = cols | 1;
         lptr T = (lptr)smem, red = T + (size_t)n * ld;
         liptr ired = (liptr)(red + 8 + n);
+        // a NaN or Inf anywhere in A, B, d: every thread tests what it stages, the flag (ired[1]) is raised by plain stores
+        if (tid == 0) ired[1] = 0;
+        __syncthreads();
+        bool bad = false;
         for (int e = tid; e < n * n; e += nt) {
             const int i = e / n, j = e - i * n;
             const double id = (i == j) ? 1.0 : 0.0, ca = c * A[e];
+            bad |= dz_nonfinite(A[e]);
             T[i * ld + j] = id - ca;
             T[i * ld + n + j] = a.method == 1 ? id : id + ca;
         }
-        for (int e = tid; e < n * m; e += nt) { const int i = e / m, j = e - i * m; T[i * ld + 2 * n + j] = dt * B[e]; }
-        for (int i = tid; i < n; i += nt) T[i * ld + 2 * n + m] = dt * d[i];
+        for (int e = tid; e < n * m; e += nt) { const int i = e / m, j = e - i * m; bad |= dz_nonfinite(B[e]); T[i * ld + 2 * n + j] = dt * B[e]; }
+        for (int i = tid; i < n; i += nt) { bad |= dz_nonfinite(d[i]); T[i * ld + 2 * n + m] = dt * d[i]; }
+        if (bad) ired[1] = 1;
         __syncthreads();
+        if (ired[1]) { if (tid == 0) a.info[b] = 2; return; }
         const bool ok = dz_gauss_jordan(T, n, cols, ld, red, ired);
         if (!ok) { if (tid == 0) a.info[b] = 1; return; }
         for (int e = tid; e < n * n; e += nt) { const int i = e / n, j = e - i * n; Ad[e] = T[i * ld + n + j]; }
@@ -128,15 +138,23 @@ __global__ __launch_bounds__(DZ_NT) void discretize_kernel(DiscArgs a) {
     const size_t N2 = (size_t)NP * NP;
     double *M = a.ws + b * 7 * N2, *M2 = M + N2, *M4 = M2 + N2, *M6 = M4 + N2, *W = M6 + N2, *U = W + N2, *V = U + N2;
     lptr red = (lptr)smem;                               // reductions; the tableau of the solve behind it
-    // M = [[A, B, d], [0, 0, 0]] dt, its 1-norm (largest column sum)
+    // M = [[A, B, d], [0, 0, 0]] dt, its 1-norm (largest column sum); a NaN or Inf entry raises the flag as in be / bil (the norm
+    // below cannot tell: fmax drops a NaN column sum)
+    liptr flag = (liptr)(red + 8 + NP) + 1;
+    if (tid == 0) *flag = 0;
+    __syncthreads();
+    bool bad = false;
     for (int e = tid; e < (int)N2; e += nt) {
         const int i = e / NP, j = e - i * NP;
         double v = 0.0;
         if (i < n) v = j < n ? A[i * n + j] : (j < n + m ? B[i * m + (j - n)] : (j == n + m ? d[i] : 0.0));
+        bad |= dz_nonfinite(v);
         M[e] = v * dt;
     }
+    if (bad) *flag = 1;
     __threadfence_block();
     __syncthreads();
+    if (*flag) { if (tid == 0) a.info[b] = 2; return; }
     double cs = 0.0;
     for (int j = tid; j < ne; j += nt) {
         double sum = 0.0;
