@@ -422,6 +422,28 @@ int silqr_solve_ssm(sssm_t *h, int mode, double dt, int N, int64_t batch, const 
                     const double *R, const double *Qf, const silqr_params *p, double *x, double *u,
                     double *K, double *cost, int32_t *iters);
 
+/* A resident iLQR plan: `batch` problems of horizon N on one pre-discretised TPWL model.  The handle owns every buffer silqr_solve
+ * allocates per call -- inputs, x, u, K, cost, iters and the kernel's work space -- and launches the same kernel through the same
+ * launcher, so a solve gives silqr_solve's results bit for bit while the policy (K above all: batch x N x n_u x n_x doubles) may stay
+ * on the device.  Q, Qf (n_z x n_z), R (n_u x n_u); p NULL: silqr_default_params.  SSM models are not offered.  The model must outlive
+ * the plan. */
+typedef struct silqr_plan silqr_plan_t;
+int silqr_plan_create(silqr_plan_t **out, stpwl_t *h, int N, int64_t batch, const double *Q, const double *R, const double *Qf,
+                      const silqr_params *p);
+int silqr_plan_destroy(silqr_plan_t *p);
+/* z_target: shared != 0: ((N+1) x n_z), one block across PCIe, replicated for every problem on the device; shared == 0:
+ * (batch x (N+1) x n_z).  Absolute, as silqr_solve's. */
+int silqr_plan_set_target(silqr_plan_t *p, const double *z_target, int shared);
+/* u_last (batch x n_u) of the solves that follow; NULL: none (zeros), as a NULL u_last of silqr_solve */
+int silqr_plan_set_u_last(silqr_plan_t *p, const double *u_last);
+/* One solve from host x0 (batch x n_x), u_warm (batch x N x n_u) or NULL, u_last (batch x n_u) or NULL (installed as by
+ * silqr_plan_set_u_last).  Any output may be NULL: what is not asked for does not cross PCIe. */
+int silqr_plan_solve(silqr_plan_t *p, const double *x0, const double *u_warm, const double *u_last, double *x, double *u, double *K,
+                     double *cost, int32_t *iters);
+/* The policy, cost and iterations of the last solve (host or device side); any may be NULL */
+int silqr_plan_policy(silqr_plan_t *p, double *x, double *u, double *K, double *cost, int32_t *iters);
+int silqr_plan_dims(silqr_plan_t *p, int *N, int *n_x, int *n_u, int *n_z, int64_t *batch);
+
 /* =====================================================================================================
  * LOCP (the horizon QP) and GuSTO. reference: sofacontrol/scp/locp.py, sofacontrol/scp/gusto.py
  * ===================================================================================================== */
@@ -984,6 +1006,56 @@ int skoop_loop_fixup(skoop_loop_t *h, const double *xopt_prev, const double *uop
  * its head and count; the loop needs a reset before its next run. */
 int skoop_loop_advance(skoop_loop_t *h, const double *uopt, const double *x, const double *W, const double *V, const double *Y_plant,
                        const double *U_applied, double *X, double *Y, double *U, int32_t *idx);
+
+/* =====================================================================================================
+ * Batched closed loop of the iLQR controller (tpwl.controllers.ilqr / TrajTracking), resident on the device.
+ * reference: sofacontrol/tpwl/controllers.py:199-215, examples/diamond/diamond.py:318-389 (run_ilqr)
+ * `batch` members, each with a plant state, an optional estimate, a per-step policy x_bar ((N+1) x n_x), u_bar (N x n_u),
+ * K (N x n_u x n_x) and a held input.  Controller step dt = r dt_sim; controller step j fires at simulation step j r since the last
+ * reset and reads policy row rows[j] (silqr_loop_set_rows: the host's table int(round(j dt, 4) / dt); default rows[j] = j).  A step
+ * whose row is outside 0 .. N-1, or beyond the table, applies the idle input u0.  One simulation step s:
+ *   1. if s % r == 0: u = u_bar[row] + K[row] (xl - x_bar[row]), xl the estimate with an observer, else the plant state; else u is held
+ *   2. x <- d_d[i] + A_d[i] x + B_d[i] u (+ w_s), i the plant's nearest point to x, tables at dt_sim
+ *   3. z = H x (the plant's output map)
+ *   4. with an observer: y = (C x + y_ref) + v_s, then one step of every filter with (u, y)
+ * Without an observer all steps of a run are one launch; with one, a step is advance -> filter -> record.  A run is one launch sequence
+ * on the handle's stream and ONE host wait; the held input and the step counter live in the handle.  create refuses (with a message):
+ * n_u > 16, a plant with n_x > 128, without tables at dt_sim or without an output map, a plan whose n_x, n_u, N or batch differ.
+ * Not offered: SSM plants or plans, weighting-mode plants, input clipping, re-planning during a run, the start-up phase before
+ * t_delay.  The plan, the plant and the observer must outlive the loop.
+ * ===================================================================================================== */
+typedef struct silqr_loop silqr_loop_t;
+int silqr_loop_create(silqr_loop_t **out, silqr_plan_t *plan /* NULL: uploaded policies only */, stpwl_t *plant, int N, int r, int64_t batch,
+                      int64_t max_steps_per_run);
+int silqr_loop_destroy(silqr_loop_t *h);
+/* shared != 0: x_bar ((N+1) x n_x), u_bar (N x n_u), K (N x n_u x n_x) for all members; else (batch x ...) each */
+int silqr_loop_set_policy(silqr_loop_t *h, const double *x_bar, const double *u_bar, const double *K, int shared);
+/* rows (count): the policy row of controller step j; a value outside 0 .. N-1 (and every j >= count) means the idle input */
+int silqr_loop_set_rows(silqr_loop_t *h, const int32_t *rows, int64_t count);
+int silqr_loop_set_idle_input(silqr_loop_t *h, const double *u0 /* (n_u) */);
+/* a batched EKF of the same batch, n_x and n_u, its model pre-discretised at dt_sim; NULL detaches.  The loop needs a reset afterwards. */
+int silqr_loop_set_observer(silqr_loop_t *h, sekf_batch_t *observer);
+/* plant states x0 (batch x n_x); with an observer the estimates x_hat0 (NULL: x0) and Sigma0 are installed.  The step counter returns
+ * to 0 and every member holds u0. */
+int silqr_loop_reset(silqr_loop_t *h, const double *x0, const double *x_hat0);
+/* One solve of the loop's plan from the belief where it stands on the device (the estimates with an observer, else the plant states),
+ * on the loop's stream, no wait; its x, u, K become the policy in place.  u_warm (batch x N x n_u) or NULL. */
+int silqr_loop_plan(silqr_loop_t *h, const double *u_warm);
+/* `steps` simulation steps from where the handle stands.  W (steps x batch x n_x), V (steps x batch x n_y) or NULL.  Records: X (batch x
+ * (steps + 1) x n_x) or NULL, Z (batch x (steps + 1) x n_z), row 0 = where the run started; U (batch x steps x n_u); with an observer
+ * Xhat (batch x (steps + 1) x n_x), Y (batch x steps x n_y) and ekf_status (batch: the OR of the run's filter statuses), else NULL. */
+int silqr_loop_run(silqr_loop_t *h, int64_t steps, const double *W, const double *V, double *X, double *Z, double *U, double *Xhat, double *Y,
+                   int32_t *ekf_status);
+/* The policy in use, in the shape it was installed (*shared says which); any may be NULL */
+int silqr_loop_last_policy(silqr_loop_t *h, double *x_bar, double *u_bar, double *K, int *shared);
+/* cost and iterations (batch each) of the plan's last solve */
+int silqr_loop_plan_info(silqr_loop_t *h, double *cost, int32_t *iters);
+int silqr_loop_stats(silqr_loop_t *h, int64_t *steps, int64_t *waits_last_run);
+/* The advance kernel alone (no observer) under the policy in use: plant states x (batch x n_x), held inputs u_held (batch x n_u; NULL:
+ * u0), `steps` steps with the step counter starting at step0 -> X (batch x steps x n_x), Z, U and the plant's picks idx (batch x steps,
+ * or NULL).  The handle's own state is not touched. */
+int silqr_loop_advance(silqr_loop_t *h, const double *x, const double *u_held, int64_t steps, int64_t step0, const double *W, double *X,
+                       double *Z, double *U, int32_t *idx);
 
 #ifdef __cplusplus
 }

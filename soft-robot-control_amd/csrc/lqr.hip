@@ -3,6 +3,7 @@
 // DARE), sofacontrol/lqr/ilqr.py:27-300 + sofacontrol/lqr/config.py (iLQR).
 #include "tpwl_host.h"
 #include "ssm_host.h"
+#include "ilqr_host.h"
 #include "dare_sda.h"
 
 namespace {
@@ -971,6 +972,12 @@ __global__ __launch_bounds__(NTH) void ilqr_kernel(TpwlDev T, SsmDev S, IlqrArgs
 #endif
 }
 
+// `count` copies of src (len) behind one another: a target shared by all problems of a plan, replicated on the device
+__global__ __launch_bounds__(256) void ilqr_tile_kernel(const double *src, int64_t len, int64_t count, double *dst) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + SRH_TID;
+    if (e < len * count) dst[e] = src[e % len];
+}
+
 }  // namespace
 
 extern "C" {
@@ -1046,32 +1053,31 @@ int sric_dare(const double *A, const double *B, int64_t batch, int n_x, int n_u,
     return sda::run(sda::Launch("sric_dare", dare_sda_kernel, NT, tail, gain_lds), A, B, batch, n_x, n_u, Q, R, tol, max_iter, L, P, iters);
 }
 
-static int ilqr_impl(stpwl_t *ht, sssm_t *hs, int ssm_mode, double dt, int N, int64_t batch, const double *x0,
-                     const double *z_target, const double *u_warm, const double *u_last, const double *Q,
-                     const double *R, const double *Qf, const silqr_params *p, double *x, double *u, double *K,
-                     double *cost, int32_t *iters) {
-    const int n = ht ? ht->n : hs->n, m = ht ? ht->m : hs->m, nz = ht ? ht->nz : hs->no;
-    SRH_REQUIRE(nz <= 16 && m <= 16, "silqr_solve: n_z and n_u must be <= 16");
-    silqr_params par;
-    if (p) par = *p; else silqr_default_params(&par);
-    srh::DevBuf d0, dz, duw, dul, dQ, dR, dQf, ox, ou, oK, oc, oi, work, iwork, lin;
+static size_t ilqr_lin_stride(int n, int m) { return (size_t)n * n + (size_t)n * m + n; }
+
+// the outputs and the work space of `batch` problems (lin: the SSM model's per-step Jacobians)
+static int ilqr_alloc_outputs(IlqrBufs &b, int N, int n, int m, int nz, int64_t batch, bool ssm) {
+    b.stride = (size_t)(N + 1) * n + (size_t)N * m * 3 + (size_t)N * m * m + (size_t)N * m * n + 2 * (size_t)(N + 1) * nz + 8;
     int rc;
-    const size_t stride = (size_t)(N + 1) * n + (size_t)N * m * 3 + (size_t)N * m * m + (size_t)N * m * n + 2 * (size_t)(N + 1) * nz + 8;
-    const size_t lstride = (size_t)n * n + (size_t)n * m + n;
-    if ((rc = d0.upload(x0, sizeof(double) * batch * n)) || (rc = dz.upload(z_target, sizeof(double) * batch * (N + 1) * nz)) ||
-        (rc = dQ.upload(Q, sizeof(double) * nz * nz)) || (rc = dR.upload(R, sizeof(double) * m * m)) ||
-        (rc = dQf.upload(Qf, sizeof(double) * nz * nz)) || (rc = ox.alloc(sizeof(double) * batch * (N + 1) * n)) ||
-        (rc = ou.alloc(sizeof(double) * batch * N * m)) || (rc = oK.alloc(sizeof(double) * batch * N * m * n)) ||
-        (rc = oc.alloc(sizeof(double) * batch)) || (rc = oi.alloc(sizeof(int32_t) * batch)) ||
-        (rc = work.alloc(sizeof(double) * stride * batch)) || (rc = iwork.alloc(sizeof(int32_t) * 2 * N * batch)))
+    if ((rc = b.x.alloc(sizeof(double) * batch * (N + 1) * n)) || (rc = b.u.alloc(sizeof(double) * batch * N * m)) ||
+        (rc = b.K.alloc(sizeof(double) * batch * N * m * n)) || (rc = b.cost.alloc(sizeof(double) * batch)) ||
+        (rc = b.iters.alloc(sizeof(int32_t) * batch)) || (rc = b.work.alloc(sizeof(double) * b.stride * batch)) ||
+        (rc = b.iwork.alloc(sizeof(int32_t) * 2 * N * batch)))
         return rc;
-    if (hs && (rc = lin.alloc(sizeof(double) * 2 * N * lstride * batch))) return rc;
-    if (u_warm && (rc = duw.upload(u_warm, sizeof(double) * batch * N * m))) return rc;
-    if (u_last && (rc = dul.upload(u_last, sizeof(double) * batch * m))) return rc;
-    IlqrArgs a{N, n, m, nz, par, d0.as<double>(), dz.as<double>(), u_warm ? duw.as<double>() : nullptr,
-               u_last ? dul.as<double>() : nullptr, dQ.as<double>(), dR.as<double>(), dQf.as<double>(), ox.as<double>(),
-               ou.as<double>(), oK.as<double>(), oc.as<double>(), oi.as<int>(), work.as<double>(), iwork.as<int>(), stride,
-               hs ? lin.as<double>() : nullptr, ssm_mode, 0, 0, 0, 0, dt};
+    if (ssm && (rc = b.lin.alloc(sizeof(double) * 2 * N * ilqr_lin_stride(n, m) * batch))) return rc;
+    return SRH_OK;
+}
+
+// THE LAUNCHER of ilqr_kernel: the one place that chooses the variant, the LDS size and the backward pass (MFMA path 1, path 2, VALU).
+// Inputs and outputs are the device buffers of b; x0 / u_warm / u_last are device pointers (the latter two may be null).  One launch on
+// `st`, no copy, no wait.
+static int ilqr_launch(stpwl_t *ht, sssm_t *hs, int ssm_mode, double dt, int N, int64_t batch, const silqr_params &par, const IlqrBufs &b,
+                       const double *x0, const double *u_warm, const double *u_last, hipStream_t st) {
+    const int n = ht ? ht->n : hs->n, m = ht ? ht->m : hs->m, nz = ht ? ht->nz : hs->no;
+    const size_t lstride = ilqr_lin_stride(n, m);
+    IlqrArgs a{N, n, m, nz, par, x0, b.z.as<double>(), u_warm, u_last, b.Q.as<double>(), b.R.as<double>(), b.Qf.as<double>(), b.x.as<double>(),
+               b.u.as<double>(), b.K.as<double>(), b.cost.as<double>(), b.iters.as<int>(), b.work.as<double>(), b.iwork.as<int>(), b.stride,
+               hs ? b.lin.as<double>() : nullptr, ssm_mode, 0, 0, 0, 0, dt};
     if (hs && !getenv("SRH_SSM_DENSE_JACOBIAN")) {
         const std::vector<int> er = ssm_exponents(hs->n, hs->order_r);
         a.jl_cap = ssm::jacobian_list_cap(er.data(), hs->nr, hs->n);
@@ -1118,7 +1124,7 @@ static int ilqr_impl(stpwl_t *ht, sssm_t *hs, int ssm_mode, double dt, int N, in
 #define X(MD, NX, MU, TH)                                                                                                       \
     if (!launched && model == MD && (NX == 0 || n == NX) && (MU == 0 || m == MU) && threads == TH) {                            \
         SRH_CHECK_HIP(hipFuncSetAttribute((const void *)ilqr_kernel<MD, NX, MU, TH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        ilqr_kernel<MD, NX, MU, TH><<<(unsigned)batch, TH, lds>>>(ht ? ht->view() : TpwlDev{}, hs ? hs->view() : SsmDev{}, a);  \
+        ilqr_kernel<MD, NX, MU, TH><<<(unsigned)batch, TH, lds, st>>>(ht ? ht->view() : TpwlDev{}, hs ? hs->view() : SsmDev{}, a); \
         launched = true;                                                                                                        \
     }
         SRH_ILQR_VARIANTS(X)
@@ -1126,12 +1132,35 @@ static int ilqr_impl(stpwl_t *ht, sssm_t *hs, int ssm_mode, double dt, int N, in
         SRH_REQUIRE(launched, "silqr_solve: no kernel variant for model %d, n_x %d, n_u %d, %d threads", model, n, m, threads);
     }
     SRH_CHECK_HIP(hipGetLastError());
-    SRH_CHECK_HIP(hipStreamSynchronize(nullptr));
-    if ((rc = ox.download(x, sizeof(double) * batch * (N + 1) * n)) || (rc = ou.download(u, sizeof(double) * batch * N * m)) ||
-        (rc = oK.download(K, sizeof(double) * batch * N * m * n)))
+    return SRH_OK;
+}
+
+// the host-pointer call: make the buffers, call the launcher, copy back
+static int ilqr_impl(stpwl_t *ht, sssm_t *hs, int ssm_mode, double dt, int N, int64_t batch, const double *x0,
+                     const double *z_target, const double *u_warm, const double *u_last, const double *Q,
+                     const double *R, const double *Qf, const silqr_params *p, double *x, double *u, double *K,
+                     double *cost, int32_t *iters) {
+    const int n = ht ? ht->n : hs->n, m = ht ? ht->m : hs->m, nz = ht ? ht->nz : hs->no;
+    SRH_REQUIRE(nz <= 16 && m <= 16, "silqr_solve: n_z and n_u must be <= 16");
+    silqr_params par;
+    if (p) par = *p; else silqr_default_params(&par);
+    IlqrBufs b;
+    int rc;
+    if ((rc = b.x0.upload(x0, sizeof(double) * batch * n)) || (rc = b.z.upload(z_target, sizeof(double) * batch * (N + 1) * nz)) ||
+        (rc = b.Q.upload(Q, sizeof(double) * nz * nz)) || (rc = b.R.upload(R, sizeof(double) * m * m)) ||
+        (rc = b.Qf.upload(Qf, sizeof(double) * nz * nz)) || (rc = ilqr_alloc_outputs(b, N, n, m, nz, batch, hs != nullptr)))
         return rc;
-    if (cost && (rc = oc.download(cost, sizeof(double) * batch))) return rc;
-    if (iters && (rc = oi.download(iters, sizeof(int32_t) * batch))) return rc;
+    if (u_warm && (rc = b.uw.upload(u_warm, sizeof(double) * batch * N * m))) return rc;
+    if (u_last && (rc = b.ul.upload(u_last, sizeof(double) * batch * m))) return rc;
+    if ((rc = ilqr_launch(ht, hs, ssm_mode, dt, N, batch, par, b, b.x0.as<double>(), u_warm ? b.uw.as<double>() : nullptr,
+                          u_last ? b.ul.as<double>() : nullptr, nullptr)))
+        return rc;
+    SRH_CHECK_HIP(hipStreamSynchronize(nullptr));
+    if ((rc = b.x.download(x, sizeof(double) * batch * (N + 1) * n)) || (rc = b.u.download(u, sizeof(double) * batch * N * m)) ||
+        (rc = b.K.download(K, sizeof(double) * batch * N * m * n)))
+        return rc;
+    if (cost && (rc = b.cost.download(cost, sizeof(double) * batch))) return rc;
+    if (iters && (rc = b.iters.download(iters, sizeof(int32_t) * batch))) return rc;
     return SRH_OK;
 }
 
@@ -1154,6 +1183,114 @@ int silqr_solve_ssm(sssm_t *h, int mode, double dt, int N, int64_t batch, const 
     SRH_REQUIRE(h->n == h->no, "silqr_solve_ssm: the reduced -> observed map needs n_x == n_o");
     SRH_REQUIRE(N > 0 && batch > 0, "silqr_solve_ssm: bad dimensions");
     return ilqr_impl(nullptr, h, mode, dt, N, batch, x0, z_target, u_warm, u_last, Q, R, Qf, p, x, u, K, cost, iters);
+}
+
+// ---- the resident plan: the buffers of ilqr_impl kept on a handle (ilqr_host.h); the same launcher
+
+int silqr_plan_create(silqr_plan_t **out, stpwl_t *h, int N, int64_t batch, const double *Q, const double *R, const double *Qf,
+                      const silqr_params *p) {
+    SRH_REQUIRE(out && h && Q && R && Qf, "silqr_plan_create: null argument");
+    *out = nullptr;
+    SRH_REQUIRE(h->has_discrete, "silqr_plan_create: model has not been pre-discretised");
+    SRH_REQUIRE(h->nz > 0, "silqr_plan_create: Need to set output or meas. model");
+    SRH_REQUIRE(N > 0 && batch > 0, "silqr_plan_create: bad dimensions");
+    const int n = h->n, m = h->m, nz = h->nz;
+    SRH_REQUIRE(nz <= 16 && m <= 16, "silqr_plan_create: n_z and n_u must be <= 16");
+    silqr_plan *q = new silqr_plan();
+    q->model = h; q->N = N; q->n = n; q->m = m; q->nz = nz; q->batch = batch;
+    if (p) q->par = *p; else silqr_default_params(&q->par);
+    int rc;
+    if ((rc = q->x0.alloc(sizeof(double) * batch * n)) || (rc = q->z.alloc(sizeof(double) * batch * (N + 1) * nz)) ||
+        (rc = q->uw.alloc(sizeof(double) * batch * N * m)) || (rc = q->ul.alloc(sizeof(double) * batch * m)) ||
+        (rc = q->Q.upload(Q, sizeof(double) * nz * nz)) || (rc = q->R.upload(R, sizeof(double) * m * m)) ||
+        (rc = q->Qf.upload(Qf, sizeof(double) * nz * nz)) || (rc = ilqr_alloc_outputs(*q, N, n, m, nz, batch, false))) {
+        delete q;
+        return rc;
+    }
+    *out = q;
+    return SRH_OK;
+}
+
+int silqr_plan_destroy(silqr_plan_t *p) {
+    SRH_REQUIRE(p, "silqr_plan_destroy: null handle");
+    (void)hipDeviceSynchronize();
+    delete p;
+    return SRH_OK;
+}
+
+int silqr_plan_set_target(silqr_plan_t *p, const double *z_target, int shared) {
+    SRH_REQUIRE(p, "silqr_plan_set_target: null handle");
+    SRH_REQUIRE(z_target, "silqr_plan_set_target: null argument");
+    SRH_CHECK_HIP(hipDeviceSynchronize());
+    const size_t len = (size_t)(p->N + 1) * p->nz;
+    if (!shared) {
+        SRH_CHECK_HIP(hipMemcpy(p->z.p, z_target, sizeof(double) * p->batch * len, hipMemcpyHostToDevice));
+    } else {
+        // one block across PCIe, replicated on the device
+        srh::DevBuf one;
+        int rc = one.upload(z_target, sizeof(double) * len);
+        if (rc) return rc;
+        ilqr_tile_kernel<<<(unsigned)srh::cdiv((int64_t)len * p->batch, 256), 256>>>(one.as<double>(), (int64_t)len, p->batch, p->z.as<double>());
+        SRH_CHECK_HIP(hipGetLastError());
+        SRH_CHECK_HIP(hipStreamSynchronize(nullptr));
+    }
+    p->has_target = true;
+    return SRH_OK;
+}
+
+int silqr_plan_set_u_last(silqr_plan_t *p, const double *u_last) {
+    SRH_REQUIRE(p, "silqr_plan_set_u_last: null handle");
+    SRH_CHECK_HIP(hipDeviceSynchronize());
+    p->has_ul = u_last != nullptr;
+    if (u_last) SRH_CHECK_HIP(hipMemcpy(p->ul.p, u_last, sizeof(double) * p->batch * p->m, hipMemcpyHostToDevice));
+    return SRH_OK;
+}
+
+int silqr_plan_solve_dev(silqr_plan *p, const double *x0_dev, const double *u_warm_dev, hipStream_t stream) {
+    SRH_REQUIRE(p && x0_dev, "silqr_plan_solve_dev: null argument");
+    SRH_REQUIRE(p->has_target, "silqr_plan_solve_dev: no target yet (call silqr_plan_set_target first)");
+    int rc = ilqr_launch(p->model, nullptr, 0, 0.0, p->N, p->batch, p->par, *p, x0_dev, u_warm_dev, p->has_ul ? p->ul.as<double>() : nullptr, stream);
+    if (rc) return rc;
+    p->solved = true;
+    return SRH_OK;
+}
+
+int silqr_plan_policy(silqr_plan_t *p, double *x, double *u, double *K, double *cost, int32_t *iters) {
+    SRH_REQUIRE(p, "silqr_plan_policy: null handle");
+    SRH_REQUIRE(p->solved, "silqr_plan_policy: the plan has not been solved yet");
+    SRH_CHECK_HIP(hipDeviceSynchronize());
+    const size_t D = sizeof(double), B = (size_t)p->batch, N = p->N, n = p->n, m = p->m;
+    int rc;
+    if ((x && (rc = p->x.download(x, D * B * (N + 1) * n))) || (u && (rc = p->u.download(u, D * B * N * m))) ||
+        (K && (rc = p->K.download(K, D * B * N * m * n))) || (cost && (rc = p->cost.download(cost, D * B))) ||
+        (iters && (rc = p->iters.download(iters, sizeof(int32_t) * B))))
+        return rc;
+    return SRH_OK;
+}
+
+int silqr_plan_solve(silqr_plan_t *p, const double *x0, const double *u_warm, const double *u_last, double *x, double *u, double *K,
+                     double *cost, int32_t *iters) {
+    SRH_REQUIRE(p, "silqr_plan_solve: null handle");
+    SRH_REQUIRE(x0, "silqr_plan_solve: null argument");
+    SRH_REQUIRE(p->has_target, "silqr_plan_solve: no target yet (call silqr_plan_set_target first)");
+    const size_t D = sizeof(double), B = (size_t)p->batch;
+    int rc;
+    if ((rc = silqr_plan_set_u_last(p, u_last))) return rc;
+    SRH_CHECK_HIP(hipMemcpy(p->x0.p, x0, D * B * p->n, hipMemcpyHostToDevice));
+    if (u_warm) SRH_CHECK_HIP(hipMemcpy(p->uw.p, u_warm, D * B * p->N * p->m, hipMemcpyHostToDevice));
+    if ((rc = silqr_plan_solve_dev(p, p->x0.as<double>(), u_warm ? p->uw.as<double>() : nullptr, nullptr))) return rc;
+    SRH_CHECK_HIP(hipStreamSynchronize(nullptr));
+    return silqr_plan_policy(p, x, u, K, cost, iters);
+}
+
+int silqr_plan_dims(silqr_plan_t *p, int *N, int *n_x, int *n_u, int *n_z, int64_t *batch) {
+    SRH_REQUIRE(p, "silqr_plan_dims: null handle");
+    if (N) *N = p->N;
+    if (n_x) *n_x = p->n;
+    if (n_u) *n_u = p->m;
+    if (n_z) *n_z = p->nz;
+    if (batch) *batch = p->batch;
+    return SRH_OK;
 }
 
 }  // extern "C"
