@@ -847,6 +847,51 @@ int skoop_mpc_step(skoop_mpc_t *plan, const double *y, const double *u_prev, con
 int skoop_mpc_set_timing(skoop_mpc_t *plan, int on);
 int skoop_mpc_stats(skoop_mpc_t *plan, int64_t *steps, int64_t *waits_last_step, double *ms);
 
+/* Koopman model identification (EDMD, csrc/koopman_fit.hip): records (y, u) -> a model (A, B) for the lift of an skoop_t handle.
+ * THE FIT (this text defines it; the reference's model came from an external MATLAB trainer that is not part of it):
+ *   records   E episodes, each y (T x n_y), u (T x m), raw; `stride` s >= 1 keeps rows 0, s, 2s, .. of every episode (a record at
+ *             dt_sim read at Ts = s dt_sim; row i s carries the input held over the step); T' = the rows kept.
+ *   zeta_i    [y_i, y_{i-1} .. y_{i-d}, u_{i-1} .. u_{i-d}] of scaled samples for kept row i >= d: what skoop_embed_lift builds;
+ *             psi_i = psi(zeta_i), the handle's observables (the constant last unless dmd).
+ *             A scaled sample is (v - offset) / factor rounded once: within one ulp of the lift's own, which rounds the subtraction
+ *             and the division separately (a term of G is a product of up to 2 degree samples and inherits each one's error).
+ *   v_i       scale_down(u[i + u_lag]); u_lag = 0: row i holds the input applied AFTER y_i (the closed loops' results), u_lag = 1:
+ *             the input applied BEFORE y_i (the rows KoopmanData.add_measurement and the device ring keep).
+ *   pairs     (i, i + 1) for d <= i <= T' - 2, never across an episode; an episode with T' <= d + 1 contributes nothing.
+ *   sums      Phi_i = [psi_i; v_i] (n = n_psi + m): G = sum Phi_i Phi_i^T (n x n), R = sum psi_{i+1} Phi_i^T (n_psi x n),
+ *             Q = sum |psi_{i+1}|^2, S = the number of pairs.
+ *   model     [A B] = R (G + ridge I)^-1, ridge >= 0: the minimiser of sum |psi_{i+1} - A psi_i - B v_i|^2 + ridge |[A B]|_F^2.
+ *   scaling   the handle's, or computed from the records over the kept rows: offset = (max + min) / 2, factor = (max - min) / 2
+ *             (skoop_fit_minmax; a channel with max == min is refused by name).
+ * Not offered: the trainer's L1 (lasso) constraint, sample weights, non-polynomial observables, truncation (a handle with W is
+ * refused).  Limits (SRH_EINVAL before any device call): n = n_psi + m <= 128 and the lift's own.  The sums are accumulated on f64
+ * MFMA without floating-point atomics, in an order fixed by (E, T, stride, d) and the model's shape: the same records give the same
+ * bits.  All calls on one handle are ordered by the caller (one stream, or synchronised between streams).
+ * skoop_fit_plan answers on the host (no GPU): n_psi, n, the pairs of a chunk of the accumulate kernel and its dynamic LDS; any
+ * output may be NULL; SRH_EINVAL when the shape is refused. */
+typedef struct skoop_fit skoop_fit_t;
+int skoop_fit_plan(int nzeta, int degree, int dmd, int m, int *n_psi, int *n, int *rows_per_chunk, int64_t *lds_bytes);
+int skoop_fit_create(skoop_fit_t **out, skoop_t *lift);     /* the lift handle must outlive the fit handle */
+int skoop_fit_destroy(skoop_fit_t *f);
+int skoop_fit_reset(skoop_fit_t *f);                        /* sums and pairs back to zero */
+/* records -> the four scale vectors (n_y, n_y, m, m); the reduction runs on the device in a fixed order; the _dev form takes
+ * device records and synchronises `stream` before it returns */
+int skoop_fit_minmax(const double *y, const double *u, int64_t E, int64_t T, int n_y, int m, int stride, double *y_offset,
+                     double *y_factor, double *u_offset, double *u_factor);
+int skoop_fit_minmax_dev(const double *y_dev, const double *u_dev, int64_t E, int64_t T, int n_y, int m, int stride, double *y_offset,
+                         double *y_factor, double *u_offset, double *u_factor, void *stream);
+/* y (E x T x n_y), u (E x T x m) are added to the handle's sums; may be called many times.  The _dev form is asynchronous on
+ * `stream`. */
+int skoop_fit_add(skoop_fit_t *f, const double *y, const double *u, int64_t E, int64_t T, int stride, int u_lag);
+int skoop_fit_add_dev(skoop_fit_t *f, const double *y_dev, const double *u_dev, int64_t E, int64_t T, int stride, int u_lag, void *stream);
+/* G (n x n), R (n_psi x n), Q (1), pairs (1); any may be NULL */
+int skoop_fit_sums(skoop_fit_t *f, double *G, double *R, double *Q, int64_t *pairs);
+/* A (n_psi x n_psi), B (n_psi x m).  info (optional): -1, or the failing pivot of G + ridge I -- not positive, not finite (a NaN of the
+ * records ends here), or not above n eps of its diagonal entry, where its sign would be rounding noise -- (SRH_ENUMERIC, "increase
+ * ridge"), or n when the solution holds a non-finite entry that no pivot caught (SRH_ENUMERIC); A and B are written on success only.
+ * SRH_EINVAL when no pair has been added. */
+int skoop_fit_solve(skoop_fit_t *f, double ridge, double *A, double *B, int32_t *info);
+
 /* =====================================================================================================
  * ROMPC baseline. reference: sofacontrol/baselines/rompc/rompc.py:57-89, rompc/observer.py:30-46, rompc_utils.py:52-53
  * `batch` independent loops on one linear reduced model (problem-major arrays everywhere).  One control step is
