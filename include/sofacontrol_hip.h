@@ -555,6 +555,20 @@ enum { SQP_IPM_INIT = 0, SQP_IPM_COLD, SQP_IPM_WARM, SQP_IPM_PRED, SQP_IPM_CORR,
        SQP_IPM_SCALES, SQP_IPM_VERDICT };
 int sqp_ipm_rule_replay(int phase, int n, const double *rows, const double *par, double *out, double *scal);
 
+/* The tile factorisation of K on one wave set of the lean kernels, as wave `wave` (0 .. 3) runs it: the ordered list of its events,
+ * produced on the host by the roster functions the device code calls (which waves work in which tile row, their tiles, every counter
+ * target).  K has KT x KT tiles of 16 x 16 (1 <= KT <= 8); wave 0 is the chain of diagonal factorisations, wave w >= 1 is worker w - 1.
+ *   nwk0 = 3: the full-size workgroup's set, three workers in every row (code is ignored);
+ *   nwk0 = 1: the half-size workgroup, whose waves 2 and 3 also run the front of the Newton solve.  code 0: the front only; code +k:
+ *             the front, then workers in the rows k .. KT - 2; code -k: workers in the rows 0 .. k - 1, then the front (1 <= k <= KT - 2;
+ *             any other code counts as 0).  *code_in_effect (may be NULL) receives the code used.
+ * An event is four int32: {kind, a, b, c}.  WAIT: counter a has reached b; SIGNAL: counter a += 1 (counters: 0 trailing updates finished,
+ * 1 diagonal inverses published, 2 panel tiles written, 3 early tiles of the next row); READ: tile (a, b); CHOL / PANEL / UPDATE: tile
+ * (a, b) is rewritten by that operation of tile row c; FRONT: the front of the Newton solve.  At most `cap` events are written, *count
+ * is the length of the whole list.  Needs no GPU; for tests of the protocol. */
+enum { SLEAN_EV_WAIT = 0, SLEAN_EV_SIGNAL, SLEAN_EV_READ, SLEAN_EV_CHOL, SLEAN_EV_PANEL, SLEAN_EV_UPDATE, SLEAN_EV_FRONT };
+int slean_roster_replay(int KT, int code, int nwk0, int wave, int cap, int32_t *events, int32_t *count, int32_t *code_in_effect);
+
 /* GuSTO.solve (gusto.py:283-487) on a pre-discretised nn-TPWL model, `batch` independent rollouts:
  *   x0 (batch x n_x), u_init (batch x N x n_u), x_init (batch x (N+1) x n_x), z (batch x (N+1) x n_z)
  *   or NULL, zf, u_des as slocp_solve; x_char / f_char (n_x,) or NULL (ones); dt = horizon step.
@@ -644,6 +658,9 @@ int sgusto_plan_info(sgusto_plan_t *plan, srh_kernel_info *info);
  * one TPWL region: the condensed matrix is block-Toeplitz and is built from one chain of N products); 0 for a plan without
  * the lean kernel, before the first solve, and for a plan created under SRH_LEAN_NO_TOEPLITZ=1.  Waits for the solve. */
 int sgusto_plan_single_region_qps(sgusto_plan_t *plan, int32_t *count);
+/* The row roster of the half-size lean kernel's tile factorisation that this plan's constants were built with (SRH_LEAN_ROSTER=<code>
+ * overrides the default when the plan is created; see slean_roster_replay for the codes); 0 for every other kernel. */
+int sgusto_plan_lean_roster(const sgusto_plan_t *plan, int32_t *code);
 int sgusto_plan_solve(sgusto_plan_t *plan, const double *x0, const double *u_init, const double *x_init,
                       const double *z, const double *zf, const double *u_des, double *xopt, double *uopt,
                       double *zopt, int32_t *iters, int32_t *status, double *trace);

@@ -360,6 +360,66 @@ int sqp_ipm_rule_replay(int phase, int n, const double *rows, const double *par,
     return SRH_OK;
 }
 
+// The set factorisation of the lean kernels as one wave sees it (ql::tile_cholesky_set and the split of ql::ipm_box4 around it), written with
+// the roster functions the device code calls: which rows the wave works in, its tiles there and every counter target come from them.
+int slean_roster_replay(int KT, int code, int nwk0, int wave, int cap, int32_t *events, int32_t *count, int32_t *code_in_effect) {
+    SRH_REQUIRE(events && count && KT >= 1 && KT <= 8 && wave >= 0 && wave <= 3 && (nwk0 == 1 || nwk0 == 3) && cap >= 0, "slean_roster_replay: bad argument");
+    if (nwk0 != 1 || !ql::roster_legal(KT, code)) code = 0;          // (the knob's rule, scp_host.h: only the half-size workgroup has rosters)
+    if (code_in_effect) *code_in_effect = code;
+    int n = 0;
+    auto ev = [&](int kind, int a, int b, int c) {
+        if (n < cap) { int32_t *e = events + 4 * (size_t)n; e[0] = kind; e[1] = a; e[2] = b; e[3] = c; }
+        ++n;
+    };
+    enum { FTRAIL = 0, FRINV = 1, FPANEL = 2, FNEXT = 3 };
+    auto chol = [&](int J) { ev(SLEAN_EV_READ, J, J, 0); ev(SLEAN_EV_CHOL, J, J, J); };
+    auto panel = [&](int J, int Jp) { ev(SLEAN_EV_READ, J, J, 0); ev(SLEAN_EV_READ, J, Jp, 0); ev(SLEAN_EV_PANEL, J, Jp, J); };
+    auto update = [&](int J, int I, int Kc) { ev(SLEAN_EV_READ, J, I, 0); ev(SLEAN_EV_READ, J, Kc, 0); ev(SLEAN_EV_READ, I, Kc, 0); ev(SLEAN_EV_UPDATE, I, Kc, J); };
+    auto rows = [&]() {
+        const int worker = wave - 1;
+        for (int J = 0; J + 1 < KT; ++J) {
+            const int nwk = ql::roster_nwk(code, nwk0, J);
+            if (!ql::roster_works(code, nwk0, worker, J)) continue;
+            ev(SLEAN_EV_WAIT, FRINV, J + 1, 0);
+            ev(SLEAN_EV_WAIT, FTRAIL, ql::roster_trail_target(code, nwk0, J), 0);
+            for (int Jp = ql::roster_panel_first(worker, J); Jp < KT; Jp += nwk) panel(J, Jp);
+            ev(SLEAN_EV_SIGNAL, FPANEL, 0, 0);
+            ev(SLEAN_EV_WAIT, FPANEL, ql::roster_panel_target(code, nwk0, J), 0);
+            const int ntr = ql::roster_ntr(KT, J);
+            for (int t = worker + 1; t < ntr; t += nwk) {
+                int I, Kc;
+                bool first;
+                ql::roster_trailing_tile(KT, J, t, I, Kc, first);
+                update(J, I, Kc);
+                if (first) ev(SLEAN_EV_SIGNAL, FNEXT, 0, 0);
+            }
+            ev(SLEAN_EV_SIGNAL, FTRAIL, 0, 0);
+        }
+    };
+    if (wave == 0) {
+        chol(0);
+        ev(SLEAN_EV_SIGNAL, FRINV, 0, 0);
+        for (int J = 0; J + 1 < KT; ++J) {
+            ev(SLEAN_EV_WAIT, FNEXT, ql::roster_next_target(J), 0);
+            panel(J, J + 1);
+            ev(SLEAN_EV_SIGNAL, FPANEL, 0, 0);
+            update(J, J + 1, J + 1);
+            chol(J + 1);
+            ev(SLEAN_EV_SIGNAL, FRINV, 0, 0);
+        }
+    } else if (nwk0 == 3) {
+        rows();                                                    // the full-size workgroup: three workers, the front is another set's
+    } else {
+        const bool has_front = wave >= 2, rows_first = wave == 1 || code < 0, has_rows = wave == 1 || code != 0;
+        for (int ph = 0; ph < 2; ++ph) {
+            if ((ph == 0) == rows_first) { if (has_rows) rows(); }
+            else if (has_front) ev(SLEAN_EV_FRONT, 0, 0, 0);
+        }
+    }
+    *count = n;
+    return SRH_OK;
+}
+
 int sgusto_plan_create(sgusto_plan_t **out, stpwl_t *h, const slocp_problem *prob, const sgusto_params *par,
                        double dt, int64_t batch, const double *x_char, const double *f_char, int max_trace) {
     SRH_REQUIRE(out && h && prob && par, "sgusto_plan_create: null argument");
@@ -586,6 +646,12 @@ int sgusto_plan_single_region_qps(sgusto_plan_t *pl, int32_t *count) {
         SRH_CHECK_HIP(hipDeviceSynchronize());          // (as sgusto_plan_info: the last solve may sit on a caller's stream)
         SRH_CHECK_HIP(hipMemcpy(count, pl->single.p, sizeof(int32_t), hipMemcpyDeviceToHost));
     }
+    return SRH_OK;
+}
+
+int sgusto_plan_lean_roster(const sgusto_plan_t *pl, int32_t *code) {
+    SRH_REQUIRE(pl && code, "sgusto_plan_lean_roster: null argument");
+    *code = pl->C.dims.lean_roster;
     return SRH_OK;
 }
 

@@ -45,6 +45,9 @@ struct QPDims {
                         // (ql::newton_back) instead of a second product with G
     int lean_toeplitz;  // 1: a QP whose horizon lies in one TPWL region condenses by the restricted recursion (ql::condense_single);
                         // 0 (SRH_LEAN_NO_TOEPLITZ=1 when the constants are built): always the general recursion
+    int lean_roster;    // half-size lean workgroup: row roster of the set factorisation (ql::roster_nwk).  0: waves 2, 3 run the Newton front
+                        // only; +k: the front, then workers in the tile rows k .. KT - 2; -k: workers in the rows < k, then the front
+                        // (SRH_LEAN_ROSTER=<code> when the constants are built; a code that is not legal for KT counts as 0)
 };
 
 // The QP without its trust-region rows (the prescreen of qp::solve, the condensed and the lean interior points): the row counts that follow

@@ -103,6 +103,46 @@ __host__ __device__ inline int gram_stage_j0(const QPDims &d) {
     while (goff(d.N, d.m, NP) - goff(j, d.m, NP) > cap) ++j;
     return j;
 }
+// ------------------------------------------------------------------ the row roster of tile_cholesky_set
+// Who works in tile row J < KT - 1 of the set factorisation, and every counter target that follows from it, stated once for the device code
+// and for the host replay (slean_roster_replay, tests/test_lean_roster_cpu.py).  Wave 0 of the protocol is the chain (the one-wave
+// factorisations and the tile (J, J + 1)), wave w >= 1 is worker w - 1.  A roster is a code and the uniform worker count nwk0 behind code 0:
+//    0: nwk0 workers in every row (the full-size workgroup: 3; the half-size one: wave 1 alone)
+//   +k: wave 1 alone in the rows < k, waves 1, 2, 3 in the rows k .. KT - 2   (half-size: waves 2, 3 come from the Newton front)
+//   -k: waves 1, 2, 3 in the rows < k, wave 1 alone from row k on              (half-size: waves 2, 3 leave for the Newton front)
+// with 1 <= k <= KT - 2.  The workers of a row are always the waves 1 .. nwk(J): a wave skips a row it does not work in without
+// touching a counter, and enters a row behind the CUMULATIVE arrivals of the rows before (whose acquire makes their tiles visible to it).
+constexpr int LEAN_ROSTER_DEFAULT = -1;      // the half-size kernel's code unless SRH_LEAN_ROSTER says otherwise (chosen by measurement: DESIGN.md section 39)
+__host__ __device__ inline bool roster_legal(int KT, int code) { const int k = code < 0 ? -code : code; return code == 0 || (k >= 1 && k <= KT - 2); }
+__host__ __device__ inline int roster_nwk(int code, int nwk0, int J) {
+    if (code == 0) return nwk0;
+    return (code > 0 ? J >= code : J < -code) ? 3 : 1;
+}
+__host__ __device__ inline bool roster_works(int code, int nwk0, int worker, int J) { return worker < roster_nwk(code, nwk0, J); }
+// Ftrail in front of row J: one arrival per worker and row before (code 0: nwk0 J)
+__host__ __device__ inline int roster_trail_target(int code, int nwk0, int J) {
+    if (code == 0) return nwk0 * J;
+    const int wide = code > 0 ? (J > code ? J - code : 0) : (J < -code ? J : -code);      // rows before J with three workers
+    return J + 2 * wide;
+}
+// Fpanel when the whole panel of row J is written: the chain and every worker, rows 0 .. J (code 0: (nwk0 + 1) (J + 1))
+__host__ __device__ inline int roster_panel_target(int code, int nwk0, int J) { return roster_trail_target(code, nwk0, J + 1) + J + 1; }
+// Fnext in front of the chain's row J: two arrivals per row before, from the row's workers 0 and 1 (worker 0 alone where it is the only one)
+__host__ __device__ inline int roster_next_target(int J) { return 2 * J; }
+// a worker's panel tiles of row J: (J, Jp), Jp = first, first + nwk, .. < KT   ((J, J + 1) is the chain's)
+__host__ __device__ inline int roster_panel_first(int worker, int J) { return J + 2 + worker; }
+// Trailing tile t of row J, 1 <= t < ntr = rem (rem + 1) / 2 with rem = KT - J - 1 (tile 0 = (J + 1, J + 1) is the chain's); worker w takes
+// t = w + 1, w + 1 + nwk, ..  The two tiles the chain needs for the NEXT row -- t = 1: (J + 1, J + 2), and (J + 2, J + 2), which changes
+// places with t = 2 -- are the first tiles of workers 0 and 1, each announced on Fnext on its own (*first).  Tile (I, Kc) -= (J, I)^T (J, Kc).
+__host__ __device__ inline int roster_ntr(int KT, int J) { const int rem = KT - J - 1; return rem * (rem + 1) / 2; }
+__host__ __device__ inline void roster_trailing_tile(int KT, int J, int t, int &I, int &Kc, bool &first) {
+    const int rem = KT - J - 1;
+    int tt = (t == 2 && rem > 2) ? rem : ((t == rem && rem > 2) ? 2 : t), Ir = 0;
+    first = (rem >= 2) && (t == 1 || tt == rem);
+    while (tt >= rem - Ir) { tt -= rem - Ir; ++Ir; }
+    I = J + 1 + Ir; Kc = I + tt;
+}
+
 __device__ inline void lds_carve(Lds &L, lptr base, const QPDims &d, int nthreads, gptr work_base = nullptr) {
     const Sizes s = sizes(d, nthreads, d.lean_j0);
     const bool half = d.lean_half != 0;
@@ -1072,8 +1112,10 @@ __device__ __forceinline__ void tile_update_reg(lptr T, const wg::qp_d4 &P, int 
     for (int qd = 0; qd < 4; ++qd) T[(kk + 4 * qd) * TS + l16] = acc[qd];
 }
 // F: three LDS counters, zero on entry.  Returns nothing: L.flag[1] = 1 iff every pivot was positive (valid after the caller's barrier).
-__device__ __forceinline__ void tile_cholesky_set(const QPDims &d, Lds &L, const Waves<true> &W, liptr F, liptr Fnext) {
-    const int KT = d.KT, wave = W.wave, lane = W.tid & 63, nwk = W.nw - 1;
+// wave: this wave's place in the protocol (0: the chain, w >= 1: worker w - 1); nwk0, roster: the row roster (roster_nwk and the targets next to
+// it) -- roster 0 is nwk0 workers in every row.  Every branch on them is scalar: they are uniform over the wave.
+__device__ __forceinline__ void tile_cholesky_set(const QPDims &d, Lds &L, int wave, int lane, int nwk0, liptr F, liptr Fnext, int roster = 0) {
+    const int KT = d.KT;
     const int l16 = lane & 15, kk = lane >> 4;
     liptr Ftrail = F, Frinv = F + 1, Fpanel = F + 2;
     if (wave == 0) {
@@ -1088,7 +1130,7 @@ __device__ __forceinline__ void tile_cholesky_set(const QPDims &d, Lds &L, const
         set_signal(Frinv);
         TC_LAP(4);
         for (int J = 0; J + 1 < KT; ++J) {
-            set_wait(Fnext, 2 * J);                               // (J, J + 1) and (J + 1, J + 1) carry the updates of row J - 1
+            set_wait(Fnext, roster_next_target(J));                // (J, J + 1) and (J + 1, J + 1) carry the updates of row J - 1
             TC_LAP(0);
             const wg::qp_d4 P = panel_tile(L, KT, J, J + 1, l16, kk);
             TC_LAP(1);
@@ -1110,21 +1152,22 @@ __device__ __forceinline__ void tile_cholesky_set(const QPDims &d, Lds &L, const
 #endif
 #undef TC_LAP
     } else {
+        const int worker = wave - 1;
         for (int J = 0; J + 1 < KT; ++J) {
+            const int nwk = roster_nwk(roster, nwk0, J);
+            if (!roster_works(roster, nwk0, worker, J)) continue;    // not in this row's roster: no counter touched
             set_wait<true>(Frinv, J + 1);
-            set_wait<true>(Ftrail, nwk * J);
-            for (int Jp = J + 2 + (wave - 1); Jp < KT; Jp += nwk) panel_tile(L, KT, J, Jp, l16, kk);      // (J, J + 1) is wave 0's
+            set_wait<true>(Ftrail, roster_trail_target(roster, nwk0, J));
+            for (int Jp = roster_panel_first(worker, J); Jp < KT; Jp += nwk) panel_tile(L, KT, J, Jp, l16, kk);      // (J, J + 1) is the chain's
             set_signal(Fpanel);
-            set_wait<true>(Fpanel, (nwk + 1) * (J + 1));
-            // tiles 1 .. ntr-1 over the workers (tile 0 = (J+1, J+1) is wave 0's).  The two tiles wave 0 needs for the NEXT row -- tile 1 =
-            // (J+1, J+2) and tile `rem` = (J+2, J+2) -- are the first tiles of workers 1 and 2 (tile `rem` changes places with tile 2),
-            // each announced on its own: wave 0 does not wait for the whole trailing update of a row (20 tiles on three waves in row 0).
-            const int rem = KT - J - 1, ntr = rem * (rem + 1) / 2, wB = nwk >= 2 ? 2 : 1;
-            for (int t = wave; t < ntr; t += nwk) {
-                int tt = (t == 2 && rem > 2) ? rem : ((t == rem && rem > 2) ? 2 : t), Ir = 0;
-                const bool first = (rem >= 2) && (t == 1 || tt == rem);
-                while (tt >= rem - Ir) { tt -= rem - Ir; ++Ir; }
-                const int I = J + 1 + Ir, Kc = I + tt;
+            set_wait<true>(Fpanel, roster_panel_target(roster, nwk0, J));
+            // tiles 1 .. ntr-1 over the workers (roster_trailing_tile): the chain does not wait for the whole trailing update of a row
+            // (20 tiles in row 0), only for the two early tiles, each announced on its own
+            const int ntr = roster_ntr(KT, J);
+            for (int t = worker + 1; t < ntr; t += nwk) {
+                int I, Kc;
+                bool first;
+                roster_trailing_tile(KT, J, t, I, Kc, first);
                 qpc::tile_update(L.B + (size_t)qpc::tile_index(I, Kc, KT) * TSZ, L.B + (size_t)qpc::tile_index(J, I, KT) * TSZ,
                                  L.B + (size_t)qpc::tile_index(J, Kc, KT) * TSZ, l16, kk);
                 if (first) set_signal(Fnext);
@@ -1757,7 +1800,7 @@ __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, co
 #endif
             auto W = half_waves(L.flag + 4);
             if (half_of_wave(wv) == 0) {
-                tile_cholesky_set(d, L, W, L.flag + 5, L.flag + 3);
+                tile_cholesky_set(d, L, W.wave, W.tid & 63, W.nw - 1, L.flag + 5, L.flag + 3);
 #ifdef SRH_PROFILE
                 if (tid == 0) L.Qu[2] = (double)(clock64() - tsplit);
 #endif
@@ -2062,15 +2105,45 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
             ++ngram;
 #endif
             // the factorisation (waves 0-1: a chain of one-wave 16 x 16 factorisations) beside the half of the Newton solve that
-            // does not need the factor (waves 2-3), see Waves
+            // does not need the factor (waves 2-3), see Waves.  Under a row roster (QPDims::lean_roster, roster_nwk) waves 2 and 3 are
+            // workers 1 and 2 of the factorisation as well, in the rows behind (code > 0) or in front of (code < 0) their Newton front:
+            // the front touches no K tile and synchronises on L.flag[4] between its two waves only, so both orders are legal.
+            // (wave indices after the ^ sw of the serial wave; every branch below is on a value uniform over the wave)
             const clptr gyd = mode == PRED ? (clptr)L.yg : (clptr) nullptr;
             const int sw = serial_wave(L);
             const int wv = __builtin_amdgcn_readfirstlane(tid >> 6) ^ sw;
+            const int rc = __builtin_amdgcn_readfirstlane(d.lean_roster);
             auto W = half_waves(L.flag + 4, sw);
-            if (half_of_wave(wv) == 0) tile_cholesky_set(d, L, W, L.flag + 5, L.flag + 3);
-            else newton_front<MSEL, true>(d, g, L, gyd, W, pf, ya_const && mode == PRED);
+#ifdef SRH_PROFILE
+            pf.last = clock64();
+            const long long tsplit = clock64();
+#endif
+            if (wv == 0) {
+                tile_cholesky_set(d, L, 0, tid & 63, 1, L.flag + 5, L.flag + 3, rc);
+#ifdef SRH_PROFILE
+                if ((tid & 63) == 0) L.Qu[2] = (double)(clock64() - tsplit);          // the chain, up to its last signal
+#endif
+            } else {
+                const bool has_front = wv >= 2, rows_first = wv == 1 || rc < 0, has_rows = wv == 1 || rc != 0;
+#pragma unroll 1
+                for (int ph = 0; ph < 2; ++ph) {
+                    if ((ph == 0) == rows_first) {
+                        if (has_rows) tile_cholesky_set(d, L, wv, tid & 63, 1, L.flag + 5, L.flag + 3, rc);
+                    } else if (has_front) {
+#ifdef SRH_PROFILE
+                        const long long tfront = clock64();
+                        pf.last = tfront;
+#endif
+                        newton_front<MSEL, true>(d, g, L, gyd, W, pf, ya_const && mode == PRED);
+#ifdef SRH_PROFILE
+                        if (W.tid == 0) L.Qu[3] = (double)(clock64() - tfront);       // the front alone, on its two waves
+#endif
+                    }
+                }
+            }
             __syncthreads();
 #ifdef SRH_PROFILE
+            prof[16] += (long long)L.Qu[2]; prof[17] += (long long)L.Qu[3];
             for (int i = 0; i < 5; ++i) prof[27 + i] += (long long)L.Qu[8 + i];
 #endif
             ok = L.flag[1] != 0;
@@ -2079,8 +2152,14 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
             Q4_LAP(5);
             if (ok) unit_tiles(d, L);
             Q4_LAP(32);                                        // (unit_tiles and its barrier alone; the factorisation up to the join is lap 5)
+#ifdef SRH_PROFILE
+            pf.last = clock64();
+#endif
             if (ok) newton_back<MSEL>(d, g, L, pf);
         } else {
+#ifdef SRH_PROFILE
+            pf.last = clock64();
+#endif
             newton_solve<MSEL>(d, g, L, (clptr) nullptr, &rd, pf, ya_const);
         }
         Q4_LAP(6);

@@ -457,6 +457,11 @@ int build_consts(const slocp_problem *pr, QPConstHost &C, bool want_half = false
                 // A/B and test knob, read when the constants are built: SRH_LEAN_NO_TOEPLITZ=1 keeps the general condensation for
                 // single-region horizons too (ql::condense_single)
                 d.lean_toeplitz = getenv("SRH_LEAN_NO_TOEPLITZ") == nullptr ? 1 : 0;
+                // A/B and test knob, read when the constants are built: SRH_LEAN_ROSTER=<code> picks the row roster of the half-size
+                // kernel's set factorisation (ql::roster_nwk; sgusto_plan_lean_roster reports the code in effect)
+                d.lean_roster = ql::LEAN_ROSTER_DEFAULT;
+                if (const char *er = getenv("SRH_LEAN_ROSTER")) d.lean_roster = atoi(er);
+                if (!half || !ql::roster_legal(d.KT, d.lean_roster)) d.lean_roster = 0;
 
                 // rows next to their sums (ql::ipm_box): the reference's HyperRectangle layout of the input rows (rows 2 b,
                 // 2 b + 1 act on input b alone, utils.py:390-414), at most 8 state rows per stage, everything in 512 threads

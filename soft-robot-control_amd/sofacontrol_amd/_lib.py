@@ -223,6 +223,26 @@ def ipm_rule_replay(phase, rows, par):
     return out, scal
 
 
+ROSTER_EVENTS = ('wait', 'signal', 'read', 'chol', 'panel', 'update', 'front')
+ROSTER_COUNTERS = ('trail', 'rinv', 'panel', 'next')
+
+
+def lean_roster_replay(KT, code, nwk0=1):
+    """slean_roster_replay: the tile factorisation of the lean kernels' wave set as each of its four waves runs it under row roster
+    `code` (csrc/locp_lean.h: roster_nwk and the targets next to it), listed on the host -- no GPU needed.  Returns (code in effect,
+    [events of wave 0, .., of wave 3]); an event is (kind, a, b, c) with kind a name of ROSTER_EVENTS (include/sofacontrol_hip.h)."""
+    waves, eff = [], C.c_int32(0)
+    for wave in range(4):
+        n = C.c_int32(0)
+        check(lib().slean_roster_replay(C.c_int(KT), C.c_int(code), C.c_int(nwk0), C.c_int(wave), C.c_int(0),
+                                        np.zeros(4, dtype=np.int32).ctypes.data_as(C.c_void_p), C.byref(n), C.byref(eff)), 'slean_roster_replay')
+        ev = np.zeros((max(1, n.value), 4), dtype=np.int32)
+        check(lib().slean_roster_replay(C.c_int(KT), C.c_int(code), C.c_int(nwk0), C.c_int(wave), C.c_int(n.value),
+                                        ev.ctypes.data_as(C.c_void_p), C.byref(n), C.byref(eff)), 'slean_roster_replay')
+        waves.append([(ROSTER_EVENTS[k], int(a), int(b), int(c)) for k, a, b, c in ev[:n.value]])
+    return int(eff.value), waves
+
+
 def gusto_plan_dims(plan):
     """sgusto_plan_dims: the shapes a resident GuSTO plan was created with, {'N', 'n_x', 'n_u', 'n_z', 'batch', 'dt', 'has_Qzf'}."""
     N, n, m, nz, hq = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)

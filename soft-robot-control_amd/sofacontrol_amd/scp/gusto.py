@@ -240,6 +240,9 @@ class GuSTO:
         nsingle = C.c_int32(0)
         _lib.check(_lib.lib().sgusto_plan_single_region_qps(self._plan, C.byref(nsingle)), 'sgusto_plan_single_region_qps')
         out['single_region_qps'] = int(nsingle.value)
+        roster = C.c_int32(0)
+        _lib.check(_lib.lib().sgusto_plan_lean_roster(self._plan, C.byref(roster)), 'sgusto_plan_lean_roster')
+        out['lean_roster'] = int(roster.value)
         return out
 
     # ---- helper tests with the reference's names (host arrays; used by the generic loop / by users)
