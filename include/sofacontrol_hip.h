@@ -291,8 +291,12 @@ int sekf_batch_step(sekf_batch_t *h, const double *u, const double *y, double *x
 
 /* Polyhedron(with_reproject=True).project_to_polyhedron (utils.py:364-407; the measurement re-projection of
  * SSM/controllers.py:96-97): Euclidean projection of `batch` points X (batch x n) onto {p : A p <= b}, A (n_rows x n)
- * row-major, n <= 16, n_rows <= 64; exact (interior point to a 1e-13 gap; the reference hands the same QP to OSQP).
- * Points already inside are returned unchanged.  SRH_ENUMERIC when the iteration does not converge (empty set). */
+ * row-major, n <= 16, n_rows <= 64 (the reference hands the same QP to OSQP).  An interior point finds the active set, an
+ * active-set step on it returns the point: a returned point carries a KKT certificate (max(A p - b) <= 1e-12 scale,
+ * multipliers >= -1e-12 scale, stationary and complementary by construction), scale = max(1, |x|_inf, |b|_inf), and is within
+ * 1e-9 scale of the projection whatever its margin; the floor of scale at 1 makes that absolute for polyhedra smaller than 1.
+ * Points with max(A x - b) <= 0 are returned bit for bit.  SRH_ENUMERIC, naming the first such point, when a point is not
+ * finite or no certified point is found in 60 iterations (empty set); SRH_EINVAL for a non-finite A or b. */
 int spoly_project(const double *A, const double *b, int n_rows, int n, const double *X, int64_t batch, double *out);
 
 /* =====================================================================================================

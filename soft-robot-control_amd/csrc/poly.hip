@@ -1,9 +1,17 @@
 // Euclidean projection onto a polyhedron {p : A p <= b}: min 1/2 |p - x|^2 s.t. A p <= b.
 // Reference: sofacontrol/utils.py:364-407 (Polyhedron(with_reproject=True).project_to_polyhedron: the same QP handed to
 // OSQP with P = I, q = -x); used on measurements that left the admissible set, SSM/controllers.py:96-97.
-// One wave per point, Mehrotra predictor-corrector interior point: lane i owns constraint i (slack, multiplier, row
-// of A in registers), the n-vectors are kept uniform in every lane; the n x n normal matrix I + A^T D A is summed
-// with wave reductions and factored in LDS (n <= 16, rows <= 64: these are output-space boxes and a few facets).
+// One wave per point, lane i owns constraint i (slack, multiplier, row of A in registers), the n-vectors are kept uniform in
+// every lane (n <= 16, rows <= 64: these are output-space boxes and a few facets).  Two stages:
+//   1. a Mehrotra predictor-corrector interior point finds the active set: the n x n normal matrix I + A^T D A is summed with
+//      wave reductions and factored in LDS.  In float64 its iterate is no better than sqrt(rows mu) at a weakly active row, and its
+//      multipliers lose eps |dp| lam / s on the strongly active ones, so it is never the result.
+//   2. a closing step on the rows it points to (lam_i >= s_i): the projection of x onto the affine hull of an independent part of
+//      them (pivoted modified Gram-Schmidt, each lane orthogonalising its own row), the multipliers from the triangular factor,
+//      then the two checks of an active-set method -- a negative multiplier leaves the set, the most violated row joins it --
+//      and again.  It returns only a point with max(A p - b) <= 1e-12 scale and multipliers >= -1e-12 scale that is stationary
+//      and complementary by construction: the KKT certificate of the unique projection.  scale = max(1, |x|_inf, |b|_inf).
+// Success means that certificate; a point the interior point reaches without one (60 iterations) is reported, never returned.
 #include "common.h"
 #include "dev_la.h"
 
@@ -17,12 +25,19 @@ struct PolyArgs {
     double *out;
     int *status;
     int mc, n;
-    double tol;
     int max_iter;
 };
 
+constexpr double IDENT_MU = 1e-9;      // the closing step is tried once mu <= IDENT_MU scale and both residuals <= IDENT_RES scale
+constexpr double IDENT_RES = 1e-6;
+constexpr double CERT_TOL = 1e-12;     // feasibility and sign of the multipliers of a returned point, relative to scale
+constexpr double DEPENDENT = 1e-18;    // |z|^2 / |a|^2 below this: the row depends on the rows already taken (an angle of 1e-9)
+constexpr int CLOSING_ROUNDS = 16;
+
 __global__ __launch_bounds__(64) void poly_project_kernel(PolyArgs a) {
     __shared__ double M[PN * PN], Lc[PN * PN], rhs[PN], sol[PN];
+    __shared__ double Rm[PN * PN], qs[PN], cs[PN], ls[PN], lmin_s;     // closing step: R of A_S^T = Q R, the current q, Q^T (x - p), lam
+    __shared__ int sel[PN], jmin_s;
     __shared__ int flag;
     const int lane = threadIdx.x, n = a.n, mc = a.mc;
     const bool act = lane < mc;
@@ -78,8 +93,98 @@ __global__ __launch_bounds__(64) void poly_project_kernel(PolyArgs a) {
         return true;
     };
     auto max_step = [&](double v, double dv) { return (act && dv < 0.0) ? -v / dv : INFINITY; };
-    double last_rpn = INFINITY;
-    for (; it < a.max_iter; ++it) {
+    // the closing step (stage 2 above) from the current lam, s; true with the certified point in pw
+    double pw[PN];
+    auto closing = [&]() -> bool {
+        bool inW = act && lam >= s;
+        double na2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < PN; ++k) na2 = fma(ar[k], ar[k], na2);
+        const double tolc = CERT_TOL * scale;
+        for (int round = 0; round < CLOSING_ROUNDS; ++round) {
+            double z[PN], h[PN];
+#pragma unroll
+            for (int k = 0; k < PN; ++k) { z[k] = ar[k]; h[k] = 0.0; pw[k] = k < n ? x[k] : 0.0; }
+            bool taken = false;
+            int nsel = 0;
+#pragma unroll
+            for (int k = 0; k < PN; ++k) {
+                if (k >= n) break;
+                double zz = 0.0;
+#pragma unroll
+                for (int m = 0; m < PN; ++m) zz = fma(z[m], z[m], zz);
+                const double cand = (inW && !taken && na2 > 0.0) ? zz / na2 : -1.0;
+                const double best = wg::wave_max(cand);
+                if (!(best > DEPENDENT)) break;
+                const int j = __ffsll((long long)__ballot(cand == best)) - 1;         // the first lane that holds the maximum
+                if (lane == j) {
+                    const double nz = sqrt(zz);
+#pragma unroll
+                    for (int m = 0; m < PN; ++m) qs[m] = z[m] / nz;
+#pragma unroll
+                    for (int m = 0; m < PN; ++m)
+                        if (m < k) Rm[m * PN + k] = h[m];
+                    Rm[k * PN + k] = nz;
+                    cs[k] = (adot(pw) - bi) / nz;           // the step along q that puts row j on its bound; earlier rows stay
+                    sel[k] = j;
+                    taken = true;
+                }
+                __syncthreads();
+                double q[PN];
+#pragma unroll
+                for (int m = 0; m < PN; ++m) q[m] = qs[m];
+                const double ck = cs[k];
+#pragma unroll
+                for (int m = 0; m < PN; ++m) pw[m] = fma(-ck, q[m], pw[m]);
+                for (int pass = 0; pass < 2; ++pass) {              // orthogonalised twice
+                    double g = 0.0;
+#pragma unroll
+                    for (int m = 0; m < PN; ++m) g = fma(z[m], q[m], g);
+#pragma unroll
+                    for (int m = 0; m < PN; ++m) z[m] = fma(-g, q[m], z[m]);
+                    h[k] += g;
+                }
+                nsel = k + 1;
+                __syncthreads();
+            }
+            // x - p = Q c = A_S^T lam:  R lam = c
+            if (lane == 0) {
+                double lm = INFINITY;
+                int jm = -1;
+                for (int i = nsel - 1; i >= 0; --i) {
+                    double sum = cs[i];
+                    for (int m = i + 1; m < nsel; ++m) sum -= Rm[i * PN + m] * ls[m];
+                    ls[i] = sum / Rm[i * PN + i];
+                }
+                for (int i = 0; i < nsel; ++i)
+                    if (ls[i] < lm) { lm = ls[i]; jm = sel[i]; }
+                lmin_s = lm;
+                jmin_s = jm;
+            }
+            __syncthreads();
+            const double lm = lmin_s;
+            const int jm = jmin_s;
+            __syncthreads();
+            if (nsel > 0 && !(lm >= -tolc)) {               // the most negative multiplier leaves (a NaN ends the step below)
+                if (!(lm < 0.0)) return false;
+                if (lane == jm) inW = false;
+                continue;
+            }
+            const double v = act ? adot(pw) - bi : -INFINITY;
+            const double vmax = wg::wave_max(v);
+            bool finite = vmax > -1e300;
+#pragma unroll
+            for (int k = 0; k < PN; ++k) finite = finite && fabs(pw[k]) < 1e300;
+            if (!finite) return false;
+            if (!(vmax > tolc)) return true;
+            const int j = __ffsll((long long)__ballot(v == vmax)) - 1;              // the most violated row joins
+            if ((__ballot(inW) >> j) & 1) return false;    // it is in the set already and depends on the rows taken
+            if (lane == j) inW = true;
+        }
+        return false;
+    };
+    bool certified = false;
+    for (;; ++it) {
         // residuals
         double rdn = 0.0;
 #pragma unroll
@@ -89,9 +194,9 @@ __global__ __launch_bounds__(64) void poly_project_kernel(PolyArgs a) {
         }
         const double rp = act ? adot(p) + s - bi : 0.0;
         const double rpn = wg::wave_max(fabs(rp));
-        last_rpn = rpn;
         const double mu = wg::wave_sum(act ? s * lam : 0.0) / mc;
-        if (mu <= a.tol * scale && rpn <= 1e-10 * scale && rdn <= 1e-10 * scale) break;
+        if (mu <= IDENT_MU * scale && rpn <= IDENT_RES * scale && rdn <= IDENT_RES * scale && closing()) { certified = true; break; }
+        if (it >= a.max_iter) { st = 1; break; }
         double dla, dsa, dpa[PN], dl, dsv, dp[PN];
         if (!newton(rp, act ? s * lam : 0.0, dla, dsa, dpa)) { st = 2; break; }
         double aa = fmin(1.0, wg::wave_min(fmin(max_step(s, dsa), max_step(lam, dla))));
@@ -103,17 +208,7 @@ __global__ __launch_bounds__(64) void poly_project_kernel(PolyArgs a) {
         for (int k = 0; k < PN; ++k) p[k] += al * dp[k];
         if (act) { s += al * dsv; lam += al * dl; }
     }
-    if (st == 0 && it >= a.max_iter) st = 1;
-    // a polyhedron without strict interior (rows with lb == ub) has no central path to follow to a 1e-13 gap: the last
-    // iterate is returned when it is feasible to 1e-6 (the reference's OSQP returns such an approximate point too)
-    {
-        const double vend = wg::wave_max(act ? adot(p) - bi : -INFINITY);     // the actual violation of the last iterate
-        bool finite = true;                 // (fmax / fmin drop NaNs: a diverged iterate must not pass as feasible)
-#pragma unroll
-        for (int k = 0; k < PN; ++k) finite = finite && (p[k] == p[k]) && fabs(p[k]) < 1e300;
-        if (st != 0 && finite && vend > -1e300 && vend <= 1e-6 * scale && last_rpn <= 1e-6 * scale) st = 0;
-    }
-    if (lane < n) a.out[(size_t)blockIdx.x * n + lane] = p[lane < PN ? lane : 0];
+    if (lane < n) a.out[(size_t)blockIdx.x * n + lane] = certified ? pw[lane < PN ? lane : 0] : p[lane < PN ? lane : 0];
     if (lane == 0) a.status[blockIdx.x] = st;
 }
 
@@ -125,6 +220,14 @@ int spoly_project(const double *A, const double *b, int n_rows, int n, const dou
     SRH_REQUIRE(A && b && X && out, "spoly_project: null argument");
     SRH_REQUIRE(n > 0 && n <= PN && n_rows > 0 && n_rows <= PM, "spoly_project: need 0 < n <= 16 and 0 < rows <= 64 (got %d, %d)",
                 n, n_rows);
+    // fmax / fmin drop NaNs: a non-finite number would pass the kernel's first test as "already inside"
+    for (int i = 0; i < n_rows * n; ++i) SRH_REQUIRE(std::isfinite(A[i]), "spoly_project: the polyhedron is not finite (A, row %d)", i / n);
+    for (int i = 0; i < n_rows; ++i) SRH_REQUIRE(std::isfinite(b[i]), "spoly_project: the polyhedron is not finite (b, row %d)", i);
+    for (int64_t i = 0; i < batch * n; ++i)
+        if (!std::isfinite(X[i])) {
+            srh::set_error("spoly_project: point %lld is not finite (coordinate %d is NaN or Inf)", (long long)(i / n), (int)(i % n));
+            return SRH_ENUMERIC;
+        }
     if (batch == 0) return SRH_OK;
     srh::DevBuf dA, db, dX, dO, dS;
     int rc;
@@ -132,7 +235,7 @@ int spoly_project(const double *A, const double *b, int n_rows, int n, const dou
         (rc = dX.upload(X, sizeof(double) * batch * n)) || (rc = dO.alloc(sizeof(double) * batch * n)) ||
         (rc = dS.alloc(sizeof(int) * batch)))
         return rc;
-    PolyArgs a{dA.as<double>(), db.as<double>(), dX.as<double>(), dO.as<double>(), dS.as<int>(), n_rows, n, 1e-13, 60};
+    PolyArgs a{dA.as<double>(), db.as<double>(), dX.as<double>(), dO.as<double>(), dS.as<int>(), n_rows, n, 60};
     poly_project_kernel<<<(unsigned)batch, 64>>>(a);
     SRH_CHECK_HIP(hipGetLastError());
     SRH_CHECK_HIP(hipStreamSynchronize(nullptr));
@@ -141,7 +244,8 @@ int spoly_project(const double *A, const double *b, int n_rows, int n, const dou
     for (int64_t i = 0; i < batch; ++i)
         if (st[i] != 0) {
             srh::set_error("spoly_project: point %lld: %s", (long long)i,
-                           st[i] == 1 ? "no convergence (empty polyhedron?)" : "normal matrix not positive definite");
+                           st[i] == 1 ? "no certified projection in 60 iterations (empty polyhedron?)"
+                                      : "normal matrix not positive definite: the iteration diverged (empty polyhedron?)");
             return SRH_ENUMERIC;
         }
     return dO.download(out, sizeof(double) * batch * n);

@@ -51,8 +51,13 @@ def load_data(filename):
 
 class Polyhedron:
     """{x : A x <= b} (sofacontrol/utils.py:364-407).  with_reproject=True enables `project_to_polyhedron`: the
-    Euclidean projection min 1/2 |p - x|^2 s.t. A p <= b -- the QP the reference hands to OSQP -- solved exactly on
-    the device (`spoly_project`, csrc/poly.hip)."""
+    Euclidean projection min 1/2 |p - x|^2 s.t. A p <= b -- the QP the reference hands to OSQP -- solved on the device
+    (`spoly_project`, csrc/poly.hip; at most 16 dimensions and 64 rows).  The contract, with
+    scale = max(1, |x|_inf, |b|_inf): a returned point is within 1e-9 scale of the projection whatever the margin of its
+    active set (weakly active rows and points barely outside included), satisfies max(A p - b) <= 1e-12 scale, and a point
+    that is already inside comes back bit for bit.  scale is floored at 1, so for a polyhedron much smaller than 1 the
+    bound is absolute: nothing below about 1e-9 is resolved.  An empty polyhedron and a NaN or Inf point raise, naming
+    the point."""
 
     def __init__(self, A, b, with_reproject=False):
         self.A = np.asarray(A, dtype=np.float64)
