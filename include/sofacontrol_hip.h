@@ -913,6 +913,48 @@ int skoop_fit_sums(skoop_fit_t *f, double *G, double *R, double *Q, int64_t *pai
  * SRH_EINVAL when no pair has been added. */
 int skoop_fit_solve(skoop_fit_t *f, double ridge, double *A, double *B, int32_t *info);
 
+/* SSM model identification (csrc/ssm_fit.hip): records (y, u) -> rd_coeff / Bd, r_coeff / B, w_coeff of an SSM model (sssm_create).
+ * THE FIT ("SSM model identification", defines it; the reference ships one trained model and no trainer):
+ *   records   E episodes, each y (T x n_y), u (T x m), raw; `stride` s >= 1 keeps rows 0, s, 2s, .. of every episode; T' = the rows
+ *             kept; row i holds the input applied after y_i.
+ *   chart     x_i = V^T (y_i - y_ref), V (n_y x n_x) given; x is the exact sum rounded once (a compensated dot product).
+ *             sssm_fit_cov returns C = sum (y - y_ref)(y - y_ref)^T over the kept rows, the matrix a PCA chart is read from.
+ *   samples   the interior rows 1 <= i <= T' - 2 of every episode, never across an episode; T' < 3 contributes nothing.
+ *   regressor Phi_i = [phi(x_i); u_i], phi = the monomials of sssm_exponents(n_x, P), P = max(rom_order, ssm_order); n = n_mon + m.
+ *   sums      G = sum Phi_i Phi_i^T (n x n), R_d = sum x_{i+1} Phi_i^T (n_x x n), R_c = sum ((x_{i+1} - x_{i-1}) / (2 Ts)) Phi_i^T
+ *             (n_x x n), R_w = sum (y_i - y_ref) phi(x_i)^T (n_y x n_mon), Q = the squared norms of the three targets, S = samples.
+ *   solves    [rd_coeff Bd] from R_d and [r_coeff B] from R_c on the columns {monomials up to rom_order} + {inputs}; w_coeff from R_w
+ *             on the monomials up to ssm_order.  Every block is equilibrated by its own diagonal: with D = diag(G_S),
+ *             (D^-1/2 G_S D^-1/2 + ridge I) z = D^-1/2 r, coeff = D^-1/2 z, ridge >= 0 (relative to the unit diagonal).
+ * Not offered: delay-embedded observations, a polynomial chart, separate autonomous and forced records, sample weights.
+ * Limits (SRH_EINVAL before any device call): n <= 128, n_x <= 32, n_x <= n_y <= 64, orders <= 7, and the panel must fit the LDS.
+ * The sums are accumulated on f64 MFMA without floating-point atomics: a workgroup sums a granule, eight consecutive 64-sample chunks
+ * of one episode, and the granules join the running sums in order.  The same records give the same bits, and records split over
+ * several add calls at episode boundaries give the bits of one call.  All calls on one handle are ordered by the caller.
+ * sssm_fit_plan answers on the host (no GPU): n_mon, n, the samples of a chunk and the accumulate kernel's dynamic LDS; any output
+ * may be NULL. */
+typedef struct sssm_fit sssm_fit_t;
+int sssm_fit_plan(int n_x, int n_y, int m, int rom_order, int ssm_order, int *n_mon, int *n, int *rows_per_chunk, int64_t *lds_bytes);
+/* V (n_y x n_x); y_ref (n_y) or NULL for zeros */
+int sssm_fit_create(sssm_fit_t **out, int n_x, int n_y, int m, int rom_order, int ssm_order, double Ts, const double *V, const double *y_ref);
+int sssm_fit_destroy(sssm_fit_t *f);
+int sssm_fit_reset(sssm_fit_t *f);                          /* sums and samples back to zero */
+/* C (n_y x n_y) = sum over the kept rows of (y - y_ref)(y - y_ref)^T, count = the rows; reduced on the device in a fixed order.  The
+ * _dev form takes device records and synchronises `stream` before it returns.  y_ref may be NULL (zeros). */
+int sssm_fit_cov(const double *y, int64_t E, int64_t T, int n_y, int stride, const double *y_ref, double *C, int64_t *count);
+int sssm_fit_cov_dev(const double *y_dev, int64_t E, int64_t T, int n_y, int stride, const double *y_ref, double *C, int64_t *count,
+                     void *stream);
+/* y (E x T x n_y), u (E x T x m) are added to the handle's sums; may be called many times.  The _dev form is asynchronous on `stream`. */
+int sssm_fit_add(sssm_fit_t *f, const double *y, const double *u, int64_t E, int64_t T, int stride);
+int sssm_fit_add_dev(sssm_fit_t *f, const double *y_dev, const double *u_dev, int64_t E, int64_t T, int stride, void *stream);
+/* G (n x n), Rd (n_x x n), Rc (n_x x n), Rw (n_y x n_mon), Q (3: of x_{i+1}, the central difference, y_i - y_ref), samples; any may be NULL */
+int sssm_fit_sums(sssm_fit_t *f, double *G, double *Rd, double *Rc, double *Rw, double *Q, int64_t *samples);
+/* rd_coeff, r_coeff (n_x x nmon(n_x, rom_order)), Bd, B (n_x x m), w_coeff (n_y x nmon(n_x, ssm_order)).  info (2, optional): {-1, -1}, or
+ * {the failing pivot's position in its block, its column of Phi} -- a pivot that is not positive, not finite, or not above n eps of
+ * its (unit) diagonal entry (SRH_ENUMERIC; the message names the monomial or the input: "increase ridge"); {block size, -1} when a
+ * solution holds a non-finite entry that no pivot caught.  SRH_EINVAL when no sample has been added. */
+int sssm_fit_solve(sssm_fit_t *f, double ridge, double *rd_coeff, double *Bd, double *r_coeff, double *B, double *w_coeff, int32_t *info);
+
 /* =====================================================================================================
  * ROMPC baseline. reference: sofacontrol/baselines/rompc/rompc.py:57-89, rompc/observer.py:30-46, rompc_utils.py:52-53
  * `batch` independent loops on one linear reduced model (problem-major arrays everywhere).  One control step is
