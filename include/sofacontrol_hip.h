@@ -554,9 +554,11 @@ int sgusto_rule_replay(const sgusto_params *par, int N, int n_x, int T, const do
  *   VERDICT    rows: ok (0 / 1), mu, rd, rp, iteration, row count; par: scale_d, scale_p, tol, max_iter, near_opt before the first row
  *              out: the predictor's verdict (a status, or -1 = go on; near_opt carries from row to row), near_opt after it, the
  *              verdict of a starting / corrector system with this ok, the verdict on this row count
+ *   CONVERGED  rows: (unused), mu, rd, rp; par: scale_d, scale_p, tol
+ *              out: 1.0 if the stopping test holds (ipm::converged), 1.0 if its part without rd holds (ipm::may_converge)
  * scal[7] = the warm-start floor in every phase.  Needs no GPU; for tests of the rule. */
 enum { SQP_IPM_INIT = 0, SQP_IPM_COLD, SQP_IPM_WARM, SQP_IPM_PRED, SQP_IPM_CORR, SQP_IPM_DIRECTION, SQP_IPM_AFFINE, SQP_IPM_ADVANCE,
-       SQP_IPM_SCALES, SQP_IPM_VERDICT };
+       SQP_IPM_SCALES, SQP_IPM_VERDICT, SQP_IPM_CONVERGED };
 int sqp_ipm_rule_replay(int phase, int n, const double *rows, const double *par, double *out, double *scal);
 
 /* The tile factorisation of K on one wave set of the lean kernels, as wave `wave` (0 .. 3) runs it: the ordered list of its events,
@@ -665,6 +667,10 @@ int sgusto_plan_single_region_qps(sgusto_plan_t *plan, int32_t *count);
 /* The row roster of the half-size lean kernel's tile factorisation that this plan's constants were built with (SRH_LEAN_ROSTER=<code>
  * overrides the default when the plan is created; see slean_roster_replay for the codes); 0 for every other kernel. */
 int sgusto_plan_lean_roster(const sgusto_plan_t *plan, int32_t *code);
+/* 1 if this plan's constants were built under SRH_IPM_LATE_STOP=1 and a lean kernel serves it: the lean interior points then test
+ * convergence behind the predictor's Newton system only (the former order), not before it.  0 otherwise, any other value of the
+ * variable included. */
+int sgusto_plan_ipm_late_stop(const sgusto_plan_t *plan, int32_t *late);
 int sgusto_plan_solve(sgusto_plan_t *plan, const double *x0, const double *u_init, const double *x_init,
                       const double *z, const double *zf, const double *u_des, double *xopt, double *uopt,
                       double *zopt, int32_t *iters, int32_t *status, double *trace);

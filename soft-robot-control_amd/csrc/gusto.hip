@@ -344,6 +344,10 @@ int sqp_ipm_rule_replay(int phase, int n, const double *rows, const double *par,
             o[1] = near_opt ? 1.0 : 0.0;
             o[2] = (double)ipm::verdict_system(r[0] != 0.0); o[3] = (double)ipm::verdict_no_rows((int)r[5]);
             break;
+        case SQP_IPM_CONVERGED:
+            o[0] = ipm::converged(r[1], r[2], r[3], par[0], par[1], par[2]) ? 1.0 : 0.0;
+            o[1] = ipm::may_converge(r[1], r[3], par[1], par[2]) ? 1.0 : 0.0;
+            break;
         default: SRH_REQUIRE(false, "sqp_ipm_rule_replay: unknown phase");
         }
     }
@@ -652,6 +656,12 @@ int sgusto_plan_single_region_qps(sgusto_plan_t *pl, int32_t *count) {
 int sgusto_plan_lean_roster(const sgusto_plan_t *pl, int32_t *code) {
     SRH_REQUIRE(pl && code, "sgusto_plan_lean_roster: null argument");
     *code = pl->C.dims.lean_roster;
+    return SRH_OK;
+}
+
+int sgusto_plan_ipm_late_stop(const sgusto_plan_t *pl, int32_t *late) {
+    SRH_REQUIRE(pl && late, "sgusto_plan_ipm_late_stop: null argument");
+    *late = pl->C.dims.ipm_late_stop;
     return SRH_OK;
 }
 

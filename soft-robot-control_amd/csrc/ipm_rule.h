@@ -7,6 +7,10 @@
 //   cold:  init_row -> Newton step -> start_shift(min g, max g), start_cold          warm:  start_warm (no starting system)
 //   scales (once per QP), then per iteration
 //   PRED:  pred_row -> Newton system -> direction(pred), step_bound -> verdict -> step_affine, affine_term -> centring
+//          The lean forms (locp_lean.h) test convergence BEFORE the system, as the oracle does (condensed_ipm.py:286-292): behind
+//          pred_row, where may_converge holds, they take the dual residual from the product G^T g_yd alone and stop with status 0 if
+//          converged holds -- no Newton system is built for an iterate that needs no step (QPDims::ipm_late_stop = 1 keeps the test
+//          inside verdict only).  The fused, condensed and dense-in-u kernels test in verdict, behind the system.
 //   CORR:  corr_row -> Newton system -> direction(!pred), step_bound -> step_length, advance
 // The operation order and grouping of every expression is what the kernels' results depend on bit for bit: keep it.
 #pragma once
@@ -85,9 +89,18 @@ SRH_IPM int verdict_failed(bool ok, double mu, double rd, bool near_opt) {
     if (!(rd == rd)) return near_opt ? 0 : 6;
     return GO_ON;
 }
-SRH_IPM int verdict_converged(double mu, double rd, double rp, double sd, double sp, double tol, int it, int max_iter, bool &near_opt) {
+// the stopping test itself (NaN in any argument: not converged), and the part of it that needs no product with G: the gate of the
+// lean forms' early test
+SRH_IPM bool converged(double mu, double rd, double rp, double sd, double sp, double tol) {
     const double ltol = fmax(tol, 1e-9);
-    if (rd <= ltol * sd && rp <= ltol * sp && mu <= tol) return 0;
+    return rd <= ltol * sd && rp <= ltol * sp && mu <= tol;
+}
+SRH_IPM bool may_converge(double mu, double rp, double sp, double tol) {
+    const double ltol = fmax(tol, 1e-9);
+    return rp <= ltol * sp && mu <= tol;
+}
+SRH_IPM int verdict_converged(double mu, double rd, double rp, double sd, double sp, double tol, int it, int max_iter, bool &near_opt) {
+    if (converged(mu, rd, rp, sd, sp, tol)) return 0;
     near_opt = (rd <= 1e-8 * sd && rp <= 1e-8 * sp && mu <= 1e-8);
     if (it >= max_iter) return 1;
     return GO_ON;

@@ -36,7 +36,7 @@ constexpr int lean_threads(int nst, int j0) { return (nst > 0 && j0 == nst) ? 25
 template <int MSEL, int NSEL, int GXSEL, int NST, int J0SEL, int NXR>
 __global__ __launch_bounds__(lean_threads(NST, J0SEL), 2) void gusto_lean_kernel(QPDims d, QPConst c, TpwlDev T, GustoPar par, GustoBatch b) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    long long prof[33] = {0};                  // (the lap slots of locp_lean.h; [32]: unit_tiles of the half-size kernel)
+    long long prof[35] = {0};                  // (the lap slots of locp_lean.h; [32]: unit_tiles of the half-size kernel; [33], [34]: the early stopping test)
 #ifdef SRH_PROFILE
     long long gup[8] = {0}, gul = clock64();
 #endif
@@ -290,6 +290,7 @@ __global__ __launch_bounds__(lean_threads(NST, J0SEL), 2) void gusto_lean_kernel
         printf("lean split (factorisation on waves 0-3 beside the front of the Newton solve on waves 4-7): factorisation %lld front %lld\n", prof[16], prof[17]);
         printf("lean factor chain (wave 0): wait %lld panel %lld update %lld factor %lld signals %lld\n", prof[27], prof[28], prof[29], prof[30], prof[31]);
         printf("lean unit tiles (half-size workgroup; behind the join, with its barrier): clocks %lld\n", prof[32]);
+        printf("lean early stop (product G^T g_yd and its maximum before the system): clocks %lld products-for-nothing %lld\n", prof[33], prof[34]);
     }
 #endif
     if (handed_over) {
@@ -304,7 +305,7 @@ __global__ __launch_bounds__(lean_threads(NST, J0SEL), 2) void gusto_lean_kernel
 template <int MSEL, int NSEL, int GXSEL, int NST, int J0SEL, int NXR>
 __global__ __launch_bounds__(lean_threads(NST, J0SEL), 2) void locp_lean_kernel(QPDims d, QPConst c, LocpBatch b) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    long long prof[33] = {0};                  // (the lap slots of locp_lean.h; [32]: unit_tiles of the half-size kernel)
+    long long prof[35] = {0};                  // (the lap slots of locp_lean.h; [32]: unit_tiles of the half-size kernel; [33], [34]: the early stopping test)
     qp::specialise<MSEL, NSEL>(d);
     fix_problem<MSEL, GXSEL, NST, J0SEL, NXR>(d);
     const size_t p = blockIdx.x;

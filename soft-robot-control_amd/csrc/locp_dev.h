@@ -48,6 +48,8 @@ struct QPDims {
     int lean_roster;    // half-size lean workgroup: row roster of the set factorisation (ql::roster_nwk).  0: waves 2, 3 run the Newton front
                         // only; +k: the front, then workers in the tile rows k .. KT - 2; -k: workers in the rows < k, then the front
                         // (SRH_LEAN_ROSTER=<code> when the constants are built; a code that is not legal for KT counts as 0)
+    int ipm_late_stop;  // lean kernels: 0: the interior point tests convergence before it builds the predictor's Newton system (ipm_rule.h,
+                        // ql::converged_early); 1 (SRH_IPM_LATE_STOP=1 when the constants are built): behind the system only, the former order
 };
 
 // The QP without its trust-region rows (the prescreen of qp::solve, the condensed and the lean interior points): the row counts that follow

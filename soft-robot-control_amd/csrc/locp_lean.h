@@ -732,7 +732,10 @@ __device__ __forceinline__ void g_times(const QPDims &d, const GP &g, Lds &L, cl
 // L2-resident rows (stages < j0) in passes of their own.  No masks: y1 / y2 must be zero from index NP up to NP + YPAD - 1
 // (the lanes run to the length of the longest row of the pass; what they read of G past the end of a row is the next
 // rows' data -- finite -- times those zeros).
-template <int MSEL, bool HALF, class GP>
+// GRP > 0: the trip count of a row is the one of a pass of GRP rows, whatever the wave set's own pass -- the trip count decides which
+// of the two chains a term lands in, so a product on all waves with GRP = the rows per pass of the Newton front's set has the front's
+// bits entry by entry (converged_early).  GRP divides the set's rows per pass and is a multiple of 8 (uniform over a wave).
+template <int MSEL, bool HALF, int GRP = 0, class GP>
 __device__ __forceinline__ void gT_times(const QPDims &d, const GP &g, Lds &L, clptr y1, clptr y2, lptr out1, lptr out2, Waves<HALF> &W) {
     constexpr int M = MSEL;
     const int NP = g.NP, nm = d.N * M, tid = W.tid, nt = W.nt;
@@ -745,7 +748,8 @@ __device__ __forceinline__ void gT_times(const QPDims &d, const GP &g, Lds &L, c
             const int j = rc / M, b = rc - j * M, len = NP - 2 * j;
             const int at = (toep ? b * NP : goff(j, M, NP) + b * len) + g8;
             clptr p1 = y1 + 2 * j + g8, p2 = (two ? y2 : y1) + 2 * j + g8;
-            const int nq = (NP - 2 * (r0 / M) + 7) >> 3;             // trips of the longest row of this pass (uniform)
+            int nq = (NP - 2 * (r0 / M) + 7) >> 3;                   // trips of the longest row of this pass (uniform)
+            if constexpr (GRP > 0) nq = (NP - 2 * ((rb + (r - rb) / GRP * GRP) / M) + 7) >> 3;      // ... of the pass of GRP rows
             double a1 = 0.0, a2 = 0.0, c1 = 0.0, c2 = 0.0;         // two chains per output
             int q = 0;
             for (; q + 4 <= nq; q += 4) {
@@ -1402,6 +1406,30 @@ __device__ __forceinline__ void chol2_psd(double S00, double S01, double S11, lp
     Lk[0] = l00; Lk[1] = 0.0; Lk[2] = l10; Lk[3] = l11;
 }
 
+__device__ __forceinline__ void reduce2(double &a, int opa, double &b, int opb, lptr scratch);      // (with ipm_box's helpers below)
+// The stopping test of the predictor pass BEFORE its Newton system (ipm_rule.h, PRED; oracle/condensed_ipm.py:286-292 tests there
+// too): mu and rp come out of the rows phase, the dual residual rd = max |g_ud + G^T g_yd| needs one product and neither K nor its
+// factor.  Where the two conditions without rd hold (ipm::may_converge: the last iteration or two of a QP) the product runs on the
+// whole workgroup into L.tc, as newton_front leaves it there, and rd is taken by the same maximum; if the test holds the caller stops
+// with status 0 and builds no system.  Otherwise the pass goes on as it was: the front repeats the product.  GRP: rows per pass of the
+// front's wave set -- rd has the bits the front gives (gT_times), so no verdict moves.  Called by every thread behind the barrier of
+// the rows phase; the answer is uniform.  EARLY_NO_GATE: no product was made (always under QPDims::ipm_late_stop); EARLY_GO_ON: the
+// product was made and the test failed; EARLY_STOP: converged.
+enum { EARLY_NO_GATE = 0, EARLY_GO_ON = 1, EARLY_STOP = 2 };
+template <int MSEL, int GRP, class GP>
+__device__ __forceinline__ int converged_early(const QPDims &d, const GP &g, Lds &L, double mu, double rp, double sd, double sp, double &rd) {
+    rd = 0.0;
+    if (d.ipm_late_stop || !ipm::may_converge(mu, rp, sp, d.tol)) return EARLY_NO_GATE;
+    auto W = all_waves();
+    gT_times<MSEL, false, GRP>(d, g, L, L.yg, (clptr) nullptr, L.tc, (lptr) nullptr, W);
+    const int nm = d.N * d.m;
+    double r = 0.0, dummy = 0.0;
+    for (int e = W.tid; e < nm; e += W.nt) r = fmax(r, fabs(L.tb[e] + L.tc[e]));
+    reduce2(r, 1, dummy, 0, L.red);
+    rd = r;
+    return ipm::converged(mu, r, rp, sd, sp, d.tol) ? EARLY_STOP : EARLY_GO_ON;
+}
+
 // ------------------------------------------------------------------ the QP without its trust-region rows
 // Results: w.u, and -- after the final rollout of solve_qp below -- w.x.  Returns 0 optimal, 1 max iterations, 2 numerical failure.
 template <int MSEL, int NSEL>
@@ -1499,6 +1527,16 @@ __device__ __forceinline__ int ipm(const QPDims &dfull, const QPConst &c, const 
         }
         __syncthreads();
         QL_LAP(1);
+        // converged already?  Then no system (converged_early; the gradients of the dual residual as below, the front's own partition)
+        if (mode == PRED && !d.ipm_late_stop && ipm::may_converge(mu, rp, sp, d.tol)) {
+            qpc::gradients(d, c, q, L, w.lam, L.tb, L.yg);
+            double rde;
+            if (converged_early<MSEL, 0>(d, g, L, mu, rp, sd, sp, rde) == EARLY_STOP) {
+                if (q.dbg && tid == 0) { gptr gd = q.dbg + 8 * it; gd[0] = mu; gd[1] = rde; gd[2] = rp; gd[3] = sd; gd[4] = sp; }
+                status = 0;
+                break;
+            }
+        }
         double rd = 0.0;
         bool ok = true;
         if (mode != CORR) {
@@ -1781,6 +1819,19 @@ __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, co
         }
         __syncthreads();
         QB_LAP(1);
+        // ---------------- converged already?  Then no system (converged_early; 32: the rows per pass of the front's four waves)
+        if (mode == PRED) {
+            double rde;                                        // (not rd: nothing of the early test stays live through the system)
+            const int early = converged_early<MSEL, 32>(d, g, L, mu, rp, sd, sp, rde);
+#ifdef SRH_PROFILE
+            if (early != EARLY_NO_GATE) { QB_LAP(33); if (early == EARLY_GO_ON) prof[34] += 1; }
+#endif
+            if (early == EARLY_STOP) {
+                if (q.dbg && tid == 0) { gptr gd = q.dbg + 8 * it; gd[0] = mu; gd[1] = rde; gd[2] = rp; gd[3] = sd; gd[4] = sp; }
+                status = 0;
+                break;
+            }
+        }
         // ---------------- Newton system
         double rd = 0.0;
         bool ok = true;
@@ -2095,6 +2146,15 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
         }
         __syncthreads();
         Q4_LAP(1);
+        // ---------------- converged already?  Then no system (converged_early; 16: the rows per pass of the front's two waves)
+        if (mode == PRED) {
+            double rde;                                        // (not rd: nothing of the early test stays live through the system)
+            const int early = converged_early<MSEL, 16>(d, g, L, mu, rp, sd, sp, rde);
+#ifdef SRH_PROFILE
+            if (early != EARLY_NO_GATE) { Q4_LAP(33); if (early == EARLY_GO_ON) prof[34] += 1; }      // the early product's own lap; products paid for nothing
+#endif
+            if (early == EARLY_STOP) { status = 0; break; }
+        }
         // ---------------- Newton system
         double rd = 0.0;
         bool ok = true;
@@ -2442,6 +2502,19 @@ __device__ __forceinline__ int ipm_wave(const QPDims &dfull, const QPConst &c, c
                 rp = wg::wave_max(rpm);
             }
             wave_fence();
+            // ---------------- converged already?  Then no system (ipm_rule.h, PRED; converged_early): the dual residual by the very
+            // product and maximum of the Newton direction below
+            if (mode == PRED && !d.ipm_late_stop && ipm::may_converge(mu, rp, sp, d.tol)) {
+                double gtd = 0.0;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) gtd = fma(gR[i], L.yg[i], gtd);
+                const double rde = wg::wave_max(isu ? fabs(tb_r + gtd) : 0.0);
+                if (ipm::converged(mu, rde, rp, sd, sp, d.tol)) {
+                    if (q.dbg && lane == 0) { gptr gd = q.dbg + 8 * it; gd[0] = mu; gd[1] = rde; gd[2] = rp; gd[3] = sd; gd[4] = sp; }
+                    status = 0;
+                    break;
+                }
+            }
             // ---------------- K = I + Ls^T (G D^-1 G^T) Ls, scaled to a unit diagonal, and its factor (one tile)
             bool ok = true;
             if (mode != CORR) {

@@ -242,6 +242,7 @@ int build_consts(const slocp_problem *pr, QPConstHost &C, bool want_half = false
     d.tol = 1e-12;
     d.reg = 1e-8;
     d.cond = 0; d.po = 0; d.KT = 0; d.qc_off = 0; d.diagD = 0; d.lean = 0; d.lean_j0 = 0; d.ls_pd = 0; d.lean_half = 0;
+    d.ipm_late_stop = 0;
     std::vector<double> Qx(n * n), QxN(n * n), Ht2(n * nz), Htf2(n * nz, 0.0), R2(m * m), xs(n, 1.0);
     std::vector<double> QzH(nz * n), QzfH(nz * n, 0.0);
     for (int a = 0; a < nz; ++a)
@@ -462,6 +463,10 @@ int build_consts(const slocp_problem *pr, QPConstHost &C, bool want_half = false
                 d.lean_roster = ql::LEAN_ROSTER_DEFAULT;
                 if (const char *er = getenv("SRH_LEAN_ROSTER")) d.lean_roster = atoi(er);
                 if (!half || !ql::roster_legal(d.KT, d.lean_roster)) d.lean_roster = 0;
+                // A/B and test knob, read when the constants are built: SRH_IPM_LATE_STOP=1 keeps the lean interior points' convergence
+                // test behind the predictor's Newton system (ipm_rule.h; sgusto_plan_ipm_late_stop reports the value in effect; any
+                // other value counts as 0, the early test)
+                if (const char *el = getenv("SRH_IPM_LATE_STOP")) d.ipm_late_stop = (el[0] == '1' && el[1] == 0) ? 1 : 0;
 
                 // rows next to their sums (ql::ipm_box): the reference's HyperRectangle layout of the input rows (rows 2 b,
                 // 2 b + 1 act on input b alone, utils.py:390-414), at most 8 state rows per stage, everything in 512 threads

@@ -207,7 +207,7 @@ def gramian_plan(n_s, n_f, cus=0):
     return {'ntile': ntile.value, 'nfull': nfull.value, 'ntail': ntail.value, 'ksplit': ksplit.value}
 
 
-IPM_PHASES = ('init', 'cold', 'warm', 'pred', 'corr', 'direction', 'affine', 'advance', 'scales', 'verdict')
+IPM_PHASES = ('init', 'cold', 'warm', 'pred', 'corr', 'direction', 'affine', 'advance', 'scales', 'verdict', 'converged')
 
 
 def ipm_rule_replay(phase, rows, par):

@@ -243,6 +243,9 @@ class GuSTO:
         roster = C.c_int32(0)
         _lib.check(_lib.lib().sgusto_plan_lean_roster(self._plan, C.byref(roster)), 'sgusto_plan_lean_roster')
         out['lean_roster'] = int(roster.value)
+        late = C.c_int32(0)
+        _lib.check(_lib.lib().sgusto_plan_ipm_late_stop(self._plan, C.byref(late)), 'sgusto_plan_ipm_late_stop')
+        out['ipm_late_stop'] = int(late.value)
         return out
 
     # ---- helper tests with the reference's names (host arrays; used by the generic loop / by users)

@@ -9,7 +9,9 @@ is slower than the product build (extra barriers at the gusto-level laps), so th
 library timed in the same run (SRH_LIB_PATH unset in that child).
 A fourth case, c2_N50_half, is C2 once more on the half-size workgroup (SRH_LEAN_HALF=1, instantiation <4, 60, 4, 50, 50, 4>), whose Gram
 fill is lapped per wave as well (`lean gram laps` / `lean gram per wave`), and whose condensation is reported per QP with its kind
-(`lean condense (this QP)`: kept from the QP before / general two-pass recursion / single-region recursion + expansion)."""
+(`lean condense (this QP)`: kept from the QP before / general two-pass recursion / single-region recursion + expansion).
+`lean early stop` (clocks_last_solve['early_stop']): the lap of the stopping test in front of the Newton system -- the product G^T g_yd
+and its maximum, made only where mu and rp already pass -- and how many of those products found the dual residual still too large."""
 import json
 import os
 import re
@@ -62,7 +64,7 @@ def child(N, dt, with_X, cap):
                                     'ms_per_scp_iteration_median': sorted(t / max(1, i) for t, i in zip(ts, its))[reps // 2] * 1e3}), flush=True)
 
 
-LINE = re.compile(r'^lean (gusto clocks|qp laps|newton laps|step laps|qp tail|split|factor chain|unit tiles)')
+LINE = re.compile(r'^lean (gusto clocks|qp laps|newton laps|step laps|qp tail|split|factor chain|unit tiles|early stop)')
 GRAM = re.compile(r'^lean gram laps \(this QP, wave 0(?:, (\d+) fills)?\): (.*)$')
 WAVES = re.compile(r'^lean gram per wave \(cumulative\) products:((?: \d+)+)  epilogue:((?: \d+)+)')
 
