@@ -1,9 +1,13 @@
 // Symmetric eigendecomposition of the snapshot Gramian on the device (method-of-snapshots POD,
 // sofacontrol/mor/pod.py:181-200 takes a thin SVD instead) and selection of the kept modes.
-// n_s <= 128: one-workgroup Jacobi in LDS; n_s <= 256: the same Jacobi over HBM, two launches per step; n_s <= 4096: the
-// block Jacobi below; larger: rocSOLVER's dsyevd, resolved at run time with dlopen so that the library does not depend on it (its first load in a process
-// takes minutes on a cold box) -- and where it cannot be loaded, or under SRH_EIGH_BLOCK=1, a two-sided block Jacobi on the
-// MFMA pipe (round 6; no library).
+// Dispatch by size: n_s <= 128 the one-workgroup Jacobi in LDS; 128 < n_s <= 256 the same scalar Jacobi over HBM, two launches per
+// step; 256 < n_s <= 4096 the two-sided block Jacobi on the MFMA pipe (pairs of 64; no library); larger: rocSOLVER's dsyevd, resolved
+// at run time with dlopen so that the library does not depend on it (its first load in a process takes minutes on a cold box) --
+// and where it cannot be loaded, the block Jacobi again.  SRH_EIGH_BLOCK=1 sends every n_s > 128 to the block form, SRH_EIGH_BLOCK=0
+// keeps the scalar form up to 2048 (rocSOLVER above), SRH_EIGH_BLOCK_PAIR=64 / 128 picks the pair size, SRH_EIGH_ROCSOLVER the library.
+// Domain: G symmetric bit for bit (the Jacobi forms read and rotate the whole matrix, rocSOLVER reads the upper triangle), magnitudes
+// within about 1e-150 .. 1e+150: the convergence tests sum squares of the entries.  Exact tests of every Jacobi path:
+// tests/test_eigh_exact_gpu.py.
 #include "common.h"
 #include "dev_la.h"
 #include "mode_rule.h"
@@ -169,7 +173,7 @@ __global__ __launch_bounds__(JAC_NT) void jacobi_eigh_kernel(double *__restrict_
     if (tid == 0) *info = done ? 0 : 1;
 }
 
-// ---- medium Gramians (128 < n <= 2048: a typical snapshot set): the same cyclic Jacobi with A and Vt in HBM/L2, one
+// ---- medium Gramians (128 < n <= 256; up to 2048 under SRH_EIGH_BLOCK=0): the same cyclic Jacobi with A and Vt in HBM/L2, one
 // pair of launches per round-robin step (n/2 disjoint rotations): `jac_angles_kernel` takes (c, s) of every pair from
 // the current diagonal blocks, `jac_apply_kernel` applies J^T A J on disjoint 2 x 2 blocks (pair i x pair j: one
 // thread each, in place) and rotates the rows of Vt.  Pairing by the circle method, computed from the step number:
@@ -323,7 +327,7 @@ int jacobi_grid(double *G_dev, int n, double *w_dev, hipStream_t st) {
     return SRH_OK;
 }
 
-// ---- large Gramians (n > 2048, e.g. BASELINE C4's 10 000 snapshots): two-sided BLOCK Jacobi, no library.  The matrix is cut into
+// ---- large Gramians (256 < n <= 4096 by default; any n > 128 without rocSOLVER or under SRH_EIGH_BLOCK=1): two-sided BLOCK Jacobi, no library.  The matrix is cut into
 // blocks of 64; a round-robin step pairs the blocks (the circle method of `jac_pair` on block numbers), every pair is a 128 x 128
 // symmetric sub-problem [A_PP A_PQ; A_QP A_QQ] that one workgroup takes through one cyclic Jacobi sweep in LDS (`bj_sub_kernel`: the
 // small-Gramian kernel's loop, its accumulated rotations Qt = J_last' ... J_1' in L2), and the step applies all of them at once:

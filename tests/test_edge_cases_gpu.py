@@ -155,7 +155,8 @@ def test_errors_are_loud():
 @pytest.mark.parametrize('n', [1, 2, 5, 40, 127, 128, 129, 150, 257, 400])
 def test_device_eigh(n):
     """srom_eigh_dev: one-workgroup Jacobi in LDS for n <= 128, the same Jacobi over HBM (two launches per round-robin
-    step) up to 2048 -- odd sizes pad with a dummy row that never mixes."""
+    step) up to 256, the block Jacobi (pairs of 64) from 257 to 4096 -- odd sizes pad with a dummy row that never mixes, the block
+    form pads to a multiple of 64.  (Every path at its edges: tests/test_eigh_exact_gpu.py.)"""
     from sofacontrol_amd.mor.pod import _device_eigh
     rng = np.random.default_rng(n)
     S = rng.standard_normal((n, n + 3)) * np.logspace(0, -3, n + 3)
