@@ -824,6 +824,27 @@ int sgusto_ssm_loop_stats(sgusto_ssm_loop_t *h, int64_t *steps, int64_t *waits_l
 int sgusto_ssm_loop_advance(sssm_t *plant, int plant_mode, sssm_t *observer_model, double dt_sim, int N, int n_keep, int64_t batch,
                             const int32_t *j, const double *theta, const double *xopt, const double *uopt, const double *x,
                             const double *W, const double *V, double *X, double *Z, double *U, double *Y, double *Xhat);
+/* The same loop on a nearest-point TPWL plant of n_p states (the reference's drivers: the controller sees only the measured tip).  The
+ * handle is an sgusto_ssm_loop with a plant kind: reset, run, set_target, last_inputs, last_plan, stats and destroy serve both kinds;
+ * with a TPWL plant x0, W and the X record have n_p columns, and the plans always start from the estimate.  C (n_o x n_p), y_ref (n_o):
+ * the measurement of the plant state.  Sub-step s of the ONE advance launch of a period (ssm_loop_advance_tpwl_kernel):
+ *           u      = [uopt ; uopt[N-1]] interpolated at (j, theta), no gain
+ *           i      = the plant's nearest point to x (the point-search rule of csrc/tpwl_dev.h; a state that is not a number picks 0)
+ *           x     <- d_d[i] + A_d[i] x + B_d[i] u (the step rule of csrc/tpwl_dev.h) (+ w)
+ *           zeta   = C x                         the record Z: without y_ref
+ *           y      = (zeta + y_ref) + v          in this order of additions
+ *           x_hat  = V_planner phi_s(y - z_ref_planner)
+ * Refused by name, with the numbers, before any launch: n_p > 128, n_u > 16, n_o other than the planner model's, a planner model whose
+ * n_x, n_u are not the plan's, a plant whose n_u is not the plan's, a plant without discrete tables (it must be pre-discretised at
+ * dt_sim), an LDS request above 160 KiB, a plan with rate rows, n_keep dt_sim > N dt. */
+int sgusto_ssm_loop_create_tpwl(sgusto_ssm_loop_t **out, sgusto_ssm_plan_t *plan, sssm_t *planner_model, stpwl_t *plant, const double *C,
+                                const double *y_ref, int n_o, double dt_sim, int n_keep, int64_t max_steps_per_run);
+/* The TPWL-plant advance kernel alone on host arrays, as sgusto_ssm_loop_advance: x (batch x n_p), W (n_keep x batch x n_p), V (n_keep x
+ * batch x n_o) or NULL -> X (batch x n_keep x n_p), Z, Y (batch x n_keep x n_o), U (batch x n_keep x n_u), Xhat (batch x n_keep x n_x of
+ * the observer model), idx (batch x n_keep) the plant's point of every sub-step. */
+int sgusto_ssm_loop_advance_tpwl(stpwl_t *plant, const double *C, const double *y_ref, int n_o, sssm_t *observer_model, double dt_sim, int N,
+                                 int n_keep, int64_t batch, const int32_t *j, const double *theta, const double *uopt, const double *x,
+                                 const double *W, const double *V, double *X, double *Z, double *U, double *Y, double *Xhat, int32_t *idx);
 
 /* =====================================================================================================
  * Koopman baseline. reference: sofacontrol/baselines/koopman/koopman_utils.py, koopman/koopman.py, baselines/ros.py:139-235
