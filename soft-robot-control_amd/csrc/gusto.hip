@@ -24,18 +24,10 @@ __global__ __launch_bounds__(1024) void lpt_order_kernel(const int32_t *__restri
     for (int64_t i = tid; i < batch; i += 1024) order[atomicAdd(&cnt[1023 - min(max(key[i], 0), 1023)], 1)] = (int32_t)i;
 }
 
-#ifdef SRH_PROFILE
-#define GU_LAP(i) do { __syncthreads(); const long long now_ = clock64(); gup[i] += now_ - gul; gul = now_; } while (0)
-#else
-#define GU_LAP(i) ((void)0)
-#endif
-
 template <bool SPLIT, int MSEL, int NSEL>
 __global__ __launch_bounds__(NTHREADS) void gusto_kernel(QPDims d, QPConst c, TpwlDev T, GustoPar par, GustoBatch b) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifdef SRH_PROFILE
-    long long gup[8] = {0}, gul = clock64();
-#endif
+    lapc::Laps<8> gup;                         // the SCP loop's laps, each behind a barrier of its own (profile builds: lap_sync)
     qp::specialise<MSEL, NSEL>(d);             // compile-time n_u (and n_x) for everything inlined below
     QPLds L;
     qp_lds_carve(L, (lptr)smem, d, NTHREADS);          // qp::solve fills the constants of the layout it uses
@@ -81,7 +73,7 @@ __global__ __launch_bounds__(NTHREADS) void gusto_kernel(QPDims d, QPConst c, Tp
         __syncthreads();
         tpwl::nearest_many(T, xk, n, N, idx);
     }
-    GU_LAP(0);
+    gup.lap_sync(0);
 
     QPDyn dyn{T.Ad, T.AdT, T.Bd, T.BdT, T.dd, (cgiptr)idx};
     while (gusto_running(par, s)) {
@@ -89,13 +81,13 @@ __global__ __launch_bounds__(NTHREADS) void gusto_kernel(QPDims d, QPConst c, Tp
         QPData q{x0, xk, zp, zfp, udp, s.delta, s.omega, (gptr)nullptr};
         double J;
         int qit;
-        GU_LAP(1);
+        gup.lap_sync(1);
         int qpass = -1;
         const int st = qp::solve<SPLIT, MSEL, NSEL>(d, c, dyn, q, base, L, &J, &qit, true, w, tr_hot, warm_relaxed, &qpass,
                                                     warm_full && tr_hot && par.warm_full != 0);
         warm_relaxed = st == 0 && qpass == 0;        // the next QP's relaxed Riccati pass may start from this one's (u, lambda)
         warm_full = st == 0 && qpass == 1;           // ... and its full pass from this one's (u, s, lambda) when it goes there directly
-        GU_LAP(2);
+        gup.lap_sync(2);
         if (st != 0) { status = 1; break; }          // gusto.py:357-365: keep the previous iterate
         // trust region test (gusto.py:174-183)
         double md = 0.0;
@@ -108,9 +100,9 @@ __global__ __launch_bounds__(NTHREADS) void gusto_kernel(QPDims d, QPConst c, Tp
         const double d_cur = s.delta, o_cur = s.omega;
         if (tr_ok) {
             // model accuracy (gusto.py:203-223) with continuous nearest-point dynamics
-            GU_LAP(3);
+            gup.lap_sync(3);
             tpwl::nearest_many(T, w.x, n, N, idx2);
-            GU_LAP(4);
+            gup.lap_sync(4);
             // (sixteen columns in flight; when the new point lies in the region of the old one its matrices are the ones already loaded:
             // same products in the same order -- the lean kernel's form, lean.hip, without its LDS copies of the trajectories)
             for (int i = wave; i < N; i += nw) {
@@ -171,7 +163,7 @@ __global__ __launch_bounds__(NTHREADS) void gusto_kernel(QPDims d, QPConst c, Tp
                 if (lane == 0) { accb[2 * i] = par.dt * sqrt(e2); accb[2 * i + 1] = par.dt * sqrt(a2); }
             }
             __syncthreads();
-            GU_LAP(5);
+            gup.lap_sync(5);
             double err = 0.0, app = 0.0;      // sequential sums in stage order, as the reference loop
             for (int i = 0; i < N; ++i) { err += accb[2 * i]; app += accb[2 * i + 1]; }
             rho_k = err / (J + app);
@@ -218,7 +210,7 @@ __global__ __launch_bounds__(NTHREADS) void gusto_kernel(QPDims d, QPConst c, Tp
         // minimiser): if this one already ended on the boundary of its trust region the next one is certain to bind
         tr_hot = on_boundary && !new_solution;
         ++s.itr;
-        GU_LAP(6);
+        gup.lap_sync(6);
         if (new_solution) {
             __syncthreads();
             for (int e = tid; e < (N + 1) * n; e += nt) xk[e] = w.x[e];
@@ -228,13 +220,11 @@ __global__ __launch_bounds__(NTHREADS) void gusto_kernel(QPDims d, QPConst c, Tp
             // w.x, same function, same data: gusto.py:466 recomputes them)
             if (par.max_iters >= 1) { for (int k = tid; k < N; k += nt) idx[k] = idx2[k]; __syncthreads(); }
         }
-        GU_LAP(7);
+        gup.lap_sync(7);
     }
-#ifdef SRH_PROFILE
-    if (tid == 0 && blockIdx.x == 0)
+    if constexpr (lapc::ON) if (tid == 0 && blockIdx.x == 0)
         printf("gusto clocks (%d iterations): init+nearest %lld loop-top %lld qp %lld tr-test %lld nearest(new) %lld accuracy %lld tests %lld accept+nearest %lld\n",
                s.itr, gup[0], gup[1], gup[2], gup[3], gup[4], gup[5], gup[6], gup[7]);
-#endif
     status = gusto_final_status(par, s, status);
     gusto_write_out(b.xopt, b.uopt, b.zopt, p, N, n, m, nz, c.H, xk, uk, tid, nt);
     if (tid == 0) { b.iters[p] = s.itr; b.status[p] = status; if (b.last_iters) b.last_iters[p] = s.itr; if (b.Jopt) b.Jopt[p] = s.J_prev; }

@@ -216,7 +216,7 @@ template <bool SPLIT, int MSEL, int GXL>
 __global__ __launch_bounds__(SSM_THREADS) void gusto_ssm_kernel(QPDims d, QPConst c, SsmDev S, GustoPar par, SsmGustoBatch b, int red_off, int tab_off, int dense_u, int task_stride) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     qp::specialise<MSEL, 0>(d);
-    long long prof[32] = {0};
+    lapc::Launch prof;
     QPLds L;
     qp_lds_carve(L, (lptr)smem, d, NTHREADS);
     const size_t p = blockIdx.x;

@@ -8,12 +8,6 @@ namespace {
 
 static_assert(NTHREADS == 512, "ql::half_waves: the two wave sets are the SIMD halves of an 8-wave workgroup");
 
-#ifdef SRH_PROFILE
-#define GU_LAP(i) do { __syncthreads(); const long long now_ = clock64(); gup[i] += now_ - gul; gul = now_; } while (0)
-#else
-#define GU_LAP(i) ((void)0)
-#endif
-
 // NST > 0: an instantiation for ONE problem layout -- horizon NST, box input rows, NXR state rows, n_z = 6, the first
 // LDS-resident stage J0SEL -- whose sizes are compile-time constants: the LDS carve becomes immediate offsets from one base
 // (no pointer per array in scalar registers), trip counts and the packed-G offsets fold.  The host only selects it for
@@ -36,10 +30,8 @@ constexpr int lean_threads(int nst, int j0) { return (nst > 0 && j0 == nst) ? 25
 template <int MSEL, int NSEL, int GXSEL, int NST, int J0SEL, int NXR>
 __global__ __launch_bounds__(lean_threads(NST, J0SEL), 2) void gusto_lean_kernel(QPDims d, QPConst c, TpwlDev T, GustoPar par, GustoBatch b) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    long long prof[35] = {0};                  // (the lap slots of locp_lean.h; [32]: unit_tiles of the half-size kernel; [33], [34]: the early stopping test)
-#ifdef SRH_PROFILE
-    long long gup[8] = {0}, gul = clock64();
-#endif
+    lapc::Launch prof;                         // (the lap slots of lap_clock.h: lapc::Slot)
+    lapc::Laps<8> gup;                         // the SCP loop's laps, each behind a barrier of its own (profile builds: lap_sync)
     qp::specialise<MSEL, NSEL>(d);
     fix_problem<MSEL, GXSEL, NST, J0SEL, NXR>(d);
     if constexpr (NST > 0) d.tr = 1;                   // GuSTO always carries the trust region
@@ -74,7 +66,7 @@ __global__ __launch_bounds__(lean_threads(NST, J0SEL), 2) void gusto_lean_kernel
     for (int e = tid; e < N * m; e += nt) uk[e] = b.u_init[p * (size_t)N * m + e];
     __syncthreads();
     tpwl::nearest_many(T, xk, n, N, idx);
-    GU_LAP(0);
+    gup.lap_sync(0);
 
     QPDyn dyn{T.Ad, T.AdT, T.Bd, T.BdT, T.dd, (cgiptr)idx};
     GustoState s = gusto_start(par);
@@ -86,7 +78,7 @@ __global__ __launch_bounds__(lean_threads(NST, J0SEL), 2) void gusto_lean_kernel
         QPData q{x0, xk, zp, zfp, udp, s.delta, s.omega, (gptr)nullptr};
         double J;
         int qit;
-        GU_LAP(1);
+        gup.lap_sync(1);
         // every QP after the first one this kernel finished starts from that one's minimiser and multipliers (ql::ipm_box: warm);
         // a warm-started interior point that does not reach the tolerances is repeated from Mehrotra's point
         int st = 0;
@@ -100,7 +92,7 @@ __global__ __launch_bounds__(lean_threads(NST, J0SEL), 2) void gusto_lean_kernel
         // same through the hand-over record, the resume launch and the host paths around them
         if (st == 0 && (par.poison_warm >> 4) - 1 == s.itr) st = 100;
         have_warm = st == 0;
-        GU_LAP(2);
+        gup.lap_sync(2);
         if (st != 0) {                               // the fused kernel takes this rollout from here
             if (tid == 0) {
                 gusto_rec_save(rec, s, st);          // st = 100: relaxed minimiser outside the trust region (the fused kernel skips its own relaxed attempts)
@@ -131,9 +123,9 @@ __global__ __launch_bounds__(lean_threads(NST, J0SEL), 2) void gusto_lean_kernel
         const double d_cur = s.delta, o_cur = s.omega;
         if (tr_ok) {
             // model accuracy (gusto.py:203-223) with continuous nearest-point dynamics
-            GU_LAP(3);
+            gup.lap_sync(3);
             tpwl::nearest_many(T, (clptr)Xn, n, N, idx2);
-            GU_LAP(4);
+            gup.lap_sync(4);
             // One wave per stage, lane = row of the three products.  The stage vectors (old / new state and input) come from the staged
             // copies in LDS instead of being fetched from L2 by every lane and every column; the matrix columns are requested sixteen at a time; when the new point lies in the region of the old one -- most stages -- its matrices
             // are the ones already loaded.  Same products in the same order (round 5: 207 k -> clocks per SCP iteration at C2 in
@@ -198,7 +190,7 @@ __global__ __launch_bounds__(lean_threads(NST, J0SEL), 2) void gusto_lean_kernel
                 if (lane == 0) { accb[2 * i] = par.dt * sqrt(e2); accb[2 * i + 1] = par.dt * sqrt(a2); }
             }
             __syncthreads();
-            GU_LAP(5);
+            gup.lap_sync(5);
             double err = 0.0, app = 0.0;      // sequential sums in stage order, as the reference loop
             for (int i = 0; i < N; ++i) { err += accb[2 * i]; app += accb[2 * i + 1]; }
             rho_k = err / (J + app);
@@ -264,7 +256,7 @@ __global__ __launch_bounds__(lean_threads(NST, J0SEL), 2) void gusto_lean_kernel
         }
         gusto_trace_row(par, b.trace, p, s.itr, tid, J, d_cur, o_cur, rho_k, [](double *) {});
         ++s.itr;
-        GU_LAP(6);
+        gup.lap_sync(6);
         if (new_solution) {
             __syncthreads();
             for (int e = tid; e < (N + 1) * n; e += nt) xk[e] = Xn[e];
@@ -274,25 +266,24 @@ __global__ __launch_bounds__(lean_threads(NST, J0SEL), 2) void gusto_lean_kernel
             // w.x, same function, same data: gusto.py:466 recomputes them)
             if (par.max_iters >= 1) { for (int k = tid; k < N; k += nt) idx[k] = idx2[k]; __syncthreads(); }
         }
-        GU_LAP(7);
+        gup.lap_sync(7);
     }
-#ifdef SRH_PROFILE
-    if (tid == 0 && blockIdx.x == 0) {
+    if constexpr (lapc::ON) if (tid == 0 && blockIdx.x == 0) {
+        using namespace lapc;
         printf("lean gusto clocks (%d iterations): init+nearest %lld loop-top %lld qp %lld tr-test %lld nearest(new) %lld accuracy %lld tests %lld accept+nearest %lld\n",
                s.itr, gup[0], gup[1], gup[2], gup[3], gup[4], gup[5], gup[6], gup[7]);
         printf("lean qp laps: setup+rollout %lld rows %lld condense %lld stage-factors %lld gram %lld cholesky %lld grad+newton %lld steps %lld\n",
-               prof[0], prof[1], prof[2], prof[3], prof[4], prof[5], prof[6], prof[7]);
+               prof[QP_SETUP], prof[QP_ROWS], prof[QP_CONDENSE], prof[QP_STAGE_FACTORS], prof[QP_GRAM], prof[QP_CHOLESKY], prof[QP_NEWTON], prof[QP_STEPS]);
         printf("lean newton laps: gradients %lld gT(1) %lld rhs+dinv %lld g(1) %lld k_solve %lld gT(2) %lld du %lld g(2) %lld\n",
-               prof[8], prof[9], prof[10], prof[11], prof[12], prof[13], prof[14], prof[15]);
-        printf("lean step laps: step rows (both modes) %lld reduce(amax) %lld affine mu rows %lld reduce(mu_aff) %lld\n", prof[18], prof[19], prof[20], prof[21]);
+               prof[NT_GRADIENTS], prof[NT_GT1], prof[NT_RHS], prof[NT_G1], prof[NT_KSOLVE], prof[NT_GT2], prof[NT_DU], prof[NT_G2]);
+        printf("lean step laps: step rows (both modes) %lld reduce(amax) %lld affine mu rows %lld reduce(mu_aff) %lld\n", prof[STEP_ROWS], prof[STEP_AMAX], prof[STEP_MU_ROWS], prof[STEP_MU_AFF]);
         printf("lean qp tail: rollout-of-minimiser %lld objective+tr-test %lld ipm-iterations %lld qps %lld warm-qps %lld\n",
-               prof[22], prof[23], prof[24], prof[25], prof[26]);
-        printf("lean split (factorisation on waves 0-3 beside the front of the Newton solve on waves 4-7): factorisation %lld front %lld\n", prof[16], prof[17]);
-        printf("lean factor chain (wave 0): wait %lld panel %lld update %lld factor %lld signals %lld\n", prof[27], prof[28], prof[29], prof[30], prof[31]);
-        printf("lean unit tiles (half-size workgroup; behind the join, with its barrier): clocks %lld\n", prof[32]);
-        printf("lean early stop (product G^T g_yd and its maximum before the system): clocks %lld products-for-nothing %lld\n", prof[33], prof[34]);
+               prof[TAIL_ROLLOUT], prof[TAIL_OBJECTIVE], prof[N_IPM_ITERS], prof[N_QPS], prof[N_WARM_QPS]);
+        printf("lean split (factorisation on waves 0-3 beside the front of the Newton solve on waves 4-7): factorisation %lld front %lld\n", prof[SPLIT_FACTOR], prof[SPLIT_FRONT]);
+        printf("lean factor chain (wave 0): wait %lld panel %lld update %lld factor %lld signals %lld\n", prof[CHAIN_WAIT], prof[CHAIN_PANEL], prof[CHAIN_UPDATE], prof[CHAIN_FACTOR], prof[CHAIN_SIGNALS]);
+        printf("lean unit tiles (half-size workgroup; behind the join, with its barrier): clocks %lld\n", prof[UNIT_TILES]);
+        printf("lean early stop (product G^T g_yd and its maximum before the system): clocks %lld products-for-nothing %lld\n", prof[EARLY_TEST], prof[N_EARLY_FOR_NOTHING]);
     }
-#endif
     if (handed_over) {
         if (tid == 0) { b.iters[p] = s.itr; b.status[p] = LEAN_PENDING; }
         return;
@@ -305,7 +296,7 @@ __global__ __launch_bounds__(lean_threads(NST, J0SEL), 2) void gusto_lean_kernel
 template <int MSEL, int NSEL, int GXSEL, int NST, int J0SEL, int NXR>
 __global__ __launch_bounds__(lean_threads(NST, J0SEL), 2) void locp_lean_kernel(QPDims d, QPConst c, LocpBatch b) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    long long prof[35] = {0};                  // (the lap slots of locp_lean.h; [32]: unit_tiles of the half-size kernel; [33], [34]: the early stopping test)
+    lapc::Launch prof;                         // (the lap slots of lap_clock.h: lapc::Slot)
     qp::specialise<MSEL, NSEL>(d);
     fix_problem<MSEL, GXSEL, NST, J0SEL, NXR>(d);
     const size_t p = blockIdx.x;
@@ -326,9 +317,7 @@ __global__ __launch_bounds__(lean_threads(NST, J0SEL), 2) void locp_lean_kernel(
     const int st = ql::solve_qp<MSEL, NSEL, GXSEL, NST, J0SEL>(d, c, dyn, q, wbase, L, &J, &it, w, prof);
     if (q.dbg && SRH_TID == 0) {
         q.dbg[8 * 61] = 2.0; q.dbg[8 * 61 + 1] = (double)st; q.dbg[8 * 61 + 2] = (double)it; q.dbg[8 * 61 + 3] = st == 100 ? 0.0 : 1.0;
-#ifdef SRH_PROFILE
-        for (int i = 0; i < 8; ++i) { q.dbg[8 * 60 + i] = (double)prof[i]; q.dbg[8 * 59 + i] = (double)prof[8 + i]; }
-#endif
+        if constexpr (lapc::ON) for (int i = 0; i < 8; ++i) { q.dbg[8 * 60 + i] = (double)prof[lapc::QP_SETUP + i]; q.dbg[8 * 59 + i] = (double)prof[lapc::NT_GRADIENTS + i]; }
     }
     if (st != 0) {
         if (SRH_TID == 0) { b.status[p] = LEAN_PENDING; b.iters[p] = it; if (b.handed_over) atomicAdd(b.handed_over, 1); }

@@ -106,13 +106,7 @@ __device__ inline void lds_carve(Lds &L, lptr base, const QPDims &d, int nthread
     L.ta = L.A; L.tb = L.A + s.nm4; L.tc = L.A + 2 * s.nm4; L.part = L.A + 3 * s.nm4;
 }
 
-#ifdef SRH_PROFILE
-struct Prof { long long t[24]; long long last; };
-#define QC_SUB(P, x) do { const long long now_ = clock64(); (P).t[x] += now_ - (P).last; (P).last = now_; } while (0)
-#else
-struct Prof { };
-#define QC_SUB(P, x) ((void)0)
-#endif
+using lapc::Prof;                      // the sub-laps of a Newton solve (lap_clock.h, included by locp_dev.h)
 
 __device__ __forceinline__ double readlane_d(double v, int lane) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
@@ -814,9 +808,9 @@ __device__ __forceinline__ void ls_apply(const QPDims &d, Lds &L, clptr in, lptr
 // cancellation and leave the dual residual at 1e-7.
 __device__ __forceinline__ void newton_solve(const QPDims &d, QCWork &qw, Lds &L, clptr gyd, double *rd, Prof &pf) {
     const int nm = d.N * d.m, ldG = qc_ldg(d), tid = SRH_TID, nt = blockDim.x;
-    QC_SUB(pf, 8);
+    pf.lap(lapc::NT_GRADIENTS);
     gT_times(d, qw, L, L.ya, gyd, L.du, gyd ? L.tc : (lptr) nullptr);            // du (scratch) = G^T gy; tc = G^T gyd
-    QC_SUB(pf, 9);
+    pf.lap(lapc::NT_GT1);
     if (gyd) {
         double r = 0.0;
         for (int e = tid; e < nm; e += nt) r = fmax(r, fabs(L.tb[e] + L.tc[e]));
@@ -825,29 +819,29 @@ __device__ __forceinline__ void newton_solve(const QPDims &d, QCWork &qw, Lds &L
     for (int e = tid; e < nm; e += nt) L.ta[e] = -(L.ta[e] + L.du[e]);        // rhs = -g
     __syncthreads();
     dinv_apply(d, L, L.ta);                                                   // t = D^-1 rhs
-    QC_SUB(pf, 10);
+    pf.lap(lapc::NT_RHS);
     g_times(d, qw, L, L.ta, L.yb);                                            // G t
-    QC_SUB(pf, 11);
+    pf.lap(lapc::NT_G1);
     ls_apply<LS_TR>(d, L, L.yb, L.yc);                                        // Ls^T G t
     for (int e = tid; e < ldG; e += nt) L.yc[e] *= L.ks[e];                   // K^-1 = ks (ks K ks)^-1 ks
     __syncthreads();
     k_solve(d, L, L.yc);                                                      // v
     for (int e = tid; e < ldG; e += nt) L.yc[e] *= L.ks[e];
     __syncthreads();
-    QC_SUB(pf, 12);
+    pf.lap(lapc::NT_KSOLVE);
     ls_apply<LS_FWD>(d, L, L.yc, L.yd);                                       // Ls v
     gT_times(d, qw, L, L.yd, (clptr) nullptr, L.du, (lptr) nullptr);             // G^T Ls v
-    QC_SUB(pf, 13);
+    pf.lap(lapc::NT_GT2);
     dinv_apply(d, L, L.du);
     for (int e = tid; e < nm; e += nt) L.du[e] = L.ta[e] - L.du[e];
     __syncthreads();
-    QC_SUB(pf, 14);
+    pf.lap(lapc::NT_DU);
     // dy = G du.  With w = ks v (in L.yc) the solved system reads (I + Ls^T Ky Ls) w = Ls^T G t, Ky = G D^-1 G^T, so that
     // G du = G t - Ky Ls w = Ls^-T w: a back substitution per output stage instead of the product (d.ls_pd: every Ls_k is
     // invertible), and the error of the K solve does not pass through K on its way into dy
     if (d.ls_pd) ls_apply<LS_INVT>(d, L, L.yc, L.dy);
     else g_times(d, qw, L, L.du, L.dy);
-    QC_SUB(pf, 15);
+    pf.lap(lapc::NT_G2);
 }
 
 // ------------------------------------------------------------------ the solve
@@ -870,15 +864,7 @@ __device__ __forceinline__ int solve(const QPDims &dfull, const QPConst &c, cons
     // a QPLds view on this carve for the shared helpers (rollout, reductions)
     Lq.v1 = L.v1; Lq.v2 = L.v2; Lq.Qu = L.Qu; Lq.part = L.part; Lq.red = L.red; Lq.idxl = L.idxl; Lq.flag = L.flag;
     Prof pf;
-#ifdef SRH_PROFILE
-    long long tq[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int i = 0; i < 24; ++i) pf.t[i] = 0;
-    long long tq_last = clock64();
-    auto qlap = [&](int slot) { const long long now = clock64(); tq[slot] += now - tq_last; tq_last = now; };
-#define QC_LAP(x) qlap(x)
-#else
-#define QC_LAP(x) ((void)0)
-#endif
+    lapc::Laps<lapc::NT_GRADIENTS> tq;              // the QP laps (slots QP_*)
     for (int e = tid; e < nm; e += nt) { w.u[e] = 0.0; L.u[e] = 0.0; }
     for (int e = tid; e <= N; e += nt) w.s[e] = 0.0;
     for (int k = tid; k < N; k += nt) L.idxl[k] = dyn.idx ? dyn.idx[k] : k;
@@ -886,11 +872,11 @@ __device__ __forceinline__ int solve(const QPDims &dfull, const QPConst &c, cons
     for (int e = tid; e < (d.nX + d.nXf) * po; e += nt) L.Tx[e] = e < d.nX * po ? c.Tx[e] : c.Txf[e - d.nX * po];
     __syncthreads();
     qp::rollout(d, dyn, q, w.u, w.x, Lq);
-    QC_LAP(0);                                      // set-up + zero-input rollout
+    tq.lap(lapc::QP_SETUP);                                      // set-up + zero-input rollout
     condense<MSEL, NSEL>(d, c, dyn, w.x, qw, L);
     for (int e = tid; e < ldG; e += nt) { L.y[e] = L.yf[e]; L.dy[e] = 0.0; }
     __syncthreads();
-    QC_LAP(2);                                      // condensation
+    tq.lap(lapc::QP_CONDENSE);                                      // condensation
     // ---- the rows of this thread: slot e = tid + nt q;  x rows (k-1) RX + r, then u rows N RX + k nU + r
     bool rv[QR], ru[QR];
     int rk[QR], rr[QR];
@@ -922,7 +908,7 @@ __device__ __forceinline__ int solve(const QPDims &dfull, const QPConst &c, cons
     bool near_opt = false;
     while (true) {
         tid = SRH_TID;
-        QC_LAP(7);
+        tq.lap(lapc::QP_STEPS);
         // ---------------- rows: weights D and gradient shifts rho of this Newton system -> L2 for the stage sums
         double musum = 0.0, rpm = 0.0;
 #pragma unroll
@@ -946,29 +932,27 @@ __device__ __forceinline__ int solve(const QPDims &dfull, const QPConst &c, cons
             rp = wg::reduce(rpm, 1, L.red);
         }
         __syncthreads();
-        QC_LAP(1);
+        tq.lap(lapc::QP_ROWS);
         // ---------------- Newton system
         double rd = 0.0;
         bool ok = true;
         if (mode != CORR) {
             ok = stage_factors(d, c, w.D, L);
-            QC_LAP(3);
+            tq.lap(lapc::QP_STAGE_FACTORS);
             if (ok) {
                 gram<MSEL>(d, qw, L);
-                QC_LAP(4);
+                tq.lap(lapc::QP_GRAM);
                 ok = tile_cholesky(d, L);
-                QC_LAP(5);
+                tq.lap(lapc::QP_CHOLESKY);
             }
         }
-#ifdef SRH_PROFILE
-        pf.last = clock64();
-#endif
+        pf.restart();
         if (ok) {
             if (mode == PRED) gradients(d, c, q, L, w.lam, L.tb, L.yg);          // multipliers: the dual residual
             gradients(d, c, q, L, w.rho, L.ta, L.ya);
             newton_solve(d, qw, L, mode == PRED ? (clptr)L.yg : (clptr) nullptr, &rd, pf);
         }
-        QC_LAP(6);
+        tq.lap(lapc::QP_NEWTON);
         // ---------------- use the direction
         if (mode == INIT) {
             if (ipm::stops(ipm::verdict_system(ok), status)) break;
@@ -1034,9 +1018,9 @@ __device__ __forceinline__ int solve(const QPDims &dfull, const QPConst &c, cons
     __syncthreads();
     for (int e = tid; e < nm; e += nt) w.u[e] = L.u[e];
     __syncthreads();
-#ifdef SRH_PROFILE
-    if (q.dbg && tid == 0) for (int i = 0; i < 8; ++i) { q.dbg[8 * 60 + i] = (double)tq[i]; q.dbg[8 * 59 + i] = (double)pf.t[8 + i]; }
-#endif
+    if constexpr (lapc::ON) {
+        if (q.dbg && tid == 0) for (int i = 0; i < 8; ++i) { q.dbg[8 * 60 + i] = (double)tq[i]; q.dbg[8 * 59 + i] = (double)pf[lapc::NT_GRADIENTS + i]; }
+    }
     if (iters_out) *iters_out = it;
     return status;
 }

@@ -10,6 +10,7 @@
 #pragma once
 #include "dev_la.h"
 #include "ipm_rule.h"
+#include "lap_clock.h"
 #include <type_traits>
 
 struct QPDims {
@@ -218,12 +219,6 @@ __device__ inline void qp_lds_init(QPLds &L, const QPDims &d, const QPConst &c) 
     }
     __syncthreads();
 }
-
-#ifdef SRH_PROFILE
-#define SRH_LAP(x) lap(x)
-#else
-#define SRH_LAP(x) ((void)0)
-#endif
 
 namespace qp {
 
@@ -870,11 +865,7 @@ __device__ __forceinline__ bool riccati_solve(const QPDims &d, const QPConst &c,
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, nw = nt >> 6;
     const int xoff = d.tr ? 2 * n + 1 : 0;
     double rd = 0.0;
-#ifdef SRH_PROFILE
-    long long tp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    long long tl = clock64();
-    auto lap = [&](int sl) { const long long now = clock64(); tp[sl] += now - tl; tl = now; };
-#endif
+    lapc::Laps<8> tp;                                  // load, W, BtW, Qu, gain, AtW+finish, vec-backward, forward (scp.hip prints them)
     // ---- terminal stage
     {
         const int k = N;
@@ -948,7 +939,7 @@ __device__ __forceinline__ bool riccati_solve(const QPDims &d, const QPConst &c,
             // product itself reads P (complete since the barrier of the previous stage's tail) and the panel: a barrier
             // is needed here only for a new panel, for K-padding rows of P, and in split mode
             if (SPLIT || reloaded || NK > n) __syncthreads();
-            SRH_LAP(0);
+            tp.lap(0);
             // split mode (n_x > 64: P, AB and W do not fit LDS together): W = P [A|B] is produced 48 rows at a
             // time; the Gram products that contract over the rows of W accumulate in MFMA registers across the
             // two halves, so only half of W is ever resident
@@ -965,24 +956,24 @@ __device__ __forceinline__ bool riccati_solve(const QPDims &d, const QPConst &c,
                     if (k >= 1) mfma_acc<4>(accP, L.AB + (size_t)r0 * ld, L.W, rows, n16 >> 4, n16 >> 4, ld);
                     __syncthreads();
                 }
-                SRH_LAP(1);
+                tp.lap(1);
                 mfma_put<2>(accQ, L.QUX, ld, 1, NPa >> 4, m);
                 __syncthreads();
             } else {
                 mfma_atb(L.W, ld, L.P, L.AB, NK, n16 >> 4, NPa >> 4, ld, n);          // W = P [A|B]
-                SRH_LAP(1);
+                tp.lap(1);
                 if (qbase) qu_phase();                                                 // upper waves, beside the product below
                 mfma_atb(L.QUX, ld, L.AB + n, L.W, NK, 1, NPa >> 4, ld, 16, m);        // [Qux | B^T P B] = B^T W
             }
-            SRH_LAP(2);
+            tp.lap(2);
             if (qbase == 0) qu_phase();
             // Quu += B^T P B
             for (int e = tid; e < m * m; e += nt) { const int a = e / m, b = e - a * m; L.Quu[e] += L.QUX[a * ld + n + b]; }
             __syncthreads();
             if (with_dual && tid < m) rd = fmax(rd, fabs(L.rdu[tid]));
-            SRH_LAP(3);
+            tp.lap(3);
             if (!stage_gain<SPLIT, MSEL>(d, w, L, k, k >= 1)) return false;
-            SRH_LAP(4);
+            tp.lap(4);
             if (k >= 1) {
                 // P_k = A^T W + (extra rows: -Y^T Y + X^T D X); columns n, n+1 deliver A^T pv, A^T adj
                 const int K2 = d.nzr ? ((d.RC + d.nzr + 3) & ~3) : NK + d.NE4;
@@ -1044,7 +1035,7 @@ __device__ __forceinline__ bool riccati_solve(const QPDims &d, const QPConst &c,
                 }
             }
             sin = snx;
-            SRH_LAP(5);
+            tp.lap(5);
         }
     }
     if (with_dual) {
@@ -1053,12 +1044,10 @@ __device__ __forceinline__ bool riccati_solve(const QPDims &d, const QPConst &c,
         rd = wg::reduce(rd, 1, L.red);
         if (rd_out) *rd_out = rd;
     }
-    SRH_LAP(6);
+    tp.lap(6);
     vector_sweep_fwd<MSEL, NSEL>(d, dyn, w, L);
-    SRH_LAP(7);
-#ifdef SRH_PROFILE
-    if (w.tprof && tid == 0) for (int i = 0; i < 8; ++i) w.tprof[i] += (double)tp[i];
-#endif
+    tp.lap(7);
+    if constexpr (lapc::ON) { if (w.tprof && tid == 0) for (int i = 0; i < 8; ++i) w.tprof[i] += (double)tp[i]; }
     return true;
 }
 
@@ -1130,9 +1119,8 @@ __device__ __forceinline__ int solve(const QPDims &dfull, const QPConst &c, cons
         warm = false;                                  // the condensed attempt has overwritten w.u / w.lam: what follows starts cold
         qp_lds_carve(L, L.base, dfull, nt);            // back to the Riccati layout (its constants are gone: ready = false)
         if (q.dbg && tid == 0) { q.dbg[8 * 61] = 1.0; q.dbg[8 * 61 + 1] = (double)st; q.dbg[8 * 61 + 2] = (double)it; }
-#ifdef SRH_PROFILE
-        if (st != 0 && tid == 0) printf("[qp] block %d: condensed path status %d after %d iterations -> Riccati path\n", (int)blockIdx.x, st, it);
-#endif
+        if constexpr (lapc::ON)
+            if (st != 0 && tid == 0) printf("[qp] block %d: condensed path status %d after %d iterations -> Riccati path\n", (int)blockIdx.x, st, it);
         if (st == 0) {
             QPDims d0 = dfull;
             d0.tr = 0;
@@ -1158,9 +1146,8 @@ __device__ __forceinline__ int solve(const QPDims &dfull, const QPConst &c, cons
                 if (iters_out) *iters_out = it;
                 return 0;
             }
-#ifdef SRH_PROFILE
-            if (tid == 0) printf("[qp] block %d: condensed minimiser outside the trust region -> full QP on the Riccati path\n", (int)blockIdx.x);
-#endif
+            if constexpr (lapc::ON)
+                if (tid == 0) printf("[qp] block %d: condensed minimiser outside the trust region -> full QP on the Riccati path\n", (int)blockIdx.x);
             first_pass = npass - 1;                      // outside the trust region: straight to the full QP
         }
     }
@@ -1182,11 +1169,7 @@ __device__ __forceinline__ int solve(const QPDims &dfull, const QPConst &c, cons
         warm = false; warm_full = false;               // (a repeated pass starts cold)
         const int N = d.N, n = d.n, m = d.m;
         w.tprof = q.dbg ? q.dbg + 8 * 63 : (gptr)nullptr;
-#ifdef SRH_PROFILE
-        long long tm[6] = {0, 0, 0, 0, 0, 0};
-        long long t_last = clock64();
-        auto lap = [&](int slot) { const long long now = clock64(); tm[slot] += now - t_last; t_last = now; };
-#endif
+        lapc::Laps<6> tm;                              // init, rows, prepass, ricc_full, ricc_vec, final (scp.hip prints them)
         const double s0 = slack0(dfull, c, q, L);
         if (!warm_now) for (int e = tid; e < N * m; e += nt) w.u[e] = 0.0;
         for (int e = tid; e <= N; e += nt) w.s[e] = (e == 0) ? s0 : ((warm_now && d.tr) ? fmax(w.s[e], 0.0) : 0.0);
@@ -1244,13 +1227,13 @@ __device__ __forceinline__ int solve(const QPDims &dfull, const QPConst &c, cons
                 });
             }
             __syncthreads();
-            SRH_LAP(1);
+            tm.lap(1);
             // ---------------- Newton system
             stage_prepass(d, c, q, w, mode == PRED);
-            SRH_LAP(2);
+            tm.lap(2);
             double rd = 0.0;
             const bool ok = riccati_solve<SPLIT, MSEL, NSEL>(d, c, dyn, w, L, mode != CORR, mode == PRED, &rd);
-            if (mode == CORR) SRH_LAP(4); else SRH_LAP(3);
+            if (mode == CORR) tm.lap(4); else tm.lap(3);
             // ---------------- use the direction
             if (mode == INIT) {
                 if (ipm::stops(ipm::verdict_system(ok), status)) break;
@@ -1327,15 +1310,13 @@ __device__ __forceinline__ int solve(const QPDims &dfull, const QPConst &c, cons
             ++it;
             mode = PRED;
         }
-        SRH_LAP(1);
+        tm.lap(1);
         if (warm_now && status != 0) { --pass; continue; }      // the warm attempt did not reach the tolerances: the same pass from the cold start
         // final consistency: x is exactly the rollout of u
         rollout(d, dyn, q, w.u, w.x, L);
         J = objective(d, c, q, w.x, w.u, w.s, L);
-        SRH_LAP(5);
-#ifdef SRH_PROFILE
-        if (q.dbg && tid == 0) for (int i = 0; i < 6; ++i) q.dbg[8 * 62 + i] = (double)tm[i];
-#endif
+        tm.lap(5);
+        if constexpr (lapc::ON) { if (q.dbg && tid == 0) for (int i = 0; i < 6; ++i) q.dbg[8 * 62 + i] = (double)tm[i]; }
         if (npass == 2 && pass == 0) {
             if (status != 0) continue;               // relaxed QP not solved: go to the full QP
             double md = 0.0;

@@ -794,9 +794,6 @@ __device__ __forceinline__ void gT_times(const QPDims &d, const GP &g, Lds &L, c
 // runs over the stages that reach it: 2 j < 16 (I + 1).  Stages with 2 j <= 16 I reach every lane of the tile row (no
 // masks); the last seven are triangular.  sched: per wave 4 tasks x {I, J0, nJ, 0} (host-built, longest first onto the
 // least loaded SIMD; nJ = 0: no more tasks).
-#ifdef SRH_PROFILE
-__device__ long long g_prof_waves[16];         // per-wave clocks of the Gram fill (products, epilogue), cumulative over the launch's workgroup 0
-#endif
 // STAGE (the half-size layout, where every packed row has its home in the L2 block): the K-tile area L.B is dead when a Gram fill
 // starts -- the factor of the iteration before has been used, every tile is rewritten here -- so the rows of the stages >= g.j0 are
 // copied into it once (g.gt == L.B, from gsrc) and the tiles read them from LDS instead of once per tile row and column they meet
@@ -823,12 +820,7 @@ __device__ __forceinline__ void gram_t(const QPDims &d, const QPConst &c, const 
     const int l16 = lane & 15, kk = lane >> 4;
     const int goff0 = goff(g.j0, M, NP);
     lptr w2 = L.tc;                                            // 1 / D per packed row
-#ifdef SRH_PROFILE
-    long long gl[6] = {0, 0, 0, 0, 0, 0}, g0 = clock64(), g1;   // 1/D pass + barrier, descriptors, products, epilogue, barrier, scaling + barrier (STAGE: scaled store + barrier)  (wave 0 -> L.Qu[4..7], L.Qu[13..14])
-#define GR_LAP(i) do { g1 = clock64(); gl[i] += g1 - g0; g0 = g1; } while (0)
-#else
-#define GR_LAP(i) ((void)0)
-#endif
+    lapc::Laps<6> gl;          // 1/D pass + barrier, descriptors, products, epilogue, barrier, scaling + barrier (STAGE: scaled store + barrier)
     // The tile tasks are PULLED: the list (longest first, scp_host.h) goes into LDS beside a counter, a wave that has finished a task
     // takes the next one -- the static assignment of round 5a left the busiest wave 40 % behind the first one to finish whatever
     // cost model placed the tasks (the waves of a SIMD share its MFMA pipe, the L2 head of G is slower than its LDS tail, ...).
@@ -854,7 +846,7 @@ __device__ __forceinline__ void gram_t(const QPDims &d, const QPConst &c, const 
         }
     }
     __syncthreads();
-    GR_LAP(0);
+    gl.lap(0);
     constexpr int NACC = STAGE ? 8 : 4;
     wg::qp_d4 acc[NACC];
     // ---- the products of one task: tiles (I, J0 .. J0 + nJ - 1) into acc[BASE ..], nJ <= CAP
@@ -999,17 +991,17 @@ __device__ __forceinline__ void gram_t(const QPDims &d, const QPConst &c, const 
             if (tnext >= GRAM_TASKS) break;
             const int I = __builtin_amdgcn_readfirstlane(tl[4 + 4 * tnext]), J0 = __builtin_amdgcn_readfirstlane(tl[5 + 4 * tnext]),
                       nJ = __builtin_amdgcn_readfirstlane(tl[6 + 4 * tnext]);
-            GR_LAP(1);
+            gl.lap(1);
             if (nJ == 0) break;
 #pragma unroll
             for (int t = 0; t < 4; ++t) acc[t] = {0.0, 0.0, 0.0, 0.0};
             products(I, J0, nJ, B0, C4, std::false_type{});
-            GR_LAP(2);
+            gl.lap(2);
             epilogue(I, J0, nJ, B0, C4, std::true_type{});
-            GR_LAP(3);
+            gl.lap(3);
         }
         __syncthreads();
-        GR_LAP(4);
+        gl.lap(4);
         // ---- symmetric scaling to a unit diagonal (see qpc::gram for why it matters): the upper tiles over the waves
         for (int t = wave, I = 0, rowlen = KT; t < KT * (KT + 1) / 2; t += nt >> 6) {
             int tt = t;
@@ -1032,7 +1024,7 @@ __device__ __forceinline__ void gram_t(const QPDims &d, const QPConst &c, const 
             const int e = 4 + 4 * (GRAM_SLOTS * wave + s);
             sI[s] = __builtin_amdgcn_readfirstlane(tl[e]); sJ[s] = __builtin_amdgcn_readfirstlane(tl[e + 1]); sn[s] = __builtin_amdgcn_readfirstlane(tl[e + 2]);
         }
-        GR_LAP(1);
+        gl.lap(1);
 #pragma unroll
         for (int t = 0; t < NACC; ++t) acc[t] = {0.0, 0.0, 0.0, 0.0};
         if (gtoep != nullptr) {
@@ -1044,24 +1036,26 @@ __device__ __forceinline__ void gram_t(const QPDims &d, const QPConst &c, const 
             if (sn[1] > 0) products(sI[1], sJ[1], sn[1], B1, C3, std::false_type{});
             if (sn[2] > 0) products(sI[2], sJ[2], sn[2], B2, C1, std::false_type{});
         }
-        GR_LAP(2);
+        gl.lap(2);
         if (sn[0] > 0) epilogue(sI[0], sJ[0], sn[0], B0, C4, std::false_type{});
         if (sn[1] > 0) epilogue(sI[1], sJ[1], sn[1], B1, C3, std::false_type{});
         if (sn[2] > 0) epilogue(sI[2], sJ[2], sn[2], B2, C1, std::false_type{});
-        GR_LAP(3);
+        gl.lap(3);
         __syncthreads();                                       // every wave has read its last staged row and published its part of L.ks: L.B takes the tiles
-        GR_LAP(4);
+        gl.lap(4);
         if (sn[0] > 0) store_scaled(sI[0], sJ[0], sn[0], B0, C4);
         if (sn[1] > 0) store_scaled(sI[1], sJ[1], sn[1], B1, C3);
         if (sn[2] > 0) store_scaled(sI[2], sJ[2], sn[2], B2, C1);
     }
     __syncthreads();
-    GR_LAP(5);
-#ifdef SRH_PROFILE
-    if (tid == 0) { for (int i = 0; i < 4; ++i) L.Qu[4 + i] += (double)gl[i]; L.Qu[13] += (double)gl[4]; L.Qu[14] += (double)gl[5]; }
-    if (lane == 0 && blockIdx.x == 0) { g_prof_waves[wave] += gl[2]; g_prof_waves[8 + wave] += gl[3]; }
-#endif
-#undef GR_LAP
+    gl.lap(5);
+    if constexpr (lapc::ON) {                                  // wave 0's laps to the mailbox, every wave's products and epilogue to the per-wave sums
+        if (tid == 0) {
+            for (int i = 0; i < 4; ++i) L.Qu[lapc::MAIL_GRAM + i] += (double)gl[i];
+            L.Qu[lapc::MAIL_GRAM_BARRIER] += (double)gl[4]; L.Qu[lapc::MAIL_GRAM_STORE] += (double)gl[5];
+        }
+        if (lane == 0 && blockIdx.x == 0) { lapc::WaveLaps::add(wave, gl[2]); lapc::WaveLaps::add(8 + wave, gl[3]); }
+    }
 }
 template <int MSEL, class GP>
 __device__ __forceinline__ void gram(const QPDims &d, const QPConst &c, const GP &g, Lds &L) { gram_t<MSEL, false>(d, c, g, L); }
@@ -1123,38 +1117,30 @@ __device__ __forceinline__ void tile_cholesky_set(const QPDims &d, Lds &L, int w
     const int l16 = lane & 15, kk = lane >> 4;
     liptr Ftrail = F, Frinv = F + 1, Fpanel = F + 2;
     if (wave == 0) {
-#ifdef SRH_PROFILE
-        long long cl[5] = {0, 0, 0, 0, 0}, c0 = clock64(), c1;            // wait, panel, update, factor, signals (L.Qu[8..12])
-#define TC_LAP(i) do { c1 = clock64(); cl[i] += c1 - c0; c0 = c1; } while (0)
-#else
-#define TC_LAP(i) ((void)0)
-#endif
+        lapc::Laps<lapc::CH_END> cl;
         bool ok = qpc::chol16<false>(L.B, rinv_tile(L, 0, KT));
-        TC_LAP(3);
+        cl.lap(lapc::CH_FACTOR);
         set_signal(Frinv);
-        TC_LAP(4);
+        cl.lap(lapc::CH_SIGNALS);
         for (int J = 0; J + 1 < KT; ++J) {
             set_wait(Fnext, roster_next_target(J));                // (J, J + 1) and (J + 1, J + 1) carry the updates of row J - 1
-            TC_LAP(0);
+            cl.lap(lapc::CH_WAIT);
             const wg::qp_d4 P = panel_tile(L, KT, J, J + 1, l16, kk);
-            TC_LAP(1);
+            cl.lap(lapc::CH_PANEL);
             set_signal(Fpanel);
-            TC_LAP(4);
+            cl.lap(lapc::CH_SIGNALS);
             lptr T = L.B + (size_t)qpc::tile_index(J + 1, J + 1, KT) * TSZ;
             __builtin_amdgcn_wave_barrier();
             tile_update_reg(T, P, l16, kk);
             __builtin_amdgcn_wave_barrier();
-            TC_LAP(2);
+            cl.lap(lapc::CH_UPDATE);
             ok = qpc::chol16<false>(T, rinv_tile(L, J + 1, KT)) && ok;
-            TC_LAP(3);
+            cl.lap(lapc::CH_FACTOR);
             set_signal(Frinv);
-            TC_LAP(4);
+            cl.lap(lapc::CH_SIGNALS);
         }
         if (lane == 0) L.flag[1] = ok ? 1 : 0;
-#ifdef SRH_PROFILE
-        if (lane == 0) for (int i = 0; i < 5; ++i) L.Qu[8 + i] = (double)cl[i];
-#endif
-#undef TC_LAP
+        if constexpr (lapc::ON) { if (lane == 0) for (int i = 0; i < lapc::CH_END; ++i) L.Qu[lapc::MAIL_CHAIN + i] = (double)cl[i]; }
     } else {
         const int worker = wave - 1;
         for (int J = 0; J + 1 < KT; ++J) {
@@ -1300,10 +1286,10 @@ template <int MSEL, bool HALF, class GP>
 __device__ __forceinline__ void newton_front(const QPDims &d, const GP &g, Lds &L, clptr gyd, Waves<HALF> &W, Prof &pf,
                                              bool keep_gt = false, bool reuse_gt = false) {
     const int N = d.N, nm = N * d.m, ldG = 16 * d.KT, tid = W.tid, nt = W.nt;
-    QC_SUB(pf, 8);
+    pf.lap(lapc::NT_GRADIENTS);
     if (!reuse_gt) gT_times<MSEL, HALF>(d, g, L, L.ya, gyd, L.du, gyd ? L.tc : (lptr) nullptr, W);
     clptr gty = reuse_gt ? (clptr)L.tb : (clptr)L.du;
-    QC_SUB(pf, 9);
+    pf.lap(lapc::NT_GT1);
     if (gyd) {
         double r = 0.0;
         for (int e = tid; e < nm; e += nt) r = fmax(r, fabs(L.tb[e] + L.tc[e]));
@@ -1317,9 +1303,9 @@ __device__ __forceinline__ void newton_front(const QPDims &d, const GP &g, Lds &
     }
     W.sync();
     if (gyd && tid == 0) { double r = L.red[0]; for (int i = 1; i < W.nw; ++i) r = fmax(r, L.red[i]); L.Qu[0] = r; }
-    QC_SUB(pf, 10);
+    pf.lap(lapc::NT_RHS);
     g_times<MSEL, HALF>(d, g, L, L.ta, L.yb, W);
-    QC_SUB(pf, 11);
+    pf.lap(lapc::NT_G1);
     // yc = ks (Ls^T yb) per output stage (p_o = 2, Ls lower: out_0 = L00 v0 + L10 v1, out_1 = L11 v1); padding zeroed
     for (int k = tid; k < ldG / 2; k += nt) {
         double o0 = 0.0, o1 = 0.0;
@@ -1358,14 +1344,14 @@ __device__ __forceinline__ void newton_back(const QPDims &d, const GP &g, Lds &L
         if (dy_here) { L.dy[2 * k] = e0; L.dy[2 * k + 1] = e1; }
     }
     __syncthreads();
-    QC_SUB(pf, 12);
+    pf.lap(lapc::NT_KSOLVE);
     gT_times<MSEL>(d, g, L, L.yd, (clptr) nullptr, L.du, (lptr) nullptr);
-    QC_SUB(pf, 13);
+    pf.lap(lapc::NT_GT2);
     for (int e = tid; e < nm; e += nt) { const double sd = L.Ldi[e]; L.du[e] = L.ta[e] - L.du[e] * (sd * sd); }
     __syncthreads();
-    QC_SUB(pf, 14);
+    pf.lap(lapc::NT_DU);
     if (!dy_here) g_times<MSEL>(d, g, L, L.du, L.dy);
-    QC_SUB(pf, 15);
+    pf.lap(lapc::NT_G2);
 }
 
 // the whole solve on the whole workgroup (the general-row interior point; corrector solves)
@@ -1375,6 +1361,20 @@ __device__ __forceinline__ void newton_solve(const QPDims &d, const GP &g, Lds &
     newton_front<MSEL, false>(d, g, L, gyd, W, pf, false, reuse_gt);
     if (gyd) *rd = L.Qu[0];
     newton_back<MSEL>(d, g, L, pf);
+}
+// (profile builds) the Gram fill's per-wave sums of a workgroup of nw waves
+__device__ __forceinline__ void print_gram_wave_laps(int nw) {
+    printf("lean gram per wave (cumulative) products:");
+    for (int i = 0; i < nw; ++i) printf(" %lld", lapc::WaveLaps::get(i));
+    printf("  epilogue:");
+    for (int i = 0; i < nw; ++i) printf(" %lld", lapc::WaveLaps::get(8 + i));
+    printf("\n");
+}
+// what the two wave sets of a split Newton system left in the lap mailbox, into the launch array (behind the join's barrier; read LDS:
+// call it behind `if constexpr (lapc::ON)`)
+__device__ __forceinline__ void split_mail_fold(Lds &L, lapc::Launch &prof) {
+    prof.add(lapc::SPLIT_FACTOR, (long long)L.Qu[lapc::MAIL_SPLIT_FACTOR]); prof.add(lapc::SPLIT_FRONT, (long long)L.Qu[lapc::MAIL_SPLIT_FRONT]);
+    for (int i = 0; i < lapc::CH_END; ++i) prof.add(lapc::CHAIN_WAIT + i, (long long)L.Qu[lapc::MAIL_CHAIN + i]);
 }
 
 // The condensation (G, free response) depends on the linearisation only: when the region sequence of this QP equals
@@ -1434,7 +1434,7 @@ __device__ __forceinline__ int converged_early(const QPDims &d, const GP &g, Lds
 // Results: w.u, and -- after the final rollout of solve_qp below -- w.x.  Returns 0 optimal, 1 max iterations, 2 numerical failure.
 template <int MSEL, int NSEL>
 __device__ __forceinline__ int ipm(const QPDims &dfull, const QPConst &c, const QPDyn &dyn, const QPData &q, gptr work_base,
-                                   Lds &L, QPLds &Lq, int *iters_out, QPWork &wout, long long *prof) {
+                                   Lds &L, QPLds &Lq, int *iters_out, QPWork &wout, lapc::Launch &prof) {
     int tid = SRH_TID;                                       // re-read at the top of every interior-point iteration (dev_la.h: SRH_TID)
     const int nt = blockDim.x;
     QPDims d = dfull;
@@ -1446,14 +1446,7 @@ __device__ __forceinline__ int ipm(const QPDims &dfull, const QPConst &c, const 
     const int N = d.N, m = d.m, po = d.po, nm = N * m, ldG = 16 * d.KT, NP = N * po;
     GPack g{(cgptr)gh, (clptr)(L.Gt), d.lean_j0, m, NP};
     Prof pf;
-#ifdef SRH_PROFILE
-    for (int i = 0; i < 24; ++i) pf.t[i] = 0;
-    long long tq_last = clock64();
-    auto qlap = [&](int slot) { const long long now = clock64(); prof[slot] += now - tq_last; tq_last = now; };
-#define QL_LAP(x) qlap(x)
-#else
-#define QL_LAP(x) ((void)0)
-#endif
+    lapc::Clock lp;
     for (int e = tid; e < nm; e += nt) { w.u[e] = 0.0; L.u[e] = 0.0; }
     static_assert(YPAD == 48, "the carve reserves 48 doubles behind ya, yd, yg");
     for (int e = tid; e < YPAD; e += nt) { L.ya[ldG + e] = 0.0; L.yd[ldG + e] = 0.0; L.yg[ldG + e] = 0.0; }
@@ -1465,14 +1458,14 @@ __device__ __forceinline__ int ipm(const QPDims &dfull, const QPConst &c, const 
     const bool reuse = same_regions(dyn, L, L.goff, N, tid, nt);
     if (!reuse) {
     rollout<MSEL, NSEL>(d, dyn, q.x0, (cgptr) nullptr, w.x, L);
-    QL_LAP(0);
+    lp.lap(prof, lapc::QP_SETUP);
     condense<MSEL, NSEL>(d, c, dyn, w.x, gh, L);
     for (int k = tid; k < N; k += nt) L.goff[k] = L.idxl[k];
     if (tid == 0) L.flag[2] = 1;
     }
     for (int e = tid; e < ldG; e += nt) { L.y[e] = L.yf[e]; L.dy[e] = 0.0; }
     __syncthreads();
-    QL_LAP(2);
+    lp.lap(prof, lapc::QP_CONDENSE);
     bool rv[QR], ru[QR];
     int rk[QR], rr[QR];
     double rh[QR], rt[QR], rlam[QR], rrg[QR], rrc[QR], rdt[QR], rdl[QR];
@@ -1503,7 +1496,7 @@ __device__ __forceinline__ int ipm(const QPDims &dfull, const QPConst &c, const 
     bool near_opt = false;
     while (true) {
         tid = SRH_TID;
-        QL_LAP(7);
+        lp.lap(prof, lapc::QP_STEPS);
         double musum = 0.0, rpm = 0.0;
 #pragma unroll
         for (int qi = 0; qi < QR; ++qi) {
@@ -1526,7 +1519,7 @@ __device__ __forceinline__ int ipm(const QPDims &dfull, const QPConst &c, const 
             rp = wg::reduce(rpm, 1, L.red);
         }
         __syncthreads();
-        QL_LAP(1);
+        lp.lap(prof, lapc::QP_ROWS);
         // converged already?  Then no system (converged_early; the gradients of the dual residual as below, the front's own partition)
         if (mode == PRED && !d.ipm_late_stop && ipm::may_converge(mu, rp, sp, d.tol)) {
             qpc::gradients(d, c, q, L, w.lam, L.tb, L.yg);
@@ -1541,24 +1534,22 @@ __device__ __forceinline__ int ipm(const QPDims &dfull, const QPConst &c, const 
         bool ok = true;
         if (mode != CORR) {
             ok = qpc::stage_factors(d, c, w.D, L);
-            QL_LAP(3);
+            lp.lap(prof, lapc::QP_STAGE_FACTORS);
             if (ok) {
                 gram<MSEL>(d, c, g, L);
-                QL_LAP(4);
+                lp.lap(prof, lapc::QP_GRAM);
                 ok = qpc::tile_cholesky(d, L);
                 if (ok) unit_tiles(d, L);
-                QL_LAP(5);
+                lp.lap(prof, lapc::QP_CHOLESKY);
             }
         }
-#ifdef SRH_PROFILE
-        pf.last = clock64();
-#endif
+        pf.restart();
         if (ok) {
             if (mode == PRED) qpc::gradients(d, c, q, L, w.lam, L.tb, L.yg);
             qpc::gradients(d, c, q, L, w.rho, L.ta, L.ya);
             newton_solve<MSEL>(d, g, L, mode == PRED ? (clptr)L.yg : (clptr) nullptr, &rd, pf);
         }
-        QL_LAP(6);
+        lp.lap(prof, lapc::QP_NEWTON);
         if (mode == INIT) {
             if (ipm::stops(ipm::verdict_system(ok), status)) break;
             for (int e = tid; e < nm; e += nt) L.u[e] += L.du[e];
@@ -1621,9 +1612,7 @@ __device__ __forceinline__ int ipm(const QPDims &dfull, const QPConst &c, const 
     __syncthreads();
     for (int e = tid; e < nm; e += nt) w.u[e] = L.u[e];
     __syncthreads();
-#ifdef SRH_PROFILE
-    for (int i = 0; i < 8; ++i) prof[8 + i] += pf.t[8 + i];
-#endif
+    pf.fold(prof);
     if (iters_out) *iters_out = it;
     return status;
 }
@@ -1659,7 +1648,7 @@ __device__ __forceinline__ double gsum(double v) {
 
 template <int MSEL, int NSEL, int GX, int NST = 0, int J0SEL = 0>
 __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, const QPDyn &dyn, const QPData &q, gptr work_base,
-                                       Lds &L, int *iters_out, QPWork &wout, long long *prof, int warm_mode = 0) {
+                                       Lds &L, int *iters_out, QPWork &wout, lapc::Launch &prof, int warm_mode = 0) {
     // warm_mode: 0 cold start, 1 warm start (below), 2 warm start whose multipliers are replaced by +inf -- a test knob
     // (GustoPar::poison_warm, SRH_LEAN_POISON_WARM=1 at plan creation) that makes the warm attempt fail so that the caller's cold
     // retry runs under a test
@@ -1675,14 +1664,7 @@ __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, co
     const int N = d.N, m = d.m, nm = N * m, ldG = 16 * d.KT, NP = 2 * N, nz = d.nz;
     GPackT<NST, J0SEL> g{(cgptr)gh, (clptr)(L.Gt), d.lean_j0, m, NP};
     Prof pf;
-#ifdef SRH_PROFILE
-    for (int i = 0; i < 24; ++i) pf.t[i] = 0;
-    long long tq_last = clock64();
-    auto qlap = [&](int slot) { const long long now = clock64(); prof[slot] += now - tq_last; tq_last = now; };
-#define QB_LAP(x) qlap(x)
-#else
-#define QB_LAP(x) ((void)0)
-#endif
+    lapc::Clock lp, split;                     // (declared here, re-armed where they start: an object in a nested scope moved two PHIs of the product kernel)
     // warm (round 4): the previous QP of this SCP solve left its minimiser in w.u and its multipliers in w.lam -- this QP differs
     // by its linearisation point only and shares most of the active set: the interior point starts from that point (u as it
     // is, slacks from THIS QP's rows, multipliers kept, both at least WARM_FLOOR from zero) and skips the initial Newton system.
@@ -1692,9 +1674,7 @@ __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, co
     for (int e = tid; e < ldG + YPAD; e += nt) { L.ya[e] = 0.0; L.yd[e] = 0.0; L.yg[e] = 0.0; }     // padding stays zero for good
     for (int e = tid; e <= N; e += nt) w.s[e] = 0.0;
     for (int k = tid; k < N; k += nt) L.idxl[k] = dyn.idx ? dyn.idx[k] : k;
-#ifdef SRH_PROFILE
-    if (tid < 16) L.Qu[tid] = 0.0;
-#endif
+    if constexpr (lapc::ON) { if (tid < 16) L.Qu[tid] = 0.0; }       // (the lap mailbox)
     if (tid < 5) L.flag[3 + tid] = 0;                          // counters of the two wave sets (Waves, tile_cholesky_set; [3]: idle between the region tests of two QPs)
     __syncthreads();
     const bool reuse = same_regions(dyn, L, L.goff, N, tid, nt);
@@ -1705,7 +1685,7 @@ __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, co
     if (!reuse) {
         const bool single = single_region(d, c, dyn, L);
         rollout<MSEL, NSEL>(d, dyn, q.x0, (cgptr) nullptr, w.x, L);
-        QB_LAP(0);
+        lp.lap(prof, lapc::QP_SETUP);
         if (single) condense_single<MSEL, NSEL>(d, c, dyn, w.x, gh, L);
         else condense<MSEL, NSEL>(d, c, dyn, w.x, gh, L);
         for (int k = tid; k < N; k += nt) L.goff[k] = L.idxl[k];
@@ -1721,7 +1701,7 @@ __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, co
         for (int e = tid; e < ldG; e += nt) { L.y[e] = L.yf[e]; L.dy[e] = 0.0; }
     }
     __syncthreads();
-    QB_LAP(2);
+    lp.lap(prof, lapc::QP_CONDENSE);
     // ---- this thread's rows
     const bool isu = tid < nm;
     const int tx = tid - nm;
@@ -1776,7 +1756,7 @@ __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, co
     }
     while (true) {
         tid = SRH_TID;
-        QB_LAP(7);
+        lp.lap(prof, lapc::QP_STEPS);
         // ---------------- rows -> weights, gradient shifts, and their per-stage sums, all in place
         double musum = 0.0, rpm = 0.0;
         double Dw[2] = {0.0, 0.0}, rho[2] = {0.0, 0.0};
@@ -1818,14 +1798,12 @@ __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, co
             rp = rpm;
         }
         __syncthreads();
-        QB_LAP(1);
+        lp.lap(prof, lapc::QP_ROWS);
         // ---------------- converged already?  Then no system (converged_early; 32: the rows per pass of the front's four waves)
         if (mode == PRED) {
             double rde;                                        // (not rd: nothing of the early test stays live through the system)
             const int early = converged_early<MSEL, 32>(d, g, L, mu, rp, sd, sp, rde);
-#ifdef SRH_PROFILE
-            if (early != EARLY_NO_GATE) { QB_LAP(33); if (early == EARLY_GO_ON) prof[34] += 1; }
-#endif
+            if (early != EARLY_NO_GATE) { lp.lap(prof, lapc::EARLY_TEST); if (early == EARLY_GO_ON) prof.add(lapc::N_EARLY_FOR_NOTHING); }
             if (early == EARLY_STOP) {
                 if (q.dbg && tid == 0) { gptr gd = q.dbg + 8 * it; gd[0] = mu; gd[1] = rde; gd[2] = rp; gd[3] = sd; gd[4] = sp; }
                 status = 0;
@@ -1836,52 +1814,37 @@ __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, co
         double rd = 0.0;
         bool ok = true;
         if (mode != CORR) {
-            QB_LAP(3);
+            lp.lap(prof, lapc::QP_STAGE_FACTORS);
             gram<MSEL>(d, c, g, L);
-            QB_LAP(4);
+            lp.lap(prof, lapc::QP_GRAM);
             // the factorisation (waves 0-3: a chain of one-wave 16 x 16 factorisations) beside the half of the Newton solve that
             // does not need the factor (waves 4-7), see Waves
             const clptr gyd = mode == PRED ? (clptr)L.yg : (clptr) nullptr;
             const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef SRH_PROFILE
-            pf.last = clock64();
-#endif
-#ifdef SRH_PROFILE
-            const long long tsplit = clock64();
-#endif
+            pf.restart();
+            split.restart();
             auto W = half_waves(L.flag + 4);
             if (half_of_wave(wv) == 0) {
                 tile_cholesky_set(d, L, W.wave, W.tid & 63, W.nw - 1, L.flag + 5, L.flag + 3);
-#ifdef SRH_PROFILE
-                if (tid == 0) L.Qu[2] = (double)(clock64() - tsplit);
-#endif
+                if constexpr (lapc::ON) { if (tid == 0) L.Qu[lapc::MAIL_SPLIT_FACTOR] = (double)split.since(); }
             } else {
                 newton_front<MSEL, true>(d, g, L, gyd, W, pf, ya_const && mode == PRED);
-#ifdef SRH_PROFILE
-                if (W.tid == 0) L.Qu[3] = (double)(clock64() - tsplit);
-#endif
+                if constexpr (lapc::ON) { if (W.tid == 0) L.Qu[lapc::MAIL_SPLIT_FRONT] = (double)split.since(); }
             }
             __syncthreads();
-#ifdef SRH_PROFILE
-            prof[16] += (long long)L.Qu[2]; prof[17] += (long long)L.Qu[3];
-            for (int i = 0; i < 5; ++i) prof[27 + i] += (long long)L.Qu[8 + i];
-#endif
+            if constexpr (lapc::ON) split_mail_fold(L, prof);
             ok = L.flag[1] != 0;
             if (tid < 5) L.flag[3 + tid] = 0;                  // the factorising half's early-tile counter, the product half's arrival counter and the factorising half's three, for the next split
             if (gyd) rd = L.Qu[0];
             if (ok) unit_tiles(d, L);
-            QB_LAP(5);
-#ifdef SRH_PROFILE
-            pf.last = clock64();
-#endif
+            lp.lap(prof, lapc::QP_CHOLESKY);
+            pf.restart();
             if (ok) newton_back<MSEL>(d, g, L, pf);
         } else {
-#ifdef SRH_PROFILE
-            pf.last = clock64();
-#endif
+            pf.restart();
             newton_solve<MSEL>(d, g, L, (clptr) nullptr, &rd, pf, ya_const);
         }
-        QB_LAP(6);
+        lp.lap(prof, lapc::QP_NEWTON);
         // ---------------- use the direction
         if (mode == INIT) {
             if (ipm::stops(ipm::verdict_system(ok), status)) break;
@@ -1914,9 +1877,9 @@ __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, co
                 ipm::step_bound(rt[s2], rlam[s2], rdt[s2], rdl[s2], amax);
             }
         }
-        QB_LAP(18);
+        lp.lap(prof, lapc::STEP_ROWS);
         reduce2(amax, 2, dummy, 0, L.red);
-        QB_LAP(19);
+        lp.lap(prof, lapc::STEP_AMAX);
         if (mode == PRED) {
             if (ipm::stops(ipm::verdict_failed(ok, mu, rd, near_opt), status)) break;
             if (q.dbg && tid == 0) { gptr gd = q.dbg + 8 * it; gd[0] = mu; gd[1] = rd; gd[2] = rp; gd[3] = sd; gd[4] = sp; }
@@ -1926,9 +1889,9 @@ __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, co
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2)
                 if (s2 < nrow) ma += ipm::affine_term(rt[s2], rlam[s2], rdt[s2], rdl[s2], a_aff);
-            QB_LAP(20);
+            lp.lap(prof, lapc::STEP_MU_ROWS);
             reduce2(ma, 0, dummy, 0, L.red);
-            QB_LAP(21);
+            lp.lap(prof, lapc::STEP_MU_AFF);
             const double mu_aff = ma / d.ng;
             sig = ipm::centring(mu_aff, mu);
             if (q.dbg && tid == 0) { gptr gd = q.dbg + 8 * it; gd[5] = a_aff; gd[6] = sig; }
@@ -1953,20 +1916,14 @@ __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, co
         for (int s2 = 0; s2 < 2; ++s2) if (s2 < nrow) w.lam[lslot + s2] = rlam[s2];
     }
     __syncthreads();
-#ifdef SRH_PROFILE
-    for (int i = 0; i < 8; ++i) prof[8 + i] += pf.t[8 + i];
-    prof[24] += it; prof[25] += 1; prof[26] += warm ? 1 : 0;
-    if (tid == 0 && blockIdx.x == 0)
-        printf("lean gram laps (this QP, wave 0): 1/D+barrier %.0f descriptors %.0f products %.0f epilogue %.0f barrier %.0f scaling+barrier %.0f\n",
-               L.Qu[4], L.Qu[5], L.Qu[6], L.Qu[7], L.Qu[13], L.Qu[14]);
-    if (tid == 0 && blockIdx.x == 0) {
-        printf("lean gram per wave (cumulative) products:");
-        for (int i = 0; i < 8; ++i) printf(" %lld", g_prof_waves[i]);
-        printf("  epilogue:");
-        for (int i = 0; i < 8; ++i) printf(" %lld", g_prof_waves[8 + i]);
-        printf("\n");
+    pf.fold(prof, it, warm);
+    if constexpr (lapc::ON) {
+        if (tid == 0 && blockIdx.x == 0) {
+            printf("lean gram laps (this QP, wave 0): 1/D+barrier %.0f descriptors %.0f products %.0f epilogue %.0f barrier %.0f scaling+barrier %.0f\n",
+                   L.Qu[lapc::MAIL_GRAM], L.Qu[lapc::MAIL_GRAM + 1], L.Qu[lapc::MAIL_GRAM + 2], L.Qu[lapc::MAIL_GRAM + 3], L.Qu[lapc::MAIL_GRAM_BARRIER], L.Qu[lapc::MAIL_GRAM_STORE]);
+            print_gram_wave_laps(8);
+        }
     }
-#endif
     if (iters_out) *iters_out = it;
     return status;
 }
@@ -1983,7 +1940,7 @@ __device__ __forceinline__ int ipm_box(const QPDims &dfull, const QPConst &c, co
 // Sums over rows are taken in another order than ipm_box's (reduce2 over 4 waves, two roles per thread): rounding-level differences.
 template <int MSEL, int NSEL, int GX, int NST = 0, int J0SEL = 0>
 __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, const QPDyn &dyn, const QPData &q, gptr work_base,
-                                        Lds &L, int *iters_out, QPWork &wout, long long *prof, int warm_mode = 0) {
+                                        Lds &L, int *iters_out, QPWork &wout, lapc::Launch &prof, int warm_mode = 0) {
     const bool warm = warm_mode != 0, poison = warm_mode == 2;
     int tid = SRH_TID;                                       // re-read at the top of every interior-point iteration (dev_la.h: SRH_TID)
     const int nt = blockDim.x;
@@ -1998,17 +1955,11 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
     // the Gram fill's own pack: the stages >= gram_stage_j0 staged in the K-tile area (gram_t)
     const GPack gg{(cgptr)gh, (clptr)(L.B), gram_stage_j0(d), m, NP};
     Prof pf;
-#ifdef SRH_PROFILE
-    for (int i = 0; i < 24; ++i) pf.t[i] = 0;
-    long long tq_last = clock64();
-    auto qlap = [&](int slot) { const long long now = clock64(); prof[slot] += now - tq_last; tq_last = now; };
-    if (tid < 15) L.Qu[tid] = 0.0;                             // (the laps of gram_t; [15] is the serial wave's)
-    int ngram = 0, cond_mode = 0;                              // condensation of this QP: 0 kept from the QP before, 1 general, 2 single-region
-    long long cond_clk = 0;
-#define Q4_LAP(x) qlap(x)
-#else
-#define Q4_LAP(x) ((void)0)
-#endif
+    lapc::Clock lp, split, front;                     // (declared here, re-armed where they start: an object in a nested scope moved two PHIs of the product kernel)
+    if constexpr (lapc::ON) { if (tid < 15) L.Qu[tid] = 0.0; }       // (the lap mailbox; [15] is the serial wave's)
+    // (printed by profile builds) Gram fills of this QP, its condensation (0 kept from the QP before, 1 general, 2 single-region) and the clocks of it
+    lapc::Counters<3> qinfo;
+    enum { NGRAM, COND_MODE, COND_CLK };
     if (warm) { for (int e = tid; e < nm; e += nt) L.u[e] = w.u[e]; }
     else { for (int e = tid; e < nm; e += nt) { w.u[e] = 0.0; L.u[e] = 0.0; } }
     for (int e = tid; e < ldG + L.ypad; e += nt) { L.ya[e] = 0.0; L.yd[e] = 0.0; L.yg[e] = 0.0; }     // padding stays zero for good
@@ -2024,12 +1975,11 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
     if (!reuse) {
         const bool single = single_region(d, c, dyn, L);
         rollout<MSEL, NSEL, false, 4>(d, dyn, q.x0, (cgptr) nullptr, w.x, L);
-        Q4_LAP(0);
+        lp.lap(prof, lapc::QP_SETUP);
         if (single) condense_single<MSEL, NSEL>(d, c, dyn, w.x, gh, L);
         else condense_half<MSEL, NSEL>(d, c, dyn, w.x, gh, L);
-#ifdef SRH_PROFILE
-        cond_mode = single ? 2 : 1; cond_clk = clock64() - tq_last;
-#endif
+        // (behind the constant: the product build must not see a second `single ? 2 : 1` in front of the one below)
+        if constexpr (lapc::ON) { qinfo.add(COND_MODE, single ? 2 : 1); qinfo.add(COND_CLK, lp.since()); }
         for (int k = tid; k < N; k += nt) L.goffg[k] = L.idxl[k];
         if (tid == 0) L.flag[2] = single ? 2 : 1;              // 2: the packed G is the expansion of L.gtoep (kept over the QPs that reuse it)
         __syncthreads();
@@ -2046,7 +1996,7 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
         for (int e = tid; e < ldG; e += nt) { L.y[e] = L.yfg[e]; L.dy[e] = 0.0; }
     }
     __syncthreads();
-    Q4_LAP(2);
+    lp.lap(prof, lapc::QP_CONDENSE);
     // ---- this thread's rows: the two box rows of input `tid`, and one state-row slot
     const bool isu = tid < nm;
     const bool isx = tid < N * GX;
@@ -2096,7 +2046,7 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
     }
     while (true) {
         tid = SRH_TID;
-        Q4_LAP(7);
+        lp.lap(prof, lapc::QP_STEPS);
         // ---------------- rows -> weights, gradient shifts, and their per-stage sums, all in place
         double musum = 0.0, rpm = 0.0;
         double Du[2] = {0.0, 0.0}, rhu[2] = {0.0, 0.0}, Dx = 0.0, rhx = 0.0;
@@ -2145,14 +2095,12 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
             rp = rpm;
         }
         __syncthreads();
-        Q4_LAP(1);
+        lp.lap(prof, lapc::QP_ROWS);
         // ---------------- converged already?  Then no system (converged_early; 16: the rows per pass of the front's two waves)
         if (mode == PRED) {
             double rde;                                        // (not rd: nothing of the early test stays live through the system)
             const int early = converged_early<MSEL, 16>(d, g, L, mu, rp, sd, sp, rde);
-#ifdef SRH_PROFILE
-            if (early != EARLY_NO_GATE) { Q4_LAP(33); if (early == EARLY_GO_ON) prof[34] += 1; }      // the early product's own lap; products paid for nothing
-#endif
+            if (early != EARLY_NO_GATE) { lp.lap(prof, lapc::EARLY_TEST); if (early == EARLY_GO_ON) prof.add(lapc::N_EARLY_FOR_NOTHING); }      // the early product's own lap; products paid for nothing
             if (early == EARLY_STOP) { status = 0; break; }
         }
         // ---------------- Newton system
@@ -2160,10 +2108,8 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
         bool ok = true;
         if (mode != CORR) {
             gram_t<MSEL, true>(d, c, gg, L, (cgptr)gh, toep ? (cgptr)L.gtoep : (cgptr) nullptr);
-            Q4_LAP(4);
-#ifdef SRH_PROFILE
-            ++ngram;
-#endif
+            lp.lap(prof, lapc::QP_GRAM);
+            qinfo.add(NGRAM);
             // the factorisation (waves 0-1: a chain of one-wave 16 x 16 factorisations) beside the half of the Newton solve that
             // does not need the factor (waves 2-3), see Waves.  Under a row roster (QPDims::lean_roster, roster_nwk) waves 2 and 3 are
             // workers 1 and 2 of the factorisation as well, in the rows behind (code > 0) or in front of (code < 0) their Newton front:
@@ -2174,15 +2120,11 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
             const int wv = __builtin_amdgcn_readfirstlane(tid >> 6) ^ sw;
             const int rc = __builtin_amdgcn_readfirstlane(d.lean_roster);
             auto W = half_waves(L.flag + 4, sw);
-#ifdef SRH_PROFILE
-            pf.last = clock64();
-            const long long tsplit = clock64();
-#endif
+            pf.restart();
+            split.restart();
             if (wv == 0) {
                 tile_cholesky_set(d, L, 0, tid & 63, 1, L.flag + 5, L.flag + 3, rc);
-#ifdef SRH_PROFILE
-                if ((tid & 63) == 0) L.Qu[2] = (double)(clock64() - tsplit);          // the chain, up to its last signal
-#endif
+                if constexpr (lapc::ON) { if ((tid & 63) == 0) L.Qu[lapc::MAIL_SPLIT_FACTOR] = (double)split.since(); }          // the chain, up to its last signal
             } else {
                 const bool has_front = wv >= 2, rows_first = wv == 1 || rc < 0, has_rows = wv == 1 || rc != 0;
 #pragma unroll 1
@@ -2190,39 +2132,28 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
                     if ((ph == 0) == rows_first) {
                         if (has_rows) tile_cholesky_set(d, L, wv, tid & 63, 1, L.flag + 5, L.flag + 3, rc);
                     } else if (has_front) {
-#ifdef SRH_PROFILE
-                        const long long tfront = clock64();
-                        pf.last = tfront;
-#endif
+                        front.restart();
+                        pf.restart(front);
                         newton_front<MSEL, true>(d, g, L, gyd, W, pf, ya_const && mode == PRED);
-#ifdef SRH_PROFILE
-                        if (W.tid == 0) L.Qu[3] = (double)(clock64() - tfront);       // the front alone, on its two waves
-#endif
+                        if constexpr (lapc::ON) { if (W.tid == 0) L.Qu[lapc::MAIL_SPLIT_FRONT] = (double)front.since(); }       // the front alone, on its two waves
                     }
                 }
             }
             __syncthreads();
-#ifdef SRH_PROFILE
-            prof[16] += (long long)L.Qu[2]; prof[17] += (long long)L.Qu[3];
-            for (int i = 0; i < 5; ++i) prof[27 + i] += (long long)L.Qu[8 + i];
-#endif
+            if constexpr (lapc::ON) split_mail_fold(L, prof);
             ok = L.flag[1] != 0;
             if (tid < 5) L.flag[3 + tid] = 0;
             if (gyd) rd = L.Qu[0];
-            Q4_LAP(5);
+            lp.lap(prof, lapc::QP_CHOLESKY);
             if (ok) unit_tiles(d, L);
-            Q4_LAP(32);                                        // (unit_tiles and its barrier alone; the factorisation up to the join is lap 5)
-#ifdef SRH_PROFILE
-            pf.last = clock64();
-#endif
+            lp.lap(prof, lapc::UNIT_TILES);                                        // (unit_tiles and its barrier alone; the factorisation up to the join is lap 5)
+            pf.restart();
             if (ok) newton_back<MSEL>(d, g, L, pf);
         } else {
-#ifdef SRH_PROFILE
-            pf.last = clock64();
-#endif
+            pf.restart();
             newton_solve<MSEL>(d, g, L, (clptr) nullptr, &rd, pf, ya_const);
         }
-        Q4_LAP(6);
+        lp.lap(prof, lapc::QP_NEWTON);
         // ---------------- use the direction
         if (mode == INIT) {
             if (ipm::stops(ipm::verdict_system(ok), status)) break;
@@ -2295,21 +2226,15 @@ __device__ __forceinline__ int ipm_box4(const QPDims &dfull, const QPConst &c, c
         if (xrow) w.lam[lsx] = lxr;
     }
     __syncthreads();
-#ifdef SRH_PROFILE
-    for (int i = 0; i < 8; ++i) prof[8 + i] += pf.t[8 + i];
-    prof[24] += it; prof[25] += 1; prof[26] += warm ? 1 : 0;
-    if (tid == 0 && blockIdx.x == 0) {
-        printf("lean condense (this QP): mode %d clocks %lld interior-point iterations %d status %d\n", cond_mode, cond_clk, it, status);
-        printf("lean gram laps (this QP, wave 0, %d fills): 1/D+staging+barrier %.0f descriptors %.0f products %.0f epilogue A %.0f barrier %.0f store+barrier %.0f\n",
-               ngram, L.Qu[4], L.Qu[5], L.Qu[6], L.Qu[7], L.Qu[13], L.Qu[14]);
-        printf("lean gram per wave (cumulative) products:");
-        for (int i = 0; i < 4; ++i) printf(" %lld", g_prof_waves[i]);
-        printf("  epilogue:");
-        for (int i = 0; i < 4; ++i) printf(" %lld", g_prof_waves[8 + i]);
-        printf("\n");
+    pf.fold(prof, it, warm);
+    if constexpr (lapc::ON) {
+        if (tid == 0 && blockIdx.x == 0) {
+            printf("lean condense (this QP): mode %d clocks %lld interior-point iterations %d status %d\n", (int)qinfo[COND_MODE], qinfo[COND_CLK], it, status);
+            printf("lean gram laps (this QP, wave 0, %d fills): 1/D+staging+barrier %.0f descriptors %.0f products %.0f epilogue A %.0f barrier %.0f store+barrier %.0f\n",
+                   (int)qinfo[NGRAM], L.Qu[lapc::MAIL_GRAM], L.Qu[lapc::MAIL_GRAM + 1], L.Qu[lapc::MAIL_GRAM + 2], L.Qu[lapc::MAIL_GRAM + 3], L.Qu[lapc::MAIL_GRAM_BARRIER], L.Qu[lapc::MAIL_GRAM_STORE]);
+            print_gram_wave_laps(4);
+        }
     }
-#endif
-#undef Q4_LAP
     if (iters_out) *iters_out = it;
     return status;
 }
@@ -2338,7 +2263,7 @@ __device__ __forceinline__ void wave_fence() {
 
 template <int MSEL, int NSEL, int GX>
 __device__ __forceinline__ int ipm_wave(const QPDims &dfull, const QPConst &c, const QPDyn &dyn, const QPData &q, gptr work_base,
-                                        Lds &L, int *iters_out, QPWork &wout, long long *prof, int warm_mode = 0) {
+                                        Lds &L, int *iters_out, QPWork &wout, lapc::Launch &prof, int warm_mode = 0) {
     static_assert(MSEL == 4 || MSEL == 8, "one-wave interior point: n_u = 4 or 8");
     const bool warm = warm_mode != 0, poison = warm_mode == 2;
     int tid = SRH_TID;                                       // re-read at the top of every interior-point iteration (dev_la.h: SRH_TID)
@@ -2351,13 +2276,7 @@ __device__ __forceinline__ int ipm_wave(const QPDims &dfull, const QPConst &c, c
     gptr gh = work_base + dfull.qc_off;
     constexpr int M = MSEL, SMAX = 2 * M;                      // k-steps of a product with G: N m / 4 <= 8 m / 4 (N <= 8)
     const int N = d.N, nm = N * M, ldG = 16, NP = 2 * N, nz = d.nz;
-#ifdef SRH_PROFILE
-    long long tq_last = clock64();
-    auto qlap = [&](int slot) { const long long now = clock64(); prof[slot] += now - tq_last; tq_last = now; };
-#define QW_LAP(x) qlap(x)
-#else
-#define QW_LAP(x) ((void)0)
-#endif
+    lapc::Clock lp;
     // ---- the preamble of ipm_box: starting point, condensation (all waves)
     if (warm) { for (int e = tid; e < nm; e += nt) L.u[e] = w.u[e]; }
     else { for (int e = tid; e < nm; e += nt) { w.u[e] = 0.0; L.u[e] = 0.0; } }
@@ -2368,13 +2287,13 @@ __device__ __forceinline__ int ipm_wave(const QPDims &dfull, const QPConst &c, c
     const bool reuse = same_regions(dyn, L, L.goff, N, tid, nt);
     if (!reuse) {
         rollout<MSEL, NSEL>(d, dyn, q.x0, (cgptr) nullptr, w.x, L);
-        QW_LAP(0);
+        lp.lap(prof, lapc::QP_SETUP);
         condense<MSEL, NSEL>(d, c, dyn, w.x, gh, L);
         for (int k = tid; k < N; k += nt) L.goff[k] = L.idxl[k];
         if (tid == 0) L.flag[2] = 1;
     }
     __syncthreads();
-    QW_LAP(2);
+    lp.lap(prof, lapc::QP_CONDENSE);
     int status = 1, it = 0;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     if (wave == 0) {
@@ -2698,10 +2617,8 @@ __device__ __forceinline__ int ipm_wave(const QPDims &dfull, const QPConst &c, c
     status = (int)L.red[0];
     it = (int)L.red[1];
     __syncthreads();
-    QW_LAP(6);
-#ifdef SRH_PROFILE
-    prof[24] += it; prof[25] += 1; prof[26] += warm ? 1 : 0;
-#endif
+    lp.lap(prof, lapc::QP_NEWTON);
+    prof.count_qp(it, warm);
     if (iters_out) *iters_out = it;
     return status;
 }
@@ -2766,7 +2683,7 @@ __host__ __device__ inline size_t objective_lds_doubles(const QPDims &d) { retur
 // means "hand this QP to the fused kernel" (status of the interior point, or 100 = minimiser outside the trust region).
 template <int MSEL, int NSEL, int GXSEL, int NST = 0, int J0SEL = 0>
 __device__ __forceinline__ int solve_qp(const QPDims &dfull, const QPConst &c, const QPDyn &dyn, const QPData &q, gptr work_base,
-                                        Lds &L, double *J_out, int *iters_out, QPWork &wout, long long *prof, int warm = 0) {
+                                        Lds &L, double *J_out, int *iters_out, QPWork &wout, lapc::Launch &prof, int warm = 0) {
     const int tid = SRH_TID, nt = blockDim.x;
     QPLds Lq{};
     Lq.v1 = L.v1; Lq.v2 = L.v2; Lq.Qu = L.Qu; Lq.part = L.part; Lq.red = L.red; Lq.idxl = L.idxl; Lq.flag = L.flag;
@@ -2783,9 +2700,7 @@ __device__ __forceinline__ int solve_qp(const QPDims &dfull, const QPConst &c, c
     else st = ipm<MSEL, NSEL>(dfull, c, dyn, q, work_base, L, Lq, &it, wout, prof);
     if (iters_out) *iters_out = it;
     if (st != 0) return st;
-#ifdef SRH_PROFILE
-    long long tail_last = clock64();
-#endif
+    lapc::Clock tail;
     QPDims d0 = dfull;
     d0.tr = 0;
     QPWork w = wout;
@@ -2797,9 +2712,7 @@ __device__ __forceinline__ int solve_qp(const QPDims &dfull, const QPConst &c, c
     lptr xs = L.B;                                        // (N + 1) n_x doubles at the start of the Theta^T area: free from here on
     rollout<MSEL, NSEL, true, HALFWG ? 4 : 8>(d0, dyn, q.x0, (cgptr)w.u, w.x, L, xs);
     __syncthreads();
-#ifdef SRH_PROFILE
-    { const long long now_ = clock64(); prof[22] += now_ - tail_last; tail_last = now_; }
-#endif
+    tail.lap(prof, lapc::TAIL_ROLLOUT);
     // (with x and H read from global memory the Diamond fixed layouts were better off with the one-thread-per-stage form -- 54.5 against
     // 55.0 ms per 4096 rollouts --; with the rollout's LDS copy of the trajectory every layout takes the form below)
     double J;
@@ -2819,9 +2732,7 @@ __device__ __forceinline__ int solve_qp(const QPDims &dfull, const QPConst &c, c
         inside = md <= q.delta;
         J += q.omega * s0;
     }
-#ifdef SRH_PROFILE
-    { const long long now_ = clock64(); prof[23] += now_ - tail_last; }
-#endif
+    tail.lap(prof, lapc::TAIL_OBJECTIVE);
     if (J_out) *J_out = J;
     return inside ? 0 : 100;
 }

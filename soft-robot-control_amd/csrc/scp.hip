@@ -120,11 +120,13 @@ static int slocp_plan_launch(slocp_plan *pl, const double *A, const double *B, c
             SRH_CHECK_HIP(hipStreamSynchronize(st));
             std::vector<double> t(8 * 64);
             pl->dbg.download(t.data(), sizeof(double) * 8 * 64);
+            using namespace lapc;
+            const double *qpl = t.data() + 8 * 60 - QP_SETUP, *ntl = t.data() + 8 * 59 - NT_GRADIENTS;     // debug rows 60 / 59: the QP laps and the Newton laps, by their slot
             fprintf(stderr, "[locp lean] j0 %d lds %zu; status %.0f iters %.0f inside %.0f\n", d.lean_j0, llds, t[8*61+1], t[8*61+2], t[8*61+3]);
             fprintf(stderr, "[locp lean] laps (SRH_PROFILE build): setup+rollout %.0f rows %.0f condense %.0f stage-factors %.0f gram %.0f cholesky %.0f grad+newton %.0f steps %.0f\n",
-                    t[8*60], t[8*60+1], t[8*60+2], t[8*60+3], t[8*60+4], t[8*60+5], t[8*60+6], t[8*60+7]);
+                    qpl[QP_SETUP], qpl[QP_ROWS], qpl[QP_CONDENSE], qpl[QP_STAGE_FACTORS], qpl[QP_GRAM], qpl[QP_CHOLESKY], qpl[QP_NEWTON], qpl[QP_STEPS]);
             fprintf(stderr, "[locp lean] newton laps: gradients %.0f gT_times(1) %.0f rhs+dinv %.0f g_times(1) %.0f k_solve %.0f gT_times(2) %.0f du %.0f g_times(2) %.0f\n",
-                    t[8*59], t[8*59+1], t[8*59+2], t[8*59+3], t[8*59+4], t[8*59+5], t[8*59+6], t[8*59+7]);
+                    ntl[NT_GRADIENTS], ntl[NT_GT1], ntl[NT_RHS], ntl[NT_G1], ntl[NT_KSOLVE], ntl[NT_GT2], ntl[NT_DU], ntl[NT_G2]);
             for (int i = 0; i < 59 && (t[8 * i + 3] != 0.0); ++i)
                 fprintf(stderr, "[locp lean] it %2d mu %.3e rd %.3e rp %.3e (sd %.2e sp %.2e) a_aff %.3e sigma %.3e a %.3e\n", i, t[8 * i], t[8 * i + 1], t[8 * i + 2], t[8 * i + 3], t[8 * i + 4], t[8 * i + 5], t[8 * i + 6], t[8 * i + 7]);
             (void)hipMemset(pl->dbg.p, 0, sizeof(double) * 8 * 64);
@@ -142,11 +144,13 @@ static int slocp_plan_launch(slocp_plan *pl, const double *A, const double *B, c
         SRH_CHECK_HIP(hipStreamSynchronize(st));
         std::vector<double> t(8 * 64);
         pl->dbg.download(t.data(), sizeof(double) * 8 * 64);
+        using namespace lapc;
+        const double *qpl = t.data() + 8 * 60 - QP_SETUP, *ntl = t.data() + 8 * 59 - NT_GRADIENTS;     // debug rows 60 / 59: the QP laps and the Newton laps, by their slot
         fprintf(stderr, "[locp] cond %d diagD %d po %d KT %d lds %zu; condensed path ran %.0f status %.0f iters %.0f inside %.0f\n", d.cond, d.diagD, d.po, d.KT, lds, t[8*61], t[8*61+1], t[8*61+2], t[8*61+3]);
         fprintf(stderr, "[locp] condensed laps (SRH_PROFILE build): setup+rollout %.0f rows %.0f condense %.0f stage-factors %.0f gram %.0f cholesky %.0f grad+newton %.0f steps %.0f\n",
-                t[8*60], t[8*60+1], t[8*60+2], t[8*60+3], t[8*60+4], t[8*60+5], t[8*60+6], t[8*60+7]);
+                qpl[QP_SETUP], qpl[QP_ROWS], qpl[QP_CONDENSE], qpl[QP_STAGE_FACTORS], qpl[QP_GRAM], qpl[QP_CHOLESKY], qpl[QP_NEWTON], qpl[QP_STEPS]);
         fprintf(stderr, "[locp] newton laps: gradients %.0f gT_times(1) %.0f rhs+dinv %.0f g_times(1) %.0f k_solve %.0f gT_times(2) %.0f du %.0f g_times(2) %.0f\n",
-                t[8*59], t[8*59+1], t[8*59+2], t[8*59+3], t[8*59+4], t[8*59+5], t[8*59+6], t[8*59+7]);
+                ntl[NT_GRADIENTS], ntl[NT_GT1], ntl[NT_RHS], ntl[NT_G1], ntl[NT_KSOLVE], ntl[NT_GT2], ntl[NT_DU], ntl[NT_G2]);
         fprintf(stderr, "[locp] time (shader clocks): init %.0f rows %.0f prepass %.0f ricc_full %.0f ricc_vec %.0f final %.0f\n", t[8*62], t[8*62+1], t[8*62+2], t[8*62+3], t[8*62+4], t[8*62+5]);
         fprintf(stderr, "[locp] riccati laps (SRH_PROFILE build): load %.0f W %.0f BtW %.0f Qu %.0f gain %.0f AtW+finish %.0f vec-backward %.0f forward %.0f\n",
                 t[8*63], t[8*63+1], t[8*63+2], t[8*63+3], t[8*63+4], t[8*63+5], t[8*63+6], t[8*63+7]);
