@@ -770,16 +770,84 @@ __device__ __forceinline__ void gT_times(const QPDims &d, const GP &g, Lds &L, c
             if (g8 == 0 && r < re) { out1[r] = a1; if (two) out2[r] = a2; }
         }
     };
+    // Rows [0, re) of a single-region G from its Toeplitz generators, half-size layout (the only one that keeps generators: g.gto is
+    // set by ipm_box4 alone; J0F == NF > 0, every row L2-resident): entry q of row (j, b) at lane g8 is
+    // g_b[g8 + 8 q] whatever j, and b = (tid >> 3) % M in every pass (M divides the 8 rows of a wave, so every set's rows per pass), so a
+    // thread's entries -- at most QMAX = ceil(NP / 8) -- are loaded ONCE per product into a register array that is indexed at compile time
+    // only, and the passes run from registers and LDS alone: no address arithmetic and no vector-memory load per trip (DESIGN section 45:
+    // the products are bound by the instructions they issue).  A lane past the last row keeps its own b: its sums are never stored.  The
+    // FMAs are those of `rows`, term by term: blocks of four alternate the two chains while q + 4 <= nq, the remainder trips feed the
+    // first chain; nq is wave-uniform, every guard on it is a scalar branch.
+    auto rows_toeplitz = [&](int re, auto TWO) {
+        constexpr bool two = decltype(TWO)::value;
+        // NPF = g.NP: a fixed-horizon instantiation only runs problems with d.N == GP::NF (lean.hip: lean_matches), as g_times_fixed assumes
+        constexpr int NPF = 2 * (GP::NF > 0 ? GP::NF : 1), QMAX = (NPF + 7) / 8, KB = (QMAX + 3) / 4;
+        double gv[QMAX];
+        auto trips = [&](int r0, int r) {                          // of the longest row of the pass (of the pass of GRP rows)
+            int nq = (NPF - 2 * (r0 / M) + 7) >> 3;
+            if constexpr (GRP > 0) nq = (NPF - 2 * (r / GRP * GRP / M) + 7) >> 3;
+            return __builtin_amdgcn_readfirstlane(nq);
+        };
+        {   // the first pass has the wave's longest rows: entries 0 .. nq - 1, rounded up to whole blocks of four (what the last block
+            // holds behind them repeats entry nq - 1: nothing is read that `rows` does not read)
+            const int at = ((tid >> 3) % M) * NPF + g8, nq = trips(0, tid >> 3);
+            srh_static_for<0, KB>([&](auto K_) {
+                constexpr int q0 = 4 * decltype(K_)::value;
+                if (q0 < nq) srh_static_for<q0, (q0 + 4 < QMAX ? q0 + 4 : QMAX)>([&](auto Q_) {
+                    constexpr int q = decltype(Q_)::value;
+                    gv[q] = g.gto[at + 8 * min(q, nq - 1)];
+                });
+            });
+        }
+        for (int r0 = 0; r0 < re; r0 += rpp) {
+            const int r = r0 + (tid >> 3), rc = r < re ? r : re - 1;
+            const int j = rc / M, nq = trips(r0, r);
+            clptr p1 = y1 + 2 * j + g8, p2 = (two ? y2 : y1) + 2 * j + g8;
+            double a1 = 0.0, a2 = 0.0, c1 = 0.0, c2 = 0.0;
+            srh_static_for<0, KB>([&](auto K_) {
+                constexpr int q0 = 4 * decltype(K_)::value;
+                if (q0 + 4 <= nq) {
+                    if constexpr (q0 + 4 <= QMAX) {
+                        double ya[4], yb[4];
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) { ya[t] = p1[8 * (q0 + t)]; if (two) yb[t] = p2[8 * (q0 + t)]; }
+                        a1 = fma(gv[q0], ya[0], a1); c1 = fma(gv[q0 + 1], ya[1], c1); a1 = fma(gv[q0 + 2], ya[2], a1); c1 = fma(gv[q0 + 3], ya[3], c1);
+                        if (two) { a2 = fma(gv[q0], yb[0], a2); c2 = fma(gv[q0 + 1], yb[1], c2); a2 = fma(gv[q0 + 2], yb[2], a2); c2 = fma(gv[q0 + 3], yb[3], c2); }
+                    }
+                } else {
+                    srh_static_for<q0, (q0 + 3 < QMAX ? q0 + 3 : QMAX)>([&](auto Q_) {
+                        constexpr int q = decltype(Q_)::value;
+                        if (q < nq) {
+                            a1 = fma(gv[q], p1[8 * q], a1);
+                            if (two) a2 = fma(gv[q], p2[8 * q], a2);
+                        }
+                    });
+                }
+            });
+            a1 += c1; a2 += c2;
+            a1 = wg::group_sum<8>(a1);
+            if (two) a2 = wg::group_sum<8>(a2);
+            if (g8 == 0 && r < re) { out1[r] = a1; if (two) out2[r] = a2; }
+        }
+        // every entry named as read (an empty statement; the loads have long landed): the compiler guards a register that a later
+        // request overwrites with a wait for loads into it that it cannot see retired -- the entries no row of this wave used
+        srh_static_for<0, QMAX>([&](auto Q_) { const double e = gv[decltype(Q_)::value]; asm volatile("" :: "v"(e)); });
+    };
     const int rh = min(nm, g.j0 * M);
     const bool toep = g.gto != nullptr;                             // (uniform) the L2-resident rows read from their generators
     cgptr head = toep ? g.gto : g.gh;
-    if (y2) {
-        if (rh > 0) rows(head, 0, rh, std::true_type{}, toep);
-        if (nm > rh) rows(g.gt - goff0, rh, nm, std::true_type{});
-    } else {
-        if (rh > 0) rows(head, 0, rh, std::false_type{}, toep);
-        if (nm > rh) rows(g.gt - goff0, rh, nm, std::false_type{});
-    }
+    auto product = [&](auto TWO) {
+        if (rh > 0) {
+            if constexpr (GP::NF > 0 && GP::J0F == GP::NF) {         // the half-size layout
+                static_assert(8 % M == 0, "rows_toeplitz: M must divide the 8 rows of a wave (b = (tid >> 3) % M in every pass)");
+                if (toep) rows_toeplitz(rh, TWO);
+                else rows(head, 0, rh, TWO, false);
+            } else rows(head, 0, rh, TWO, toep);
+        }
+        if (nm > rh) rows(g.gt - goff0, rh, nm, TWO);
+    };
+    if (y2) product(std::true_type{});
+    else product(std::false_type{});
     W.sync();
 }
 template <int MSEL, class GP>
