@@ -14,7 +14,7 @@ namespace {
 
 constexpr int KP_MAX_NZ = 64;            // zeta dimension
 constexpr int KP_MAX_DEG = 4;            // observable degree
-constexpr int KP_MAX_PSI = 1024;         // observables (16 rows x 1025 doubles of LDS at the largest)
+constexpr int KP_MAX_PSI = 1024;         // observables (the largest tile: nz 43, degree 2 -- 16 rows x (992 + 43) doubles, 133 120 B of LDS)
 constexpr size_t KP_LDS_TARGET = 64 * 1024;
 typedef double kp_d4 __attribute__((ext_vector_type(4)));
 
