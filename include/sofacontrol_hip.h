@@ -982,6 +982,51 @@ int sssm_fit_sums(sssm_fit_t *f, double *G, double *Rd, double *Rc, double *Rw, 
  * solution holds a non-finite entry that no pivot caught.  SRH_EINVAL when no sample has been added. */
 int sssm_fit_solve(sssm_fit_t *f, double ridge, double *rd_coeff, double *Bd, double *r_coeff, double *B, double *w_coeff, int32_t *info);
 
+/* TPWL model identification (csrc/tpwl_fit.hip): records (x, u) of the reduced state and P linearisation points -> the tables A_c, B_c,
+ * d_c, u of a TPWL model (stpwl_create).
+ * THE FIT ("TPWL model identification", defines it; the reference builds its tables from the simulator's Jacobians):
+ *   records   E episodes, each x (T x n_x), x = [v; q], n_x = 2 r, and u (T x m); row i holds the input applied after x_i; `stride`
+ *             s >= 1 keeps rows 0, s, 2s, .. of every episode; T' = the rows kept.
+ *   samples   the kept rows i <= T' - 2 of every episode (those with a kept successor), never across an episode; T' < 2 gives none.
+ *   points    q, v (P x r) and the weights (w_q, w_v); x_p = [v_p; q_p].  p(i) = the nearest point to x_i by the point-search rule of
+ *             stpwl_nearest (first minimum of w_q |q_p - q| + w_v |v_p - v|).
+ *   regressor phi_i = [x_i - x_p; u_i; 1], n = n_x + m + 1; target g_i = (x_{i+1} - x_i) / Ts (the forward difference over kept rows:
+ *             the fitted model is the one whose forward-Euler discretisation at Ts reproduces the one-step map).
+ *   sums      per point over its samples: G_p = sum phi phi^T (n x n), R_p = sum g phi^T (n_x x n), Q_p = sum |g|^2, S_p = the samples.
+ *   solve     per point, equilibrated by D = diag(G_p): (D^-1/2 G_p D^-1/2 + ridge I) z = D^-1/2 r, [A_c | B_c | c] = the rows D^-1/2 z,
+ *             ridge >= 0 (relative to the unit diagonal); d_c = c - A_c x_p, so that xdot = A_c x + B_c u + d_c; u = the mean input of
+ *             the point's samples.
+ *   status    per point: 0 solved; 1 S_p < min_samples (a duplicated point: the first-minimum rule gives the later one no samples);
+ *             2 a pivot that is not positive, not finite or not above n eps (1 + ridge), `column` = its column of phi (0 .. n_x - 1 a
+ *             state, n_x .. n_x + m - 1 an input, n - 1 the constant), or n when the solution holds a non-finite entry that no pivot
+ *             caught.  The tables of a point that did not solve are zeros.
+ * Not offered: weighting-mode fits, sample weights, a choice of points, full-order records (project them first).
+ * Limits (SRH_EINVAL before any device call): n <= 128, m <= 16 (stpwl_create's), P <= 1024, fewer than 2^31 kept rows per add call.
+ * A kept row that is not finite (x or u) is refused by stpwl_fit_add / _add_dev with the episode and row of the first one; the sums
+ * are untouched then.  The sums are accumulated on f64 MFMA without floating-point atomics: the kept rows are ordered by region with a
+ * stable counting sort, a workgroup sums a granule (eight 64-entry chunks of one region's list), and the granules join the running
+ * sums of their point in order.  The same sequence of add calls gives the same bits, and device records give the bits of host arrays;
+ * two add calls do not give the bits of one (their ordered lists differ).  All calls on one handle are ordered by the caller.
+ * stpwl_fit_plan answers on the host (no GPU): n, the entries of a chunk, the tiles a wave keeps in registers and the accumulate
+ * kernel's dynamic LDS; any output may be NULL. */
+typedef struct stpwl_fit stpwl_fit_t;
+int stpwl_fit_plan(int P, int r, int m, int *n, int *rows_per_chunk, int *tiles_per_wave, int64_t *lds_bytes);
+/* q, v (P x r) */
+int stpwl_fit_create(stpwl_fit_t **out, int P, int r, int m, const double *q, const double *v, double w_q, double w_v, double Ts);
+int stpwl_fit_destroy(stpwl_fit_t *f);
+int stpwl_fit_reset(stpwl_fit_t *f);                        /* sums and counts back to zero */
+/* x (E x T x n_x), u (E x T x m) are added to the handle's sums; may be called many times.  The _dev form reads device records on
+ * `stream` and synchronises it before it returns. */
+int stpwl_fit_add(stpwl_fit_t *f, const double *x, const double *u, int64_t E, int64_t T, int stride);
+int stpwl_fit_add_dev(stpwl_fit_t *f, const double *x_dev, const double *u_dev, int64_t E, int64_t T, int stride, void *stream);
+int stpwl_fit_counts(stpwl_fit_t *f, int64_t *counts);      /* (P) the samples of every point */
+/* one point's G (n x n), R (n_x x n), Q (1), samples (1); any may be NULL */
+int stpwl_fit_sums(stpwl_fit_t *f, int p, double *G, double *R, double *Q, int64_t *samples);
+/* A_c (P x n_x x n_x), B_c (P x n_x x m), d_c (P x n_x), u (P x m), status (P), column (P).  min_samples < 0: the default n + 1.
+ * SRH_EINVAL when no sample has been added; a point that does not solve is reported in status, not by the return code. */
+int stpwl_fit_solve(stpwl_fit_t *f, double ridge, int64_t min_samples, double *A_c, double *B_c, double *d_c, double *u, int32_t *status,
+                    int32_t *column);
+
 /* =====================================================================================================
  * ROMPC baseline. reference: sofacontrol/baselines/rompc/rompc.py:57-89, rompc/observer.py:30-46, rompc_utils.py:52-53
  * `batch` independent loops on one linear reduced model (problem-major arrays everywhere).  One control step is

@@ -1,0 +1,329 @@
+"""TPWL model identification on the device: records (x, u) of the reduced state and P linearisation points -> a TPWLATV that the
+planners, observers and closed loops accept unchanged (csrc/tpwl_fit.hip; C ABI: stpwl_fit_* in include/sofacontrol_hip.h).
+
+THE FIT.  The reference builds its tables from the simulator's Jacobians (tpwl_utils.TPWLSnapshotData.add_point); this text defines
+the fit from records.
+  Records: E episodes, each X (T x n_x) of reduced states x = [v; q], n_x = 2 r, and U (T x m).  Row i holds the input applied after
+  x_i.  `stride` s >= 1 keeps rows 0, s, 2s, .. of every episode: a record at dt_sim becomes one at Ts = s dt_sim.  T' = rows kept.
+  Samples: the kept rows i <= T' - 2, those with a kept successor in the same episode; an episode with one kept row contributes
+  nothing; no sample pairs across episodes.
+  Points: P points (q_p, v_p) and dist_weights = {q, v}; x_p = [v_p; q_p].
+  Assignment: p(i) = the nearest point to x_i by the point-search rule every TPWL kernel uses (calc_nearest_point: the first
+  minimum of w_q |q_p - q| + w_v |v_p - v|).
+  Regressor phi_i = [x_i - x_p; u_i; 1], n = n_x + m + 1.  Target g_i = (x_{i+1} - x_i) / Ts over kept rows: the forward difference, so
+  the fitted model is the one whose 'fe' discretisation at Ts reproduces the one-step map.
+  Sums per point over its samples: G_p = sum phi phi^T, R_p = sum g phi^T, Q_p = sum |g|^2, S_p = the samples.
+  Solve per point: [A_c | B_c | c] = R_p (G_p + ridge diag)^-1 after equilibration: with D = diag(G_p),
+  (D^-1/2 G_p D^-1/2 + ridge I) z = D^-1/2 r, coefficients = D^-1/2 z; the scaled block's diagonal is 1 + ridge exactly; a pivot must
+  exceed n eps (1 + ridge).  d_c[p] = c - A_c[p] x_p, so that xdot = A_c[p] x + B_c[p] u + d_c[p]; u[p] = the mean input of the point's
+  samples.
+  Status per point: 0 solved; 1 S_p < min_samples (default n + 1; a duplicated point falls here: the first-minimum rule gives the later
+  duplicate no samples); 2 a failing pivot, with its column named ('state x7', 'input u2', 'constant').
+  A kept row that is not finite is refused at `add` with its episode and row; the sums stay untouched.
+  Bits: the same sequence of `add` calls gives the same bits, and device-resident records give the bits of host arrays.  Two `add`
+  calls do NOT give the bits of one: the samples are ordered by region per call, so the chains of additions differ (both meet the
+  same error bound).
+  Limits: n = n_x + m + 1 <= 128 (the accumulate kernel then keeps 36 + 64 tiles, 25 per wave, in registers), m <= 16, P <= 1024.
+
+NOT OFFERED: weighting-mode fits; sample weights; selection of points by the reference's distance heuristics
+(points_from_records runs k-means on the kept states instead); full-order records (project them first: POD.compute_RO_state)."""
+import ctypes as C
+
+import numpy as np
+
+from .. import _lib
+from .. import utils as scutils
+from .tpwl import TPWLATV
+
+_BOUND = False
+MAX_N = 128
+
+
+def _bind():
+    global _BOUND
+    L = _lib.lib()
+    if _BOUND:
+        return L
+    vp, dp, i64, ip, i32p = C.c_void_p, _lib.c_double_p, C.c_int64, C.POINTER(C.c_int), _lib.c_int32_p
+    L.stpwl_fit_plan.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, ip, C.POINTER(i64)]
+    L.stpwl_fit_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, dp, dp, C.c_double, C.c_double, C.c_double]
+    L.stpwl_fit_destroy.argtypes = [vp]
+    L.stpwl_fit_reset.argtypes = [vp]
+    L.stpwl_fit_add.argtypes = [vp, dp, dp, i64, i64, C.c_int]
+    L.stpwl_fit_add_dev.argtypes = [vp, vp, vp, i64, i64, C.c_int, vp]
+    L.stpwl_fit_counts.argtypes = [vp, C.POINTER(i64)]
+    L.stpwl_fit_sums.argtypes = [vp, C.c_int, dp, dp, dp, C.POINTER(i64)]
+    L.stpwl_fit_solve.argtypes = [vp, C.c_double, i64, dp, dp, dp, dp, i32p, i32p]
+    _BOUND = True
+    return L
+
+
+def fit_plan(P, r, m):
+    """stpwl_fit_plan, on the host (no GPU): {'n', 'rows_per_chunk', 'tiles_per_wave', 'lds_bytes'}; raises when the shape is refused."""
+    a, b, c, d = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int64(0)
+    _lib.check(_bind().stpwl_fit_plan(int(P), int(r), int(m), C.byref(a), C.byref(b), C.byref(c), C.byref(d)), 'stpwl_fit_plan')
+    return {'n': a.value, 'rows_per_chunk': b.value, 'tiles_per_wave': c.value, 'lds_bytes': int(d.value)}
+
+
+def column_name(c, n_x, m):
+    """'state x7', 'input u2' or 'constant': column c of phi (1-based within its group)."""
+    if c < 0:
+        return 'none'
+    if c < n_x:
+        return 'state x%d' % (c + 1)
+    if c < n_x + m:
+        return 'input u%d' % (c - n_x + 1)
+    if c == n_x + m:
+        return 'constant'
+    return 'a non-finite solution'
+
+
+def _records(X, U, n_x, m, shape, who):
+    """(X, U, E, T, on_device) of records given as arrays ((E, T, n_x) / (T, n_x)) or DeviceBuffers with shape = (E, T)."""
+    dev = isinstance(X, _lib.DeviceBuffer)
+    if dev != isinstance(U, _lib.DeviceBuffer):
+        raise RuntimeError('%s: X and U must both be arrays or both be DeviceBuffers' % who)
+    if dev:
+        if shape is None or len(tuple(shape)) != 2:
+            raise RuntimeError('%s: DeviceBuffer records need shape = (E, T)' % who)
+        E, T = int(shape[0]), int(shape[1])
+        if E < 1 or T < 1 or X.nbytes < 8 * E * T * n_x or U.nbytes < 8 * E * T * m:
+            raise RuntimeError('%s: the DeviceBuffers are smaller than (E, T, n_x) = (%d, %d, %d) and (E, T, m) = (%d, %d, %d) doubles'
+                               % (who, E, T, n_x, E, T, m))
+        return X, U, E, T, True
+    X, U = np.asarray(X, dtype=np.float64), np.asarray(U, dtype=np.float64)
+    if X.ndim == 2:
+        X = X[None]
+    if U.ndim == 2:
+        U = U[None]
+    if X.ndim != 3 or X.shape[2] != n_x or X.shape[0] < 1 or X.shape[1] < 1:
+        raise RuntimeError('%s: X must have shape (E, T, n_x) or (T, n_x) with n_x = %d, got %r' % (who, n_x, tuple(np.shape(X))))
+    if U.shape != (X.shape[0], X.shape[1], m):
+        raise RuntimeError('%s: U (E, T, m) must have shape %r, got %r' % (who, (X.shape[0], X.shape[1], m), tuple(U.shape)))
+    return _lib.f64(X), _lib.f64(U), X.shape[0], X.shape[1], False
+
+
+def _check_stride(stride, who):
+    if int(stride) != stride or stride < 1:
+        raise RuntimeError('%s: stride = %r, need an integer stride >= 1' % (who, stride))
+
+
+class TPWLFitResult:
+    """samples (the total), counts (P), status (P), column (P: the failing column of a status-2 point, else -1), ridge, and per point
+    residual_rms = sqrt((Q - 2 tr(X R^T) + tr(X G X^T)) / (S n_x)), X = [A_c | B_c | c], from the sums (NaN of a point that did not
+    solve).  The three terms cancel: of an exact fit about sqrt(eps) of the target's rms survives, and a figure clipped to 0 says no
+    more than that.  residual_floor = sqrt(eps Q / (S n_x)) per point is that resolution: read a figure below its floor as "at most the
+    floor" (one_step_error measures the one-step map's residual directly).  `kept` = the points of the model, as indices of the fit's."""
+
+    def __init__(self, samples, counts, status, column, ridge, residual_rms, residual_floor, kept=None):
+        self.samples, self.counts, self.status, self.column, self.ridge = samples, counts, status, column, ridge
+        self.residual_rms, self.residual_floor, self.kept = residual_rms, residual_floor, kept
+
+    def __repr__(self):
+        ok = self.status == 0
+        worst = float(np.nanmax(self.residual_rms[ok])) if np.any(ok) else float('nan')
+        return 'TPWLFitResult(samples=%d, points=%d, solved=%d, ridge=%g, worst residual_rms=%g)' % (
+            self.samples, len(self.counts), int(ok.sum()), self.ridge, worst)
+
+
+class TPWLSysID:
+    """Accumulates the per-point sums of the fit over any number of `add` calls and solves every point in one launch (the module's
+    docstring states the fit).  q, v: (P, r); dist_weights = {'q': .., 'v': ..}."""
+
+    def __init__(self, q, v, dist_weights, m, Ts):
+        q, v = np.atleast_2d(np.asarray(q, dtype=np.float64)), np.atleast_2d(np.asarray(v, dtype=np.float64))
+        if q.ndim != 2 or q.shape != v.shape or q.shape[0] < 1 or q.shape[1] < 1:
+            raise RuntimeError('TPWLSysID: q and v must both have shape (P, r), got %r and %r' % (tuple(q.shape), tuple(v.shape)))
+        if not (np.all(np.isfinite(q)) and np.all(np.isfinite(v))):
+            raise RuntimeError('TPWLSysID: the points hold a non-finite entry')
+        try:
+            self.dist_weights = {'q': float(dist_weights['q']), 'v': float(dist_weights['v'])}
+        except (TypeError, KeyError):
+            raise RuntimeError("TPWLSysID: dist_weights must be {'q': .., 'v': ..}")
+        self.q, self.v = np.ascontiguousarray(q), np.ascontiguousarray(v)
+        self.P, self.r, self.n_x, self.m, self.Ts = q.shape[0], q.shape[1], 2 * q.shape[1], int(m), float(Ts)
+        if not self.Ts > 0 or not np.isfinite(self.Ts):
+            raise RuntimeError('TPWLSysID: need a finite Ts > 0, got %r' % (Ts,))
+        plan = fit_plan(self.P, self.r, self.m)                 # refuses n > 128 and the other limits, on the host
+        self.n, self.rows_per_chunk = plan['n'], plan['rows_per_chunk']
+        self.x_points = scutils.qv2x(self.q, self.v)
+        self._h, self._samples = C.c_void_p(), 0
+
+    @property
+    def samples(self):
+        return self._samples
+
+    def _ensure(self):
+        if not self._h:
+            _lib.check(_bind().stpwl_fit_create(C.byref(self._h), self.P, self.r, self.m, _lib.dptr(self.q), _lib.dptr(self.v),
+                                                self.dist_weights['q'], self.dist_weights['v'], self.Ts), 'stpwl_fit_create')
+
+    def add(self, X, U, stride=1, shape=None, stream=None):
+        """Adds records to the sums: X (E, T, n_x) or (T, n_x) and U alike, numpy arrays or _lib.DeviceBuffers with shape = (E, T)
+        (device records are read in place on `stream`, which is synchronised).  Returns the samples added."""
+        _check_stride(stride, 'TPWLSysID.add')
+        X, U, E, T, dev = _records(X, U, self.n_x, self.m, shape, 'TPWLSysID.add')
+        self._ensure()
+        L = _bind()
+        if dev:
+            _lib.check(L.stpwl_fit_add_dev(self._h, X.ptr, U.ptr, E, T, int(stride), stream), 'stpwl_fit_add_dev')
+        else:
+            _lib.check(L.stpwl_fit_add(self._h, _lib.dptr(X), _lib.dptr(U), E, T, int(stride)), 'stpwl_fit_add')
+        added = E * ((T - 1) // int(stride))
+        self._samples += added
+        return added
+
+    def counts(self):
+        """(P,) the samples of every point."""
+        out = np.zeros(self.P, dtype=np.int64)
+        if self._h:
+            _lib.check(_bind().stpwl_fit_counts(self._h, out.ctypes.data_as(C.POINTER(C.c_int64))), 'stpwl_fit_counts')
+        return out
+
+    def sums(self, p):
+        """{'G' (n x n), 'R' (n_x x n), 'Q', 'samples'} of point p as accumulated so far (synchronises the device)."""
+        p = int(p)
+        if not 0 <= p < self.P:
+            raise RuntimeError('TPWLSysID.sums: point %d is outside 0 .. %d' % (p, self.P - 1))
+        G, R, Q, S = np.zeros((self.n, self.n)), np.zeros((self.n_x, self.n)), C.c_double(0.0), C.c_int64(0)
+        if self._h:
+            _lib.check(_bind().stpwl_fit_sums(self._h, p, _lib.dptr(G), _lib.dptr(R), C.cast(C.byref(Q), _lib.c_double_p), C.byref(S)),
+                       'stpwl_fit_sums')
+        return {'G': G, 'R': R, 'Q': Q.value, 'samples': S.value}
+
+    def solve_tables(self, ridge=0.0, min_samples=None):
+        """{'A_c' (P, n_x, n_x), 'B_c' (P, n_x, m), 'd_c' (P, n_x), 'u' (P, m), 'status' (P), 'column' (P)} by the device's solve; a point
+        that does not solve is reported in status (its tables are zeros)."""
+        if not (ridge >= 0.0 and np.isfinite(ridge)):
+            raise RuntimeError('TPWLSysID.solve: need a finite ridge >= 0, got %r' % (ridge,))
+        if min_samples is not None and (int(min_samples) != min_samples or min_samples < 1):
+            raise RuntimeError('TPWLSysID.solve: min_samples = %r, need an integer >= 1 (default n + 1 = %d)' % (min_samples, self.n + 1))
+        if self._samples == 0:
+            raise RuntimeError('TPWLSysID.solve: no samples have been added (S = 0)')
+        P, nx, m = self.P, self.n_x, self.m
+        out = dict(A_c=np.zeros((P, nx, nx)), B_c=np.zeros((P, nx, m)), d_c=np.zeros((P, nx)), u=np.zeros((P, m)),
+                   status=np.zeros(P, dtype=np.int32), column=np.zeros(P, dtype=np.int32))
+        _lib.check(_bind().stpwl_fit_solve(self._h, float(ridge), -1 if min_samples is None else int(min_samples),
+                                           *[_lib.dptr(out[k]) for k in ('A_c', 'B_c', 'd_c', 'u')], _lib.iptr(out['status']),
+                                           _lib.iptr(out['column'])), 'stpwl_fit_solve')
+        return out
+
+    def result(self, tables, ridge=0.0, kept=None):
+        """TPWLFitResult of solved tables: the residuals per point from the sums."""
+        P, nx = self.P, self.n_x
+        counts = self.counts()
+        rms, floor = np.full(P, np.nan), np.full(P, np.nan)
+        eps = np.finfo(np.float64).eps
+        for p in np.flatnonzero(tables['status'] == 0):
+            s = self.sums(p)
+            c = tables['d_c'][p] + tables['A_c'][p] @ self.x_points[p]
+            Xc = np.hstack([tables['A_c'][p], tables['B_c'][p], c[:, None]])
+            r2 = s['Q'] - 2.0 * np.sum(Xc * s['R']) + np.sum((Xc @ s['G']) * Xc)
+            rms[p] = np.sqrt(max(r2, 0.0) / (max(1, s['samples']) * nx))
+            floor[p] = np.sqrt(eps * s['Q'] / (max(1, s['samples']) * nx))
+        return TPWLFitResult(int(counts.sum()), counts, tables['status'].copy(), tables['column'].copy(), float(ridge), rms, floor, kept)
+
+    def describe_failures(self, tables):
+        """One line per point that did not solve."""
+        counts, lines = self.counts(), []
+        for p in np.flatnonzero(tables['status'] != 0):
+            if tables['status'][p] == 1:
+                lines.append('point %d: %d samples, fewer than min_samples' % (p, counts[p]))
+            else:
+                lines.append('point %d: failing pivot at %s (column %d of phi): increase ridge' % (
+                    p, column_name(int(tables['column'][p]), self.n_x, self.m), tables['column'][p]))
+        return lines
+
+    def model(self, tables, rom_info, on_fail='raise', Cf=None, Hf=None):
+        """(TPWLATV, kept) of solved tables; see solve."""
+        if on_fail not in ('raise', 'drop'):
+            raise RuntimeError("TPWLSysID.solve: on_fail = %r, need 'raise' or 'drop'" % (on_fail,))
+        bad = self.describe_failures(tables)
+        if bad and on_fail == 'raise':
+            raise RuntimeError('TPWLSysID.solve: %d of %d points did not solve (on_fail=\'drop\' leaves them out): %s'
+                               % (len(bad), self.P, '; '.join(bad)))
+        kept = np.flatnonzero(tables['status'] == 0)
+        if kept.size == 0:
+            raise RuntimeError('TPWLSysID.solve: no point solved: %s' % '; '.join(bad))
+        data = dict(q=self.q[kept].copy(), v=self.v[kept].copy(), u=tables['u'][kept].copy(), A_c=tables['A_c'][kept].copy(),
+                    B_c=tables['B_c'][kept].copy(), d_c=tables['d_c'][kept].copy(), rom_info=rom_info)
+        mdl = TPWLATV(data=data, params=dict(tpwl_method='nn', dist_weights=dict(self.dist_weights)), Cf=Cf, Hf=Hf, discr_method='fe')
+        mdl.fit_Ts = self.Ts
+        return mdl, kept
+
+    def solve(self, rom_info, ridge=0.0, min_samples=None, on_fail='raise', Cf=None, Hf=None):
+        """The fitted TPWLATV (discr_method='fe', tpwl_method='nn', the fit's dist_weights).  on_fail='raise' names the points that did
+        not solve; 'drop' leaves them out of the model (`last_result.kept` lists the points that stayed)."""
+        if on_fail not in ('raise', 'drop'):
+            raise RuntimeError("TPWLSysID.solve: on_fail = %r, need 'raise' or 'drop'" % (on_fail,))
+        tables = self.solve_tables(ridge, min_samples)
+        mdl, kept = self.model(tables, rom_info, on_fail, Cf, Hf)
+        self.last_result = self.result(tables, ridge, kept)
+        return mdl
+
+    def reset(self):
+        """Sums and counts back to zero; the points stay."""
+        if self._h:
+            _lib.check(_bind().stpwl_fit_reset(self._h), 'stpwl_fit_reset')
+        self._samples = 0
+
+    def __del__(self):
+        try:
+            if getattr(self, '_h', None):
+                _lib.lib().stpwl_fit_destroy(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass
+
+
+def fit_tpwl(X, U, q, v, dist_weights, Ts, rom_info, stride=1, ridge=0.0, min_samples=None, on_fail='raise', shape=None, m=None, Cf=None,
+             Hf=None):
+    """The one-call form: records and points -> (TPWLATV, TPWLFitResult).  Arrays give m by U's last axis; DeviceBuffers need
+    shape = (E, T) and m."""
+    if not isinstance(U, _lib.DeviceBuffer):
+        m = np.shape(U)[-1]
+    elif m is None:
+        raise RuntimeError('fit_tpwl: DeviceBuffer records need m')
+    sid = TPWLSysID(q, v, dist_weights, m, Ts)
+    sid.add(X, U, stride=stride, shape=shape)
+    mdl = sid.solve(rom_info, ridge=ridge, min_samples=min_samples, on_fail=on_fail, Cf=Cf, Hf=Hf)
+    return mdl, sid.last_result
+
+
+def one_step_error(model, X, U, stride=1, worst=False, Ts=None):
+    """The residual of the model's one-step map x_i + Ts (A_c[p] x_i + B_c[p] u_i + d_c[p]), p the model's nearest point to x_i, on
+    held-out records (arrays (E, T, n_x) / (T, n_x)) over the samples the fit defines: the rms over samples and coordinates, or with
+    worst=True the largest 2-norm over the samples.  Ts defaults to the fit's (model.fit_Ts)."""
+    _check_stride(stride, 'one_step_error')
+    Ts = getattr(model, 'fit_Ts', None) if Ts is None else Ts
+    if Ts is None:
+        raise RuntimeError('one_step_error: the model carries no fit_Ts; give Ts')
+    X, U, E, T, _ = _records(X, U, model.get_state_dim(), model.get_input_dim(), None, 'one_step_error')
+    Xk, Uk = X[:, ::stride], U[:, ::stride]
+    if Xk.shape[1] < 2:
+        raise RuntimeError('one_step_error: the records hold no sample')
+    x0 = np.ascontiguousarray(Xk[:, :-1].reshape(-1, X.shape[2]))
+    u0, x1 = Uk[:, :-1].reshape(-1, U.shape[2]), Xk[:, 1:].reshape(-1, X.shape[2])
+    A, B, d, _ = model.linearize_batch(x0)
+    err = x1 - (x0 + Ts * (np.einsum('bij,bj->bi', A, x0) + np.einsum('bij,bj->bi', B, u0) + d))
+    if worst:
+        return float(np.sqrt((err * err).sum(axis=1)).max())
+    return float(np.sqrt(np.mean(err * err)))
+
+
+def points_from_records(X, k, random_state=0, n_init=10, stride=1):
+    """(q, v), each (k, r): the k-means centroids of the kept states of records X ((E, T, n_x) / (T, n_x)), by the device k-means
+    (mor.pod.compute_kmeans_centroids), split with x2qv."""
+    from ..mor import pod
+    _check_stride(stride, 'points_from_records')
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim == 2:
+        X = X[None]
+    if X.ndim != 3 or X.shape[2] % 2:
+        raise RuntimeError('points_from_records: X must have shape (E, T, n_x) or (T, n_x) with n_x even, got %r' % (tuple(X.shape),))
+    S = np.ascontiguousarray(X[:, ::stride].reshape(-1, X.shape[2]))
+    if not 1 <= int(k) <= S.shape[0]:
+        raise RuntimeError('points_from_records: k = %r, need 1 <= k <= %d kept states' % (k, S.shape[0]))
+    cent = np.asarray(pod.compute_kmeans_centroids(S, int(k), n_init=n_init, random_state=random_state))
+    q, v = scutils.x2qv(cent)
+    return np.ascontiguousarray(q), np.ascontiguousarray(v)
