@@ -6,7 +6,11 @@ target phases: the Monte-Carlo run to set beside examples/diamond_rompc_closed_l
 identified on, so the tracking error printed is that of a mismatched model; the loop's mechanics are what the example shows.  All loops
 stay on the device (baselines.koopman.closed_loop.KoopmanClosedLoopBatch): one launch sequence and one host wait for the whole run.
 
-    python examples/diamond_koopman_closed_loop_batch.py [--batch 256] [--periods 40] [--rollout-horizon 1] [--seed 0]
+    python examples/diamond_koopman_closed_loop_batch.py [--batch 256] [--periods 40] [--rollout-horizon 1] [--seed 0] [--Y 20]
+
+--Y H re-projects every measurement onto the box |y - y_ref|_inf <= H around the tip's rest position before the controller reads it (the
+reference driver's Y, examples/diamond/diamond_koopman.py:117), inside the resident loop, and runs the same seeds without Y beside it: the
+share of projected samples and the tip error of both runs are printed.
 
 Needs an MI355X (no CPU fallback)."""
 import argparse
@@ -71,13 +75,24 @@ def diamond_plant():
     return tp, np.ascontiguousarray(w['H'][3:6]), np.array([0.0, 0.0, -114.0])
 
 
-def diamond_koopman(B, max_steps_per_run, rollout_horizon=1, phase=None):
+def tip_box(half, y_ref=(0.0, 0.0, -114.0)):
+    """The admissible set of the tip measurement: the box of half-width `half` around y_ref, as a Polyhedron that may be projected onto."""
+    from sofacontrol_amd.utils import Polyhedron
+    y_ref = np.asarray(y_ref, dtype=np.float64)
+    A = np.kron(np.eye(3), np.array([[1.0], [-1.0]]))
+    b = np.ravel(np.stack([y_ref + half, -(y_ref - half)], axis=1))
+    return Polyhedron(A, b, with_reproject=True)
+
+
+def diamond_koopman(B, max_steps_per_run, rollout_horizon=1, phase=None, Y=None):
     """(loop, model, scaling, plant, C, y_ref, zf, target) of the example's set-up with B members."""
     from sofacontrol_amd.baselines.koopman.closed_loop import KoopmanClosedLoopBatch
     model, scaling, cost, target, U, zf = diamond_problem()
     tp, Cm, y_ref = diamond_plant()
     loop = KoopmanClosedLoopBatch(model, N, cost, tp, Cm, y_ref, DT_SIM, rollout_horizon, t=target.t, z=target.z, u=target.u, phase=phase, U=U,
                                   u0=np.full(model.m, U0), batch=B, max_steps_per_run=max_steps_per_run)
+    if Y is not None:
+        loop.set_reproject(Y)
     return loop, model, scaling, tp, Cm, y_ref, zf, target
 
 
@@ -87,6 +102,7 @@ def main():
     ap.add_argument('--periods', type=int, default=40, help='periods of rollout_horizon controller steps of 0.05 s')
     ap.add_argument('--rollout-horizon', type=int, default=1)
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--Y', type=float, default=None, metavar='H', help='re-project the measurements onto the box of half-width H around the tip at rest')
     args = ap.parse_args()
     B, P, rh = args.batch, args.periods, args.rollout_horizon
 
@@ -114,6 +130,19 @@ def main():
     codes, counts = np.unique(res.status, return_counts=True)
     print('solve status over %d solves: ' % res.status.size + ', '.join('%d: %d' % (int(c), k) for c, k in zip(codes, counts)))
     assert np.isfinite(res.x).all() and np.isfinite(res.y).all() and np.isfinite(res.u).all()
+
+    if args.Y is not None:
+        loop_y = diamond_koopman(B, P * nk, rollout_horizon=rh, phase=phase, Y=tip_box(args.Y))[0]
+        loop_y.reset(x0=x0, y_hist=y_rest[:, None, :], u_hist=np.full((B, 1, model.m), U0), u_prev0=np.full((B, model.m), U0))
+        ry = loop_y.run(P, V=V)
+        err_y = np.linalg.norm(ry.y[:, 1:, :2] - want[:, 1:], axis=2)
+        rms_y = np.sqrt(np.mean(err_y ** 2, axis=1))
+        words, counts = np.unique(ry.proj, return_counts=True)
+        print('with Y = tip box of half-width %g: %.1f %% of the %d samples projected (status words ' % (args.Y, 100.0 * np.mean(ry.proj == 1), ry.proj.size)
+              + ', '.join('%d: %d' % (int(c), k) for c, k in zip(words, counts)) + ')')
+        print('tip error (x, y) rms per loop with Y: median %.3f, best %.3f, worst %.3f   (without Y: median %.3f, best %.3f, worst %.3f)'
+              % (np.median(rms_y), rms_y.min(), rms_y.max(), np.median(rms), rms.min(), rms.max()))
+        assert np.isfinite(ry.y_used).all() and (ry.proj >= 0).all()
 
 
 if __name__ == '__main__':

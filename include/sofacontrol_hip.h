@@ -298,6 +298,12 @@ int sekf_batch_step(sekf_batch_t *h, const double *u, const double *y, double *x
  * Points with max(A x - b) <= 0 are returned bit for bit.  SRH_ENUMERIC, naming the first such point, when a point is not
  * finite or no certified point is found in 60 iterations (empty set); SRH_EINVAL for a non-finite A or b. */
 int spoly_project(const double *A, const double *b, int n_rows, int n, const double *X, int64_t batch, double *out);
+/* The same projection with a status word per point instead of a failed call -- the form the closed-loop advance kernels use on every
+ * measurement (one device function, csrc/poly_dev.h: a point has the same bits here, in spoly_project and inside a loop):
+ *    0  already inside (max(A x - b) > 0 is false): out = x bit for bit        1  projected, with the certificate above
+ *   -1  no certified projection in 60 iterations (an empty polyhedron): out = x    -2  the point is not finite: out = x
+ * SRH_EINVAL only for the shape limits and a non-finite A or b. */
+int spoly_project_status(const double *A, const double *b, int n_rows, int n, const double *X, int64_t batch, double *out, int32_t *status);
 
 /* =====================================================================================================
  * SSM polynomial reduced model.                                  reference: sofacontrol/SSM/ssm.py
@@ -845,6 +851,29 @@ int sgusto_ssm_loop_create_tpwl(sgusto_ssm_loop_t **out, sgusto_ssm_plan_t *plan
 int sgusto_ssm_loop_advance_tpwl(stpwl_t *plant, const double *C, const double *y_ref, int n_o, sssm_t *observer_model, double dt_sim, int N,
                                  int n_keep, int64_t batch, const int32_t *j, const double *theta, const double *uopt, const double *x,
                                  const double *W, const double *V, double *X, double *Z, double *U, double *Y, double *Xhat, int32_t *idx);
+/* The admissible set of the measurements for either plant kind (SSM/controllers.py:96-97): Y = {y : A y <= b}, A (rows x n_o) row-major.
+ * From the next reset on every measurement y -- the reset's first one included -- that lies outside Y is replaced by its Euclidean
+ * projection inside the advance kernel, and the estimate reads y_used - z_ref_planner (the device function of spoly_project: the same
+ * bits; a sample without a projection is used as it is and reported by its status word, spoly_project_status).  n_o <= 16, rows <= 64,
+ * A and b finite, and a loop created with observe = 0 are refused with the numbers.  A = NULL or b = NULL removes Y.  The loop needs a
+ * reset behind either. */
+int sgusto_ssm_loop_set_reproject(sgusto_ssm_loop_t *h, const double *A, const double *b, int rows);
+/* sgusto_ssm_loop_run with the two records of the re-projection: Y_used (batch x (S + 1) x n_o) the measurements as the observer map read
+ * them, proj (batch x (S + 1)) their status words; row 0 = where the run started.  Y_cl stays the raw measurement. */
+int sgusto_ssm_loop_run_reprojected(sgusto_ssm_loop_t *h, int periods, const double *W, const double *V, double *X_cl, double *Z_cl,
+                                    double *U_cl, double *Y_cl, double *Xhat, int32_t *iters, int32_t *status, double *J, double *Y_used,
+                                    int32_t *proj);
+/* The two advance kernels alone with a Y (YA (y_rows x n_o), Yb): as sgusto_ssm_loop_advance / _advance_tpwl, and Y_used (batch x n_keep x
+ * n_o), proj (batch x n_keep) of every sub-step. */
+int sgusto_ssm_loop_advance_reprojected(sssm_t *plant, int plant_mode, sssm_t *observer_model, double dt_sim, int N, int n_keep, int64_t batch,
+                                        const int32_t *j, const double *theta, const double *uopt, const double *x, const double *W,
+                                        const double *V, const double *YA, const double *Yb, int y_rows, double *X, double *Z, double *U,
+                                        double *Y, double *Xhat, double *Y_used, int32_t *proj);
+int sgusto_ssm_loop_advance_tpwl_reprojected(stpwl_t *plant, const double *C, const double *y_ref, int n_o, sssm_t *observer_model,
+                                             double dt_sim, int N, int n_keep, int64_t batch, const int32_t *j, const double *theta,
+                                             const double *uopt, const double *x, const double *W, const double *V, const double *YA,
+                                             const double *Yb, int y_rows, double *X, double *Z, double *U, double *Y, double *Xhat,
+                                             int32_t *idx, double *Y_used, int32_t *proj);
 
 /* =====================================================================================================
  * Koopman baseline. reference: sofacontrol/baselines/koopman/koopman_utils.py, koopman/koopman.py, baselines/ros.py:139-235
@@ -1141,8 +1170,10 @@ int srompc_loop_advance(srompc_loop_t *h, const double *xopt, const double *uopt
  *               u_s     = uopt[s / r] * u_factor + u_offset            (scale_up of the plan row of the controller step that has fired)
  *               x_s+1   = A_p[i] x_s + B_p[i] u_s + d_p[i] (+ w_s), i the plant's nearest point to x_s
  *               y_s+1   = (C x_s+1 + y_ref) + v_s, or read from Y_plant
- *               push (y_s+1, u_s) -- with U_applied: (y_s+1, U_applied_s) -- scaled down, into the member's ring
- * Not offered: the start-up phase before t_delay, the Y= re-projection of the measurement, input clipping, dU rows, input_nullspace,
+ *               with a Y (skoop_loop_set_reproject): y_s+1 outside Y is replaced by its projection (koopman.py:150-151), with a plant and
+ *                       in replay alike; the sample's status word (spoly_project_status) is recorded, -1 / -2 use the raw sample
+ *               push (y_s+1 as used, u_s) -- with U_applied: (y_s+1, U_applied_s) -- scaled down, into the member's ring
+ * Not offered: the start-up phase before t_delay, projecting the y_hist rows, input clipping, dU rows, input_nullspace,
  * nonlinear_observer, weighting-mode plants, the lifted model as its own plant.  The reference reads its input tape at its own knots,
  * so input_hold changes nothing and is not a parameter.
  * The loop works on the skoop_t handle's ring and advances its head and count: do not push to the handle elsewhere between a reset and
@@ -1186,6 +1217,18 @@ int skoop_loop_fixup(skoop_loop_t *h, const double *xopt_prev, const double *uop
  * its head and count; the loop needs a reset before its next run. */
 int skoop_loop_advance(skoop_loop_t *h, const double *uopt, const double *x, const double *W, const double *V, const double *Y_plant,
                        const double *U_applied, double *X, double *Y, double *U, int32_t *idx);
+/* The admissible set of the measurements, Y = {y : A y <= b}, A (rows x n_y) row-major: from the next reset on every sample -- y_0 of
+ * the reset included, the y_hist rows not -- is projected onto Y before it enters the ring.  n_y <= 16, rows <= 64, A and b finite
+ * (refused with the numbers).  A = NULL or b = NULL removes Y.  The loop needs a reset behind either. */
+int skoop_loop_set_reproject(skoop_loop_t *h, const double *A, const double *b, int rows);
+/* skoop_loop_run with the two records of the re-projection: Y_used (batch x (S + 1) x n_y) the samples as the ring received them, proj
+ * (batch x (S + 1)) their status words (spoly_project_status); row 0 = where the run started.  Y stays the raw measurement. */
+int skoop_loop_run_reprojected(skoop_loop_t *h, int periods, const double *W, const double *V, const double *Y_plant, const double *U_applied,
+                               double *X, double *Y, double *U, double *Xlift, double *J, int32_t *status, int32_t *iters, double *Y_used,
+                               int32_t *proj);
+/* skoop_loop_advance of a loop with a Y: also Y_used (batch x n_keep x n_y) and proj (batch x n_keep) of every sub-step */
+int skoop_loop_advance_reprojected(skoop_loop_t *h, const double *uopt, const double *x, const double *W, const double *V, const double *Y_plant,
+                                   const double *U_applied, double *X, double *Y, double *U, int32_t *idx, double *Y_used, int32_t *proj);
 
 /* =====================================================================================================
  * Batched closed loop of the iLQR controller (tpwl.controllers.ilqr / TrajTracking), resident on the device.

@@ -6,6 +6,7 @@
 #pragma once
 #include "common.h"
 #include "dev_la.h"
+#include "poly_dev.h"
 
 namespace {
 
@@ -57,6 +58,51 @@ __device__ __forceinline__ double query_time(double t0, double dt, int k) {
 #pragma clang fp contract(off)
     const double s = dt * (double)k;
     return t0 + s;
+}
+
+// THE RE-PROJECTION OF A MEASUREMENT onto the admissible set Y = {y : A y <= b} inside an advance kernel (koopman.py:150-151,
+// SSM/controllers.py:96-97: `if not Y.contains(y): y = Y.project_to_polyhedron(y)`), stated once for the advance kernels that offer
+// it.  Wave 0 of the workgroup does it between two workgroup barriers: the sample is complete in LDS in front of the first, the used
+// sample is complete in LDS behind the second.  The arithmetic is poly::project_wave, the device function of spoly_project: a sample
+// projected here has the bits of the stand-alone call.  A sample without a projection (status -1, -2) is used as it is.
+struct ReprojArgs {
+    const double *A, *b;                // (rows x ny), (rows): Y, on the device
+    int rows;
+    double *Yu;                         // record (B x rows_x x ny) of the used samples (rows as the Y record), or null
+    int32_t *proj;                      // record (B x rows_x) of the status words, or null
+};
+struct ReprojWave {                     // what a lane of wave 0 holds for the whole launch: its row of A, its b
+    double ar[poly::PN], bi;
+};
+// the LDS of the re-projection in doubles, at the start of the launch's LDS: the wave's work area | the used sample (ny, padded to even)
+__host__ __device__ inline int reproject_doubles(int ny) { return poly::LDS_BYTES / 8 + ((ny + 1) & ~1); }
+__device__ __forceinline__ lptr reproject_used(lptr area) { return area + poly::LDS_BYTES / 8; }
+__device__ __forceinline__ void reproject_load(const ReprojArgs &r, int ny, int lane, ReprojWave &yw) {
+    poly::load_row((cgptr)r.A, (cgptr)r.b, r.rows, ny, lane, yw.ar, yw.bi);
+}
+// all 64 lanes of one wave: yu (ny) <- the sample the controller uses in place of y (ny); the status word of poly_dev.h
+__device__ __forceinline__ int reproject_sample(const ReprojWave &yw, int rows, int ny, clptr y, lptr yu, lptr area, int lane) {
+    return poly::status_word(poly::project_wave(yw.ar, yw.bi, rows, ny, y, yu, poly::carve(area), lane, poly::MAX_ITER));
+}
+
+// The same for an observer map that reads y - z_ref (the two advance kernels of gusto_ssm_loop.hip), between the barrier behind the sample
+// y (no, LDS) and the estimate: yu <- the used sample, yd <- yu - zref, the record rows Yur (no) / pjr (one word) unless null.  All nt
+// threads of the workgroup; ends with a sync.  Returns the status word (valid in wave 0).
+__device__ __forceinline__ int reproject_measurement(const ReprojWave &yw, int rows, int no, clptr y, lptr yu, lptr area, clptr zref, lptr yd,
+                                                     gptr Yur, giptr pjr, int tid, int nt) {
+    int pj = 0;
+    if (__builtin_amdgcn_readfirstlane(tid >> 6) == 0) {
+        pj = reproject_sample(yw, rows, no, y, yu, area, tid & 63);
+        if ((tid & 63) == 0 && pjr != nullptr) *pjr = pj;
+    }
+    __syncthreads();
+    for (int e = tid; e < no; e += nt) {
+        const double v = yu[e];
+        yd[e] = v - zref[e];
+        if (Yur != nullptr) Yur[e] = v;
+    }
+    __syncthreads();
+    return pj;
 }
 
 struct PrepArgs {

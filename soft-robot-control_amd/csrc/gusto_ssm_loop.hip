@@ -35,6 +35,9 @@ struct SsmAdvArgs {
     double *x_out, *z_out, *y_out, *xh_out;     // where the launch ends (B x .), any may be null (x_out may be x_in)
     double *X, *Z, *U, *Y, *Xhat;       // records: row row0 + s of rollout b (any may be null)
     int64_t rows_x, row0_x, rows_u, row0_u, B, w_step0;
+    ReprojArgs Yp_;                     // the admissible set Y of the measurements and the two records (<true> instantiation only)
+    double *yu_out;                     // (B x no) the last used measurement, or null
+    int32_t *pj_out;                    // (B) its status word, or null
 };
 
 // What the kernel reads of the observer's model (the planner's): the observed -> reduced map and the ssm basis it is written in
@@ -55,10 +58,11 @@ size_t ssm_loop_front_doubles(int n, int m, int no, int nr, int ns_max) {
     return ssm::work_doubles(n, m, no, nr, ns_max) + 3 * (size_t)n + 16 + 5 * (size_t)no + (size_t)n * n + (size_t)n * m + n;
 }
 
-size_t ssm_loop_lds_bytes(const sssm *plant, const sssm *obs) {
+// With a Y (the <true> instantiations) the launch's LDS starts with wave 0's projection area, reproject_doubles(no) doubles.
+size_t ssm_loop_lds_bytes(const sssm *plant, const sssm *obs, bool proj = false) {
     const int ns_max = std::max(plant->ns, obs->ns);
     size_t d = ssm_loop_front_doubles(plant->n, plant->m, plant->no, plant->nr, ns_max) + (size_t)plant->n * obs->ns +
-               ssm::lds_tab_doubles(plant->n, plant->no, plant->nr, plant->ns, 0);
+               ssm::lds_tab_doubles(plant->n, plant->no, plant->nr, plant->ns, 0) + (proj ? reproject_doubles(plant->no) : 0);
     if (obs != plant) d += (size_t)obs->ns + 1;
     return srh::lds_request(sizeof(double) * (d + 2));
 }
@@ -92,6 +96,10 @@ __device__ __forceinline__ void ssm_loop_estimate(liptr ps, liptr vs, const int 
 // paths of ssm::discretize; x' = A_d x + B_d u + d_d (+ w) in the sums of ssm_rollout_kernel; then `measure`: zeta = C_plant(x')
 // (ssm::observe_l), y = (zeta + z_ref_plant) + v, x_hat = V phi_s(y - z_ref_observer).  With init = 1 `measure` runs once at x_in first:
 // a launch of zero sub-steps is the reset's first observer update, so the maps are stated once.
+// PROJ (the loop has a Y): between the barrier behind y and the estimate, wave 0 projects y onto Y and the estimate reads y_used - z_ref
+// (reproject_measurement of gusto_loop_prep.h, SSM/controllers.py:96-97); the init measurement of a reset passes through it too.  <false>
+// (the default) is the kernel as it was: every PROJ part is compiled out.
+template <bool PROJ = false>
 __global__ __launch_bounds__(SL_NT) void ssm_loop_advance_kernel(SsmDev S, SsmObsDev P, SsmAdvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int n = S.n, m = S.m, no = S.no, N = a.N, tid = threadIdx.x, nt = SL_NT;
@@ -99,9 +107,10 @@ __global__ __launch_bounds__(SL_NT) void ssm_loop_advance_kernel(SsmDev S, SsmOb
     const bool dm = a.mode == SSM_DISCRETE_MAP;
     SsmDev Sc = S;
     Sc.ns = max(S.ns, P.ns);                               // the work area's monomial vector serves both ssm bases
+    lptr base = (lptr)smem + (PROJ ? reproject_doubles(no) : 0);
     ssm::Work w;
-    ssm::carve(w, (lptr)smem, Sc);
-    lptr xs = (lptr)smem + ssm::work_doubles(n, m, no, S.nr, Sc.ns);
+    ssm::carve(w, base, Sc);
+    lptr xs = base + ssm::work_doubles(n, m, no, S.nr, Sc.ns);
     lptr xn = xs + n, xh = xn + n, us = xh + n;            // n each, u: 16
     lptr zs = us + 16, ys = zs + no, yd = ys + no, zrl = yd + no, zrp = zrl + no;       // no each
     lptr Al = zrp + no, Bl = Al + (size_t)n * n, dl = Bl + (size_t)n * m;
@@ -120,24 +129,35 @@ __global__ __launch_bounds__(SL_NT) void ssm_loop_advance_kernel(SsmDev S, SsmOb
     for (int e = tid; e < n * P.ns; e += nt) Vl[e] = P.Vc[e];
     for (int e = tid; e < no; e += nt) { zrl[e] = S.z_ref[e]; zrp[e] = P.z_ref[e]; }
     for (int e = tid; e < n; e += nt) xs[e] = ((cgptr)a.x_in)[b * n + e];
+    [[maybe_unused]] ReprojWave yw;
+    [[maybe_unused]] lptr yu = nullptr;
+    [[maybe_unused]] int pj = 0;
+    if constexpr (PROJ) {
+        yu = reproject_used((lptr)smem);
+        if (tid < 64) reproject_load(a.Yp_, no, tid, yw);
+    }
     __syncthreads();
 
-    // zeta, y and x_hat of the state in xs; v (no) or null; rows of the records or null.  Ends with a sync.
-    auto measure = [&](cgptr v, gptr Zr, gptr Yr, gptr XHr) {
+    // zeta, y and x_hat of the state in xs; v (no) or null; rows of the records or null (row: of the two records of Y, < 0: none).
+    // Ends with a sync.
+    auto measure = [&](cgptr v, gptr Zr, gptr Yr, gptr XHr, [[maybe_unused]] int64_t row) {
         ssm::observe_l(S, T, xs, w, zs);
         for (int e = tid; e < no; e += nt) {
             double y = zs[e] + zrl[e];
             if (v != nullptr) y += v[e];
             ys[e] = y;
-            yd[e] = y - zrp[e];
+            if constexpr (!PROJ) yd[e] = y - zrp[e];
             if (Zr != nullptr) Zr[e] = zs[e];
             if (Yr != nullptr) Yr[e] = y;
         }
         __syncthreads();
+        if constexpr (PROJ)
+            pj = reproject_measurement(yw, a.Yp_.rows, no, ys, yu, (lptr)smem, zrp, yd, (row >= 0 && a.Yp_.Yu) ? (gptr)a.Yp_.Yu + row * no : (gptr) nullptr,
+                                       (row >= 0 && a.Yp_.proj) ? (giptr)a.Yp_.proj + row : (giptr) nullptr, tid, nt);
         ssm_loop_estimate(pps, pvs, plv, P.order_s, P.ns, no, n, yd, w.phi, Vl, xh, XHr, tid, nt);
     };
 
-    if (a.init) measure(a.v0 ? (cgptr)a.v0 + b * no : (cgptr) nullptr, (gptr) nullptr, (gptr) nullptr, (gptr) nullptr);
+    if (a.init) measure(a.v0 ? (cgptr)a.v0 + b * no : (cgptr) nullptr, (gptr) nullptr, (gptr) nullptr, (gptr) nullptr, -1);
     cgptr uo = (cgptr)a.uopt + b * (size_t)N * m, Wd = (cgptr)a.W, Vd = (cgptr)a.Vn, thg = (cgptr)a.theta;
     cgiptr jsg = (cgiptr)a.js;
     for (int s = 0; s < a.n_keep; ++s) {
@@ -167,7 +187,7 @@ __global__ __launch_bounds__(SL_NT) void ssm_loop_advance_kernel(SsmDev S, SsmOb
         }
         __syncthreads();
         measure(Vd != nullptr ? Vd + ((size_t)(a.w_step0 + s) * a.B + b) * no : (cgptr) nullptr, a.Z ? (gptr)a.Z + row * no : (gptr) nullptr,
-                a.Y ? (gptr)a.Y + row * no : (gptr) nullptr, a.Xhat ? (gptr)a.Xhat + row * n : (gptr) nullptr);
+                a.Y ? (gptr)a.Y + row * no : (gptr) nullptr, a.Xhat ? (gptr)a.Xhat + row * n : (gptr) nullptr, (int64_t)row);
     }
     for (int e = tid; e < n; e += nt) {
         if (a.x_out) ((gptr)a.x_out)[b * n + e] = xs[e];
@@ -176,6 +196,11 @@ __global__ __launch_bounds__(SL_NT) void ssm_loop_advance_kernel(SsmDev S, SsmOb
     for (int e = tid; e < no; e += nt) {
         if (a.z_out) ((gptr)a.z_out)[b * no + e] = zs[e];
         if (a.y_out) ((gptr)a.y_out)[b * no + e] = ys[e];
+    }
+    if constexpr (PROJ) {
+        if (a.yu_out)
+            for (int e = tid; e < no; e += nt) ((gptr)a.yu_out)[b * no + e] = yu[e];
+        if (a.pj_out && tid == 0) ((giptr)a.pj_out)[b] = pj;
     }
 }
 
@@ -195,8 +220,15 @@ int ssm_loop_check_models(const char *who, const sssm *plant, int plant_mode, co
     return SRH_OK;
 }
 
+// (lds: of the instantiation the arguments choose -- with a Y, ssm_loop_lds_bytes(.., true))
 int ssm_loop_launch(const sssm *plant, const sssm *obs, size_t lds, const SsmAdvArgs &a, hipStream_t st) {
-    SRH_CHECK_HIP(hipFuncSetAttribute((const void *)ssm_loop_advance_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (a.Yp_.rows) {
+        SRH_CHECK_HIP(hipFuncSetAttribute((const void *)ssm_loop_advance_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        ssm_loop_advance_kernel<true><<<(unsigned)a.B, SL_NT, lds, st>>>(plant->view(), obs_view(obs), a);
+        SRH_CHECK_HIP(hipGetLastError());
+        return SRH_OK;
+    }
+    SRH_CHECK_HIP(hipFuncSetAttribute((const void *)ssm_loop_advance_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     ssm_loop_advance_kernel<<<(unsigned)a.B, SL_NT, lds, st>>>(plant->view(), obs_view(obs), a);
     SRH_CHECK_HIP(hipGetLastError());
     return SRH_OK;
@@ -218,6 +250,9 @@ struct SsmTpwlAdvArgs {
     double *X, *Z, *U, *Y, *Xhat;       // records: row row0 + s of rollout b (any may be null)
     int32_t *idx;                       // (B x n_keep) the plant's point of every sub-step, or null
     int64_t rows_x, row0_x, rows_u, row0_u, B, w_step0;
+    ReprojArgs Yp_;                     // the admissible set Y of the measurements and the two records (<true> instantiation only)
+    double *yu_out;                     // (B x no) the last used measurement, or null
+    int32_t *pj_out;                    // (B) its status word, or null
 };
 
 // LDS of the launch in doubles, every block padded to even so that the panel is 16-byte aligned: x (np) | u (16) | zeta, y, y - z_ref,
@@ -225,9 +260,9 @@ struct SsmTpwlAdvArgs {
 // tables of its ssm basis (2 ns ints) | the staged step of tpwl_dev.h: partial sums of A x, B u (256 each), the point (2), the plant's
 // panel A^T, B^T, d (np is even: x = [v; q]).
 __host__ __device__ inline int sl_even(int v) { return (v + 1) & ~1; }
-size_t ssm_loop_tpwl_lds_bytes(int np, int m, int n, int no, int ns) {
+size_t ssm_loop_tpwl_lds_bytes(int np, int m, int n, int no, int ns, bool proj = false) {
     const size_t d = (size_t)sl_even(np) + 16 + 5 * (size_t)sl_even(no) + (size_t)sl_even(n) + 2 * (size_t)sl_even(ns) + (size_t)sl_even(no * np) +
-                     (size_t)sl_even(n * ns) + tpwl::step_doubles(np, m, SL_NT) + 2;
+                     (size_t)sl_even(n * ns) + tpwl::step_doubles(np, m, SL_NT) + 2 + (proj ? reproject_doubles(no) : 0);
     return srh::lds_request(sizeof(double) * d);
 }
 
@@ -241,10 +276,12 @@ size_t ssm_loop_tpwl_lds_bytes(int np, int m, int n, int no, int ns) {
 //   zeta_e = out_row(C, e, np, x'), y_e = measure_row: (zeta_e + y_ref[e]) + v_e     (gusto_loop_prep.h); the record Z is zeta
 //   x_hat  = THE ESTIMATE (ssm_loop_estimate) of y - z_ref_observer
 // With init = 1 the measurement and the estimate run once at x_in first: a launch of zero sub-steps is the reset's first observer update.
+// PROJ: as ssm_loop_advance_kernel -- y is projected onto Y between its barrier and the estimate, which then reads y_used - z_ref.
+template <bool PROJ = false>
 __global__ __launch_bounds__(SL_NT) void ssm_loop_advance_tpwl_kernel(TpwlDev TL, SsmObsDev P, SsmTpwlAdvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int np = a.np, m = a.m, n = a.n, no = a.no, ns = P.ns, N = a.N, nt = SL_NT;
-    lptr xc = (lptr)smem;                                // np     plant state
+    lptr xc = (lptr)smem + (PROJ ? reproject_doubles(no) : 0);      // np     plant state
     lptr uc = xc + sl_even(np);                          // 16     input of the sub-step
     lptr zs = uc + 16;                                   // no     zeta = C x
     lptr ys = zs + sl_even(no);                          // no     measurement
@@ -269,25 +306,35 @@ __global__ __launch_bounds__(SL_NT) void ssm_loop_advance_tpwl_kernel(TpwlDev TL
     for (int e = tid; e < no * np; e += nt) Cl[e] = ((cgptr)a.C)[e];
     for (int e = tid; e < no; e += nt) { yr[e] = ((cgptr)a.yref)[e]; zrp[e] = P.z_ref[e]; }
     for (int e = tid; e < np; e += nt) xc[e] = ((cgptr)a.x_in)[b * np + e];
+    [[maybe_unused]] ReprojWave yw;
+    [[maybe_unused]] lptr yu = nullptr;
+    [[maybe_unused]] int pj = 0;
+    if constexpr (PROJ) {
+        yu = reproject_used((lptr)smem);
+        if (wave == 0) reproject_load(a.Yp_, no, lane, yw);
+    }
     __syncthreads();
 
     // zeta, y and x_hat of the state in xc; noise: the block the row iv0 .. iv0 + no - 1 is read from, or null; rows of the records or
-    // null.  Ends with a sync.
-    auto measure = [&](cgptr noise, size_t iv0, gptr Zr, gptr Yr, gptr XHr) {
+    // null (row: of the two records of Y, < 0: none).  Ends with a sync.
+    auto measure = [&](cgptr noise, size_t iv0, gptr Zr, gptr Yr, gptr XHr, [[maybe_unused]] int64_t row) {
         for (int e = tid; e < no; e += nt) {
             const double zeta = out_row(Cl, e, np, xc);
             const double y = measure_row(Cl, e, np, xc, yr, noise, iv0 + e);
             zs[e] = zeta;
             ys[e] = y;
-            yd[e] = y - zrp[e];
+            if constexpr (!PROJ) yd[e] = y - zrp[e];
             if (Zr != nullptr) Zr[e] = zeta;
             if (Yr != nullptr) Yr[e] = y;
         }
         __syncthreads();
+        if constexpr (PROJ)
+            pj = reproject_measurement(yw, a.Yp_.rows, no, ys, yu, (lptr)smem, zrp, yd, (row >= 0 && a.Yp_.Yu) ? (gptr)a.Yp_.Yu + row * no : (gptr) nullptr,
+                                       (row >= 0 && a.Yp_.proj) ? (giptr)a.Yp_.proj + row : (giptr) nullptr, tid, nt);
         ssm_loop_estimate(pps, pvs, plv, P.order_s, ns, no, n, yd, phi, Vl, xh, XHr, tid, nt);
     };
 
-    if (a.init) measure((cgptr)a.v0, b * no, (gptr) nullptr, (gptr) nullptr, (gptr) nullptr);
+    if (a.init) measure((cgptr)a.v0, b * no, (gptr) nullptr, (gptr) nullptr, (gptr) nullptr, -1);
     cgptr uo = (cgptr)a.uopt + b * (size_t)N * m, Wd = (cgptr)a.W, Vd = (cgptr)a.Vn, thg = (cgptr)a.theta;
     cgiptr jsg = (cgiptr)a.js;
     int cur = -1;
@@ -321,7 +368,7 @@ __global__ __launch_bounds__(SL_NT) void ssm_loop_advance_tpwl_kernel(TpwlDev TL
         }
         __syncthreads();
         measure(Vd, ((size_t)(a.w_step0 + s) * a.B + b) * no, a.Z ? (gptr)a.Z + row * no : (gptr) nullptr,       // 4., 5.
-                a.Y ? (gptr)a.Y + row * no : (gptr) nullptr, a.Xhat ? (gptr)a.Xhat + row * n : (gptr) nullptr);
+                a.Y ? (gptr)a.Y + row * no : (gptr) nullptr, a.Xhat ? (gptr)a.Xhat + row * n : (gptr) nullptr, (int64_t)row);
     }
     for (int e = tid; e < np; e += nt)
         if (a.x_out) ((gptr)a.x_out)[b * np + e] = xc[e];
@@ -330,6 +377,11 @@ __global__ __launch_bounds__(SL_NT) void ssm_loop_advance_tpwl_kernel(TpwlDev TL
     for (int e = tid; e < no; e += nt) {
         if (a.z_out) ((gptr)a.z_out)[b * no + e] = zs[e];
         if (a.y_out) ((gptr)a.y_out)[b * no + e] = ys[e];
+    }
+    if constexpr (PROJ) {
+        if (a.yu_out)
+            for (int e = tid; e < no; e += nt) ((gptr)a.yu_out)[b * no + e] = yu[e];
+        if (a.pj_out && tid == 0) ((giptr)a.pj_out)[b] = pj;
     }
 }
 
@@ -347,7 +399,13 @@ int ssm_loop_check_tpwl(const char *who, const stpwl *plant, int n_o, const sssm
 }
 
 int ssm_loop_launch_tpwl(const stpwl *plant, const sssm *obs, size_t lds, const SsmTpwlAdvArgs &a, hipStream_t st) {
-    SRH_CHECK_HIP(hipFuncSetAttribute((const void *)ssm_loop_advance_tpwl_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (a.Yp_.rows) {
+        SRH_CHECK_HIP(hipFuncSetAttribute((const void *)ssm_loop_advance_tpwl_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        ssm_loop_advance_tpwl_kernel<true><<<(unsigned)a.B, SL_NT, lds, st>>>(plant->view(), obs_view(obs), a);
+        SRH_CHECK_HIP(hipGetLastError());
+        return SRH_OK;
+    }
+    SRH_CHECK_HIP(hipFuncSetAttribute((const void *)ssm_loop_advance_tpwl_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     ssm_loop_advance_tpwl_kernel<<<(unsigned)a.B, SL_NT, lds, st>>>(plant->view(), obs_view(obs), a);
     SRH_CHECK_HIP(hipGetLastError());
     return SRH_OK;
@@ -363,7 +421,21 @@ struct sgusto_ssm_loop : LoopCore {
     bool observe = true;
     srh::DevBuf zcur, ycur, xhcur, v0;  // where the loops stand beside the plant state xcur: its output, the last measurement, the estimate
     srh::DevBuf cst, xp;                // TPWL plant: C (no x np) | y_ref (no); the plant states (B x np) -- xcur has the planner's width
-    __attribute__((always_inline)) sgusto_ssm_loop() {}        // (inlined: no constructor among the library's dynamic symbols)
+    // the re-projection onto Y (sgusto_ssm_loop_set_reproject): Y on the device (A | b), the LDS of the <true> instantiation, where the
+    // used measurement and its status word stand (row 0 of the next run's records), the two records
+    int yrows = 0;
+    size_t lds_proj = 0;
+    srh::DevBuf Yd, yucur, pjcur;
+    LoopRec YUrec, PJrec;
+    __attribute__((always_inline)) sgusto_ssm_loop() {         // (inlined: no constructor among the library's dynamic symbols)
+        recs.push_back(&YUrec); recs.push_back(&PJrec);
+    }
+    size_t lds_now() const { return yrows ? lds_proj : lds; }
+    template <class Args> void reproject_args(Args &a) const {
+        if (!yrows) return;
+        a.Yp_.A = Yd.as<double>(); a.Yp_.b = a.Yp_.A + (size_t)yrows * no; a.Yp_.rows = yrows;
+        a.yu_out = yucur.as<double>(); a.pj_out = pjcur.as<int32_t>();
+    }
     ~sgusto_ssm_loop() { drain(); }
     SsmTpwlAdvArgs adv_args_tpwl() const {
         SsmTpwlAdvArgs a{};
@@ -371,6 +443,7 @@ struct sgusto_ssm_loop : LoopCore {
         a.js = js.as<int32_t>(); a.theta = theta.as<double>();
         a.C = cst.as<double>(); a.yref = a.C + (size_t)no * np;
         a.B = B;
+        reproject_args(a);
         return a;
     }
     SsmAdvArgs adv_args() const {
@@ -379,6 +452,7 @@ struct sgusto_ssm_loop : LoopCore {
         a.dt_sim = dt_sim;
         a.js = js.as<int32_t>(); a.theta = theta.as<double>();
         a.B = B;
+        reproject_args(a);
         return a;
     }
 };
@@ -482,7 +556,7 @@ int sgusto_ssm_loop_reset(sgusto_ssm_loop_t *h, const double *x0, const double *
         a.v0 = v0 ? h->v0.as<double>() : nullptr;
         a.x_in = h->xp.as<double>();
         a.z_out = h->zcur.as<double>(); a.y_out = h->ycur.as<double>(); a.xh_out = h->xhcur.as<double>();
-        const int rc = loop_wait(ssm_loop_launch_tpwl(h->tplant, h->planner, h->lds, a, h->stream), h->stream);
+        const int rc = loop_wait(ssm_loop_launch_tpwl(h->tplant, h->planner, h->lds_now(), a, h->stream), h->stream);
         if (rc) return rc;
         h->t_start = t_start; h->k = 0; h->have_state = true;
         return SRH_OK;
@@ -493,25 +567,31 @@ int sgusto_ssm_loop_reset(sgusto_ssm_loop_t *h, const double *x0, const double *
     a.v0 = v0 ? h->v0.as<double>() : nullptr;
     a.x_in = h->xcur.as<double>();
     a.z_out = h->zcur.as<double>(); a.y_out = h->ycur.as<double>(); a.xh_out = h->xhcur.as<double>();
-    const int rc = loop_wait(ssm_loop_launch(h->plant, h->planner, h->lds, a, h->stream), h->stream);
+    const int rc = loop_wait(ssm_loop_launch(h->plant, h->planner, h->lds_now(), a, h->stream), h->stream);
     if (rc) return rc;
     h->t_start = t_start; h->k = 0; h->have_state = true;
     return SRH_OK;
 }
 
-int sgusto_ssm_loop_run(sgusto_ssm_loop_t *h, int periods, const double *W, const double *V, double *X_cl, double *Z_cl, double *U_cl, double *Y_cl,
-                        double *Xhat, int32_t *iters, int32_t *status, double *J) {
-    SRH_REQUIRE(h && Z_cl && U_cl && Y_cl && Xhat && iters && status && J, "sgusto_ssm_loop_run: null argument");
-    SRH_REQUIRE(periods >= 1, "sgusto_ssm_loop_run: periods must be positive");
-    SRH_REQUIRE(h->have_state, "sgusto_ssm_loop_run: no plant state yet (call sgusto_ssm_loop_reset first)");
+}  // extern "C"
+
+namespace {
+
+// a run, with the two records of the re-projection when the loop has a Y (Y_used, proj: null without one)
+int ssm_loop_run(sgusto_ssm_loop *h, const char *who, int periods, const double *W, const double *V, double *X_cl, double *Z_cl, double *U_cl,
+                 double *Y_cl, double *Xhat, int32_t *iters, int32_t *status, double *J, double *Y_used, int32_t *proj) {
+    SRH_REQUIRE(h && Z_cl && U_cl && Y_cl && Xhat && iters && status && J, "%s: null argument", who);
+    SRH_REQUIRE(periods >= 1, "%s: periods must be positive", who);
+    SRH_REQUIRE(h->have_state, "%s: no plant state yet (call sgusto_ssm_loop_reset first)", who);
     const size_t B = (size_t)h->B;
+    h->YUrec.host = Y_used; h->PJrec.host = proj;
     h->Wd.host = (void *)W; h->Vd.host = (void *)V; h->Xrec.host = X_cl; h->Zrec.host = Z_cl; h->Urec.host = U_cl; h->Yrec.host = Y_cl;
     h->XHrec.host = Xhat; h->Irec.host = iters; h->Srec.host = status; h->Jrec.host = J;
     // the plan starts from the estimate (the reference's loop) or from the plant state (perfect state feedback); no H, no zf, and row 0 of
     // the records is where the loops stand (LoopRec::row0, set at create): the advance kernel writes the records
     // (a TPWL plant's state is not the planner's: its plans always start from the estimate)
     const PrepUnit u{(h->observe || h->tplant) ? h->xhcur.as<double>() : h->xcur.as<double>(), nullptr, nullptr, nullptr, false};
-    return loop_run_periods(h, "sgusto_ssm_loop_run", periods, u, [&](int p, const PrepArgs &a, const LoopRows &r) -> int {
+    return loop_run_periods(h, who, periods, u, [&](int p, const PrepArgs &a, const LoopRows &r) -> int {
         int rc;
         // scp/ros.py:78-79: the first guess is the planner's own zero-input rollout from x0
         if (a.first && (rc = sssm_rollout_dev(h->planner, a.x0, a.u_init, h->N, h->B, h->plan_mode, h->dt, a.x_init, nullptr, (void *)h->stream)))
@@ -530,7 +610,8 @@ int sgusto_ssm_loop_run(sgusto_ssm_loop_t *h, int periods, const double *W, cons
             v.X = X_cl ? h->Xrec.as<double>() : nullptr; v.Z = h->Zrec.as<double>(); v.U = h->Urec.as<double>();
             v.Y = h->Yrec.as<double>(); v.Xhat = h->XHrec.as<double>();
             v.rows_x = r.rows_x; v.row0_x = r.row0_x; v.rows_u = r.rows_u; v.row0_u = r.row0_u;
-            return ssm_loop_launch_tpwl(h->tplant, h->planner, h->lds, v, h->stream);
+            v.Yp_.Yu = Y_used ? h->YUrec.as<double>() : nullptr; v.Yp_.proj = proj ? h->PJrec.as<int32_t>() : nullptr;
+            return ssm_loop_launch_tpwl(h->tplant, h->planner, h->lds_now(), v, h->stream);
         }
         SsmAdvArgs v = h->adv_args();
         v.uopt = a.uopt;
@@ -540,8 +621,69 @@ int sgusto_ssm_loop_run(sgusto_ssm_loop_t *h, int periods, const double *W, cons
         v.X = X_cl ? h->Xrec.as<double>() : nullptr; v.Z = h->Zrec.as<double>(); v.U = h->Urec.as<double>();
         v.Y = h->Yrec.as<double>(); v.Xhat = h->XHrec.as<double>();
         v.rows_x = r.rows_x; v.row0_x = r.row0_x; v.rows_u = r.rows_u; v.row0_u = r.row0_u;
-        return ssm_loop_launch(h->plant, h->planner, h->lds, v, h->stream);
+        v.Yp_.Yu = Y_used ? h->YUrec.as<double>() : nullptr; v.Yp_.proj = proj ? h->PJrec.as<int32_t>() : nullptr;
+        return ssm_loop_launch(h->plant, h->planner, h->lds_now(), v, h->stream);
     });
+}
+
+// Y of a stand-alone advance entry on the device (A | b), checked as set_reproject checks it
+int ssm_loop_stage_Y(const char *who, const double *A, const double *b, int rows, int no, srh::DevBuf &d, ReprojArgs &r) {
+    SRH_REQUIRE(A && b, "%s: null argument", who);
+    SRH_REQUIRE(no <= poly::PN && rows > 0 && rows <= poly::PM, "%s: Y needs n_o <= 16 and 0 < rows <= 64 (got n_o = %d, rows = %d)", who, no, rows);
+    for (int i = 0; i < rows * no; ++i) SRH_REQUIRE(std::isfinite(A[i]), "%s: Y is not finite (A, row %d)", who, i / no);
+    for (int i = 0; i < rows; ++i) SRH_REQUIRE(std::isfinite(b[i]), "%s: Y is not finite (b, row %d)", who, i);
+    std::vector<double> c(A, A + (size_t)rows * no);
+    c.insert(c.end(), b, b + rows);
+    const int rc = d.upload(c.data(), sizeof(double) * c.size());
+    if (rc) return rc;
+    r.A = d.as<double>(); r.b = r.A + (size_t)rows * no; r.rows = rows;
+    return SRH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sgusto_ssm_loop_run(sgusto_ssm_loop_t *h, int periods, const double *W, const double *V, double *X_cl, double *Z_cl, double *U_cl, double *Y_cl,
+                        double *Xhat, int32_t *iters, int32_t *status, double *J) {
+    return ssm_loop_run(h, "sgusto_ssm_loop_run", periods, W, V, X_cl, Z_cl, U_cl, Y_cl, Xhat, iters, status, J, nullptr, nullptr);
+}
+
+int sgusto_ssm_loop_run_reprojected(sgusto_ssm_loop_t *h, int periods, const double *W, const double *V, double *X_cl, double *Z_cl, double *U_cl,
+                                    double *Y_cl, double *Xhat, int32_t *iters, int32_t *status, double *J, double *Y_used, int32_t *proj) {
+    SRH_REQUIRE(h, "sgusto_ssm_loop_run_reprojected: null argument");
+    SRH_REQUIRE(h->yrows, "sgusto_ssm_loop_run_reprojected: the loop has no Y (sgusto_ssm_loop_set_reproject)");
+    return ssm_loop_run(h, "sgusto_ssm_loop_run_reprojected", periods, W, V, X_cl, Z_cl, U_cl, Y_cl, Xhat, iters, status, J, Y_used, proj);
+}
+
+int sgusto_ssm_loop_set_reproject(sgusto_ssm_loop_t *h, const double *A, const double *b, int rows) {
+    SRH_REQUIRE(h, "sgusto_ssm_loop_set_reproject: null handle");
+    SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
+    h->have_state = false;               // the estimate the loops stand at was formed under the previous rule: a reset forms it anew
+    if (!A || !b) {
+        h->yrows = 0;
+        return SRH_OK;
+    }
+    SRH_REQUIRE(h->observe, "sgusto_ssm_loop_set_reproject: the loop was created with observe = 0 (plans start from the plant state): no "
+                "measurement is read, a Y would change nothing");
+    const int no = h->no;
+    SRH_REQUIRE(no <= poly::PN && rows > 0 && rows <= poly::PM,
+                "sgusto_ssm_loop_set_reproject: Y needs n_o <= 16 and 0 < rows <= 64 (got n_o = %d, rows = %d)", no, rows);
+    const size_t lds = h->tplant ? ssm_loop_tpwl_lds_bytes(h->np, h->m, h->n, no, h->planner->ns, true) : ssm_loop_lds_bytes(h->plant, h->planner, true);
+    SRH_REQUIRE(lds <= (size_t)160 * 1024, "sgusto_ssm_loop_set_reproject: the advance kernel needs %zu bytes of LDS (160 KiB available)", lds);
+    ReprojArgs r{};
+    int rc;
+    const size_t D = sizeof(double), B = (size_t)h->B;
+    if ((rc = ssm_loop_stage_Y("sgusto_ssm_loop_set_reproject", A, b, rows, no, h->Yd, r)) || (rc = h->yucur.alloc(D * B * no)) ||
+        (rc = h->pjcur.alloc(sizeof(int32_t) * B)))
+        return rc;
+    if (!h->YUrec.d.p) {
+        h->YUrec.shape(D * no, 1); h->PJrec.shape(sizeof(int32_t), 1);
+        if ((rc = h->alloc_recs({&h->YUrec, &h->PJrec}))) return rc;
+    }
+    h->YUrec.row0 = h->yucur.p; h->PJrec.row0 = h->pjcur.p;
+    h->lds_proj = lds; h->yrows = rows;
+    return SRH_OK;
 }
 
 int sgusto_ssm_loop_last_inputs(sgusto_ssm_loop_t *h, double *x0, double *u_init, double *x_init, double *z, double *u_des) {
@@ -554,19 +696,31 @@ int sgusto_ssm_loop_stats(sgusto_ssm_loop_t *h, int64_t *steps, int64_t *waits_l
     return loop_stats(h, "sgusto_ssm_loop_stats", steps, waits_last_run);
 }
 
-int sgusto_ssm_loop_advance(sssm_t *plant, int plant_mode, sssm_t *observer_model, double dt_sim, int N, int n_keep, int64_t batch, const int32_t *j,
-                            const double *theta, const double *xopt, const double *uopt, const double *x, const double *W, const double *V, double *X,
-                            double *Z, double *U, double *Y, double *Xhat) {
-    SRH_REQUIRE(plant && observer_model && j && theta && uopt && x && X && Z && U && Y && Xhat, "sgusto_ssm_loop_advance: null argument");
-    SRH_REQUIRE(N >= 1 && n_keep >= 1 && batch >= 1 && dt_sim > 0.0, "sgusto_ssm_loop_advance: need N, n_keep, batch >= 1 and dt_sim > 0");
+}  // extern "C"
+
+namespace {
+
+// YA (rows x n_o), Yb: the admissible set of the measurements, or null (then Y_used and proj are not written)
+int ssm_loop_advance(const char *who, sssm_t *plant, int plant_mode, sssm_t *observer_model, double dt_sim, int N, int n_keep, int64_t batch,
+                     const int32_t *j, const double *theta, const double *uopt, const double *x, const double *W, const double *V, double *X, double *Z,
+                     double *U, double *Y, double *Xhat, const double *YA, const double *Yb, int yrows, double *Y_used, int32_t *proj) {
+    SRH_REQUIRE(plant && observer_model && j && theta && uopt && x && X && Z && U && Y && Xhat, "%s: null argument", who);
+    SRH_REQUIRE(N >= 1 && n_keep >= 1 && batch >= 1 && dt_sim > 0.0, "%s: need N, n_keep, batch >= 1 and dt_sim > 0", who);
     for (int s = 0; s < n_keep; ++s)
-        SRH_REQUIRE(j[s] >= 0 && j[s] <= N - 1, "sgusto_ssm_loop_advance: j[%d] = %d is not an interval 0..N-1 of the plan (N = %d)", s, j[s], N);
-    (void)xopt;                         // (the law u = u_bar(t) has no gain: the plan's states are not read)
+        SRH_REQUIRE(j[s] >= 0 && j[s] <= N - 1, "%s: j[%d] = %d is not an interval 0..N-1 of the plan (N = %d)", who, s, j[s], N);
     size_t lds = 0;
     int rc;
-    if ((rc = ssm_loop_check_models("sgusto_ssm_loop_advance", plant, plant_mode, observer_model, &lds))) return rc;
+    if ((rc = ssm_loop_check_models(who, plant, plant_mode, observer_model, &lds))) return rc;
     const size_t D = sizeof(double), B = (size_t)batch, n = plant->n, m = plant->m, no = plant->no, nk = n_keep;
-    srh::DevBuf dj, dth, duo, dx, dW, dV, dX, dZ, dU, dY, dXH;
+    srh::DevBuf dj, dth, duo, dx, dW, dV, dX, dZ, dU, dY, dXH, dYs, dYu, dPj;
+    ReprojArgs yp{};
+    if (YA) {
+        if ((rc = ssm_loop_stage_Y(who, YA, Yb, yrows, (int)no, dYs, yp)) || (rc = dYu.alloc(D * B * nk * no)) || (rc = dPj.alloc(sizeof(int32_t) * B * nk)))
+            return rc;
+        yp.Yu = dYu.as<double>(); yp.proj = dPj.as<int32_t>();
+        lds = ssm_loop_lds_bytes(plant, observer_model, true);
+        SRH_REQUIRE(lds <= (size_t)160 * 1024, "%s: the advance kernel needs %zu bytes of LDS (160 KiB available)", who, lds);
+    }
     if ((rc = dj.upload(j, sizeof(int32_t) * nk)) || (rc = dth.upload(theta, D * nk)) || (rc = duo.upload(uopt, D * B * N * m)) ||
         (rc = dx.upload(x, D * B * n)) || (W && (rc = dW.upload(W, D * nk * B * n))) || (V && (rc = dV.upload(V, D * nk * B * no))) ||
         (rc = dX.alloc(D * B * nk * n)) || (rc = dZ.alloc(D * B * nk * no)) || (rc = dU.alloc(D * B * nk * m)) || (rc = dY.alloc(D * B * nk * no)) ||
@@ -581,28 +735,38 @@ int sgusto_ssm_loop_advance(sssm_t *plant, int plant_mode, sssm_t *observer_mode
     a.x_in = dx.as<double>();
     a.X = dX.as<double>(); a.Z = dZ.as<double>(); a.U = dU.as<double>(); a.Y = dY.as<double>(); a.Xhat = dXH.as<double>();
     a.rows_x = (int64_t)nk; a.rows_u = (int64_t)nk; a.B = batch;
+    a.Yp_ = yp;
     if ((rc = loop_wait(ssm_loop_launch(plant, observer_model, lds, a, nullptr), nullptr))) return rc;
     if ((rc = dX.download(X, D * B * nk * n)) || (rc = dZ.download(Z, D * B * nk * no)) || (rc = dU.download(U, D * B * nk * m)) ||
-        (rc = dY.download(Y, D * B * nk * no)) || (rc = dXH.download(Xhat, D * B * nk * n)))
+        (rc = dY.download(Y, D * B * nk * no)) || (rc = dXH.download(Xhat, D * B * nk * n)) ||
+        (YA && ((rc = dYu.download(Y_used, D * B * nk * no)) || (rc = dPj.download(proj, sizeof(int32_t) * B * nk)))))
         return rc;
     return SRH_OK;
 }
 
-int sgusto_ssm_loop_advance_tpwl(stpwl_t *plant, const double *Cm, const double *y_ref, int n_o, sssm_t *observer_model, double dt_sim, int N,
-                                 int n_keep, int64_t batch, const int32_t *j, const double *theta, const double *uopt, const double *x,
-                                 const double *W, const double *V, double *X, double *Z, double *U, double *Y, double *Xhat, int32_t *idx) {
-    SRH_REQUIRE(plant && Cm && y_ref && observer_model && j && theta && uopt && x && X && Z && U && Y && Xhat && idx,
-                "sgusto_ssm_loop_advance_tpwl: null argument");
-    SRH_REQUIRE(N >= 1 && n_keep >= 1 && batch >= 1 && dt_sim > 0.0, "sgusto_ssm_loop_advance_tpwl: need N, n_keep, batch >= 1 and dt_sim > 0");
+int ssm_loop_advance_tpwl(const char *who, stpwl_t *plant, const double *Cm, const double *y_ref, int n_o, sssm_t *observer_model, double dt_sim, int N,
+                          int n_keep, int64_t batch, const int32_t *j, const double *theta, const double *uopt, const double *x, const double *W,
+                          const double *V, double *X, double *Z, double *U, double *Y, double *Xhat, int32_t *idx, const double *YA, const double *Yb,
+                          int yrows, double *Y_used, int32_t *proj) {
+    SRH_REQUIRE(plant && Cm && y_ref && observer_model && j && theta && uopt && x && X && Z && U && Y && Xhat && idx, "%s: null argument", who);
+    SRH_REQUIRE(N >= 1 && n_keep >= 1 && batch >= 1 && dt_sim > 0.0, "%s: need N, n_keep, batch >= 1 and dt_sim > 0", who);
     for (int s = 0; s < n_keep; ++s)
-        SRH_REQUIRE(j[s] >= 0 && j[s] <= N - 1, "sgusto_ssm_loop_advance_tpwl: j[%d] = %d is not an interval 0..N-1 of the plan (N = %d)", s, j[s], N);
+        SRH_REQUIRE(j[s] >= 0 && j[s] <= N - 1, "%s: j[%d] = %d is not an interval 0..N-1 of the plan (N = %d)", who, s, j[s], N);
     size_t lds = 0;
     int rc;
-    if ((rc = ssm_loop_check_tpwl("sgusto_ssm_loop_advance_tpwl", plant, n_o, observer_model, &lds))) return rc;
+    if ((rc = ssm_loop_check_tpwl(who, plant, n_o, observer_model, &lds))) return rc;
     const size_t D = sizeof(double), B = (size_t)batch, np = plant->n, n = observer_model->n, m = plant->m, no = (size_t)n_o, nk = n_keep;
     std::vector<double> c(Cm, Cm + no * np);             // C | y_ref
     c.insert(c.end(), y_ref, y_ref + no);
-    srh::DevBuf dc, dj, dth, duo, dx, dW, dV, dX, dZ, dU, dY, dXH, di;
+    srh::DevBuf dc, dj, dth, duo, dx, dW, dV, dX, dZ, dU, dY, dXH, di, dYs, dYu, dPj;
+    ReprojArgs yp{};
+    if (YA) {
+        if ((rc = ssm_loop_stage_Y(who, YA, Yb, yrows, n_o, dYs, yp)) || (rc = dYu.alloc(D * B * nk * no)) || (rc = dPj.alloc(sizeof(int32_t) * B * nk)))
+            return rc;
+        yp.Yu = dYu.as<double>(); yp.proj = dPj.as<int32_t>();
+        lds = ssm_loop_tpwl_lds_bytes(plant->n, plant->m, observer_model->n, n_o, observer_model->ns, true);
+        SRH_REQUIRE(lds <= (size_t)160 * 1024, "%s: the advance kernel needs %zu bytes of LDS (160 KiB available)", who, lds);
+    }
     if ((rc = dc.upload(c.data(), D * c.size())) || (rc = dj.upload(j, sizeof(int32_t) * nk)) || (rc = dth.upload(theta, D * nk)) ||
         (rc = duo.upload(uopt, D * B * N * m)) || (rc = dx.upload(x, D * B * np)) || (W && (rc = dW.upload(W, D * nk * B * np))) ||
         (V && (rc = dV.upload(V, D * nk * B * no))) || (rc = dX.alloc(D * B * nk * np)) || (rc = dZ.alloc(D * B * nk * no)) ||
@@ -618,11 +782,50 @@ int sgusto_ssm_loop_advance_tpwl(stpwl_t *plant, const double *Cm, const double 
     a.x_in = dx.as<double>();
     a.X = dX.as<double>(); a.Z = dZ.as<double>(); a.U = dU.as<double>(); a.Y = dY.as<double>(); a.Xhat = dXH.as<double>(); a.idx = di.as<int32_t>();
     a.rows_x = (int64_t)nk; a.rows_u = (int64_t)nk; a.B = batch;
+    a.Yp_ = yp;
     if ((rc = loop_wait(ssm_loop_launch_tpwl(plant, observer_model, lds, a, nullptr), nullptr))) return rc;
     if ((rc = dX.download(X, D * B * nk * np)) || (rc = dZ.download(Z, D * B * nk * no)) || (rc = dU.download(U, D * B * nk * m)) ||
-        (rc = dY.download(Y, D * B * nk * no)) || (rc = dXH.download(Xhat, D * B * nk * n)) || (rc = di.download(idx, sizeof(int32_t) * B * nk)))
+        (rc = dY.download(Y, D * B * nk * no)) || (rc = dXH.download(Xhat, D * B * nk * n)) || (rc = di.download(idx, sizeof(int32_t) * B * nk)) ||
+        (YA && ((rc = dYu.download(Y_used, D * B * nk * no)) || (rc = dPj.download(proj, sizeof(int32_t) * B * nk)))))
         return rc;
     return SRH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sgusto_ssm_loop_advance(sssm_t *plant, int plant_mode, sssm_t *observer_model, double dt_sim, int N, int n_keep, int64_t batch, const int32_t *j,
+                            const double *theta, const double *xopt, const double *uopt, const double *x, const double *W, const double *V, double *X,
+                            double *Z, double *U, double *Y, double *Xhat) {
+    (void)xopt;                         // (the law u = u_bar(t) has no gain: the plan's states are not read)
+    return ssm_loop_advance("sgusto_ssm_loop_advance", plant, plant_mode, observer_model, dt_sim, N, n_keep, batch, j, theta, uopt, x, W, V, X, Z, U,
+                            Y, Xhat, nullptr, nullptr, 0, nullptr, nullptr);
+}
+
+int sgusto_ssm_loop_advance_reprojected(sssm_t *plant, int plant_mode, sssm_t *observer_model, double dt_sim, int N, int n_keep, int64_t batch,
+                                        const int32_t *j, const double *theta, const double *uopt, const double *x, const double *W, const double *V,
+                                        const double *YA, const double *Yb, int y_rows, double *X, double *Z, double *U, double *Y, double *Xhat,
+                                        double *Y_used, int32_t *proj) {
+    SRH_REQUIRE(YA && Yb && Y_used && proj, "sgusto_ssm_loop_advance_reprojected: null argument");
+    return ssm_loop_advance("sgusto_ssm_loop_advance_reprojected", plant, plant_mode, observer_model, dt_sim, N, n_keep, batch, j, theta, uopt, x, W, V,
+                            X, Z, U, Y, Xhat, YA, Yb, y_rows, Y_used, proj);
+}
+
+int sgusto_ssm_loop_advance_tpwl(stpwl_t *plant, const double *Cm, const double *y_ref, int n_o, sssm_t *observer_model, double dt_sim, int N,
+                                 int n_keep, int64_t batch, const int32_t *j, const double *theta, const double *uopt, const double *x,
+                                 const double *W, const double *V, double *X, double *Z, double *U, double *Y, double *Xhat, int32_t *idx) {
+    return ssm_loop_advance_tpwl("sgusto_ssm_loop_advance_tpwl", plant, Cm, y_ref, n_o, observer_model, dt_sim, N, n_keep, batch, j, theta, uopt, x, W,
+                                 V, X, Z, U, Y, Xhat, idx, nullptr, nullptr, 0, nullptr, nullptr);
+}
+
+int sgusto_ssm_loop_advance_tpwl_reprojected(stpwl_t *plant, const double *Cm, const double *y_ref, int n_o, sssm_t *observer_model, double dt_sim,
+                                             int N, int n_keep, int64_t batch, const int32_t *j, const double *theta, const double *uopt,
+                                             const double *x, const double *W, const double *V, const double *YA, const double *Yb, int y_rows,
+                                             double *X, double *Z, double *U, double *Y, double *Xhat, int32_t *idx, double *Y_used, int32_t *proj) {
+    SRH_REQUIRE(YA && Yb && Y_used && proj, "sgusto_ssm_loop_advance_tpwl_reprojected: null argument");
+    return ssm_loop_advance_tpwl("sgusto_ssm_loop_advance_tpwl_reprojected", plant, Cm, y_ref, n_o, observer_model, dt_sim, N, n_keep, batch, j, theta,
+                                 uopt, x, W, V, X, Z, U, Y, Xhat, idx, YA, Yb, y_rows, Y_used, proj);
 }
 
 }  // extern "C"

@@ -23,11 +23,16 @@
 //                                                                    integer row arithmetic, no interpolation, no gain
 //               2. x_{s+1} = A_p[i] x_s + B_p[i] u_s + d_p[i] (+ w_s), i the plant's nearest point to x_s (THE STEP RULE of tpwl_dev.h)
 //               3. y_{s+1} = (C x_{s+1} + y_ref) + v_s  (measure_row), or y_{s+1} read from the given record Y_plant
+//               3b. with a Y (skoop_loop_set_reproject): a sample outside Y = {y : A y <= b} is replaced by its Euclidean projection
+//                  (koopman.py:150-151; the device function of spoly_project, poly_dev.h), with a plant and in replay alike -- the
+//                  reference's evaluate projects whatever it is handed.  The status word of every sample is recorded (0 inside, 1
+//                  projected, -1 no certified projection, -2 not finite); with -1 and -2 the raw sample is used.  The reset passes y_0
+//                  through the stand-alone entry, the same function; the y_hist rows are taken as given.
 //               4. push (y_{s+1}, u_s) -- with a recorded input: (y_{s+1}, U_applied_s) -- scaled down by the two operations of
-//                  koop_push_kernel into the member's ring; the head advances inside the kernel, the host advances head / count of the
-//                  skoop handle behind the enqueue.
+//                  koop_push_kernel into the member's ring (the sample as used, behind 3b); the head advances inside the kernel, the
+//                  host advances head / count of the skoop handle behind the enqueue.
 // The reference reads its input tape at its own knots, so input_hold changes nothing and is not a parameter.
-// Not offered: the start-up phase before t_delay, the Y= re-projection of the measurement, input clipping, dU, input_nullspace,
+// Not offered: the start-up phase before t_delay, projecting the y_hist rows, input clipping, dU, input_nullspace,
 // nonlinear_observer, weighting-mode plants, the lifted model as its own plant.  The host shell of a handle and of a run is
 // gusto_loop_host.h, the target window gusto_loop_prep.h.
 #include "koopman_host.h"
@@ -114,14 +119,18 @@ struct KlAdvArgs {
     double *U;                          // record (B x rows_u x m): row row0_u + s
     int32_t *idx;                       // (B x n_keep) the plant's point of every sub-step, or null
     int64_t rows_x, row0_x, rows_u, row0_u, B, w_step0;
+    ReprojArgs Yp_;                     // the admissible set Y and the two records of the re-projection (<true> instantiation only)
+    double *yu_out;                     // (B x ny) the last used sample, or null
+    int32_t *pj_out;                    // (B) its status word, or null
 };
 
 // LDS of the launch in doubles: x (np) | u (16) | y (ny) | y_ref (ny) | y_offset, y_factor (ny each) | u_offset, u_factor (16 each) |
 // C (ny x np) | the staged step of tpwl_dev.h: partial sums of A x, B u (256 each), the point (2), the plant's panel A^T, B^T, d.
 // np, ny and ny np are padded to even so that the panel is 16-byte aligned.  Without a plant only u and the scaling vectors are used.
 __host__ __device__ inline int kl_even(int v) { return (v + 1) & ~1; }
-size_t kl_advance_lds_bytes(int np, int m, int ny, bool plant) {
-    const size_t d = (size_t)kl_even(np) + 16 + 4 * (size_t)kl_even(ny) + 2 * 16 + (size_t)kl_even(ny * np);
+// With Y (the <true> instantiation) the launch's LDS starts with wave 0's projection area, reproject_doubles(ny) doubles.
+size_t kl_advance_lds_bytes(int np, int m, int ny, bool plant, bool proj = false) {
+    const size_t d = (size_t)kl_even(np) + 16 + 4 * (size_t)kl_even(ny) + 2 * 16 + (size_t)kl_even(ny * np) + (proj ? reproject_doubles(ny) : 0);
     return srh::lds_request(sizeof(double) * (d + (plant ? tpwl::step_doubles(np, m, 256) + 2 : 0)));
 }
 
@@ -132,10 +141,15 @@ size_t kl_advance_lds_bytes(int np, int m, int ny, bool plant) {
 //   x'    = THE STEP RULE of tpwl_dev.h (+ w)
 //   y_e   = measure_row (gusto_loop_prep.h): (C x')_e + y_ref[e], then + v_e
 //   ring  = (y_e - y_offset[e]) / y_factor[e], (u_e - u_offset[e]) / u_factor[e]    (the two operations of koop_push_kernel)
+// PROJ (the loop has a Y): behind step 3 and one barrier, wave 0 projects the sample onto Y (reproject_sample of gusto_loop_prep.h: the
+// device function of spoly_project, its row of A and b in registers for the whole launch); behind a second barrier step 4 pushes the
+// USED sample.  The raw sample keeps its record, the used one and its status word get theirs; the plant state is never touched.
+// <false> is the kernel as it was: every PROJ part is compiled out.
+template <bool PROJ>
 __global__ __launch_bounds__(256) void koop_loop_advance_kernel(TpwlDev TL, KlAdvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int np = a.np, m = a.m, ny = a.ny, N = a.N, w = ny + m;
-    lptr xc = (lptr)smem;                                // np     plant state
+    lptr xc = (lptr)smem + (PROJ ? reproject_doubles(ny) : 0);     // np     plant state
     lptr uc = xc + kl_even(np);                          // 16     raw input of the sub-step
     lptr yc = uc + 16;                                   // ny     raw measurement
     lptr yr = yc + kl_even(ny);                          // ny     y_ref
@@ -165,6 +179,13 @@ __global__ __launch_bounds__(256) void koop_loop_advance_kernel(TpwlDev TL, KlAd
         for (int e = tid; e < np; e += 256) xc[e] = ((cgptr)a.x_in)[b * np + e];
         for (int e = tid; e < ny; e += 256) yr[e] = ((cgptr)a.yref)[e];
         for (int e = tid; e < ny * np; e += 256) Cl[e] = ((cgptr)a.C)[e];
+    }
+    [[maybe_unused]] ReprojWave yw;
+    [[maybe_unused]] lptr yu = nullptr;
+    [[maybe_unused]] int pj = 0;
+    if constexpr (PROJ) {
+        yu = reproject_used((lptr)smem);
+        if (wave == 0) reproject_load(a.Yp_, ny, lane, yw);
     }
     __syncthreads();
     int cur = -1, head = a.head;
@@ -204,10 +225,28 @@ __global__ __launch_bounds__(256) void koop_loop_advance_kernel(TpwlDev TL, KlAd
             const double v = a.plant ? measure_row(Cl, e, np, xc, yr, Vd, ((size_t)(a.w_step0 + s) * a.B + b) * ny + e) : Yp[rx * ny + e];
             yc[e] = v;
             if (a.Y) ((gptr)a.Y)[rx * ny + e] = v;
-            ring[(size_t)head * w + e] = koop_scale_down(v, yoff[e], yfac[e]);
+            if constexpr (!PROJ) ring[(size_t)head * w + e] = koop_scale_down(v, yoff[e], yfac[e]);
+        }
+        if constexpr (PROJ) {
+            __syncthreads();                             // the sample is complete
+            if (wave == 0) {
+                pj = reproject_sample(yw, a.Yp_.rows, ny, (clptr)yc, yu, (lptr)smem, lane);
+                if (lane == 0 && a.Yp_.proj) ((giptr)a.Yp_.proj)[rx] = pj;
+            }
+            __syncthreads();
+            for (int e = tid; e < ny; e += 256) {        // 4. the used sample into the ring
+                const double v = yu[e];
+                if (a.Yp_.Yu) ((gptr)a.Yp_.Yu)[rx * ny + e] = v;
+                ring[(size_t)head * w + e] = koop_scale_down(v, yoff[e], yfac[e]);
+            }
         }
     }
     __syncthreads();
+    if constexpr (PROJ) {
+        if (a.yu_out)
+            for (int e = tid; e < ny; e += 256) ((gptr)a.yu_out)[b * ny + e] = yu[e];
+        if (a.pj_out && tid == 0) ((giptr)a.pj_out)[b] = pj;
+    }
     if (a.plant && a.x_out)
         for (int e = tid; e < np; e += 256) ((gptr)a.x_out)[b * np + e] = xc[e];
     if (a.y_out)
@@ -228,8 +267,15 @@ struct skoop_loop : LoopCore {
     // the plants and their measurements stand
     srh::DevBuf cst, Ah, Bh, dh, zero, xalt, ualt, zf, xp, ycur;
     LoopRec XLrec, YPd, UAd;            // record: the requests (P x B x n); inputs: recorded measurements (B x (S + 1) x ny), inputs (B x S x m)
+    // the re-projection onto Y (skoop_loop_set_reproject): Y on the host and on the device (A | b), where the used sample and its status
+    // word stand (row 0 of the next run's records), the two records
+    int yrows = 0;
+    size_t lds_proj = 0;
+    std::vector<double> YAh, Ybh;
+    srh::DevBuf Yd, yucur, pjcur;
+    LoopRec YUrec, PJrec;
     __attribute__((always_inline)) skoop_loop() {              // (inlined: no constructor among the library's dynamic symbols)
-        recs.push_back(&XLrec);
+        recs.push_back(&XLrec); recs.push_back(&YUrec); recs.push_back(&PJrec);
         ins.push_back(&YPd); ins.push_back(&UAd);
     }
     ~skoop_loop() {
@@ -245,6 +291,9 @@ struct skoop_loop : LoopCore {
         a.scale = scale();
         a.ring = koop->ring.as<double>();
         a.B = B;
+        if (yrows) {
+            a.Yp_.A = Yd.as<double>(); a.Yp_.b = a.Yp_.A + (size_t)yrows * ny; a.Yp_.rows = yrows;
+        }
         return a;
     }
     KlFixArgs fix_args() const {
@@ -261,7 +310,8 @@ struct skoop_loop : LoopCore {
     }
     // the launch, and behind it the ring's head and count as the n_keep pushes leave them
     int launch_advance(const KlAdvArgs &a) {
-        koop_loop_advance_kernel<<<(unsigned)B, 256, lds, stream>>>(a.plant ? plant->view() : TpwlDev{}, a);
+        if (a.Yp_.rows) koop_loop_advance_kernel<true><<<(unsigned)B, 256, lds_proj, stream>>>(a.plant ? plant->view() : TpwlDev{}, a);
+        else koop_loop_advance_kernel<false><<<(unsigned)B, 256, lds, stream>>>(a.plant ? plant->view() : TpwlDev{}, a);
         SRH_CHECK_HIP(hipGetLastError());
         koop->head = (int)(((int64_t)koop->head + n_keep) % koop->slots);
         koop->count += n_keep;
@@ -307,7 +357,7 @@ int skoop_loop_create(skoop_loop_t **out, skoop_t *koop, const slocp_problem *pr
     int rc;
     if ((rc = slocp_plan_create(&h->qp, prob, B))) return fail(rc);
     const char *what = "set up the advance kernel / the stream";
-    if (hipFuncSetAttribute((const void *)koop_loop_advance_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    if (hipFuncSetAttribute((const void *)koop_loop_advance_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return fail(loop_setup_failed("skoop_loop_create", what));
     const size_t D = sizeof(double), Bz = (size_t)B, Nz = (size_t)N;
     if ((rc = h->setup("skoop_loop_create", what, N, n, m, prob->n_z, B, Ts, dt_sim, n_keep, max_steps_per_run, (size_t)prob->n_z))) return fail(rc);
@@ -315,6 +365,7 @@ int skoop_loop_create(skoop_loop_t **out, skoop_t *koop, const slocp_problem *pr
     h->Xrec.shape(D * std::max(np, 1), 1); h->Wd.shape(D * std::max(np, 1), 0);
     h->Yrec.shape(D * ny, 1); h->Vd.shape(D * ny, 0); h->XLrec.shape(D * n, 0, true);
     h->YPd.shape(D * ny, 1); h->UAd.shape(D * m, 0);
+    h->YUrec.shape(D * ny, 1); h->PJrec.shape(sizeof(int32_t), 1);
     h->yrh.assign((size_t)ny, 0.0);
     h->u0h.assign((size_t)m, 0.0);
     if (plant) {
@@ -381,8 +432,13 @@ int skoop_loop_reset(skoop_loop_t *h, const double *x0, const double *y0, const 
             y[b * ny + e] = v;
         }
     int rc;
+    // with a Y the sample y_0 passes through it like every later one: the stand-alone entry runs the advance kernel's device function
+    std::vector<double> yu(y);
+    std::vector<int32_t> pj(B, 0);
+    if (h->yrows && (rc = spoly_project_status(h->YAh.data(), h->Ybh.data(), h->yrows, (int)ny, y.data(), (int64_t)B, yu.data(), pj.data())))
+        return rc;
     if ((rc = skoop_reset(k))) return rc;
-    // the older samples, oldest first, then (y_0, u_prev0): skoop_push scales them down
+    // the older samples, oldest first (taken as given: Y is not applied to them), then (y_0 as used, u_prev0): skoop_push scales them down
     std::vector<double> yj(B * ny), uj(B * m);
     for (int j = 0; j < k->delay; ++j) {
         for (size_t b = 0; b < B; ++b) {
@@ -393,21 +449,30 @@ int skoop_loop_reset(skoop_loop_t *h, const double *x0, const double *y0, const 
     }
     for (size_t b = 0; b < B; ++b)
         for (size_t e = 0; e < m; ++e) u[b * m + e] = u_prev0 ? u_prev0[b * m + e] : h->u0h[e];
-    if ((rc = skoop_push(k, y.data(), u.data()))) return rc;
+    if ((rc = skoop_push(k, yu.data(), u.data()))) return rc;
     SRH_CHECK_HIP(hipStreamSynchronize(k->stream));
     k->push_pending = false;
     if (h->plant) SRH_CHECK_HIP(hipMemcpy(h->xp.p, x0, D * B * np, hipMemcpyHostToDevice));
     SRH_CHECK_HIP(hipMemcpy(h->ycur.p, y.data(), D * B * ny, hipMemcpyHostToDevice));
+    if (h->yrows) {
+        SRH_CHECK_HIP(hipMemcpy(h->yucur.p, yu.data(), D * B * ny, hipMemcpyHostToDevice));
+        SRH_CHECK_HIP(hipMemcpy(h->pjcur.p, pj.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice));
+    }
     h->t_start = t_start; h->k = 0; h->have_state = true;
     return SRH_OK;
 }
 
-int skoop_loop_run(skoop_loop_t *h, int periods, const double *W, const double *V, const double *Y_plant, const double *U_applied, double *X,
-                   double *Y, double *U, double *Xlift, double *J, int32_t *status, int32_t *iters) {
-    SRH_REQUIRE(h, "skoop_loop_run: null handle");
-    SRH_REQUIRE(periods >= 1, "skoop_loop_run: periods must be positive");
-    SRH_REQUIRE(h->have_state, "skoop_loop_run: no measurement history yet (call skoop_loop_reset first)");
-    SRH_REQUIRE(h->plant || Y_plant, "skoop_loop_run: the loop was created without a plant (replay only): Y_plant is required");
+}  // extern "C"
+
+namespace {
+
+// a run, with the two records of the re-projection when the loop has a Y (Y_used, proj: null without one)
+int koop_loop_run(skoop_loop *h, const char *who, int periods, const double *W, const double *V, const double *Y_plant, const double *U_applied,
+                  double *X, double *Y, double *U, double *Xlift, double *J, int32_t *status, int32_t *iters, double *Y_used, int32_t *proj) {
+    SRH_REQUIRE(periods >= 1, "%s: periods must be positive", who);
+    SRH_REQUIRE(h->have_state, "%s: no measurement history yet (call skoop_loop_reset first)", who);
+    SRH_REQUIRE(h->plant || Y_plant, "%s: the loop was created without a plant (replay only): Y_plant is required", who);
+    h->YUrec.host = Y_used; h->PJrec.host = proj;
     const size_t B = (size_t)h->B;
     const bool replay = Y_plant != nullptr;
     h->Wd.host = (void *)((W && !replay) ? W : nullptr); h->Vd.host = (void *)((V && !replay) ? V : nullptr);
@@ -446,8 +511,58 @@ int skoop_loop_run(skoop_loop_t *h, int periods, const double *W, const double *
         v.x_in = h->xp.as<double>(); v.x_out = h->xp.as<double>(); v.y_out = h->ycur.as<double>();
         v.X = h->Xrec.host ? h->Xrec.as<double>() : nullptr; v.Y = Y ? h->Yrec.as<double>() : nullptr; v.U = U ? h->Urec.as<double>() : nullptr;
         v.rows_x = r.rows_x; v.row0_x = r.row0_x; v.rows_u = r.rows_u; v.row0_u = r.row0_u;
+        v.Yp_.Yu = Y_used ? h->YUrec.as<double>() : nullptr; v.Yp_.proj = proj ? h->PJrec.as<int32_t>() : nullptr;
+        v.yu_out = h->yucur.as<double>(); v.pj_out = h->pjcur.as<int32_t>();
         return h->launch_advance(v);
     });
+}
+
+}  // namespace
+
+extern "C" {
+
+int skoop_loop_run(skoop_loop_t *h, int periods, const double *W, const double *V, const double *Y_plant, const double *U_applied, double *X,
+                   double *Y, double *U, double *Xlift, double *J, int32_t *status, int32_t *iters) {
+    SRH_REQUIRE(h, "skoop_loop_run: null handle");
+    return koop_loop_run(h, "skoop_loop_run", periods, W, V, Y_plant, U_applied, X, Y, U, Xlift, J, status, iters, nullptr, nullptr);
+}
+
+int skoop_loop_run_reprojected(skoop_loop_t *h, int periods, const double *W, const double *V, const double *Y_plant, const double *U_applied,
+                               double *X, double *Y, double *U, double *Xlift, double *J, int32_t *status, int32_t *iters, double *Y_used,
+                               int32_t *proj) {
+    SRH_REQUIRE(h, "skoop_loop_run_reprojected: null handle");
+    SRH_REQUIRE(h->yrows, "skoop_loop_run_reprojected: the loop has no Y (skoop_loop_set_reproject)");
+    return koop_loop_run(h, "skoop_loop_run_reprojected", periods, W, V, Y_plant, U_applied, X, Y, U, Xlift, J, status, iters, Y_used, proj);
+}
+
+int skoop_loop_set_reproject(skoop_loop_t *h, const double *A, const double *b, int rows) {
+    SRH_REQUIRE(h, "skoop_loop_set_reproject: null handle");
+    SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
+    h->have_state = false;               // the first sample of the ring was pushed under the previous rule: a reset states it anew
+    if (!A || !b) {
+        h->yrows = 0;
+        return SRH_OK;
+    }
+    const int ny = h->ny;
+    SRH_REQUIRE(ny <= poly::PN && rows > 0 && rows <= poly::PM,
+                "skoop_loop_set_reproject: Y needs n_y <= 16 and 0 < rows <= 64 (got n_y = %d, rows = %d)", ny, rows);
+    for (int i = 0; i < rows * ny; ++i) SRH_REQUIRE(std::isfinite(A[i]), "skoop_loop_set_reproject: Y is not finite (A, row %d)", i / ny);
+    for (int i = 0; i < rows; ++i) SRH_REQUIRE(std::isfinite(b[i]), "skoop_loop_set_reproject: Y is not finite (b, row %d)", i);
+    const size_t lds = kl_advance_lds_bytes(h->np, h->m, ny, h->plant != nullptr, true);
+    SRH_REQUIRE(lds <= (size_t)160 * 1024, "skoop_loop_set_reproject: the advance kernel needs %zu bytes of LDS (160 KiB available)", lds);
+    if (hipFuncSetAttribute((const void *)koop_loop_advance_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return loop_setup_failed("skoop_loop_set_reproject", "set up the advance kernel");
+    std::vector<double> c(A, A + (size_t)rows * ny);
+    c.insert(c.end(), b, b + rows);
+    const size_t D = sizeof(double), B = (size_t)h->B;
+    int rc;
+    if ((rc = h->Yd.upload(c.data(), D * c.size())) || (rc = h->yucur.alloc(D * B * ny)) || (rc = h->pjcur.alloc(sizeof(int32_t) * B)) ||
+        (!h->YUrec.d.p && (rc = h->alloc_recs({&h->YUrec, &h->PJrec}))))
+        return rc;
+    h->YAh.assign(A, A + (size_t)rows * ny); h->Ybh.assign(b, b + rows);
+    h->YUrec.row0 = h->yucur.p; h->PJrec.row0 = h->pjcur.p;
+    h->lds_proj = lds; h->yrows = rows;
+    return SRH_OK;
 }
 
 int skoop_loop_last_inputs(skoop_loop_t *h, double *x0, double *z, double *zf, double *u_des) {
@@ -483,18 +598,22 @@ int skoop_loop_fixup(skoop_loop_t *h, const double *xopt_prev, const double *uop
     return SRH_OK;
 }
 
-int skoop_loop_advance(skoop_loop_t *h, const double *uopt, const double *x, const double *W, const double *V, const double *Y_plant,
-                       const double *U_applied, double *X, double *Y, double *U, int32_t *idx) {
-    SRH_REQUIRE(h && uopt && Y && U && idx, "skoop_loop_advance: null argument");
-    SRH_REQUIRE(h->plant || Y_plant, "skoop_loop_advance: the loop was created without a plant (replay only): Y_plant is required");
-    SRH_REQUIRE(Y_plant || (x && X), "skoop_loop_advance: a stepped plant needs its states x and the record X");
+}  // extern "C"
+
+namespace {
+
+int koop_loop_advance(skoop_loop *h, const char *who, const double *uopt, const double *x, const double *W, const double *V, const double *Y_plant,
+                      const double *U_applied, double *X, double *Y, double *U, int32_t *idx, double *Y_used, int32_t *proj) {
+    SRH_REQUIRE(h->plant || Y_plant, "%s: the loop was created without a plant (replay only): Y_plant is required", who);
+    SRH_REQUIRE(Y_plant || (x && X), "%s: a stepped plant needs its states x and the record X", who);
     const size_t D = sizeof(double), B = (size_t)h->B, N = h->N, m = h->m, ny = h->ny, np = h->np, nk = h->n_keep;
     const bool replay = Y_plant != nullptr;
     SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
     SRH_CHECK_HIP(hipStreamSynchronize(h->koop->stream));
     h->have_state = false;               // the ring moves on, the loop's plant state and measurement do not
     int rc;
-    srh::DevBuf duo, dx, dW, dV, dYp, dUa, dX, dY, dU, di;
+    srh::DevBuf duo, dx, dW, dV, dYp, dUa, dX, dY, dU, di, dYu, dPj;
+    if ((Y_used && (rc = dYu.alloc(D * B * (nk + 1) * ny))) || (proj && (rc = dPj.alloc(sizeof(int32_t) * B * (nk + 1))))) return rc;
     // X, Y and Y_plant carry a row in front (row 0: where the launch starts), as the records of a run do; it is not copied back
     if ((rc = duo.upload(uopt, D * B * N * m)) || (!replay && (rc = dx.upload(x, D * B * np))) ||
         (W && !replay && (rc = dW.upload(W, D * nk * B * np))) || (V && !replay && (rc = dV.upload(V, D * nk * B * ny))) ||
@@ -511,6 +630,7 @@ int skoop_loop_advance(skoop_loop_t *h, const double *uopt, const double *x, con
     v.x_in = dx.as<double>();
     v.X = replay ? nullptr : dX.as<double>(); v.Y = dY.as<double>(); v.U = dU.as<double>(); v.idx = di.as<int32_t>();
     v.rows_x = (int64_t)nk + 1; v.row0_x = 1; v.rows_u = (int64_t)nk; v.row0_u = 0;
+    v.Yp_.Yu = Y_used ? dYu.as<double>() : nullptr; v.Yp_.proj = proj ? dPj.as<int32_t>() : nullptr;
     if ((rc = loop_wait(h->launch_advance(v), h->stream))) return rc;
     // rows 1 .. n_keep of the n_keep + 1 row blocks -> the caller's (B x n_keep x .) arrays
     std::vector<double> blk;
@@ -521,9 +641,31 @@ int skoop_loop_advance(skoop_loop_t *h, const double *uopt, const double *x, con
         return e;
     };
     if ((!replay && (rc = rows(dX, X, np))) || (rc = rows(dY, Y, ny)) || (rc = dU.download(U, D * B * nk * m)) ||
-        (rc = di.download(idx, sizeof(int32_t) * B * nk)))
+        (rc = di.download(idx, sizeof(int32_t) * B * nk)) || (Y_used && (rc = rows(dYu, Y_used, ny))))
         return rc;
+    if (proj) {
+        std::vector<int32_t> w(B * (nk + 1));
+        if ((rc = dPj.download(w.data(), sizeof(int32_t) * w.size()))) return rc;
+        for (size_t b = 0; b < B; ++b) std::copy(w.begin() + b * (nk + 1) + 1, w.begin() + (b + 1) * (nk + 1), proj + b * nk);
+    }
     return SRH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int skoop_loop_advance(skoop_loop_t *h, const double *uopt, const double *x, const double *W, const double *V, const double *Y_plant,
+                       const double *U_applied, double *X, double *Y, double *U, int32_t *idx) {
+    SRH_REQUIRE(h && uopt && Y && U && idx, "skoop_loop_advance: null argument");
+    return koop_loop_advance(h, "skoop_loop_advance", uopt, x, W, V, Y_plant, U_applied, X, Y, U, idx, nullptr, nullptr);
+}
+
+int skoop_loop_advance_reprojected(skoop_loop_t *h, const double *uopt, const double *x, const double *W, const double *V, const double *Y_plant,
+                                   const double *U_applied, double *X, double *Y, double *U, int32_t *idx, double *Y_used, int32_t *proj) {
+    SRH_REQUIRE(h && uopt && Y && U && idx && Y_used && proj, "skoop_loop_advance_reprojected: null argument");
+    SRH_REQUIRE(h->yrows, "skoop_loop_advance_reprojected: the loop has no Y (skoop_loop_set_reproject)");
+    return koop_loop_advance(h, "skoop_loop_advance_reprojected", uopt, x, W, V, Y_plant, U_applied, X, Y, U, idx, Y_used, proj);
 }
 
 }  // extern "C"

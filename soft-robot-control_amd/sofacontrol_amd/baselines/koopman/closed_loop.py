@@ -16,10 +16,16 @@ controller steps, n_keep = rollout_horizon r sub-steps; period p starts at t_p =
              input row.  The status is recorded either way.
   sub-steps  u_s = scale_up(uopt[s // r]); x_{s+1} = A_p[i] x_s + B_p[i] u_s + d_p[i] (+ w_s), i the plant's nearest point to x_s;
              y_{s+1} = (C x_{s+1} + y_ref) + v_s, or read from Y_plant; push (y_{s+1}, u_s) -- or (y_{s+1}, U_applied_s) -- into the ring.
+  Y          the Y= re-projection of the measurement: behind set_reproject(Polyhedron(A, b, with_reproject=True)) every sample -- y_0 of the reset, every y_{s+1}, stepped or replayed -- that lies
+             outside Y is replaced by its Euclidean projection before it enters the ring (koopman.py:150-151), inside the advance kernel,
+             by the device function behind Polyhedron.project_to_polyhedron: the same bits.  The result's `y` stays the raw sample,
+             `y_used` is what the ring received and `proj` its status word: 0 inside (bit for bit), 1 projected, -1 no certified
+             projection (an empty Y), -2 the sample is not finite; with -1 and -2 the raw sample is used and the run goes on.  The
+             y_hist rows are taken as given.  The plant is never touched.
 The reference reads its input tape at its own knots, so input_hold changes nothing and is not a parameter.
 
-Not offered: the start-up phase before t_delay (the reset states the history at the first solve), the Y= re-projection of the
-measurement, input clipping, dU, input_nullspace, nonlinear_observer, weighting-mode plants, the lifted model as its own plant."""
+Not offered: the start-up phase before t_delay (the reset states the history at the first solve), projecting the y_hist rows,
+input clipping, dU, input_nullspace, nonlinear_observer, weighting-mode plants, the lifted model as its own plant."""
 import ctypes as C_          # (C is the plant's measurement matrix in this module)
 
 import numpy as np
@@ -31,7 +37,10 @@ from ...scp.closed_loop import _LoopBatch, _ptr, schedule
 class KoopmanLoopResult:
     """Records of one `run` with S = periods n_keep: x (B, S + 1, n_plant) or None, y (B, S + 1, n_y) -- row 0 where the run started --,
     u (B, S, n_u), all raw; x_lift (periods, B, n_lift) the requests; iters, status, J (periods, B) of the solves; t (S + 1,) the times
-    of the rows."""
+    of the rows.  With a Y: y_used (B, S + 1, n_y) the samples as the ring received them and proj (B, S + 1) int32 their status words
+    (0 inside, 1 projected, -1 no certified projection, -2 not finite); both None without one."""
+
+    y_used = proj = None
 
     def __init__(self, x, y, u, x_lift, iters, status, J, t):
         self.x, self.y, self.u, self.x_lift = x, y, u, x_lift
@@ -48,7 +57,8 @@ class KoopmanClosedLoopBatch(_LoopBatch):
         y = C x + y_ref (C (n_y, n_plant), n_y the model's n), or None: replay only (run(Y_plant=...)).  rollout_horizon: controller
         steps per period.  t (T,), z (T, n_y), u (T, n_u) or (n_u,): the target table in the QP's scaled units; phase (B,): a time offset
         of every loop's target.  u0 (n_u) raw: the idle input (a failed first solve, and u_prev0 of a reset without one).  The loop owns
-        its lift handle and so its measurement history."""
+        its lift handle and so its measurement history.  The admissible set of the measurements is set behind the constructor:
+        set_reproject(Y)."""
         from ...scp.locp import make_problem
         name = type(self).__name__
         if dU is not None:
@@ -173,13 +183,18 @@ class KoopmanClosedLoopBatch(_LoopBatch):
         stepped = self.plant is not None and Y_plant is None
         r = dict(x=f64(B, S + 1, self.n_plant) if fits and record_x and stepped else None, y=f64(B, S + 1, self.n_y), u=f64(B, S, self.n_u),
                  x_lift=f64(periods, B, self.n_x), J=f64(periods, B), status=i32(), iters=i32())
+        if self._Y is not None:
+            r.update(y_used=f64(B, S + 1, self.n_y), proj=np.empty((B, S + 1) if fits else 1, dtype=np.int32))
         if not fits:                                              # (refused by the library, with its message: it is handed dummies)
             W = V = U_applied = None
             Y_plant = None if Y_plant is None else np.empty(1)
-        self._call('_run', C_.c_int(periods), *[_ptr(a) for a in [W, V, Y_plant, U_applied] + list(r.values())])
+        self._call('_run' if self._Y is None else '_run_reprojected', C_.c_int(periods),
+                   *[_ptr(a) for a in [W, V, Y_plant, U_applied] + list(r.values())])
         t = schedule(self.N, self.dt, self.dt_sim, nk, self.t_start, self._k).t_k + self.dt_sim * np.arange(S + 1)
         self._k += periods
-        return KoopmanLoopResult(r['x'], r['y'], r['u'], r['x_lift'], r['iters'], r['status'], r['J'], t)
+        res = KoopmanLoopResult(r['x'], r['y'], r['u'], r['x_lift'], r['iters'], r['status'], r['J'], t)
+        res.y_used, res.proj = r.get('y_used'), r.get('proj')
+        return res
 
     def step(self, W=None, V=None, Y_plant=None, U_applied=None, record_x=True):
         return self.run(1, W=W, V=V, Y_plant=Y_plant, U_applied=U_applied, record_x=record_x)
@@ -210,7 +225,8 @@ class KoopmanClosedLoopBatch(_LoopBatch):
         """The advance kernel alone (for tests): plans uopt (B, N, n_u), plant states x (B, n_plant), W (n_keep, B, n_plant), V (n_keep,
         B, n_y), Y_plant (B, n_keep + 1, n_y), U_applied (B, n_keep, n_u) -> dict X (B, n_keep, n_plant; None in replay) and Y after
         every sub-step, U and the plant's points idx (B, n_keep; -1 in replay) of every sub-step.  The samples go into the loop's own
-        ring as it stands; the loop needs a reset before its next run."""
+        ring as it stands; the loop needs a reset before its next run.  With a Y also Y_used (B, n_keep, n_y), the samples as the ring
+        received them, and proj (B, n_keep) int32, their status words."""
         B, N, nk = self.B, self.N, self.n_keep
         f = lambda a, *shape: None if a is None else _lib.f64(np.asarray(a).reshape(shape))
         uopt, x = f(uopt, B, N, self.n_u), f(x, B, self.n_plant)
@@ -218,6 +234,9 @@ class KoopmanClosedLoopBatch(_LoopBatch):
         Y_plant, U_applied = f(Y_plant, B, nk + 1, self.n_y), f(U_applied, B, nk, self.n_u)
         r = dict(X=None if Y_plant is not None else np.empty((B, nk, self.n_plant)), Y=np.empty((B, nk, self.n_y)),
                  U=np.empty((B, nk, self.n_u)), idx=np.empty((B, nk), dtype=np.int32))
+        if self._Y is not None:
+            r.update(Y_used=np.empty((B, nk, self.n_y)), proj=np.empty((B, nk), dtype=np.int32))
         self._k = None
-        self._call('_advance', *[_ptr(a) for a in [uopt, x, W, V, Y_plant, U_applied] + list(r.values())])
+        self._call('_advance' if self._Y is None else '_advance_reprojected',
+                   *[_ptr(a) for a in [uopt, x, W, V, Y_plant, U_applied] + list(r.values())])
         return r

@@ -44,6 +44,10 @@ class ClosedLoopResult:
     """Records of one `run`: x (B, S + 1, n_x) or None, z (B, S + 1, n_z), u (B, S, n_u) with S = periods n_keep (row 0: the state the run
     started from); iters, status, J (periods, B) of the solves; t (S + 1,) the times of the rows."""
 
+    # a loop with a Y (SSMClosedLoopBatch.set_reproject; None without one): y_used (B, S + 1, n_o) the measurements as the observer map read
+    # them, proj (B, S + 1) int32 their status words: 0 inside Y, 1 projected, -1 no certified projection, -2 not finite
+    y_used = proj = None
+
     def __init__(self, x, z, u, iters, status, J, t, x_hat=None, y=None, ekf_status=None):
         self.x, self.z, self.u, self.iters, self.status, self.J, self.t = x, z, u, iters, status, J, t
         # the observed loop (None without an observer): x_hat (B, S + 1, n_x) the estimates, row 0 those the run started from; y (B, S,
@@ -79,6 +83,51 @@ class _LoopBatch:
         self.has_z, self.has_u = z is not None, u is not None
         self.t_start, self._k = 0.0, None
         self._h = C.c_void_p()
+
+    @classmethod
+    def _check_reproject(cls, Y, n_y):
+        """The admissible set of the measurements as the advance kernels take it: (A (rows, n_y), b (rows,)) of a
+        Polyhedron(with_reproject=True), or None.  Everything else is refused here, before any device call."""
+        if Y is None:
+            return None
+        from ..utils import Polyhedron
+        name = cls.__name__
+        if not isinstance(Y, Polyhedron):
+            raise RuntimeError('%s: Y must be a Polyhedron(A, b, with_reproject=True), got %s' % (name, type(Y).__name__))
+        if not Y.with_reproject:
+            raise RuntimeError('%s: Y was made without with_reproject=True: the reference refuses to project onto it '
+                               '(Polyhedron(A, b, with_reproject=True))' % name)
+        A, b = np.asarray(Y.A, dtype=np.float64), np.asarray(Y.b, dtype=np.float64).reshape(-1)
+        if A.ndim != 2 or A.shape[1] != n_y or A.shape[0] != b.shape[0]:
+            raise RuntimeError('%s: Y needs A of shape (rows, n_y = %d) and b of rows entries, got A %s and b %s'
+                               % (name, n_y, A.shape, b.shape))
+        if n_y > 16 or A.shape[0] > 64 or A.shape[0] < 1:
+            raise RuntimeError('%s: the re-projection onto Y is limited to n_y <= 16 and 1 <= rows <= 64 (got n_y = %d, rows = %d)'
+                               % (name, n_y, A.shape[0]))
+        if not (np.isfinite(A).all() and np.isfinite(b).all()):
+            bad = int(np.argmax(~(np.isfinite(A).all(axis=1) & np.isfinite(b))))
+            raise RuntimeError('%s: Y is not finite (row %d of A or b holds a NaN or an Inf)' % (name, bad))
+        return _lib.f64(A), _lib.f64(b)
+
+    _Y = None                                                      # (A, b) of the admissible set of the measurements, or None
+    _n_meas = 'n_y'                                                # the attribute that holds the measurement's dimension
+
+    def set_reproject(self, Y):
+        """The admissible set of the measurements (the reference's `Y=` of KoopmanMPC and of the SSM scp controller): from the next reset on
+        every measurement outside Y is replaced by its Euclidean projection before the controller reads it, inside the advance kernel.
+        Y: a Polyhedron(A, b, with_reproject=True) in the raw measurement's coordinates, at most 16 dimensions and 64 rows; None removes
+        it.  Refused by name, with the numbers, before any device call.  The loop needs a reset behind it.  Returns the loop."""
+        Yab = self._check_reproject(Y, int(getattr(self, self._n_meas)))
+        self._check_reproject_allowed(Yab)
+        if Yab is None:
+            self._call('_set_reproject', None, None, C.c_int(0))
+        else:
+            self._call('_set_reproject', _lib.dptr(Yab[0]), _lib.dptr(Yab[1]), C.c_int(Yab[0].shape[0]))
+        self._Y, self._k = Yab, None
+        return self
+
+    def _check_reproject_allowed(self, Yab):
+        pass
 
     def _call(self, entry, *args):
         _lib.check(getattr(_lib.lib(), self._sym + entry)(self._h, *args), self._sym + entry)
@@ -122,7 +171,9 @@ class _LoopBatch:
         self._call(entry, C.c_int(periods), *[_ptr(a) for a in arrays])
         t = schedule(self.N, self.dt, self.dt_sim, self.n_keep, self.t_start, self._k).t_k + self.dt_sim * np.arange(periods * self.n_keep + 1)
         self._k += periods
-        return ClosedLoopResult(r['x'], r['z'], r['u'], r['iters'], r['status'], r['J'], t, x_hat=r.get('x_hat'), y=r.get('y'), ekf_status=r.get('ekf_status'))
+        res = ClosedLoopResult(r['x'], r['z'], r['u'], r['iters'], r['status'], r['J'], t, x_hat=r.get('x_hat'), y=r.get('y'), ekf_status=r.get('ekf_status'))
+        res.y_used, res.proj = r.get('y_used'), r.get('proj')
+        return res
 
     def step(self):
         return self.run(1)

@@ -8,7 +8,13 @@ the handle's stream and ONE host wait; only the records of the run cross PCIe.  
 `closed_loop.schedule`.
 
 The plant may also be a nearest-point TPWL model of more states than the SSM model, of which the controller sees only the measured tip
-y = (C x + y_ref) + v (the reference's drivers): `SSMClosedLoopBatch.on_plant(..., C=, y_ref=)`, `advance_tpwl`."""
+y = (C x + y_ref) + v (the reference's drivers): `SSMClosedLoopBatch.on_plant(..., C=, y_ref=)`, `advance_tpwl`.
+
+Behind `set_reproject(Polyhedron(A, b, with_reproject=True))` (either plant kind) every measurement that lies outside Y -- the reset's first one included
+-- is replaced by its Euclidean projection before the observer map reads it (SSM/controllers.py:96-97), inside the advance kernel, by the
+device function behind Polyhedron.project_to_polyhedron: the same bits.  The result's `y` stays the raw measurement, `y_used` is what the
+map read and `proj` its status word: 0 inside (bit for bit), 1 projected, -1 no certified projection (an empty Y), -2 the sample is not
+finite; with -1 and -2 the raw sample is used and the run goes on."""
 import ctypes
 import ctypes as C
 
@@ -38,7 +44,8 @@ class SSMClosedLoopBatch(_LoopBatch):
         map); n_keep: plant steps per period.  t (T,), z (T, n_z), u (T, n_u): the target table, z in the shifted coordinates the solver
         takes (zfyf_to_zy); phase (B,): a time offset of every loop's target.  observe: plans start from the estimate (True, the
         reference's loop) or from the plant state (False, perfect state feedback); the measurement and the estimate are recorded either
-        way.  max_steps_per_run: the longest run in plant steps (sizes the record blocks; default 16 periods).
+        way.  max_steps_per_run: the longest run in plant steps (sizes the record blocks; default 16 periods).  The admissible set of
+        the measurements is set behind the constructor: set_reproject(Y) (refused with observe=False: no measurement is read there).
         A nearest-point TPWL plant needs its measurement as well: SSMClosedLoopBatch.on_plant(..., C=, y_ref=)."""
         self._build(gusto, plant, dt_sim, n_keep, t, z, u, phase, observe, max_steps_per_run, None, None)
 
@@ -53,6 +60,13 @@ class SSMClosedLoopBatch(_LoopBatch):
         self = cls.__new__(cls)
         self._build(gusto, plant, dt_sim, n_keep, t, z, u, phase, observe, max_steps_per_run, C, y_ref)
         return self
+
+    _n_meas = 'n_o'
+
+    def _check_reproject_allowed(self, Yab):
+        if Yab is not None and not self.observe:
+            raise RuntimeError('SSMClosedLoopBatch: Y together with observe=False is refused: the plans start from the plant state, no '
+                               'measurement is read, a Y would change nothing')
 
     def _build(self, gusto, plant, dt_sim, n_keep, t, z, u, phase, observe, max_steps_per_run, Cm, y_ref):
         if not getattr(gusto, '_ssm', False):
@@ -132,7 +146,7 @@ class SSMClosedLoopBatch(_LoopBatch):
         """`periods` periods from where the last run ended.  W (periods, n_keep, B, n_x): added to the plant's next state; V (periods,
         n_keep, B, n_o): added to the measurement.  Returns a ClosedLoopResult with x (B, S + 1, n_x) or None, z, y (B, S + 1, n_o),
         x_hat (B, S + 1, n_x), u (B, S, n_u), S = periods n_keep, row 0 where the run started; iters, status, J (periods, B); t.
-        On a TPWL plant W and x have n_plant columns."""
+        On a TPWL plant W and x have n_plant columns.  With a Y also y_used (B, S + 1, n_o) and proj (B, S + 1) int32 (y stays raw)."""
         periods = int(periods)
         if self.n_plant is not None:
             W = self._shaped('W (periods, n_keep, B, n_plant)', W, (periods, self.n_keep, self.B, self.n_plant))
@@ -144,13 +158,29 @@ class SSMClosedLoopBatch(_LoopBatch):
             r['x'] = np.empty((self.B, periods * self.n_keep + 1, self.n_plant))
         if not fits:
             W = V = None
-        return self._run('_run', periods, [W, V] + [r[k] for k in ('x', 'z', 'u', 'y', 'x_hat', 'iters', 'status', 'J')], r)
+        names = ('x', 'z', 'u', 'y', 'x_hat', 'iters', 'status', 'J')
+        if self._Y is not None:
+            S = periods * self.n_keep
+            r['y_used'] = np.empty((self.B, S + 1, self.n_o) if fits else 1)
+            r['proj'] = np.empty((self.B, S + 1) if fits else 1, dtype=np.int32)
+            return self._run('_run_reprojected', periods, [W, V] + [r[k] for k in names + ('y_used', 'proj')], r)
+        return self._run('_run', periods, [W, V] + [r[k] for k in names], r)
 
 
-def advance(plant, observer_model, dt_sim, N, j, theta, uopt, x, W=None, V=None, xopt=None):
+def _Y_arrays(who, Y, n_o):
+    """(A, b, rows) of a Y handed to a stand-alone advance entry, checked as the loops check it."""
+    class _Named(_LoopBatch):
+        pass
+    _Named.__name__ = who
+    A, b = _Named._check_reproject(Y, int(n_o))
+    return A, b, A.shape[0]
+
+
+def advance(plant, observer_model, dt_sim, N, j, theta, uopt, x, W=None, V=None, xopt=None, Y=None):
     """sgusto_ssm_loop_advance: the advance kernel alone on host arrays, without a plan or a loop (for tests).  plant, observer_model:
     SSMDynamics; j, theta (n_keep): the schedule; uopt (B, N, n_u), x (B, n_x), W (n_keep, B, n_x), V (n_keep, B, n_o) ->
-    dict X, Xhat (B, n_keep, n_x), Z, Y (B, n_keep, n_o), U (B, n_keep, n_u)."""
+    dict X, Xhat (B, n_keep, n_x), Z, Y (B, n_keep, n_o), U (B, n_keep, n_u).  With Y (a Polyhedron(with_reproject=True)) the
+    measurements pass through it (sgusto_ssm_loop_advance_reprojected): also Y_used (B, n_keep, n_o) and proj (B, n_keep) int32."""
     uopt = _lib.f64(np.asarray(uopt))
     B, n, m, no, nk = uopt.shape[0], plant.state_dim, plant.input_dim, plant.output_dim, len(j)
     uopt = _lib.f64(uopt.reshape(B, N, m)); x = _lib.f64(np.asarray(x).reshape(B, n))
@@ -158,6 +188,15 @@ def advance(plant, observer_model, dt_sim, N, j, theta, uopt, x, W=None, V=None,
     W = None if W is None else _lib.f64(np.asarray(W).reshape(nk, B, n))
     V = None if V is None else _lib.f64(np.asarray(V).reshape(nk, B, no))
     j = np.ascontiguousarray(j, dtype=np.int32); theta = _lib.f64(np.asarray(theta).reshape(nk))
+    if Y is not None:
+        YA, Yb, yrows = _Y_arrays('advance', Y, no)
+        X, Xh, Z, Ym, U = np.empty((B, nk, n)), np.empty((B, nk, n)), np.empty((B, nk, no)), np.empty((B, nk, no)), np.empty((B, nk, m))
+        Yu, pj = np.empty((B, nk, no)), np.empty((B, nk), dtype=np.int32)
+        _lib.check(_lib.lib().sgusto_ssm_loop_advance_reprojected(
+            plant.handle, C.c_int(_plant_mode(plant)), observer_model.handle, C.c_double(float(dt_sim)), C.c_int(int(N)), C.c_int(nk), C.c_int64(B),
+            _lib.iptr(j), _lib.dptr(theta), _lib.dptr(uopt), _lib.dptr(x), _lib.dptr(W), _lib.dptr(V), _lib.dptr(YA), _lib.dptr(Yb), C.c_int(yrows),
+            _lib.dptr(X), _lib.dptr(Z), _lib.dptr(U), _lib.dptr(Ym), _lib.dptr(Xh), _lib.dptr(Yu), _lib.iptr(pj)), 'sgusto_ssm_loop_advance_reprojected')
+        return dict(X=X, Z=Z, U=U, Y=Ym, Xhat=Xh, Y_used=Yu, proj=pj)
     X, Xh, Z, Y, U = np.empty((B, nk, n)), np.empty((B, nk, n)), np.empty((B, nk, no)), np.empty((B, nk, no)), np.empty((B, nk, m))
     _lib.check(_lib.lib().sgusto_ssm_loop_advance(plant.handle, C.c_int(_plant_mode(plant)), observer_model.handle, C.c_double(float(dt_sim)),
                                                   C.c_int(int(N)), C.c_int(nk), C.c_int64(B), _lib.iptr(j), _lib.dptr(theta), _lib.dptr(xopt),
@@ -166,12 +205,24 @@ def advance(plant, observer_model, dt_sim, N, j, theta, uopt, x, W=None, V=None,
     return dict(X=X, Z=Z, U=U, Y=Y, Xhat=Xh)
 
 
+def advance_tpwl_reprojected(plant, C, y_ref, observer_model, dt_sim, N, j, theta, uopt, x, Y, W=None, V=None):
+    """advance_tpwl with the admissible set Y of the measurements (sgusto_ssm_loop_advance_tpwl_reprojected): also Y_used (B, n_keep, n_o)
+    and proj (B, n_keep) int32."""
+    return _advance_tpwl(plant, C, y_ref, observer_model, dt_sim, N, j, theta, uopt, x, W, V, Y)
+
+
 def advance_tpwl(plant, C, y_ref, observer_model, dt_sim, N, j, theta, uopt, x, W=None, V=None):
+    """sgusto_ssm_loop_advance_tpwl: the TPWL-plant advance kernel alone on host arrays (for tests; the arrays are those of _advance_tpwl)."""
+    return _advance_tpwl(plant, C, y_ref, observer_model, dt_sim, N, j, theta, uopt, x, W, V, None)
+
+
+def _advance_tpwl(plant, C, y_ref, observer_model, dt_sim, N, j, theta, uopt, x, W, V, Y):
     """sgusto_ssm_loop_advance_tpwl: the TPWL-plant advance kernel alone on host arrays, without a plan or a loop (for tests).  plant: a
     nearest-point TPWLATV (its handle_for(dt_sim)); C (n_o, n_plant), y_ref (n_o,): its measurement; observer_model: the SSMDynamics
     whose V and z_ref form x_hat; j, theta (n_keep): the schedule; uopt (B, N, n_u), x (B, n_plant), W (n_keep, B, n_plant), V (n_keep, B,
     n_o) -> dict X (B, n_keep, n_plant), Z, Y (B, n_keep, n_o), U (B, n_keep, n_u), Xhat (B, n_keep, n_x), idx (B, n_keep) int32: the
-    plant's point of every sub-step."""
+    plant's point of every sub-step.  With Y (a Polyhedron(with_reproject=True)): also Y_used (B, n_keep, n_o), proj (B, n_keep) int32."""
+    admissible = Y                                                 # (Y names the measurement record below)
     uopt = _lib.f64(np.asarray(uopt))
     C = _lib.f64(np.asarray(C))
     B, n_p, m, n, nk = uopt.shape[0], int(plant.get_state_dim()), int(plant.get_input_dim()), observer_model.state_dim, len(j)
@@ -185,6 +236,15 @@ def advance_tpwl(plant, C, y_ref, observer_model, dt_sim, N, j, theta, uopt, x, 
     j = np.ascontiguousarray(j, dtype=np.int32); theta = _lib.f64(np.asarray(theta).reshape(nk))
     X, Xh, Z, Y, U = np.empty((B, nk, n_p)), np.empty((B, nk, n)), np.empty((B, nk, no)), np.empty((B, nk, no)), np.empty((B, nk, m))
     idx = np.empty((B, nk), dtype=np.int32)
+    if admissible is not None:
+        YA, Yb, yrows = _Y_arrays('advance_tpwl', admissible, no)
+        Ym, Yu, pj = np.empty((B, nk, no)), np.empty((B, nk, no)), np.empty((B, nk), dtype=np.int32)
+        _lib.check(_lib.lib().sgusto_ssm_loop_advance_tpwl_reprojected(
+            plant.handle_for(float(dt_sim)), _lib.dptr(C), _lib.dptr(y_ref), ctypes.c_int(no), observer_model.handle, ctypes.c_double(float(dt_sim)),
+            ctypes.c_int(int(N)), ctypes.c_int(nk), ctypes.c_int64(B), _lib.iptr(j), _lib.dptr(theta), _lib.dptr(uopt), _lib.dptr(x), _lib.dptr(W),
+            _lib.dptr(V), _lib.dptr(YA), _lib.dptr(Yb), ctypes.c_int(yrows), _lib.dptr(X), _lib.dptr(Z), _lib.dptr(U), _lib.dptr(Ym), _lib.dptr(Xh),
+            _lib.iptr(idx), _lib.dptr(Yu), _lib.iptr(pj)), 'sgusto_ssm_loop_advance_tpwl_reprojected')
+        return dict(X=X, Z=Z, U=U, Y=Ym, Xhat=Xh, idx=idx, Y_used=Yu, proj=pj)
     _lib.check(_lib.lib().sgusto_ssm_loop_advance_tpwl(plant.handle_for(float(dt_sim)), _lib.dptr(C), _lib.dptr(y_ref), ctypes.c_int(no),
                                                        observer_model.handle, ctypes.c_double(float(dt_sim)), ctypes.c_int(int(N)), ctypes.c_int(nk), ctypes.c_int64(B),
                                                        _lib.iptr(j), _lib.dptr(theta), _lib.dptr(uopt), _lib.dptr(x), _lib.dptr(W), _lib.dptr(V),

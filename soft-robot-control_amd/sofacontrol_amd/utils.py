@@ -85,6 +85,24 @@ class Polyhedron:
                                             _lib.dptr(X), C.c_int64(X.shape[0]), _lib.dptr(out)), 'spoly_project')
         return out[0] if np.ndim(x) == 1 else out
 
+    def project_with_status(self, x):
+        """project_to_polyhedron for a batch that may hold points without a projection: (points, status (int32)), status 0 already
+        inside (bit for bit), 1 projected, -1 no certified projection (an empty polyhedron), -2 the point is not finite; with -1 and
+        -2 the point comes back as it is.  This is what the batched closed loops do to every measurement (`spoly_project_status`)."""
+        if not self.with_reproject:
+            raise RuntimeError('Reproject not specified for class instance, set with_reproject=True to enable'
+                               'reprojection to the Polyhedron through a QP')
+        import ctypes as C
+        from . import _lib
+        X = _lib.f64(np.atleast_2d(x))
+        A, b = _lib.f64(self.A), _lib.f64(self.b)
+        if X.shape[1] != A.shape[1]:
+            raise RuntimeError('project_with_status: expected points of dimension %d, got %s' % (A.shape[1], np.shape(x)))
+        out, st = np.empty_like(X), np.zeros(X.shape[0], dtype=np.int32)
+        _lib.check(_lib.lib().spoly_project_status(_lib.dptr(A), _lib.dptr(b), C.c_int(A.shape[0]), C.c_int(A.shape[1]), _lib.dptr(X),
+                                                   C.c_int64(X.shape[0]), _lib.dptr(out), _lib.iptr(st)), 'spoly_project_status')
+        return (out[0], int(st[0])) if np.ndim(x) == 1 else (out, st)
+
 
 class HyperRectangle(Polyhedron):
     """Rows alternate +e_i, -e_i with b = [ub_i, -lb_i, ...] (sofacontrol/utils.py:409-414)."""
