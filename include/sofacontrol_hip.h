@@ -581,6 +581,18 @@ int sqp_ipm_rule_replay(int phase, int n, const double *rows, const double *par,
 enum { SLEAN_EV_WAIT = 0, SLEAN_EV_SIGNAL, SLEAN_EV_READ, SLEAN_EV_CHOL, SLEAN_EV_PANEL, SLEAN_EV_UPDATE, SLEAN_EV_FRONT };
 int slean_roster_replay(int KT, int code, int nwk0, int wave, int cap, int32_t *events, int32_t *count, int32_t *code_in_effect);
 
+/* y = G u of the half-size lean kernel (horizon NF, M inputs, NP = 2 NF <= 128 output columns) as lane `lane` (0 .. 63) of wave `wave`
+ * of a wave set of `set_size` threads (128: the Newton front, 256: the whole workgroup) runs it, produced on the host by the schedule
+ * functions the device code calls.  Column i of the packed G^T is summed in four chains, chain c over the stages c, c + 4, .. <= i / 2 of
+ * every input in turn; a lane owns one (column, chain) task per round, the four tasks of a column sit in one quad of lanes.  A step is
+ * nine int32 {round, input, step, column, chain, stage, flags, packed, toeplitz}, in the order the lane executes them: stage = the stage
+ * whose term the step adds to the chain, or -1 where the lane is outside the triangle and adds nothing; packed / toeplitz = the index it
+ * reads, in the packed rows / in the Toeplitz generators (M x NP) of a single-region G.  flags: SLEAN_GU_SPARE = the quad stands past
+ * the round's last column (it repeats that column and stores nothing), SLEAN_GU_STORES = this lane stores the column's sum.  At most
+ * `cap` steps are written, *count is the length of the whole list.  Needs no GPU; for tests of the schedule. */
+enum { SLEAN_GU_SPARE = 1, SLEAN_GU_STORES = 2 };
+int slean_gu_schedule(int NF, int M, int set_size, int wave, int lane, int cap, int32_t *steps, int32_t *count);
+
 /* GuSTO.solve (gusto.py:283-487) on a pre-discretised nn-TPWL model, `batch` independent rollouts:
  *   x0 (batch x n_x), u_init (batch x N x n_u), x_init (batch x (N+1) x n_x), z (batch x (N+1) x n_z)
  *   or NULL, zf, u_des as slocp_solve; x_char / f_char (n_x,) or NULL (ones); dt = horizon step.

@@ -414,6 +414,35 @@ int slean_roster_replay(int KT, int code, int nwk0, int wave, int cap, int32_t *
     return SRH_OK;
 }
 
+// y = G u of the half-size lean kernel as one lane runs it (ql::g_times_tasks), written with the schedule functions the device code calls:
+// the wave's rounds longest first, the inputs of its class inside a round, the steps inside an input.
+int slean_gu_schedule(int NF, int M, int set_size, int wave, int lane, int cap, int32_t *steps, int32_t *count) {
+    SRH_REQUIRE(steps && count && NF >= 1 && NF <= 512 && M >= 1 && M <= 16 && cap >= 0, "slean_gu_schedule: bad argument");
+    const int CW = 64 * ql::GU_WAVES, NP = 2 * NF;
+    SRH_REQUIRE(set_size >= CW && set_size % CW == 0 && wave >= 0 && wave < set_size / 64 && lane >= 0 && lane < 64 && NP <= CW,
+                "slean_gu_schedule: bad argument");
+    const int GR = set_size / CW, grp = wave / ql::GU_WAVES, wv = wave % ql::GU_WAVES, c = lane & 3;
+    int n = 0;
+    for (int r = ql::gu_rounds(NP) - 1; r >= 0; --r) {
+        if (ql::gu_round_wave(NP, r) != wv) continue;
+        const int i = ql::gu_lane_col(NP, r, lane), S = ql::gu_round_steps(NP, r), SE = ql::gu_first_edge_step(NP, r);
+        const int flags = ((lane >> 2) >= ql::gu_round_ncols(NP, r) ? SLEAN_GU_SPARE : 0) | (ql::gu_lane_stores(NP, r, lane) ? SLEAN_GU_STORES : 0);
+        for (int b = grp; b < M; b += GR)
+            for (int s = 0; s < S; ++s) {
+                const bool outside = s >= SE && c + 4 * s > i / 2;
+                if (n < cap) {
+                    int32_t *e = steps + 9 * (size_t)n;
+                    e[0] = r; e[1] = b; e[2] = s; e[3] = i; e[4] = c; e[5] = outside ? -1 : c + 4 * s; e[6] = flags;
+                    e[7] = outside ? ql::gu_index_outside(NP, b, i) : ql::gu_index_packed(M, NP, c, s, b, i);
+                    e[8] = outside ? ql::gu_index_outside(NP, b, i) : ql::gu_index_toeplitz(NP, c, s, b, i);
+                }
+                ++n;
+            }
+    }
+    *count = n;
+    return SRH_OK;
+}
+
 int sgusto_plan_create(sgusto_plan_t **out, stpwl_t *h, const slocp_problem *prob, const sgusto_params *par,
                        double dt, int64_t batch, const double *x_char, const double *f_char, int max_trace) {
     SRH_REQUIRE(out && h && prob && par, "sgusto_plan_create: null argument");

@@ -112,7 +112,7 @@ __host__ __device__ inline int gram_stage_j0(const QPDims &d) {
 //   -k: waves 1, 2, 3 in the rows < k, wave 1 alone from row k on              (half-size: waves 2, 3 leave for the Newton front)
 // with 1 <= k <= KT - 2.  The workers of a row are always the waves 1 .. nwk(J): a wave skips a row it does not work in without
 // touching a counter, and enters a row behind the CUMULATIVE arrivals of the rows before (whose acquire makes their tiles visible to it).
-constexpr int LEAN_ROSTER_DEFAULT = -1;      // the half-size kernel's code unless SRH_LEAN_ROSTER says otherwise (chosen by measurement: DESIGN.md section 39)
+constexpr int LEAN_ROSTER_DEFAULT = -1;      // the half-size kernel's code unless SRH_LEAN_ROSTER says otherwise (chosen by measurement: DESIGN.md sections 39 and 49)
 __host__ __device__ inline bool roster_legal(int KT, int code) { const int k = code < 0 ? -code : code; return code == 0 || (k >= 1 && k <= KT - 2); }
 __host__ __device__ inline int roster_nwk(int code, int nwk0, int J) {
     if (code == 0) return nwk0;
@@ -142,6 +142,57 @@ __host__ __device__ inline void roster_trailing_tile(int KT, int J, int t, int &
     while (tt >= rem - Ir) { tt -= rem - Ir; ++Ir; }
     I = J + 1 + Ir; Kc = I + tt;
 }
+
+// ------------------------------------------------------------------ the (column, chain) schedule of y = G u, half-size layout
+// g_times_fixed sums column i of the packed G^T in four chains, chain c over the stages j = c, c + 4, .. <= i / 2 of every input in turn,
+// and the chains meet only in (a0 + a1) + (a2 + a3).  The half-size kernel deals the triangle by TASK = (column, chain): the four tasks of
+// a column sit in one quad of lanes, a wave-ROUND is 16 adjacent columns x 4 chains, and step s of a round is stage c + 4 s in every lane.
+// The rounds, who runs them and what a lane reads are stated here once, for the device code (g_times_tasks) and for the host listing
+// (slean_gu_schedule, tests/test_lean_gu_schedule_cpu.py).  NP = 2 NF columns; the two waves of an input class (GU_WAVES) share the rounds.
+//   Round 0 has the columns [0, lead), round r >= 1 the columns [lead + 16 (r - 1), lead + 16 r) below NP.  lead is 8 when that saves a
+//   step per round without adding a round (NP mod 16 in 1 .. 8), else 16: a round's length follows its LAST column, and with the columns a
+//   multiple of 8 only its last two steps meet the triangle's edge.  NP = 100: 8 + 5 x 16 + 12 columns in 1, 3, .. 13 steps = 49 per
+//   input (lead 16: 2, 4, .. 12, 13 = 55, the last round with four columns).
+//   The rounds go to the waves longest first, each to the wave with the fewer steps so far (ties: the lower wave): NP = 100, wave 0 the
+//   rounds 6, 3, 2 (25 steps), wave 1 the rounds 5, 4, 1, 0 (24).
+constexpr int GU_WAVES = 2;                  // waves of one input class: CW = 128 threads
+__host__ __device__ constexpr int gu_lead(int NP) { return (NP % 16 >= 1 && NP % 16 <= 8) ? 8 : 16; }
+__host__ __device__ constexpr int gu_rounds(int NP) { return NP <= gu_lead(NP) ? 1 : 1 + (NP - gu_lead(NP) + 15) / 16; }
+__host__ __device__ constexpr int gu_round_col0(int NP, int r) { return r == 0 ? 0 : gu_lead(NP) + 16 * (r - 1); }
+__host__ __device__ constexpr int gu_round_ncols(int NP, int r) {
+    const int end = gu_lead(NP) + 16 * r;
+    return (end < NP ? end : NP) - gu_round_col0(NP, r);
+}
+// steps of round r: its last column i reaches the stages 0 .. i / 2
+__host__ __device__ constexpr int gu_round_steps(int NP, int r) { return ((gu_round_col0(NP, r) + gu_round_ncols(NP, r) - 1) / 2) / 4 + 1; }
+__host__ __device__ constexpr int gu_round_wave(int NP, int r) {
+    int load[GU_WAVES] = {};
+    for (int q = gu_rounds(NP) - 1; q >= 0; --q) {           // (the rounds' lengths ascend with r)
+        int w = 0;
+        for (int v = 1; v < GU_WAVES; ++v) if (load[v] < load[w]) w = v;
+        if (q == r) return w;
+        load[w] += gu_round_steps(NP, q);
+    }
+    return -1;
+}
+// steps s >= gu_first_edge_step have lanes outside the triangle (stage c + 4 s > i / 2 for some live (i, c)): the last two
+__host__ __device__ constexpr int gu_first_edge_step(int NP, int r) { const int s = gu_round_steps(NP, r) - 2; return s < 0 ? 0 : s; }
+// lane -> task: chain = lane & 3; the column of quad lane >> 2, a quad past the round's last column repeats that column (never stored)
+__host__ __device__ constexpr int gu_lane_col(int NP, int r, int lane) {
+    const int q = lane >> 2, nc = gu_round_ncols(NP, r);
+    return gu_round_col0(NP, r) + (q < nc ? q : nc - 1);
+}
+__host__ __device__ constexpr bool gu_lane_stores(int NP, int r, int lane) { return (lane & 3) == 0 && (lane >> 2) < gu_round_ncols(NP, r); }
+// Element (j, b, i) of the packed rows by the walk the device code takes: from the task's first stage c in steps of four stages,
+//     R(c + 4 s, b) + i = R(c, b) + i + E(s) - s (8 M c + 8 b),   E(s) = s (4 M NP - 12 M - 8) - 16 M s (s - 1)
+// (four times the recurrence of R in the products' header below); a lane outside the triangle reads element (0, b, i) instead -- inside
+// the packed block and inside the generators, whatever the stage would have been.
+__host__ __device__ constexpr int gu_walk_e(int M, int NP, int s) { return s * (4 * M * NP - 12 * M - 8) - 16 * M * s * (s - 1); }
+__host__ __device__ constexpr int gu_index_packed(int M, int NP, int c, int s, int b, int i) {
+    return M * (c * NP - c * (c - 1)) + b * (NP - 2 * c) - 2 * c + i + gu_walk_e(M, NP, s) - s * (8 * M * c + 8 * b);
+}
+__host__ __device__ constexpr int gu_index_toeplitz(int NP, int c, int s, int b, int i) { return b * NP + i - 2 * c - 8 * s; }
+__host__ __device__ constexpr int gu_index_outside(int NP, int b, int i) { return b * NP + i; }
 
 __device__ inline void lds_carve(Lds &L, lptr base, const QPDims &d, int nthreads, gptr work_base = nullptr) {
     const Sizes s = sizes(d, nthreads, d.lean_j0);
@@ -605,8 +656,11 @@ __device__ __forceinline__ bool single_region(const QPDims &d, const QPConst &c,
 // plus a select in the triangular part; g_times spends about ten instructions per stage on the same (index arithmetic of
 // the run-time loop, clamps and masks of its eight-stage trips).  Stages in blocks of sixteen; a block no lane of the wave
 // needs is skipped, a block every lane needs whole runs without the selects.  C2: 7.9 k -> 5.5 k clocks, C5: 15.7 k -> 11.6 k.
+template <int MSEL, bool HALF, int NF, class GP>
+__device__ __forceinline__ void g_times_tasks(const GP &g, Lds &L, clptr uv, lptr yv, int ldG, Waves<HALF> &W);
 template <int MSEL, bool HALF, int NF, int J0F, class GP>
 __device__ __forceinline__ void g_times_fixed(const GP &g, Lds &L, clptr uv, lptr yv, int ldG, Waves<HALF> &W) {
+    if constexpr (J0F == NF) { g_times_tasks<MSEL, HALF, NF>(g, L, uv, yv, ldG, W); return; }      // the half-size layout
     constexpr int M = MSEL, CW = 128, NP = 2 * NF;
     constexpr int BLK = 16;                 // stages per block: 16 + 16 loads in flight (8: 6.2 k clocks at C2, 16: 5.5 k)
     constexpr int goff0 = M * (J0F * NP - J0F * (J0F - 1));
@@ -660,6 +714,78 @@ __device__ __forceinline__ void g_times_fixed(const GP &g, Lds &L, clptr uv, lpt
     if (tid < ldG) {
         double s = 0.0;
         if (tid < NP) for (int q = 0; q < GR; ++q) s += part[q * CW + tid];
+        yv[tid] = s;
+    }
+    W.sync();
+}
+
+// The same product for the half-size layout (J0F == NF: every packed row in the L2 block), dealt by (column, chain) TASKS -- the schedule
+// stated next to the roster functions above (gu_rounds .. gu_index_outside).  With a thread per column, g_times_fixed runs the wave of
+// the columns 64 .. 127 (36 live lanes at NP = 100) through all NF stages and every block of it through the selects of the triangle's
+// edge: 50 + 32 stage slots per input on the two waves of an input class for 25.5 full ones.  Here a lane owns ONE of the four chains of
+// a column: it sees that chain's operands in that chain's order (the inputs in turn, the stages c, c + 4, .. ascending inside each, one
+// accumulator kept across the inputs), the quad forms (a0 + a1) + (a2 + a3) -- the additions of g_times_fixed, a pair sum commutes -- and
+// `part`, the sum over the input classes and both syncs stay: the same bits.  A wave runs its rounds one after the other; a round and an
+// input are one round trip: every load of the round (at most 13) and its reads of u before the first FMA.  Only a round's last two steps
+// meet the triangle's edge: there a lane outside reads element (0, b, i) and skips the FMA, every earlier step runs bare.  The Toeplitz
+// generators are read at immediate offsets from one address per lane and input (- 8 doubles per step), the packed rows along gu_index_packed.
+// One difference to g_times_fixed: a lane outside the triangle executed fma(0.0, u, acc) there and picked up a NaN from a non-finite u
+// (which only occurs behind a failed pivot, L.flag[1] == 0, when the product is discarded); here it executes nothing.  Finite data:
+// every bit the same.
+template <int MSEL, bool HALF, int NF, class GP>
+__device__ __forceinline__ void g_times_tasks(const GP &g, Lds &L, clptr uv, lptr yv, int ldG, Waves<HALF> &W) {
+    constexpr int M = MSEL, CW = 64 * GU_WAVES, NP = 2 * NF, NR = gu_rounds(NP);
+    const int tid = W.tid, nt = W.nt;
+    const int GR = nt / CW, grp = __builtin_amdgcn_readfirstlane(tid / CW), wv = __builtin_amdgcn_readfirstlane((tid % CW) >> 6);
+    const int lane = tid & 63, c = lane & 3;
+    const bool toep = g.gto != nullptr;                               // (uniform)
+    lptr part = L.part + grp * CW;
+    clptr pu0 = uv + c * M;
+    srh_static_for<0, NR>([&](auto R_) {
+        constexpr int r = NR - 1 - decltype(R_)::value;               // a wave's longest round first
+        constexpr int S = gu_round_steps(NP, r), SE = gu_first_edge_step(NP, r);
+        if (wv != gu_round_wave(NP, r)) return;                       // uniform
+        const int i = gu_lane_col(NP, r, lane), jlast = i >> 1;
+        // byte offsets from the store's (uniform) base in one 32-bit register per lane: a step of the walk of gu_index_packed is the
+        // step's constant plus the lane's - 8 (8 M c + 8 b), a step along the generators - 64
+        const unsigned at_p = 8u * (unsigned)gu_index_packed(M, NP, c, 0, 0, i), at_t = 8u * (unsigned)gu_index_toeplitz(NP, c, 0, 0, i);
+        double acc = 0.0;
+        auto input = [&](cgptr src, int b, auto TOEP) {
+            constexpr bool tp = decltype(TOEP)::value;
+            clptr pu = pu0 + b;
+            const unsigned e0 = 8u * (unsigned)gu_index_outside(NP, b, i);
+            unsigned e = tp ? at_t + 8u * (unsigned)(b * NP) : at_p + 8u * (unsigned)(b * (NP - 2 * c));
+            const unsigned ndq = 0u - 8u * (unsigned)(8 * M * c + 8 * b);
+            double gv[S], uu[S];
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+                if (s > 0) e = tp ? e - 64u : e + ndq + 8u * (unsigned)(gu_walk_e(M, NP, s) - gu_walk_e(M, NP, s - 1));
+                const unsigned es = (s >= SE && c + 4 * s > jlast) ? e0 : e;
+                gv[s] = *(cgptr)((const __attribute__((address_space(1))) char *)src + es);
+                uu[s] = pu[4 * M * s];
+            }
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+                const double t = fma(gv[s], uu[s], acc);
+                if (s >= SE) acc = c + 4 * s <= jlast ? t : acc;
+                else acc = t;
+            }
+        };
+        for (int b0 = grp; b0 < M; b0 += GR) {                        // uniform
+            // (b opaque in every trip: left to itself the compiler turns each step's offset into an induction variable of this loop,
+            // 2 S registers and a multiplication per step in front of every round)
+            int b = b0;
+            asm volatile("" : "+s"(b));
+            if (toep) input(g.gto, b, std::true_type{});
+            else input(g.gh, b, std::false_type{});
+        }
+        acc = wg::group_sum<4>(acc);                                  // lane 0 of the quad: (a0 + a1) + (a2 + a3)
+        if (gu_lane_stores(NP, r, lane)) part[i] = acc;
+    });
+    W.sync();
+    if (tid < ldG) {
+        double s = 0.0;
+        if (tid < NP) for (int q = 0; q < GR; ++q) s += L.part[q * CW + tid];
         yv[tid] = s;
     }
     W.sync();

@@ -243,6 +243,26 @@ def lean_roster_replay(KT, code, nwk0=1):
     return int(eff.value), waves
 
 
+GU_SPARE, GU_STORES = 1, 2
+
+
+def lean_gu_schedule(NF, M, set_size):
+    """slean_gu_schedule: y = G u of the half-size lean kernel by (column, chain) tasks (csrc/locp_lean.h: gu_rounds and the functions
+    next to it), listed on the host -- no GPU needed.  Returns {(wave, lane): int32 array (steps x 9)} for the set's waves, a row being
+    (round, input, step, column, chain, stage or -1, flags, packed index, toeplitz index) (include/sofacontrol_hip.h)."""
+    out = {}
+    for wave in range(set_size // 64):
+        for lane in range(64):
+            n = C.c_int32(0)
+            args = (C.c_int(NF), C.c_int(M), C.c_int(set_size), C.c_int(wave), C.c_int(lane))
+            check(lib().slean_gu_schedule(*args, C.c_int(0), np.zeros(9, dtype=np.int32).ctypes.data_as(C.c_void_p), C.byref(n)),
+                  'slean_gu_schedule')
+            st = np.zeros((max(1, n.value), 9), dtype=np.int32)
+            check(lib().slean_gu_schedule(*args, C.c_int(n.value), st.ctypes.data_as(C.c_void_p), C.byref(n)), 'slean_gu_schedule')
+            out[(wave, lane)] = st[:n.value]
+    return out
+
+
 def gusto_plan_dims(plan):
     """sgusto_plan_dims: the shapes a resident GuSTO plan was created with, {'N', 'n_x', 'n_u', 'n_z', 'batch', 'dt', 'has_Qzf'}."""
     N, n, m, nz, hq = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
