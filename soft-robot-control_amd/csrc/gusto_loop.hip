@@ -4,9 +4,9 @@
 // tpwl/controllers.py:298-333 (the scp controller's interpolated plan and feedback law), tpwl/tpwl.py:160-168, 336-339 (plant step).
 // The solve itself is sgusto_plan_solve_dev (gusto.hip); this unit is the glue around it: loop_prepare_kernel (gusto_loop_prep.h) turns
 // the previous period's output into the next solve's input, loop_advance_kernel runs the plant under the feedback law for the n_keep
-// sub-steps.  The host shell of a handle and of a run -- shared with gusto_ssm_loop.hip -- is gusto_loop_host.h.
-#include "observer_host.h"
-#include "gusto_loop_host.h"
+// sub-steps.  The host shell of a handle and of a run -- shared with the four other loop units -- is gusto_loop_host.h, the observed
+// sub-step chain -- shared with ilqr_loop.hip -- loop_observed_host.h.
+#include "loop_observed_host.h"
 
 namespace {
 
@@ -127,15 +127,6 @@ size_t advance_lds_bytes(int n, int m, bool observed) {
     return srh::lds_request(sizeof(double) * ((size_t)3 * n + 16 + 16 + 2 + tpwl::step_doubles(n, m, 256) + (observed ? n : 0)));
 }
 
-// After a batched filter step: the estimates into row `row` of the record (B x rows x n), and the filters' status words into the
-// period's entry of the status record -- assigned at the period's first sub-step, or-ed at the others.
-__global__ __launch_bounds__(64) void loop_estimate_record_kernel(const double *xhat, const int *status, double *Xhat, int32_t *E, int n,
-                                                                  int64_t rows, int64_t row, int first) {
-    const size_t b = blockIdx.x;
-    for (int e = threadIdx.x; e < n; e += 64) Xhat[(b * (size_t)rows + row) * n + e] = xhat[b * n + e];
-    if (threadIdx.x == 0) E[b] = first ? status[b] : (E[b] | status[b]);
-}
-
 }  // namespace
 
 struct sgusto_loop : LoopCore {
@@ -167,25 +158,17 @@ struct sgusto_loop : LoopCore {
         SRH_CHECK_HIP(hipGetLastError());
         return SRH_OK;
     }
-    // The observed sub-step chain of one period on the handle's stream: n_keep x (advance of one sub-step under the law at the estimate,
-    // with its measurement -> one step of every filter from the recorded u and y -> the estimates and the status into their records).
-    // v: the arguments of the whole period (records, plan, W / Vn, x_in / x_out); XH / xh_rows / xh_row0: the estimate record and the
-    // row of sub-step 0's estimate; E: the period's status entry (B); pick: (B x n_keep) filter regions or null.
+    // The observed sub-step chain of one period (loop_observed_host.h): a launch covers one sub-step.  v: the arguments of the whole
+    // period (records, plan, W / Vn, x_in / x_out); XH / xh_rows / xh_row0: the estimate record and the row of sub-step 0's estimate;
+    // E: the period's status entry (B); pick: (B x n_keep) filter regions or null.
     int launch_observed_chain(AdvArgs v, double *XH, int64_t xh_rows, int64_t xh_row0, int32_t *E, int32_t *pick) const {
         v.xhat = obs->x_dev(); v.C = obs->C.as<double>(); v.y_ref = obs->yref_dev(); v.ny = ny;
-        int rc;
-        for (int s = 0; s < n_keep; ++s) {
-            v.s0 = s; v.s1 = s + 1;
+        return loop_observed_chain(this, obs, n_keep, ObsRecs{v.U, v.Y, v.rows_u, v.row0_u, XH, xh_rows, xh_row0, E, pick, n_keep}, [&](int64_t s) -> int {
+            v.s0 = (int)s; v.s1 = (int)s + 1;
             loop_advance_kernel<true><<<(unsigned)B, 256, lds_obs, stream>>>(planner->view(), plant->view(), v);
             SRH_CHECK_HIP(hipGetLastError());
-            if ((rc = sekf_batch_step_dev(obs, v.U + (size_t)(v.row0_u + s) * m, v.rows_u * m, v.Y + (size_t)(v.row0_u + s) * ny, v.rows_u * ny,
-                                          pick ? pick + s : nullptr, n_keep, stream)))
-                return rc;
-            loop_estimate_record_kernel<<<(unsigned)B, 64, 0, stream>>>(v.xhat, obs->status_dev(), XH, E, n, xh_rows, xh_row0 + s,
-                                                                       s == 0 ? 1 : 0);
-            SRH_CHECK_HIP(hipGetLastError());
-        }
-        return SRH_OK;
+            return SRH_OK;
+        });
     }
 };
 
@@ -336,22 +319,15 @@ int sgusto_loop_set_observer(sgusto_loop_t *h, sekf_batch_t *observer) {
     SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
     h->obs = nullptr; h->observed_state = false;
     if (!observer) return SRH_OK;
-    const int n = observer->n, m = observer->m, ny = observer->ny;
-    SRH_REQUIRE(observer->batch == h->B, "sgusto_loop_set_observer: the observer has batch = %lld filters, the loop %lld members",
-                (long long)observer->batch, (long long)h->B);
-    SRH_REQUIRE(n == h->n && m == h->m, "sgusto_loop_set_observer: the observer's model has n_x = %d, n_u = %d, the loop n_x = %d, n_u = %d", n, m,
-                h->n, h->m);
-    SRH_REQUIRE(observer->model->has_discrete, "sgusto_loop_set_observer: the observer's model has not been pre-discretised (at dt_sim)");
+    int rc;
+    if ((rc = loop_check_observer("sgusto_loop_set_observer", observer, h->B, h->n, h->m))) return rc;
     h->lds_obs = advance_lds_bytes(h->n, h->m, true);
     SRH_REQUIRE(h->lds_obs <= (size_t)160 * 1024, "sgusto_loop_set_observer: the observed advance kernel needs %zu bytes of LDS (160 KiB available)",
                 h->lds_obs);
     SRH_CHECK_HIP(hipFuncSetAttribute((const void *)loop_advance_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_obs));
-    const size_t D = sizeof(double);
-    h->XHrec.shape(D * n, 1); h->Yrec.shape(D * ny, 0); h->Erec.shape(sizeof(int32_t), 0, true); h->Vd.shape(D * ny, 0);
-    (void)h->Vd.d.alloc(0);             // (the noise block of another n_y is given back: the first run with noise allocates this one's)
-    int rc;
+    loop_shape_observed(h->XHrec, h->Yrec, h->Erec, h->Vd, h->n, observer->ny);
     if ((rc = h->alloc_recs({&h->XHrec, &h->Yrec, &h->Erec}))) return rc;
-    h->obs = observer; h->ny = ny;
+    h->obs = observer; h->ny = observer->ny;
     return SRH_OK;
 }
 

@@ -1,9 +1,12 @@
-// The host shell of the closed-loop units (gusto_loop.hip: TPWL plans, gusto_ssm_loop.hip: SSM plans, rompc_loop.hip: the chained linear
-// MPC of the ROMPC baseline), stated once: the handle's
-// common part (LoopCore), the blocks of a run that cross PCIe as a table (LoopRec), the checks and set-up of a create, the bodies of
-// set_target / last_inputs / last_plan / stats, and the skeleton of a run (loop_run_periods: capacity, staging, per period the prepare
-// kernel and the unit's own part, the copy back, ONE wait, the drain on an error).  What a unit keeps: its advance kernels, which
-// rollout / solve it calls, and where row 0 of its records comes from.  The device side of what they share is gusto_loop_prep.h.
+// The host shell of the five closed-loop units (gusto_loop.hip: TPWL plans, gusto_ssm_loop.hip: SSM plans, rompc_loop.hip: the chained
+// linear MPC of the ROMPC baseline, koopman_loop.hip: the Koopman baseline's MPC, ilqr_loop.hip: the tracked iLQR policy), stated once:
+// what every run stages (LoopStage: stream, waits, the blocks of a run that cross PCIe as a table of LoopRec, and loop_run_staged: the
+// copies up, row 0, the unit's launches, the copies back, ONE wait, the drain on an error), the common part of a handle with periods
+// (LoopCore), the checks and set-up of a create, the bodies of set_target / last_inputs / last_plan / stats, and the periods of a run
+// (loop_run_periods: capacity, per period the prepare kernel and the unit's own part).  What a unit keeps: its advance kernels, which
+// rollout / solve it calls, and where row 0 of its records comes from.  The device side of what they share is gusto_loop_prep.h; the
+// constant-horizon QP and the plan shift of the two linear MPC units are mpc_loop_host.h, the observed sub-step chain of the TPWL and
+// iLQR units is loop_observed_host.h.
 #pragma once
 #include "gusto_loop_prep.h"
 
@@ -56,28 +59,38 @@ struct LoopRows {
     int64_t rows_x, row0_x, rows_u, row0_u, w_step0;
 };
 
-struct LoopCore {
-    int N = 0, n = 0, m = 0, nz = 0, n_keep = 0, T = 0;
-    int64_t B = 0, max_steps = 0;
-    double dt = 0.0, dt_sim = 0.0, t_start = 0.0;
-    bool has_z = false, has_ud = false, has_phase = false, have_state = false;
-    int64_t k = 0;                      // periods since the last reset
+// What a run needs whether or not it has periods: the members, the stream, and the blocks that cross PCIe in front of the launches
+// (ins) and behind them (recs, in the order of their copies back)
+struct LoopStage {
+    int64_t B = 0;
     int64_t waits = 0;                  // blocking host waits of the last run
-    size_t lds = 0;
+    bool have_state = false;
     hipStream_t stream = nullptr;
+    std::vector<LoopRec *> recs, ins;
+    void drain() { if (stream) (void)hipStreamSynchronize(stream); }
+    ~LoopStage() {
+        drain();
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+struct LoopCore : LoopStage {
+    int N = 0, n = 0, m = 0, nz = 0, n_keep = 0, T = 0;
+    int64_t max_steps = 0;
+    double dt = 0.0, dt_sim = 0.0, t_start = 0.0;
+    bool has_z = false, has_ud = false, has_phase = false;
+    int64_t k = 0;                      // periods since the last reset
+    size_t lds = 0;
     srh::DevBuf x0, u_init, x_init, z, ud, xopt, uopt, zopt, xcur, tt, tz, tu, phase, js, theta;
     // records: states (B x (S + 1) x n, allocated by the first run that asks for it), outputs, inputs (B x S x m), iterations, status and
     // cost of every solve (P x B), estimates (B x (S + 1) x n), measurements; noise: W (steps x B x n), V.  A unit shapes Z, XH, Y and V
     // (their widths and rows are its own) and appends what only it records.
     LoopRec Xrec, Zrec, Urec, Irec, Srec, Jrec, XHrec, Yrec, Wd, Vd;
-    // the records in the order of their copies back, largest first: the S + 1 row blocks, the inputs, then the per-period words
-    std::vector<LoopRec *> recs{&Xrec, &Zrec, &Yrec, &XHrec, &Urec, &Irec, &Srec, &Jrec};
-    // the blocks of a run that go the other way, in front of the periods: the noise, and what a unit appends (a recorded plant)
-    std::vector<LoopRec *> ins{&Wd, &Vd};
-    void drain() { if (stream) (void)hipStreamSynchronize(stream); }
-    ~LoopCore() {
-        drain();
-        if (stream) (void)hipStreamDestroy(stream);
+    // the records in the order of their copies back, largest first: the S + 1 row blocks, the inputs, then the per-period words; the
+    // blocks of a run that go the other way, in front of the periods: the noise, and what a unit appends (a recorded plant)
+    LoopCore() {
+        recs = {&Xrec, &Zrec, &Yrec, &XHrec, &Urec, &Irec, &Srec, &Jrec};
+        ins = {&Wd, &Vd};
     }
     int alloc_recs(std::initializer_list<LoopRec *> list) {
         int rc;
@@ -178,6 +191,41 @@ int loop_wait(int rc, hipStream_t st) {
     return SRH_OK;
 }
 
+// The frame of a run of S steps in P periods: the `host` arrays of h->ins through pinned memory and up, row 0 of the records that name
+// one (LoopRec::row0), enqueue() -- the unit's launches on h->stream --, the records of h->recs down, ONE wait, and the copy to the
+// caller's arrays.  From the first copy on work is enqueued on the handle's stream: on any error it is drained before returning.
+template <class Enqueue>
+int loop_run_staged(LoopStage *h, size_t S, size_t P, Enqueue enqueue) {
+    const size_t B = (size_t)h->B;
+    h->waits = 0;
+    hipStream_t st = h->stream;
+    int rc;
+    auto body = [&]() -> int {
+        for (LoopRec *r : h->ins)
+            if (r->host) {
+                memcpy(r->pin.p, r->host, r->bytes(B, S, P));
+                SRH_CHECK_HIP(hipMemcpyAsync(r->d.p, r->pin.p, r->bytes(B, S, P), hipMemcpyHostToDevice, st));
+            }
+        for (LoopRec *r : h->recs)
+            if (r->host && r->row0)
+                SRH_CHECK_HIP(hipMemcpy2DAsync(r->d.p, r->unit * (S + 1), r->row0, r->unit, r->unit, B, hipMemcpyDeviceToDevice, st));
+        if ((rc = enqueue())) return rc;
+        for (LoopRec *r : h->recs)
+            if (r->host) SRH_CHECK_HIP(hipMemcpyAsync(r->pin.p, r->d.p, r->bytes(B, S, P), hipMemcpyDeviceToHost, st));
+        h->waits += 1;
+        SRH_CHECK_HIP(hipStreamSynchronize(st));
+        return SRH_OK;
+    };
+    if ((rc = body())) {
+        (void)hipStreamSynchronize(st);
+        h->have_state = false;          // part of a run was enqueued: the state is not the one the caller knows
+        return rc;
+    }
+    for (LoopRec *r : h->recs)
+        if (r->host) memcpy(r->host, r->pin.p, r->bytes(B, S, P));
+    return SRH_OK;
+}
+
 // `periods` periods from where the handle stands, the records into the `host` arrays of h->recs, noise from those of Wd / Vd.
 // period(p, a, r): the unit's part of period p behind the prepare kernel -- first guess (a.first), solve, costs, advance -- enqueued on
 // h->stream; a: the prepare kernel's arguments (the solve's inputs), r: the rows of the records the advance writes.
@@ -190,18 +238,8 @@ int loop_run_periods(LoopCore *h, const char *who, int periods, const PrepUnit &
     if (h->Xrec.host && !h->Xrec.d.p && (rc = h->alloc_recs({&h->Xrec}))) return rc;          // the blocks only some runs ask for
     for (LoopRec *r : h->ins)
         if (r->host && !r->d.p && (rc = h->alloc_recs({r}))) return rc;
-    h->waits = 0;
     hipStream_t st = h->stream;
-    // from here on work is enqueued on the handle's stream: on any error it is drained before returning
-    auto body = [&]() -> int {
-        for (LoopRec *r : h->ins)
-            if (r->host) {
-                memcpy(r->pin.p, r->host, r->bytes(B, S, P));
-                SRH_CHECK_HIP(hipMemcpyAsync(r->d.p, r->pin.p, r->bytes(B, S, P), hipMemcpyHostToDevice, st));
-            }
-        for (LoopRec *r : h->recs)
-            if (r->host && r->row0)
-                SRH_CHECK_HIP(hipMemcpy2DAsync(r->d.p, r->unit * (S + 1), r->row0, r->unit, r->unit, B, hipMemcpyDeviceToDevice, st));
+    rc = loop_run_staged(h, S, P, [&]() -> int {
         for (int p = 0; p < periods; ++p) {
             const int64_t k = h->k + p;
             PrepArgs a{};
@@ -224,23 +262,13 @@ int loop_run_periods(LoopCore *h, const char *who, int periods, const PrepUnit &
             loop_prepare_kernel<<<(unsigned)B, 256, 0, st>>>(a);
             SRH_CHECK_HIP(hipGetLastError());
             const LoopRows r{(int64_t)S + 1, (int64_t)p * nk + 1, (int64_t)S, (int64_t)p * nk, (int64_t)p * nk};
-            if ((rc = period(p, a, r))) return rc;
+            int e = period(p, a, r);
+            if (e) return e;
         }
-        for (LoopRec *r : h->recs)
-            if (r->host) SRH_CHECK_HIP(hipMemcpyAsync(r->pin.p, r->d.p, r->bytes(B, S, P), hipMemcpyDeviceToHost, st));
-        h->waits += 1;
-        SRH_CHECK_HIP(hipStreamSynchronize(st));
         return SRH_OK;
-    };
-    if ((rc = body())) {
-        (void)hipStreamSynchronize(st);
-        h->have_state = false;          // part of a run was enqueued: the state is not the one the caller knows
-        return rc;
-    }
-    for (LoopRec *r : h->recs)
-        if (r->host) memcpy(r->host, r->pin.p, r->bytes(B, S, P));
-    h->k += periods;
-    return SRH_OK;
+    });
+    if (!rc) h->k += periods;
+    return rc;
 }
 
 }  // namespace

@@ -1,8 +1,10 @@
-// The device side of what the three closed-loop units (gusto_loop.hip: TPWL plans, gusto_ssm_loop.hip: SSM plans, rompc_loop.hip: the
-// ROMPC baseline) share, stated once: the plan point of a sub-step, the output and measurement rows, the target table's interpolation,
-// the query times, and loop_prepare_kernel -- the kernel that turns the previous period's output into the next solve's input (x0, the
-// shifted guess, the target window).  Its one launch, and the host shell around it, is gusto_loop_host.h.  Each unit gets its own
-// instance of the kernel (anonymous namespace); an SSM loop passes no H (it has no linear output map) and no zf (no terminal cost).
+// The device side of what the five closed-loop units (gusto_loop.hip: TPWL plans, gusto_ssm_loop.hip: SSM plans, rompc_loop.hip: the
+// ROMPC baseline, koopman_loop.hip: the Koopman baseline, ilqr_loop.hip: the iLQR policy) share, stated once: the plan point of a
+// sub-step, the output and measurement rows, the target table's interpolation, the query times, the measurement's re-projection, and
+// loop_prepare_kernel -- the kernel that turns the previous period's output into the next solve's input (x0, the shifted guess, the
+// target window).  Its one launch, and the host shell around it, is gusto_loop_host.h.  Each unit gets its own instance of the kernel
+// (anonymous namespace; the iLQR loop, which has no periods, never launches its own); an SSM loop passes no H (it has no linear output
+// map) and no zf (no terminal cost).
 #pragma once
 #include "common.h"
 #include "dev_la.h"

@@ -16,11 +16,10 @@
 //   4. with an observer: y = (C x + y_ref) + v_s (measure_row), then one step of every filter with (u, y)
 // The held input and the step counter live in the handle: a run may stop and resume in the middle of a controller step.
 // Not offered: SSM plants or plans, weighting-mode plants, input clipping, re-planning during a run, the start-up phase before t_delay.
-// The blocks of a run that cross PCIe are LoopRec / PinBuf of gusto_loop_host.h; there are no periods here, so loop_run_periods and the
-// prepare kernel are not used.
+// The staging of a run is LoopStage / loop_run_staged of gusto_loop_host.h (there are no periods here, so LoopCore, loop_run_periods and
+// the prepare kernel are not used); the observed chain -- shared with gusto_loop.hip -- is loop_observed_host.h.
 #include "ilqr_host.h"
-#include "observer_host.h"
-#include "gusto_loop_host.h"
+#include "loop_observed_host.h"
 
 #include <algorithm>
 
@@ -199,28 +198,17 @@ __global__ __launch_bounds__(64) void il_row0_kernel(const double *x, const doub
     for (int e = SRH_TID; e < nz; e += 64) ((gptr)Z)[b * (size_t)rows * nz + e] = out_row((cgptr)H, e, n, xc);
 }
 
-// After a batched filter step: the estimates into row `row` of the record (B x rows x n), and the filters' status words into the run's
-// status record -- assigned at the run's first step, or-ed at the others
-__global__ __launch_bounds__(64) void il_estimate_record_kernel(const double *xhat, const int *status, double *Xhat, int32_t *E, int n,
-                                                                int64_t rows, int64_t row, int first) {
-    const size_t b = blockIdx.x;
-    for (int e = SRH_TID; e < n; e += 64) ((gptr)Xhat)[(b * (size_t)rows + row) * n + e] = ((cgptr)xhat)[b * n + e];
-    if (SRH_TID == 0) E[b] = first ? status[b] : (E[b] | status[b]);
-}
-
 }  // namespace
 
-struct silqr_loop {
+struct silqr_loop : LoopStage {
     silqr_plan *plan = nullptr;
     stpwl *plant = nullptr;
     sekf_batch *obs = nullptr;
     int N = 0, n = 0, m = 0, nz = 0, r = 1, ny = 0;
-    int64_t B = 0, max_steps = 0;
+    int64_t max_steps = 0;
     int64_t step = 0;                   // simulation steps since the last reset
-    int64_t waits = 0;                  // blocking host waits of the last run
-    bool have_state = false, have_policy = false, policy_is_plan = false, policy_shared = false;
+    bool have_policy = false, policy_is_plan = false, policy_shared = false;
     size_t lds = 0, lds_obs = 0;
-    hipStream_t stream = nullptr;
     // xcur, uheld: where the plants stand and the inputs they hold; u0: the idle input; rows: the row table; pxb, pub, pK: an uploaded policy
     srh::DevBuf xcur, uheld, u0, rows, pxb, pub, pK;
     int64_t n_rows = 0;
@@ -232,14 +220,11 @@ struct silqr_loop {
     }
     // records: states, outputs, estimates (B x (S + 1) x .), inputs, measurements (B x S x .), the filters' status (B); noise W, V (S x B x .)
     LoopRec Xrec, Zrec, XHrec, Urec, Yrec, Erec, Wd, Vd;
-    std::vector<LoopRec *> recs{&Xrec, &Zrec, &XHrec, &Yrec, &Urec, &Erec};
-    std::vector<LoopRec *> ins{&Wd, &Vd};
-    ~silqr_loop() {
-        if (stream) {
-            (void)hipStreamSynchronize(stream);
-            (void)hipStreamDestroy(stream);
-        }
+    silqr_loop() {
+        recs = {&Xrec, &Zrec, &XHrec, &Yrec, &Urec, &Erec};
+        ins = {&Wd, &Vd};
     }
+    ~silqr_loop() { drain(); }
     IlAdvArgs adv_args() const {
         IlAdvArgs a{};
         a.N = N; a.n = n; a.m = m; a.nz = nz; a.r = r;
@@ -262,24 +247,17 @@ struct silqr_loop {
         SRH_CHECK_HIP(hipGetLastError());
         return SRH_OK;
     }
-    // The observed chain on the handle's stream, S x (advance of one step under the law at the estimate, with its measurement -> one step
-    // of every filter from the recorded u and y -> the estimates and the status into their records): the order of launch_observed_chain
-    // in gusto_loop.hip.  v: the arguments of the whole run; XH: the estimate record (rows as X); E: the status record (B).
+    // The observed chain (loop_observed_host.h): a launch covers one step.  v: the arguments of the whole run; XH: the estimate record
+    // (rows as X); E: the status record (B).
     int launch_observed_chain(IlAdvArgs v, double *XH, int32_t *E) const {
         v.xhat = obs->x_dev(); v.C = obs->C.as<double>(); v.y_ref = obs->yref_dev(); v.ny = ny;
         const int64_t S = v.S, step0 = v.step0, row0_x = v.row0_x, row0_u = v.row0_u, w0 = v.w_step0;
-        int rc;
-        for (int64_t s = 0; s < S; ++s) {
+        return loop_observed_chain(this, obs, S, ObsRecs{v.U, v.Y, v.rows_u, row0_u, XH, v.rows_x, row0_x, E, nullptr, 0}, [&](int64_t s) -> int {
             v.S = 1; v.step0 = step0 + s; v.row0_x = row0_x + s; v.row0_u = row0_u + s; v.w_step0 = w0 + s;
             il_advance_kernel<true><<<(unsigned)B, 256, lds_obs, stream>>>(plant->view(), v);
             SRH_CHECK_HIP(hipGetLastError());
-            if ((rc = sekf_batch_step_dev(obs, v.U + (size_t)(row0_u + s) * m, v.rows_u * m, v.Y + (size_t)(row0_u + s) * ny, v.rows_u * ny, nullptr,
-                                          0, stream)))
-                return rc;
-            il_estimate_record_kernel<<<(unsigned)B, 64, 0, stream>>>(v.xhat, obs->status_dev(), XH, E, n, v.rows_x, row0_x + s, s == 0 ? 1 : 0);
-            SRH_CHECK_HIP(hipGetLastError());
-        }
-        return SRH_OK;
+            return SRH_OK;
+        });
     }
 };
 
@@ -369,22 +347,16 @@ int silqr_loop_set_observer(silqr_loop_t *h, sekf_batch_t *observer) {
     SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
     h->obs = nullptr; h->have_state = false;
     if (!observer) return SRH_OK;
-    const int n = observer->n, m = observer->m, ny = observer->ny;
-    SRH_REQUIRE(observer->batch == h->B, "silqr_loop_set_observer: the observer has batch = %lld filters, the loop %lld members",
-                (long long)observer->batch, (long long)h->B);
-    SRH_REQUIRE(n == h->n && m == h->m, "silqr_loop_set_observer: the observer's model has n_x = %d, n_u = %d, the loop n_x = %d, n_u = %d", n, m,
-                h->n, h->m);
-    SRH_REQUIRE(observer->model->has_discrete, "silqr_loop_set_observer: the observer's model has not been pre-discretised (at dt_sim)");
+    int rc;
+    if ((rc = loop_check_observer("silqr_loop_set_observer", observer, h->B, h->n, h->m))) return rc;
     h->lds_obs = il_advance_lds_bytes(h->n, h->m, true);
     SRH_REQUIRE(h->lds_obs <= (size_t)160 * 1024, "silqr_loop_set_observer: the observed advance kernel needs %zu bytes of LDS (160 KiB available)",
                 h->lds_obs);
     SRH_CHECK_HIP(hipFuncSetAttribute((const void *)il_advance_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_obs));
-    const size_t D = sizeof(double), B = (size_t)h->B, S = (size_t)h->max_steps;
-    h->XHrec.shape(D * n, 1); h->Yrec.shape(D * ny, 0); h->Erec.shape(sizeof(int32_t), 0, true); h->Vd.shape(D * ny, 0);
-    (void)h->Vd.d.alloc(0);             // (the noise block of another n_y is given back: the first run with noise allocates this one's)
-    int rc;
+    const size_t B = (size_t)h->B, S = (size_t)h->max_steps;
+    loop_shape_observed(h->XHrec, h->Yrec, h->Erec, h->Vd, h->n, observer->ny);
     if ((rc = h->XHrec.alloc(B, S, 1)) || (rc = h->Yrec.alloc(B, S, 1)) || (rc = h->Erec.alloc(B, S, 1))) return rc;
-    h->obs = observer; h->ny = ny;
+    h->obs = observer; h->ny = observer->ny;
     return SRH_OK;
 }
 
@@ -439,21 +411,11 @@ int silqr_loop_run(silqr_loop_t *h, int64_t steps, const double *W, const double
     if (X && !h->Xrec.d.p && (rc = h->Xrec.alloc(B, Sm, 1))) return rc;              // the blocks only some runs ask for
     for (LoopRec *r : h->ins)
         if (r->host && !r->d.p && (rc = r->alloc(B, Sm, 1))) return rc;
-    h->waits = 0;
-    hipStream_t st = h->stream;
-    // from here on work is enqueued on the handle's stream: on any error it is drained before returning
-    auto body = [&]() -> int {
-        for (LoopRec *r : h->ins)
-            if (r->host) {
-                memcpy(r->pin.p, r->host, r->bytes(B, S, 1));
-                SRH_CHECK_HIP(hipMemcpyAsync(r->d.p, r->pin.p, r->bytes(B, S, 1), hipMemcpyHostToDevice, st));
-            }
-        il_row0_kernel<<<(unsigned)B, 64, 0, st>>>(h->xcur.as<double>(), h->plant->H.as<double>(), X ? h->Xrec.as<double>() : nullptr,
-                                                    h->Zrec.as<double>(), h->n, h->nz, (int64_t)S + 1);
+    h->XHrec.row0 = observed ? h->obs->x_dev() : nullptr;             // row 0 of the estimate record: the estimates the run starts from
+    rc = loop_run_staged(h, S, 1, [&]() -> int {
+        il_row0_kernel<<<(unsigned)B, 64, 0, h->stream>>>(h->xcur.as<double>(), h->plant->H.as<double>(), X ? h->Xrec.as<double>() : nullptr,
+                                                           h->Zrec.as<double>(), h->n, h->nz, (int64_t)S + 1);
         SRH_CHECK_HIP(hipGetLastError());
-        if (observed)
-            SRH_CHECK_HIP(hipMemcpy2DAsync(h->XHrec.d.p, h->XHrec.unit * (S + 1), h->obs->x_dev(), h->XHrec.unit, h->XHrec.unit, B,
-                                           hipMemcpyDeviceToDevice, st));
         IlAdvArgs v = h->adv_args();
         v.S = (int64_t)S; v.step0 = h->step;
         v.W = W ? h->Wd.as<double>() : nullptr; v.w_step0 = 0;
@@ -461,27 +423,12 @@ int silqr_loop_run(silqr_loop_t *h, int64_t steps, const double *W, const double
         v.u_in = h->uheld.as<double>(); v.u_out = h->uheld.as<double>();
         v.X = X ? h->Xrec.as<double>() : nullptr; v.Z = h->Zrec.as<double>(); v.U = h->Urec.as<double>();
         v.rows_x = (int64_t)S + 1; v.row0_x = 1; v.rows_u = (int64_t)S; v.row0_u = 0;
-        if (!observed) {
-            if ((rc = h->launch_advance(v))) return rc;
-        } else {
-            v.Vn = V ? h->Vd.as<double>() : nullptr; v.Y = h->Yrec.as<double>();
-            if ((rc = h->launch_observed_chain(v, h->XHrec.as<double>(), h->Erec.as<int32_t>()))) return rc;
-        }
-        for (LoopRec *r : h->recs)
-            if (r->host) SRH_CHECK_HIP(hipMemcpyAsync(r->pin.p, r->d.p, r->bytes(B, S, 1), hipMemcpyDeviceToHost, st));
-        h->waits += 1;
-        SRH_CHECK_HIP(hipStreamSynchronize(st));
-        return SRH_OK;
-    };
-    if ((rc = body())) {
-        (void)hipStreamSynchronize(st);
-        h->have_state = false;          // part of a run was enqueued: the state is not the one the caller knows
-        return rc;
-    }
-    for (LoopRec *r : h->recs)
-        if (r->host) memcpy(r->host, r->pin.p, r->bytes(B, S, 1));
-    h->step += steps;
-    return SRH_OK;
+        if (!observed) return h->launch_advance(v);
+        v.Vn = V ? h->Vd.as<double>() : nullptr; v.Y = h->Yrec.as<double>();
+        return h->launch_observed_chain(v, h->XHrec.as<double>(), h->Erec.as<int32_t>());
+    });
+    if (!rc) h->step += steps;
+    return rc;
 }
 
 int silqr_loop_last_policy(silqr_loop_t *h, double *x_bar, double *u_bar, double *K, int *shared) {

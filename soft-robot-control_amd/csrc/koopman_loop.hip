@@ -17,7 +17,8 @@
 //   solve     the trust-region-free QP on the constant (A_d, B_d), d = 0, all members in one launch (slocp_plan_solve_dev_resident).
 //   fix-up    a member whose QP reports a non-zero status goes on with the previous plan moved up ONE row, its last row held (ros.py:
 //             223-227, whatever rh is); in period 0 such a member gets x0 in every state row and the scaled-down u0 in every input row;
-//             the status is recorded either way (koop_loop_fixup_kernel).
+//             the status is recorded either way (THE PLAN SHIFT of mpc_loop_host.h with row 0 as solved, the idle input u0 through the
+//             input scaling, and the request copied into its record).
 //   sub-steps s = 0..n_keep-1, all of them in ONE launch, one workgroup per member (koop_loop_advance_kernel):
 //               1. u_s = uopt[s / r] * u_factor + u_offset          scale_up of the plan row of the controller step that has fired:
 //                                                                    integer row arithmetic, no interpolation, no gain
@@ -34,21 +35,15 @@
 // The reference reads its input tape at its own knots, so input_hold changes nothing and is not a parameter.
 // Not offered: the start-up phase before t_delay, projecting the y_hist rows, input clipping, dU, input_nullspace,
 // nonlinear_observer, weighting-mode plants, the lifted model as its own plant.  The host shell of a handle and of a run is
-// gusto_loop_host.h, the target window gusto_loop_prep.h.
+// gusto_loop_host.h, the constant-horizon QP and the plan shift mpc_loop_host.h, the target window gusto_loop_prep.h.
 #include "koopman_host.h"
 #include "tpwl_host.h"
-#include "gusto_loop_host.h"
+#include "mpc_loop_host.h"
 
 #include <algorithm>
 #include <cmath>
 
 namespace {
-
-// `count` copies of src (len) behind one another: the constant horizon of the QP
-__global__ __launch_bounds__(256) void koop_loop_tile_kernel(const double *src, int64_t len, int64_t count, double *dst) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + SRH_TID;
-    if (e < len * count) dst[e] = src[e % len];
-}
 
 // scale_down / scale_up of KoopmanScaling (koopman_utils.py:98-107): two operations each, rounded on their own
 __device__ __forceinline__ double koop_scale_down(double v, double off, double fac) { return (v - off) / fac; }
@@ -56,50 +51,6 @@ __device__ __forceinline__ double koop_scale_up(double v, double off, double fac
 #pragma clang fp contract(off)
     const double p = v * fac;
     return p + off;
-}
-
-struct KlFixArgs {
-    int N, n, m, first;
-    const double *xprev, *uprev;        // the plan as the previous period left it (B x (N+1) x n), (B x N x m); not read when first
-    const double *xsol, *usol;          // the QP's answer (may be xout / uout: every element is read by the thread that writes it)
-    const double *x0;                   // (B x n) the request's state
-    const double *u0, *uoff, *ufac;     // (m) each: the raw idle input and the input scaling
-    const int32_t *status;              // (B) the QP's status words
-    double *xout, *uout;                // the plan of this period
-    double *xlift;                      // (B x n) the period's row of the request record, or null
-};
-
-// One workgroup per member.  Every element of the plan as it stands after the fix-up is a function of the inputs alone.
-__global__ __launch_bounds__(256) void koop_loop_fixup_kernel(KlFixArgs a) {
-    const size_t b = blockIdx.x;
-    const int N = a.N, n = a.n, m = a.m, tid = SRH_TID;
-    cgptr xs = (cgptr)a.xsol + b * (size_t)(N + 1) * n, us = (cgptr)a.usol + b * (size_t)N * m;
-    cgptr xp = (cgptr)a.xprev + b * (size_t)(N + 1) * n, up = (cgptr)a.uprev + b * (size_t)N * m;
-    cgptr x0 = (cgptr)a.x0 + b * n;
-    cgptr u0 = (cgptr)a.u0, uoff = (cgptr)a.uoff, ufac = (cgptr)a.ufac;
-    const bool failed = ((cgiptr)a.status)[b] != 0, first = a.first != 0;
-    gptr xo = (gptr)a.xout + b * (size_t)(N + 1) * n, uo = (gptr)a.uout + b * (size_t)N * m;
-    // (the values are formed before the first store of the pass: xsol may be xout)
-    for (int e0 = 0; e0 < (N + 1) * n; e0 += 256) {
-        const int e = e0 + tid;
-        double v = 0.0;
-        if (e < (N + 1) * n) {
-            const int k = e / n, c = e % n;
-            v = !failed ? xs[e] : (first ? x0[c] : xp[(size_t)min(k + 1, N) * n + c]);
-        }
-        if (e < (N + 1) * n) xo[e] = v;
-    }
-    for (int e0 = 0; e0 < N * m; e0 += 256) {
-        const int e = e0 + tid;
-        double v = 0.0;
-        if (e < N * m) {
-            const int k = e / m, c = e % m;
-            v = !failed ? us[e] : (first ? koop_scale_down(u0[c], uoff[c], ufac[c]) : up[(size_t)min(k + 1, N - 1) * m + c]);
-        }
-        if (e < N * m) uo[e] = v;
-    }
-    if (a.xlift)
-        for (int c = tid; c < n; c += 256) ((gptr)a.xlift)[b * n + c] = x0[c];
 }
 
 struct KlAdvArgs {
@@ -255,17 +206,13 @@ __global__ __launch_bounds__(256) void koop_loop_advance_kernel(TpwlDev TL, KlAd
 
 }  // namespace
 
-struct skoop_loop : LoopCore {
+struct skoop_loop : MpcLoopCore {
     skoop *koop = nullptr;
     stpwl *plant = nullptr;
-    slocp_plan_t *qp = nullptr;
     int np = 0, ny = 0, r = 1;          // plant states, measurements, simulation steps per controller step
-    bool has_Qzf = false, horizon_resident = false;
     std::vector<double> Ch, yrh, u0h;   // host copies of C, y_ref and u0 (the reset forms y_0 from them)
-    // cst: C | y_ref | u0; Ah, Bh, dh: the QP's constant horizon tiled over B x N (d = 0); zero: B zeros (the QP's delta and omega);
-    // xalt, ualt: the plan the solve writes (swapped with xopt, uopt behind the fix-up kernel); zf: the terminal target; xp, ycur: where
-    // the plants and their measurements stand
-    srh::DevBuf cst, Ah, Bh, dh, zero, xalt, ualt, zf, xp, ycur;
+    // cst: C | y_ref | u0; xp, ycur: where the plants and their measurements stand (the QP's horizon has d = 0)
+    srh::DevBuf cst, xp, ycur;
     LoopRec XLrec, YPd, UAd;            // record: the requests (P x B x n); inputs: recorded measurements (B x (S + 1) x ny), inputs (B x S x m)
     // the re-projection onto Y (skoop_loop_set_reproject): Y on the host and on the device (A | b), where the used sample and its status
     // word stand (row 0 of the next run's records), the two records
@@ -278,10 +225,7 @@ struct skoop_loop : LoopCore {
         recs.push_back(&XLrec); recs.push_back(&YUrec); recs.push_back(&PJrec);
         ins.push_back(&YPd); ins.push_back(&UAd);
     }
-    ~skoop_loop() {
-        drain();
-        if (qp) slocp_plan_destroy(qp);
-    }
+    ~skoop_loop() { drain(); }
     const double *scale() const { return koop->scale.as<double>(); }
     KlAdvArgs adv_args() const {
         KlAdvArgs a{};
@@ -296,17 +240,13 @@ struct skoop_loop : LoopCore {
         }
         return a;
     }
-    KlFixArgs fix_args() const {
-        KlFixArgs c{};
+    // the fix-up: row 0 as solved, the scaled-down idle input behind a failed first solve
+    ShiftArgs shift_args() const {
+        ShiftArgs c{};
         c.N = N; c.n = n; c.m = m;
-        c.u0 = cst.as<double>() + (size_t)ny * np + ny;
+        c.u_idle = cst.as<double>() + (size_t)ny * np + ny;
         c.uoff = scale() + 2 * ny; c.ufac = c.uoff + m;
         return c;
-    }
-    int launch_fixup(const KlFixArgs &c) const {
-        koop_loop_fixup_kernel<<<(unsigned)B, 256, 0, stream>>>(c);
-        SRH_CHECK_HIP(hipGetLastError());
-        return SRH_OK;
     }
     // the launch, and behind it the ring's head and count as the n_keep pushes leave them
     int launch_advance(const KlAdvArgs &a) {
@@ -330,10 +270,9 @@ int skoop_loop_create(skoop_loop_t **out, skoop_t *koop, const slocp_problem *pr
     SRH_REQUIRE(N >= 1 && Ts > 0.0 && dt_sim > 0.0, "skoop_loop_create: need a horizon N >= 1, Ts > 0 and dt_sim > 0");
     SRH_REQUIRE(prob->n_x == n && prob->n_u == m, "skoop_loop_create: the QP has n_x = %d, n_u = %d, the lift writes %d states and the model has n_u = %d",
                 prob->n_x, prob->n_u, n, m);
-    SRH_REQUIRE(!prob->tr_active, "skoop_loop_create: the MPC QP has no trust region (is_tr_active=False, baselines/ros.py:161)");
-    SRH_REQUIRE(prob->ndU == 0, "skoop_loop_create: input-rate rows (dU) are not offered by the resident loop");
+    int rc;
+    if ((rc = MpcLoopCore::check_problem("skoop_loop_create", prob, m))) return rc;
     SRH_REQUIRE(n <= 96, "skoop_loop_create: n_lift = %d exceeds the limit n_lift <= 96 of the QP", n);
-    SRH_REQUIRE(m <= 16, "skoop_loop_create: n_u = %d exceeds the limit n_u <= 16 of the advance kernel", m);
     const double ratio = Ts / dt_sim, rr = std::round(ratio);
     SRH_REQUIRE(!(std::fabs(ratio - rr) > 1e-9) && rr >= 1.0 && rr <= 1e6,
                 "skoop_loop_create: Ts / dt_sim = %.12g is not an integer >= 1 (the controller step must be a whole number of simulation steps)", ratio);
@@ -353,13 +292,10 @@ int skoop_loop_create(skoop_loop_t **out, skoop_t *koop, const slocp_problem *pr
     skoop_loop *h = new skoop_loop();
     auto fail = [&](int code) { delete h; return code; };
     h->koop = koop; h->plant = plant; h->np = np; h->ny = ny; h->r = r; h->lds = lds;
-    h->has_Qzf = prob->Qzf != nullptr;
-    int rc;
-    if ((rc = slocp_plan_create(&h->qp, prob, B))) return fail(rc);
     const char *what = "set up the advance kernel / the stream";
     if (hipFuncSetAttribute((const void *)koop_loop_advance_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return fail(loop_setup_failed("skoop_loop_create", what));
-    const size_t D = sizeof(double), Bz = (size_t)B, Nz = (size_t)N;
+    const size_t D = sizeof(double), Bz = (size_t)B;
     if ((rc = h->setup("skoop_loop_create", what, N, n, m, prob->n_z, B, Ts, dt_sim, n_keep, max_steps_per_run, (size_t)prob->n_z))) return fail(rc);
     // the plant's records and noise have the plant's width, not the QP's
     h->Xrec.shape(D * std::max(np, 1), 1); h->Wd.shape(D * std::max(np, 1), 0);
@@ -376,21 +312,12 @@ int skoop_loop_create(skoop_loop_t **out, skoop_t *koop, const slocp_problem *pr
     std::vector<double> c(h->Ch);                        // C (none without a plant) | y_ref | u0
     c.insert(c.end(), h->yrh.begin(), h->yrh.end());
     c.insert(c.end(), h->u0h.begin(), h->u0h.end());
-    if ((rc = h->alloc_recs({&h->Yrec, &h->XLrec})) || (rc = h->cst.upload(c.data(), D * c.size())) || (rc = h->Ah.alloc(D * Bz * Nz * n * n)) ||
-        (rc = h->Bh.alloc(D * Bz * Nz * n * m)) || (rc = h->dh.alloc(D * Bz * Nz * n)) || (rc = h->zero.alloc(D * Bz)) ||
-        (rc = h->xalt.alloc(D * Bz * (Nz + 1) * n)) || (rc = h->ualt.alloc(D * Bz * Nz * m)) || (rc = h->zf.alloc(D * Bz * prob->n_z)) ||
+    if ((rc = h->alloc_recs({&h->Yrec, &h->XLrec})) || (rc = h->cst.upload(c.data(), D * c.size())) ||
         (rc = h->xp.alloc(D * Bz * std::max(np, 1))) || (rc = h->ycur.alloc(D * Bz * ny)))
         return fail(rc);
-    // constant (A, B) tiled over B x N once, d = 0; the prepare kernel's state source (xcur) is zeros: the lift overwrites x0 behind it
-    srh::DevBuf a1, b1;
-    if ((rc = a1.upload(A, D * n * n)) || (rc = b1.upload(Bm, D * n * m))) return fail(rc);
-    const int64_t cnt = B * N;
-    koop_loop_tile_kernel<<<(unsigned)srh::cdiv(cnt * n * n, 256), 256, 0, h->stream>>>(a1.as<double>(), (int64_t)n * n, cnt, h->Ah.as<double>());
-    koop_loop_tile_kernel<<<(unsigned)srh::cdiv(cnt * n * m, 256), 256, 0, h->stream>>>(b1.as<double>(), (int64_t)n * m, cnt, h->Bh.as<double>());
-    if (hipGetLastError() != hipSuccess || hipMemsetAsync(h->dh.p, 0, D * Bz * Nz * n, h->stream) != hipSuccess ||
-        hipMemsetAsync(h->zero.p, 0, D * Bz, h->stream) != hipSuccess || hipMemsetAsync(h->xcur.p, 0, D * Bz * n, h->stream) != hipSuccess ||
-        hipStreamSynchronize(h->stream) != hipSuccess)
-        return fail(loop_setup_failed("skoop_loop_create", "tile the horizon"));
+    // the prepare kernel's state source (xcur) is zeros: the lift overwrites x0 behind it; the QP's horizon is (A, B), d = 0
+    if (hipMemsetAsync(h->xcur.p, 0, D * Bz * n, h->stream) != hipSuccess) return fail(loop_setup_failed("skoop_loop_create", "tile the horizon"));
+    if ((rc = h->make_horizon("skoop_loop_create", prob, A, Bm, nullptr))) return fail(rc);
     h->Xrec.row0 = h->xp.p; h->Yrec.row0 = h->ycur.p;
     *out = h;
     return SRH_OK;
@@ -473,36 +400,24 @@ int koop_loop_run(skoop_loop *h, const char *who, int periods, const double *W, 
     SRH_REQUIRE(h->have_state, "%s: no measurement history yet (call skoop_loop_reset first)", who);
     SRH_REQUIRE(h->plant || Y_plant, "%s: the loop was created without a plant (replay only): Y_plant is required", who);
     h->YUrec.host = Y_used; h->PJrec.host = proj;
-    const size_t B = (size_t)h->B;
     const bool replay = Y_plant != nullptr;
     h->Wd.host = (void *)((W && !replay) ? W : nullptr); h->Vd.host = (void *)((V && !replay) ? V : nullptr);
     h->YPd.host = (void *)Y_plant; h->UAd.host = (void *)U_applied;
     h->Xrec.host = (h->plant && !replay) ? X : nullptr; h->Yrec.host = Y; h->Urec.host = U; h->XLrec.host = Xlift;
     h->Jrec.host = J; h->Srec.host = status; h->Irec.host = iters;
     // the prepare kernel copies zeros into x0 and forms the target window; the ring lift overwrites x0 behind it
-    const PrepUnit u{h->xcur.as<double>(), nullptr, nullptr, (h->has_z && h->has_Qzf) ? h->zf.as<double>() : nullptr, false};
+    const PrepUnit u{h->xcur.as<double>(), nullptr, nullptr, h->zf_dev(), false};
     return loop_run_periods(h, "skoop_loop_run", periods, u, [&](int p, const PrepArgs &a, const LoopRows &r) -> int {
         int rc;
         KoopLiftArgs la{};
         la.rows = h->B; la.ring = h->koop->ring.as<double>(); la.head = h->koop->head; la.out = a.x0;
         if ((rc = koop_launch_lift(h->koop, KP_RING, la, h->stream))) return rc;
-        // the solve writes (xalt, ualt); (xopt, uopt) still hold the previous period's plan for the fix-up
-        if ((rc = slocp_plan_solve_dev_resident(h->qp, h->horizon_resident ? 0 : 1, h->Ah.as<double>(), h->Bh.as<double>(), h->dh.as<double>(), a.x0,
-                                                nullptr, h->zero.as<double>(), h->zero.as<double>(), h->has_z ? a.z : nullptr, a.zf,
-                                                h->has_ud ? a.ud : nullptr, h->xalt.as<double>(), h->ualt.as<double>(), nullptr,
-                                                h->Jrec.as<double>() + p * B, h->Srec.as<int32_t>() + p * B, h->Irec.as<int32_t>() + p * B,
-                                                (void *)h->stream)))
-            return rc;
-        h->horizon_resident = true;
-        KlFixArgs c = h->fix_args();
-        c.first = a.first;
-        c.xprev = h->xopt.as<double>(); c.uprev = h->uopt.as<double>();
-        c.xsol = h->xalt.as<double>(); c.usol = h->ualt.as<double>();
-        c.x0 = a.x0; c.status = h->Srec.as<int32_t>() + p * B;
-        c.xout = h->xalt.as<double>(); c.uout = h->ualt.as<double>();
-        c.xlift = h->XLrec.as<double>() + (size_t)p * B * h->n;
-        if ((rc = h->launch_fixup(c))) return rc;
-        std::swap(h->xopt.p, h->xalt.p); std::swap(h->uopt.p, h->ualt.p);            // (same sizes; the launches hold the pointers they were given)
+        if ((rc = h->solve(p, a))) return rc;
+        ShiftArgs c = h->shift_args();
+        h->shift_in_place(c, p, a);
+        c.xlift = h->XLrec.as<double>() + (size_t)p * (size_t)h->B * h->n;
+        if ((rc = h->launch_shift(c))) return rc;
+        h->take_solution();
         KlAdvArgs v = h->adv_args();
         v.plant = replay ? 0 : 1;
         v.uopt = h->uopt.as<double>();
@@ -566,10 +481,7 @@ int skoop_loop_set_reproject(skoop_loop_t *h, const double *A, const double *b, 
 }
 
 int skoop_loop_last_inputs(skoop_loop_t *h, double *x0, double *z, double *zf, double *u_des) {
-    int rc = loop_last_inputs(h, "skoop_loop_last_inputs", x0, nullptr, nullptr, z, u_des);
-    if (rc) return rc;
-    if (zf && h->has_z && h->has_Qzf && (rc = h->zf.download(zf, sizeof(double) * h->B * h->nz))) return rc;
-    return SRH_OK;
+    return mpc_last_inputs(h, "skoop_loop_last_inputs", x0, z, zf, u_des);
 }
 
 int skoop_loop_last_plan(skoop_loop_t *h, double *xopt, double *uopt) { return loop_last_plan(h, "skoop_loop_last_plan", xopt, uopt); }
@@ -580,22 +492,7 @@ int skoop_loop_fixup(skoop_loop_t *h, const double *xopt_prev, const double *uop
                      const int32_t *status, int first, double *xopt_out, double *uopt_out) {
     SRH_REQUIRE(h && xopt && uopt && x0 && status && xopt_out && uopt_out, "skoop_loop_fixup: null argument");
     SRH_REQUIRE(first || (xopt_prev && uopt_prev), "skoop_loop_fixup: the previous plan is required behind the first period");
-    const size_t D = sizeof(double), B = (size_t)h->B, N = h->N, n = h->n, m = h->m;
-    srh::DevBuf dxp, dup, dxs, dus, dx0, dst, dxo, duo;
-    int rc;
-    if ((xopt_prev && (rc = dxp.upload(xopt_prev, D * B * (N + 1) * n))) || (uopt_prev && (rc = dup.upload(uopt_prev, D * B * N * m))) ||
-        (rc = dxs.upload(xopt, D * B * (N + 1) * n)) || (rc = dus.upload(uopt, D * B * N * m)) || (rc = dx0.upload(x0, D * B * n)) ||
-        (rc = dst.upload(status, sizeof(int32_t) * B)) || (rc = dxo.alloc(D * B * (N + 1) * n)) || (rc = duo.alloc(D * B * N * m)))
-        return rc;
-    KlFixArgs c = h->fix_args();
-    c.first = first ? 1 : 0;
-    // (a first period never reads the previous plan: the solve's arrays stand in for the missing pointers)
-    c.xprev = xopt_prev ? dxp.as<double>() : dxs.as<double>(); c.uprev = uopt_prev ? dup.as<double>() : dus.as<double>();
-    c.xsol = dxs.as<double>(); c.usol = dus.as<double>(); c.x0 = dx0.as<double>(); c.status = dst.as<int32_t>();
-    c.xout = dxo.as<double>(); c.uout = duo.as<double>();
-    if ((rc = loop_wait(h->launch_fixup(c), h->stream))) return rc;
-    if ((rc = dxo.download(xopt_out, D * B * (N + 1) * n)) || (rc = duo.download(uopt_out, D * B * N * m))) return rc;
-    return SRH_OK;
+    return mpc_shift_alone(h, h->shift_args(), xopt_prev, uopt_prev, xopt, uopt, x0, status, first, xopt_out, uopt_out, nullptr);
 }
 
 }  // extern "C"
@@ -633,21 +530,11 @@ int koop_loop_advance(skoop_loop *h, const char *who, const double *uopt, const 
     v.Yp_.Yu = Y_used ? dYu.as<double>() : nullptr; v.Yp_.proj = proj ? dPj.as<int32_t>() : nullptr;
     if ((rc = loop_wait(h->launch_advance(v), h->stream))) return rc;
     // rows 1 .. n_keep of the n_keep + 1 row blocks -> the caller's (B x n_keep x .) arrays
-    std::vector<double> blk;
-    auto rows = [&](const srh::DevBuf &d, double *dst, size_t w) -> int {
-        blk.resize(B * (nk + 1) * w);
-        int e = d.download(blk.data(), D * blk.size());
-        for (size_t b = 0; !e && b < B; ++b) std::copy(blk.begin() + (b * (nk + 1) + 1) * w, blk.begin() + (b + 1) * (nk + 1) * w, dst + b * nk * w);
-        return e;
-    };
-    if ((!replay && (rc = rows(dX, X, np))) || (rc = rows(dY, Y, ny)) || (rc = dU.download(U, D * B * nk * m)) ||
-        (rc = di.download(idx, sizeof(int32_t) * B * nk)) || (Y_used && (rc = rows(dYu, Y_used, ny))))
+    auto rows = [&](const srh::DevBuf &d, void *dst, size_t w) { return loop_rows_to_host(d, dst, B, nk, w, 1); };
+    if ((!replay && (rc = rows(dX, X, D * np))) || (rc = rows(dY, Y, D * ny)) || (rc = dU.download(U, D * B * nk * m)) ||
+        (rc = di.download(idx, sizeof(int32_t) * B * nk)) || (Y_used && (rc = rows(dYu, Y_used, D * ny))) ||
+        (proj && (rc = rows(dPj, proj, sizeof(int32_t)))))
         return rc;
-    if (proj) {
-        std::vector<int32_t> w(B * (nk + 1));
-        if ((rc = dPj.download(w.data(), sizeof(int32_t) * w.size()))) return rc;
-        for (size_t b = 0; b < B; ++b) std::copy(w.begin() + b * (nk + 1) + 1, w.begin() + (b + 1) * (nk + 1), proj + b * nk);
-    }
     return SRH_OK;
 }
 

@@ -13,7 +13,8 @@
 //             the tiled horizon goes through the plan's transposes once).
 //   chain     row 0 of the plan's states is set to x0_p; a member whose QP reports a non-zero status gets the previous plan moved up one
 //             row with its last row held (ros.py:223-227), in period 0 x0_0 in every state row and zero inputs; the status is recorded
-//             either way.  The next request's x0 is read off the plan as it stands after this (rompc_chain_kernel).
+//             either way.  The next request's x0 is read off the plan as it stands after this (THE PLAN SHIFT of mpc_loop_host.h with
+//             row 0 pinned, no idle input and x0_next).
 //   sub-steps s = 0..n_replan-1 at tau = s dt_sim, (j_s, theta_s) of sgusto_loop_schedule, ubar_s / xbar_s = lo + theta (hi - lo) with
 //             the input held over the last interval (rompc_loop_advance_kernel):
 //               1. y_s = (C x_s + y_ref) + v_s                      the measurement of the current plant state
@@ -22,67 +23,15 @@
 //               4. x_{s+1} = A_p[i] x_s + B_p[i] u_s + d_p[i] (+ w_s), i the plant's nearest point to x_s (tpwl::nearest_wave), or
 //                  x_{s+1} read from the given plant record.
 // Not offered: the start-up phase before t_delay, the full-order state and its projection per step, input clipping, dU rows,
-// input_nullspace.  The host shell of a handle and of a run is gusto_loop_host.h, the target window gusto_loop_prep.h.
+// input_nullspace.  The host shell of a handle and of a run is gusto_loop_host.h, the constant-horizon QP and the plan shift
+// mpc_loop_host.h, the target window gusto_loop_prep.h.
 #include "rompc_host.h"
 #include "tpwl_host.h"
-#include "gusto_loop_host.h"
+#include "mpc_loop_host.h"
 
 #include <algorithm>
 
 namespace {
-
-// `count` copies of src (len) behind one another: the constant horizon of the QP
-__global__ __launch_bounds__(256) void rompc_tile_kernel(const double *src, int64_t len, int64_t count, double *dst) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + SRH_TID;
-    if (e < len * count) dst[e] = src[e % len];
-}
-
-struct ChainArgs {
-    int N, n, m, first;
-    int j_end;                          // interval and position of tau = n_replan dt_sim in the plan
-    double th_end;
-    const double *xprev, *uprev;        // the plan as the previous period left it (B x (N+1) x n), (B x N x m); not read when first
-    const double *xsol, *usol;          // the QP's answer (may be xout / uout: every element is read by the thread that writes it)
-    const double *x0;                   // (B x n) the request's state
-    const int32_t *status;              // (B) the QP's status words
-    double *xout, *uout, *x0_next;      // the plan of this period, and (B x n) the next request's state
-};
-
-// One workgroup per member.  Every element of the plan as it stands after the fix-up is a function of the inputs alone (state_at /
-// input_at below), so the copies and the interpolated request state are formed from the same values and nothing is read back.
-__global__ __launch_bounds__(256) void rompc_chain_kernel(ChainArgs a) {
-    const size_t b = blockIdx.x;
-    const int N = a.N, n = a.n, m = a.m, tid = SRH_TID;
-    cgptr xs = (cgptr)a.xsol + b * (size_t)(N + 1) * n, us = (cgptr)a.usol + b * (size_t)N * m;
-    cgptr xp = (cgptr)a.xprev + b * (size_t)(N + 1) * n, up = (cgptr)a.uprev + b * (size_t)N * m;
-    cgptr x0 = (cgptr)a.x0 + b * n;
-    const bool failed = ((cgiptr)a.status)[b] != 0, first = a.first != 0;
-    auto state_at = [&](int k, int c) -> double {
-        if (failed) return first ? x0[c] : (k == 0 ? x0[c] : xp[(size_t)min(k + 1, N) * n + c]);
-        return k == 0 ? x0[c] : xs[(size_t)k * n + c];
-    };
-    auto input_at = [&](int k, int c) -> double {
-        if (failed) return first ? 0.0 : up[(size_t)min(k + 1, N - 1) * m + c];
-        return us[(size_t)k * m + c];
-    };
-    gptr xo = (gptr)a.xout + b * (size_t)(N + 1) * n, uo = (gptr)a.uout + b * (size_t)N * m;
-    // (the values are formed before the first store of the pass: xsol may be xout)
-    for (int e0 = 0; e0 < (N + 1) * n; e0 += 256) {
-        const int e = e0 + tid;
-        double v = 0.0;
-        if (e < (N + 1) * n) v = state_at(e / n, e % n);
-        if (e < (N + 1) * n) xo[e] = v;
-    }
-    for (int e0 = 0; e0 < N * m; e0 += 256) {
-        const int e = e0 + tid;
-        double v = 0.0;
-        if (e < N * m) v = input_at(e / m, e % m);
-        if (e < N * m) uo[e] = v;
-    }
-    // the next request: the plan point (gusto_loop_prep.h) of rows j_end, j_end + 1.  Row 0 is x0 in every branch, rows >= 1 are read
-    // from xprev / xsol, which this kernel writes only where xsol is xout -- and there with the value read.
-    for (int c = tid; c < n; c += 256) ((gptr)a.x0_next)[b * n + c] = lerp(state_at(a.j_end, c), state_at(a.j_end + 1, c), a.th_end);
-}
 
 struct RlAdvArgs {
     int N, n_keep, n, m, ny, nz;
@@ -227,27 +176,20 @@ __global__ __launch_bounds__(256) void rompc_loop_advance_kernel(TpwlDev TL, RlA
 
 }  // namespace
 
-struct srompc_loop : LoopCore {
+struct srompc_loop : MpcLoopCore {
     srompc *ctrl = nullptr;
     stpwl *plant = nullptr;
-    slocp_plan_t *qp = nullptr;
     int ny = 0, nzc = 0;                // the controller's measurement width and the width of its output map (the Z record)
     int j_end = 0;
     double th_end = 0.0;
-    bool has_Qzf = false, horizon_resident = false;
-    // cst: [F B L]^T | d | K | C | y_ref | H (re-formed from the controller's host copies at every reset); Ah, Bh, dh: the QP's constant
-    // horizon tiled over B x N; zero: B zeros (the QP's delta and omega); xreq: the next request's state; xalt, ualt: the plan the solve
-    // writes (swapped with xopt, uopt behind the chain kernel); zf: the terminal target
-    srh::DevBuf cst, Ah, Bh, dh, zero, xreq, xalt, ualt, zf;
+    // cst: [F B L]^T | d | K | C | y_ref | H (re-formed from the controller's host copies at every reset); xreq: the next request's state
+    srh::DevBuf cst, xreq;
     LoopRec UBrec, XBrec, XPd;          // records u_bar (B x S x m), x_bar (B x (S + 1) x n); input: the recorded plant (B x (S + 1) x n)
     __attribute__((always_inline)) srompc_loop() {            // (inlined: no constructor among the library's dynamic symbols)
         recs.push_back(&XBrec); recs.push_back(&UBrec);
         ins.push_back(&XPd);
     }
-    ~srompc_loop() {
-        drain();
-        if (qp) slocp_plan_destroy(qp);
-    }
+    ~srompc_loop() { drain(); }
     size_t cst_doubles() const { return (size_t)(n + m + ny) * n + n + (size_t)m * n + (size_t)ny * n + ny + (size_t)nzc * n; }
     // [F B L]^T and the rest from the controller's host copies, as they stand now (blocking: reset path)
     int upload_consts() {
@@ -276,15 +218,11 @@ struct srompc_loop : LoopCore {
         a.B = B;
         return a;
     }
-    ChainArgs chain_args() const {
-        ChainArgs c{};
-        c.N = N; c.n = n; c.m = m; c.j_end = j_end; c.th_end = th_end;
+    // the chain: row 0 pinned to the request, zero inputs behind a failed first solve, the next request read off the plan
+    ShiftArgs shift_args() const {
+        ShiftArgs c{};
+        c.N = N; c.n = n; c.m = m; c.pin_row0 = 1; c.j_end = j_end; c.th_end = th_end;
         return c;
-    }
-    int launch_chain(const ChainArgs &c) const {
-        rompc_chain_kernel<<<(unsigned)B, 256, 0, stream>>>(c);
-        SRH_CHECK_HIP(hipGetLastError());
-        return SRH_OK;
     }
     int launch_advance(const RlAdvArgs &a) const {
         rompc_loop_advance_kernel<<<(unsigned)B, 256, lds, stream>>>(a.plant ? plant->view() : TpwlDev{}, a);
@@ -304,35 +242,29 @@ int srompc_loop_create(srompc_loop_t **out, srompc_t *ctrl, const slocp_problem 
     SRH_REQUIRE(N >= 1 && dt_mpc > 0.0, "srompc_loop_create: need a horizon N >= 1 and dt_mpc > 0");
     SRH_REQUIRE(prob->n_x == n && prob->n_u == m, "srompc_loop_create: the QP has n_x = %d, n_u = %d, the controller n_x = %d, n_u = %d", prob->n_x,
                 prob->n_u, n, m);
-    SRH_REQUIRE(!prob->tr_active, "srompc_loop_create: the MPC QP has no trust region (is_tr_active=False, baselines/ros.py:161)");
-    SRH_REQUIRE(prob->ndU == 0, "srompc_loop_create: input-rate rows (dU) are not offered by the resident loop");
-    SRH_REQUIRE(m <= 16, "srompc_loop_create: n_u = %d exceeds the limit n_u <= 16 of the advance kernel", m);
+    int rc;
+    if ((rc = MpcLoopCore::check_problem("srompc_loop_create", prob, m))) return rc;
     SRH_REQUIRE(n <= 128, "srompc_loop_create: n_x = %d exceeds the limit n_x <= 128 of the advance kernel", n);
     if (plant) {
         SRH_REQUIRE(plant->n == n && plant->m == m, "srompc_loop_create: the plant has n_x = %d, n_u = %d, the controller n_x = %d, n_u = %d", plant->n,
                     plant->m, n, m);
         SRH_REQUIRE(plant->has_discrete, "srompc_loop_create: the plant has not been pre-discretised at dt_sim");
     }
-    int rc;
     if ((rc = loop_check_periods("srompc_loop_create", N, dt_mpc, dt_sim, n_replan, max_steps_per_run))) return rc;
     const size_t lds = rl_advance_lds_bytes(n, m, ny, plant != nullptr);
     SRH_REQUIRE(lds <= (size_t)160 * 1024, "srompc_loop_create: the advance kernel needs %zu bytes of LDS (160 KiB available)", lds);
     srompc_loop *h = new srompc_loop();
     auto fail = [&](int code) { delete h; return code; };
     h->ctrl = ctrl; h->plant = plant; h->ny = ny; h->nzc = ctrl->nz; h->lds = lds;
-    h->has_Qzf = prob->Qzf != nullptr;
-    if ((rc = slocp_plan_create(&h->qp, prob, B))) return fail(rc);
     const char *what = "set up the advance kernel / the stream";
     if (hipFuncSetAttribute((const void *)rompc_loop_advance_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return fail(loop_setup_failed("srompc_loop_create", what));
-    const size_t D = sizeof(double), Bz = (size_t)B, Nz = (size_t)N;
+    const size_t D = sizeof(double), Bz = (size_t)B;
     h->XHrec.shape(D * n, 1); h->Yrec.shape(D * ny, 0); h->Vd.shape(D * ny, 0);
     h->UBrec.shape(D * m, 0); h->XBrec.shape(D * n, 1); h->XPd.shape(D * n, 1);
     if ((rc = h->setup("srompc_loop_create", what, N, n, m, prob->n_z, B, dt_mpc, dt_sim, n_replan, max_steps_per_run, (size_t)ctrl->nz)) ||
         (rc = h->alloc_recs({&h->XHrec, &h->Yrec, &h->UBrec, &h->XBrec})) || (rc = h->cst.alloc(D * h->cst_doubles())) ||
-        (rc = h->Ah.alloc(D * Bz * Nz * n * n)) || (rc = h->Bh.alloc(D * Bz * Nz * n * m)) || (rc = h->dh.alloc(D * Bz * Nz * n)) ||
-        (rc = h->zero.alloc(D * Bz)) || (rc = h->xreq.alloc(D * Bz * n)) || (rc = h->xalt.alloc(D * Bz * (Nz + 1) * n)) ||
-        (rc = h->ualt.alloc(D * Bz * Nz * m)) || (rc = h->zf.alloc(D * Bz * prob->n_z)))
+        (rc = h->xreq.alloc(D * Bz * n)) || (rc = h->make_horizon("srompc_loop_create", prob, A_mpc, B_mpc, d_mpc)))
         return fail(rc);
     {
         // where the period ends in the plan: the schedule's rule for tau = n_replan dt_sim, every product and sum rounded on its own
@@ -343,16 +275,6 @@ int srompc_loop_create(srompc_loop_t **out, srompc_t *ctrl, const slocp_problem 
         const double back = (double)h->j_end * dt_mpc;
         h->th_end = (tau - back) / dt_mpc;
     }
-    // constant (A, B, d) tiled over B x N once
-    srh::DevBuf a1, b1, d1;
-    if ((rc = a1.upload(A_mpc, D * n * n)) || (rc = b1.upload(B_mpc, D * n * m)) || (rc = d1.upload(d_mpc, D * n))) return fail(rc);
-    const int64_t cnt = B * N;
-    rompc_tile_kernel<<<(unsigned)srh::cdiv(cnt * n * n, 256), 256, 0, h->stream>>>(a1.as<double>(), (int64_t)n * n, cnt, h->Ah.as<double>());
-    rompc_tile_kernel<<<(unsigned)srh::cdiv(cnt * n * m, 256), 256, 0, h->stream>>>(b1.as<double>(), (int64_t)n * m, cnt, h->Bh.as<double>());
-    rompc_tile_kernel<<<(unsigned)srh::cdiv(cnt * n, 256), 256, 0, h->stream>>>(d1.as<double>(), (int64_t)n, cnt, h->dh.as<double>());
-    if (hipGetLastError() != hipSuccess || hipMemsetAsync(h->zero.p, 0, D * Bz, h->stream) != hipSuccess ||
-        hipStreamSynchronize(h->stream) != hipSuccess)
-        return fail(loop_setup_failed("srompc_loop_create", "tile the horizon"));
     h->Xrec.row0 = h->xcur.p; h->XHrec.row0 = ctrl->est();
     *out = h;
     return SRH_OK;
@@ -389,7 +311,6 @@ int srompc_loop_run(srompc_loop_t *h, int periods, const double *W, const double
     SRH_REQUIRE(periods >= 1, "srompc_loop_run: periods must be positive");
     SRH_REQUIRE(h->have_state, "srompc_loop_run: no plant state and estimate yet (call srompc_loop_reset first)");
     SRH_REQUIRE(h->plant || X_plant, "srompc_loop_run: the loop was created without a plant (replay only): X_plant is required");
-    const size_t B = (size_t)h->B;
     h->Wd.host = (void *)W; h->Vd.host = (void *)V; h->XPd.host = (void *)X_plant;
     h->Xrec.host = X; h->XHrec.host = XH; h->Yrec.host = Y; h->Zrec.host = Z; h->Urec.host = U; h->UBrec.host = Ubar; h->XBrec.host = Xbar;
     h->Jrec.host = J; h->Srec.host = status; h->Irec.host = iters;
@@ -397,25 +318,15 @@ int srompc_loop_run(srompc_loop_t *h, int periods, const double *W, const double
     double *xcur = h->xcur.as<double>(), *est = h->ctrl->est();
     // the request starts from xreq (the estimate of the reset, then the plan's end); no output map for the prepare kernel: row 0 of X and
     // XH is where the loops stand (LoopRec::row0), row 0 of Z the advance kernel's
-    const PrepUnit u{h->xreq.as<double>(), nullptr, nullptr, (h->has_z && h->has_Qzf) ? h->zf.as<double>() : nullptr, false};
+    const PrepUnit u{h->xreq.as<double>(), nullptr, nullptr, h->zf_dev(), false};
     return loop_run_periods(h, "srompc_loop_run", periods, u, [&](int p, const PrepArgs &a, const LoopRows &r) -> int {
         int rc;
-        // the solve writes (xalt, ualt); (xopt, uopt) still hold the previous period's plan for the chain
-        if ((rc = slocp_plan_solve_dev_resident(h->qp, h->horizon_resident ? 0 : 1, h->Ah.as<double>(), h->Bh.as<double>(), h->dh.as<double>(), a.x0,
-                                                nullptr, h->zero.as<double>(), h->zero.as<double>(), h->has_z ? a.z : nullptr, a.zf,
-                                                h->has_ud ? a.ud : nullptr, h->xalt.as<double>(), h->ualt.as<double>(), nullptr,
-                                                h->Jrec.as<double>() + p * B, h->Srec.as<int32_t>() + p * B, h->Irec.as<int32_t>() + p * B,
-                                                (void *)h->stream)))
-            return rc;
-        h->horizon_resident = true;
-        ChainArgs c = h->chain_args();
-        c.first = a.first;
-        c.xprev = h->xopt.as<double>(); c.uprev = h->uopt.as<double>();
-        c.xsol = h->xalt.as<double>(); c.usol = h->ualt.as<double>();
-        c.x0 = a.x0; c.status = h->Srec.as<int32_t>() + p * B;
-        c.xout = h->xalt.as<double>(); c.uout = h->ualt.as<double>(); c.x0_next = h->xreq.as<double>();
-        if ((rc = h->launch_chain(c))) return rc;
-        std::swap(h->xopt.p, h->xalt.p); std::swap(h->uopt.p, h->ualt.p);            // (same sizes; the launches hold the pointers they were given)
+        if ((rc = h->solve(p, a))) return rc;
+        ShiftArgs c = h->shift_args();
+        h->shift_in_place(c, p, a);
+        c.x0_next = h->xreq.as<double>();
+        if ((rc = h->launch_shift(c))) return rc;
+        h->take_solution();
         RlAdvArgs v = h->adv_args();
         v.plant = replay ? 0 : 1; v.z0 = p == 0 ? 1 : 0;
         v.xopt = h->xopt.as<double>(); v.uopt = h->uopt.as<double>();
@@ -431,10 +342,7 @@ int srompc_loop_run(srompc_loop_t *h, int periods, const double *W, const double
 }
 
 int srompc_loop_last_inputs(srompc_loop_t *h, double *x0, double *z, double *zf, double *u_des) {
-    int rc = loop_last_inputs(h, "srompc_loop_last_inputs", x0, nullptr, nullptr, z, u_des);
-    if (rc) return rc;
-    if (zf && h->has_z && h->has_Qzf && (rc = h->zf.download(zf, sizeof(double) * h->B * h->nz))) return rc;
-    return SRH_OK;
+    return mpc_last_inputs(h, "srompc_loop_last_inputs", x0, z, zf, u_des);
 }
 
 int srompc_loop_last_plan(srompc_loop_t *h, double *xopt, double *uopt) { return loop_last_plan(h, "srompc_loop_last_plan", xopt, uopt); }
@@ -445,24 +353,7 @@ int srompc_loop_chain(srompc_loop_t *h, const double *xopt_prev, const double *u
                       const int32_t *status, int first, double *xopt_out, double *uopt_out, double *x0_next) {
     SRH_REQUIRE(h && xopt && uopt && x0 && status && xopt_out && uopt_out && x0_next, "srompc_loop_chain: null argument");
     SRH_REQUIRE(first || (xopt_prev && uopt_prev), "srompc_loop_chain: the previous plan is required behind the first period");
-    const size_t D = sizeof(double), B = (size_t)h->B, N = h->N, n = h->n, m = h->m;
-    srh::DevBuf dxp, dup, dxs, dus, dx0, dst, dxo, duo, dxn;
-    int rc;
-    if ((xopt_prev && (rc = dxp.upload(xopt_prev, D * B * (N + 1) * n))) || (uopt_prev && (rc = dup.upload(uopt_prev, D * B * N * m))) ||
-        (rc = dxs.upload(xopt, D * B * (N + 1) * n)) || (rc = dus.upload(uopt, D * B * N * m)) || (rc = dx0.upload(x0, D * B * n)) ||
-        (rc = dst.upload(status, sizeof(int32_t) * B)) || (rc = dxo.alloc(D * B * (N + 1) * n)) || (rc = duo.alloc(D * B * N * m)) ||
-        (rc = dxn.alloc(D * B * n)))
-        return rc;
-    ChainArgs c = h->chain_args();
-    c.first = first ? 1 : 0;
-    // (a first period never reads the previous plan: the solve's arrays stand in for the missing pointers)
-    c.xprev = xopt_prev ? dxp.as<double>() : dxs.as<double>(); c.uprev = uopt_prev ? dup.as<double>() : dus.as<double>();
-    c.xsol = dxs.as<double>(); c.usol = dus.as<double>(); c.x0 = dx0.as<double>(); c.status = dst.as<int32_t>();
-    c.xout = dxo.as<double>(); c.uout = duo.as<double>(); c.x0_next = dxn.as<double>();
-    if ((rc = loop_wait(h->launch_chain(c), h->stream))) return rc;
-    if ((rc = dxo.download(xopt_out, D * B * (N + 1) * n)) || (rc = duo.download(uopt_out, D * B * N * m)) || (rc = dxn.download(x0_next, D * B * n)))
-        return rc;
-    return SRH_OK;
+    return mpc_shift_alone(h, h->shift_args(), xopt_prev, uopt_prev, xopt, uopt, x0, status, first, xopt_out, uopt_out, x0_next);
 }
 
 int srompc_loop_advance(srompc_loop_t *h, const double *xopt, const double *uopt, const double *x, const double *x_hat, const double *W,
@@ -492,10 +383,7 @@ int srompc_loop_advance(srompc_loop_t *h, const double *xopt, const double *uopt
     v.rows_x = (int64_t)nk + 1; v.row0_x = 1; v.rows_u = (int64_t)nk; v.row0_u = 0;
     if ((rc = loop_wait(h->launch_advance(v), h->stream))) return rc;
     // rows 1 .. n_keep of the S + 1 row blocks (rows 0 .. n_keep - 1 of Xbar) -> the caller's (B x n_keep x .) arrays
-    auto rows = [&](const srh::DevBuf &d, double *dst, size_t w, size_t skip) -> int {
-        SRH_CHECK_HIP(hipMemcpy2D(dst, D * nk * w, (const char *)d.p + D * skip * w, D * (nk + 1) * w, D * nk * w, B, hipMemcpyDeviceToHost));
-        return SRH_OK;
-    };
+    auto rows = [&](const srh::DevBuf &d, double *dst, size_t w, size_t skip) { return loop_rows_to_host(d, dst, B, nk, D * w, skip); };
     if ((rc = rows(dX, X, n, 1)) || (rc = rows(dXH, XH, n, 1)) || (rc = rows(dZ, Z, nz, 1)) || (rc = rows(dXb, Xbar, n, 0)) ||
         (rc = dY.download(Y, D * B * nk * ny)) || (rc = dU.download(U, D * B * nk * m)) || (rc = dUb.download(Ubar, D * B * nk * m)))
         return rc;

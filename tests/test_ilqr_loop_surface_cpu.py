@@ -58,12 +58,19 @@ def test_one_launcher_and_the_unit_keeps_to_the_shared_rules():
     unit = open(os.path.join(csrc, 'ilqr_loop.hip')).read()
     for text in ('ext_vector_type(2)', 'At[q * n + j]', 'th * (hi - lo)', 'AdT +', 'BdT +', 'loop_prepare_kernel<<<', 'loop_run_periods('):
         assert text not in unit, text
-    for text in ('tpwl::panel_load', 'tpwl::step_slices', 'tpwl::step_sum', 'tpwl::nearest_wave', 'sekf_batch_step_dev', 'silqr_plan_solve_dev',
-                 'LoopRec', 'loop_wait'):
+    for text in ('tpwl::panel_load', 'tpwl::step_slices', 'tpwl::step_sum', 'tpwl::nearest_wave', 'silqr_plan_solve_dev', 'LoopRec', 'loop_wait',
+                 'loop_run_staged(', 'loop_observed_chain('):
         assert text in unit, text
-    calls = re.findall(r'hipMemcpyAsync\(.*?\);', unit, flags=re.S)
+    # the filter step of the observed chain and the staging of a run are the shared ones (loop_observed_host.h, gusto_loop_host.h): the unit
+    # has no copy of either
+    shell, chain = (open(os.path.join(csrc, f)).read() for f in ('gusto_loop_host.h', 'loop_observed_host.h'))
+    assert 'sekf_batch_step_dev' not in unit and chain.count('sekf_batch_step_dev(') == 1
+    assert 'hipMemcpyAsync' not in unit and 'hipStreamSynchronize(st)' not in unit
+    frame = shell[shell.index('int loop_run_staged('):shell.index('int loop_run_periods(')]
+    calls = re.findall(r'hipMemcpyAsync\(.*?\);', frame, flags=re.S)
     assert len([c for c in calls if 'hipMemcpyDeviceToHost' in c]) == 1          # the records of a run: one copy loop, one wait behind it
-    assert unit.count('hipStreamSynchronize(st)') == 2                           # the run's wait, and the drain on an error
+    assert frame.count('hipStreamSynchronize(st)') == 2                          # the run's wait, and the drain on an error
+    assert 'hipMemcpyDeviceToHost' not in shell.replace(frame, '')               # (no other copy back in the shell)
 
 
 def test_python_surface():

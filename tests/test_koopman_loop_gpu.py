@@ -1,8 +1,8 @@
 """GPU: the batched closed-loop Koopman MPC (csrc/koopman_loop.hip, baselines/koopman/closed_loop.py), every arrow of a period.
 
 Advance (koop_loop_advance_kernel alone on the seeded cases of tests/koopman_loop_cases.py, with the ring it leaves), fix-up
-(koop_loop_fixup_kernel alone on seeded plans and status words), preparation and solve (the request against the lift handle's own ring
-lift, the loop's plan against a second slocp plan fed with the loop's own inputs), their composition, and the reference's own
+(loop_plan_shift_kernel of csrc/mpc_loop_host.h alone on seeded plans and status words, at N = 1 too, and in place inside a run),
+preparation and solve (the request against the lift handle's own ring lift, the loop's plan against a second slocp plan fed with the loop's own inputs), their composition, and the reference's own
 KoopmanMPC.evaluate traces (tests/golden/g22_koopman.npz) replayed through the loop.  Comparisons between two runs of the same kernel on
 the same bits are exact; comparisons with the long-double reference (tests/koopman_loop_reference.py) use the project's rule
 tol = max(100 e_oracle, 1e-13) on max|a - b| / max(1, max|b|), e_oracle = the float64 statement's own error on the same case (asserted
@@ -402,6 +402,69 @@ def test_failed_solves_go_on():
     xs, us = cl._fixup(c['xsol'], c['usol'], c['x0'], c['status'], c['xprev'], c['uprev'], first=False)
     np.testing.assert_array_equal(xs[:, :-1], c['xprev'][:, 1:]); np.testing.assert_array_equal(us[:, :-1], c['uprev'][:, 1:])
     np.testing.assert_array_equal(xs[:, -1], c['xprev'][:, -1]); np.testing.assert_array_equal(us[:, -1], c['uprev'][:, -1])
+
+
+# ---------------------------------------------------------------------------------------------------------------- the shortest horizon
+def short_loop():
+    """(loop, inputs) of the shipped model on the r36 plant at N = 1 -- the shortest horizon slocp_plan_create accepts (scp_host.h:
+    N >= 1) -- with B = 2, r = 5, rollout_horizon = 1."""
+    from sofacontrol_amd.baselines.koopman.closed_loop import KoopmanClosedLoopBatch
+    from sofacontrol_amd.utils import QuadraticCost
+    inp = loop_inputs('5-1', 2)
+    if 'short' not in _cache:
+        g = kc.golden()
+        _cache['short'] = KoopmanClosedLoopBatch(model_of('ship'), 1, QuadraticCost(Q=g['cost_Q'], R=g['cost_R']), plant('r36'), inp['C'],
+                                                 inp['y_ref'], kc.DT_SIM[5], 1, t=g['cost_t'], z=g['cost_z'], u=g['cost_u'], phase=inp['phase'],
+                                                 U=Poly(g['cost_UA'], g['cost_Ub']), u0=U0, batch=2)
+    return _cache['short'], inp
+
+
+def test_fixup_alone_at_the_shortest_horizon():
+    """N = 1, one member solved and one failed, first and later period: min(k + 1, N - 1) = 0 for the one input row and min(k + 1, N) = N
+    for both state rows of the failed member."""
+    cl, _ = short_loop()
+    s = kc.spec('ship')
+    n, m = s['n_lift'], s['m']
+    rng = np.random.default_rng(9877)
+    c = dict(xsol=rng.standard_normal((2, 2, n)), usol=rng.standard_normal((2, 1, m)), x0=rng.standard_normal((2, n)),
+             xprev=rng.standard_normal((2, 2, n)), uprev=rng.standard_normal((2, 1, m)), status=np.array([0, 3], dtype=np.int32))
+    u0s = (U0 - s['u_offset']) / s['u_factor']
+    for first in (True, False):
+        xo, uo = cl._fixup(c['xsol'], c['usol'], c['x0'], c['status'], None if first else c['xprev'], None if first else c['uprev'], first=first)
+        for b in range(2):
+            ex, eu = kr.fixup(c['xsol'][b], c['usol'][b], c['x0'][b], c['status'][b], c['xprev'][b], c['uprev'][b], first, u0s, np.float64)
+            np.testing.assert_array_equal(xo[b], ex); np.testing.assert_array_equal(uo[b], eu)
+        np.testing.assert_array_equal(xo[0], c['xsol'][0]); np.testing.assert_array_equal(uo[0], c['usol'][0])
+        if first:
+            assert (xo[1] == c['x0'][1]).all() and (uo[1] == u0s).all()
+        else:                      # one row up with the last row held: both state rows are the previous plan's last, the input row its only one
+            assert (xo[1] == c['xprev'][1, 1]).all()
+            np.testing.assert_array_equal(uo[1], c['uprev'][1])
+
+
+def test_run_shifts_in_place_as_the_fixup_alone():
+    """Inside a run the shift kernel's output is the array the solve wrote (xsol is xout).  The same N = 1 loop with member 1 forced to
+    fail -- the older sample of its ring is not a number, so is its request, which the interior point reports (ipm_rule.h:
+    verdict_failed) -- and member 0 solved: the plan behind the period equals the stand-alone entry's answer, which writes into a third
+    array, for the same inputs; the request record is the request."""
+    cl, inp = short_loop()
+    inp = dict(inp, y_hist=inp['y_hist'].copy())
+    inp['y_hist'][1] = np.nan
+    reset(cl, inp)
+    r = cl.step()
+    li, (xo, uo) = cl.last_inputs(), cl.last_plan()
+    assert np.isnan(li['x0'][1]).any() and np.isfinite(li['x0'][0]).all()
+    np.testing.assert_array_equal(r.x_lift[0], li['x0'])
+    xs, us, J, st, it = second_plan_solve(cl, li)
+    print('status %s' % st)
+    assert st[0] == 0 and st[1] != 0
+    np.testing.assert_array_equal(r.status[0], st)
+    ax, au = cl._fixup(xs, us, li['x0'], st, None, None, first=True)
+    np.testing.assert_array_equal(xo, ax); np.testing.assert_array_equal(uo, au)
+    np.testing.assert_array_equal(xo[0], xs[0]); np.testing.assert_array_equal(uo[0], us[0])
+    s = kc.spec('ship')
+    assert (uo[1] == (U0 - s['u_offset']) / s['u_factor']).all()
+    np.testing.assert_array_equal(xo[1], np.broadcast_to(li['x0'][1], xo[1].shape))
 
 
 # ---------------------------------------------------------------------------------------------------------------- the reference's trace

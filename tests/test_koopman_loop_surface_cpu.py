@@ -83,8 +83,14 @@ def test_the_unit_keeps_to_the_shared_shell():
     units = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith(('.hip', '.h'))}
     unit = units['koopman_loop.hip']
     assert 'THE POLICY' in unit.split('#include')[0]
-    assert 'struct skoop_loop : LoopCore' in unit and 'loop_run_periods(h, "skoop_loop_run"' in unit
-    assert 'koop_loop_fixup_kernel' in unit and 'koop_loop_advance_kernel' in unit and unit.count('__launch_bounds__(256)') == 3
+    assert 'struct skoop_loop : MpcLoopCore' in unit and 'struct MpcLoopCore : LoopCore' in units['mpc_loop_host.h']
+    assert 'loop_run_periods(h, "skoop_loop_run"' in unit
+    # the unit's one kernel is its advance kernel: the tile and the plan-shift kernels are the linear-MPC shell's, stated once for both units
+    assert 'koop_loop_advance_kernel' in unit and unit.count('__launch_bounds__(256)') == 1 and unit.count('__global__') == 1
+    for kernel in ('loop_plan_shift_kernel(', 'loop_tile_kernel('):
+        assert [f for f, u in units.items() if '__global__ __launch_bounds__(256) void ' + kernel in u] == ['mpc_loop_host.h'], kernel
+    assert sorted(f for f, u in units.items() if '#include "mpc_loop_host.h"' in u) == ['koopman_loop.hip', 'rompc_loop.hip']
+    assert 'h->solve(p, a)' in unit and 'slocp_plan_solve_dev_resident(' not in unit and 'slocp_plan_create(' not in unit
     for text in ('loop_prepare_kernel<<<', 'hipMemcpyDeviceToHost', 'hipStreamCreate', 'AdT +', 'BdT +', 'ext_vector_type', 'th * (hi - lo)',
                  'int sgusto_loop_schedule', 'At[q * n + j]'):
         assert text not in unit, text
@@ -97,7 +103,8 @@ def test_the_unit_keeps_to_the_shared_shell():
     for f in ('koopman.hip', 'koopman_loop.hip'):
         assert '#include "koopman_host.h"' in units[f], f
     mk = open(os.path.join(csrc, 'Makefile')).read()
-    for dep in (r'koopman_loop\.o[^\n]*: \$\(TPWL_H\)', r'koopman_loop\.o[^\n]*: gusto_loop_prep\.h gusto_loop_host\.h', r'koopman\.o koopman_loop\.o: koopman_host\.h'):
+    for dep in (r'koopman_loop\.o[^\n]*: \$\(TPWL_H\)', r'koopman_loop\.o[^\n]*: gusto_loop_prep\.h gusto_loop_host\.h', r'koopman\.o koopman_loop\.o: koopman_host\.h',
+                r'rompc_loop\.o koopman_loop\.o: mpc_loop_host\.h'):
         assert re.search(dep, mk), dep
 
 

@@ -1,8 +1,9 @@
 """GPU: the batched closed-loop ROMPC (csrc/rompc_loop.hip, baselines/rompc/closed_loop.py), every arrow of a period.
 
 Preparation (request state, target window), solve (the loop's plan against a second slocp plan fed with the loop's own inputs), chain
-(rompc_chain_kernel alone on seeded plans and status words), advance (rompc_loop_advance_kernel alone on the seeded cases of
-tests/rompc_loop_cases.py), their composition, and the imported reference's trace (tests/golden/g23_rompc.npz) replayed through the loop.
+(loop_plan_shift_kernel of csrc/mpc_loop_host.h alone on seeded plans and status words, at N = 1 too, and in place inside a run),
+advance (rompc_loop_advance_kernel alone on the seeded cases of tests/rompc_loop_cases.py), their composition, and the imported
+reference's trace (tests/golden/g23_rompc.npz) replayed through the loop.
 Comparisons between two runs of the same kernel on the same bits are exact; comparisons with the long-double reference
 (tests/rompc_loop_reference.py) use the project's rule tol = max(100 e_oracle, 1e-13) on max|a - b| / max(1, max|b|), e_oracle = the
 float64 statement's own error on the same case (asserted <= 1e-11 in tests/test_rompc_loop_reference_cpu.py), every figure printed
@@ -241,6 +242,73 @@ def test_chain_alone(case):
               % (name, first, j_end, th_end, worst_o, worst, cr.tolerance(worst_o)))
         assert worst_o <= cr.E_ORACLE_MAX
         assert worst <= cr.tolerance(worst_o)
+
+
+def short_loop():
+    """The g6 loop with targets at N = 1 -- the shortest horizon slocp_plan_create accepts (scp_host.h: N >= 1) -- B = 2, and
+    n_replan dt_sim = 5 * 0.01 = N dt_mpc: the next request's state is read at (j, theta) = (N - 1, 1), rows N - 1 and N of the plan."""
+    from sofacontrol_amd.baselines.rompc.closed_loop import ROMPCClosedLoopBatch
+    from sofacontrol_amd.utils import QuadraticCost
+    if 'short' not in _cache:
+        g = cc.g6()
+        _cache['short'] = ROMPCClosedLoopBatch(observer(rc.controller('g6', 3, 0.01, True), 2), mpc_model('g6'), 1, cc.DT,
+                                               QuadraticCost(Q=g['Qz'], R=g['R']), plant('g6'), 0.01, 5, t=g['t'], z=g['zt'],
+                                               U=Poly(g['U_A'], g['U_b']))
+    assert rr.end_point(1, cc.DT, 0.01, 5) == (0, 1.0)
+    return _cache['short']
+
+
+def test_chain_alone_at_the_shortest_horizon():
+    """N = 1, one member solved and one failed, first and later period: min(k + 1, N - 1) = 0 for the one input row, min(k + 1, N) = N for
+    the last state row, and the request's rows j_end + 1 = N at theta == 1."""
+    cl = short_loop()
+    N, n, m = 1, cl.n_x, cl.n_u
+    c = rc.chain_case(2, N, n, m, 77)
+    assert c['status'][0] == 0 and c['status'][1] != 0
+    j_end, th_end = rr.end_point(N, cc.DT, 0.01, 5)
+    for first in (True, False):
+        xo, uo, xn = cl._chain(c['xsol'], c['usol'], c['x0'], c['status'], None if first else c['xprev'], None if first else c['uprev'], first=first)
+        worst, worst_o = 0.0, 0.0
+        for b in range(2):
+            ref = rr.chain(c['xsol'][b], c['usol'][b], c['x0'][b], c['status'][b], c['xprev'][b], c['uprev'][b], first, j_end, th_end, cr.LD)
+            f64 = rr.chain(c['xsol'][b], c['usol'][b], c['x0'][b], c['status'][b], c['xprev'][b], c['uprev'][b], first, j_end, th_end, np.float64)
+            np.testing.assert_array_equal(xo[b], f64[0]); np.testing.assert_array_equal(uo[b], f64[1])
+            np.testing.assert_array_equal(xo[b, 0], c['x0'][b])
+            if b == 1 and first:
+                assert (xo[b] == c['x0'][b]).all() and not uo[b].any()
+            elif b == 1:           # one row up with the last row held: the only later state row and the only input row are the last ones
+                np.testing.assert_array_equal(xo[b, 1], c['xprev'][b, 1]); np.testing.assert_array_equal(uo[b, 0], c['uprev'][b, 0])
+            else:
+                np.testing.assert_array_equal(xo[b, 1], c['xsol'][b, 1]); np.testing.assert_array_equal(uo[b], c['usol'][b])
+            worst_o = max(worst_o, cr.err(f64[2], ref[2])); worst = max(worst, cr.err(xn[b], ref[2]))
+        print('N = 1, first %s: request state e_oracle %.3e, device %.3e, tolerance %.3e' % (first, worst_o, worst, cr.tolerance(worst_o)))
+        assert worst_o <= cr.E_ORACLE_MAX
+        assert worst <= cr.tolerance(worst_o)
+
+
+def test_run_shifts_in_place_as_the_chain_alone():
+    """Inside a run the shift kernel's output is the array the solve wrote (xsol is xout).  The same N = 1 loop with member 1 forced to
+    fail -- its first estimate is not a number, which the interior point reports (ipm_rule.h: verdict_failed) and the request carries into
+    the next period -- and member 0 solved: the plan and the next request behind each of two periods equal the stand-alone entry's
+    answer, which writes into a third array, for the same inputs."""
+    cl = short_loop()
+    inp = loop_inputs('zf-u', 2)
+    xh0 = inp['x_hat0'].copy()
+    xh0[1] = np.nan
+    cl.reset(inp['x0'], xh0, 0.1)
+    xprev = uprev = None
+    for p in range(2):
+        r = cl.step()
+        li, (xo, uo) = cl.last_inputs(), cl.last_plan()
+        xs, us, J, st, it = second_plan_solve(cl, li)
+        print('period %d: status %s' % (p, st))
+        assert st[0] == 0 and st[1] != 0
+        np.testing.assert_array_equal(r.status[0], st)
+        ax, au, an = cl._chain(xs, us, li['x0'], st, xprev, uprev, first=p == 0)
+        np.testing.assert_array_equal(xo, ax); np.testing.assert_array_equal(uo, au); np.testing.assert_array_equal(r.x_bar[:, -1], an)
+        np.testing.assert_array_equal(xo[0, 1], xs[0, 1]); np.testing.assert_array_equal(xo[:, 0], li['x0'])
+        assert np.isnan(xo[1]).all() and np.isfinite(xo[0]).all()
+        xprev, uprev = xo, uo
 
 
 # ---------------------------------------------------------------------------------------------------------------- advance alone

@@ -1,6 +1,6 @@
-"""Bit-level dump of the closed-loop units (csrc/gusto_loop.hip, csrc/gusto_ssm_loop.hip, csrc/rompc_loop.hip and the host shell they
-share, csrc/gusto_loop_host.h) and of the TPWL rollout kernels (csrc/tpwl.hip) for comparing two builds of the library (SRH_LIB_PATH
-selects one).
+"""Bit-level dump of the five closed-loop units (csrc/gusto_loop.hip, gusto_ssm_loop.hip, rompc_loop.hip, koopman_loop.hip, ilqr_loop.hip
+and the host shell they share, csrc/gusto_loop_host.h with mpc_loop_host.h and loop_observed_host.h) and of the TPWL rollout kernels
+(csrc/tpwl.hip) for comparing two builds of the library (SRH_LIB_PATH selects one).
 
 Runs the loops of the test suites at their own smallest shapes through scp.closed_loop / scp.closed_loop_ssm and records every array
 that comes back, raw:
@@ -12,10 +12,17 @@ that comes back, raw:
     stand-alone advance on one entry of ssm_loop_cases.ADVANCE;
   - ROMPC (tests/test_rompc_loop_gpu.py: 'frac' and 'zf-u', g6 model, B = 3): reset(x0, x_hat0, 0.1), run(2, W, V) twice, then _chain (first
     and later period) and _advance alone on the entries 'g6-frac-10', 'r36-5-10', 'm8-frac-10' and 'g6-replay' of rompc_loop_cases.ADVANCE;
+  - Koopman (tests/test_koopman_loop_gpu.py: '5-1' and '1-3', the shipped model on the r36 plant, B = 3): reset, run(2, W, V) twice, then
+    _fixup (first and later period) and _advance alone on the entries 'r36-ship-5-1', 'm8-w-1-1', 'g6-dmd-5-1' and 'r36-ship-replay' of
+    koopman_loop_cases.ADVANCE, and the re-projected _advance of tests/test_koopman_reproject_gpu.py (n_y = 3, 'box+1', B = 3, replay);
+  - iLQR (tests/test_ilqr_loop_gpu.py: 'g6-r5-tail' (r = 5) and 'g6-r1' of ilqr_loop_cases.ADVANCE, 'obs-r5-mismatch' of OBSERVED): _advance
+    alone, a run split in two in the middle of a controller step without and with an observer, last_policy and stats behind each;
   - rollout (tests/test_tpwl_rollout_staged_gpu.py: every entry of SHAPES -- staged with the held table, staged with the wave search,
     plain above 64 KB -- and the velocity-weighted model): X and Z of the staged handle and of the plain one;
 after every run also last_inputs(), last_plan() and stats().  The host-side refusals are recorded as text, message for message: run
-before reset, periods * n_keep over the cap, last_inputs before a period, the observed run without an observer, the SSM model mismatch.
+before reset, periods * n_keep over the cap, last_inputs before a period, the observed run without an observer, the SSM model mismatch,
+the later-period shift without a previous plan, a QP with a trust region or input-rate rows handed to the two linear MPC creates, the
+iLQR run without a policy and the observers of another batch or model.
 
     python tools/loop_dump.py --out dumps/new        writes <out>.bin (the records, raw) and <out>.json (their index)
     python tools/loop_dump.py --compare A B --log profiles/x.log    compares two dumps record by record, byte for byte; exit 1 on a difference
@@ -152,6 +159,10 @@ def dump_rompc(rec):
         cl.reset(inp['x0'], inp['x_hat0'], T_START)
         for q in range(2):
             rec.after_run('%s/run2_%d' % (label, q), cl, cl.run(2, W=inp['W'][2 * q:2 * q + 2], V=inp['V'][2 * q:2 * q + 2]), tr.FIELDS + ('t',))
+    from sofacontrol_amd import _lib
+    create_refusals(rec, 'srompc', cl, lambda h, prob: _lib.lib().srompc_loop_create(
+        C.byref(h), cl.observer._h, C.cast(C.byref(prob), C.c_void_p), _lib.dptr(cl._A), _lib.dptr(cl._B), _lib.dptr(cl._d), C.c_double(cl.dt),
+        cl.plant.handle_for(cl.dt_sim), C.c_double(cl.dt_sim), C.c_int(cl.n_keep), C.c_int64(cl.max_steps_per_run)))
     for name in ('g6-frac-10', 'r36-5-10', 'm8-frac-10', 'g6-replay'):
         case = [c for c in rc.ADVANCE if c[0] == name][0]
         c, cl = rc.advance_case(case), tr.advance_loop(case)
@@ -161,6 +172,119 @@ def dump_rompc(rec):
             for first in (True, False):
                 got = cl._chain(k['xsol'], k['usol'], k['x0'], k['status'], None if first else k['xprev'], None if first else k['uprev'], first=first)
                 rec.arrays('rompc/chain/%s_%s' % (name, 'first' if first else 'later'), dict(zip(('xopt', 'uopt', 'x0_next'), got)))
+            if name == 'g6-frac-10':
+                rec.refusal('rompc/later_chain_without_a_previous_plan', lambda: cl._chain(k['xsol'], k['usol'], k['x0'], k['status'], first=False))
+
+
+def create_refusals(rec, label, cl, create):
+    """The library's answers to a QP the resident linear MPC loops do not offer: create(problem) is the class's own create call."""
+    from sofacontrol_amd import _lib
+    for field, value in (('tr_active', 1), ('ndU', 1)):
+        prob = type(cl.problem())()
+        C.pointer(prob)[0] = cl.problem()
+        setattr(prob, field, value)
+        h = C.c_void_p()
+        rec.refusal('%s/create_%s' % (label, field), lambda: _lib.check(create(h, prob), label + '_loop_create'))
+        assert not h.value
+
+
+def dump_koopman(rec):
+    import koopman_loop_cases as kc
+    import koopman_reproject_cases as qc
+    import test_koopman_loop_gpu as tk
+    import test_koopman_reproject_gpu as tq
+    from sofacontrol_amd import _lib
+    for name in tk.LOOPS:
+        cl, inp = tk.make_loop(name, 3)
+        label = 'koopman/' + name
+        if name == '5-1':
+            rec.refusal('koopman/run_before_reset', lambda: cl.run(1))
+        tk.reset(cl, inp, T_START)
+        if name == '5-1':
+            rec.refusal('koopman/last_inputs_before_a_period', lambda: cl.last_inputs())
+        for q in range(2):             # (three periods of noise: the second run reads periods 1 and 2)
+            rec.after_run('%s/run2_%d' % (label, q), cl, cl.run(2, W=inp['W'][q:q + 2], V=inp['V'][q:q + 2]), tk.FIELDS + ('t',))
+    rec.refusal('koopman/over_the_cap', lambda: cl.run(17))
+    p = cl.plant.handle_for(cl.dt_sim)
+    create_refusals(rec, 'skoop', cl, lambda h, prob: _lib.lib().skoop_loop_create(
+        C.byref(h), cl.lift._h, C.cast(C.byref(prob), C.c_void_p), _lib.dptr(cl._A), _lib.dptr(cl._Bm), C.c_double(kc.TS), p, _lib.dptr(cl._C),
+        _lib.dptr(cl._yref), _lib.dptr(cl.u0), C.c_double(cl.dt_sim), C.c_int(cl.rollout_horizon), C.c_int64(cl.max_steps_per_run)))
+    for name in ('r36-ship-5-1', 'm8-w-1-1', 'g6-dmd-5-1', 'r36-ship-replay'):
+        case = [c for c in kc.ADVANCE if c[0] == name][0]
+        c, cl, h = kc.advance_case(case), tk.advance_loop(case), kc.history(case, case[5])
+        sim = case[8] == 'sim'
+        cl.reset(x0=c['x'] if sim else None, y0=None if sim else c['Y_plant'][:, 0], y_hist=h['y_hist'], u_hist=h['u_hist'], u_prev0=h['u_prev0'],
+                 v0=h['v0'] if sim else None)
+        rec.arrays('koopman/advance/' + name, cl._advance(c['uopt'], c['x'] if sim else None, W=c['W'], V=c['V'], Y_plant=c['Y_plant'],
+                                                          U_applied=c['U_applied']))
+        rec.array('koopman/advance/%s/ring' % name, tk.ring_of(cl.lift)[0])
+        if name == 'r36-ship-5-1':
+            rec.refusal('koopman/run_behind_the_advance', lambda: cl.run(1))
+        if sim:
+            s = kc.spec(case[2])
+            k = kc.fixup_case(case[5], s['n_lift'], s['m'], case[-1])
+            k['status'][0] = 5 if case[5] == 1 else 0
+            for first in (True, False):
+                got = cl._fixup(k['xsol'], k['usol'], k['x0'], k['status'], None if first else k['xprev'], None if first else k['uprev'], first=first)
+                rec.arrays('koopman/fixup/%s_%s' % (name, 'first' if first else 'later'), dict(zip(('xopt', 'uopt'), got)))
+            if name == 'r36-ship-5-1':
+                rec.refusal('koopman/later_fixup_without_a_previous_plan', lambda: cl._fixup(k['xsol'], k['usol'], k['x0'], k['status'], first=False))
+    ny, rows, B = 3, 'box+1', 3
+    s = qc.spec(ny)
+    nk = qc.N * qc.R
+    Yp, _ = qc.replay_samples(ny, rows, B, nk)
+    cl = tq.replay_loop(ny, B, qc.N, tq.Ypoly(*qc.polyhedron(ny, rows)))
+    rng = np.random.default_rng(31 + ny)
+    y_hist = s['y_offset'] + s['y_factor'] * rng.uniform(-1.0, 1.0, (B, 1, ny))
+    u_hist, u_prev0 = rng.uniform(0.0, 100.0, (B, 1, qc.M)), rng.uniform(0.0, 100.0, (B, qc.M))
+    cl.reset(y0=Yp[:, 0], y_hist=y_hist, u_hist=u_hist, u_prev0=u_prev0)
+    rec.arrays('koopman/advance/reprojected-3-box+1', cl._advance(rng.uniform(-1.0, 1.0, (B, qc.N, qc.M)), Y_plant=Yp))
+
+
+def dump_ilqr(rec):
+    import ilqr_loop_cases as ic
+    import test_ilqr_loop_gpu as ti
+    from sofacontrol_amd.lqr.closed_loop import ILQRClosedLoopBatch
+    from sofacontrol_amd.tpwl.observer import DiscreteEKFObserverBatch
+
+    def after(label, cl, r):
+        rec.arrays(label, {f: getattr(r, f) for f in ('x', 'z', 'u', 'x_hat', 'y', 'ekf_status', 't')})
+        rec.arrays(label + '/last_policy', dict(zip(('x_bar', 'u_bar', 'K'), cl.last_policy())))
+        rec.append((label + '/stats', json.dumps(cl.stats(), sort_keys=True).encode()))
+
+    bare = ILQRClosedLoopBatch(ti.ilqr_of('g6', 12), ti.plant('g6'), 0.05, 3, max_steps_per_run=10)
+    rec.refusal('ilqr/run_before_reset', lambda: bare.run(1))
+    bare.reset(ic.advance_case(ic.ADVANCE[0])['x'])
+    rec.refusal('ilqr/run_without_a_policy', lambda: bare.run(1))
+    rec.refusal('ilqr/last_policy_without_a_policy', lambda: bare.last_policy())
+    for name in ('g6-r5-tail', 'g6-r1'):
+        case = [c for c in ic.ADVANCE if c[0] == name][0]
+        S = case[5]
+        cl, c = ti.make_loop(case, max_steps_per_run=S)
+        rec.arrays('ilqr/advance/' + name, dict(zip(('X', 'Z', 'U', 'idx'), cl._advance(c['x'], S, W=c['W']))))
+        cl.reset(c['x'])
+        k = 7 if case[4] > 1 else S // 2           # (r = 5: the held input crosses the run boundary)
+        cut = lambda a, lo, hi: None if a is None else a[lo:hi]
+        after('ilqr/%s/run_%d' % (name, k), cl, cl.run(k, W=cut(c['W'], 0, k)))
+        after('ilqr/%s/run_%d' % (name, S - k), cl, cl.run(S - k, W=cut(c['W'], k, S)))
+        if name == 'g6-r1':
+            rec.refusal('ilqr/over_the_cap', lambda: cl.run(S + 1))
+    cs = [c for c in ic.OBSERVED if c[0] == 'obs-r5-mismatch'][0]
+    steps = cs[3]
+    cl, c = ti.make_observed(cs)
+    cl.reset(c['x'], c['x_hat'])
+    cut = lambda a, lo, hi: None if a is None else a[lo:hi]
+    after('ilqr/%s/run_7' % cs[0], cl, cl.run(7, W=cut(c['W'], 0, 7), V=cut(c['V'], 0, 7)))
+    after('ilqr/%s/run_%d' % (cs[0], steps - 7), cl, cl.run(steps - 7, W=cut(c['W'], 7, steps), V=cut(c['V'], 7, steps)))
+    # the library's own answers to an observer of another batch and of another model width (the class may refuse earlier, in its own words)
+    from sofacontrol_amd import _lib
+    import clobs_cases as oc
+    ms = oc.measurement('g6')
+    four = DiscreteEKFObserverBatch(ti.filter_model(True), 4, Sigma0=ms['Sigma0'], W=ms['W'], V=ms['V'])
+    rec.refusal('ilqr/observer_of_another_batch', lambda: _lib.check(_lib.lib().silqr_loop_set_observer(cl._h, four._h), 'silqr_loop_set_observer'))
+    r36, _ = ti.make_loop([c for c in ic.ADVANCE if c[0] == 'r36-r5'][0])
+    three = DiscreteEKFObserverBatch(ti.filter_model(True), 3, Sigma0=ms['Sigma0'], W=ms['W'], V=ms['V'])
+    rec.refusal('ilqr/observer_of_another_model', lambda: _lib.check(_lib.lib().silqr_loop_set_observer(r36._h, three._h), 'silqr_loop_set_observer'))
 
 
 def dump_rollout(rec):
@@ -185,6 +309,8 @@ def dump(out):
     dump_observed(rec)
     dump_ssm(rec)
     dump_rompc(rec)
+    dump_koopman(rec)
+    dump_ilqr(rec)
     dump_rollout(rec)
     index, off = [], 0
     with open(out + '.bin', 'wb') as f:

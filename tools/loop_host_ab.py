@@ -1,8 +1,11 @@
-"""A/B of two builds of the library on the host path of a closed-loop period (csrc/gusto_loop_host.h and the two units around it): the
+"""A/B of two builds of the library on the host path of a closed-loop period (csrc/gusto_loop_host.h and the five units around it): the
 median period of run(1) over 3 warm-up and 20 timed periods of
   - contender (a) of tools/gusto_ssm_loop_probe.py (SSMClosedLoopBatch, the hardware driver's shape) at B = 1, 256, 4096;
   - the unobserved and the observed TPWL loop of tools/gusto_loop_observer_probe.py (ClosedLoopBatch.run / run_observed) at B = 256;
-  - the ROMPC loop of tools/rompc_loop_probe.py (ROMPCClosedLoopBatch.run, the Diamond shape with the TPWL model as the plant) at B = 256.
+  - the ROMPC loop of tools/rompc_loop_probe.py (ROMPCClosedLoopBatch.run, the Diamond shape with the TPWL model as the plant) at B = 256;
+  - the Koopman loop of tools/koopman_loop_probe.py (KoopmanClosedLoopBatch.run, the Diamond shape) at B = 256;
+  - the iLQR loop of tools/ilqr_loop_probe.py (ILQRClosedLoopBatch, state feedback and observed, the Diamond shape) at B = 256: it has no
+    periods, so the timed call is one run(N) of the probe's N = 100 steps behind a reset, under the policy of one plan().
 
     python tools/loop_host_ab.py --parent <library built from the parent commit> [--rounds 5] [--out profiles/loop_host_ab.json]
 
@@ -24,9 +27,11 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, 'soft-robot-control_amd'), os.path.join(ROOT, 'tools'), os.path.join(ROOT, 'examples')]
 
-SSM_BATCHES, TPWL_BATCH, ROMPC_BATCH = (1, 256, 4096), 256, 256
+SSM_BATCHES, TPWL_BATCH, ROMPC_BATCH, KOOPMAN_BATCH, ILQR_BATCH, ILQR_STEPS = (1, 256, 4096), 256, 256, 256, 256, 100
 FIGURES = ['ssm_period_ms_B%d' % B for B in SSM_BATCHES] + ['tpwl_period_ms_B%d' % TPWL_BATCH, 'tpwl_observed_period_ms_B%d' % TPWL_BATCH,
-                                                                'rompc_period_ms_B%d' % ROMPC_BATCH]
+                                                                'rompc_period_ms_B%d' % ROMPC_BATCH, 'koopman_period_ms_B%d' % KOOPMAN_BATCH,
+                                                                'ilqr_run%d_ms_B%d' % (ILQR_STEPS, ILQR_BATCH),
+                                                                'ilqr_observed_run%d_ms_B%d' % (ILQR_STEPS, ILQR_BATCH)]
 
 
 def median_period_ms(period, warm, timed):
@@ -38,15 +43,31 @@ def median_period_ms(period, warm, timed):
     return float(np.median(ts[warm:]))
 
 
+def median_run_ms(loop, x0, x_hat0, steps, warm, timed):
+    """The iLQR loop: run(steps) from the same state every time (the reset is outside the clock)."""
+    ts = []
+    for k in range(warm + timed):
+        loop.reset(x0, x_hat0)
+        t0 = time.perf_counter()
+        loop.run(steps, record_x=x_hat0 is not None)
+        ts.append(1e3 * (time.perf_counter() - t0))
+    return float(np.median(ts[warm:]))
+
+
 def measure():
     import gusto_loop_observer_probe as op
     import gusto_ssm_loop_probe as sp
+    import ilqr_loop_probe as ip
+    import koopman_loop_probe as kp
     import rompc_loop_probe as rp
     import workloads as wl
+    from diamond_koopman_closed_loop_batch import diamond_koopman, U0
     from diamond_rompc_closed_loop_batch import diamond_rompc
     from sofacontrol_amd import _lib
+    from sofacontrol_amd.lqr.closed_loop import ILQRClosedLoopBatch
     from sofacontrol_amd.scp.closed_loop import ClosedLoopBatch
     from sofacontrol_amd.scp.closed_loop_ssm import SSMClosedLoopBatch
+    from sofacontrol_amd.tpwl.observer import DiscreteEKFObserverBatch
     assert _lib.device_count() >= 1, 'no GPU visible'
     _lib.set_device(0)
     out = {}
@@ -71,6 +92,22 @@ def measure():
     loop.reset(x0, x0 + 0.1 * rng.standard_normal(x0.shape))
     out['rompc_period_ms_B%d' % ROMPC_BATCH] = median_period_ms(lambda k: loop.run(1), op.WARM, op.TIMED)
     assert loop.stats()['waits_last_run'] == 1
+    B = KOOPMAN_BATCH
+    with contextlib.redirect_stdout(io.StringIO()):
+        loop, model, _, _, Cm, y_ref, _, _ = diamond_koopman(B, kp.NK, rollout_horizon=kp.RH)
+    x0 = 0.5 * rng.standard_normal((B, loop.n_plant))
+    loop.reset(x0=x0, y_hist=(x0 @ Cm.T + y_ref)[:, None, :], u_hist=np.full((B, 1, model.m), U0), u_prev0=np.full((B, model.m), U0))
+    out['koopman_period_ms_B%d' % B] = median_period_ms(lambda k: loop.run(1), op.WARM, op.TIMED)
+    assert loop.stats()['waits_last_run'] == 1
+    B, N = ILQR_BATCH, ILQR_STEPS
+    for observed, key in ((False, 'ilqr_run%d_ms_B%d'), (True, 'ilqr_observed_run%d_ms_B%d')):
+        model, policy, x0, x_hat0, z = ip.problem(B, N, observed)
+        obs = DiscreteEKFObserverBatch(model, B, W=100.0 * np.eye(x0.shape[1]), V=np.eye(30)) if observed else None
+        loop = ILQRClosedLoopBatch(policy, model, ip.DT, B, z=z, observer=obs, max_steps_per_run=N)
+        loop.reset(x0, x_hat0)
+        loop.plan()
+        out[key % (N, B)] = median_run_ms(loop, x0, x_hat0, N, op.WARM, op.TIMED)
+        assert loop.stats()['waits_last_run'] == 1
     print('LOOP_HOST_AB ' + json.dumps(out), flush=True)
 
 
@@ -91,7 +128,7 @@ def main():
             env = {key: v for key, v in os.environ.items() if key != 'SRH_LIB_PATH'}
             if build == 'parent':
                 env['SRH_LIB_PATH'] = os.path.abspath(args.parent)
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), '--measure'], env=env, capture_output=True, text=True, timeout=240)
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), '--measure'], env=env, capture_output=True, text=True, timeout=400)
             line = [l for l in p.stdout.splitlines() if l.startswith('LOOP_HOST_AB ')]
             if p.returncode != 0 or not line:          # nothing more is started on the GPU after a failed measurement
                 print(p.stdout[-2000:], p.stderr[-4000:])
