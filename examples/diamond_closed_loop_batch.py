@@ -5,7 +5,11 @@ one host wait for the whole run.  Without --observer state feedback is perfect; 
 filter (tpwl.observer.DiscreteEKFObserverBatch) on five measured nodes (n_y = 30) with measurement noise and a wrong initial
 estimate, plans from the estimate and controls from it -- the loop the reference's drivers close.
 
-    python examples/diamond_closed_loop_batch.py [--batch 256] [--periods 20] [--seed 0] [--observer]
+    python examples/diamond_closed_loop_batch.py [--batch 256] [--periods 20] [--seed 0] [--observer] [--chained]
+
+--chained runs the reference's default policy, mpc=False (tpwl/controllers.py:236; what examples/diamond/diamond.py:249 runs): plan
+k + 1 starts from the end of the followed part of plan k, not from the plant state or the estimate, so only the law and the filter
+close the loop.  It then runs mpc=True -- every period re-plans from the plant -- on the same seeds, and prints the tip error of both.
 
 Needs an MI355X (no CPU fallback)."""
 import argparse
@@ -28,6 +32,7 @@ def main():
     ap.add_argument('--periods', type=int, default=20, help='re-planning periods of 10 steps of 0.01 s')
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--observer', action='store_true', help='output feedback: one EKF per loop on five measured nodes, noise, wrong initial estimate')
+    ap.add_argument('--chained', action='store_true', help="the reference's default policy mpc=False, then mpc=True on the same seeds")
     args = ap.parse_args()
 
     import workloads as wl
@@ -69,24 +74,41 @@ def main():
                   U=HyperRectangle([1500.] * m, [0.] * m), X=Polyhedron(w['XA'], w['Xb']), x_char=xc, f_char=fc, convg_thresh=1e-3,
                   max_gusto_iters=3, batch=B, first_solve_cap=1, max_trace=0)
     observer = DiscreteEKFObserverBatch(model, B, W=100.0 * np.eye(2 * r), V=np.eye(30)) if args.observer else None
-    loop = ClosedLoopBatch(gusto, model, dt_sim, n_keep, t=w['t'], z=w['z'], phase=phase, K=K, max_steps_per_run=args.periods * n_keep,
-                           observer=observer)
     if args.observer:
         x_hat0 = x0 + 0.1 * rng.standard_normal(x0.shape)                     # where a first update at t = 0 would have left the filters
         noise = 0.05 * rng.standard_normal((args.periods, n_keep, B, 30))
-        loop.reset_observed(x0, x_hat0)
-        t0 = time.perf_counter()
-        res = loop.run_observed(args.periods, V=noise)
-        wall = time.perf_counter() - t0
-    else:
-        loop.reset(x0)
-        t0 = time.perf_counter()
-        res = loop.run(args.periods, record_x=False)
-        wall = time.perf_counter() - t0
 
-    target = zi(phase[:, None] + res.t[None, :])                              # (B, S + 1, 6)
-    err = np.linalg.norm((res.z - target)[:, 1:, 3:5], axis=2)
-    rms = np.sqrt(np.mean(err ** 2, axis=1))
+    def run_policy(mpc):
+        """(loop, records, seconds) of one policy on the seeded states, estimates and noise."""
+        loop = ClosedLoopBatch(gusto, model, dt_sim, n_keep, t=w['t'], z=w['z'], phase=phase, K=K, max_steps_per_run=args.periods * n_keep,
+                               observer=observer, mpc=mpc, record_tape=not mpc)
+        if args.observer:
+            loop.reset_observed(x0, x_hat0)
+            t0 = time.perf_counter()
+            res = loop.run_observed(args.periods, V=noise)
+        else:
+            loop.reset(x0)
+            t0 = time.perf_counter()
+            res = loop.run(args.periods, record_x=False)
+        return loop, res, time.perf_counter() - t0
+
+    def tip_rms(res):
+        target = zi(phase[:, None] + res.t[None, :])                          # (B, S + 1, 6)
+        err = np.linalg.norm((res.z - target)[:, 1:, 3:5], axis=2)
+        return np.sqrt(np.mean(err ** 2, axis=1))
+
+    loop, res, wall = run_policy(not args.chained)
+    rms = tip_rms(res)
+    if args.chained:
+        _, res_mpc, wall_mpc = run_policy(True)
+        rms_mpc = tip_rms(res_mpc)
+        # the nominal tape the loops follow (the reference's x_opt of save_controller_info), as outputs: how far the PLAN is from the target
+        tape = np.linalg.norm((res.x_bar @ H.T - zi(phase[:, None] + res.t[None, :]))[:, 1:, 3:5], axis=2)
+        print('policy mpc=False (chained, the reference\'s default): tip rms median %.3f, worst %.3f; its nominal tape alone: median %.3f; '
+              '%.1f ms per period' % (np.median(rms), rms.max(), np.median(np.sqrt(np.mean(tape ** 2, axis=1))), 1e3 * wall / args.periods))
+        print('policy mpc=True  (re-plan from the %s):           tip rms median %.3f, worst %.3f; %.1f ms per period'
+              % ('estimate' if args.observer else 'plant', np.median(rms_mpc), rms_mpc.max(), 1e3 * wall_mpc / args.periods))
+        print('loops where the chained policy tracks better: %d of %d (the records below are the chained policy\'s)' % (int((rms < rms_mpc).sum()), B))
     print('%d loops x %d periods (%.2f s each), %d host wait(s), %.1f ms per period' %
           (B, args.periods, args.periods * n_keep * dt_sim, loop.stats()['waits_last_run'], 1e3 * wall / args.periods))
     print('tip tracking rms (x, y) per loop: median %.3f, best %.3f, worst %.3f   (target amplitude %.1f)' %

@@ -792,6 +792,31 @@ int sgusto_loop_stats(sgusto_loop_t *h, int64_t *steps, int64_t *waits_last_run)
 /* The schedule of period k (no GPU): *t_k, *idx0 (0 for k = 0), j (n_keep), theta (n_keep).  Any output may be NULL. */
 int sgusto_loop_schedule(int N, double dt, double dt_sim, int n_keep, double t_start, int64_t k, double *t_k, int *idx0, int32_t *j,
                          double *theta);
+/* ---- the chained policy: the reference's `mpc=False` (tpwl/controllers.py:236, its default, and what its TPWL drivers run).  Period 0
+ * after a reset is as above.  Period k >= 1 starts from the END of the part of plan k - 1 that the robot follows,
+ *   x0      = xopt[j_end] + theta_end (xopt[j_end + 1] - xopt[j_end])  of the previous plan (controllers.py:272: x_opt[-1]),
+ *             (j_end, theta_end) = the schedule's rule of a sub-step at tau = n_keep dt_sim (sgusto_loop_end_row),
+ * not from the plant state or the estimate: the plans do not depend on the plant, only the law and the filters close the loop.  Guess,
+ * target, solve and advance are unchanged; row 0 of the X / Z records is the plant's state as before.  One more launch per period,
+ * behind the solve: loop_chain_kernel forms x0 of the next period and the period's rows of the nominal tape the reference stitches
+ * (controllers.py:302-315; x_opt / u_opt of save_controller_info): Xbar (batch x (S + 1) x n_x), Ubar (batch x (S + 1) x n_u), row
+ * p n_keep + s the plan of period p at tau = s dt_sim (s = n_keep: at tau_end; the input held over the plan's last interval).  At a
+ * junction row k n_keep, k >= 1, Xbar keeps the OLD plan's end (x_opt_new[1:] is appended) and Ubar takes the NEW plan's first row
+ * (u_opt[:-1] is kept); row 0 of a run that continues another is the old plan's end as well.
+ * set_chained: on != 0 selects the policy, 0 the default (re-plan from the plant).  Refused unless no period has run since the
+ * create or the last reset.  The chain state lives in the handle: runs continue it, a reset drops it. */
+int sgusto_loop_set_chained(sgusto_loop_t *h, int on);
+/* sgusto_loop_run (Xhat, Y_cl, ekf_status and V all NULL) or sgusto_loop_run_observed (all three records given) with the tape: Xbar,
+ * Ubar as above, either may be NULL.  Asking for a tape is refused unless the loop is chained. */
+int sgusto_loop_run_tape(sgusto_loop_t *h, int periods, const double *W, const double *V, double *X_cl, double *Z_cl, double *U_cl,
+                         int32_t *iters, int32_t *status, double *J, double *Xhat, double *Y_cl, int32_t *ekf_status, double *Xbar, double *Ubar);
+/* The end row of the schedule (no GPU): tau = n_keep dt_sim, *j_end = min((int)(tau / dt), N - 1), *theta_end = (tau - j_end dt) / dt.
+ * At n_keep dt_sim == N dt: j_end = N - 1 and theta_end is 1 to rounding.  Either output may be NULL. */
+int sgusto_loop_end_row(int N, double dt, double dt_sim, int n_keep, int32_t *j_end, double *theta_end);
+/* The chain kernel alone -- the launch a chained period makes, in its period-0 form -- on host-supplied plans: xopt (batch x (N+1) x n_x),
+ * uopt (batch x N x n_u) -> x_next (batch x n_x), Xbar_rows (batch x (n_keep + 1) x n_x), Ubar_rows (batch x (n_keep + 1) x n_u), rows
+ * s = 0..n_keep; any output may be NULL.  The loop's own state is not touched. */
+int sgusto_loop_chain(sgusto_loop_t *h, const double *xopt, const double *uopt, double *x_next, double *Xbar_rows, double *Ubar_rows);
 
 /* Batched closed loop on a resident SSM GuSTO plan (csrc/gusto_ssm_loop.hip): the loop of the reference's hardware driver
  * (examples/hardware/diamond_SSM.py:353-361, SSM/controllers.py: the scp controller applies u = u_bar(t) with no feedback gain, the

@@ -127,6 +127,48 @@ size_t advance_lds_bytes(int n, int m, bool observed) {
     return srh::lds_request(sizeof(double) * ((size_t)3 * n + 16 + 16 + 2 + tpwl::step_doubles(n, m, 256) + (observed ? n : 0)));
 }
 
+// THE CHAINED POLICY (the reference's default, mpc=False: tpwl/controllers.py:269-274, 298-315).  Plan k + 1 starts from the END of the
+// part of plan k that the robot follows -- the plan point at tau_end = n_keep dt_sim, (j_end, theta_end) of sgusto_loop_end_row --
+// not from the plant: the plans no longer depend on the plant, only the law and the filter close the loop.  loop_chain_kernel, behind
+// the solve of a chained period, forms that point for every member (x_next) and the period's rows of the nominal tape the reference
+// stitches (x_opt / u_opt of save_controller_info): row s = 0..n_keep of a period is the plan point at tau = s dt_sim, s = n_keep the
+// end point.  All of it by plan_at, with the (j, theta) the advance kernel reads: a tape row has the bits of that kernel's x_bar / u_bar.
+struct ChainArgs {
+    int N, n, m, n_keep;
+    int j_end;                          // the plan interval and the position inside it of tau_end
+    double theta_end;
+    const double *xopt, *uopt;          // the plans (B x (N+1) x n), (B x N x m)
+    const int32_t *js;                  // (n_keep) the schedule of the sub-steps, as AdvArgs
+    const double *theta;
+    double *x_next;                     // (B x n) the next period's start state, or null
+    double *Xbar, *Ubar;                // tape records: row row0 + s of member b, or null
+    int64_t rows, row0, B;              // rows per member of both records
+    int x_row0;                         // whether row s = 0 of Xbar is written (period 0 after a reset: later it is the old plan's end, which
+                                        // the reference keeps -- x_opt_new[1:] is appended --, while u_opt[:-1] gives way to the new plan's row)
+};
+
+// One thread per lerp: element e = (s, c) of member b, s = 0..n_keep, c < n a state, otherwise input c - n; consecutive threads write
+// consecutive addresses of a record row.  No LDS, no cross-lane traffic: any n <= 128, m <= 16, B.
+__global__ __launch_bounds__(256) void loop_chain_kernel(ChainArgs a) {
+    const int n = a.n, m = a.m, N = a.N, w = n + m;
+    const size_t per = (size_t)(a.n_keep + 1) * w;
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= (size_t)a.B * per) return;
+    const size_t b = g / per;
+    const int e = (int)(g - b * per), s = e / w, c = e - s * w;
+    const bool end = s == a.n_keep;
+    const int j = end ? a.j_end : ((cgiptr)a.js)[s];
+    const double th = end ? a.theta_end : ((cgptr)a.theta)[s];
+    const size_t row = b * (size_t)a.rows + a.row0 + s;
+    if (c < n) {
+        const double v = plan_at((cgptr)a.xopt + b * (size_t)(N + 1) * n, n, j, j + 1, th, c);
+        if (end && a.x_next) ((gptr)a.x_next)[b * n + c] = v;
+        if (a.Xbar && (s > 0 || a.x_row0)) ((gptr)a.Xbar)[row * n + c] = v;
+    } else if (a.Ubar) {
+        ((gptr)a.Ubar)[row * m + (c - n)] = plan_at((cgptr)a.uopt + b * (size_t)N * m, m, j, min(j + 1, N - 1), th, c - n);
+    }
+}
+
 }  // namespace
 
 struct sgusto_loop : LoopCore {
@@ -141,7 +183,14 @@ struct sgusto_loop : LoopCore {
     size_t lds_obs = 0;
     srh::DevBuf K, zf;
     LoopRec Erec;                       // observed loop: the filters' status (P x B); Y is (B x S x ny) here
-    __attribute__((always_inline)) sgusto_loop() { recs.push_back(&Erec); }       // (inlined: no constructor among the library's dynamic symbols)
+    // the chained policy (sgusto_loop_set_chained): the next period's start state (B x n; it holds one whenever k > 0), the end row of
+    // the schedule, and the tape records (B x (S + 1) x n), (B x (S + 1) x m), allocated by the first run that asks for them
+    bool chained = false;
+    int j_end = 0;
+    double theta_end = 0.0;
+    srh::DevBuf xchain;
+    LoopRec XBrec, UBrec;
+    __attribute__((always_inline)) sgusto_loop() { recs.insert(recs.end(), {&Erec, &XBrec, &UBrec}); }       // (inlined: no constructor among the library's dynamic symbols)
     ~sgusto_loop() { drain(); }
     AdvArgs adv_args() const {
         AdvArgs a{};
@@ -152,6 +201,20 @@ struct sgusto_loop : LoopCore {
         a.B = B;
         a.s0 = 0; a.s1 = n_keep;
         return a;
+    }
+    ChainArgs chain_args() const {
+        ChainArgs c{};
+        c.N = N; c.n = n; c.m = m; c.n_keep = n_keep; c.j_end = j_end; c.theta_end = theta_end;
+        c.js = js.as<int32_t>(); c.theta = theta.as<double>();
+        c.B = B;
+        return c;
+    }
+    int launch_chain(const ChainArgs &c) const {
+        const size_t blocks = ((size_t)B * (n_keep + 1) * (n + m) + 255) / 256;
+        SRH_REQUIRE(blocks <= (size_t)0x7fffffff, "sgusto_loop: the chain kernel's grid of %zu workgroups exceeds 2^31 - 1", blocks);
+        loop_chain_kernel<<<(unsigned)blocks, 256, 0, stream>>>(c);
+        SRH_CHECK_HIP(hipGetLastError());
+        return SRH_OK;
     }
     int launch_advance(const AdvArgs &a) const {
         loop_advance_kernel<false><<<(unsigned)B, 256, lds, stream>>>(planner->view(), plant->view(), a);
@@ -207,6 +270,20 @@ int sgusto_loop_schedule(int N, double dt, double dt_sim, int n_keep, double t_s
     return SRH_OK;
 }
 
+int sgusto_loop_end_row(int N, double dt, double dt_sim, int n_keep, int32_t *j_end, double *theta_end) {
+#pragma clang fp contract(off)          // as sgusto_loop_schedule: the rule of a sub-step at tau = n_keep dt_sim
+    SRH_REQUIRE(N >= 1 && dt > 0.0 && dt_sim > 0.0 && n_keep >= 1, "sgusto_loop_end_row: bad argument");
+    const double tau = (double)n_keep * dt_sim;
+    const double q = tau / dt;
+    const int je = std::min((int)q, N - 1);
+    if (j_end) *j_end = je;
+    if (theta_end) {
+        const double back = (double)je * dt;
+        *theta_end = (tau - back) / dt;
+    }
+    return SRH_OK;
+}
+
 int sgusto_loop_create(sgusto_loop_t **out, sgusto_plan_t *plan, stpwl_t *planner_model, stpwl_t *plant, double dt_sim, int n_keep,
                        int64_t max_steps_per_run) {
     SRH_REQUIRE(out && plan && planner_model && plant, "sgusto_loop_create: null argument");
@@ -239,6 +316,8 @@ int sgusto_loop_create(sgusto_loop_t **out, sgusto_plan_t *plan, stpwl_t *planne
     if ((rc = h->setup("sgusto_loop_create", what, N, n, m, nz, B, dt, dt_sim, n_keep, max_steps_per_run, nz)) ||
         (rc = h->zf.alloc(sizeof(double) * B * nz)))
         return fail(rc);
+    (void)sgusto_loop_end_row(N, dt, dt_sim, n_keep, &h->j_end, &h->theta_end);
+    h->XBrec.shape(sizeof(double) * n, 1); h->UBrec.shape(sizeof(double) * m, 1);
     *out = h;
     return SRH_OK;
 }
@@ -263,6 +342,17 @@ int sgusto_loop_set_feedback(sgusto_loop_t *h, const double *K) {
     return SRH_OK;
 }
 
+int sgusto_loop_set_chained(sgusto_loop_t *h, int on) {
+    SRH_REQUIRE(h, "sgusto_loop_set_chained: null handle");
+    SRH_REQUIRE(h->k == 0, "sgusto_loop_set_chained: %lld period(s) have run since the last reset: the policy of a loop changes only in front "
+                "of its first period (call sgusto_loop_reset first)", (long long)h->k);
+    SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
+    int rc;
+    if (on && !h->xchain.p && (rc = h->xchain.alloc(sizeof(double) * h->B * h->n))) return rc;
+    h->chained = on != 0;
+    return SRH_OK;
+}
+
 int sgusto_loop_reset(sgusto_loop_t *h, const double *x0, double t_start) {
     SRH_REQUIRE(h && x0, "sgusto_loop_reset: null argument");
     SRH_CHECK_HIP(hipStreamSynchronize(h->stream));
@@ -272,17 +362,26 @@ int sgusto_loop_reset(sgusto_loop_t *h, const double *x0, double t_start) {
 }
 
 // sgusto_loop_run and sgusto_loop_run_observed: Xhat != null is the observed loop (Vn, Y_cl, ekf_status belong to it)
+// Xbar / Ubar: the tape of the chained policy (sgusto_loop_run_tape), or null
 static int loop_run(sgusto_loop_t *h, int periods, const double *W, const double *Vn, double *X_cl, double *Z_cl, double *U_cl, int32_t *iters,
-                    int32_t *status, double *J, double *Xhat, double *Y_cl, int32_t *ekf_status) {
+                    int32_t *status, double *J, double *Xhat, double *Y_cl, int32_t *ekf_status, double *Xbar = nullptr, double *Ubar = nullptr) {
     const bool observed = Xhat != nullptr;
     const size_t B = (size_t)h->B;
-    double *xhat = observed ? h->obs->x_dev() : nullptr, *xcur = h->xcur.as<double>();
+    double *xhat = observed ? h->obs->x_dev() : nullptr, *xcur = h->xcur.as<double>(), *xchain = h->xchain.as<double>();
+    int rc0;
+    if (Xbar && !h->XBrec.d.p && (rc0 = h->alloc_recs({&h->XBrec}))) return rc0;
+    if (Ubar && !h->UBrec.d.p && (rc0 = h->alloc_recs({&h->UBrec}))) return rc0;
+    h->XBrec.host = Xbar; h->UBrec.host = Ubar;
+    h->XBrec.row0 = h->k > 0 ? xchain : nullptr;          // row 0 of a later run: the old plan's end, where the run's first plan starts
     h->Wd.host = (void *)W; h->Vd.host = (void *)Vn; h->Xrec.host = X_cl; h->Zrec.host = Z_cl; h->Urec.host = U_cl; h->Irec.host = iters;
     h->Srec.host = status; h->Jrec.host = J; h->XHrec.host = Xhat; h->Yrec.host = Y_cl; h->Erec.host = ekf_status;
     h->XHrec.row0 = xhat;               // row 0 of the estimate record: the estimates the run starts from
     // with an observer the plan starts from the estimate; row 0 of the records (the prepare kernel's) is the plant's state all the same
-    const PrepUnit u{observed ? xhat : xcur, observed ? xcur : nullptr, h->planner->H.as<double>(),
-                     (h->has_z && h->has_Qzf) ? h->zf.as<double>() : nullptr, true};
+    PrepUnit u{observed ? xhat : xcur, observed ? xcur : nullptr, h->planner->H.as<double>(),
+               (h->has_z && h->has_Qzf) ? h->zf.as<double>() : nullptr, true};
+    // a chained period k >= 1 starts from the chain state; row 0 of the records stays the plant's state
+    auto chain_on = [&]() { u.xcur = xchain; u.xplant = xcur; };
+    if (h->chained && h->k > 0) chain_on();
     return loop_run_periods(h, "sgusto_loop_run", periods, u, [&](int p, const PrepArgs &a, const LoopRows &r) -> int {
         int rc;
         // scp/standalone.py:32-33: the first guess is the planner's own zero-input rollout from x0
@@ -292,6 +391,15 @@ static int loop_run(sgusto_loop_t *h, int periods, const double *W, const double
                                         h->Srec.as<int32_t>() + p * B, nullptr, (void *)h->stream)) ||
             (rc = sgusto_plan_costs_dev(h->plan, h->Jrec.as<double>() + p * B, (void *)h->stream)))
             return rc;
+        if (h->chained) {
+            ChainArgs c = h->chain_args();
+            c.xopt = a.xopt; c.uopt = a.uopt;
+            c.x_next = xchain;
+            c.Xbar = Xbar ? h->XBrec.as<double>() : nullptr; c.Ubar = Ubar ? h->UBrec.as<double>() : nullptr;
+            c.rows = r.rows_x; c.row0 = r.row0_u; c.x_row0 = a.first;
+            if ((rc = h->launch_chain(c))) return rc;
+            chain_on();                 // (read by the next period's prepare launch)
+        }
         AdvArgs v = h->adv_args();
         v.xopt = a.xopt; v.uopt = a.uopt;
         v.W = W ? h->Wd.as<double>() : nullptr; v.w_step0 = r.w_step0;
@@ -350,6 +458,46 @@ int sgusto_loop_run_observed(sgusto_loop_t *h, int periods, const double *W, con
     SRH_REQUIRE(h->obs, "sgusto_loop_run_observed: no observer attached (sgusto_loop_set_observer)");
     SRH_REQUIRE(h->have_state && h->observed_state, "sgusto_loop_run_observed: no plant state and estimate yet (call sgusto_loop_reset_observed first)");
     return loop_run(h, periods, W, V, X_cl, Z_cl, U_cl, iters, status, J, Xhat, Y_cl, ekf_status);
+}
+
+int sgusto_loop_run_tape(sgusto_loop_t *h, int periods, const double *W, const double *V, double *X_cl, double *Z_cl, double *U_cl,
+                         int32_t *iters, int32_t *status, double *J, double *Xhat, double *Y_cl, int32_t *ekf_status, double *Xbar, double *Ubar) {
+    SRH_REQUIRE(h && Z_cl && U_cl && iters && status && J, "sgusto_loop_run_tape: null argument");
+    SRH_REQUIRE(h->chained || (!Xbar && !Ubar), "sgusto_loop_run_tape: the loop re-plans from the plant (mpc=True): it follows no nominal tape "
+                "(sgusto_loop_set_chained)");
+    const bool observed = Xhat != nullptr;
+    SRH_REQUIRE(observed ? (Y_cl && ekf_status) : (!V && !Y_cl && !ekf_status), "sgusto_loop_run_tape: Xhat, Y_cl and ekf_status come together "
+                "(the observed loop), V with them");
+    SRH_REQUIRE(periods >= 1, "sgusto_loop_run_tape: periods must be positive");
+    if (!observed) {
+        SRH_REQUIRE(h->have_state, "sgusto_loop_run_tape: no plant state yet (call sgusto_loop_reset first)");
+        SRH_REQUIRE(!h->observed_state, "sgusto_loop_run_tape: the loop was reset with estimates (sgusto_loop_reset_observed): pass Xhat, Y_cl and "
+                    "ekf_status, or call sgusto_loop_reset");
+    } else {
+        SRH_REQUIRE(h->obs, "sgusto_loop_run_tape: no observer attached (sgusto_loop_set_observer)");
+        SRH_REQUIRE(h->have_state && h->observed_state, "sgusto_loop_run_tape: no plant state and estimate yet (call sgusto_loop_reset_observed first)");
+    }
+    return loop_run(h, periods, W, V, X_cl, Z_cl, U_cl, iters, status, J, Xhat, Y_cl, ekf_status, Xbar, Ubar);
+}
+
+int sgusto_loop_chain(sgusto_loop_t *h, const double *xopt, const double *uopt, double *x_next, double *Xbar_rows, double *Ubar_rows) {
+    SRH_REQUIRE(h && xopt && uopt, "sgusto_loop_chain: null argument");
+    const size_t D = sizeof(double), B = (size_t)h->B, N = h->N, n = h->n, m = h->m, nk = h->n_keep;
+    srh::DevBuf dxo, duo, dx, dX, dU;
+    int rc;
+    if ((rc = dxo.upload(xopt, D * B * (N + 1) * n)) || (rc = duo.upload(uopt, D * B * N * m)) || (x_next && (rc = dx.alloc(D * B * n))) ||
+        (Xbar_rows && (rc = dX.alloc(D * B * (nk + 1) * n))) || (Ubar_rows && (rc = dU.alloc(D * B * (nk + 1) * m))))
+        return rc;
+    ChainArgs c = h->chain_args();
+    c.xopt = dxo.as<double>(); c.uopt = duo.as<double>();
+    c.x_next = x_next ? dx.as<double>() : nullptr;
+    c.Xbar = Xbar_rows ? dX.as<double>() : nullptr; c.Ubar = Ubar_rows ? dU.as<double>() : nullptr;
+    c.rows = (int64_t)nk + 1; c.row0 = 0; c.x_row0 = 1;
+    if ((rc = loop_wait(h->launch_chain(c), h->stream))) return rc;
+    if (x_next && (rc = dx.download(x_next, D * B * n))) return rc;
+    if (Xbar_rows && (rc = dX.download(Xbar_rows, D * B * (nk + 1) * n))) return rc;
+    if (Ubar_rows && (rc = dU.download(Ubar_rows, D * B * (nk + 1) * m))) return rc;
+    return SRH_OK;
 }
 
 int sgusto_loop_last_inputs(sgusto_loop_t *h, double *x0, double *u_init, double *x_init, double *z, double *zf, double *u_des) {

@@ -280,3 +280,12 @@ def gusto_loop_schedule(N, dt, dt_sim, n_keep, t_start, k):
     check(lib().sgusto_loop_schedule(C.c_int(N), C.c_double(dt), C.c_double(dt_sim), C.c_int(n_keep), C.c_double(t_start), C.c_int64(k),
                                      C.byref(t_k), C.byref(idx0), iptr(j), dptr(theta)), 'sgusto_loop_schedule')
     return t_k.value, idx0.value, j, theta
+
+
+def gusto_loop_end_row(N, dt, dt_sim, n_keep):
+    """sgusto_loop_end_row: the end row (j_end, theta_end) of a period's schedule as the library computes it, on the host -- no GPU
+    needed; scp.closed_loop.schedule_end is the numpy statement."""
+    j, theta = C.c_int32(0), C.c_double(0.0)
+    check(lib().sgusto_loop_end_row(C.c_int(N), C.c_double(dt), C.c_double(dt_sim), C.c_int(n_keep), C.byref(j), C.byref(theta)),
+          'sgusto_loop_end_row')
+    return j.value, theta.value

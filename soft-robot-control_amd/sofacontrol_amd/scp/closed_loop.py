@@ -8,7 +8,11 @@ the times of a period -- is computed on the host in float64 (`schedule`).
 
 With `observer=` (a tpwl.observer.DiscreteEKFObserverBatch) the loop is the reference's output-feedback loop (tpwl/controllers.py:85-117):
 the plans start from the filters' estimates, the law reads the estimate, and every plant step is followed by a measurement
-y = C x + y_ref (+ v) and one step of every filter -- still one host wait per run."""
+y = C x + y_ref (+ v) and one step of every filter -- still one host wait per run.
+
+`mpc=False` selects the reference's DEFAULT policy (tpwl/controllers.py:236): from period 1 on a plan starts from the previous plan at
+n_keep dt_sim into it (`schedule_end`), not from the plant or the estimate; `record_tape=True` adds the nominal tape the reference
+stitches (x_bar, u_bar of the result).  The default here stays mpc=True."""
 import collections
 import ctypes as C
 
@@ -40,6 +44,16 @@ def schedule(N, dt, dt_sim, n_keep, t_start=0.0, k=0):
     return Schedule(t_k, idx0, j, theta)
 
 
+def schedule_end(N, dt, dt_sim, n_keep):
+    """(j_end, theta_end): the rule of a sub-step at the period's end tau = n_keep dt_sim -- where the chained policy (mpc=False) reads
+    the plan for the next period's start state, x_opt[-1] of tpwl/controllers.py:272.  At n_keep dt_sim == N dt: j_end = N - 1 and
+    theta_end is 1 to rounding.  Plain float64 arithmetic, no GPU and no library call."""
+    N, n_keep, dt, dt_sim = int(N), int(n_keep), float(dt), float(dt_sim)
+    tau = n_keep * dt_sim
+    j = min(int(tau / dt), N - 1)
+    return j, (tau - j * dt) / dt
+
+
 class ClosedLoopResult:
     """Records of one `run`: x (B, S + 1, n_x) or None, z (B, S + 1, n_z), u (B, S, n_u) with S = periods n_keep (row 0: the state the run
     started from); iters, status, J (periods, B) of the solves; t (S + 1,) the times of the rows."""
@@ -48,8 +62,11 @@ class ClosedLoopResult:
     # them, proj (B, S + 1) int32 their status words: 0 inside Y, 1 projected, -1 no certified projection, -2 not finite
     y_used = proj = None
 
-    def __init__(self, x, z, u, iters, status, J, t, x_hat=None, y=None, ekf_status=None):
+    def __init__(self, x, z, u, iters, status, J, t, x_hat=None, y=None, ekf_status=None, x_bar=None, u_bar=None):
         self.x, self.z, self.u, self.iters, self.status, self.J, self.t = x, z, u, iters, status, J, t
+        # the chained policy's nominal tape (ClosedLoopBatch(mpc=False, record_tape=True); None otherwise): x_bar (B, S + 1, n_x), u_bar
+        # (B, S + 1, n_u), the reference's x_opt / u_opt of save_controller_info at the rows' times
+        self.x_bar, self.u_bar = x_bar, u_bar
         # the observed loop (None without an observer): x_hat (B, S + 1, n_x) the estimates, row 0 those the run started from; y (B, S,
         # n_y) the measurements; ekf_status (periods, B) the OR of the period's filter statuses
         self.x_hat, self.y, self.ekf_status = x_hat, y, ekf_status
@@ -171,7 +188,8 @@ class _LoopBatch:
         self._call(entry, C.c_int(periods), *[_ptr(a) for a in arrays])
         t = schedule(self.N, self.dt, self.dt_sim, self.n_keep, self.t_start, self._k).t_k + self.dt_sim * np.arange(periods * self.n_keep + 1)
         self._k += periods
-        res = ClosedLoopResult(r['x'], r['z'], r['u'], r['iters'], r['status'], r['J'], t, x_hat=r.get('x_hat'), y=r.get('y'), ekf_status=r.get('ekf_status'))
+        res = ClosedLoopResult(r['x'], r['z'], r['u'], r['iters'], r['status'], r['J'], t, x_hat=r.get('x_hat'), y=r.get('y'), ekf_status=r.get('ekf_status'),
+                               x_bar=r.get('x_bar'), u_bar=r.get('u_bar'))
         res.y_used, res.proj = r.get('y_used'), r.get('proj')
         return res
 
@@ -203,7 +221,8 @@ class _LoopBatch:
 class ClosedLoopBatch(_LoopBatch):
     _sym, _max_iters = 'sgusto_loop', 'sgusto_plan_set_max_iters'
 
-    def __init__(self, gusto, plant, dt_sim, n_keep, t=None, z=None, u=None, phase=None, K=None, max_steps_per_run=None, observer=None):
+    def __init__(self, gusto, plant, dt_sim, n_keep, t=None, z=None, u=None, phase=None, K=None, max_steps_per_run=None, observer=None, mpc=True,
+                 record_tape=False):
         """gusto: a GuSTO on a TPWLGuSTO model with batch=B (the fused resident plan); plant: a TPWLATV (it may be the planner's own
         dyn_sys), stepped at dt_sim; n_keep: plant steps per period (the reference's N_replan with the controller clock at dt_sim).
         t (T,), z (T, n_z), u (T, n_u): the target table, interpolated as scp/standalone.py:29-31 does; phase (B,): a time offset of
@@ -211,7 +230,17 @@ class ClosedLoopBatch(_LoopBatch):
         max_steps_per_run: the longest run in plant steps (sizes the record blocks; default 16 periods).
         observer: a DiscreteEKFObserverBatch of the same batch, n_x and n_u; its model is stepped at dt_sim (it may be the planner's
         dyn_sys, and it need not be the plant).  The loop binds it to dt_sim and steps it on its own stream: do not step it elsewhere
-        while the loop is in use."""
+        while the loop is in use.
+        mpc: the reference's flag of the same name (tpwl/controllers.py:236).  True, the default HERE: every period re-plans from the
+        plant state (the estimate with an observer).  False -- the REFERENCE's default, and what its TPWL drivers run
+        (examples/diamond/diamond.py:249, examples/hardware/diamond.py:270, examples/trunk/trunk.py:266) --: the chained policy.  Period 0
+        after a reset is the same; period k >= 1 starts from the previous plan at tau = n_keep dt_sim into it (`schedule_end`; x_opt[-1]
+        of controllers.py:272), so the plans do not depend on the plant and only the law and the filters close the loop.  Warm start,
+        targets, law and plant step are the same; one small launch per period is added (loop_chain_kernel).
+        record_tape: with mpc=False, every run also returns the nominal tape the reference stitches (x_opt / u_opt of
+        save_controller_info): x_bar (B, S + 1, n_x), u_bar (B, S + 1, n_u) of the result.  Row p n_keep + s is plan p at s dt_sim; at a
+        junction row k n_keep (k >= 1) x_bar keeps the old plan's end and u_bar takes the new plan's first row, as the reference's
+        concatenate does (controllers.py:313-315).  It is a property of the loop (`set_record_tape`), not of a call."""
         if not (getattr(gusto, '_fused', False) and not getattr(gusto, '_ssm', False)):
             raise RuntimeError('ClosedLoopBatch needs a GuSTO on a TPWLGuSTO model with a fused resident plan (not an SSM plan, not '
                                'the host loop): there is no device rollout / solve to chain otherwise')
@@ -239,6 +268,19 @@ class ClosedLoopBatch(_LoopBatch):
             observer.bind(self.dt_sim)
             self.n_y = observer.meas_dim
             self._call('_set_observer', observer._h)
+        self.mpc, self.record_tape = bool(mpc), False
+        if not self.mpc:
+            self._call('_set_chained', C.c_int(1))
+        self.set_record_tape(record_tape)
+
+    def set_record_tape(self, on):
+        """Whether the runs from now on return the chained policy's tape (x_bar, u_bar of the result).  Refused with mpc=True: a loop
+        that re-plans from the plant follows no nominal tape.  Returns the loop."""
+        if on and self.mpc:
+            raise RuntimeError('ClosedLoopBatch: record_tape=True needs mpc=False: a loop that re-plans from the plant every period '
+                               '(mpc=True) follows no nominal tape')
+        self.record_tape = bool(on)
+        return self
 
     def reset(self, x0, t_start=0.0):
         """Plant states x0 (B, n_x) at t_start.  With an observer: reset_observed(x0, None, t_start) -- the estimates start at x0."""
@@ -270,7 +312,16 @@ class ClosedLoopBatch(_LoopBatch):
         periods = int(periods)
         fits, r = self._records(periods, record_x, self.n_z)
         W = None if W is None or not fits else _lib.f64(np.asarray(W).reshape(periods, self.n_keep, self.B, self.n_x))
+        if self.record_tape:
+            return self._run_tape(periods, fits, [W, None], r, [None] * 3)
         return self._run('_run', periods, [W] + list(r.values()), r)
+
+    def _run_tape(self, periods, fits, noise, r, observed):
+        """sgusto_loop_run_tape: the records r, the observed loop's records (or three None), then the tape."""
+        B, S = self.B, periods * self.n_keep
+        r = dict(r, x_bar=np.empty((B, S + 1, self.n_x) if fits else 1), u_bar=np.empty((B, S + 1, self.n_u) if fits else 1))
+        head = [r[k] for k in ('x', 'z', 'u', 'iters', 'status', 'J')]
+        return self._run('_run_tape', periods, noise + head + observed + [r['x_bar'], r['u_bar']], r)
 
     def run_observed(self, periods, W=None, V=None, record_x=True):
         """run with the filters in the loop.  V (periods, n_keep, B, n_y): measurement noise, None: zero.  The result carries x_hat, y
@@ -286,7 +337,23 @@ class ClosedLoopBatch(_LoopBatch):
             V = _lib.f64(V)
         fits, r = self._records(periods, record_x, self.n_z, x_hat=(1, self.n_x), y=(0, self.n_y), ekf_status=None)
         W = None if W is None or not fits else _lib.f64(np.asarray(W).reshape(periods, self.n_keep, self.B, self.n_x))
+        if self.record_tape:
+            return self._run_tape(periods, fits, [W, V if fits else None], r, [r['x_hat'], r['y'], r['ekf_status']])
         return self._run('_run_observed', periods, [W, V if fits else None] + list(r.values()), r)
+
+    def _chain(self, xopt, uopt):
+        """The chain kernel alone on host-supplied plans (for tests): xopt (B, N+1, n_x), uopt (B, N, n_u) -> x_next (B, n_x), the start
+        state of the next period, and the tape rows s = 0..n_keep of a period: x_bar (B, n_keep + 1, n_x), u_bar (B, n_keep + 1, n_u)."""
+        B, N, nk = self.B, self.N, self.n_keep
+        xopt, uopt = np.asarray(xopt), np.asarray(uopt)
+        if xopt.shape != (B, N + 1, self.n_x) or uopt.shape != (B, N, self.n_u):
+            raise RuntimeError('ClosedLoopBatch._chain: xopt must have shape (B, N + 1, n_x) = %s and uopt (B, N, n_u) = %s, got %s and %s'
+                               % ((B, N + 1, self.n_x), (B, N, self.n_u), xopt.shape, uopt.shape))
+        xopt, uopt = _lib.f64(xopt), _lib.f64(uopt)
+        xn, xb, ub = np.empty((B, self.n_x)), np.empty((B, nk + 1, self.n_x)), np.empty((B, nk + 1, self.n_u))
+        _lib.check(_lib.lib().sgusto_loop_chain(self._h, _lib.dptr(xopt), _lib.dptr(uopt), _lib.dptr(xn), _lib.dptr(xb), _lib.dptr(ub)),
+                   'sgusto_loop_chain')
+        return xn, xb, ub
 
     def _advance(self, xopt, uopt, x, W=None):
         """The advance kernel alone on host-supplied plans (for tests): xopt (B, N+1, n_x), uopt (B, N, n_u), x (B, n_x), W (n_keep, B,

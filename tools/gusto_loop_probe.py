@@ -79,10 +79,15 @@ class HostLoop:
         self.p, self.gu, self.w, self.schedule, self.ws = p, gusto, w, schedule, GuSTOSolverNode._warm_start
         self.x, self.k, self.xopt, self.uopt = p['x0'].copy(), 0, None, None
 
+    def start_state(self):
+        """The states the period's plans start from: the plant's (mpc=True; tools/gusto_loop_chain_probe.py overrides it)."""
+        return self.x
+
     def period(self):
         p, gu, N, dt = self.p, self.gu, self.w['N'], self.w['dt']
         B, m = self.x.shape[0], self.w['m']
         s = self.schedule(N, dt, DT_SIM, N_KEEP, 0.0, self.k)
+        x_start = self.start_state()
         if self.k == 0:
             u_init = np.zeros((B, N, m))
             x_init, _ = p['gm'].rollout(self.x, u_init, dt)
@@ -92,7 +97,7 @@ class HostLoop:
                 node = types.SimpleNamespace(topt=np.arange(N + 1.0), xopt=self.xopt[b], uopt=self.uopt[b], N=N)
                 u_init[b], x_init[b] = self.ws(node, float(s.idx0))
         z = p['zi']((s.t_k + p['phase'])[:, None] + dt * np.arange(N + 1))
-        xo, uo, _ = gu.solve_batch(self.x, u_init, x_init, z=z)
+        xo, uo, _ = gu.solve_batch(x_start, u_init, x_init, z=z)
         self.xopt, self.uopt = xo, uo
         uext = np.concatenate((uo, uo[:, -1:]), axis=1)
         Ad, Bd, dd = p['tables']
