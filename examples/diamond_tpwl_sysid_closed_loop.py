@@ -5,14 +5,18 @@ points), stepped at dt_sim = 0.01 s, the reference driver's cost, input box and 
 planner is the plant's own model.  Here the plant is excited first: E open-loop episodes from seeded disturbed starts under seeded
 random inputs inside the input box, each held for one planner step (five simulation steps), rolled out by the batched plant rollout
 (TPWLATV.rollout).  tpwl.sysid.fit_tpwl fits the tables at Ts = 0.05 from the dt_sim = 0.01 records with stride = 5, so the fitted
-model's forward-Euler step at Ts is the plant's five-step map.  The linearisation points are the plant's own by default (a user knows
-where the robot was linearised), or with --kmeans K the centroids of the kept states (points_from_records).  Points that received too
-few samples are dropped (on_fail='drop'): the open-loop episodes do not visit every region.
+model's forward-Euler step at Ts is the plant's five-step map.  The linearisation points come from --points: `plant`, the plant's own
+(the default: a user knows where the robot was linearised); `kmeans`, the --kmeans K centroids of the kept states (points_from_records;
+--kmeans K alone selects it too); `distance`, the reference's distance rule on the kept states (points_by_distance) with --threshold
+(default: half the largest distance of a kept position from the mean kept position) -- every point is then a visited state, and their
+number follows the spread of the records.  Points that received too few samples are dropped (on_fail='drop'): the open-loop episodes do
+not visit every region.  For the chosen source the points, the points dropped, the one-step error and the tip error are printed; no
+source is promised to beat another.
 
 The one-step error of the fitted model is printed on the fit's records and on held-out episodes, then B loops run on the true plant with
 the fitted planner, and the tip error is printed.
 
-    python examples/diamond_tpwl_sysid_closed_loop.py [--episodes 128] [--steps 500] [--batch 16] [--periods 10] [--ridge 1e-8] [--kmeans 0] [--seed 0]
+    python examples/diamond_tpwl_sysid_closed_loop.py [--episodes 128] [--steps 500] [--batch 16] [--periods 10] [--ridge 1e-8] [--points plant|kmeans|distance] [--kmeans 0] [--threshold T] [--seed 0]
 
 Needs an MI355X (no CPU fallback)."""
 import argparse
@@ -50,8 +54,13 @@ def main():
     ap.add_argument('--periods', type=int, default=10, help='re-planning periods of 10 steps of 0.01 s')
     ap.add_argument('--ridge', type=float, default=1e-8)
     ap.add_argument('--kmeans', type=int, default=0, help='take K points from the records by k-means instead of the plant\'s own')
+    ap.add_argument('--points', choices=('plant', 'kmeans', 'distance'), default=None, help='the source of the linearisation points (default: plant)')
+    ap.add_argument('--threshold', type=float, default=None, help='--points distance: the threshold of the distance rule')
     ap.add_argument('--seed', type=int, default=0)
     args = ap.parse_args()
+    source = args.points or ('kmeans' if args.kmeans else 'plant')
+    if source == 'kmeans' and not args.kmeans:
+        args.kmeans = 32
 
     import workloads as wl
     from scipy.interpolate import interp1d
@@ -59,7 +68,7 @@ def main():
     from sofacontrol_amd.scp.closed_loop import ClosedLoopBatch
     from sofacontrol_amd.scp.gusto import GuSTO
     from sofacontrol_amd.scp.models.tpwl import TPWLGuSTO
-    from sofacontrol_amd.tpwl.sysid import fit_tpwl, one_step_error, points_from_records
+    from sofacontrol_amd.tpwl.sysid import fit_tpwl, one_step_error, points_by_distance, points_from_records
     from sofacontrol_amd.tpwl.tpwl import TPWLATV
     from sofacontrol_amd.utils import HyperRectangle
 
@@ -78,11 +87,23 @@ def main():
     X, U = excite(plant, E, S, rng)
     assert np.isfinite(X).all(), 'the open-loop episodes left the plant\'s range'
     Xv, Uv = excite(plant, max(2, E // 8), S, rng)                           # held-out episodes
-    if args.kmeans:
+    if source == 'kmeans':
         with contextlib.redirect_stdout(io.StringIO()):
             q, v = points_from_records(X, args.kmeans, stride=STRIDE)
+        print('points: %d k-means centroids of the kept states' % len(q))
+    elif source == 'distance':
+        thr = args.threshold
+        if thr is None:
+            qk = X[:, ::STRIDE, r:].reshape(-1, r)
+            thr = 0.5 * float(np.linalg.norm(qk - qk.mean(axis=0), axis=1).max())
+        t0 = time.perf_counter()
+        sel = points_by_distance(X, weights, thr, stride=STRIDE)
+        print('points: %r by the distance rule, threshold %.4g, %.1f ms (records from the host)%s'
+              % (sel, thr, 1e3 * (time.perf_counter() - t0), '' if sel.complete else '; the cap of 1024 points was met: raise the threshold'))
+        q, v = sel.q, sel.v
     else:
         q, v = np.asarray(w['tab']['q']), np.asarray(w['tab']['v'])
+        print('points: the %d points of the plant\'s own table' % len(q))
     t0 = time.perf_counter()
     with contextlib.redirect_stdout(io.StringIO()):
         model, fit = fit_tpwl(X, U, q, v, weights, STRIDE * DT_SIM, rom_info, stride=STRIDE, ridge=args.ridge, on_fail='drop', Hf=Hf)

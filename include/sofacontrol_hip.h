@@ -1066,7 +1066,8 @@ int sssm_fit_solve(sssm_fit_t *f, double ridge, double *rd_coeff, double *Bd, do
  *             2 a pivot that is not positive, not finite or not above n eps (1 + ridge), `column` = its column of phi (0 .. n_x - 1 a
  *             state, n_x .. n_x + m - 1 an input, n - 1 the constant), or n when the solution holds a non-finite entry that no pivot
  *             caught.  The tables of a point that did not solve are zeros.
- * Not offered: weighting-mode fits, sample weights, a choice of points, full-order records (project them first).
+ * Not offered: weighting-mode fits, sample weights, full-order records (project them first).  The points are the caller's;
+ * stpwl_select_points (below) chooses them from the records by the reference's distance rule.
  * Limits (SRH_EINVAL before any device call): n <= 128, m <= 16 (stpwl_create's), P <= 1024, fewer than 2^31 kept rows per add call.
  * A kept row that is not finite (x or u) is refused by stpwl_fit_add / _add_dev with the episode and row of the first one; the sums
  * are untouched then.  The sums are accumulated on f64 MFMA without floating-point atomics: the kept rows are ordered by region with a
@@ -1092,6 +1093,42 @@ int stpwl_fit_sums(stpwl_fit_t *f, int p, double *G, double *R, double *Q, int64
  * SRH_EINVAL when no sample has been added; a point that does not solve is reported in status, not by the return code. */
 int stpwl_fit_solve(stpwl_fit_t *f, double ridge, int64_t min_samples, double *A_c, double *B_c, double *d_c, double *u, int32_t *status,
                     int32_t *column);
+
+/* TPWL point selection from records (csrc/tpwl_select.hip): the reference's distance rule (tpwl_utils.py:156-196) as a greedy scan over
+ * recorded reduced states; what it returns goes into stpwl_fit_create unchanged.
+ * THE SELECTION RULE ("TPWL model identification", defines it):
+ *   records    x (E x T x n_x), x = [v; q], n_x = 2 r, and `stride` s >= 1 as for stpwl_fit_add.  The candidates are ALL kept rows
+ *              0, s, 2s, .. of every episode (the last kept row too), scanned episode by episode and inside an episode in row order.
+ *   points     the table starts as the seed q0, v0 (P0 x r each, P0 >= 0; NULL when P0 = 0).  With an empty table the first candidate is
+ *              taken unconditionally (tpwl_utils.py:161-162).
+ *   distances  of a candidate c to a point p: dq = w_q ||q_p - q_c||, dv = w_v ||v_p - v_c||, in the arithmetic of the point-search rule
+ *              of stpwl_nearest: each squared norm summed by fma in the order j = 0, 1, ... from 0.0, then a correctly rounded sqrt.
+ *              With w_v == 0 the velocity part is not read and dv = 0.
+ *   decision   separate == 0 (tpwl_utils.py:193): c is taken iff dq + dv >= threshold for EVERY point of the table; separate != 0
+ *              (tpwl_utils.py:187-191): iff dq >= threshold for every point, or dv >= threshold for every point.  A taken candidate
+ *              joins the table before the next candidate is examined.
+ *   cap        max_points counts the seed plus the taken points, max(P0, 1) <= max_points <= 1024 (the fit's limit on P).  When a
+ *              candidate would become point max_points + 1 the scan stops there: status 1, stopped_at = that candidate; the rows behind
+ *              it were not examined.
+ * Outputs: count = the points of the table at the end (seed included); for the count - P0 taken points, in the order taken: index
+ * ((max_points - P0) x 2 int64: episode, row in the UNstrided record), q and v ((max_points - P0) x r: bit-for-bit copies of the record's
+ * entries), dmin ((max_points - P0), or x 2 when separate: min dq, min dv) = the smallest distance to the table at the moment the point
+ * was taken, +inf for an unconditional first point; status 0 complete / 1 cap reached; stopped_at (2: episode, row; -1, -1 when
+ * complete).  Any output other than count may be NULL.
+ * Refused with SRH_EINVAL before anything is written: threshold not finite or <= 0; a weight negative or not finite, or both zero;
+ * r < 1 (r <= 128); a seed entry that is not finite; a kept row that is not finite (the message names the episode and row of the first
+ * one, as stpwl_fit_add does).
+ * The answer does not depend on how the device splits the work (min is exact; no floating-point atomics), and scanning x1 and then x2
+ * with the first result as the seed gives exactly the result of scanning their concatenation.  stpwl_select_points takes host records;
+ * the _dev form reads device records in place on `stream` and synchronises it once, at the end.  stpwl_select_plan answers on the host
+ * (no GPU): the candidates of a chunk, the dynamic LDS of the distance kernel and the launches of a call of `candidates` kept rows. */
+int stpwl_select_plan(int r, int64_t candidates, int *chunk, int64_t *lds_bytes, int64_t *launches);
+int stpwl_select_points(const double *x, int64_t E, int64_t T, int r, int stride, double w_q, double w_v, double threshold, int separate,
+                        int P0, const double *q0, const double *v0, int max_points, int *count, int64_t *index, double *q, double *v,
+                        double *dmin, int *status, int64_t *stopped_at);
+int stpwl_select_points_dev(const double *x_dev, int64_t E, int64_t T, int r, int stride, double w_q, double w_v, double threshold,
+                            int separate, int P0, const double *q0, const double *v0, int max_points, int *count, int64_t *index,
+                            double *q, double *v, double *dmin, int *status, int64_t *stopped_at, void *stream);
 
 /* =====================================================================================================
  * ROMPC baseline. reference: sofacontrol/baselines/rompc/rompc.py:57-89, rompc/observer.py:30-46, rompc_utils.py:52-53

@@ -1,1 +1,2 @@
-from .sysid import TPWLFitResult, TPWLSysID, fit_tpwl, one_step_error, points_from_records  # noqa: F401
+from .sysid import (TPWLFitResult, TPWLPointSelection, TPWLSysID, fit_tpwl, one_step_error, points_by_distance,  # noqa: F401
+                    points_from_records)

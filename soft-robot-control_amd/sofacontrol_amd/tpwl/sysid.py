@@ -25,8 +25,21 @@ the fit from records.
   same error bound).
   Limits: n = n_x + m + 1 <= 128 (the accumulate kernel then keeps 36 + 64 tiles, 25 per wave, in registers), m <= 16, P <= 1024.
 
-NOT OFFERED: weighting-mode fits; sample weights; selection of points by the reference's distance heuristics
-(points_from_records runs k-means on the kept states instead); full-order records (project them first: POD.compute_RO_state)."""
+THE POINTS.  The fit takes the caller's points.  Two functions choose them from the records.
+  points_by_distance: the reference's distance rule (tpwl_utils.TPWLSnapshotData.evaluate_point, eval_type = 'distance') as a greedy scan
+  on the device (csrc/tpwl_select.hip; C ABI: stpwl_select_points).  The candidates are ALL kept rows of every episode (the last kept row
+  too), scanned episode by episode in row order; the table starts as the optional seed (q0, v0); with an empty table the first candidate
+  is taken unconditionally.  For a candidate c and a point p, dq = w_q |q_p - q_c| and dv = w_v |v_p - v_c| in the arithmetic of the
+  point-search rule (with w_v == 0 the velocity is not read, dv = 0).  separate=False: c is taken iff dq + dv >= threshold for EVERY point
+  of the table; separate=True: iff dq >= threshold for every point, or dv >= threshold for every point.  A taken candidate joins the table
+  before the next one is examined.  max_points counts the seed plus the taken points (max(P0, 1) <= max_points <= 1024); when a candidate
+  would become point max_points + 1 the scan stops there (complete = False, stopped_at = its episode and row).  The number of points
+  follows the spread of the data, every point is a visited state, and every kept row lies within the threshold of some point.  Scanning
+  X1 and then X2 with the first result as the seed gives exactly the result of scanning their concatenation.
+  points_from_records: the k-means centroids of the kept states (k is the caller's; a centroid is an average, not a visited state).
+
+NOT OFFERED: weighting-mode fits; sample weights; the reference's 'dynamics' rule of selection (it needs the simulator's Jacobians at the
+candidate); full-order records (project them first: POD.compute_RO_state)."""
 import ctypes as C
 
 import numpy as np
@@ -54,6 +67,11 @@ def _bind():
     L.stpwl_fit_counts.argtypes = [vp, C.POINTER(i64)]
     L.stpwl_fit_sums.argtypes = [vp, C.c_int, dp, dp, dp, C.POINTER(i64)]
     L.stpwl_fit_solve.argtypes = [vp, C.c_double, i64, dp, dp, dp, dp, i32p, i32p]
+    i64p, dbl = C.POINTER(i64), C.c_double
+    sel = [i64, i64, C.c_int, C.c_int, dbl, dbl, dbl, C.c_int, C.c_int, dp, dp, C.c_int, ip, i64p, dp, dp, dp, ip, i64p]
+    L.stpwl_select_plan.argtypes = [C.c_int, i64, ip, i64p, i64p]
+    L.stpwl_select_points.argtypes = [dp] + sel
+    L.stpwl_select_points_dev.argtypes = [vp] + sel + [vp]
     _BOUND = True
     return L
 
@@ -327,3 +345,115 @@ def points_from_records(X, k, random_state=0, n_init=10, stride=1):
     cent = np.asarray(pod.compute_kmeans_centroids(S, int(k), n_init=n_init, random_state=random_state))
     q, v = scutils.x2qv(cent)
     return np.ascontiguousarray(q), np.ascontiguousarray(v)
+
+
+MAX_POINTS = 1024
+
+
+def select_plan(r, candidates):
+    """stpwl_select_plan, on the host (no GPU): {'chunk', 'lds_bytes', 'launches'} of a scan of `candidates` kept rows."""
+    a, b, c = C.c_int(0), C.c_int64(0), C.c_int64(0)
+    _lib.check(_bind().stpwl_select_plan(int(r), int(candidates), C.byref(a), C.byref(b), C.byref(c)), 'stpwl_select_plan')
+    return {'chunk': a.value, 'lds_bytes': int(b.value), 'launches': int(c.value)}
+
+
+class TPWLPointSelection:
+    """The result of points_by_distance: q, v (P, r), the seed first; index (P_taken, 2): episode and row in the UNstrided record of every
+    taken point; dmin (P_taken,), or (P_taken, 2) = (min dq, min dv) when separate: the smallest distance to the table at the moment the
+    point was taken (+inf for an unconditional first point); complete; stopped_at = (episode, row) of the candidate that met the cap, or
+    None; candidates = the kept rows of the records (those behind stopped_at were not examined); seeded = the points of the seed."""
+
+    def __init__(self, q, v, index, dmin, complete, stopped_at, candidates, seeded=0):
+        self.q, self.v, self.index, self.dmin = q, v, index, dmin
+        self.complete, self.stopped_at, self.candidates, self.seeded = complete, stopped_at, candidates, seeded
+
+    def __repr__(self):
+        tail = '' if self.complete else ', stopped at episode %d row %d' % tuple(self.stopped_at)
+        return 'TPWLPointSelection(%d points (%d seeded) from %d candidates%s)' % (len(self.q), self.seeded, self.candidates, tail)
+
+
+def points_by_distance(X, dist_weights, threshold, separate=False, stride=1, shape=None, q0=None, v0=None, max_points=MAX_POINTS, stream=None):
+    """The linearisation points of records by the reference's distance rule (the module's docstring states it): a TPWLPointSelection.
+    X: (E, T, n_x) or (T, n_x) array, or a _lib.DeviceBuffer with shape = (E, T) or (E, T, n_x) (read in place on `stream`, which is synchronised);
+    dist_weights = {'q': .., 'v': ..}; q0, v0: an optional seed, (P0, r) each.  TPWLSysID(sel.q, sel.v, dist_weights, m, Ts) takes the
+    result unchanged."""
+    who = 'points_by_distance'
+    _check_stride(stride, who)
+    try:
+        w_q, w_v = float(dist_weights['q']), float(dist_weights['v'])
+    except (TypeError, KeyError):
+        raise RuntimeError("%s: dist_weights must be {'q': .., 'v': ..}" % who)
+    threshold = float(threshold)
+    if not (np.isfinite(threshold) and threshold > 0):
+        raise RuntimeError('%s: threshold = %r, need a finite threshold > 0' % (who, threshold))
+    for name, w in (('q', w_q), ('v', w_v)):
+        if not (np.isfinite(w) and w >= 0):
+            raise RuntimeError("%s: the weight dist_weights['%s'] = %r is negative or not finite" % (who, name, w))
+    if w_q == 0 and w_v == 0:
+        raise RuntimeError('%s: both weights are zero' % who)
+    dev = isinstance(X, _lib.DeviceBuffer)
+    if dev:
+        if shape is None or len(tuple(shape)) not in (2, 3):
+            raise RuntimeError('%s: DeviceBuffer records need shape = (E, T) or (E, T, n_x)' % who)
+        E, T = int(shape[0]), int(shape[1])
+        if len(tuple(shape)) == 3:
+            n_x = int(shape[2])
+        else:                                                   # (E, T) as TPWLSysID.add takes it: the buffer's size gives n_x
+            if E < 1 or T < 1 or X.nbytes % (8 * E * T):
+                raise RuntimeError('%s: a DeviceBuffer of %d bytes is not (E, T, n_x) = (%d, %d, ..) doubles; give shape = (E, T, n_x)'
+                                   % (who, X.nbytes, E, T))
+            n_x = X.nbytes // (8 * E * T)
+    else:
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim == 2:
+            X = X[None]
+        if X.ndim != 3:
+            raise RuntimeError('%s: X must have shape (E, T, n_x) or (T, n_x), got %r' % (who, tuple(X.shape)))
+        E, T, n_x = X.shape
+    if n_x < 2 or n_x % 2:
+        raise RuntimeError('%s: n_x = %d, need n_x = 2 r with r >= 1 (x = [v; q])' % (who, n_x))
+    if E < 1 or T < 1:
+        raise RuntimeError('%s: need E >= 1 episodes of T >= 1 rows, got E = %d, T = %d' % (who, E, T))
+    r = n_x // 2
+    if dev and X.nbytes < 8 * E * T * n_x:
+        raise RuntimeError('%s: the DeviceBuffer is smaller than (E, T, n_x) = (%d, %d, %d) doubles' % (who, E, T, n_x))
+    if (q0 is None) != (v0 is None):
+        raise RuntimeError('%s: a seed needs both q0 and v0' % who)
+    if q0 is None:
+        q0, v0 = np.zeros((0, r)), np.zeros((0, r))
+    q0, v0 = np.asarray(q0, dtype=np.float64), np.asarray(v0, dtype=np.float64)
+    q0, v0 = q0.reshape(-1, r) if q0.size == 0 else np.atleast_2d(q0), v0.reshape(-1, r) if v0.size == 0 else np.atleast_2d(v0)
+    if q0.ndim != 2 or q0.shape != v0.shape or q0.shape[1] != r:
+        raise RuntimeError('%s: the seed q0 and v0 must both have shape (P0, r) with r = %d, got %r and %r'
+                           % (who, r, tuple(q0.shape), tuple(v0.shape)))
+    if not (np.all(np.isfinite(q0)) and np.all(np.isfinite(v0))):
+        bad = int(np.flatnonzero(~(np.isfinite(q0).all(axis=1) & np.isfinite(v0).all(axis=1)))[0])
+        raise RuntimeError('%s: seed point %d holds a non-finite entry' % (who, bad))
+    P0 = q0.shape[0]
+    if int(max_points) != max_points or not max(P0, 1) <= max_points <= MAX_POINTS:
+        raise RuntimeError('%s: max_points = %r, need an integer with max(P0, 1) = %d <= max_points <= %d'
+                           % (who, max_points, max(P0, 1), MAX_POINTS))
+    max_points = int(max_points)
+    if not dev:
+        X = _lib.f64(X)
+        ok = np.isfinite(X[:, ::int(stride)]).all(axis=2)
+        if not ok.all():
+            ep, i = np.argwhere(~ok)[0]
+            raise RuntimeError('%s: episode %d, row %d of the records is not finite; nothing was selected' % (who, ep, i * int(stride)))
+    q0, v0 = np.ascontiguousarray(q0), np.ascontiguousarray(v0)
+    nt = max_points - P0
+    count, status = C.c_int(0), C.c_int(0)
+    index, stopped = np.zeros((nt, 2), dtype=np.int64), np.zeros(2, dtype=np.int64)
+    q, v, dmin = np.zeros((nt, r)), np.zeros((nt, r)), np.zeros((nt, 2) if separate else (nt,))
+    i64p = C.POINTER(C.c_int64)
+    args = [E, T, r, int(stride), w_q, w_v, threshold, 1 if separate else 0, P0, _lib.dptr(q0) if P0 else None, _lib.dptr(v0) if P0 else None,
+            max_points, C.byref(count), index.ctypes.data_as(i64p), _lib.dptr(q), _lib.dptr(v), _lib.dptr(dmin), C.byref(status),
+            stopped.ctypes.data_as(i64p)]
+    L = _bind()
+    if dev:
+        _lib.check(L.stpwl_select_points_dev(X.ptr, *args, stream), 'stpwl_select_points_dev')
+    else:
+        _lib.check(L.stpwl_select_points(_lib.dptr(X), *args), 'stpwl_select_points')
+    n = count.value - P0
+    return TPWLPointSelection(np.vstack([q0, q[:n]]), np.vstack([v0, v[:n]]), index[:n].copy(), dmin[:n].copy(), status.value == 0,
+                              None if status.value == 0 else (int(stopped[0]), int(stopped[1])), E * ((T - 1) // int(stride) + 1), P0)
