@@ -13,8 +13,9 @@ number follows the spread of the records.  Points that received too few samples 
 not visit every region.  For the chosen source the points, the points dropped, the one-step error and the tip error are printed; no
 source is promised to beat another.
 
-The one-step error of the fitted model is printed on the fit's records and on held-out episodes, then B loops run on the true plant with
-the fitted planner, and the tip error is printed.
+The one-step error of the fitted model is printed on the fit's records and on held-out episodes, and next to it the k-step output error
+(tpwl.sysid.horizon_error: rms_z at k = 1, N / 2 and N of the planner's horizon, open loop from every kept row of the held-out episodes),
+which is what the planner's rollouts meet; then B loops run on the true plant with the fitted planner, and the tip error is printed.
 
     python examples/diamond_tpwl_sysid_closed_loop.py [--episodes 128] [--steps 500] [--batch 16] [--periods 10] [--ridge 1e-8] [--points plant|kmeans|distance] [--kmeans 0] [--threshold T] [--seed 0]
 
@@ -68,7 +69,7 @@ def main():
     from sofacontrol_amd.scp.closed_loop import ClosedLoopBatch
     from sofacontrol_amd.scp.gusto import GuSTO
     from sofacontrol_amd.scp.models.tpwl import TPWLGuSTO
-    from sofacontrol_amd.tpwl.sysid import fit_tpwl, one_step_error, points_by_distance, points_from_records
+    from sofacontrol_amd.tpwl.sysid import fit_tpwl, horizon_error, one_step_error, points_by_distance, points_from_records
     from sofacontrol_amd.tpwl.tpwl import TPWLATV
     from sofacontrol_amd.utils import HyperRectangle
 
@@ -114,6 +115,15 @@ def main():
     print('one-step residual rms per coordinate at Ts = %.2f: %.3e on the fit\'s records, %.3e on %d held-out episodes (worst sample %.3e)'
           % (STRIDE * DT_SIM, one_step_error(model, X, U, stride=STRIDE), one_step_error(model, Xv, Uv, stride=STRIDE), Xv.shape[0],
              one_step_error(model, Xv, Uv, stride=STRIDE, worst=True)))
+    # the planner never uses the model for one step: its open-loop error over the planner's own horizon, from every kept row of the
+    # held-out episodes (tpwl.sysid.horizon_error: the records are read on the device, the curve over k = 0 .. N comes back)
+    t0 = time.perf_counter()
+    hz = horizon_error(model, Xv, Uv, N, stride=STRIDE)
+    ks = sorted({1, max(1, N // 2), N})
+    print('k-step output error rms_z at Ts = %.2f on the held-out episodes, --points %s: %s; worst window at k = %d: %.3e (episode %d, row %d); '
+          '%d windows, %d diverged, %.1f ms (records from the host)'
+          % (STRIDE * DT_SIM, source, ', '.join('k = %d: %.3e' % (k, hz.rms_z[k]) for k in ks), N, hz.worst_z[N], hz.worst_z_at[N, 0],
+             hz.worst_z_at[N, 1], hz.windows, hz.diverged, 1e3 * (time.perf_counter() - t0)))
 
     # the loop of examples/diamond_closed_loop_batch.py with the fitted planner on the true plant (no feedback gains: u = u_bar)
     gm = TPWLGuSTO(model)

@@ -1130,6 +1130,46 @@ int stpwl_select_points_dev(const double *x_dev, int64_t E, int64_t T, int r, in
                             int separate, int P0, const double *q0, const double *v0, int max_points, int *count, int64_t *index,
                             double *q, double *v, double *dmin, int *status, int64_t *stopped_at, void *stream);
 
+/* TPWL horizon error (csrc/tpwl_horizon.hip): the k-step open-loop prediction error of a nearest-point TPWL model over records, read in
+ * place on the device -- the reference's model check (examples/hardware/diamond.py:20-73 TPWL_rollout) for every window start at once.
+ * THE HORIZON ERROR ("TPWL horizon error", defines it):
+ *   records     x (E x T x n_x), u (E x T x m) and `stride` s >= 1 as for stpwl_fit_add (row i holds the input applied after x_i);
+ *               T' = the rows kept.
+ *   model       the handle's discrete tables (stpwl_create with A_d, B_d, d_d, or stpwl_set_discrete) and its output model, if set.
+ *   windows     starts at the kept rows j0 = 0, w, 2w, .. (`every` = w >= 1) of every episode while j0 + H <= T' - 1, H = `horizon`;
+ *               numbered episode by episode in row order; an episode with T' <= H has none; W = 0 windows is refused.
+ *   prediction  xh_0 = x_{j0}; xh_{k+1} = A_d[i] xh_k + B_d[i] u_{j0+k} + d_d[i], i the nearest point to xh_k, k = 0 .. H - 1, in the
+ *               arithmetic of stpwl_rollout: exactly its X for (x_{j0}, U[j0 : j0 + H]), bit for bit.
+ *   errors      e_k = xh_k - x_{j0+k}; with an output model ez_k = H e_k (z_ref cancels).
+ *   status      of a window: 0 ok; 1 some xh_k is not finite; 2 some record row the window reads (the states j0 .. j0 + H, the inputs
+ *               j0 .. j0 + H - 1) is not finite; 2 wins over 1.  Only status-0 windows enter the sums and the maxima.
+ * Outputs (any but counts may be NULL): sse (2 x (H + 1)): sse_x[k] = sum_w |e_k|^2, then sse_z[k] (zeros without an output model);
+ * worst (2 x (H + 1)): max_w |e_k|_2, then of ez (-1 when no window has status 0); worst_at (2 x (H + 1) x 2 int64): episode and row in
+ * the UNstrided record of the start of the window that attains it, ties to the lowest window number (-1, -1: none); counts (3 int64):
+ * windows W, status-1 windows, status-2 windows; final_norms (2 x W): |e_H|_2, then |ez_H|_2 per window, NaN where status != 0; status
+ * (W); x_pred (W x (H + 1) x n_x): the predictions, refused above the byte cap that stpwl_horizon_plan states (rows behind the one
+ * at which a window left its loop are NaN).  Row k = 0 of every curve is exactly 0.
+ * Bits: no floating-point atomics; the windows are dealt to workgroups in fixed blocks by window number (`block` windows of one episode)
+ * and the blocks' partial sums are joined in block order, so the result is a function of the records and parameters alone: not of
+ * the CU count, a rerun gives the same bits, and device records give the bits of host arrays.  max is exact.
+ * Limits (SRH_EINVAL before any device call, with the offending number): n_x <= 128, m <= 16, 1 <= H <= 1024, stride, every >= 1; a
+ * handle without discrete tables is refused.  stpwl_horizon_error takes host records; the _dev form reads device records in place on
+ * `stream`; both wait for the stream once, at the end.
+ * stpwl_horizon_plan answers on the host (no GPU) for a model of P points, r = n_x / 2, n_u inputs, n_z outputs and velocity weight w_v:
+ * the windows W, the windows of a block and the blocks (= workgroups), mode (0 the L2-fed step: the staged layout plus the accumulators
+ * exceed the 160 KB of LDS; 1 the region's panel staged in LDS; 2 staged with the point table held in registers: w_v = 0, P <= 64,
+ * r <= 32), the dynamic LDS of the launch, the launches (2) and the byte cap of x_pred.  Not offered: weighting-mode models, the
+ * Koopman and SSM analogues, closed-loop prediction, error weights other than H. */
+int stpwl_horizon_plan(int r, int n_u, int P, int n_z, double w_v, int64_t E, int64_t T, int horizon, int stride, int every,
+                       int64_t *windows, int *block, int64_t *blocks, int *mode, int64_t *lds_bytes, int64_t *launches,
+                       int64_t *pred_cap_bytes);
+int stpwl_horizon_error(stpwl_t *h, const double *x, const double *u, int64_t E, int64_t T, int horizon, int stride, int every,
+                        double *sse, double *worst, int64_t *worst_at, int64_t *counts, double *final_norms, int32_t *status,
+                        double *x_pred);
+int stpwl_horizon_error_dev(stpwl_t *h, const double *x_dev, const double *u_dev, int64_t E, int64_t T, int horizon, int stride,
+                            int every, double *sse, double *worst, int64_t *worst_at, int64_t *counts, double *final_norms,
+                            int32_t *status, double *x_pred, void *stream);
+
 /* =====================================================================================================
  * ROMPC baseline. reference: sofacontrol/baselines/rompc/rompc.py:57-89, rompc/observer.py:30-46, rompc_utils.py:52-53
  * `batch` independent loops on one linear reduced model (problem-major arrays everywhere).  One control step is

@@ -38,6 +38,33 @@ THE POINTS.  The fit takes the caller's points.  Two functions choose them from 
   X1 and then X2 with the first result as the seed gives exactly the result of scanning their concatenation.
   points_from_records: the k-means centroids of the kept states (k is the caller's; a centroid is an average, not a visited state).
 
+THE HORIZON ERROR.  horizon_error judges a model the way the planners use it: rolled out open loop over H steps from every window start
+of held-out records, read in place on the device (csrc/tpwl_horizon.hip; C ABI: stpwl_horizon_error; the reference's model check,
+examples/hardware/diamond.py TPWL_rollout, for every window at once).
+  Records as the fit defines them (X (E, T, n_x), U (E, T, m), row i holds the input applied after x_i; `stride` keeps rows 0, s, 2s, ..,
+  T' kept rows; arrays, or DeviceBuffers with shape = (E, T)).
+  Model: a nearest-point TPWLATV and a step dt, defaulting to model.fit_Ts; the tables are those of model.handle_for(dt) in the model's
+  own discretisation method.  A weighting-mode model is refused by name.
+  Windows: starts at the kept rows j0 = 0, w, 2w, .. (`every` = w >= 1) of every episode while j0 + H <= T' - 1, numbered episode by
+  episode in row order; an episode with T' <= H has none; W = 0 raises.
+  Prediction of a window: xh_0 = x_{j0}; xh_{k+1} = the step rule of csrc/tpwl_dev.h applied to (xh_k, u_{j0+k}) with the point search of
+  the same file, k = 0 .. H - 1: exactly model.rollout(x_{j0}, U[j0:j0+H], dt), bit for bit.
+  Errors: e_k = xh_k - x_{j0+k}; with an output model ez_k = H e_k (z_ref cancels).
+  Window status: 0 ok; 1 some xh_k is not finite; 2 some record row the window reads (a state j0 .. j0 + H or an input j0 .. j0 + H - 1)
+  is not finite; status 2 wins over 1.  Only status-0 windows enter the sums.
+  Results for k = 0 .. H: sse_x[k] = sum_w |e_k|^2 and sse_z[k]; rms_x[k] = sqrt(sse_x[k] / (W_ok n_x)), rms_z with n_z; worst_x[k] =
+  max_w |e_k|_2 with worst_x_at[k] = (episode, unstrided row) of that window's start, ties to the lowest window number, the same for z;
+  the counts windows, diverged (status 1) and bad_rows (status 2).  Row 0 of every curve is exactly 0.
+  On request: per_window=True gives final_x (W,), final_z (W,) (the norms at k = H, NaN where status != 0) and status (W,);
+  predictions=True gives x_pred (W, H + 1, n_x), refused above the byte cap that horizon_plan states (tests and small studies; the rows
+  behind the one at which a window left its loop are NaN).
+  Bits: no floating-point atomics; the windows are dealt to workgroups in fixed blocks by window number and the blocks' partial sums are
+  joined in block order, so the result is a function of the records and parameters alone: not of the CU count, a rerun gives the same
+  bits, and device records give the bits of host arrays.  max is exact; its tie rule is the lowest window number.
+  Limits: n_x <= 128, m <= 16, H <= 1024, each refused on the host with the offending number.
+  Not offered here: the Koopman and SSM analogues, weighting-mode models, closed-loop (feedback) prediction, error weights other than the
+  model's H.  one_step_error is unchanged.
+
 NOT OFFERED: weighting-mode fits; sample weights; the reference's 'dynamics' rule of selection (it needs the simulator's Jacobians at the
 candidate); full-order records (project them first: POD.compute_RO_state)."""
 import ctypes as C
@@ -72,6 +99,11 @@ def _bind():
     L.stpwl_select_plan.argtypes = [C.c_int, i64, ip, i64p, i64p]
     L.stpwl_select_points.argtypes = [dp] + sel
     L.stpwl_select_points_dev.argtypes = [vp] + sel + [vp]
+    hor = [i64, i64, C.c_int, C.c_int, C.c_int, dp, dp, i64p, i64p, dp, i32p, dp]
+    L.stpwl_horizon_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, dbl, i64, i64, C.c_int, C.c_int, C.c_int, i64p, ip, i64p, ip, i64p, i64p,
+                                     i64p]
+    L.stpwl_horizon_error.argtypes = [vp, dp, dp] + hor
+    L.stpwl_horizon_error_dev.argtypes = [vp, vp, vp] + hor + [vp]
     _BOUND = True
     return L
 
@@ -457,3 +489,111 @@ def points_by_distance(X, dist_weights, threshold, separate=False, stride=1, sha
     n = count.value - P0
     return TPWLPointSelection(np.vstack([q0, q[:n]]), np.vstack([v0, v[:n]]), index[:n].copy(), dmin[:n].copy(), status.value == 0,
                               None if status.value == 0 else (int(stopped[0]), int(stopped[1])), E * ((T - 1) // int(stride) + 1), P0)
+
+
+HORIZON_MODES = ('l2', 'staged', 'staged_held')
+
+
+def _horizon_model(model, who):
+    """(P, r, m, n_z, w_v) of a nearest-point model; a weighting-mode model is refused by name."""
+    method = getattr(model, 'tpwl_method', None)
+    if method != 'nn':
+        raise RuntimeError("%s: tpwl_method = %r: only nearest-point ('nn') models are offered, not weighting-mode models" % (who, method))
+    n_x, m = int(model.get_state_dim()), int(model.get_input_dim())
+    if n_x < 2 or n_x % 2:
+        raise RuntimeError('%s: n_x = %d, need n_x = 2 r with r >= 1 (x = [v; q])' % (who, n_x))
+    n_z = int(model.get_output_dim()) if getattr(model, 'H', None) is not None else 0
+    return int(model.num_points), n_x // 2, m, n_z, float(model.dist_weights['v'])
+
+
+def _horizon_ints(horizon, stride, every, who):
+    _check_stride(stride, who)
+    for name, val in (('horizon', horizon), ('every', every)):
+        if int(val) != val or val < 1:
+            raise RuntimeError('%s: %s = %r, need an integer %s >= 1' % (who, name, val, name))
+    return int(horizon), int(stride), int(every)
+
+
+def horizon_plan(model, E, T, horizon, stride=1, every=1):
+    """stpwl_horizon_plan, on the host (no GPU), for horizon_error(model, records of E episodes of T rows, horizon, stride=, every=):
+    {'windows', 'block' (windows of a workgroup), 'blocks', 'mode' ('l2' | 'staged' | 'staged_held'), 'lds_bytes', 'launches',
+    'pred_cap_bytes' (the largest x_pred that predictions=True may ask for)}; raises when the call would be refused (n_x > 128, H > 1024,
+    W = 0 windows, ..)."""
+    who = 'horizon_plan'
+    P, r, m, n_z, w_v = _horizon_model(model, who)
+    H, stride, every = _horizon_ints(horizon, stride, every, who)
+    w, bl, nb, mode, lds, ln, cap = C.c_int64(0), C.c_int(0), C.c_int64(0), C.c_int(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    _lib.check(_bind().stpwl_horizon_plan(r, m, P, n_z, w_v, int(E), int(T), H, stride, every, C.byref(w), C.byref(bl), C.byref(nb), C.byref(mode),
+                                          C.byref(lds), C.byref(ln), C.byref(cap)), 'stpwl_horizon_plan')
+    return {'windows': int(w.value), 'block': bl.value, 'blocks': int(nb.value), 'mode': HORIZON_MODES[mode.value], 'lds_bytes': int(lds.value),
+            'launches': int(ln.value), 'pred_cap_bytes': int(cap.value)}
+
+
+class TPWLHorizonError:
+    """The result of horizon_error (the module's docstring defines every field): horizon, dt, windows, diverged, bad_rows; for
+    k = 0 .. H: sse_x, rms_x, worst_x (H + 1,), worst_x_at (H + 1, 2) = (episode, unstrided row) of the worst window's start, and the same
+    with z (None without an output model); on request final_x, final_z, status (W,) and x_pred (W, H + 1, n_x)."""
+
+    def __init__(self, horizon, dt, windows, diverged, bad_rows, sse_x, rms_x, worst_x, worst_x_at, sse_z=None, rms_z=None, worst_z=None,
+                 worst_z_at=None, final_x=None, final_z=None, status=None, x_pred=None):
+        self.horizon, self.dt, self.windows, self.diverged, self.bad_rows = horizon, dt, windows, diverged, bad_rows
+        self.sse_x, self.rms_x, self.worst_x, self.worst_x_at = sse_x, rms_x, worst_x, worst_x_at
+        self.sse_z, self.rms_z, self.worst_z, self.worst_z_at = sse_z, rms_z, worst_z, worst_z_at
+        self.final_x, self.final_z, self.status, self.x_pred = final_x, final_z, status, x_pred
+
+    @property
+    def windows_ok(self):
+        return self.windows - self.diverged - self.bad_rows
+
+    def __repr__(self):
+        tail = '' if self.rms_z is None else ', rms_z[H]=%g' % self.rms_z[-1]
+        return 'TPWLHorizonError(H=%d, %d windows (%d diverged, %d with bad rows), rms_x[H]=%g%s)' % (
+            self.horizon, self.windows, self.diverged, self.bad_rows, self.rms_x[-1], tail)
+
+
+def horizon_error(model, X, U, horizon, dt=None, stride=1, every=1, shape=None, per_window=False, predictions=False):
+    """The k-step open-loop prediction error of a nearest-point TPWL model over records, k = 0 .. horizon, from every window start (the
+    module's docstring states the definition): a TPWLHorizonError.  X (E, T, n_x) or (T, n_x) and U alike, numpy arrays or
+    _lib.DeviceBuffers with shape = (E, T) (read in place); dt defaults to model.fit_Ts."""
+    who = 'horizon_error'
+    P, r, m, n_z, w_v = _horizon_model(model, who)
+    H, stride, every = _horizon_ints(horizon, stride, every, who)
+    n_x = 2 * r
+    X, U, E, T, dev = _records(X, U, n_x, m, shape, who)
+    plan = horizon_plan(model, E, T, H, stride, every)          # every refusal of the shapes, on the host
+    W = plan['windows']
+    if predictions and 8 * W * (H + 1) * n_x > plan['pred_cap_bytes']:
+        raise RuntimeError('%s: predictions of %d windows x %d rows x %d need %d bytes, above the cap of %d bytes'
+                           % (who, W, H + 1, n_x, 8 * W * (H + 1) * n_x, plan['pred_cap_bytes']))
+    dt = getattr(model, 'fit_Ts', None) if dt is None else dt
+    if dt is None:
+        raise RuntimeError('%s: the model carries no fit_Ts; give dt' % who)
+    h = model.handle_for(float(dt))
+    sse, worst = np.zeros((2, H + 1)), np.zeros((2, H + 1))
+    at, counts = np.zeros((2, H + 1, 2), dtype=np.int64), np.zeros(3, dtype=np.int64)
+    fin = np.zeros((2, W)) if per_window else None
+    status = np.zeros(W, dtype=np.int32) if per_window else None
+    pred = np.zeros((W, H + 1, n_x)) if predictions else None
+    i64p = C.POINTER(C.c_int64)
+    args = [E, T, H, stride, every, _lib.dptr(sse), _lib.dptr(worst), at.ctypes.data_as(i64p), counts.ctypes.data_as(i64p),
+            _lib.dptr(fin) if per_window else None, _lib.iptr(status) if per_window else None, _lib.dptr(pred) if predictions else None]
+    L = _bind()
+    if dev:
+        _lib.check(L.stpwl_horizon_error_dev(h, X.ptr, U.ptr, *args, None), 'stpwl_horizon_error_dev')
+    else:
+        _lib.check(L.stpwl_horizon_error(h, _lib.dptr(X), _lib.dptr(U), *args), 'stpwl_horizon_error')
+    ok = int(counts[0] - counts[1] - counts[2])
+
+    def rms(s, dim):
+        return np.sqrt(s / (ok * dim)) if ok > 0 else np.full(H + 1, np.nan)
+
+    def none(a):                                                # no status-0 window: no maximum
+        return np.where(a < 0, np.nan, a)
+
+    out = TPWLHorizonError(H, float(dt), int(counts[0]), int(counts[1]), int(counts[2]), sse[0].copy(), rms(sse[0], n_x), none(worst[0]), at[0].copy())
+    if n_z > 0:
+        out.sse_z, out.rms_z, out.worst_z, out.worst_z_at = sse[1].copy(), rms(sse[1], n_z), none(worst[1]), at[1].copy()
+    if per_window:
+        out.final_x, out.final_z, out.status = fin[0].copy(), (fin[1].copy() if n_z > 0 else None), status
+    out.x_pred = pred
+    return out
