@@ -140,6 +140,12 @@ def main():
           % (E, S + 1, fit.samples, fit.ridge, 1e3 * wall, one_step_error(model, Y, U, y_ref=y_eq), one_step_error(model, Yv, Uv, y_ref=y_eq),
              Yv.shape[0], np.abs(Y - y_eq).max()))
     planner = SSMDynamics(y_eq.copy(), discrete=False, discr_method='be', model=model, params=params)
+    # what the one-step figure does not show: the open-loop output error over the planner's own horizon (N_SSM stages of DT_SSM), started
+    # from the observer map as the planner starts, from every kept row of the held-out episodes (SSM.sysid.horizon_error)
+    from sofacontrol_amd.SSM.sysid import horizon_error
+    hz = horizon_error(planner, Yv, Uv, N_SSM, dt=DT_SSM, stride=int(round(DT_SSM / DT_SIM)))
+    print('k-step output error rms_z of the planner at dt = %.2f on the held-out episodes: %s; %d windows, %d diverged'
+          % (DT_SSM, ', '.join('k = %d: %.3e' % (k, hz.rms_z[k]) for k in sorted({0, 1, max(1, N_SSM // 2), N_SSM})), hz.windows, hz.diverged))
 
     t, fig8 = target_table()
     phase = rng.uniform(0.0, PERIOD / 2, B)

@@ -105,6 +105,13 @@ def main():
              one_step_error(model, Yv, Uv, y_ref=z_eq), Yv.shape[0], np.abs(Y - z_eq).max()))
 
     fitted = SSMDynamics(z_eq.copy(), discrete=False, discr_method='be', model=model, params=params)
+    # the planner never uses the model for one step: its open-loop output error over the planner's own horizon, started from the observer
+    # map as the planner starts, from every kept row of the held-out episodes (SSM.sysid.horizon_error: the records are read on the device)
+    from sofacontrol_amd.SSM.sysid import horizon_error
+    for name, mdl in (('fitted', fitted), ('shipped', plant)):
+        hz = horizon_error(mdl, Yv, Uv, N, dt=DT)
+        print('%-7s model: k-step output error rms_z on the held-out episodes: %s; %d windows, %d diverged'
+              % (name, ', '.join('k = %d: %.3e' % (k, hz.rms_z[k]) for k in sorted({0, 1, max(1, N // 2), N})), hz.windows, hz.diverged))
     t = np.linspace(0.0, 4.0, 201)                              # a slow circle of the first two outputs around the equilibrium
     zt = np.zeros((201, n)); zt[:, 0] = 5.0 * np.sin(0.5 * np.pi * t); zt[:, 1] = 5.0 * (1.0 - np.cos(0.5 * np.pi * t))
     phase = rng.uniform(0.0, 2.0, B)

@@ -1159,7 +1159,7 @@ int stpwl_select_points_dev(const double *x_dev, int64_t E, int64_t T, int r, in
  * the windows W, the windows of a block and the blocks (= workgroups), mode (0 the L2-fed step: the staged layout plus the accumulators
  * exceed the 160 KB of LDS; 1 the region's panel staged in LDS; 2 staged with the point table held in registers: w_v = 0, P <= 64,
  * r <= 32), the dynamic LDS of the launch, the launches (2) and the byte cap of x_pred.  Not offered: weighting-mode models, the
- * Koopman and SSM analogues, closed-loop prediction, error weights other than H. */
+ * Koopman analogue (the SSM analogue is sssm_horizon_error), closed-loop prediction, error weights other than H. */
 int stpwl_horizon_plan(int r, int n_u, int P, int n_z, double w_v, int64_t E, int64_t T, int horizon, int stride, int every,
                        int64_t *windows, int *block, int64_t *blocks, int *mode, int64_t *lds_bytes, int64_t *launches,
                        int64_t *pred_cap_bytes);
@@ -1169,6 +1169,55 @@ int stpwl_horizon_error(stpwl_t *h, const double *x, const double *u, int64_t E,
 int stpwl_horizon_error_dev(stpwl_t *h, const double *x_dev, const double *u_dev, int64_t E, int64_t T, int horizon, int stride,
                             int every, double *sse, double *worst, int64_t *worst_at, int64_t *counts, double *final_norms,
                             int32_t *status, double *x_pred, void *stream);
+
+/* SSM horizon error (csrc/ssm_horizon.hip): the k-step open-loop prediction error of an SSM model over records, read in place on the
+ * device and started from the observer map exactly as the planners start -- the reference's model check
+ * (examples/hardware/diamond_SSM.py:83-140 module_test) for every window start at once.
+ * THE SSM HORIZON ERROR ("SSM horizon error", defines it):
+ *   records     y (E x T x n_y) raw measurements as sssm_fit_add takes them, u (E x T x m), row i holds the input applied after y_i;
+ *               `stride` s >= 1 keeps rows 0, s, 2s, ..; T' = the rows kept.
+ *   model       the handle, a mode (SSSM_FE, SSSM_BE, SSSM_BIL at dt, or SSSM_DISCRETE_MAP), and the handle's z_ref.  Required:
+ *               n_x == n_o == n_y, as sssm_rollout with outputs and the loops require.
+ *   observed    xo_j = W_map(y_j - z_ref) = V phi_s(y_j - z_ref) for every kept row (the reference's SSMObserver).
+ *   windows     starts at the kept rows j0 = 0, w, 2w, .. (`every` = w >= 1) of every episode while j0 + H <= T' - 1, H = `horizon`;
+ *               numbered episode by episode in row order; an episode with T' <= H has none; W = 0 windows is refused (the window
+ *               rule of stpwl_horizon_plan).
+ *   prediction  xh_0 = xo_{j0}, or x_start (n_x) for every window when it is not NULL; xh_{k+1} = A_d xh_k + B_d u_{j0+k} + d_d with
+ *               (A_d, B_d, d_d) linearised at (xh_k, u_{j0+k}) and discretised by the mode at dt; zh_k = C_map(xh_k) + z_ref.  The
+ *               arithmetic is the plant step of sgusto_ssm_loop_advance: x_pred and z_pred are its X and Z + z_ref records bit for bit
+ *               (not the bits of sssm_rollout, whose kernel sums in another order).
+ *   errors      ez_k = zh_k - y_{j0+k} in the output space (NOT zero at k = 0: C_map(W_map(.)) is not the identity); ex_k = xh_k -
+ *               xo_{j0+k} in the reduced space (exactly 0 at k = 0 without x_start).
+ *   status      of a window: 0 ok; 1 some xh_k or zh_k is not finite; 2 some record row the window reads (y at j0 .. j0 + H, u at
+ *               j0 .. j0 + H - 1) is not finite; 2 wins over 1.  Only status-0 windows enter the sums and the maxima.
+ * Outputs (any but counts may be NULL): sse (2 x (H + 1)): sums of |ex_k|^2, then of |ez_k|^2; worst (2 x (H + 1)): the largest norm
+ * (-1 when no window has status 0); worst_at (2 x (H + 1) x 2 int64): episode and row in the UNstrided record of the start of the window
+ * that attains it, ties to the lowest window number (-1, -1: none); counts (3 int64): windows W, status-1 windows, status-2 windows;
+ * final_norms (2 x W): |ex_H|_2, then |ez_H|_2 per window, NaN where status != 0; status (W); x_pred (W x (H + 1) x n_x), z_pred
+ * (W x (H + 1) x n_o), x_obs (E x T' x n_x): the three together are refused above the byte cap that sssm_horizon_plan states.  A
+ * window that left its loop at step k (the first xh_k or zh_k that is not finite) keeps its rows 0 .. k, the rows behind are NaN; a
+ * status-2 window is not rolled out and all its rows are NaN.
+ * Bits: no floating-point atomics; the windows are dealt to workgroups in fixed blocks by window number (`block` windows of one episode)
+ * and the blocks' partial sums are joined in block order, so the result is a function of the records and parameters alone: not of
+ * the CU count, a rerun gives the same bits, and device records give the bits of host arrays.  max is exact.
+ * Limits (SRH_EINVAL before any device call, with the offending number): n_x <= 32, m <= 16, 1 <= H <= 1024, stride, every >= 1; the
+ * continuous mode; the discrete map on a handle without rd_coeff; m > (n_x | 1) in be / bil (the B_d scratch panel of ssm::discretize); n_x != n_o or n_y != n_o; a launch above 160 KiB of LDS (with the
+ * byte count).  sssm_horizon_error takes host records; the _dev form reads device records in place on `stream`; both wait for the
+ * stream once, at the end.
+ * sssm_horizon_plan answers on the host (no GPU) for a model of n_x states, n_u inputs, n_o outputs and the two orders, records of
+ * n_y columns, a mode and whether the model has a discrete map: the windows W, the windows of a block and the blocks (= workgroups of
+ * the window kernel), its dynamic LDS, the launches (3: observe, windows, join) and the byte cap of x_pred + z_pred + x_obs.
+ * Not offered: the Koopman analogue, models with n_x != n_o, closed-loop prediction, error weights. */
+int sssm_horizon_plan(int n_x, int n_u, int n_o, int n_y, int rom_order, int ssm_order, int mode, int has_discrete, int64_t E, int64_t T,
+                      int horizon, int stride, int every, int64_t *windows, int *block, int64_t *blocks, int64_t *lds_bytes,
+                      int64_t *launches, int64_t *pred_cap_bytes);
+int sssm_horizon_error(sssm_t *h, int mode, double dt, const double *y, const double *u, int n_y, int64_t E, int64_t T, int horizon,
+                       int stride, int every, const double *x_start, double *sse, double *worst, int64_t *worst_at, int64_t *counts,
+                       double *final_norms, int32_t *status, double *x_pred, double *z_pred, double *x_obs);
+int sssm_horizon_error_dev(sssm_t *h, int mode, double dt, const double *y_dev, const double *u_dev, int n_y, int64_t E, int64_t T,
+                           int horizon, int stride, int every, const double *x_start, double *sse, double *worst, int64_t *worst_at,
+                           int64_t *counts, double *final_norms, int32_t *status, double *x_pred, double *z_pred, double *x_obs,
+                           void *stream);
 
 /* =====================================================================================================
  * ROMPC baseline. reference: sofacontrol/baselines/rompc/rompc.py:57-89, rompc/observer.py:30-46, rompc_utils.py:52-53

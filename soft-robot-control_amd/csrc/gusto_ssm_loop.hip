@@ -12,6 +12,7 @@
 // tpwl_dev.h, measure_row and plan_at of gusto_loop_prep.h and the estimate (ssm_loop_estimate, stated once for both kernels) together;
 // the handle is the same sgusto_ssm_loop with a plant kind (sgusto_ssm_loop_create_tpwl).
 #include "ssm_host.h"
+#include "ssm_step_dev.h"
 #include "tpwl_host.h"
 #include "gusto_loop_host.h"
 
@@ -172,10 +173,7 @@ __global__ __launch_bounds__(SL_NT) void ssm_loop_advance_kernel(SsmDev S, SsmOb
         ssm::jacobians_l(S, T, dm, xs, us, w, Al, n, Bl, dl);
         ssm::discretize(S, a.mode, a.dt_sim, w, Al, n, Bl, dl);
         for (int i = tid; i < n; i += nt) {
-            double ax = 0.0, bu = 0.0;
-            for (int j = 0; j < n; ++j) ax = fma(Al[i * n + j], xs[j], ax);
-            for (int j = 0; j < m; ++j) bu = fma(Bl[i * m + j], us[j], bu);
-            double v = ax + bu + dl[i];
+            double v = ssm_step_affine_row(Al, Bl, dl, xs, us, n, m, i);               // (ssm_step_dev.h: the SSM horizon error calls it too)
             if (Wd != nullptr) v += Wd[((size_t)(a.w_step0 + s) * a.B + b) * n + i];
             xn[i] = v;
         }

@@ -1,0 +1,1 @@
+from .sysid import SSMHorizonError, horizon_error, horizon_plan  # noqa: F401

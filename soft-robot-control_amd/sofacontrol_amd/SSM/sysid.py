@@ -23,6 +23,35 @@ identification") defines the fit, and this is its summary.
   Records split over several `add` calls at episode boundaries give the bits of one call: a workgroup sums a fixed run of chunks of
   one episode, and the runs join the sums in order.
 
+THE SSM HORIZON ERROR.  horizon_error judges a model the way the planners use it: rolled out open loop over H steps from every window
+start of held-out records, started from the observer map as the planner starts, read in place on the device (csrc/ssm_horizon.hip;
+C ABI: sssm_horizon_error; the reference's model check, examples/hardware/diamond_SSM.py module_test, for every window at once).
+INTEGRATION.md ("SSM horizon error") defines it, and this is its summary.
+  Records: y (E, T, n_y) raw measurements as SSMSysID.add takes them, u (E, T, m), row i holds the input applied after y_i; `stride`
+  keeps rows 0, s, 2s, .. (T' kept rows); arrays, or DeviceBuffers with shape = (E, T), read in place.
+  Model: an SSMDynamics: its handle, its mode (model._mode(): discrete map, fe, be or bil), dt (default float(model.Ts)) and its
+  z_ref.  Required: n_x == n_o == n_y.
+  Observed states: xo_j = W_map(y_j - z_ref) for every kept row (the reference's SSMObserver).
+  Windows: starts at the kept rows j0 = 0, w, 2w, .. (`every` = w >= 1) of every episode while j0 + H <= T' - 1, numbered episode by
+  episode in row order; an episode with T' <= H has none; W = 0 raises.
+  Prediction: xh_0 = xo_{j0}, or x_start (n_x,) for every window (p0 = zeros of module_test); xh_{k+1} = A_d xh_k + B_d u_{j0+k} + d_d,
+  linearised at (xh_k, u_{j0+k}) and discretised by the mode at dt; zh_k = C_map(xh_k) + z_ref.  The arithmetic is the SSM closed
+  loop's plant step: the X and Z + z_ref records of sgusto_ssm_loop_advance bit for bit (not the bits of SSM.rollout).
+  Errors: ez_k = zh_k - y_{j0+k} (NOT zero at k = 0: C_map(W_map(.)) is not the identity); ex_k = xh_k - xo_{j0+k} (exactly 0 at k = 0
+  without x_start).
+  Window status: 0 ok; 1 some xh_k or zh_k is not finite; 2 some record row the window reads (y at j0 .. j0 + H, u at j0 .. j0 + H - 1) is
+  not finite; 2 wins over 1.  Only status-0 windows enter the sums and the maxima.
+  Results for k = 0 .. H: sse_x, sse_z; rms_x = sqrt(sse_x / (ok n_x)), rms_z = sqrt(sse_z / (ok n_o)) (NaN when no window is ok);
+  worst_x, worst_z with worst_*_at = (episode, unstrided row) of that window's start, ties to the lowest window number; the counts
+  windows, diverged (status 1) and bad_rows (status 2).
+  On request: per_window=True gives final_x, final_z (W,) (NaN where status != 0) and status (W,); predictions=True gives x_pred
+  (W, H + 1, n_x), z_pred (W, H + 1, n_o) and x_obs (E, T', n_x), together refused above the byte cap that horizon_plan states.  A window
+  that left its loop at step k keeps rows 0 .. k, the rows behind are NaN; a status-2 window is not rolled out: all its rows are NaN.
+  Limits, each refused on the host with the offending number: n_x <= 32, m <= 16, 1 <= H <= 1024, stride, every >= 1, the continuous
+  mode, the discrete map without rd_coeff, m > (n_x | 1) in be / bil, n_x != n_o or n_y != n_o, a launch above 160 KiB of LDS.
+  Not offered: the Koopman analogue, models with n_x != n_o, closed-loop (feedback) prediction, error weights.  one_step_error is
+  unchanged.
+
 NOT OFFERED: delay-embedded observations, a polynomial chart, separate autonomous and forced record sets, sample weights, fitting
 inside a running loop."""
 import ctypes as C
@@ -53,6 +82,11 @@ def _bind():
     L.sssm_fit_solve.argtypes = [vp, C.c_double, dp, dp, dp, dp, dp, _lib.c_int32_p]
     L.sssm_num_monomials.argtypes = [C.c_int, C.c_int]
     L.sssm_exponents.argtypes = [C.c_int, C.c_int, _lib.c_int32_p]
+    i64p, i32p, dbl = C.POINTER(i64), _lib.c_int32_p, C.c_double
+    hor = [C.c_int, i64, i64, C.c_int, C.c_int, C.c_int, dp, dp, dp, i64p, i64p, dp, i32p, dp, dp, dp]
+    L.sssm_horizon_plan.argtypes = [C.c_int] * 8 + [i64, i64, C.c_int, C.c_int, C.c_int, i64p, ip, i64p, i64p, i64p, i64p]
+    L.sssm_horizon_error.argtypes = [vp, C.c_int, dbl, dp, dp] + hor
+    L.sssm_horizon_error_dev.argtypes = [vp, C.c_int, dbl, vp, vp] + hor + [vp]
     _BOUND = True
     return L
 
@@ -346,3 +380,115 @@ def one_step_error(model, Y, U, y_ref=None, stride=1, worst=False):
     if cnt == 0:
         raise RuntimeError('one_step_error: the records hold no sample')
     return big if worst else float(np.sqrt(tot / cnt))
+
+
+def _horizon_model(model, who):
+    """(n_x, m, n_o, ROM_order, SSM_order, mode, has_discrete) of an SSM model; the mode is model._mode() (the continuous mode does not
+    occur there: an unknown discr_method raises by name)."""
+    for name in ('state_dim', 'input_dim', 'output_dim', 'ROM_order', 'SSM_order', '_mode'):
+        if not hasattr(model, name):
+            raise RuntimeError('%s: the model must be an SSMDynamics (it has no %s)' % (who, name))
+    has_d = getattr(model, 'rd_coeff', None) is not None and getattr(model, 'Bd_r', None) is not None
+    return (int(model.state_dim), int(model.input_dim), int(model.output_dim), int(model.ROM_order), int(model.SSM_order), int(model._mode()),
+            bool(has_d))
+
+
+def _horizon_ints(horizon, stride, every, who):
+    _check_stride(stride, who)
+    for name, val in (('horizon', horizon), ('every', every)):
+        if int(val) != val or val < 1:
+            raise RuntimeError('%s: %s = %r, need an integer %s >= 1' % (who, name, val, name))
+    return int(horizon), int(stride), int(every)
+
+
+def horizon_plan(model, E, T, horizon, stride=1, every=1, n_y=None):
+    """sssm_horizon_plan, on the host (no GPU), for horizon_error(model, records of E episodes of T rows of n_y columns (default: the
+    model's n_o), horizon, stride=, every=): {'windows', 'block' (windows of a workgroup), 'blocks', 'lds_bytes', 'launches',
+    'pred_cap_bytes' (the most that x_pred + z_pred + x_obs of predictions=True may need)}; raises when the call would be refused."""
+    who = 'horizon_plan'
+    n_x, m, n_o, ro, so, mode, has_d = _horizon_model(model, who)
+    H, stride, every = _horizon_ints(horizon, stride, every, who)
+    w, bl, nb, lds, ln, cap = C.c_int64(0), C.c_int(0), C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    _lib.check(_bind().sssm_horizon_plan(n_x, m, n_o, n_o if n_y is None else int(n_y), ro, so, mode, int(has_d), int(E), int(T), H, stride, every,
+                                         C.byref(w), C.byref(bl), C.byref(nb), C.byref(lds), C.byref(ln), C.byref(cap)), 'sssm_horizon_plan')
+    return {'windows': int(w.value), 'block': bl.value, 'blocks': int(nb.value), 'lds_bytes': int(lds.value), 'launches': int(ln.value),
+            'pred_cap_bytes': int(cap.value)}
+
+
+class SSMHorizonError:
+    """The result of horizon_error (the module's docstring defines every field): horizon, dt, windows, diverged, bad_rows; for
+    k = 0 .. H: sse_x, rms_x, worst_x (H + 1,), worst_x_at (H + 1, 2) = (episode, unstrided row) of the worst window's start, and the same
+    with z; on request final_x, final_z, status (W,), x_pred (W, H + 1, n_x), z_pred (W, H + 1, n_o) and x_obs (E, T', n_x)."""
+
+    def __init__(self, horizon, dt, windows, diverged, bad_rows, sse_x, rms_x, worst_x, worst_x_at, sse_z, rms_z, worst_z, worst_z_at,
+                 final_x=None, final_z=None, status=None, x_pred=None, z_pred=None, x_obs=None):
+        self.horizon, self.dt, self.windows, self.diverged, self.bad_rows = horizon, dt, windows, diverged, bad_rows
+        self.sse_x, self.rms_x, self.worst_x, self.worst_x_at = sse_x, rms_x, worst_x, worst_x_at
+        self.sse_z, self.rms_z, self.worst_z, self.worst_z_at = sse_z, rms_z, worst_z, worst_z_at
+        self.final_x, self.final_z, self.status = final_x, final_z, status
+        self.x_pred, self.z_pred, self.x_obs = x_pred, z_pred, x_obs
+
+    @property
+    def windows_ok(self):
+        return self.windows - self.diverged - self.bad_rows
+
+    def __repr__(self):
+        return 'SSMHorizonError(H=%d, %d windows (%d diverged, %d with bad rows), rms_x[H]=%g, rms_z[0]=%g, rms_z[H]=%g)' % (
+            self.horizon, self.windows, self.diverged, self.bad_rows, self.rms_x[-1], self.rms_z[0], self.rms_z[-1])
+
+
+def horizon_error(model, Y, U, horizon, dt=None, stride=1, every=1, shape=None, x_start=None, per_window=False, predictions=False):
+    """The k-step open-loop prediction error of an SSM model over records, k = 0 .. horizon, from every window start (the module's
+    docstring states the definition): an SSMHorizonError.  Y (E, T, n_y) or (T, n_y) and U alike, numpy arrays or _lib.DeviceBuffers
+    with shape = (E, T) (read in place); dt defaults to float(model.Ts); x_start (n_x,) starts every window there instead of at the
+    observed state."""
+    who = 'horizon_error'
+    n_x, m, n_o, ro, so, mode, has_d = _horizon_model(model, who)
+    H, stride, every = _horizon_ints(horizon, stride, every, who)
+    n_y = n_o if isinstance(Y, _lib.DeviceBuffer) else int(np.shape(Y)[-1])
+    if n_x != n_o or n_y != n_o:                                # (before the records are shaped by n_y)
+        horizon_plan(model, 1, H + 1, H, n_y=n_y)
+    Y, U, E, T, dev = _records(Y, U, n_y, m, shape, who)
+    plan = horizon_plan(model, E, T, H, stride, every, n_y=n_y)  # every refusal of the shapes, on the host
+    W, Tk = plan['windows'], (T - 1) // stride + 1
+    need = 8 * (W * (H + 1) * (n_x + n_o) + E * Tk * n_x)
+    if predictions and need > plan['pred_cap_bytes']:
+        raise RuntimeError('%s: x_pred, z_pred and x_obs of %d windows x %d rows and %d kept rows need %d bytes, above the cap of %d bytes'
+                           % (who, W, H + 1, E * Tk, need, plan['pred_cap_bytes']))
+    dt = float(model.Ts) if dt is None else float(dt)
+    if not (dt > 0.0 and np.isfinite(dt)):
+        raise RuntimeError('%s: dt = %r, need a finite dt > 0' % (who, dt))
+    if x_start is not None:
+        x_start = _lib.f64(np.ravel(np.asarray(x_start, dtype=np.float64)))
+        if x_start.shape != (n_x,):
+            raise RuntimeError('%s: x_start must hold n_x = %d entries, got %d' % (who, n_x, x_start.size))
+    sse, worst = np.zeros((2, H + 1)), np.zeros((2, H + 1))
+    at, counts = np.zeros((2, H + 1, 2), dtype=np.int64), np.zeros(3, dtype=np.int64)
+    fin = np.zeros((2, W)) if per_window else None
+    status = np.zeros(W, dtype=np.int32) if per_window else None
+    xp = np.zeros((W, H + 1, n_x)) if predictions else None
+    zp = np.zeros((W, H + 1, n_o)) if predictions else None
+    xo = np.zeros((E, Tk, n_x)) if predictions else None
+    i64p = C.POINTER(C.c_int64)
+    opt = lambda a: None if a is None else _lib.dptr(a)
+    args = [n_y, E, T, H, stride, every, opt(x_start), _lib.dptr(sse), _lib.dptr(worst), at.ctypes.data_as(i64p), counts.ctypes.data_as(i64p),
+            opt(fin), _lib.iptr(status) if per_window else None, opt(xp), opt(zp), opt(xo)]
+    L = _bind()
+    if dev:
+        _lib.check(L.sssm_horizon_error_dev(model.handle, mode, dt, Y.ptr, U.ptr, *args, None), 'sssm_horizon_error_dev')
+    else:
+        _lib.check(L.sssm_horizon_error(model.handle, mode, dt, _lib.dptr(Y), _lib.dptr(U), *args), 'sssm_horizon_error')
+    ok = int(counts[0] - counts[1] - counts[2])
+
+    def rms(s, dim):
+        return np.sqrt(s / (ok * dim)) if ok > 0 else np.full(H + 1, np.nan)
+
+    def none(a):                                                # no status-0 window: no maximum
+        return np.where(a < 0, np.nan, a)
+
+    out = SSMHorizonError(H, dt, int(counts[0]), int(counts[1]), int(counts[2]), sse[0].copy(), rms(sse[0], n_x), none(worst[0]), at[0].copy(),
+                          sse[1].copy(), rms(sse[1], n_o), none(worst[1]), at[1].copy())
+    if per_window:
+        out.final_x, out.final_z, out.status = fin[0].copy(), fin[1].copy(), status
+    out.x_pred, out.z_pred, out.x_obs = xp, zp, xo
+    return out
